@@ -21,7 +21,7 @@ gate for gate), TFHE default 128-bit parameters (n=630, N=1024, k=1, l=3, Bg=2^7
 `--mode auto` (default) = match at --gpus 1, sharded at --gpus N > 1, so that the driver's
 `bench.py --gpus N` measures the split north_star names: ONE curve, "scaling": "strong" -- its N = 1
 point is one rank holding every slot, which is the reference's unsplit Function_f (the line says so);
-`weak_scaling` (independent matches per GPU) rides beside it at every N.
+`weak_scaling` (independent matches per GPU) rides beside it at every N under `--full`.
 
 Inputs (probe, template, threshold ciphertexts) and the evaluation keys are resident in HBM
 before the timed region.  Prints ONE JSON line on rank 0.  `value` counts executed blind
@@ -39,6 +39,13 @@ bus id, the collectives run and their issue order, the transport and why).
 This file: argument parsing, the timed region, the CPU baseline, the JSON line.  benchkit/: the roofline models and committed
 counter summaries (roofline.py), the launcher, the transport negotiation and the evidence (launch.py), the untimed extra
 workloads of the single-GPU line (extras.py) -- nothing in there runs inside the timed region.
+
+A plain run sets up, warms up, times --steps steps and prints the line; `ms_per_step` is one timed step.  Everything else
+runs only with `--full`: the decrypted check of the last timed step's result, the CPU baseline, the untimed extra workloads
+(--gpus 1, --mode match) and, at N > 1 in mode sharded, the weak-scaling and reference-order-combine legs.
+`--dump-outputs DIR` writes the ciphertext words the last timed step returned (what a caller of the path receives) as
+DIR/<mode>_result_words.npy: float64 holding the u32 torus words, one row per ciphertext.  Keys and inputs are seeded, so the
+same arguments give the same words on every run and build.
 """
 import argparse
 import ctypes
@@ -138,6 +145,24 @@ def cpu_baseline(seed):
                     "parity oracle.  exact_port_value = the parity oracle (exact two-prime NTT, scalar C)."}
 
 
+def sample_words(L, lib, pp, ptr, count):
+    """The words of `count` samples at a bare LweSample pointer (the result arrays of the sharded match), [count, words]."""
+    import numpy as np
+    out = np.zeros((count, pp.words), dtype=np.int32)
+    if L.tfhe_hip_export_samples(ctypes.cast(ptr, lib.LS), count, pp.ptr, out.ctypes.data_as(lib.I32P)) != 0:
+        raise RuntimeError(f"tfhe_hip_export_samples: {L.tfhe_hip_last_error().decode()}")
+    return out
+
+
+def dump_outputs(directory, name, words):
+    """--dump-outputs: the u32 torus words as float64 (exact), so that two builds can be compared word for word."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arr = np.ascontiguousarray(words, dtype=np.int32).view(np.uint32).astype(np.float64)
+    assert arr.nbytes <= 64 << 20, f"{name}: {arr.nbytes} bytes"
+    np.save(os.path.join(directory, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -157,17 +182,17 @@ def main():
     ap.add_argument("--matches", type=int, default=8, help="--mode identify: matches per GPU and step (configs[3]: 128)")
     ap.add_argument("--group", type=int, default=4, help="--mode identify: matches recorded per flush")
     ap.add_argument("--weak-matches", type=int, default=8,
-                    help="--gpus N > 1, --mode sharded: after the timed (strong-scaling) steps every rank also runs this many "
+                    help="--full, --gpus N > 1, --mode sharded: after the timed (strong-scaling) steps every rank also runs this many "
                          "independent matches of its own (--group per flush; BASELINE configs[3]) -- timed on its own, reported "
                          "as `weak_scaling` beside the strong curve; 0 = skip")
     ap.add_argument("--reference-combine-leg", type=int, default=1,
-                    help="--gpus N > 1, --mode sharded without --ripple-combine: also time ONE match with the reference-order "
+                    help="--full, --gpus N > 1, --mode sharded without --ripple-combine: also time ONE match with the reference-order "
                          "combine on rank 0 (SURVEY 8e's ADDN tree + minimum), reported as `reference_order_combine`; 0 = skip")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="diagnostic: no HIP events around the launches (the roofline block is then empty): what the events cost")
     ap.add_argument("--extras", type=int, default=1,
-                    help="at --gpus 1 --mode match: also run the untimed extra workloads (gate sharing, batched "
+                    help="--full at --gpus 1 --mode match: also run the untimed extra workloads (gate sharing, batched "
                          "matches, 256-slot match, Hamming, optimised DAG); 0 = skip")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group even at world size 1 (exercises the N>1 code path)")
@@ -179,7 +204,16 @@ def main():
                     help="nccl (= RCCL, one GPU per rank; the default and what the driver runs) or gloo: the exchange "
                          "goes through host buffers and every rank uses GPU `LOCAL_RANK mod device count`, so the N>1 "
                          "logic can be rehearsed with several processes on ONE GPU (tests do; never a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the check of the last timed result, the CPU baseline "
+                         "(unless --no-cpu-baseline), the extra workloads (unless --extras 0) and the N > 1 legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the ciphertext words of the last timed step's result as DIR/<mode>_result_words.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher: THIS process becomes the launcher and nothing else -- it has not
@@ -280,6 +314,9 @@ def main():
             if use_dist and rank == 0:
                 assert (all_bits.words()[0] == last.words()[0]).all(), "gathered match-bit ciphertext differs"
             return "decrypted match bit of the last timed match == plaintext rule (distance > bound)"
+
+        def result_words(last):
+            return last.words()
         workload = (f"Function_f: {nslots} slots x {bitsize} bit template match per GPU, every recorded gate executed")
         parallelism, scaling = f"1 match per GPU x {world}", "weak"
         if args.mode == "auto":
@@ -328,6 +365,9 @@ def main():
             bit = L.bootsSymDecrypt(C.cast(last, lib.LS), ks.ptr)
             assert bit == plain_bit(tmpl_vals), f"sharded match bit {bit}"
             return "decrypted match bit of the last timed sharded match == plaintext rule (distance > bound)"
+
+        def result_words(last):
+            return None if last is None else sample_words(L, lib, pp, last, pd.PARTIAL_BITS)
         workload = (f"slot-sharded Function_f: ONE {nslots} slots x {bitsize} bit match, slots partitioned over "
                     f"{nranks} {'ranks' if use_dist else 'logical ranks on one device'}, one gather of 24-ciphertext "
                     f"partial sums, {'ripple-adder tree + bit-serial comparator' if args.ripple_combine else 'carry-save compressor + prefix adder + prefix comparator'} on rank 0"
@@ -349,6 +389,9 @@ def main():
             got = [int(b) for b in last.decrypt(ks)]
             assert got == [plain_bit(t) for t in tv], f"rank {rank}: identification bits {got}"
             return f"all {M} decrypted match bits per GPU == plaintext rule; the genuine template is the only 0"
+
+        def result_words(last):
+            return last.words()
         workload = (f"1-to-N identification: probe against {M} independent {nslots} slots x {bitsize} bit templates per GPU "
                     f"(Function_f each, {args.group} recorded per flush)")
         parallelism, scaling = f"{M} matches per GPU x {world}", "weak"
@@ -379,14 +422,16 @@ def main():
         rr = torch.tensor([rotations_all], dtype=torch.float64, device=xdev)
         dist.all_reduce(rr, op=dist.ReduceOp.SUM)
         rotations_all = float(rr.item())
-    checked = check(last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, f"{mode}_result_words", result_words(last))
+    checked = check(last) if args.full else "nothing (--full checks the decrypted result of the last timed step)"
 
     # N > 1: the other way the path shards -- independent matches per GPU (1-to-N identification, BASELINE configs[3];
     # /root/reference/src/main.cpp:533-542 once per enrolled client), no data-path collective, only the match bits are
     # gathered.  Untimed by the contract (the timed steps above are the strong-scaling split north_star names), timed on
     # its own like the single-GPU extras, so that ONE line per N carries both curves.
     weak = None
-    if use_dist and mode == "sharded" and args.weak_matches > 0:
+    if args.full and use_dist and mode == "sharded" and args.weak_matches > 0:
         weak = weak_scaling_leg(api, circuits, identify, dist, torch, pp, ks, probe, bound, base, bitsize, rank, world,
                                 args.weak_matches, args.group, xdev, plain_bit, comm)
 
@@ -394,7 +439,7 @@ def main():
     # (the pairwise tree of the reference's ripple adders ADDN(23) + its bit-serial comparator minimum(24), the DAG the
     # golden digests pin) -- timed on its own, so that the line says what the reference's own combine costs at this N
     ref_combine = None
-    if use_dist and mode == "sharded" and not args.ripple_combine and args.reference_combine_leg:
+    if args.full and use_dist and mode == "sharded" and not args.ripple_combine and args.reference_combine_leg:
         sync()
         api.reset_stats()
         tr = time.perf_counter()
@@ -508,7 +553,7 @@ def main():
             out["reference_order_combine"] = ref_combine
         if evidence is not None:
             out["dist"] = evidence
-        if world == 1 and mode == "match" and args.extras > 0:
+        if args.full and world == 1 and mode == "match" and args.extras > 0:
             out.update(extras(api, circuits, identify, lib, pd, pp, ks, probe, tmpl, bound, base, probe_vals, bitsize,
                               plain_bit, last))
             # the N = 1 point of the weak-scaling curve the N > 1 lines carry: independent matches on the one GPU
@@ -517,7 +562,7 @@ def main():
             out["weak_scaling"] = {"gates_per_s_all_ranks": i4["gates_per_s"], "per_gpu": i4["gates_per_s"], "matches_per_gpu": 4,
                                    "group": 4, "seconds": i4["seconds"], "n_gpus": 1,
                                    "note": "independent matches per GPU (1-to-N identification, configs[3]); every recorded gate executed"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             api.set_deferred(False)
             out["cpu_baseline"] = cpu_baseline(seed)
         else:

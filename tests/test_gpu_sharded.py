@@ -438,7 +438,7 @@ def test_bench_fallback_transport_moves_the_same_ciphertexts():
     contact with several GPUs happens in the driver's run, not here): the library's host transport carried by the torch
     group's collectives on DEVICE tensors.  Rehearsed over gloo (two ranks cannot share one GPU under RCCL); the same checks
     as the default rehearsal -- match bit, rotation counts, gathered match bits, both combines."""
-    out = _torchrun(2, ["bench.py", "--gpus", "2", "--backend", "gloo", "--transport", "torch", "--steps", "1", "--warmup", "0",
+    out = _torchrun(2, ["bench.py", "--gpus", "2", "--backend", "gloo", "--transport", "torch", "--steps", "1", "--warmup", "0", "--full",
                         "--slots", "8", "--no-cpu-baseline"], 29645)
     j = _check_rehearsal_line(out, transport="torch.distributed device tensors")
     assert j["dist"]["transport_fallback_reason"] == "--transport torch"
@@ -456,7 +456,7 @@ def test_bench_launches_its_own_ranks_when_called_without_a_launcher():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PEBA1_ROOT"] = ROOT
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--backend", "gloo", "--steps", "1", "--warmup", "0",
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--backend", "gloo", "--steps", "1", "--warmup", "0", "--full",
                           "--slots", "8", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=400, cwd=ROOT)
     j = _check_rehearsal_line(out, world=4)
     assert out.stdout.rstrip().splitlines()[-1].startswith("{")           # the line is the LAST thing on stdout
@@ -478,7 +478,7 @@ def test_bench_tries_its_own_communicator_in_a_child_process_first(hang):
     env.update(MASTER_PORT="29671", PEBA1_BENCH_TRIAL_BUDGET_S="12" if hang else "150")
     if hang:
         env["PEBA1_BENCH_TRIAL_HANG"] = "1"
-    out = subprocess.run([sys.executable, "bench.py", "--mode", "sharded", "--force-dist", "--steps", "1", "--warmup", "0", "--slots", "8",
+    out = subprocess.run([sys.executable, "bench.py", "--mode", "sharded", "--force-dist", "--steps", "1", "--warmup", "0", "--full", "--slots", "8",
                           "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=400, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

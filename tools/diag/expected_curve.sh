@@ -27,7 +27,7 @@ for n in (1, 2, 4, 8):
         row.append("%7.0f + %5.0f = %7.0f ms (%.2fx)" % (max(p["partial_ms_per_rank"]), p["combine_ms"], t, base[form] / t))
     print("%5d  %s      %s" % (n, row[0], row[1]))
 PY
-timeout -k 10 400 python bench.py --gpus 4 --backend gloo --steps 2 --warmup 1 --no-cpu-baseline > $O/rehearsal_4_processes_gloo.json 2> $O/rehearsal_4.err || { tail -5 $O/rehearsal_4.err; exit 1; }
+timeout -k 10 400 python bench.py --gpus 4 --backend gloo --steps 2 --warmup 1 --full --no-cpu-baseline > $O/rehearsal_4_processes_gloo.json 2> $O/rehearsal_4.err || { tail -5 $O/rehearsal_4.err; exit 1; }
 python3 -c "
 import json; j=json.loads(open('$O/rehearsal_4_processes_gloo.json').read().strip().split('\n')[-1]); d=j['dist']
 print('rehearsal, 4 processes on one GPU over gloo: world', d['world'], 'collectives', d['data_collectives'], 'status', d['status_word_collectives'], 'same issue order', d['same_issue_order_on_every_rank'], 'kernel in roofline', j['roofline']['valu_issue']['kernel'])"

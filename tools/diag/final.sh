@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests -m gpu -q -x --durations=6 -p no:cacheprovider > $OUT/tests.log 2>&1; rc=$?
 tail -10 $OUT/tests.log; echo "pytest rc $rc"; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 150 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - <<PY
 import json
 j = json.loads(open("$OUT/bench.json").read().strip().split("\n")[-1])
