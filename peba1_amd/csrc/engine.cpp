@@ -469,7 +469,6 @@ SlotPool *Engine::pool_for(const Params &p) {
     // 288 GB of HBM -- eight 128-slot matches recorded while the eight of the flush in flight are still pinned
     size_t cap = 1u << 22;
     if (const char *env = std::getenv("TFHE_HIP_POOL_SLOTS")) cap = (size_t)std::atoll(env);
-    // slot ids are packed into 29-bit fields by the recorder's table of pending gates (shim.cpp gate_key)
     if (cap < 8 || cap > MAX_POOL_SLOTS) {
         set_error("TFHE_HIP_POOL_SLOTS out of range [8, 2^29]; clamped");
         cap = cap < 8 ? 8 : MAX_POOL_SLOTS;
@@ -642,57 +641,86 @@ bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const Rot
     return false;
 }
 
+// The key-switch launch rule, one place for launch_ks and for execute()'s sizing of the partial sums: a launch of `count`
+// gates runs in chunks of at most KS_CHUNK gates when tiled (bounds the partial-sum buffer: 0.66 GB at P128), each chunk of
+// cnt gates in ks_splits(cnt) coefficient ranges.  Tiles of 24 or 32 gates exist in the index form only (kernels.hip
+// keyswitch_index_kernel); tile 0 = per-gate kernel only.
+constexpr int KS_CHUNK = 8192;
+static int ks_tile_size(const Engine &e) { return (e.ks_tile > 16 && !e.ks_index) ? 16 : e.ks_tile; }
+
+// the tiled kernel: wide launches, ranges of at most 64 input coefficients
+static bool ks_tiled(const Engine &e, int count, const DevParams &dp) {
+    const int tile = ks_tile_size(e);
+    return tile > 0 && count >= 2 * tile && dp.ks_t == 8 && dp.ks_basebit == 2 && e.ks_max_splits > 1 &&
+           (dp.k * dp.N + e.ks_max_splits - 1) / e.ks_max_splits <= 64;
+}
+
+static int ks_splits(const Engine &e, int cnt, const DevParams &dp) {
+    int splits = 1;
+    if (ks_tiled(e, cnt, dp)) {
+        // the number of coefficient ranges is free between nin/64 and ks_max_splits: take the
+        // one whose grid (tiles x ranges) fills whole rounds of the workgroups the chip holds,
+        // e.g. 36 tiles x 28 ranges = 1008 of 1024 slots in two rounds instead of 36 x 32 = 1152 in three
+        const int tile = ks_tile_size(e);
+        const int threads = ((dp.ct_stride / 4 + 63) / 64) * 64;
+        // index form: no LDS strips; 120 VGPRs at tile 16 (four waves per SIMD), 162 at 24 (three), 204 at 32 (two);
+        // strip form: ~235 VGPRs (two waves per SIMD) and 16 x threads x 16 bytes of strips
+        int per_cu = std::max(1, (tile == 16 ? 16 : tile == 24 ? 12 : 8) / (threads / 64));
+        if (!e.ks_index) {
+            const size_t lds = (size_t)16 * threads * 16 + (size_t)tile * 65 * 4;
+            per_cu = std::max(1, std::min((int)((160 * 1024) / lds), 8 / (threads / 64)));
+        }
+        const long long slots = (long long)e.cu_count() * per_cu;
+        const long long tiles = (cnt + tile - 1) / tile;
+        const int lo = std::max(2, (dp.k * dp.N + 63) / 64);
+        double best = -1.0;
+        for (int sp = lo; sp <= e.ks_max_splits; ++sp) {
+            const long long blocks = tiles * sp, rounds = (blocks + slots - 1) / slots;
+            const double eff = (double)blocks / (double)(rounds * slots);
+            // ties: fewer, longer ranges (less partial-sum traffic) or more, shorter ones (ks_split_ties)
+            if (e.ks_split_ties ? eff >= best - 1e-9 : eff > best + 1e-9) { best = eff; splits = sp; }
+        }
+    } else {
+        // narrow launches: doubling may pass ks_max_splits once (up to 64)
+        while (splits < e.ks_max_splits && cnt * splits * 2 <= e.ks_target_blocks) splits *= 2;
+    }
+    return splits;
+}
+
+// the largest key-switch partial-sum buffer a launch of `count` gates uses
+static size_t ks_partial_bytes(const Engine &e, int count, const DevParams &dp) {
+    size_t most = 0;
+    const int chunk = ks_tiled(e, count, dp) ? KS_CHUNK : count;
+    for (int done = 0; done < count; done += chunk) {
+        const int cnt = std::min(chunk, count - done), splits = ks_splits(e, cnt, dp);
+        if (splits > 1) most = std::max(most, (size_t)cnt * splits * dp.ct_stride * 4);
+    }
+    return most;
+}
+
 void Engine::launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
                        hipStream_t stream) {
     ENGINE_DEVICE_SCOPE();
     if (count <= 0) return;
     if (!stream) stream = stream_;
     const DevParams &dp = key->dp;
-    const int nin = dp.k * dp.N;
-    // tiles of 24 or 32 gates exist in the index form only (kernels.hip keyswitch_index_kernel)
-    const int ks_tile = (this->ks_tile > 16 && !ks_index) ? 16 : this->ks_tile;
-    // tiled kernel: wide launches, ranges of at most 64 input coefficients
-    const bool tiled = ks_tile > 0 && count >= 2 * ks_tile && dp.ks_t == 8 && dp.ks_basebit == 2 && ks_max_splits > 1 &&
-                       (nin + ks_max_splits - 1) / ks_max_splits <= 64;
-    const int chunk = tiled ? 8192 : count;              // bounds the partial-sum buffer (0.66 GB at P128)
+    const size_t bytes = ks_partial_bytes(*this, count, dp);
+    if (in_execute_ && bytes > (scratch_size_.size() > 10 ? scratch_size_[10] : 0))
+        fatal("launch_ks: the key-switch partial sums were not sized by execute()");
+    int32_t *partial = bytes ? static_cast<int32_t *>(scratch(10, bytes)) : nullptr;
+    const bool tiled = ks_tiled(*this, count, dp);
+    const int chunk = tiled ? KS_CHUNK : count;
     for (int done = 0; done < count; done += chunk) {
-        const int cnt = std::min(chunk, count - done);
-        int splits = 1;
-        if (tiled && cnt >= 2 * ks_tile) {
-            // the number of coefficient ranges is free between nin/64 and ks_max_splits: take the
-            // one whose grid (tiles x ranges) fills whole rounds of the workgroups the chip holds,
-            // e.g. 36 tiles x 28 ranges = 1008 of 1024 slots in two rounds instead of 36 x 32 = 1152 in three
-            const int threads = ((dp.ct_stride / 4 + 63) / 64) * 64;
-            // index form: no LDS strips; 120 VGPRs at tile 16 (four waves per SIMD), 162 at 24 (three), 204 at 32 (two);
-            // strip form: ~235 VGPRs (two waves per SIMD) and 16 x threads x 16 bytes of strips
-            int per_cu = std::max(1, (ks_tile == 16 ? 16 : ks_tile == 24 ? 12 : 8) / (threads / 64));
-            if (!ks_index) {
-                const size_t lds = (size_t)16 * threads * 16 + (size_t)ks_tile * 65 * 4;
-                per_cu = std::max(1, std::min((int)((160 * 1024) / lds), 8 / (threads / 64)));
-            }
-            const long long slots = (long long)cu_count_ * per_cu;
-            const long long tiles = (cnt + ks_tile - 1) / ks_tile;
-            const int lo = std::max(2, (nin + 63) / 64);
-            double best = -1.0;
-            for (int sp = lo; sp <= ks_max_splits; ++sp) {
-                const long long blocks = tiles * sp, rounds = (blocks + slots - 1) / slots;
-                const double eff = (double)blocks / (double)(rounds * slots);
-                // ties: fewer, longer ranges (less partial-sum traffic) or more, shorter ones (ks_split_ties)
-                if (ks_split_ties ? eff >= best - 1e-9 : eff > best + 1e-9) { best = eff; splits = sp; }
-            }
-        } else {
-            while (splits < ks_max_splits && cnt * splits * 2 <= ks_target_blocks) splits *= 2;
-        }
-        int32_t *partial = nullptr;
-        if (splits > 1) partial = static_cast<int32_t *>(scratch(10, (size_t)cnt * splits * dp.ct_stride * 4));
-        launch_keyswitch(stream, dp, key->key, u_buf, descs + done, cnt, pool, splits, partial, tiled ? ks_tile : 0, ks_index != 0);
+        const int cnt = std::min(chunk, count - done), splits = ks_splits(*this, cnt, dp);
+        launch_keyswitch(stream, dp, key->key, u_buf, descs + done, cnt, pool, splits, splits > 1 ? partial : nullptr,
+                         tiled ? ks_tile_size(*this) : 0, ks_index != 0);
     }
 }
 
 // wait = false: the launches are enqueued and the call returns; the flush is "in flight" until wait_flight() (called by
 // the next execute() before it touches the descriptor buffers, by every host read of a slot, by the statistics).  The
 // host work of the NEXT flush -- recording, dead-gate elimination, levelling, building its plan -- then overlaps this
-// one's execution (shim.cpp flush_locked).
+// one's execution (recorder.cpp flush_locked).
 void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan_in, bool wait) {
     ENGINE_DEVICE_SCOPE();
     wait_flight();                                   // at most one flush in flight: its descriptors and scratch are in use
@@ -700,13 +728,16 @@ void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan
     // Every device buffer of the flush is sized here, before anything is enqueued and before the plan changes hands:
     // scratch() may reallocate, which must not happen under a running launch -- and it may throw (out of device memory:
     // recoverable_alloc), in which case nothing has run, the caller's recorded gates are still pending and its flush
-    // returns -1 (shim.cpp flush_locked releases nothing before this call returns)
+    // returns -1 (recorder.cpp flush_locked releases nothing of the flush before this call returns)
     RotDesc *drots = static_cast<RotDesc *>(scratch(0, plan_in.rots.size() * sizeof(RotDesc) + 16));
     KsDesc *dks = static_cast<KsDesc *>(scratch(1, plan_in.kss.size() * sizeof(KsDesc) + 16));
     NotDesc *dnots = static_cast<NotDesc *>(scratch(2, plan_in.nots.size() * sizeof(NotDesc) + 16));
-    // extract buffer and key-switch partial sums, sized for the widest level
+    // extract buffer, sized for the widest level, and key-switch partial sums, sized by the split rule launch_ks applies
     int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)(plan_in.max_rots + 1) * key->dp.u_stride * 4));
-    (void)scratch(10, (size_t)std::min(plan_in.max_rots + 1, 8192) * ks_max_splits * key->dp.ct_stride * 4);
+    size_t partial = 0;
+    for (int g = 0; g < plan_in.levels; ++g)
+        partial = std::max(partial, ks_partial_bytes(*this, plan_in.ks_off[g + 1] - plan_in.ks_off[g], key->dp));
+    if (partial) (void)scratch(10, partial);
     flight_plan_ = std::move(plan_in);               // owns the host descriptors until the uploads have certainly happened
     const LevelPlan &plan = flight_plan_;
     const int levels = plan.levels;
@@ -729,6 +760,7 @@ void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan
         timed.reserve((size_t)levels + 1);
     }
     hipEvent_t shared_end = nullptr;
+    in_execute_ = true;
     for (int L = 0; L <= levels; ++L) {
         const size_t gg = L > 0 ? (size_t)(L - 1) : 0;       // gate index
         const int nrot = L > 0 ? plan.rot_off[gg + 1] - plan.rot_off[gg] : 0;
@@ -745,9 +777,7 @@ void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan
             shared_end = nullptr;
         }
         if (nrot) {
-            in_execute_ = true;
             t.wide8 = launch_br(key, pool->data(), drots + plan.rot_off[gg], nrot, u_buf, nullptr, stream_);
-            in_execute_ = false;
             if (t.wide8) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)nrot; }
             if (tail_count_) {                       // a second launch, of the 8-wave kernel
                 t.em = tail_event_;
@@ -768,6 +798,7 @@ void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan
         stats.linear_ops += (uint64_t)nnot;
         if (nrot) ++stats.br_launches;
     }
+    in_execute_ = false;
     if (const char *trace = std::getenv("TFHE_HIP_TRACE_LEVELS")) {   // diagnostic: rotations per level
         if (FILE *f = std::fopen(trace, "a")) {
             std::fprintf(f, "flush levels=%d lanes=1\n", levels);

@@ -48,7 +48,7 @@ void set_alloc_cap(long long bytes);
 // Pool of device-resident ciphertext slots (ct_stride words each).  Slots are
 // immutable once written (the recorder renames every destination), reference
 // counted, and recycled through a free list.
-// slot ids must fit the 29-bit fields of the recorder's pending-gate keys (shim.cpp gate_key)
+// the most slots a pool may hold (TFHE_HIP_POOL_SLOTS is clamped to it)
 constexpr size_t MAX_POOL_SLOTS = (size_t)1 << 29;
 
 class SlotPool {
@@ -167,7 +167,7 @@ public:
     // of at most 7 bits; split form: stage 0, and the first radix-4 step too where digits have at most 6
     // bits); 2 = split form: stage 0 only; 0 = multiplies (env TFHE_HIP_BR_TABLE, tuning "br_digit_table")
     int br_digit_table = 1;
-    // stream == nullptr: the engine's stream
+    // stream == nullptr: the engine's stream; inside execute() the partial sums never grow (checked)
     void launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
                    hipStream_t stream = nullptr);
     // returns true when the launch used the 8-wave form
@@ -186,7 +186,7 @@ private:
     void note_async_io();
     hipEvent_t io_event_ = nullptr;                     // behind the last stream-ordered transfer that returned without a wait
     bool io_pending_ = false;
-    bool in_execute_ = false;                           // launch_br called for a level of execute(): the tail event has a reader
+    bool in_execute_ = false;                           // launches of execute()'s levels: the tail event has a reader
     hipEvent_t tail_event_ = nullptr;                   // set by launch_br when it split a level (kernel_timing only)
     int tail_count_ = 0;
     std::vector<Timed> flight_timed_;

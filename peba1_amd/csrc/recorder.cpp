@@ -1,0 +1,384 @@
+// recorder.cpp -- see recorder.hpp.  Host logic only: no gate arithmetic happens here.
+#include "recorder.hpp"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "scheduler.hpp"
+
+namespace tfhe_hip {
+namespace {
+
+// truth tables of the two-input gates, index [gate code][2 a + b] (enum TfheHipGate; GATE_LIN's signs say the same)
+const uint8_t GATE_TT[10][4] = {
+    {1, 1, 1, 0}, {0, 1, 1, 1}, {0, 0, 0, 1}, {1, 0, 0, 0}, {0, 1, 1, 0}, {1, 0, 0, 1},
+    {0, 1, 0, 0}, {0, 0, 1, 0}, {1, 1, 0, 1}, {1, 0, 1, 1},
+};
+
+// a pending op by what it computes: kind and operand slots (-1 = absent)
+struct OpKey {
+    int32_t kind, a, b, c;
+    bool operator==(const OpKey &o) const { return kind == o.kind && a == o.a && b == o.b && c == o.c; }
+};
+struct OpKeyHash {
+    size_t operator()(const OpKey &k) const {
+        uint64_t h = ((uint64_t)(uint32_t)k.a << 32 | (uint32_t)k.b) * 0x9E3779B97F4A7C15ull;
+        h ^= ((uint64_t)(uint32_t)k.c << 8 | (uint32_t)k.kind) * 0xC2B2AE3D27D4EB4Full;
+        return (size_t)(h ^ (h >> 29));
+    }
+};
+// symmetric two-input gates (sa == sb in GATE_LIN: t = c0 + s (A + B)) are keyed with ordered operands
+OpKey op_key(int kind, int32_t a, int32_t b, int32_t c) {
+    if (kind < OP_MUX && GATE_LIN[kind].sa == GATE_LIN[kind].sb && b < a) std::swap(a, b);
+    return OpKey{kind, a, b, c};
+}
+
+struct Recorder {
+    std::recursive_mutex mtx;
+    // Default: deferred.  The reference (and any caller that stays inside the tfhe C API) never reads a field of LweSample
+    // -- results are only ever observed through bootsSymDecrypt or an export, and both run the pending gates first -- so
+    // recording is transparent to it and is what lets an UNMODIFIED caller run at batch throughput (one gate per launch is
+    // 3.4 ms: 290 gates/s).  TFHE_HIP_DEFERRED=0 / tfhe_hip_set_deferred(0) restores strict per-call completion with the
+    // host mirror (a, b) refreshed on return, as upstream's own struct has it.
+    bool deferred = true;
+    const TFheGateBootstrappingCloudKeySet *key = nullptr;   // key of the pending operations
+    SlotPool *pool = nullptr;
+    std::vector<PendingOp> ops;
+    int32_t max_level = 0;
+    bool balance_levels = true;   // slack-aware level filling (scheduler.hpp)
+    // operations of a flush launched without waiting (tfhe_hip_flush_async): released when it is complete
+    std::vector<PendingOp> flight_ops;
+    SlotPool *flight_pool = nullptr;
+    // Pending ops by (kind, operand slots): an op recorded again with the same operands before the flush is the same
+    // function of the same ciphertexts, so its result slot is shared instead of evaluated twice (the reference's circuits
+    // do this 12,545 times per match, mostly AND / XOR against the shared constant samples).  Results are unchanged.
+    bool reuse_gates = true;
+    std::unordered_map<OpKey, int32_t, OpKeyHash> index;   // key -> result slot (reuse_gates only)
+    std::unordered_map<int32_t, int32_t> not_origin;       // pending NOT output slot -> its operand slot
+    // Dead-gate elimination at flush: an op whose destination slot is held by nothing but the op's own pending reference
+    // -- every handle that pointed at it was re-pointed or freed, no live op reads it -- can never be observed, so it is
+    // dropped (and with it, transitively, what only it read).  The reference's ripple adders compute a carry out of their
+    // last bit and drop it (Math.cpp:60-64 into a freed temporary): 5 of the 7 gates of that bit, ~55 gates per slot.
+    bool eliminate_dead = true;
+    // Constant folding at record time (round 6; OPT-IN: tuning "fold_constants", env TFHE_HIP_FOLD_CONSTANTS).  A trivial
+    // sample -- bootsCONSTANT, a fresh sample, a copy of either -- is a PUBLIC constant, and a gate with such an operand
+    // needs no bootstrap to be evaluated: its result is a constant, the other operand, or its negation (linear); a MUX with
+    // a constant data operand is a two-input gate.  The reference's circuits are full of them (zero-padded partial products,
+    // adders fed with constant zeros: 62 % of the 215,544 gates of a 128-slot Function_f).  Decrypted results are the
+    // same; the CIPHERTEXTS are not what TFHE produces (it bootstraps every gate whatever its operands), which is why this is
+    // off by default -- the drop-in's contract is TFHE's words.  The oracle's provider folds by the same rule
+    // (oracle/boots_oracle.c orc_boots_set_fold), so folded circuits have oracle digests of their own.
+    bool fold_constants = false;
+};
+Recorder &rec() {
+    static Recorder r;
+    static bool init = [] {
+        if (const char *e = std::getenv("TFHE_HIP_DEFERRED")) r.deferred = std::atoi(e) != 0;
+        if (const char *e = std::getenv("TFHE_HIP_FOLD_CONSTANTS")) r.fold_constants = std::atoi(e) != 0;   // opt-in (Recorder)
+        return true;
+    }();
+    (void)init;
+    return r;
+}
+
+void release_refs(SlotPool *pool, const PendingOp &op) {    // the pending references an op holds
+    for (const int32_t s : {op.dst, op.a, op.b, op.c})
+        if (s >= 0) pool->release(s);
+}
+
+void begin_op(const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    if (r.key && r.key != bk && !r.ops.empty()) flush_locked();
+    r.key = bk;
+    r.pool = pool_of_key(bk);
+    // pending operations pin their slots until they run: flush before the pool runs dry, so
+    // arbitrarily long recordings need only bounded device memory
+    if (!r.ops.empty() && r.pool->capacity() - r.pool->in_use() < 4096) flush_locked();
+}
+
+void finish_op(LweSample *result) {
+    if (!rec().deferred) {
+        flush_locked();
+        sync_sample_locked(result);   // immediate mode: host mirror valid on return, as upstream
+    }
+}
+
+// result becomes (a handle of) `slot`: a COPY
+void point_at(LweSample *result, SlotPool *pool, int32_t slot) {
+    pool->retain(slot);
+    repoint(result, pool, slot);
+    finish_op(result);
+}
+
+// 0 / 1 if `slot` is one of the pool's shared trivial samples (a public constant), else -1
+int const_bit(const SlotPool *pool, int32_t slot) { return slot == pool->const_slot[0] ? 0 : slot == pool->const_slot[1] ? 1 : -1; }
+
+// The one record path: share the result of a pending op that computes the same (kind, a, b, c), else append the op.
+// Two-input gates: c = -1; NOT: b = c = -1.
+void record_op(int kind, LweSample *result, SlotPool *pool, const int32_t a, const int32_t b, const int32_t c) {
+    Recorder &r = rec();
+    const OpKey key = op_key(kind, a, b, c);
+    if (r.reuse_gates) {
+        auto it = r.index.find(key);
+        if (it != r.index.end()) {
+            ++Engine::get().stats.reused_gates;
+            return point_at(result, pool, it->second);
+        }
+    }
+    const int32_t dst = alloc_slot(pool);     // may flush: levels are read after it
+    int32_t level = 0;
+    for (const int32_t s : {a, b, c})
+        if (s >= 0) { level = std::max(level, pool->level[s]); pool->retain(s); }   // and the pending references
+    if (kind != OP_NOT) ++level;              // a NOT is linear: it rides on its operand's level
+    pool->level[dst] = level;
+    pool->pending[dst] = 1;                   // pending even at level 0 (NOT of a materialised sample)
+    pool->retain(dst);
+    r.ops.push_back(PendingOp{(uint8_t)kind, dst, a, b, c, level});
+    if (r.reuse_gates) r.index.emplace(key, dst);
+    if (kind == OP_NOT) r.not_origin.emplace(dst, a);
+    r.max_level = std::max(r.max_level, level);
+    repoint(result, pool, dst);
+    finish_op(result);
+}
+
+// Recorder::eliminate_dead.  An op is dropped with its index and NOT-origin entries (recorder.hpp: the invariant).
+void eliminate_dead_ops() {
+    Recorder &r = rec();
+    SlotPool *pool = r.pool;
+    // reverse recording order = reverse topological order: dropping a consumer first lets its producers die too
+    size_t dead = 0;
+    std::vector<uint8_t> is_dead(r.ops.size(), 0);
+    for (size_t i = r.ops.size(); i-- > 0;) {
+        const PendingOp &op = r.ops[i];
+        if (pool->refs(op.dst) != 1) continue;          // a handle or a live operation still holds the result
+        auto it = r.index.find(op_key(op.kind, op.a, op.b, op.c));
+        if (it != r.index.end() && it->second == op.dst) r.index.erase(it);
+        if (op.kind == OP_NOT) r.not_origin.erase(op.dst);
+        pool->level[op.dst] = 0;
+        pool->pending[op.dst] = 0;
+        release_refs(pool, op);
+        is_dead[i] = 1;
+        ++dead;
+    }
+    if (!dead) return;
+    size_t w = 0;
+    int32_t depth = 0;
+    for (size_t i = 0; i < r.ops.size(); ++i)
+        if (!is_dead[i]) { depth = std::max(depth, r.ops[i].level); r.ops[w++] = r.ops[i]; }
+    r.ops.resize(w);
+    r.max_level = depth;
+    Engine::get().stats.dead_gates += dead;
+}
+
+}  // namespace
+
+std::unique_lock<std::recursive_mutex> recorder_lock() { return std::unique_lock<std::recursive_mutex>(rec().mtx); }
+
+SlotPool *pool_of_key(const TFheGateBootstrappingCloudKeySet *bk) {
+    if (!bk || !bk->bk) api_fail("null cloud key");
+    // keysets made host-only or loaded from a file get their device image at first use
+    // (aborts with a clear message when there is no GPU: gates are never evaluated on the CPU)
+    if (!bk->bk->dev) bk->bk->dev = Engine::get().upload_key(*bk->bk);
+    return Engine::get().pool_for(bk->bk->p);
+}
+
+// a fresh slot; when the pool is dry, the pending operations (which pin their operands and
+// results) are run first.  Throws ApiError if that frees nothing.
+int32_t alloc_slot(SlotPool *pool) {
+    Recorder &r = rec();
+    if (pool->in_use() == pool->capacity()) {
+        finish_flight_locked();                          // a completed asynchronous flush still pins its slots
+        if (pool->in_use() == pool->capacity() && !r.ops.empty() && r.pool == pool) flush_locked();
+    }
+    return pool->alloc();
+}
+
+int32_t ensure_slot(const LweSample *cs, SlotPool *pool) {
+    auto *s = const_cast<LweSample *>(cs);
+    bind_pool(cs, pool);
+    if (s->slot >= 0) return s->slot;
+    if (s->slot == SLOT_ZERO) {
+        pool->retain(pool->const_slot[0]);
+        s->slot = pool->const_slot[0];
+        return s->slot;
+    }
+    const int32_t slot = alloc_slot(pool);
+    Engine::get().write_slot(pool, slot, s->a, s->b);
+    s->slot = slot;
+    return slot;
+}
+
+void repoint(LweSample *s, SlotPool *pool, int32_t slot) {
+    bind_pool(s, pool);
+    if (s->slot >= 0) pool->release(s->slot);
+    s->slot = slot;
+}
+
+void sync_sample_locked(const LweSample *cs) {
+    Recorder &r = rec();
+    auto *s = const_cast<LweSample *>(cs);
+    if (s->slot < 0) return;                       // host mirror is authoritative (fresh: trivial 0)
+    SlotPool *pool = pool_of_sample(s);
+    // pending = written by a recorded operation that has not run (a gate, or a NOT riding on
+    // level 0 of an already materialised operand)
+    if (pool->pending[s->slot] && !r.ops.empty()) flush_locked();
+    Engine::get().read_slot(pool, s->slot, s->a, &s->b);
+}
+
+void record_gate2_locked(int code, LweSample *result, const LweSample *ca, const LweSample *cb,
+                         const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    begin_op(bk);
+    SlotPool *pool = r.pool;
+    bind_pool(result, pool);                  // refuse a foreign / mismatched result before anything changes
+    const int32_t sa = ensure_slot(ca, pool), sb = ensure_slot(cb, pool);
+    if (r.fold_constants) {
+        const int ka = const_bit(pool, sa), kb = const_bit(pool, sb);
+        if (ka >= 0 || kb >= 0) {
+            // the gate as a function of its non-constant operand x: f(0), f(1)
+            const uint8_t *tt = GATE_TT[code];
+            const int f0 = ka >= 0 ? tt[2 * ka + (kb >= 0 ? kb : 0)] : tt[kb];
+            const int f1 = ka >= 0 ? tt[2 * ka + (kb >= 0 ? kb : 1)] : tt[2 + kb];
+            ++Engine::get().stats.folded_gates;
+            if (f0 == f1) return point_at(result, pool, pool->const_slot[f0]);          // a constant
+            if (f0 == 0) return point_at(result, pool, ka >= 0 ? sb : sa);                // x itself
+            return record_not_locked(result, ka >= 0 ? cb : ca, bk);                      // NOT x: linear, no bootstrap
+        }
+    }
+    record_op(code, result, pool, sa, sb, -1);
+}
+
+void record_not_locked(LweSample *result, const LweSample *ca, const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    begin_op(bk);
+    SlotPool *pool = r.pool;
+    bind_pool(result, pool);
+    const int32_t sa = ensure_slot(ca, pool);
+    if (r.fold_constants && const_bit(pool, sa) >= 0)             // NOT of a public constant is the other constant
+        return point_at(result, pool, pool->const_slot[1 - const_bit(pool, sa)]);
+    // NOT of a still-pending NOT: -(-x) = x exactly, so alias the original operand; two NOTs
+    // of one level would otherwise sit in the same launch and race
+    auto it = r.not_origin.find(sa);
+    if (it != r.not_origin.end()) return point_at(result, pool, it->second);
+    record_op(OP_NOT, result, pool, sa, -1, -1);
+}
+
+void record_mux_locked(LweSample *result, const LweSample *a, const LweSample *b, const LweSample *c,
+                       const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    begin_op(bk);
+    SlotPool *pool = r.pool;
+    bind_pool(result, pool);
+    const int32_t sa = ensure_slot(a, pool), sb = ensure_slot(b, pool), sc = ensure_slot(c, pool);
+    if (r.fold_constants) {
+        const int ka = const_bit(pool, sa), kb = const_bit(pool, sb), kc = const_bit(pool, sc);
+        if (ka >= 0 || kb >= 0 || kc >= 0 || sb == sc) {
+            ++Engine::get().stats.folded_gates;
+            if (ka >= 0) return point_at(result, pool, ka ? sb : sc);                     // a constant selector picks an operand
+            if (sb == sc) return point_at(result, pool, sb);                                // both data operands the same sample
+            if (kb >= 0 && kc >= 0) {                                                       // (kb != kc here)  MUX(a, 1, 0) = a, MUX(a, 0, 1) = NOT a
+                if (kb == 1) return point_at(result, pool, sa);
+                return record_not_locked(result, a, bk);
+            }
+            // one constant data operand: a two-input gate, one blind rotation instead of two
+            if (kc >= 0) return record_gate2_locked(kc == 0 ? TFHE_HIP_AND : TFHE_HIP_ORNY, result, a, b, bk);   // a & b | !a | b
+            return record_gate2_locked(kb == 0 ? TFHE_HIP_ANDNY : TFHE_HIP_OR, result, a, c, bk);               // !a & c | a | c
+        }
+    }
+    record_op(OP_MUX, result, pool, sa, sb, sc);
+}
+
+void record_constant_locked(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    begin_op(bk);
+    bind_pool(result, r.pool);          // refuse before anything changes
+    const int32_t s = r.pool->const_slot[value ? 1 : 0];
+    r.pool->retain(s);
+    repoint(result, r.pool, s);
+    if (!r.deferred) {   // keep the host mirror exact without a device round trip
+        std::memset(result->a, 0, (size_t)bk->params->in_out_params->n * sizeof(Torus32));
+        result->b = value ? (1 << 29) : -(1 << 29);
+    }
+}
+
+void record_copy_locked(LweSample *result, const LweSample *ca, const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    begin_op(bk);
+    if (result == ca) return;
+    bind_pool(result, r.pool);
+    const int32_t s = ensure_slot(ca, r.pool);
+    r.pool->retain(s);
+    repoint(result, r.pool, s);
+    if (!r.deferred) sync_sample_locked(result);
+}
+
+void finish_flight_locked() {
+    Recorder &r = rec();
+    Engine::get().wait_flight();
+    for (const PendingOp &op : r.flight_ops) release_refs(r.flight_pool, op);
+    r.flight_ops.clear();
+    r.flight_pool = nullptr;
+}
+
+int flush_locked(bool wait) {
+    Recorder &r = rec();
+    if (!r.ops.empty() && r.eliminate_dead) eliminate_dead_ops();
+    if (r.ops.empty()) { r.max_level = 0; if (wait) finish_flight_locked(); return 0; }
+    SlotPool *pool = r.pool;
+    // level of every op: ASAP, or slack-aware balanced (same depth, fuller narrow levels)
+    std::vector<int32_t> lvl, alap;
+    const int levels = schedule_levels(r.ops, r.max_level, r.balance_levels, Engine::get().cu_count(), lvl, &alap);
+    if (const char *trace = std::getenv("TFHE_HIP_TRACE_DAG")) {      // diagnostic: per op "kind asap alap level dst a b c" (slots)
+        if (FILE *f = std::fopen(trace, "w")) {
+            for (size_t i = 0; i < r.ops.size(); ++i)
+                std::fprintf(f, "%d %d %d %d %d %d %d %d\n", (int)r.ops[i].kind, r.ops[i].level, alap[i], lvl[i],
+                             r.ops[i].dst, r.ops[i].a, r.ops[i].b, r.ops[i].c);
+            std::fclose(f);
+        }
+    }
+    LevelPlan plan = build_level_plan(r.ops, lvl, levels);
+    // everything above -- elimination, levelling, the plan -- ran while the device was busy with the previous asynchronous
+    // flush, if any; execute() would wait for it first anyway
+    finish_flight_locked();
+    Engine::get().execute(r.key->bk->dev, pool, std::move(plan), wait);    // throws before anything runs, or runs it all
+    for (const PendingOp &op : r.ops) {
+        pool->level[op.dst] = 0;          // a later recording reads these slots as inputs: the stream orders it behind
+        pool->pending[op.dst] = 0;
+        if (wait) release_refs(pool, op);
+    }
+    if (!wait) { r.flight_ops.swap(r.ops); r.flight_pool = pool; }
+    r.ops.clear();
+    r.index.clear();
+    r.not_origin.clear();
+    r.max_level = 0;
+    return levels;
+}
+
+void flush_pending_locked(bool wait) { if (!rec().ops.empty()) flush_locked(wait); }
+
+void forget_key_locked(const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    if (r.key == bk) { flush_locked(); r.key = nullptr; }
+}
+
+bool deferred_mode() { return rec().deferred; }
+
+bool set_deferred_locked(bool on) { return std::exchange(rec().deferred, on); }
+
+bool set_recorder_tuning_locked(const char *name, bool on) {
+    Recorder &r = rec();
+    bool *knob = std::strcmp(name, "reuse_gates") == 0      ? &r.reuse_gates
+                 : std::strcmp(name, "eliminate_dead") == 0 ? &r.eliminate_dead
+                 : std::strcmp(name, "fold_constants") == 0 ? &r.fold_constants
+                 : std::strcmp(name, "balance_levels") == 0 ? &r.balance_levels
+                                                            : nullptr;
+    if (knob) *knob = on;
+    return knob != nullptr;
+}
+
+}  // namespace tfhe_hip

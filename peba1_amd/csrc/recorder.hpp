@@ -1,0 +1,60 @@
+// recorder.hpp -- the deferred gate recorder behind the boots* entries (recorder.cpp).  Host logic only.
+//
+// Every ciphertext value lives in an immutable device slot.  A boots* call allocates a fresh destination slot, records an
+// op that reads its operands' CURRENT slots, and re-points the destination handle to the new slot (SSA renaming): safe
+// under deferral for a result aliasing an input (Math.cpp:272), a temporary overwritten four times (Math.cpp:34-42),
+// temporaries freed right after use (Math.cpp:47-49).  An op's level is 1 + the maximum level of its operand slots; a
+// flush executes level 1, 2, ... as batched kernel launches.  bootsCOPY and bootsCONSTANT only re-point handles.
+//
+// Every op is recorded through one path (record_op) and looked up in ONE index keyed by (kind, a, b, c): a hit shares the
+// pending result, a miss appends the op.  Invariant: every entry of the index and of the NOT-origin table names the
+// destination of an op still recorded.  Dead-gate elimination drops an op's entries in the loop that drops the op, and a
+// successful flush clears both tables with the ops, so a flush refused for want of device memory can be retried.
+//
+// Every function here expects the recorder lock (recorder_lock()) to be held.
+#pragma once
+#include <cstdint>
+#include <mutex>
+
+#include "engine.hpp"
+#include "../../include/tfhe/tfhe.h"
+
+namespace tfhe_hip {
+#pragma GCC visibility push(hidden)   // library-internal: the exported surface is the C ABI
+
+constexpr int32_t SLOT_HOST = -1;   // LweSample::slot: the value lives in the host mirror
+constexpr int32_t SLOT_ZERO = -2;   // fresh sample: trivial encryption of bit 0, (0, -1/8)
+
+// provided by shim.cpp (the array headers): bind the sample's array to `pool` on first device use; the pool it is bound to
+void bind_pool(const LweSample *sample, SlotPool *pool);
+SlotPool *pool_of_sample(const LweSample *sample);
+
+std::unique_lock<std::recursive_mutex> recorder_lock();
+SlotPool *pool_of_key(const TFheGateBootstrappingCloudKeySet *bk);   // uploads the key image at first use
+
+// recording (each refuses a foreign result sample before anything changes)
+void record_gate2_locked(int code, LweSample *result, const LweSample *a, const LweSample *b,
+                         const TFheGateBootstrappingCloudKeySet *bk);
+void record_not_locked(LweSample *result, const LweSample *a, const TFheGateBootstrappingCloudKeySet *bk);
+void record_mux_locked(LweSample *result, const LweSample *a, const LweSample *b, const LweSample *c,
+                       const TFheGateBootstrappingCloudKeySet *bk);
+void record_constant_locked(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk);
+void record_copy_locked(LweSample *result, const LweSample *a, const TFheGateBootstrappingCloudKeySet *bk);
+
+int32_t alloc_slot(SlotPool *pool);                          // may flush when the pool is dry
+int32_t ensure_slot(const LweSample *s, SlotPool *pool);     // a device slot holding the sample's current value
+void repoint(LweSample *s, SlotPool *pool, int32_t slot);    // `slot` already retained for the handle
+void sync_sample_locked(const LweSample *s);                 // host mirror := current value (flushes if pending)
+
+// levelise, build the plan, execute, release; wait = false leaves the launches in flight (tfhe_hip_flush_async).  Returns
+// the number of levels; throws ApiError, with nothing run and everything still recorded, when the scratch cannot be had.
+int flush_locked(bool wait = true);
+void flush_pending_locked(bool wait = true);   // flush_locked if anything is recorded
+void finish_flight_locked();                   // the asynchronous flush (if any) is complete: wait, release what it pinned
+void forget_key_locked(const TFheGateBootstrappingCloudKeySet *bk);   // a key about to be deleted: run what it recorded
+bool deferred_mode();
+bool set_deferred_locked(bool on);                          // returns the previous mode
+bool set_recorder_tuning_locked(const char *name, bool on); // reuse_gates, eliminate_dead, fold_constants, balance_levels
+#pragma GCC visibility pop
+
+}  // namespace tfhe_hip

@@ -1,6 +1,8 @@
 // scheduler.cpp -- see scheduler.hpp.  Host logic only.
 #include "scheduler.hpp"
 
+#include "engine.hpp"
+
 #include <algorithm>
 #include <queue>
 #include <unordered_map>
@@ -141,6 +143,56 @@ int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool bala
         for (int32_t i : batch) release_successors(i, L, release_successors);
     }
     return asap_depth;
+}
+
+LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<int32_t> &lvl, int levels) {
+    LevelPlan plan;
+    plan.levels = levels;
+    // counting sort by level: gates of level L (1-based) in group L - 1, NOTs riding on level L (0 = inputs) in group L
+    plan.rot_off.assign((size_t)levels + 1, 0);
+    plan.ks_off.assign((size_t)levels + 1, 0);
+    plan.not_off.assign((size_t)levels + 2, 0);
+    for (size_t i = 0; i < ops.size(); ++i) {
+        if (ops[i].kind == OP_NOT) { ++plan.not_off[(size_t)lvl[i] + 1]; continue; }
+        plan.rot_off[(size_t)lvl[i]] += op_rotations(ops[i]);
+        ++plan.ks_off[(size_t)lvl[i]];
+    }
+    plan.max_rots = 0;
+    for (size_t g = 0; g < (size_t)levels; ++g) {
+        plan.max_rots = std::max(plan.max_rots, plan.rot_off[g + 1]);
+        plan.rot_off[g + 1] += plan.rot_off[g];
+        plan.ks_off[g + 1] += plan.ks_off[g];
+    }
+    for (size_t g = 0; g <= (size_t)levels; ++g) plan.not_off[g + 1] += plan.not_off[g];
+    plan.rots.resize(plan.rot_off.back());
+    plan.kss.resize(plan.ks_off.back());
+    plan.nots.resize(plan.not_off.back());
+    std::vector<int32_t> rpos(plan.rot_off.begin(), plan.rot_off.end() - 1);   // cursor per group
+    std::vector<int32_t> kpos(plan.ks_off.begin(), plan.ks_off.end() - 1);
+    std::vector<int32_t> npos(plan.not_off.begin(), plan.not_off.end() - 1);
+    const int32_t mu = 1 << 29;
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const PendingOp &op = ops[i];
+        if (op.kind == OP_NOT) {
+            plan.nots[npos[(size_t)lvl[i]]++] = NotDesc{op.a, op.dst};
+            continue;
+        }
+        const size_t g = (size_t)(lvl[i] - 1);
+        const int32_t base = plan.rot_off[g];
+        if (op.kind == OP_MUX) {
+            // tfhe bootsMUX: u1 = BR(-1/8 + a + b), u2 = BR(-1/8 - a + c), KS(u1 + u2 + 1/8)
+            const int32_t i0 = rpos[g]++, i1 = rpos[g]++;
+            plan.rots[i0] = RotDesc{op.a, op.b, 1, 1, -(mu), i0 - base};
+            plan.rots[i1] = RotDesc{op.a, op.c, -1, 1, -(mu), i1 - base};
+            plan.kss[kpos[g]++] = KsDesc{i0 - base, i1 - base, mu, op.dst};
+        } else {
+            const GateLin &gl = GATE_LIN[op.kind];
+            const int32_t i0 = rpos[g]++;
+            plan.rots[i0] = RotDesc{op.a, op.b, gl.sa, gl.sb, gl.c8 * mu, i0 - base};
+            plan.kss[kpos[g]++] = KsDesc{i0 - base, -1, 0, op.dst};
+        }
+    }
+    return plan;
 }
 
 }  // namespace tfhe_hip

@@ -24,6 +24,13 @@ constexpr uint8_t OP_MUX = 16, OP_NOT = 17;
 
 inline int op_rotations(const PendingOp &op) { return op.kind == OP_NOT ? 0 : (op.kind == OP_MUX ? 2 : 1); }
 
+// prelude constants of the two-input gates: (c0 in eighths, sa, sb), tfhe boot-gates.cpp
+struct GateLin { int32_t c8, sa, sb; };
+constexpr GateLin GATE_LIN[10] = {
+    {1, -1, -1}, {1, 1, 1}, {-1, 1, 1}, {-1, -1, -1}, {2, 2, 2}, {-2, -2, -2},
+    {-1, -1, 1}, {-1, 1, -1}, {1, -1, 1}, {1, 1, -1},
+};
+
 // Fills lvl[i] with the level at which ops[i] runs (bootstrapped gates: 1..depth,
 // NOTs: 0..depth, executed after the gates of that level).  `unit` = rotations one
 // full pass of the latency kernel holds (the CU count); levels are filled to 1, 2
@@ -33,5 +40,9 @@ inline int op_rotations(const PendingOp &op) { return op.kind == OP_NOT ? 0 : (o
 int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool balance, int unit,
                     std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out = nullptr);
 
+// The descriptors of a flush (engine.hpp): ops[i] runs at level lvl[i] (schedule_levels), levels in all.
+struct LevelPlan;
+__attribute__((visibility("hidden"))) LevelPlan build_level_plan(const std::vector<PendingOp> &ops,
+                                                                 const std::vector<int32_t> &lvl, int levels);
 
 }  // namespace tfhe_hip

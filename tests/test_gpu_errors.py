@@ -217,6 +217,44 @@ L.tfhe_hip_test_set_alloc_cap(0)
 L.tfhe_hip_clear_error()
 assert api.flush() >= 1 and L.tfhe_hip_last_error().decode() == ""
 assert (r.decrypt(ks) == (xa & xb)).all()
+# (1b) a refused flush with dead gates pending: elimination has released their result slots, which the next gates of the
+# retry get again (the pool's free list is LIFO).  Recording the same gates again must not share those freed slots, and a
+# NOT of a gate that got a dead NOT's slot must not be aliased to that NOT's operand.
+K = 8
+w = api.CiphertextArray(pp, G)                                 # with r: a level twice as wide as (1)'s, so its scratch must grow
+dead2, deadmux, deadnot, notnot = (api.CiphertextArray(pp, K) for _ in range(4))
+for i in range(G):
+    L.bootsXOR(r.at(i), a.at(i), b.at(i), ks.cloud)
+    L.bootsOR(w.at(i), a.at(i), b.at(i), ks.cloud)
+def record_dying():
+    for j in range(K):
+        L.bootsNAND(dead2.at(j), a.at(j), b.at(j), ks.cloud)
+        L.bootsMUX(deadmux.at(j), a.at(j), b.at(j), b.at(j + 1), ks.cloud)
+        L.bootsNOT(deadnot.at(j), a.at(j), ks.cloud)
+        L.bootsNOT(notnot.at(j), deadnot.at(j), ks.cloud)         # NOT of a pending NOT: aliases a[j]
+record_dying()
+for arr in (dead2, deadmux, deadnot):                          # overwritten before the flush: the gates above are dead
+    for j in range(K):
+        L.bootsCONSTANT(arr.at(j), 0, ks.cloud)
+L.tfhe_hip_test_set_alloc_cap(64 << 20)
+assert api.flush() == -1
+record_dying()                                                 # the same gates again
+fresh, freshnot = api.CiphertextArray(pp, 3 * K), api.CiphertextArray(pp, 3 * K)
+for j in range(3 * K):                                         # as many new, distinct gates as died
+    L.bootsANDYN(fresh.at(j), a.at(K + j), b.at(2 * K + j), ks.cloud)
+    L.bootsNOT(freshnot.at(j), fresh.at(j), ks.cloud)
+L.tfhe_hip_test_set_alloc_cap(0)
+L.tfhe_hip_clear_error()
+assert api.flush() >= 1 and L.tfhe_hip_last_error().decode() == ""
+xs, xs1 = xa[:K], xb[1:K + 1]
+assert (r.decrypt(ks) == (xa ^ xb)).all() and (w.decrypt(ks) == (xa | xb)).all()
+assert (dead2.decrypt(ks) == 1 - (xa[:K] & xb[:K])).all()
+assert (deadmux.decrypt(ks) == np.where(xs == 1, xb[:K], xs1)).all()
+assert (deadnot.decrypt(ks) == 1 - xs).all() and (notnot.decrypt(ks) == xs).all()
+want_fresh = xa[K:4 * K] & (1 - xb[2 * K:5 * K])
+assert (fresh.decrypt(ks) == want_fresh).all() and (freshnot.decrypt(ks) == 1 - want_fresh).all()
+for arr in (w, dead2, deadmux, deadnot, notnot, fresh, freshnot):
+    arr.close()
 # (2) the slot pool's growth (it starts at 65,536 slots): the gate that needs slot 65,537 is refused and has no effect;
 # with the cap lifted the same call works and every gate recorded before it still evaluates
 L.tfhe_hip_test_set_alloc_cap(1 << 20)
