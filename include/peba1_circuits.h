@@ -96,6 +96,22 @@ void peba1_hamming_distance(LweSample *count, LweSample *a, LweSample *b, int nb
 void peba1_hamming_match(LweSample *result_b, LweSample *a, LweSample *b, int nbits, LweSample *bound_match,
                          const TFheGateBootstrappingCloudKeySet *ck);
 
+/* ---- multi-client batches: K clients' matches, client c under its own cloud key ck[c] (all of one parameter set),
+ * recorded with libtfhe-hip's multi-key flushes ("batch_keys", include/tfhe_hip.h) and deferred mode on, then run as ONE
+ * flush; the caller's two settings are restored.  The server entry for many enrolled users: the K circuits fill the levels
+ * of one flush instead of running as K narrow flushes.  Client c's results are the words its own single-client call
+ * produces.  Return the flush's level count (< 0 on error; 0 over a provider without libtfhe-hip's extensions, which
+ * evaluates call by call). ---- */
+/* Function_f per client: result_b[c] (3*bitsize samples), a[c] / b[c] (nslots sample arrays each), bound_match[c];
+ * fast != 0: peba1_function_f_fast's DAG */
+int peba1_function_f_batch(LweSample *const *result_b, LweSample *const *const *a, LweSample *const *const *b, int nclients,
+                           int nslots, LweSample *const *bound_match, int bitsize,
+                           const TFheGateBootstrappingCloudKeySet *const *ck, int fast);
+/* peba1_hamming_match per client: result_b[c] / bound_match[c] (peba1_hamming_count_bits(nbits) samples), a[c] / b[c]
+ * (nbits samples) */
+int peba1_hamming_match_batch(LweSample *const *result_b, LweSample *const *a, LweSample *const *b, int nclients, int nbits,
+                              LweSample *const *bound_match, const TFheGateBootstrappingCloudKeySet *const *ck);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,7 +147,7 @@ void tfhe_hip_set_diag_label(const char *label);
 int tfhe_hip_gate_batch(int gate, LweSample *result, const LweSample *a, const LweSample *b,
                         int32_t count, const TFheGateBootstrappingCloudKeySet *bk);
 
-/* ---- tuning (ten names that results never depend on, and the opt-in "fold_constants") ----
+/* ---- tuning (eleven names that results never depend on, and the opt-in "fold_constants") ----
  * "br_variant": which form of the blind-rotate kernel runs wide launches (env TFHE_HIP_BR_VARIANT): -1 (default) =
  * the fastest measured for the ring size (N = 1024: 4 waves per rotation; N = 2048: split), 0 = 4 waves (N = 1024),
  * 2 = split (8 waves, every transform as two half-size ones), 4 = 2 waves (N = 1024; the form with the widest admissible
@@ -178,6 +178,12 @@ int tfhe_hip_gate_batch(int gate, LweSample *result, const LweSample *a, const L
  * a two-input gate.  The reference's match circuit loses 62 % of its bootstraps that way.  Decrypted results are the same;
  * the ciphertext WORDS are not TFHE's (which bootstraps every gate), which is why it is off unless asked for -- the only
  * tuning results depend on.  The oracle folds by the same rule (orc_boots_set_fold): folded circuits have digests too.
+ * "batch_keys": 0 (default) / 1 (env TFHE_HIP_BATCH_KEYS) = OPT-IN multi-key flushes: gates recorded under different cloud
+ * keys of the SAME parameter set stay recorded together and run as one level sequence (one flush), each bootstrap and key
+ * switch under its own gate's key -- a server's K clients fill the levels of one flush instead of running as K narrow
+ * flushes.  0: a gate under another key than the pending gates' flushes them first.  A key of another parameter set
+ * flushes either way.  The words are the same as with 0; every key of such a flush stays alive until it has run (deleting
+ * a keyset runs the whole recording first).
  * "sync_deadline_ms": see "bounded host waits" above.
  * (Environment only: TFHE_HIP_KS_BLOCKS / TFHE_HIP_KS_MAX_SPLITS / TFHE_HIP_KS_SPLIT_TIES, how key switches are cut into
  * coefficient ranges -- engine.hpp.)
@@ -219,6 +225,10 @@ void tfhe_hip_get_stats(TfheHipStats *out);
 void tfhe_hip_reset_stats(void);
 /* when on, every kernel launch is bracketed by HIP events, read back after the flush */
 void tfhe_hip_set_kernel_timing(int on);
+/* distinct cloud keys the last executed flush ran under (1 unless "batch_keys" is on; 0 before the first flush) */
+int tfhe_hip_last_flush_keys(void);
+/* "batch_keys" := on (0 / 1); returns the previous setting (so that a caller can restore it) */
+int tfhe_hip_set_batch_keys(int on);
 
 /* ---- host-logic test entry: does blind-rotate kernel form `form` (0 = 4 waves, 1 = split, 2 = 8 waves, 3 = 2 waves)
  * keep its magnitude bounds for gadget (l, Bgbit) at ring size N with digit-table mode

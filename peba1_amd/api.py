@@ -273,6 +273,11 @@ def stats():
     return {f: getattr(s, f) for f, _ in s._fields_}
 
 
+def last_flush_keys():
+    """Distinct cloud keys the last executed flush ran under (tuning "batch_keys")."""
+    return _l.load().tfhe_hip_last_flush_keys()
+
+
 def reset_stats():
     _l.load().tfhe_hip_reset_stats()
 

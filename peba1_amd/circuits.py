@@ -45,6 +45,11 @@ def load():
             f = getattr(Lc, name)
             f.restype = None
             f.argtypes = args
+        Lc.peba1_function_f_batch.restype = C.c_int
+        Lc.peba1_function_f_batch.argtypes = [LSP, C.POINTER(LSP), C.POINTER(LSP), C.c_int, C.c_int, LSP, C.c_int,
+                                              C.POINTER(CK), C.c_int]
+        Lc.peba1_hamming_match_batch.restype = C.c_int
+        Lc.peba1_hamming_match_batch.argtypes = [LSP, LSP, LSP, C.c_int, C.c_int, LSP, C.POINTER(CK)]
         Lc.peba1_hamming_count_bits.restype = C.c_int
         Lc.peba1_hamming_count_bits.argtypes = [C.c_int]
         _circ = Lc
@@ -135,3 +140,39 @@ def hamming_distance(count, a, b, nbits, key):
 
 def hamming_count_bits(nbits):
     return load().peba1_hamming_count_bits(nbits)
+
+
+def _cloud_array(keys):
+    arr = (_l.CK * len(keys))()
+    for i, k in enumerate(keys):
+        arr[i] = k.cloud
+    return arr
+
+
+def function_f_batch(results_b, samples, templates, bounds, bitsize, keys, fast=False):
+    """Function_f for K clients in ONE flush, client c under its own key keys[c] (peba1_function_f_batch: multi-key
+    flushes, include/tfhe_hip.h "batch_keys").  Lists of K each; returns the flush's level count."""
+    k = len(keys)
+    assert len(results_b) == len(samples) == len(templates) == len(bounds) == k
+    nslots = len(samples[0].slots)
+    assert all(len(s.slots) == nslots and len(t.slots) == nslots for s, t in zip(samples, templates))
+    sa = [_ptr_array(s.slots) for s in samples]
+    ta = [_ptr_array(t.slots) for t in templates]
+    LSP = C.POINTER(_l.LS)
+    sp, tp = (LSP * k)(*[C.cast(x, LSP) for x in sa]), (LSP * k)(*[C.cast(x, LSP) for x in ta])
+    rc = load().peba1_function_f_batch(_ptr_array(results_b), sp, tp, k, nslots, _ptr_array(bounds), bitsize,
+                                       _cloud_array(keys), 1 if fast else 0)
+    if rc < 0:
+        raise RuntimeError(api.last_error())
+    return rc
+
+
+def hamming_match_batch(results_b, a, b, nbits, bounds, keys):
+    """peba1_hamming_match for K clients in ONE flush, client c under keys[c]; returns the flush's level count."""
+    k = len(keys)
+    assert len(results_b) == len(a) == len(b) == len(bounds) == k
+    rc = load().peba1_hamming_match_batch(_ptr_array(results_b), _ptr_array(a), _ptr_array(b), k, nbits,
+                                          _ptr_array(bounds), _cloud_array(keys))
+    if rc < 0:
+        raise RuntimeError(api.last_error())
+    return rc

@@ -42,6 +42,33 @@ void copy_bits(LweSample *dst, const LweSample *src, int count, CK *ck) {
 
 }  // namespace
 
+// libtfhe-hip's extensions used by the batch drivers: weak, so that the library still links and runs over any provider of
+// the plain tfhe API (the tests' plaintext mock), where a batch is simply recorded and evaluated call by call
+extern "C" {
+__attribute__((weak)) int tfhe_hip_set_batch_keys(int on);
+__attribute__((weak)) int tfhe_hip_get_deferred(void);
+__attribute__((weak)) void tfhe_hip_set_deferred(int on);
+__attribute__((weak)) int tfhe_hip_flush(void);
+}
+
+namespace {
+
+// K clients' circuits recorded back to back with multi-key flushes ("batch_keys") and deferred mode on, then run as ONE
+// flush; the caller's settings are restored.  Returns the flush's level count (0 without libtfhe-hip, < 0 on error).
+template <typename Record>
+int record_batch(int nclients, Record &&record) {
+    const int had_batch = tfhe_hip_set_batch_keys ? tfhe_hip_set_batch_keys(1) : 0;
+    const int had_deferred = tfhe_hip_get_deferred && tfhe_hip_set_deferred ? tfhe_hip_get_deferred() : 1;
+    if (tfhe_hip_set_deferred) tfhe_hip_set_deferred(1);
+    for (int c = 0; c < nclients; ++c) record(c);
+    const int levels = tfhe_hip_flush ? tfhe_hip_flush() : 0;
+    if (tfhe_hip_set_deferred) tfhe_hip_set_deferred(had_deferred);
+    if (tfhe_hip_set_batch_keys) tfhe_hip_set_batch_keys(had_batch);
+    return levels;
+}
+
+}  // namespace
+
 extern "C" {
 
 // Math.cpp:27-50
@@ -277,6 +304,20 @@ void peba1_hamming_match(LweSample *result_b, LweSample *a, LweSample *b, int nb
     Tmp count(w, ck), smaller(w, ck);
     peba1_hamming_distance(count, a, b, nbits, ck);
     peba1_minimum(smaller, result_b, count, bound_match, w, ck);
+}
+
+// ---- K clients, each under its own cloud key, in one flush ----------------------------------------------------------------
+int peba1_function_f_batch(LweSample *const *result_b, LweSample *const *const *a, LweSample *const *const *b, int nclients,
+                           int nslots, LweSample *const *bound_match, int bitsize, CK *const *ck, int fast) {
+    return record_batch(nclients, [&](int c) {
+        if (fast) peba1_function_f_fast(result_b[c], a[c], b[c], nslots, bound_match[c], bitsize, ck[c]);
+        else peba1_function_f(result_b[c], a[c], b[c], nslots, bound_match[c], bitsize, ck[c]);
+    });
+}
+
+int peba1_hamming_match_batch(LweSample *const *result_b, LweSample *const *a, LweSample *const *b, int nclients, int nbits,
+                              LweSample *const *bound_match, CK *const *ck) {
+    return record_batch(nclients, [&](int c) { peba1_hamming_match(result_b[c], a[c], b[c], nbits, bound_match[c], ck[c]); });
 }
 
 }  // extern "C"

@@ -571,13 +571,8 @@ hipEvent_t Engine::next_timing_event() {
     return timing_events_[timing_used_++];
 }
 
-bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const RotDesc *rots, int count, int32_t *u_buf,
-                       int32_t *acc_dbg, hipStream_t stream) {
-    ENGINE_DEVICE_SCOPE();
-    if (!stream) stream = stream_;
-    tail_event_ = nullptr;                   // what an earlier launch left is not this one's
-    tail_count_ = 0;
-    DevParams dp = key->dp;
+int Engine::br_form(const DeviceKeyImage *key, int count, int *tables_out) const {
+    const DevParams &dp = key->dp;
     // the form the tunings ask for ...
     int form;
     if (br_variant == 4 && dp.N == 1024) form = BR_FORM_WAVE2;
@@ -603,6 +598,20 @@ bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const Rot
         if (pick_f < 0) fatal("no admissible blind-rotate form (upload_key should have refused this key)");
         form = pick_f; tables = pick_t;
     }
+    if (tables_out) *tables_out = tables;
+    return form;
+}
+
+bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const RotDesc *rots, int count, int32_t *u_buf,
+                       int32_t *acc_dbg, hipStream_t stream, const DevKey *mk_keys, const int32_t *mk_rot_keys) {
+    ENGINE_DEVICE_SCOPE();
+    if (!stream) stream = stream_;
+    tail_event_ = nullptr;                   // what an earlier launch left is not this one's
+    tail_count_ = 0;
+    DevParams dp = key->dp;
+    int tables = 0;
+    const int form = br_form(key, count, &tables);
+    if (mk_keys && form != BR_FORM_WIDE4 && form != BR_FORM_WAVE8) fatal("launch_br: no multi-key kernel for this form");
     dp.digit_table = tables;
     if (kernel_timing) {
         if (!clock_acc_) {
@@ -621,7 +630,8 @@ bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const Rot
     }
     dp.wg_times = wg_times_dbg_;
     if (form == BR_FORM_WAVE8) {
-        launch_blind_rotate8(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
+        if (mk_keys) launch_blind_rotate8_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count, u_buf);
+        else launch_blind_rotate8(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
         return true;
     }
     // the last, at most half-filled round of a wide launch on the 8-wave form (descriptors carry their own output
@@ -629,15 +639,19 @@ bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const Rot
     const int round = 2 * cu_count_, tail = count % round;
     if (br_tail8 && count > round && tail > 0 && tail <= std::min(br8_max_rotations, cu_count_) && dp.l >= 2 &&
         !acc_dbg && !wg_times_dbg_ && key->form_ok[BR_FORM_WAVE8][tables]) {
-        launch_blind_rotate4(stream, dp, key->key, pool, rots, count - tail, u_buf, nullptr);
+        if (mk_keys) launch_blind_rotate4_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count - tail, u_buf);
+        else launch_blind_rotate4(stream, dp, key->key, pool, rots, count - tail, u_buf, nullptr);
         tail_count_ = tail;
         // the event between the two launches belongs to execute()'s per-flush set (reset there); the raw test paths and
         // probes have no reader for it and must not grow the set
         if (kernel_timing && in_execute_) { tail_event_ = next_timing_event(); hip_check(hipEventRecord(tail_event_, stream), "event"); }
-        launch_blind_rotate8(stream, dp, key->key, pool, rots + (count - tail), tail, u_buf, nullptr);
+        if (mk_keys)
+            launch_blind_rotate8_mk(stream, dp, key->key, mk_keys, mk_rot_keys + (count - tail), pool, rots + (count - tail), tail, u_buf);
+        else launch_blind_rotate8(stream, dp, key->key, pool, rots + (count - tail), tail, u_buf, nullptr);
         return false;
     }
-    launch_blind_rotate4(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
+    if (mk_keys) launch_blind_rotate4_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count, u_buf);
+    else launch_blind_rotate4(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
     return false;
 }
 
@@ -721,10 +735,15 @@ void Engine::launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const Ks
 // the next execute() before it touches the descriptor buffers, by every host read of a slot, by the statistics).  The
 // host work of the NEXT flush -- recording, dead-gate elimination, levelling, building its plan -- then overlaps this
 // one's execution (recorder.cpp flush_locked).
-void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan_in, bool wait) {
+void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *pool, LevelPlan &&plan_in, bool wait) {
     ENGINE_DEVICE_SCOPE();
     wait_flight();                                   // at most one flush in flight: its descriptors and scratch are in use
     flight_t0_ = std::chrono::steady_clock::now();
+    // several keys (recorder "batch_keys"): all of one parameter set, so the descriptors, the extract buffer, the twiddles
+    // and the form rules are those of keys[0]; each rotation and each key switch runs under its own gate's key
+    const DeviceKeyImage *key = keys.at(0);
+    const int nkeys = plan_in.nkeys;
+    if (nkeys < 1 || (size_t)nkeys != keys.size()) fatal("execute: the plan's key count differs from the flush's key list");
     // Every device buffer of the flush is sized here, before anything is enqueued and before the plan changes hands:
     // scratch() may reallocate, which must not happen under a running launch -- and it may throw (out of device memory:
     // recoverable_alloc), in which case nothing has run, the caller's recorded gates are still pending and its flush
@@ -735,9 +754,23 @@ void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan
     // extract buffer, sized for the widest level, and key-switch partial sums, sized by the split rule launch_ks applies
     int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)(plan_in.max_rots + 1) * key->dp.u_stride * 4));
     size_t partial = 0;
-    for (int g = 0; g < plan_in.levels; ++g)
-        partial = std::max(partial, ks_partial_bytes(*this, plan_in.ks_off[g + 1] - plan_in.ks_off[g], key->dp));
+    if (nkeys == 1) {
+        for (int g = 0; g < plan_in.levels; ++g)
+            partial = std::max(partial, ks_partial_bytes(*this, plan_in.ks_off[g + 1] - plan_in.ks_off[g], key->dp));
+    } else {                                         // one key-switch launch per (level, key)
+        for (size_t sg = 0; sg + 1 < plan_in.ks_koff.size(); ++sg)
+            partial = std::max(partial, ks_partial_bytes(*this, plan_in.ks_koff[sg + 1] - plan_in.ks_koff[sg], key->dp));
+    }
     if (partial) (void)scratch(10, partial);
+    // the key table and the key index of every rotation
+    DevKey *dkeys = nullptr;
+    int32_t *drot_keys = nullptr;
+    if (nkeys > 1) {
+        dkeys = static_cast<DevKey *>(scratch(11, (size_t)nkeys * sizeof(DevKey)));
+        drot_keys = static_cast<int32_t *>(scratch(12, plan_in.rot_key.size() * sizeof(int32_t) + 16));
+        plan_in.dev_keys.resize((size_t)nkeys);
+        for (int k = 0; k < nkeys; ++k) plan_in.dev_keys[(size_t)k] = keys[(size_t)k]->key;
+    }
     flight_plan_ = std::move(plan_in);               // owns the host descriptors until the uploads have certainly happened
     const LevelPlan &plan = flight_plan_;
     const int levels = plan.levels;
@@ -747,6 +780,12 @@ void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan
         hip_check(hipMemcpyAsync(dks, plan.kss.data(), plan.kss.size() * sizeof(KsDesc), hipMemcpyHostToDevice, stream_), "upload ks");
     if (!plan.nots.empty())
         hip_check(hipMemcpyAsync(dnots, plan.nots.data(), plan.nots.size() * sizeof(NotDesc), hipMemcpyHostToDevice, stream_), "upload nots");
+    if (nkeys > 1) {
+        hip_check(hipMemcpyAsync(dkeys, plan.dev_keys.data(), plan.dev_keys.size() * sizeof(DevKey), hipMemcpyHostToDevice, stream_), "upload keys");
+        if (!plan.rot_key.empty())
+            hip_check(hipMemcpyAsync(drot_keys, plan.rot_key.data(), plan.rot_key.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "upload rot keys");
+    }
+    last_flush_keys = nkeys;
 
     timing_used_ = 0;                                    // timing events used: base, then 2-3 (one more with a tail launch) per level
     auto timing_event = [&]() { return next_timing_event(); };
@@ -776,7 +815,29 @@ void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan
             else { t.e0 = timing_event(); hip_check(hipEventRecord(t.e0, stream_), "event"); }
             shared_end = nullptr;
         }
-        if (nrot) {
+        if (nrot && nkeys > 1) {
+            // the form follows the level's total width (as for one key); forms without a multi-key kernel run one launch
+            // per key over that key's contiguous run of the level's rotations
+            const int form = br_form(key, nrot);
+            if (form == BR_FORM_WIDE4 || form == BR_FORM_WAVE8) {
+                t.wide8 = launch_br(key, pool->data(), drots + plan.rot_off[gg], nrot, u_buf, nullptr, stream_, dkeys,
+                                    drot_keys + plan.rot_off[gg]);
+            } else {
+                for (int k = 0; k < nkeys; ++k) {
+                    const size_t sg = gg * (size_t)nkeys + (size_t)k;
+                    const int n = plan.rot_koff[sg + 1] - plan.rot_koff[sg];
+                    if (n) launch_br(keys[(size_t)k], pool->data(), drots + plan.rot_koff[sg], n, u_buf, nullptr, stream_);
+                }
+                tail_count_ = 0;
+            }
+            if (t.wide8) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)nrot; }
+            if (tail_count_) {
+                t.em = tail_event_;
+                t.tail = tail_count_;
+                ++stats.br8_launches; ++stats.br_launches;
+                stats.br8_rotations += (uint64_t)tail_count_;
+            }
+        } else if (nrot) {
             t.wide8 = launch_br(key, pool->data(), drots + plan.rot_off[gg], nrot, u_buf, nullptr, stream_);
             if (t.wide8) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)nrot; }
             if (tail_count_) {                       // a second launch, of the 8-wave kernel
@@ -787,7 +848,15 @@ void Engine::execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan
             }
         }
         if (kernel_timing) { t.e1 = timing_event(); hip_check(hipEventRecord(t.e1, stream_), "event"); }
-        if (nks) launch_ks(key, u_buf, dks + plan.ks_off[gg], nks, pool->data(), stream_);
+        if (nks && nkeys > 1) {                      // one key-switch launch per key: the key-switch kernels are single-key
+            for (int k = 0; k < nkeys; ++k) {
+                const size_t sg = gg * (size_t)nkeys + (size_t)k;
+                const int n = plan.ks_koff[sg + 1] - plan.ks_koff[sg];
+                if (n) launch_ks(keys[(size_t)k], u_buf, dks + plan.ks_koff[sg], n, pool->data(), stream_);
+            }
+        } else if (nks) {
+            launch_ks(key, u_buf, dks + plan.ks_off[gg], nks, pool->data(), stream_);
+        }
         if (kernel_timing) {
             t.e2 = timing_event(); hip_check(hipEventRecord(t.e2, stream_), "event"); timed.push_back(t);
             if (nnot == 0) shared_end = t.e2;

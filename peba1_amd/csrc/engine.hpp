@@ -86,6 +86,12 @@ struct LevelPlan {
     std::vector<int32_t> rot_off, ks_off;   // size levels + 1; gates of level L (1-based): index L - 1
     std::vector<int32_t> not_off;           // size levels + 2; NOTs riding on level L (0 = inputs): index L
     int32_t max_rots = 0;                   // widest level (sizes the extract buffer)
+    // several cloud keys of one parameter set (recorder "batch_keys"; nkeys > 1 only): the key index of every rotation,
+    // and the descriptors of level L (1-based) under key k at [rot_koff / ks_koff][(L - 1) nkeys + k, ... + 1)
+    int nkeys = 1;
+    std::vector<int32_t> rot_key;
+    std::vector<int32_t> rot_koff, ks_koff;
+    std::vector<tfhe_hip::DevKey> dev_keys; // the key table execute() uploads (held until the upload has happened)
 };
 
 class Engine {
@@ -109,9 +115,11 @@ public:
     void write_slots_packed(SlotPool *pool, const int32_t *slots, int count, const Torus32 *words, bool words_on_device, bool wait = true);
     void read_slots_packed(SlotPool *pool, const int32_t *slots, int count, Torus32 *words, bool words_on_device, bool wait = true);
 
-    // run a levelised plan.  wait = true: synchronises the stream before returning; false: returns with the launches
-    // enqueued ("in flight") -- see engine.cpp
-    void execute(const DeviceKeyImage *key, SlotPool *pool, LevelPlan &&plan, bool wait = true);
+    // run a levelised plan under the flush's keys (plan.nkeys of them, all of one parameter set and resident; the plan's
+    // key indices refer to this list).  wait = true: synchronises the stream before returning; false: returns with the
+    // launches enqueued ("in flight") -- see engine.cpp
+    void execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *pool, LevelPlan &&plan, bool wait = true);
+    int last_flush_keys = 0;            // distinct cloud keys of the last flush executed (tfhe_hip_last_flush_keys)
     void wait_flight();                 // completes an asynchronous execute(): waits, then reads the timing events
     // host waits (engine.cpp "host waits"): bounded by sync_deadline_ms when that is set
     void sync_stream(const char *what); // everything enqueued on the engine's stream has completed
@@ -132,8 +140,8 @@ public:
 
     TfheHipStats stats{};
     bool kernel_timing = false;
-    // Tunings (tfhe_hip_set_tuning; ten names in all: these six, the recorder's reuse_gates / eliminate_dead /
-    // balance_levels, and sync_deadline_ms above).  HISTORY.md lists the forms and knobs removed in round 6.
+    // Tunings (tfhe_hip_set_tuning; these six, the recorder's reuse_gates / eliminate_dead / balance_levels / fold_constants /
+    // batch_keys, and sync_deadline_ms above).  HISTORY.md lists the forms and knobs removed in round 6.
     //
     // Key switches of a narrow launch are split (power of two <= ks_max_splits) until about ks_target_blocks workgroups
     // exist: beyond filling the chip, more splits mean the blocks in flight share a KSK sub-table small enough for an
@@ -170,9 +178,14 @@ public:
     // stream == nullptr: the engine's stream; inside execute() the partial sums never grow (checked)
     void launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
                    hipStream_t stream = nullptr);
-    // returns true when the launch used the 8-wave form
+    // returns true when the launch used the 8-wave form.  mk_keys / mk_rot_keys (device key table and per-rotation key
+    // indices of a multi-key level): the 4- and 8-wave forms run each rotation under its own key; only for those forms
+    // (br_form), and `key` is entry 0 of the table
     bool launch_br(const DeviceKeyImage *key, const int32_t *pool, const RotDesc *rots, int count, int32_t *u_buf,
-                   int32_t *acc_dbg, hipStream_t stream = nullptr);
+                   int32_t *acc_dbg, hipStream_t stream = nullptr, const DevKey *mk_keys = nullptr,
+                   const int32_t *mk_rot_keys = nullptr);
+    // the form launch_br runs `count` rotations of this key's parameter set on (BR_FORM_*), and its digit-table mode
+    int br_form(const DeviceKeyImage *key, int count, int *tables_out = nullptr) const;
     // diagnostic (tools/wg_times.py): ONE 4-wave blind-rotate launch of `width` random gates whose workgroups stamp s_memtime
     // and s_memrealtime at start and end into wg_times[4 * width]; returns that launch's event time in ms (< 0: no stamps)
     double run_wg_times(const DeviceKeyImage *key, int width, unsigned long long *wg_times);

@@ -63,6 +63,12 @@ void launch_blind_rotate4(hipStream_t s, const DevParams &p, const DevKey &key, 
 // 8-wave form (N = 1024, l >= 2) for launches of at most one workgroup per CU: a second wave per SIMD
 void launch_blind_rotate8(hipStream_t s, const DevParams &p, const DevKey &key, const int32_t *pool,
                           const RotDesc *rots, int count, int32_t *u_buf, int32_t *acc_dbg);
+// multi-key forms of the 4- and 8-wave launches (tuning "batch_keys"): rotation i runs under the key image
+// keys[rot_keys[i]].bk_img (device table and indices); the twiddles come from key0, the same for every key of the set
+void launch_blind_rotate4_mk(hipStream_t s, const DevParams &p, const DevKey &key0, const DevKey *keys, const int32_t *rot_keys,
+                             const int32_t *pool, const RotDesc *rots, int count, int32_t *u_buf);
+void launch_blind_rotate8_mk(hipStream_t s, const DevParams &p, const DevKey &key0, const DevKey *keys, const int32_t *rot_keys,
+                             const int32_t *pool, const RotDesc *rots, int count, int32_t *u_buf);
 // split form (8 waves per rotation, every transform as two half-size ones; N = 1024 or 2048)
 void launch_blind_rotate_split(hipStream_t s, const DevParams &p, const DevKey &key, const int32_t *pool,
                                const RotDesc *rots, int count, int32_t *u_buf, int32_t *acc_dbg);

@@ -20,22 +20,24 @@ const uint8_t GATE_TT[10][4] = {
     {0, 1, 0, 0}, {0, 0, 1, 0}, {1, 1, 0, 1}, {1, 0, 1, 1},
 };
 
-// a pending op by what it computes: kind and operand slots (-1 = absent)
+// a pending op by what it computes: kind, operand slots (-1 = absent) and the cloud key it bootstraps under (index in the
+// recording's key list): the same gate of the same slots under two keys gives two different ciphertexts
 struct OpKey {
-    int32_t kind, a, b, c;
-    bool operator==(const OpKey &o) const { return kind == o.kind && a == o.a && b == o.b && c == o.c; }
+    int32_t kind, a, b, c, key;
+    bool operator==(const OpKey &o) const { return kind == o.kind && a == o.a && b == o.b && c == o.c && key == o.key; }
 };
 struct OpKeyHash {
     size_t operator()(const OpKey &k) const {
         uint64_t h = ((uint64_t)(uint32_t)k.a << 32 | (uint32_t)k.b) * 0x9E3779B97F4A7C15ull;
         h ^= ((uint64_t)(uint32_t)k.c << 8 | (uint32_t)k.kind) * 0xC2B2AE3D27D4EB4Full;
+        h ^= (uint64_t)(uint32_t)k.key * 0x165667B19E3779F9ull;
         return (size_t)(h ^ (h >> 29));
     }
 };
 // symmetric two-input gates (sa == sb in GATE_LIN: t = c0 + s (A + B)) are keyed with ordered operands
-OpKey op_key(int kind, int32_t a, int32_t b, int32_t c) {
+OpKey op_key(int kind, int32_t a, int32_t b, int32_t c, int32_t key) {
     if (kind < OP_MUX && GATE_LIN[kind].sa == GATE_LIN[kind].sb && b < a) std::swap(a, b);
-    return OpKey{kind, a, b, c};
+    return OpKey{kind, a, b, c, key};
 }
 
 struct Recorder {
@@ -46,14 +48,24 @@ struct Recorder {
     // 3.4 ms: 290 gates/s).  TFHE_HIP_DEFERRED=0 / tfhe_hip_set_deferred(0) restores strict per-call completion with the
     // host mirror (a, b) refreshed on return, as upstream's own struct has it.
     bool deferred = true;
-    const TFheGateBootstrappingCloudKeySet *key = nullptr;   // key of the pending operations
+    // cloud keys of the pending operations (PendingOp::key indexes this list) and the key of the op being recorded.  One
+    // key unless batch_keys is on; several keys always share one parameter set, hence one slot pool
+    std::vector<const TFheGateBootstrappingCloudKeySet *> keys;
+    uint16_t cur_key = 0;
     SlotPool *pool = nullptr;
+    // Multi-key flushes (OPT-IN: tuning "batch_keys", env TFHE_HIP_BATCH_KEYS).  Off: a gate under another cloud key than the
+    // pending ones flushes them first (one flush per key).  On: gates under different keys of the SAME parameter set stay
+    // recorded together and run as one level sequence, each rotation and key switch under its own gate's key -- K clients'
+    // circuits fill the levels of one flush instead of running as K narrow flushes.  A key of another parameter set still
+    // flushes.  Results are the same words either way.
+    bool batch_keys = false;
     std::vector<PendingOp> ops;
     int32_t max_level = 0;
     bool balance_levels = true;   // slack-aware level filling (scheduler.hpp)
     // operations of a flush launched without waiting (tfhe_hip_flush_async): released when it is complete
     std::vector<PendingOp> flight_ops;
     SlotPool *flight_pool = nullptr;
+    std::vector<const TFheGateBootstrappingCloudKeySet *> flight_keys;   // keys it runs under: not deleted before it completes
     // Pending ops by (kind, operand slots): an op recorded again with the same operands before the flush is the same
     // function of the same ciphertexts, so its result slot is shared instead of evaluated twice (the reference's circuits
     // do this 12,545 times per match, mostly AND / XOR against the shared constant samples).  Results are unchanged.
@@ -80,6 +92,7 @@ Recorder &rec() {
     static bool init = [] {
         if (const char *e = std::getenv("TFHE_HIP_DEFERRED")) r.deferred = std::atoi(e) != 0;
         if (const char *e = std::getenv("TFHE_HIP_FOLD_CONSTANTS")) r.fold_constants = std::atoi(e) != 0;   // opt-in (Recorder)
+        if (const char *e = std::getenv("TFHE_HIP_BATCH_KEYS")) r.batch_keys = std::atoi(e) != 0;           // opt-in (Recorder)
         return true;
     }();
     (void)init;
@@ -91,10 +104,28 @@ void release_refs(SlotPool *pool, const PendingOp &op) {    // the pending refer
         if (s >= 0) pool->release(s);
 }
 
+// begin_op for a key other than the last op's: the recording's key list gains it, or the pending ops run first
+void select_key(const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    auto known = std::find(r.keys.begin(), r.keys.end(), bk);
+    if (known == r.keys.end() && !r.ops.empty()) {
+        // a key the recording does not hold yet: one more key of the flush (batch_keys, same parameter set) or a flush
+        if (!r.batch_keys || pool_of_key(bk) != r.pool) flush_locked();
+    }
+    if (r.ops.empty()) r.keys.clear();            // nothing pending: the list starts afresh with this key
+    known = std::find(r.keys.begin(), r.keys.end(), bk);
+    if (known == r.keys.end()) {
+        if (r.keys.size() > UINT16_MAX) flush_locked();   // (PendingOp::key) -- a flush empties the list below
+        if (r.ops.empty()) r.keys.clear();
+        r.keys.push_back(bk);
+        known = r.keys.end() - 1;
+    }
+    r.cur_key = (uint16_t)(known - r.keys.begin());
+}
+
 void begin_op(const TFheGateBootstrappingCloudKeySet *bk) {
     Recorder &r = rec();
-    if (r.key && r.key != bk && !r.ops.empty()) flush_locked();
-    r.key = bk;
+    if (r.keys.empty() || r.keys[r.cur_key] != bk) select_key(bk);
     r.pool = pool_of_key(bk);
     // pending operations pin their slots until they run: flush before the pool runs dry, so
     // arbitrarily long recordings need only bounded device memory
@@ -122,7 +153,7 @@ int const_bit(const SlotPool *pool, int32_t slot) { return slot == pool->const_s
 // Two-input gates: c = -1; NOT: b = c = -1.
 void record_op(int kind, LweSample *result, SlotPool *pool, const int32_t a, const int32_t b, const int32_t c) {
     Recorder &r = rec();
-    const OpKey key = op_key(kind, a, b, c);
+    const OpKey key = op_key(kind, a, b, c, r.cur_key);
     if (r.reuse_gates) {
         auto it = r.index.find(key);
         if (it != r.index.end()) {
@@ -138,7 +169,7 @@ void record_op(int kind, LweSample *result, SlotPool *pool, const int32_t a, con
     pool->level[dst] = level;
     pool->pending[dst] = 1;                   // pending even at level 0 (NOT of a materialised sample)
     pool->retain(dst);
-    r.ops.push_back(PendingOp{(uint8_t)kind, dst, a, b, c, level});
+    r.ops.push_back(PendingOp{(uint8_t)kind, dst, a, b, c, level, r.cur_key});
     if (r.reuse_gates) r.index.emplace(key, dst);
     if (kind == OP_NOT) r.not_origin.emplace(dst, a);
     r.max_level = std::max(r.max_level, level);
@@ -156,7 +187,7 @@ void eliminate_dead_ops() {
     for (size_t i = r.ops.size(); i-- > 0;) {
         const PendingOp &op = r.ops[i];
         if (pool->refs(op.dst) != 1) continue;          // a handle or a live operation still holds the result
-        auto it = r.index.find(op_key(op.kind, op.a, op.b, op.c));
+        auto it = r.index.find(op_key(op.kind, op.a, op.b, op.c, op.key));
         if (it != r.index.end() && it->second == op.dst) r.index.erase(it);
         if (op.kind == OP_NOT) r.not_origin.erase(op.dst);
         pool->level[op.dst] = 0;
@@ -323,6 +354,7 @@ void finish_flight_locked() {
     for (const PendingOp &op : r.flight_ops) release_refs(r.flight_pool, op);
     r.flight_ops.clear();
     r.flight_pool = nullptr;
+    r.flight_keys.clear();
 }
 
 int flush_locked(bool wait) {
@@ -341,17 +373,31 @@ int flush_locked(bool wait) {
             std::fclose(f);
         }
     }
-    LevelPlan plan = build_level_plan(r.ops, lvl, levels);
+    // the keys the ops use, in list order (a flush in the middle of recording an op can leave keys of no pending op)
+    std::vector<int32_t> remap(r.keys.size(), -1);
+    for (const PendingOp &op : r.ops) remap[op.key] = 0;
+    std::vector<const TFheGateBootstrappingCloudKeySet *> used;
+    std::vector<const DeviceKeyImage *> images;
+    for (size_t k = 0; k < r.keys.size(); ++k)
+        if (remap[k] == 0) { remap[k] = (int32_t)used.size(); used.push_back(r.keys[k]); images.push_back(r.keys[k]->bk->dev); }
+    LevelPlan plan;
+    if (used.size() == r.keys.size()) {
+        plan = build_level_plan(r.ops, lvl, levels, (int)used.size());
+    } else {
+        std::vector<PendingOp> ops = r.ops;
+        for (PendingOp &op : ops) op.key = (uint16_t)remap[op.key];
+        plan = build_level_plan(ops, lvl, levels, (int)used.size());
+    }
     // everything above -- elimination, levelling, the plan -- ran while the device was busy with the previous asynchronous
     // flush, if any; execute() would wait for it first anyway
     finish_flight_locked();
-    Engine::get().execute(r.key->bk->dev, pool, std::move(plan), wait);    // throws before anything runs, or runs it all
+    Engine::get().execute(images, pool, std::move(plan), wait);    // throws before anything runs, or runs it all
     for (const PendingOp &op : r.ops) {
         pool->level[op.dst] = 0;          // a later recording reads these slots as inputs: the stream orders it behind
         pool->pending[op.dst] = 0;
         if (wait) release_refs(pool, op);
     }
-    if (!wait) { r.flight_ops.swap(r.ops); r.flight_pool = pool; }
+    if (!wait) { r.flight_ops.swap(r.ops); r.flight_pool = pool; r.flight_keys = std::move(used); }
     r.ops.clear();
     r.index.clear();
     r.not_origin.clear();
@@ -363,12 +409,17 @@ void flush_pending_locked(bool wait) { if (!rec().ops.empty()) flush_locked(wait
 
 void forget_key_locked(const TFheGateBootstrappingCloudKeySet *bk) {
     Recorder &r = rec();
-    if (r.key == bk) { flush_locked(); r.key = nullptr; }
+    const bool pending = std::find(r.keys.begin(), r.keys.end(), bk) != r.keys.end();
+    const bool flying = std::find(r.flight_keys.begin(), r.flight_keys.end(), bk) != r.flight_keys.end();
+    // the whole recording runs (gates of the other keys too), and a flush in flight under the key completes
+    if (pending || flying) { flush_locked(); r.keys.clear(); }
 }
 
 bool deferred_mode() { return rec().deferred; }
 
 bool set_deferred_locked(bool on) { return std::exchange(rec().deferred, on); }
+
+bool set_batch_keys_locked(bool on) { return std::exchange(rec().batch_keys, on); }
 
 bool set_recorder_tuning_locked(const char *name, bool on) {
     Recorder &r = rec();
@@ -376,6 +427,7 @@ bool set_recorder_tuning_locked(const char *name, bool on) {
                  : std::strcmp(name, "eliminate_dead") == 0 ? &r.eliminate_dead
                  : std::strcmp(name, "fold_constants") == 0 ? &r.fold_constants
                  : std::strcmp(name, "balance_levels") == 0 ? &r.balance_levels
+                 : std::strcmp(name, "batch_keys") == 0     ? &r.batch_keys
                                                             : nullptr;
     if (knob) *knob = on;
     return knob != nullptr;

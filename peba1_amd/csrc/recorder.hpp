@@ -6,7 +6,7 @@
 // temporaries freed right after use (Math.cpp:47-49).  An op's level is 1 + the maximum level of its operand slots; a
 // flush executes level 1, 2, ... as batched kernel launches.  bootsCOPY and bootsCONSTANT only re-point handles.
 //
-// Every op is recorded through one path (record_op) and looked up in ONE index keyed by (kind, a, b, c): a hit shares the
+// Every op is recorded through one path (record_op) and looked up in ONE index keyed by (kind, a, b, c, key): a hit shares the
 // pending result, a miss appends the op.  Invariant: every entry of the index and of the NOT-origin table names the
 // destination of an op still recorded.  Dead-gate elimination drops an op's entries in the loop that drops the op, and a
 // successful flush clears both tables with the ops, so a flush refused for want of device memory can be retried.
@@ -51,10 +51,12 @@ void sync_sample_locked(const LweSample *s);                 // host mirror := c
 int flush_locked(bool wait = true);
 void flush_pending_locked(bool wait = true);   // flush_locked if anything is recorded
 void finish_flight_locked();                   // the asynchronous flush (if any) is complete: wait, release what it pinned
-void forget_key_locked(const TFheGateBootstrappingCloudKeySet *bk);   // a key about to be deleted: run what it recorded
+void forget_key_locked(const TFheGateBootstrappingCloudKeySet *bk);   // a key about to be deleted: run the recording it is in
 bool deferred_mode();
 bool set_deferred_locked(bool on);                          // returns the previous mode
-bool set_recorder_tuning_locked(const char *name, bool on); // reuse_gates, eliminate_dead, fold_constants, balance_levels
+bool set_batch_keys_locked(bool on);                        // tuning "batch_keys"; returns the previous setting
+bool set_recorder_tuning_locked(const char *name, bool on); // reuse_gates, eliminate_dead, fold_constants, balance_levels,
+                                                            // batch_keys
 #pragma GCC visibility pop
 
 }  // namespace tfhe_hip

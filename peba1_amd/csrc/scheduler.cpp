@@ -145,30 +145,38 @@ int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool bala
     return asap_depth;
 }
 
-LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<int32_t> &lvl, int levels) {
+LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<int32_t> &lvl, int levels, int nkeys) {
     LevelPlan plan;
     plan.levels = levels;
-    // counting sort by level: gates of level L (1-based) in group L - 1, NOTs riding on level L (0 = inputs) in group L
-    plan.rot_off.assign((size_t)levels + 1, 0);
-    plan.ks_off.assign((size_t)levels + 1, 0);
+    plan.nkeys = nkeys;
+    // counting sort by level: gates of level L (1-based) in group L - 1, NOTs riding on level L (0 = inputs) in group L.
+    // Several keys: gates of level L under key k in sub-group (L - 1) nkeys + k, so that a level's descriptors are
+    // contiguous per key (rot_koff / ks_koff); with one key the sub-groups are the groups.
+    const size_t groups = (size_t)levels * nkeys;
+    std::vector<int32_t> roff(groups + 1, 0), koff(groups + 1, 0);
     plan.not_off.assign((size_t)levels + 2, 0);
     for (size_t i = 0; i < ops.size(); ++i) {
         if (ops[i].kind == OP_NOT) { ++plan.not_off[(size_t)lvl[i] + 1]; continue; }
-        plan.rot_off[(size_t)lvl[i]] += op_rotations(ops[i]);
-        ++plan.ks_off[(size_t)lvl[i]];
+        const size_t sg = (size_t)(lvl[i] - 1) * nkeys + ops[i].key;
+        roff[sg + 1] += op_rotations(ops[i]);
+        ++koff[sg + 1];
     }
+    for (size_t sg = 0; sg < groups; ++sg) { roff[sg + 1] += roff[sg]; koff[sg + 1] += koff[sg]; }
+    plan.rot_off.assign((size_t)levels + 1, 0);
+    plan.ks_off.assign((size_t)levels + 1, 0);
     plan.max_rots = 0;
-    for (size_t g = 0; g < (size_t)levels; ++g) {
-        plan.max_rots = std::max(plan.max_rots, plan.rot_off[g + 1]);
-        plan.rot_off[g + 1] += plan.rot_off[g];
-        plan.ks_off[g + 1] += plan.ks_off[g];
+    for (size_t g = 0; g <= (size_t)levels; ++g) {
+        plan.rot_off[g] = roff[g * nkeys];
+        plan.ks_off[g] = koff[g * nkeys];
+        if (g > 0) plan.max_rots = std::max(plan.max_rots, plan.rot_off[g] - plan.rot_off[g - 1]);
     }
     for (size_t g = 0; g <= (size_t)levels; ++g) plan.not_off[g + 1] += plan.not_off[g];
     plan.rots.resize(plan.rot_off.back());
     plan.kss.resize(plan.ks_off.back());
     plan.nots.resize(plan.not_off.back());
-    std::vector<int32_t> rpos(plan.rot_off.begin(), plan.rot_off.end() - 1);   // cursor per group
-    std::vector<int32_t> kpos(plan.ks_off.begin(), plan.ks_off.end() - 1);
+    if (nkeys > 1) plan.rot_key.resize(plan.rots.size());
+    std::vector<int32_t> rpos(roff.begin(), roff.end() - 1);   // cursor per sub-group
+    std::vector<int32_t> kpos(koff.begin(), koff.end() - 1);
     std::vector<int32_t> npos(plan.not_off.begin(), plan.not_off.end() - 1);
     const int32_t mu = 1 << 29;
     for (size_t i = 0; i < ops.size(); ++i) {
@@ -177,21 +185,24 @@ LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<
             plan.nots[npos[(size_t)lvl[i]]++] = NotDesc{op.a, op.dst};
             continue;
         }
-        const size_t g = (size_t)(lvl[i] - 1);
+        const size_t g = (size_t)(lvl[i] - 1), sg = g * nkeys + op.key;
         const int32_t base = plan.rot_off[g];
+        const int32_t r0 = rpos[sg];
         if (op.kind == OP_MUX) {
             // tfhe bootsMUX: u1 = BR(-1/8 + a + b), u2 = BR(-1/8 - a + c), KS(u1 + u2 + 1/8)
-            const int32_t i0 = rpos[g]++, i1 = rpos[g]++;
+            const int32_t i0 = rpos[sg]++, i1 = rpos[sg]++;
             plan.rots[i0] = RotDesc{op.a, op.b, 1, 1, -(mu), i0 - base};
             plan.rots[i1] = RotDesc{op.a, op.c, -1, 1, -(mu), i1 - base};
-            plan.kss[kpos[g]++] = KsDesc{i0 - base, i1 - base, mu, op.dst};
+            plan.kss[kpos[sg]++] = KsDesc{i0 - base, i1 - base, mu, op.dst};
         } else {
             const GateLin &gl = GATE_LIN[op.kind];
-            const int32_t i0 = rpos[g]++;
+            const int32_t i0 = rpos[sg]++;
             plan.rots[i0] = RotDesc{op.a, op.b, gl.sa, gl.sb, gl.c8 * mu, i0 - base};
-            plan.kss[kpos[g]++] = KsDesc{i0 - base, -1, 0, op.dst};
+            plan.kss[kpos[sg]++] = KsDesc{i0 - base, -1, 0, op.dst};
         }
+        for (int32_t r = r0; r < rpos[sg] && nkeys > 1; ++r) plan.rot_key[r] = op.key;
     }
+    if (nkeys > 1) { plan.rot_koff.swap(roff); plan.ks_koff.swap(koff); }
     return plan;
 }
 

@@ -19,6 +19,7 @@ struct PendingOp {
     uint8_t kind;       // 0..9 two-input gate code, OP_MUX, OP_NOT
     int32_t dst, a, b, c;   // slots; b, c = -1 when absent
     int32_t level;      // ASAP level (NOT: the level of its operand, 0 = already materialised)
+    uint16_t key = 0;   // index of the gate's cloud key in the flush's key list (recorder "batch_keys"; NOT: unused)
 };
 constexpr uint8_t OP_MUX = 16, OP_NOT = 17;
 
@@ -40,9 +41,10 @@ constexpr GateLin GATE_LIN[10] = {
 int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool balance, int unit,
                     std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out = nullptr);
 
-// The descriptors of a flush (engine.hpp): ops[i] runs at level lvl[i] (schedule_levels), levels in all.
+// The descriptors of a flush (engine.hpp): ops[i] runs at level lvl[i] (schedule_levels), levels in all.  nkeys > 1 (a
+// flush of gates under several cloud keys): within a level, descriptors are grouped by ops[i].key.
 struct LevelPlan;
 __attribute__((visibility("hidden"))) LevelPlan build_level_plan(const std::vector<PendingOp> &ops,
-                                                                 const std::vector<int32_t> &lvl, int levels);
+                                                                 const std::vector<int32_t> &lvl, int levels, int nkeys = 1);
 
 }  // namespace tfhe_hip

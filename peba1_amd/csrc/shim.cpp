@@ -557,7 +557,7 @@ int tfhe_hip_set_tuning(const char *name, int64_t value) {
     if (name && std::strcmp(name, "br8_max_rotations") == 0) { Engine::get().br8_max_rotations = (int)value; return 0; }
     if (name && std::strcmp(name, "br_tail8") == 0) { Engine::get().br_tail8 = (int)value; return 0; }
     if (name && std::strcmp(name, "br_variant") == 0) { Engine::get().br_variant = (int)value; return 0; }
-    if (name && set_recorder_tuning_locked(name, value != 0)) return 0;   // reuse_gates, eliminate_dead, fold_constants, balance_levels
+    if (name && set_recorder_tuning_locked(name, value != 0)) return 0;   // reuse_gates, eliminate_dead, fold_constants, balance_levels, batch_keys
     if (name && std::strcmp(name, "sync_deadline_ms") == 0) { Engine::get().sync_deadline_ms = value > 0 ? (long long)value : 0; return 0; }
     set_error(std::string("tfhe_hip_set_tuning: unknown name ") + (name ? name : "(null)"));
     return -1;
@@ -574,6 +574,14 @@ void tfhe_hip_reset_stats(void) {
     Engine::get().stats = TfheHipStats{};
 }
 void tfhe_hip_set_kernel_timing(int on) { Engine::get().kernel_timing = on != 0; }
+int tfhe_hip_last_flush_keys(void) {
+    auto g = recorder_lock();
+    return Engine::get().last_flush_keys;
+}
+int tfhe_hip_set_batch_keys(int on) {
+    auto g = recorder_lock();
+    return set_batch_keys_locked(on != 0) ? 1 : 0;
+}
 
 static int test_build_ops(const int32_t *ops5, int32_t count, std::vector<PendingOp> &ops) {
     // ops5[i] = {kind, dst, a, b, c}; ASAP levels are derived here exactly as the recorder derives them

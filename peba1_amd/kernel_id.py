@@ -12,7 +12,8 @@ import hashlib
 import os
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-KERNEL_FILES = ("kernels.hip", "kernels.hpp", "ntt_wave.hpp", "ntt_field.hpp", "br_forms.hpp", "ks_index_asm.inc", "build.sh")
+KERNEL_FILES = ("kernels.hip", "kernels.hpp", "ntt_wave.hpp", "ntt_field.hpp", "br_forms.hpp", "ks_index_asm.inc", "br8_body.inc",
+                "build.sh")
 
 
 def kernels_sha16():

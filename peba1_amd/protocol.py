@@ -14,6 +14,10 @@ function runs in deferred mode and is flushed by the decryption (or the explicit
 that follows it.
 
     python -m peba1_amd.protocol --nslots 128            # genuine and impostor run, one GPU
+    python -m peba1_amd.protocol --clients 4             # four clients, each with a key pair of its own, batched
+
+With --clients K the server side runs as a multi-user server does: Function_f of all K clients in ONE flush and
+Function_g of all K in a second one (multi-key flushes, tuning "batch_keys"), one JSON line per client.
 """
 import argparse
 import json
@@ -56,13 +60,84 @@ def run_p1(params, key, sample, template, bound_match, r0, r1, bitsize=8, cloud=
             "levels": {"function_f": levels_f, "function_g": levels_g}}
 
 
-def main():
+def run_p1_clients(params, keys, samples, templates, bounds, r0s, r1s, bitsize=8, fast=False):
+    """run_p1 for K clients at once, client c with its own secret keyset keys[c]: every client's Function_f in one flush,
+    every Function_g in a second.  Returns one dict per client, as run_p1's (the timings are the batch's)."""
+    from . import lib
+    k = len(keys)
+    t0 = time.perf_counter()
+    enc_t = [circuits.EncryptedVector(params, templates[c], bitsize, keys[c]).to_device() for c in range(k)]
+    enc_s = [circuits.EncryptedVector(params, samples[c], bitsize, keys[c]).to_device() for c in range(k)]
+    enc_bound = [circuits.encrypt_number(params, bounds[c], MAX_BITSIZE, keys[c]) for c in range(k)]
+    enc_r0 = [circuits.encrypt_number(params, r0s[c], bitsize, keys[c]) for c in range(k)]
+    enc_r1 = [circuits.encrypt_number(params, r1s[c], bitsize, keys[c]) for c in range(k)]
+    t_enc = time.perf_counter()
+    enc_b = [api.CiphertextArray(params, MAX_BITSIZE) for _ in range(k)]
+    levels_f = circuits.function_f_batch(enc_b, enc_s, enc_t, enc_bound, bitsize, keys, fast=fast)
+    t_f = time.perf_counter()
+    enc_y = [api.CiphertextArray(params, bitsize + 1) for _ in range(k)]
+    L = lib.load()
+    was_deferred, had_batch = api.get_deferred(), L.tfhe_hip_set_batch_keys(1)
+    api.set_deferred(True)
+    try:
+        for c in range(k):
+            circuits.function_g(enc_y[c], enc_b[c], enc_r0[c], enc_r1[c], bitsize, keys[c])
+        levels_g = api.flush()
+    finally:
+        api.set_deferred(was_deferred)
+        L.tfhe_hip_set_batch_keys(had_batch)
+    t_g = time.perf_counter()
+    out = []
+    for c in range(k):
+        y = circuits.decrypt_number(enc_y[c], keys[c], bitsize)
+        b = int(enc_b[c].decrypt(keys[c])[0])
+        out.append({"client": c, "y": y, "r0": r0s[c], "r1": r1s[c], "match_bit": b, "authenticated": y == r1s[c],
+                    "seconds": {"encrypt": t_enc - t0, "function_f": t_f - t_enc, "function_g": t_g - t_f},
+                    "levels": {"function_f": levels_f, "function_g": levels_g}})
+    return out
+
+
+def client_inputs(c, nslots, seed):
+    """Inputs of client c of a --clients run: its own key seed, template, sample (genuine for even c, impostor for odd
+    c) and server randomness."""
+    template = [(37 * i + 11 + 5 * c) % 255 for i in range(nslots)]
+    sample = [t + 1 for t in template] if c % 2 == 0 else [(91 * i + 5 + 3 * c) % 256 for i in range(nslots)]
+    return {"key_seed": seed + 1 + c, "template": template, "sample": sample, "r0": (17 + c) % 256, "r1": (99 + 7 * c) % 256}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--nslots", type=int, default=128)
     ap.add_argument("--bound", type=int, default=256)
     ap.add_argument("--seed", type=lambda v: int(v, 0), default=0x5EBA1)
     ap.add_argument("--fast", action="store_true", help="Function_f through the optimised DAG (circuits_fast.cpp)")
-    a = ap.parse_args()
+    ap.add_argument("--clients", type=int, default=0,
+                    help="K > 0: K clients with key pairs of their own, Function_f and Function_g batched over them")
+    a = ap.parse_args(argv)
+    if a.clients < 0:
+        ap.error("--clients must be >= 0")
+    return a
+
+
+def main_clients(a):
+    params = api.ParameterSet(128)
+    inputs = [client_inputs(c, a.nslots, a.seed) for c in range(a.clients)]
+    keys = [api.SecretKeySet(params, x["key_seed"]) for x in inputs]
+    try:
+        outs = run_p1_clients(params, keys, [x["sample"] for x in inputs], [x["template"] for x in inputs],
+                              [a.bound] * a.clients, [x["r0"] for x in inputs], [x["r1"] for x in inputs], fast=a.fast)
+        for x, out in zip(inputs, outs):
+            out["distance"] = sum((s - t) ** 2 for s, t in zip(x["sample"], x["template"]))
+            print(json.dumps(out))
+    finally:
+        for k in keys:
+            k.close()
+
+
+def main():
+    a = parse_args()
+    if a.clients:
+        return main_clients(a)
     params = api.ParameterSet(128)
     key = api.SecretKeySet(params, a.seed + 1)
     template = [(37 * i + 11) % 255 for i in range(a.nslots)]             # SURVEY 8c inputs
