@@ -182,8 +182,9 @@ int tfhe_hip_gate_batch(int gate, LweSample *result, const LweSample *a, const L
  * keys of the SAME parameter set stay recorded together and run as one level sequence (one flush), each bootstrap and key
  * switch under its own gate's key -- a server's K clients fill the levels of one flush instead of running as K narrow
  * flushes.  0: a gate under another key than the pending gates' flushes them first.  A key of another parameter set
- * flushes either way.  The words are the same as with 0; every key of such a flush stays alive until it has run (deleting
- * a keyset runs the whole recording first).
+ * flushes either way; the same set = equal n, N, k, l, Bgbit, ks_t and ks_basebit, by value (two parameter-set objects
+ * with equal numbers are one set; the noise deviations do not matter).  The words are the same as with 0; every key of
+ * such a flush stays alive until it has run (deleting a keyset runs the whole recording first).
  * "sync_deadline_ms": see "bounded host waits" above.
  * (Environment only: TFHE_HIP_KS_BLOCKS / TFHE_HIP_KS_MAX_SPLITS / TFHE_HIP_KS_SPLIT_TIES, how key switches are cut into
  * coefficient ranges -- engine.hpp.)
@@ -246,6 +247,17 @@ void tfhe_hip_test_set_alloc_cap(int64_t bytes);
  * records (kind: gate code 0..9, 16 = MUX, 17 = NOT; absent operands -1) without
  * touching the device; writes the level of each op, returns the depth ---- */
 int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int32_t balance, int32_t *levels_out);
+/* ---- host-logic test entry: the same levelisation, then the level plan a flush of these ops under `nkeys` cloud keys
+ * hands to the engine (op i bootstraps under key op_keys[i], 0 <= op_keys[i] < nkeys), without touching the device.
+ * The caller provides room for the largest plan `count` ops can give: levels_out[count]; rot_off, ks_off
+ * [count + 1]; rot_koff, ks_koff [count * nkeys + 1]; rot_key [2 count]; rots6 [6 * 2 count] ({slot_a, slot_b,
+ * sa, sb, c0, u_index} per rotation); kss4 [4 count] ({u0, u1, add_b, dst_slot} per key switch; u0 / u1 index the
+ * level's extracted samples).  sizes6 = {levels, rotations, key switches, entries of rot_koff, of ks_koff, of rot_key}
+ * (the last three are 0 with one key); rot_off and ks_off hold levels + 1 entries.  Returns the number of levels,
+ * -1 on bad arguments. ---- */
+int tfhe_hip_test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                             int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
+                             int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots6, int32_t *kss4);
 /* Diagnostic (tools/wg_times.py): a 4-wave blind-rotate launch of `width` random gates (the second of two back to back);
  * times4[4i .. 4i+3] = s_memtime (shader cycles; the start stamp carries the XCC / CU id in its top 16
  * bits) at the start and end of workgroup i, then s_memrealtime (constant 100 MHz) at its start and

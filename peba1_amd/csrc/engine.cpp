@@ -744,6 +744,14 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
     const DeviceKeyImage *key = keys.at(0);
     const int nkeys = plan_in.nkeys;
     if (nkeys < 1 || (size_t)nkeys != keys.size()) fatal("execute: the plan's key count differs from the flush's key list");
+    // (recorder.cpp select_key keeps keys of another set out of a recording; checked again here, before any launch, because
+    // a key with a larger ring or gadget than keys[0]'s would be read beyond its image and write beyond the extract buffer)
+    for (const DeviceKeyImage *k : keys) {
+        const DevParams &a = key->dp, &b = k->dp;
+        if (a.n != b.n || a.N != b.N || a.k != b.k || a.l != b.l || a.Bgbit != b.Bgbit || a.ks_t != b.ks_t ||
+            a.ks_basebit != b.ks_basebit)
+            fatal("execute: the keys of a multi-key flush differ in a parameter that evaluation reads");
+    }
     // Every device buffer of the flush is sized here, before anything is enqueued and before the plan changes hands:
     // scratch() may reallocate, which must not happen under a running launch -- and it may throw (out of device memory:
     // recoverable_alloc), in which case nothing has run, the caller's recorded gates are still pending and its flush
@@ -823,12 +831,17 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
                 t.wide8 = launch_br(key, pool->data(), drots + plan.rot_off[gg], nrot, u_buf, nullptr, stream_, dkeys,
                                     drot_keys + plan.rot_off[gg]);
             } else {
+                int launched = 0;
                 for (int k = 0; k < nkeys; ++k) {
                     const size_t sg = gg * (size_t)nkeys + (size_t)k;
                     const int n = plan.rot_koff[sg + 1] - plan.rot_koff[sg];
-                    if (n) launch_br(keys[(size_t)k], pool->data(), drots + plan.rot_koff[sg], n, u_buf, nullptr, stream_);
+                    if (!n) continue;
+                    launch_br(keys[(size_t)k], pool->data(), drots + plan.rot_koff[sg], n, u_buf, nullptr, stream_);
+                    ++launched;
                 }
                 tail_count_ = 0;
+                stats.br_launches += (uint64_t)(launched - 1);   // br_launches counts launches: one per key with a share (the
+                                                                 // level's own +1 is below)
             }
             if (t.wide8) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)nrot; }
             if (tail_count_) {

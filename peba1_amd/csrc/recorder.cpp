@@ -104,13 +104,25 @@ void release_refs(SlotPool *pool, const PendingOp &op) {    // the pending refer
         if (s >= 0) pool->release(s);
 }
 
+// "Same parameter set" for a multi-key flush: every field that evaluation reads, by VALUE (two separately allocated sets
+// with equal numbers are one set).  execute() runs all rotations of a flush with the DevParams, form rules and extract
+// stride of its first key, so a key that differs in any of these must not join; sharing a slot pool is not enough, pools
+// are matched on n alone (Engine::find_pool).  The three noise deviations are left out: they shape key generation and
+// encryption only, no kernel and no launch rule reads them.
+bool same_evaluation_params(const Params &a, const Params &b) {
+    return a.n == b.n && a.N == b.N && a.k == b.k && a.l == b.l && a.Bgbit == b.Bgbit && a.ks_t == b.ks_t &&
+           a.ks_basebit == b.ks_basebit;
+}
+
 // begin_op for a key other than the last op's: the recording's key list gains it, or the pending ops run first
 void select_key(const TFheGateBootstrappingCloudKeySet *bk) {
     Recorder &r = rec();
     auto known = std::find(r.keys.begin(), r.keys.end(), bk);
     if (known == r.keys.end() && !r.ops.empty()) {
-        // a key the recording does not hold yet: one more key of the flush (batch_keys, same parameter set) or a flush
-        if (!r.batch_keys || pool_of_key(bk) != r.pool) flush_locked();
+        // a key the recording does not hold yet: one more key of the flush (batch_keys, same parameter set) or a flush.
+        // Every key of the list passed this test against the first, so comparing with the first compares with all
+        if (!r.batch_keys || pool_of_key(bk) != r.pool || !same_evaluation_params(bk->bk->p, r.keys.front()->bk->p))
+            flush_locked();
     }
     if (r.ops.empty()) r.keys.clear();            // nothing pending: the list starts afresh with this key
     known = std::find(r.keys.begin(), r.keys.end(), bk);

@@ -611,6 +611,37 @@ int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int
     return d;
 }
 
+int tfhe_hip_test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                             int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
+                             int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots6, int32_t *kss4) {
+    if (count < 0 || nkeys < 1 || nkeys > UINT16_MAX) { set_error("test_level_plan: bad count or nkeys"); return -1; }
+    for (int32_t i = 0; i < count; ++i)
+        if (op_keys[i] < 0 || op_keys[i] >= nkeys) { set_error("test_level_plan: key index out of range"); return -1; }
+    std::vector<PendingOp> ops;
+    const int depth = test_build_ops(ops5, count, ops);
+    for (int32_t i = 0; i < count; ++i) ops[i].key = (uint16_t)op_keys[i];
+    std::vector<int32_t> lvl;
+    const int levels = schedule_levels(ops, depth, balance != 0, unit, lvl);
+    const LevelPlan plan = build_level_plan(ops, lvl, levels, nkeys);     // exactly what flush_locked hands to execute()
+    for (int32_t i = 0; i < count; ++i) levels_out[i] = lvl[i];
+    sizes6[0] = plan.levels;
+    sizes6[1] = (int32_t)plan.rots.size();
+    sizes6[2] = (int32_t)plan.kss.size();
+    sizes6[3] = (int32_t)plan.rot_koff.size();
+    sizes6[4] = (int32_t)plan.ks_koff.size();
+    sizes6[5] = (int32_t)plan.rot_key.size();
+    static_assert(sizeof(RotDesc) == 6 * sizeof(int32_t) && sizeof(KsDesc) == 4 * sizeof(int32_t), "descriptors are plain words");
+    auto copy = [](int32_t *dst, const void *src, size_t words) { if (words) std::memcpy(dst, src, words * sizeof(int32_t)); };
+    copy(rot_off, plan.rot_off.data(), plan.rot_off.size());
+    copy(ks_off, plan.ks_off.data(), plan.ks_off.size());
+    copy(rot_koff, plan.rot_koff.data(), plan.rot_koff.size());
+    copy(ks_koff, plan.ks_koff.data(), plan.ks_koff.size());
+    copy(rot_key, plan.rot_key.data(), plan.rot_key.size());
+    copy(rots6, plan.rots.data(), 6 * plan.rots.size());
+    copy(kss4, plan.kss.data(), 4 * plan.kss.size());
+    return levels;
+}
+
 
 int tfhe_hip_test_wg_times(const TFheGateBootstrappingCloudKeySet *bk, int32_t width, uint64_t *times4, double *launch_ms) {
     if (!bk || !bk->bk || !times4 || width <= 0) { set_error("wg_times: bad arguments"); return -1; }

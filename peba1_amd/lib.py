@@ -136,7 +136,8 @@ SIGNATURES = {
     "tfhe_hip_last_flush_keys": (C.c_int, []),
     "tfhe_hip_set_batch_keys": (C.c_int, [C.c_int]),
     "tfhe_hip_test_schedule": (C.c_int, [I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
-    "tfhe_hip_kernel_negacyclic": (C.c_int, [CK, I32P, I32P, I32P, C.c_int32]),
+    "tfhe_hip_test_level_plan": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [I32P] * 9),
+    "tfhe_hip_kernel_negacyclic":(C.c_int, [CK, I32P, I32P, I32P, C.c_int32]),
     "tfhe_hip_kernel_bootstrap_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P]),
     "tfhe_hip_kernel_keyswitch": (C.c_int, [CK, I32P, C.c_int32, I32P]),
 }
