@@ -67,6 +67,12 @@ void peba1_euclidean_distance_fast(LweSample *result, LweSample *const *a, LweSa
                                    int bitsize, const TFheGateBootstrappingCloudKeySet *ck);
 void peba1_function_f_fast(LweSample *result_b, LweSample *const *a, LweSample *const *b, int nslots,
                            LweSample *bound_match, int bitsize, const TFheGateBootstrappingCloudKeySet *ck);
+/* peba1_function_f_fast's DAG with every full adder of its compressor (sum = XOR3, carry = MAJ3) and of its borrow chain
+ * (difference = XOR3, borrow = MAJ3 with the minuend negated) as 2 bootstraps at depth 1 through libtfhe-hip's three-input
+ * gates (tfhe_hip_gate3, include/tfhe_hip.h -- not part of upstream TFHE's API).  Over a provider without them it is
+ * peba1_function_f_fast's gate sequence.  Same interface, same decrypted result_b. */
+void peba1_function_f_fast3(LweSample *result_b, LweSample *const *a, LweSample *const *b, int nslots,
+                            LweSample *bound_match, int bitsize, const TFheGateBootstrappingCloudKeySet *ck);
 
 /* Slot-sharded variant of the distance for multi-GPU runs: the
  * partial sum of squares over slots [0, nslots) of this rank, 24 samples, with
@@ -95,6 +101,14 @@ void peba1_hamming_distance(LweSample *count, LweSample *a, LweSample *b, int nb
  * peba1_hamming_count_bits(nbits) samples */
 void peba1_hamming_match(LweSample *result_b, LweSample *a, LweSample *b, int nbits, LweSample *bound_match,
                          const TFheGateBootstrappingCloudKeySet *ck);
+/* The same count and match through a carry-save column compressor: XOR per bit, every column taken down to one wire
+ * with full adders (XOR3 + MAJ3 through tfhe_hip_gate3 where the provider has it, else 2 XOR + 1 MUX) and half adders
+ * (XOR + AND), then the prefix comparator of circuits_fast.cpp.  Same interface, polarity and decrypted results as
+ * peba1_hamming_distance / peba1_hamming_match; NOT their gate sequence. */
+void peba1_hamming_distance_csa(LweSample *count, LweSample *a, LweSample *b, int nbits,
+                                const TFheGateBootstrappingCloudKeySet *ck);
+void peba1_hamming_match_csa(LweSample *result_b, LweSample *a, LweSample *b, int nbits, LweSample *bound_match,
+                             const TFheGateBootstrappingCloudKeySet *ck);
 
 /* ---- multi-client batches: K clients' matches, client c under its own cloud key ck[c] (all of one parameter set),
  * recorded with libtfhe-hip's multi-key flushes ("batch_keys", include/tfhe_hip.h) and deferred mode on, then run as ONE
@@ -103,7 +117,7 @@ void peba1_hamming_match(LweSample *result_b, LweSample *a, LweSample *b, int nb
  * produces.  Return the flush's level count (< 0 on error; 0 over a provider without libtfhe-hip's extensions, which
  * evaluates call by call). ---- */
 /* Function_f per client: result_b[c] (3*bitsize samples), a[c] / b[c] (nslots sample arrays each), bound_match[c];
- * fast != 0: peba1_function_f_fast's DAG */
+ * fast = 2: peba1_function_f_fast3's DAG; any other fast != 0: peba1_function_f_fast's */
 int peba1_function_f_batch(LweSample *const *result_b, LweSample *const *const *a, LweSample *const *const *b, int nclients,
                            int nslots, LweSample *const *bound_match, int bitsize,
                            const TFheGateBootstrappingCloudKeySet *const *ck, int fast);
@@ -111,6 +125,9 @@ int peba1_function_f_batch(LweSample *const *result_b, LweSample *const *const *
  * (nbits samples) */
 int peba1_hamming_match_batch(LweSample *const *result_b, LweSample *const *a, LweSample *const *b, int nclients, int nbits,
                               LweSample *const *bound_match, const TFheGateBootstrappingCloudKeySet *const *ck);
+/* peba1_hamming_match_csa per client, same arguments */
+int peba1_hamming_match_csa_batch(LweSample *const *result_b, LweSample *const *a, LweSample *const *b, int nclients,
+                                  int nbits, LweSample *const *bound_match, const TFheGateBootstrappingCloudKeySet *const *ck);
 
 #ifdef __cplusplus
 }

@@ -147,6 +147,27 @@ void tfhe_hip_set_diag_label(const char *label);
 int tfhe_hip_gate_batch(int gate, LweSample *result, const LweSample *a, const LweSample *b,
                         int32_t count, const TFheGateBootstrappingCloudKeySet *bk);
 
+/* ---- three-input gates: NOT PART OF UPSTREAM TFHE'S API.  With the +-1/8 encoding and the constant test vector every
+ * gate uses, one bootstrap also evaluates the majority and the parity of three bits, so sum and carry of a full adder
+ * are 2 bootstraps at depth 1.  The words are this library's own, defined by integers: the result is the bootstrap (test
+ * vector and mu = 1/8 as for every gate) and key switch of
+ *     t = sa A + sb B + sc C      (wrapping mod 2^32 on all n+1 words; no constant term)
+ * with (sa, sb, sc) = (+1, +1, +1) for MAJ3, (-2, -2, -2) for XOR3, (+2, +2, +2) for XNOR3; bit i of negate_mask (a = bit
+ * 0, b = bit 1, c = bit 2) flips the sign of operand i's coefficient -- the gate of the NEGATED operand, at no cost:
+ * borrow = MAJ3(!a, b, c) is tfhe_hip_gate3(TFHE_HIP_MAJ3, 1, ...).  One blind rotation and one key switch per gate.
+ * Noise: the sum of three samples stands 1/8 (MAJ3) or 1/4 (XOR3) from the decision boundary like AND / XOR do, under
+ * three input noises instead of two.  Recorded in deferred mode (shared, eliminated and levelled like every gate), complete
+ * on return in immediate mode; "fold_constants" turns a gate with a constant operand into the two-input gate with the same
+ * truth table (MAJ3 with 0 -> AND, with 1 -> OR; XOR3 with 0 -> XOR, with 1 -> XNOR; negations carried into ANDNY / ANDYN
+ * / NOR / ORNY / ORYN / NAND / XOR / XNOR), bootstrapped with exactly the words bootsAND etc. give.  Errors as for every
+ * boots* entry: tfhe_hip_last_error(), call without effect. ---- */
+enum TfheHipGate3 { TFHE_HIP_MAJ3 = 0, TFHE_HIP_XOR3, TFHE_HIP_XNOR3 };
+void tfhe_hip_gate3(int gate, int negate_mask, LweSample *result, const LweSample *a, const LweSample *b,
+                    const LweSample *c, const TFheGateBootstrappingCloudKeySet *bk);
+/* result[i] = gate3(a[i], b[i], c[i]) for i < count, one batched launch; 0 / -1 */
+int tfhe_hip_gate3_batch(int gate, int negate_mask, LweSample *result, const LweSample *a, const LweSample *b,
+                         const LweSample *c, int32_t count, const TFheGateBootstrappingCloudKeySet *bk);
+
 /* ---- tuning (eleven names that results never depend on, and the opt-in "fold_constants") ----
  * "br_variant": which form of the blind-rotate kernel runs wide launches (env TFHE_HIP_BR_VARIANT): -1 (default) =
  * the fastest measured for the ring size (N = 1024: 4 waves per rotation; N = 2048: split), 0 = 4 waves (N = 1024),
@@ -244,8 +265,8 @@ int tfhe_hip_test_form_admissible(int form, int32_t N, int32_t l, int32_t Bgbit,
 void tfhe_hip_test_set_alloc_cap(int64_t bytes);
 
 /* ---- host-logic test entry: levelise a DAG given as count x {kind, dst, a, b, c} slot
- * records (kind: gate code 0..9, 16 = MUX, 17 = NOT; absent operands -1) without
- * touching the device; writes the level of each op, returns the depth ---- */
+ * records (kind: gate code 0..9, 16 = MUX, 17 = NOT, 32 + 8 * TfheHipGate3 + negate_mask = a three-input gate; absent
+ * operands -1) without touching the device; writes the level of each op, returns the depth (-1: unknown kind) ---- */
 int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int32_t balance, int32_t *levels_out);
 /* ---- host-logic test entry: the same levelisation, then the level plan a flush of these ops under `nkeys` cloud keys
  * hands to the engine (op i bootstraps under key op_keys[i], 0 <= op_keys[i] < nkeys), without touching the device.
@@ -258,6 +279,11 @@ int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int
 int tfhe_hip_test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
                              int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
                              int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots6, int32_t *kss4);
+/* The same with eight words per rotation: {slot_a, slot_b, sa, sb, c0, u_index, slot_c, sc}; slot_c = -1, sc = 0 where the
+ * rotation has no third operand (rots8 [8 * 2 count]).  tfhe_hip_test_level_plan gives the first six of these. */
+int tfhe_hip_test_level_plan3(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                              int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
+                              int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots8, int32_t *kss4);
 /* Diagnostic (tools/wg_times.py): a 4-wave blind-rotate launch of `width` random gates (the second of two back to back);
  * times4[4i .. 4i+3] = s_memtime (shader cycles; the start stamp carries the XCC / CU id in its top 16
  * bits) at the start and end of workgroup i, then s_memrealtime (constant 100 MHz) at its start and

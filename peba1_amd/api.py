@@ -12,6 +12,9 @@ from . import lib as _l
 
 GATE_CODES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5,
               "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
+# three-input gates (tfhe_hip_gate3; not in upstream's API): t = s (+-A +- B +- C) with s = GATE3_LIN[name]
+GATE3_CODES = {"MAJ3": 0, "XOR3": 1, "XNOR3": 2}
+GATE3_LIN = {"MAJ3": 1, "XOR3": -2, "XNOR3": 2}
 
 
 def _i32p(a):
@@ -237,6 +240,19 @@ class CiphertextArray:
 
 def gate_batch(name, result, a, b, key):
     rc = _l.load().tfhe_hip_gate_batch(GATE_CODES[name], result.ptr, a.ptr, b.ptr, result.count, key.cloud)
+    if rc != 0:
+        raise RuntimeError(last_error())
+
+
+def gate3(name, result, a, b, c, key, negate_mask=0):
+    """result = name(a, b, c), each an LweSample pointer (CiphertextArray.at); bit i of negate_mask negates operand i.
+    Errors go to last_error() and leave the result untouched, as for the boots* entries."""
+    _l.load().tfhe_hip_gate3(GATE3_CODES[name], int(negate_mask), result, a, b, c, key.cloud)
+
+
+def gate3_batch(name, result, a, b, c, key, negate_mask=0):
+    rc = _l.load().tfhe_hip_gate3_batch(GATE3_CODES[name], int(negate_mask), result.ptr, a.ptr, b.ptr, c.ptr, result.count,
+                                        key.cloud)
     if rc != 0:
         raise RuntimeError(last_error())
 

@@ -40,6 +40,9 @@ def load():
             "peba1_combine_and_compare_fast": [LS, LSP, C.c_int, LS, CK],
             "peba1_hamming_distance": [LS, LS, LS, C.c_int, CK],
             "peba1_hamming_match": [LS, LS, LS, C.c_int, LS, CK],
+            "peba1_function_f_fast3": [LS, LSP, LSP, C.c_int, LS, C.c_int, CK],
+            "peba1_hamming_distance_csa": [LS, LS, LS, C.c_int, CK],
+            "peba1_hamming_match_csa": [LS, LS, LS, C.c_int, LS, CK],
         }
         for name, args in sig.items():
             f = getattr(Lc, name)
@@ -50,6 +53,8 @@ def load():
                                               C.POINTER(CK), C.c_int]
         Lc.peba1_hamming_match_batch.restype = C.c_int
         Lc.peba1_hamming_match_batch.argtypes = [LSP, LSP, LSP, C.c_int, C.c_int, LSP, C.POINTER(CK)]
+        Lc.peba1_hamming_match_csa_batch.restype = C.c_int
+        Lc.peba1_hamming_match_csa_batch.argtypes = Lc.peba1_hamming_match_batch.argtypes
         Lc.peba1_hamming_count_bits.restype = C.c_int
         Lc.peba1_hamming_count_bits.argtypes = [C.c_int]
         _circ = Lc
@@ -104,6 +109,12 @@ def function_f_fast(result_b, sample, template, bound, bitsize, key):
                                  len(sample.slots), bound.ptr, bitsize, key.cloud)
 
 
+def function_f_fast3(result_b, sample, template, bound, bitsize, key):
+    """function_f_fast's DAG with its full adders as XOR3 + MAJ3 (tfhe_hip_gate3: 2 bootstraps at depth 1 each)."""
+    load().peba1_function_f_fast3(result_b.ptr, _ptr_array(sample.slots), _ptr_array(template.slots),
+                                  len(sample.slots), bound.ptr, bitsize, key.cloud)
+
+
 def euclidean_distance_fast(result, sample, template, bitsize, key):
     load().peba1_euclidean_distance_fast(result.ptr, _ptr_array(sample.slots), _ptr_array(template.slots),
                                          len(sample.slots), bitsize, key.cloud)
@@ -138,6 +149,16 @@ def hamming_distance(count, a, b, nbits, key):
     load().peba1_hamming_distance(count.ptr, a.ptr, b.ptr, nbits, key.cloud)
 
 
+def hamming_match_csa(result_b, a, b, nbits, bound, key):
+    """hamming_match through a carry-save compressor of three-input full adders: same result, a quarter of the
+    bootstraps."""
+    load().peba1_hamming_match_csa(result_b.ptr, a.ptr, b.ptr, nbits, bound.ptr, key.cloud)
+
+
+def hamming_distance_csa(count, a, b, nbits, key):
+    load().peba1_hamming_distance_csa(count.ptr, a.ptr, b.ptr, nbits, key.cloud)
+
+
 def hamming_count_bits(nbits):
     return load().peba1_hamming_count_bits(nbits)
 
@@ -151,7 +172,8 @@ def _cloud_array(keys):
 
 def function_f_batch(results_b, samples, templates, bounds, bitsize, keys, fast=False):
     """Function_f for K clients in ONE flush, client c under its own key keys[c] (peba1_function_f_batch: multi-key
-    flushes, include/tfhe_hip.h "batch_keys").  Lists of K each; returns the flush's level count."""
+    flushes, include/tfhe_hip.h "batch_keys").  Lists of K each; returns the flush's level count.  fast: False, True
+    (function_f_fast's DAG) or 2 (function_f_fast3's)."""
     k = len(keys)
     assert len(results_b) == len(samples) == len(templates) == len(bounds) == k
     nslots = len(samples[0].slots)
@@ -161,17 +183,19 @@ def function_f_batch(results_b, samples, templates, bounds, bitsize, keys, fast=
     LSP = C.POINTER(_l.LS)
     sp, tp = (LSP * k)(*[C.cast(x, LSP) for x in sa]), (LSP * k)(*[C.cast(x, LSP) for x in ta])
     rc = load().peba1_function_f_batch(_ptr_array(results_b), sp, tp, k, nslots, _ptr_array(bounds), bitsize,
-                                       _cloud_array(keys), 1 if fast else 0)
+                                       _cloud_array(keys), 2 if fast == 2 else 1 if fast else 0)
     if rc < 0:
         raise RuntimeError(api.last_error())
     return rc
 
 
-def hamming_match_batch(results_b, a, b, nbits, bounds, keys):
-    """peba1_hamming_match for K clients in ONE flush, client c under keys[c]; returns the flush's level count."""
+def hamming_match_batch(results_b, a, b, nbits, bounds, keys, csa=False):
+    """peba1_hamming_match (csa: peba1_hamming_match_csa) for K clients in ONE flush, client c under keys[c]; returns
+    the flush's level count."""
     k = len(keys)
     assert len(results_b) == len(a) == len(b) == len(bounds) == k
-    rc = load().peba1_hamming_match_batch(_ptr_array(results_b), _ptr_array(a), _ptr_array(b), k, nbits,
+    entry = load().peba1_hamming_match_csa_batch if csa else load().peba1_hamming_match_batch
+    rc = entry(_ptr_array(results_b), _ptr_array(a), _ptr_array(b), k, nbits,
                                           _ptr_array(bounds), _cloud_array(keys))
     if rc < 0:
         raise RuntimeError(api.last_error())

@@ -310,7 +310,8 @@ void peba1_hamming_match(LweSample *result_b, LweSample *a, LweSample *b, int nb
 int peba1_function_f_batch(LweSample *const *result_b, LweSample *const *const *a, LweSample *const *const *b, int nclients,
                            int nslots, LweSample *const *bound_match, int bitsize, CK *const *ck, int fast) {
     return record_batch(nclients, [&](int c) {
-        if (fast) peba1_function_f_fast(result_b[c], a[c], b[c], nslots, bound_match[c], bitsize, ck[c]);
+        if (fast == 2) peba1_function_f_fast3(result_b[c], a[c], b[c], nslots, bound_match[c], bitsize, ck[c]);
+        else if (fast) peba1_function_f_fast(result_b[c], a[c], b[c], nslots, bound_match[c], bitsize, ck[c]);
         else peba1_function_f(result_b[c], a[c], b[c], nslots, bound_match[c], bitsize, ck[c]);
     });
 }
@@ -318,6 +319,11 @@ int peba1_function_f_batch(LweSample *const *result_b, LweSample *const *const *
 int peba1_hamming_match_batch(LweSample *const *result_b, LweSample *const *a, LweSample *const *b, int nclients, int nbits,
                               LweSample *const *bound_match, CK *const *ck) {
     return record_batch(nclients, [&](int c) { peba1_hamming_match(result_b[c], a[c], b[c], nbits, bound_match[c], ck[c]); });
+}
+
+int peba1_hamming_match_csa_batch(LweSample *const *result_b, LweSample *const *a, LweSample *const *b, int nclients,
+                                  int nbits, LweSample *const *bound_match, CK *const *ck) {
+    return record_batch(nclients, [&](int c) { peba1_hamming_match_csa(result_b[c], a[c], b[c], nbits, bound_match[c], ck[c]); });
 }
 
 }  // extern "C"

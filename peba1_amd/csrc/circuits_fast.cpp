@@ -15,15 +15,26 @@
 //
 // Written against the public gate API only (AND, ANDNY, ANDYN, OR, XOR, XNOR, MUX, NOT, COPY,
 // CONSTANT), so it runs on upstream TFHE, on libtfhe-hip and on the test providers alike.
+//
+// The *_fast3 / *_csa entries build their full adders from libtfhe-hip's three-input gates where the provider has
+// them (tfhe_hip_gate3, include/tfhe_hip.h: sum = XOR3, carry = MAJ3, 2 bootstraps at depth 1) and from 2 XOR + 1 MUX
+// (4 rotations at depth 2) elsewhere: the same decrypted results either way.
 #include <algorithm>
 #include <cstddef>
 #include <vector>
 
 #include "../../include/peba1_circuits.h"
 
+// weak, like the batch drivers' extensions in circuits.cpp: absent over a provider of the plain tfhe API
+extern "C" __attribute__((weak)) void tfhe_hip_gate3(int gate, int negate_mask, LweSample *result, const LweSample *a,
+                                                     const LweSample *b, const LweSample *c,
+                                                     const TFheGateBootstrappingCloudKeySet *bk);
+
 namespace {
 
 using CK = const TFheGateBootstrappingCloudKeySet;
+
+enum { GATE3_MAJ3 = 0, GATE3_XOR3 = 1 };   // enum TfheHipGate3
 
 // a wire: a sample, or the constant 0 (s == nullptr); depth = gate levels below it
 struct Net {
@@ -34,7 +45,8 @@ struct Net {
 
 class Builder {
 public:
-    explicit Builder(CK *ck) : ck_(ck) {}
+    // gate3: full adders from the three-input gates, if the provider has them
+    explicit Builder(CK *ck, bool gate3 = false) : ck_(ck), use3_(gate3 && tfhe_hip_gate3 != nullptr) {}
     ~Builder() {
         for (auto &c : chunks_) delete_gate_bootstrapping_ciphertext_array(CHUNK, c);
     }
@@ -69,6 +81,33 @@ public:
         return r;
     }
     CK *ck() const { return ck_; }
+    bool use3() const { return use3_; }
+    // three-input gate of three real wires (use3() only); bit i of negate_mask negates operand i
+    Net g_gate3(int gate, int negate_mask, Net a, Net b, Net c) {
+        Net r{fresh(), std::max(a.depth, std::max(b.depth, c.depth)) + 1};
+        tfhe_hip_gate3(gate, negate_mask, r.s, a.s, b.s, c.s, ck_);
+        return r;
+    }
+    // full adder of three real wires: XOR3 + MAJ3, or 2 XOR + 1 MUX; the carry only if asked for
+    struct SumCarry { Net sum, carry; };
+    SumCarry full_add(Net a, Net b, Net c, bool want_carry) {
+        SumCarry r;
+        if (use3_) {
+            r.sum = g_gate3(GATE3_XOR3, 0, a, b, c);
+            if (want_carry) r.carry = g_gate3(GATE3_MAJ3, 0, a, b, c);
+            return r;
+        }
+        const Net x = g_xor(a, b);
+        r.sum = g_xor(x, c);
+        if (want_carry) r.carry = g_mux(x, c, a);   // majority
+        return r;
+    }
+    SumCarry half_add(Net a, Net b, bool want_carry) {
+        SumCarry r;
+        r.sum = g_xor(a, b);
+        if (want_carry) r.carry = g_and(a, b);
+        return r;
+    }
 
 private:
     using Gate2 = void (*)(LweSample *, const LweSample *, const LweSample *, CK *);
@@ -86,6 +125,7 @@ private:
     }
     static constexpr int CHUNK = 4096;
     CK *ck_;
+    bool use3_;
     std::vector<LweSample *> chunks_;
     int used_ = CHUNK;
 };
@@ -96,6 +136,11 @@ std::vector<Net> abs_difference(Builder &B, LweSample *a, LweSample *b, int bits
     Net borrow;                                            // constant 0
     for (int i = 0; i < bits; ++i) {
         const Net ai = B.input(a + i), bi = B.input(b + i);
+        if (B.use3() && i > 0) {                           // difference and borrow of a full subtractor, 2 bootstraps
+            diff[i] = B.g_gate3(GATE3_XOR3, 0, ai, bi, borrow);
+            borrow = B.g_gate3(GATE3_MAJ3, 1, ai, bi, borrow);   // majority(~a, b, borrow in)
+            continue;
+        }
         const Net x = B.g_xor(ai, bi);
         diff[i] = B.g_xor(x, borrow);
         // borrow out = (~a & b) | (~(a ^ b) & borrow in)
@@ -128,9 +173,9 @@ void compress_columns(Builder &B, std::vector<std::vector<Net>> &cols) {
             size_t i = 0;
             for (; i + 3 <= c.size() && c.size() > 2; i += 3) {
                 any = true;
-                const Net x = B.g_xor(c[i], c[i + 1]);
-                next[w].push_back(B.g_xor(x, c[i + 2]));
-                if (w + 1 < width) next[w + 1].push_back(B.g_mux(x, c[i + 2], c[i]));   // majority
+                const Builder::SumCarry fa = B.full_add(c[i], c[i + 1], c[i + 2], w + 1 < width);
+                next[w].push_back(fa.sum);
+                if (w + 1 < width) next[w + 1].push_back(fa.carry);
             }
             for (; i < c.size(); ++i) next[w].push_back(c[i]);
         }
@@ -202,6 +247,35 @@ std::vector<Net> squared_distance(Builder &B, LweSample *const *a, LweSample *co
     return prefix_add(B, cols);
 }
 
+// population count of `bits` on `width` wires: a carry-save compressor that takes every column down to ONE wire --
+// the three shallowest wires of a column into a full adder, the last two into a half adder, carries into the next
+// column, columns from the lowest up; carries out of the top column are dropped (the count fits `width` bits)
+std::vector<Net> count_ones(Builder &B, const std::vector<Net> &bits, int width) {
+    std::vector<std::vector<Net>> cols(width);
+    cols[0] = bits;
+    std::vector<Net> count(width);
+    for (int w = 0; w < width; ++w) {
+        std::vector<Net> &c = cols[w];
+        const bool carry = w + 1 < width;
+        while (c.size() > 1) {
+            std::stable_sort(c.begin(), c.end(), [](const Net &x, const Net &y) { return x.depth < y.depth; });
+            const size_t take = c.size() >= 3 ? 3 : 2;
+            const Builder::SumCarry r = take == 3 ? B.full_add(c[0], c[1], c[2], carry) : B.half_add(c[0], c[1], carry);
+            c.erase(c.begin(), c.begin() + take);
+            c.push_back(r.sum);
+            if (carry) cols[w + 1].push_back(r.carry);
+        }
+        if (!c.empty()) count[w] = c[0];
+    }
+    return count;
+}
+
+std::vector<Net> hamming_count(Builder &B, LweSample *a, LweSample *b, int nbits, int width) {
+    std::vector<Net> x(nbits);
+    for (int i = 0; i < nbits; ++i) x[i] = B.g_xor(B.input(a + i), B.input(b + i));
+    return count_ones(B, x, width);
+}
+
 void store(Builder &B, LweSample *dst, Net v) {
     if (v.zero()) bootsCONSTANT(dst, 0, B.ck());
     else bootsCOPY(dst, v.s, B.ck());
@@ -244,6 +318,31 @@ void peba1_function_f_fast(LweSample *result_b, LweSample *const *a, LweSample *
     const std::vector<Net> dist = squared_distance(B, a, b, nslots, bitsize, width);
     store(B, result_b, greater_than(B, dist, bound_match, width));
     for (int i = 1; i < width; ++i) bootsCONSTANT(result_b + i, 0, ck);    // as minimum() leaves them, Math.cpp:282-285
+}
+
+// peba1_function_f_fast's DAG with the full adders of its compressor and of its borrow chain in the 2-bootstrap form
+void peba1_function_f_fast3(LweSample *result_b, LweSample *const *a, LweSample *const *b, int nslots,
+                            LweSample *bound_match, int bitsize, CK *ck) {
+    const int width = 3 * bitsize;
+    Builder B(ck, true);
+    const std::vector<Net> dist = squared_distance(B, a, b, nslots, bitsize, width);
+    store(B, result_b, greater_than(B, dist, bound_match, width));
+    for (int i = 1; i < width; ++i) bootsCONSTANT(result_b + i, 0, ck);
+}
+
+void peba1_hamming_distance_csa(LweSample *count, LweSample *a, LweSample *b, int nbits, CK *ck) {
+    const int w = peba1_hamming_count_bits(nbits);
+    Builder B(ck, true);
+    const std::vector<Net> cnt = hamming_count(B, a, b, nbits, w);
+    for (int i = 0; i < w; ++i) store(B, count + i, cnt[i]);
+}
+
+void peba1_hamming_match_csa(LweSample *result_b, LweSample *a, LweSample *b, int nbits, LweSample *bound_match, CK *ck) {
+    const int w = peba1_hamming_count_bits(nbits);
+    Builder B(ck, true);
+    const std::vector<Net> cnt = hamming_count(B, a, b, nbits, w);
+    store(B, result_b, greater_than(B, cnt, bound_match, w));
+    for (int i = 1; i < w; ++i) bootsCONSTANT(result_b + i, 0, ck);     // as peba1_minimum leaves them
 }
 
 }  // extern "C"

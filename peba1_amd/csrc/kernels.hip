@@ -165,16 +165,26 @@ __global__ __launch_bounds__(128) void negacyclic_kernel(const int32_t *__restri
 // ---------------------------------------------------------------------------
 // shared pieces of the blind-rotate kernels
 // ---------------------------------------------------------------------------
-// K1: t = (0,c0) + sa*A + sb*B, modulus switch to Z_{2N} (tfhe modSwitchFromTorus32)
+// K1: t = (0,c0) + sa*A + sb*B (+ sc*C), modulus switch to Z_{2N} (tfhe modSwitchFromTorus32).  rd comes from a
+// workgroup-uniform address, so the test for a third operand is uniform; a two-input gate never forms C's address
 template <int LOGN, int THREADS>
 __device__ __forceinline__ void prelude_modswitch(const DevParams &p, const RotDesc &rd, const int32_t *__restrict__ pool,
                                                   uint16_t *lds_bar, int tid) {
     const int32_t *A = pool + (size_t)rd.slot_a * p.ct_stride;
     const int32_t *B = pool + (size_t)rd.slot_b * p.ct_stride;
-    for (int i = tid; i <= p.n; i += THREADS) {
-        uint32_t t = (uint32_t)rd.sa * (uint32_t)A[i] + (uint32_t)rd.sb * (uint32_t)B[i];
-        if (i == p.n) t += (uint32_t)rd.c0;
-        lds_bar[i] = (uint16_t)((t + (1u << (30 - LOGN))) >> (31 - LOGN));     // round(t * 2N / 2^32) mod 2N
+    if (rd.slot_c < 0) {
+        for (int i = tid; i <= p.n; i += THREADS) {
+            uint32_t t = (uint32_t)rd.sa * (uint32_t)A[i] + (uint32_t)rd.sb * (uint32_t)B[i];
+            if (i == p.n) t += (uint32_t)rd.c0;
+            lds_bar[i] = (uint16_t)((t + (1u << (30 - LOGN))) >> (31 - LOGN));     // round(t * 2N / 2^32) mod 2N
+        }
+    } else {
+        const int32_t *C = pool + (size_t)rd.slot_c * p.ct_stride;
+        for (int i = tid; i <= p.n; i += THREADS) {
+            uint32_t t = (uint32_t)rd.sa * (uint32_t)A[i] + (uint32_t)rd.sb * (uint32_t)B[i] + (uint32_t)rd.sc * (uint32_t)C[i];
+            if (i == p.n) t += (uint32_t)rd.c0;
+            lds_bar[i] = (uint16_t)((t + (1u << (30 - LOGN))) >> (31 - LOGN));
+        }
     }
 }
 

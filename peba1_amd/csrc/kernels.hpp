@@ -33,13 +33,16 @@ struct DevKey {
                              // then the same for the two half transforms of the split kernels, 6N words each
 };
 
-// One blind rotation: t = (0, c0) + sa * slot_a + sb * slot_b, then
-// modswitch, blind rotate, sample extract into u_buf[u_index].
+// One blind rotation: t = (0, c0) + sa * slot_a + sb * slot_b (+ sc * slot_c), then
+// modswitch, blind rotate, sample extract into u_buf[u_index].  slot_c = -1: no third operand (every upstream gate);
+// the three-input gates of tfhe_hip_gate3 set it.  The kernels read slot_c's words only when it is >= 0.
 struct RotDesc {
     int32_t slot_a, slot_b;
     int32_t sa, sb;
     int32_t c0;
     int32_t u_index;
+    int32_t slot_c = -1;
+    int32_t sc = 0;
 };
 
 // One key switch: (u_buf[u0] (+ u_buf[u1]) + (0, add_b)) -> pool[dst_slot].

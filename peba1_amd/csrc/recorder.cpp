@@ -336,6 +336,48 @@ void record_mux_locked(LweSample *result, const LweSample *a, const LweSample *b
     record_op(OP_MUX, result, pool, sa, sb, sc);
 }
 
+// Three-input gates (tfhe_hip_gate3): gate = enum TfheHipGate3, bit i of negate_mask negates operand i.  The operands are
+// recorded in slot order with their mask bits (the prelude's sum commutes word for word), so the same gate of the same
+// samples in another order shares the pending result.
+void record_gate3_locked(int gate, int negate_mask, LweSample *result, const LweSample *a, const LweSample *b,
+                         const LweSample *c, const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    begin_op(bk);
+    SlotPool *pool = r.pool;
+    bind_pool(result, pool);
+    struct Operand { int32_t slot; int neg; const LweSample *sample; };
+    Operand in[3] = {{ensure_slot(a, pool), negate_mask & 1, a}, {ensure_slot(b, pool), (negate_mask >> 1) & 1, b},
+                     {ensure_slot(c, pool), (negate_mask >> 2) & 1, c}};
+    if (r.fold_constants) {
+        int nconst = 0, which = -1;
+        for (int i = 0; i < 3; ++i)
+            if (const_bit(pool, in[i].slot) >= 0) { ++nconst; which = i; }
+        if (nconst > 0) {
+            // one constant operand v: the two-input gate of the other two, x and y, with the same truth table --
+            // MAJ3 -> AND (v = 0) / OR (v = 1), XOR3 -> XOR / XNOR -- the negations carried into its variant.  More
+            // constants: that gate folds again by its own rule (and counts the fold there)
+            const int v = const_bit(pool, in[which].slot) ^ in[which].neg;
+            const Operand &x = in[which == 0 ? 1 : 0], &y = in[which == 2 ? 1 : 2];
+            int code;
+            if (gate == TFHE_HIP_MAJ3) {
+                static const int AND_CODE[4] = {TFHE_HIP_AND, TFHE_HIP_ANDNY, TFHE_HIP_ANDYN, TFHE_HIP_NOR};
+                static const int OR_CODE[4] = {TFHE_HIP_OR, TFHE_HIP_ORNY, TFHE_HIP_ORYN, TFHE_HIP_NAND};
+                code = (v ? OR_CODE : AND_CODE)[x.neg + 2 * y.neg];
+            } else {
+                const int odd = v ^ x.neg ^ y.neg ^ (gate == TFHE_HIP_XNOR3 ? 1 : 0);
+                code = odd ? TFHE_HIP_XNOR : TFHE_HIP_XOR;
+            }
+            if (nconst == 1) ++Engine::get().stats.folded_gates;
+            return record_gate2_locked(code, result, x.sample, y.sample, bk);
+        }
+    }
+    if (in[1].slot < in[0].slot) std::swap(in[0], in[1]);
+    if (in[2].slot < in[1].slot) std::swap(in[1], in[2]);
+    if (in[1].slot < in[0].slot) std::swap(in[0], in[1]);
+    const int mask = in[0].neg | in[1].neg << 1 | in[2].neg << 2;
+    record_op(OP_GATE3 + 8 * gate + mask, result, pool, in[0].slot, in[1].slot, in[2].slot);
+}
+
 void record_constant_locked(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk) {
     Recorder &r = rec();
     begin_op(bk);

@@ -38,6 +38,8 @@ void record_gate2_locked(int code, LweSample *result, const LweSample *a, const 
 void record_not_locked(LweSample *result, const LweSample *a, const TFheGateBootstrappingCloudKeySet *bk);
 void record_mux_locked(LweSample *result, const LweSample *a, const LweSample *b, const LweSample *c,
                        const TFheGateBootstrappingCloudKeySet *bk);
+void record_gate3_locked(int gate, int negate_mask, LweSample *result, const LweSample *a, const LweSample *b,
+                         const LweSample *c, const TFheGateBootstrappingCloudKeySet *bk);
 void record_constant_locked(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk);
 void record_copy_locked(LweSample *result, const LweSample *a, const TFheGateBootstrappingCloudKeySet *bk);
 

@@ -194,6 +194,12 @@ LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<
             plan.rots[i0] = RotDesc{op.a, op.b, 1, 1, -(mu), i0 - base};
             plan.rots[i1] = RotDesc{op.a, op.c, -1, 1, -(mu), i1 - base};
             plan.kss[kpos[sg]++] = KsDesc{i0 - base, i1 - base, mu, op.dst};
+        } else if (op_is_gate3(op.kind)) {
+            // t = sa A + sb B + sc C, c0 = 0: one rotation, one key switch
+            const int32_t i0 = rpos[sg]++;
+            plan.rots[i0] = RotDesc{op.a, op.b, gate3_coef(op.kind, 0), gate3_coef(op.kind, 1), 0, i0 - base,
+                                    op.c, gate3_coef(op.kind, 2)};
+            plan.kss[kpos[sg]++] = KsDesc{i0 - base, -1, 0, op.dst};
         } else {
             const GateLin &gl = GATE_LIN[op.kind];
             const int32_t i0 = rpos[sg]++;

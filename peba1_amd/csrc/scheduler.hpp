@@ -16,12 +16,17 @@
 namespace tfhe_hip {
 
 struct PendingOp {
-    uint8_t kind;       // 0..9 two-input gate code, OP_MUX, OP_NOT
+    uint8_t kind;       // 0..9 two-input gate code, OP_MUX, OP_NOT, OP_GATE3 + 8 gate + negation mask
     int32_t dst, a, b, c;   // slots; b, c = -1 when absent
     int32_t level;      // ASAP level (NOT: the level of its operand, 0 = already materialised)
     uint16_t key = 0;   // index of the gate's cloud key in the flush's key list (recorder "batch_keys"; NOT: unused)
 };
 constexpr uint8_t OP_MUX = 16, OP_NOT = 17;
+// three-input gates (tfhe_hip_gate3; not in upstream's API): kind = OP_GATE3 + 8 * gate + mask, gate = enum TfheHipGate3,
+// bit i of mask negates operand i (a = bit 0) -- 32..55.  The mask is part of the kind, hence of the recorder's index key
+constexpr uint8_t OP_GATE3 = 32, OP_GATE3_END = OP_GATE3 + 3 * 8;
+inline bool op_is_gate3(int kind) { return kind >= OP_GATE3 && kind < OP_GATE3_END; }
+inline bool op_kind_valid(int kind) { return (kind >= 0 && kind < 10) || kind == OP_MUX || kind == OP_NOT || op_is_gate3(kind); }
 
 inline int op_rotations(const PendingOp &op) { return op.kind == OP_NOT ? 0 : (op.kind == OP_MUX ? 2 : 1); }
 
@@ -31,6 +36,14 @@ constexpr GateLin GATE_LIN[10] = {
     {1, -1, -1}, {1, 1, 1}, {-1, 1, 1}, {-1, -1, -1}, {2, 2, 2}, {-2, -2, -2},
     {-1, -1, 1}, {-1, 1, -1}, {1, -1, 1}, {1, 1, -1},
 };
+
+// prelude coefficient of the three-input gates, by gate: t = s (+-A +- B +- C), c0 = 0 (MAJ3, XOR3, XNOR3); a set
+// mask bit flips the sign of its operand's coefficient
+constexpr int32_t GATE3_LIN[3] = {1, -2, 2};
+inline int32_t gate3_coef(int kind, int operand) {
+    const int32_t s = GATE3_LIN[(kind - OP_GATE3) >> 3];
+    return ((kind - OP_GATE3) >> operand) & 1 ? -s : s;
+}
 
 // Fills lvl[i] with the level at which ops[i] runs (bootstrapped gates: 1..depth,
 // NOTs: 0..depth, executed after the gates of that level).  `unit` = rotations one

@@ -2,6 +2,7 @@
 // /root/reference/src/Math.cpp and src/main.cpp bind plus the
 // tfhe_hip_* extensions.  Host logic only: the array headers, keys, I/O glue, tunings and statistics; the
 // boots* gate entries hand over to the recorder (recorder.hpp).  No gate arithmetic happens here.
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -536,6 +537,35 @@ int tfhe_hip_gate_batch(int gate, LweSample *result, const LweSample *a, const L
     return rc;
 }
 
+static bool gate3_args_ok(const char *who, int gate, int negate_mask) {
+    if (gate < TFHE_HIP_MAJ3 || gate > TFHE_HIP_XNOR3) { set_error(std::string(who) + ": bad gate code"); return false; }
+    if (negate_mask < 0 || negate_mask > 7) { set_error(std::string(who) + ": bad negation mask"); return false; }
+    return true;
+}
+
+void tfhe_hip_gate3(int gate, int negate_mask, LweSample *result, const LweSample *a, const LweSample *b, const LweSample *c,
+                    const TFheGateBootstrappingCloudKeySet *bk) {
+    if (!gate3_args_ok("tfhe_hip_gate3", gate, negate_mask)) return;
+    guarded([&] {
+        auto g = recorder_lock();
+        record_gate3_locked(gate, negate_mask, result, a, b, c, bk);
+    });
+}
+
+int tfhe_hip_gate3_batch(int gate, int negate_mask, LweSample *result, const LweSample *a, const LweSample *b,
+                         const LweSample *c, int32_t count, const TFheGateBootstrappingCloudKeySet *bk) {
+    if (!gate3_args_ok("tfhe_hip_gate3_batch", gate, negate_mask)) return -1;
+    auto g = recorder_lock();
+    const bool was = set_deferred_locked(true);
+    const int rc = guarded_rc([&] {
+        for (int32_t i = 0; i < count; ++i) record_gate3_locked(gate, negate_mask, &result[i], &a[i], &b[i], &c[i], bk);
+        return 0;
+    });
+    set_deferred_locked(was);
+    if (!was) flush_locked();      // gates recorded before a refused one still run
+    return rc;
+}
+
 void tfhe_hip_test_set_alloc_cap(int64_t bytes) {
     auto g = recorder_lock();
     set_alloc_cap((long long)bytes);
@@ -585,6 +615,8 @@ int tfhe_hip_set_batch_keys(int on) {
 
 static int test_build_ops(const int32_t *ops5, int32_t count, std::vector<PendingOp> &ops) {
     // ops5[i] = {kind, dst, a, b, c}; ASAP levels are derived here exactly as the recorder derives them
+    for (int32_t i = 0; i < count; ++i)
+        if (!op_kind_valid(ops5[5 * (size_t)i])) { set_error("test schedule: unknown op kind"); return -1; }
     ops.resize((size_t)count);
     std::vector<int32_t> slot_level;
     int depth = 0;
@@ -605,20 +637,23 @@ static int test_build_ops(const int32_t *ops5, int32_t count, std::vector<Pendin
 int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int32_t balance, int32_t *levels_out) {
     std::vector<PendingOp> ops;
     const int depth = test_build_ops(ops5, count, ops);
+    if (depth < 0) return -1;
     std::vector<int32_t> lvl;
     const int d = schedule_levels(ops, depth, balance != 0, unit, lvl);
     for (int32_t i = 0; i < count; ++i) levels_out[i] = lvl[i];
     return d;
 }
 
-int tfhe_hip_test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
-                             int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
-                             int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots6, int32_t *kss4) {
+// rot_words = 6: the two-operand words of every rotation (the form older callers know); 8: slot_c and sc as well
+static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                           int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
+                           int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots, int rot_words, int32_t *kss4) {
     if (count < 0 || nkeys < 1 || nkeys > UINT16_MAX) { set_error("test_level_plan: bad count or nkeys"); return -1; }
     for (int32_t i = 0; i < count; ++i)
         if (op_keys[i] < 0 || op_keys[i] >= nkeys) { set_error("test_level_plan: key index out of range"); return -1; }
     std::vector<PendingOp> ops;
     const int depth = test_build_ops(ops5, count, ops);
+    if (depth < 0) return -1;
     for (int32_t i = 0; i < count; ++i) ops[i].key = (uint16_t)op_keys[i];
     std::vector<int32_t> lvl;
     const int levels = schedule_levels(ops, depth, balance != 0, unit, lvl);
@@ -630,16 +665,30 @@ int tfhe_hip_test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_
     sizes6[3] = (int32_t)plan.rot_koff.size();
     sizes6[4] = (int32_t)plan.ks_koff.size();
     sizes6[5] = (int32_t)plan.rot_key.size();
-    static_assert(sizeof(RotDesc) == 6 * sizeof(int32_t) && sizeof(KsDesc) == 4 * sizeof(int32_t), "descriptors are plain words");
+    static_assert(sizeof(RotDesc) == 8 * sizeof(int32_t) && offsetof(RotDesc, slot_c) == 6 * sizeof(int32_t) &&
+                      sizeof(KsDesc) == 4 * sizeof(int32_t), "descriptors are plain words, the third operand last");
     auto copy = [](int32_t *dst, const void *src, size_t words) { if (words) std::memcpy(dst, src, words * sizeof(int32_t)); };
     copy(rot_off, plan.rot_off.data(), plan.rot_off.size());
     copy(ks_off, plan.ks_off.data(), plan.ks_off.size());
     copy(rot_koff, plan.rot_koff.data(), plan.rot_koff.size());
     copy(ks_koff, plan.ks_koff.data(), plan.ks_koff.size());
     copy(rot_key, plan.rot_key.data(), plan.rot_key.size());
-    copy(rots6, plan.rots.data(), 6 * plan.rots.size());
+    for (size_t r = 0; r < plan.rots.size(); ++r) copy(rots + (size_t)rot_words * r, &plan.rots[r], (size_t)rot_words);
     copy(kss4, plan.kss.data(), 4 * plan.kss.size());
     return levels;
+}
+
+int tfhe_hip_test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                             int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
+                             int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots6, int32_t *kss4) {
+    return test_level_plan(ops5, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
+                           rot_key, rots6, 6, kss4);
+}
+int tfhe_hip_test_level_plan3(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                              int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
+                              int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots8, int32_t *kss4) {
+    return test_level_plan(ops5, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
+                           rot_key, rots8, 8, kss4);
 }
 
 

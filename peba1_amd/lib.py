@@ -127,6 +127,8 @@ SIGNATURES = {
     "tfhe_hip_wait_event": (C.c_int, [C.c_void_p, C.c_char_p]),
     "tfhe_hip_set_diag_label": (None, [C.c_char_p]),
     "tfhe_hip_gate_batch": (C.c_int, [C.c_int, LS, LS, LS, C.c_int32, CK]),
+    "tfhe_hip_gate3": (None, [C.c_int, C.c_int, LS, LS, LS, LS, CK]),
+    "tfhe_hip_gate3_batch": (C.c_int, [C.c_int, C.c_int, LS, LS, LS, LS, C.c_int32, CK]),
     "tfhe_hip_set_tuning": (C.c_int, [C.c_char_p, C.c_int64]),
     "tfhe_hip_test_form_admissible": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int]),
     "tfhe_hip_test_set_alloc_cap": (None, [C.c_int64]),
@@ -137,6 +139,7 @@ SIGNATURES = {
     "tfhe_hip_set_batch_keys": (C.c_int, [C.c_int]),
     "tfhe_hip_test_schedule": (C.c_int, [I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_level_plan": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [I32P] * 9),
+    "tfhe_hip_test_level_plan3": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [I32P] * 9),
     "tfhe_hip_kernel_negacyclic":(C.c_int, [CK, I32P, I32P, I32P, C.c_int32]),
     "tfhe_hip_kernel_bootstrap_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P]),
     "tfhe_hip_kernel_keyswitch": (C.c_int, [CK, I32P, C.c_int32, I32P]),
