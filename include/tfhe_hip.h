@@ -242,6 +242,16 @@ typedef struct TfheHipStats {
     /* gates answered WITHOUT a bootstrap because an operand was a public constant (a trivial sample): "fold_constants",
      * opt-in; a MUX turned into a two-input gate counts once */
     uint64_t folded_gates;
+    /* blind-rotate kernel launches by the form that really ran (after the fallback of br_forms.hpp) and by the digit-table
+     * mode it ran with, counted where the kernel is launched -- the raw test path (tfhe_hip_kernel_bootstrap_woks)
+     * included, which the totals above leave out.  A level split into a 4-wave launch and an 8-wave tail counts one of each. */
+    uint64_t br_wide4_launches;
+    uint64_t br_split_launches;
+    uint64_t br_wave8_launches;
+    uint64_t br_wave2_launches;
+    uint64_t br_tables0_launches;
+    uint64_t br_tables1_launches;
+    uint64_t br_tables2_launches;
 } TfheHipStats;
 void tfhe_hip_get_stats(TfheHipStats *out);
 void tfhe_hip_reset_stats(void);

@@ -613,6 +613,12 @@ bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const Rot
     const int form = br_form(key, count, &tables);
     if (mk_keys && form != BR_FORM_WIDE4 && form != BR_FORM_WAVE8) fatal("launch_br: no multi-key kernel for this form");
     dp.digit_table = tables;
+    // per-form and per-table-mode launch counters (TfheHipStats): what ran, whatever the tunings asked for
+    auto note = [&](int f) {
+        ++(f == BR_FORM_WIDE4 ? stats.br_wide4_launches : f == BR_FORM_SPLIT ? stats.br_split_launches
+           : f == BR_FORM_WAVE8 ? stats.br_wave8_launches : stats.br_wave2_launches);
+        ++(tables == 0 ? stats.br_tables0_launches : tables == 1 ? stats.br_tables1_launches : stats.br_tables2_launches);
+    };
     if (kernel_timing) {
         if (!clock_acc_) {
             hip_check(hipMalloc(&clock_acc_, 2 * sizeof(unsigned long long)), "hipMalloc(clock sums)");
@@ -621,15 +627,18 @@ bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const Rot
         dp.clock_acc = clock_acc_;
     }
     if (form == BR_FORM_WAVE2) {
+        note(form);
         launch_blind_rotate2(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
         return false;
     }
     if (form == BR_FORM_SPLIT) {
+        note(form);
         launch_blind_rotate_split(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
         return false;
     }
     dp.wg_times = wg_times_dbg_;
     if (form == BR_FORM_WAVE8) {
+        note(form);
         if (mk_keys) launch_blind_rotate8_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count, u_buf);
         else launch_blind_rotate8(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
         return true;
@@ -639,6 +648,8 @@ bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const Rot
     const int round = 2 * cu_count_, tail = count % round;
     if (br_tail8 && count > round && tail > 0 && tail <= std::min(br8_max_rotations, cu_count_) && dp.l >= 2 &&
         !acc_dbg && !wg_times_dbg_ && key->form_ok[BR_FORM_WAVE8][tables]) {
+        note(BR_FORM_WIDE4);
+        note(BR_FORM_WAVE8);
         if (mk_keys) launch_blind_rotate4_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count - tail, u_buf);
         else launch_blind_rotate4(stream, dp, key->key, pool, rots, count - tail, u_buf, nullptr);
         tail_count_ = tail;
@@ -650,6 +661,7 @@ bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const Rot
         else launch_blind_rotate8(stream, dp, key->key, pool, rots + (count - tail), tail, u_buf, nullptr);
         return false;
     }
+    note(BR_FORM_WIDE4);
     if (mk_keys) launch_blind_rotate4_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count, u_buf);
     else launch_blind_rotate4(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
     return false;

@@ -54,7 +54,11 @@ class Stats(C.Structure):
                 ("ms_blind_rotate_busy", C.c_double), ("reused_gates", C.c_uint64),
                 ("br8_launches", C.c_uint64), ("br8_rotations", C.c_uint64), ("ms_blind_rotate8", C.c_double),
                 ("clk_shader_cycles", C.c_uint64), ("clk_ref_ticks", C.c_uint64), ("dead_gates", C.c_uint64),
-                ("folded_gates", C.c_uint64)]
+                ("folded_gates", C.c_uint64),
+                ("br_wide4_launches", C.c_uint64), ("br_split_launches", C.c_uint64),
+                ("br_wave8_launches", C.c_uint64), ("br_wave2_launches", C.c_uint64),
+                ("br_tables0_launches", C.c_uint64), ("br_tables1_launches", C.c_uint64),
+                ("br_tables2_launches", C.c_uint64)]
 
 
 PS = C.POINTER(ParameterSet)
