@@ -208,7 +208,7 @@ int tfhe_hip_gate3_batch(int gate, int negate_mask, LweSample *result, const Lwe
  * such a flush stays alive until it has run (deleting a keyset runs the whole recording first).
  * "sync_deadline_ms": see "bounded host waits" above.
  * (Environment only: TFHE_HIP_KS_BLOCKS / TFHE_HIP_KS_MAX_SPLITS / TFHE_HIP_KS_SPLIT_TIES, how key switches are cut into
- * coefficient ranges -- engine.hpp.)
+ * coefficient ranges -- peba1_amd/csrc/launch_plan.hpp.)
  * Returns 0, or -1 for an unknown name. */
 int tfhe_hip_set_tuning(const char *name, int64_t value);
 
@@ -294,6 +294,21 @@ int tfhe_hip_test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_
 int tfhe_hip_test_level_plan3(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
                               int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
                               int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots8, int32_t *kss4);
+/* ---- host-logic test entries: the launch rules of peba1_amd/csrc/launch_plan.hpp, without touching the device.
+ * tfhe_hip_test_br_plan: the blind-rotate launches of a level of `count` rotations of gadget (l, Bgbit) at ring size N on
+ * a card of `cu_count` CUs under tunings4 = {br_variant, br8_max_rotations, br_tail8, br_digit_table}; flags bit 0 = the
+ * workgroup-time probe is on, bit 1 = the raw accumulators are read back.  out3 = {form (as tfhe_hip_test_form_admissible;
+ * -1: no form admits the gadget), digit-table mode, tail}: tail > 0 = the first count - tail rotations on the 4-wave form,
+ * the last `tail` on the 8-wave form as a second launch.
+ * tfhe_hip_test_ks_plan: the key-switch launches of `count` gates of a set with LWE dimension n, ring (N, k) and key-switch
+ * digits (ks_t, ks_basebit) under tunings5 = {ks_target_blocks, ks_max_splits, ks_split_ties, ks_tile, ks_index}.
+ * out6 = {tiled kernel 1 / 0, gates per tile (0: per-gate kernel), gates per launch (all launches but the last), coefficient
+ * ranges of the first launch, of the last launch, bytes of partial sums the whole sequence needs}.
+ * Both return 0, -1 on bad arguments. ---- */
+int tfhe_hip_test_br_plan(int32_t N, int32_t l, int32_t Bgbit, const int32_t *tunings4, int32_t cu_count, int32_t count,
+                          int32_t flags, int32_t *out3);
+int tfhe_hip_test_ks_plan(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
+                          int32_t cu_count, int32_t count, int64_t *out6);
 /* Diagnostic (tools/wg_times.py): a 4-wave blind-rotate launch of `width` random gates (the second of two back to back);
  * times4[4i .. 4i+3] = s_memtime (shader cycles; the start stamp carries the XCC / CU id in its top 16
  * bits) at the start and end of workgroup i, then s_memrealtime (constant 100 MHz) at its start and

@@ -161,11 +161,11 @@ void Engine::ensure_init() {
     if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
         fatal("no HIP device available: libtfhe-hip evaluates gates on the GPU only (there is no CPU fallback)");
     if (const char *env = std::getenv("TFHE_HIP_DEVICE")) device_ = std::atoi(env);
-    if (const char *env = std::getenv("TFHE_HIP_KS_BLOCKS")) ks_target_blocks = std::atoi(env);
-    if (const char *env = std::getenv("TFHE_HIP_KS_MAX_SPLITS")) ks_max_splits = std::atoi(env);
-    if (const char *env = std::getenv("TFHE_HIP_KS_TILE")) ks_tile = std::atoi(env);
-    if (const char *env = std::getenv("TFHE_HIP_KS_INDEX")) ks_index = std::atoi(env);
-    if (const char *env = std::getenv("TFHE_HIP_KS_SPLIT_TIES")) ks_split_ties = std::atoi(env);
+    if (const char *env = std::getenv("TFHE_HIP_KS_BLOCKS")) tunings.ks_target_blocks = std::atoi(env);
+    if (const char *env = std::getenv("TFHE_HIP_KS_MAX_SPLITS")) tunings.ks_max_splits = std::atoi(env);
+    if (const char *env = std::getenv("TFHE_HIP_KS_TILE")) tunings.ks_tile = std::atoi(env);
+    if (const char *env = std::getenv("TFHE_HIP_KS_INDEX")) tunings.ks_index = std::atoi(env);
+    if (const char *env = std::getenv("TFHE_HIP_KS_SPLIT_TIES")) tunings.ks_split_ties = std::atoi(env);
     DeviceScope bind(device_);               // (an invalid device shows at the first runtime call below)
     {
         int cur = -1;
@@ -181,10 +181,10 @@ void Engine::ensure_init() {
         hip_check(hipDeviceGetStreamPriorityRange(&least, &greatest), "priority range");
         hip_check(hipStreamCreateWithPriority(&stream_, hipStreamNonBlocking, greatest), "hipStreamCreate");
     }
-    if (const char *env = std::getenv("TFHE_HIP_BR8_MAX")) br8_max_rotations = std::atoi(env);
-    if (const char *env = std::getenv("TFHE_HIP_BR_TAIL8")) br_tail8 = std::atoi(env);
-    if (const char *env = std::getenv("TFHE_HIP_BR_VARIANT")) br_variant = std::atoi(env);
-    if (const char *env = std::getenv("TFHE_HIP_BR_TABLE")) br_digit_table = std::atoi(env);
+    if (const char *env = std::getenv("TFHE_HIP_BR8_MAX")) tunings.br8_max_rotations = std::atoi(env);
+    if (const char *env = std::getenv("TFHE_HIP_BR_TAIL8")) tunings.br_tail8 = std::atoi(env);
+    if (const char *env = std::getenv("TFHE_HIP_BR_VARIANT")) tunings.br_variant = std::atoi(env);
+    if (const char *env = std::getenv("TFHE_HIP_BR_TABLE")) tunings.br_digit_table = std::atoi(env);
     if (const char *env = std::getenv("TFHE_HIP_SYNC_DEADLINE_MS")) sync_deadline_ms = std::atoll(env);
     // a caller that cannot reach tfhe_hip_set_kernel_timing (the reference's unmodified program) asks for the per-level
     // times by naming the trace file
@@ -396,8 +396,7 @@ DeviceKeyImage *Engine::upload_key(const TfheHipCloudKey &ck) {
     if (const char *why = unsupported_reason(p)) api_fail(why);
     auto *img = new DeviceKeyImage();
     img->dp = make_dev_params(p);
-    for (int f = 0; f < BR_FORM_COUNT; ++f)
-        for (int t = 0; t < 3; ++t) img->form_ok[f][t] = br_form_admissible(f, p.N, p.l, p.Bgbit, t);
+    fill_form_ok(img->form_ok, p.N, p.l, p.Bgbit);
     uint32_t scale[2];
     const std::vector<uint32_t> tw = make_twiddles(p.N, scale);
     const size_t bk_words = p.bk_words();
@@ -571,53 +570,27 @@ hipEvent_t Engine::next_timing_event() {
     return timing_events_[timing_used_++];
 }
 
-int Engine::br_form(const DeviceKeyImage *key, int count, int *tables_out) const {
-    const DevParams &dp = key->dp;
-    // the form the tunings ask for ...
-    int form;
-    if (br_variant == 4 && dp.N == 1024) form = BR_FORM_WAVE2;
-    else if (br_variant == 2 || dp.N == 2048) form = BR_FORM_SPLIT;
-    // launches that leave CUs with at most one workgroup: the 8-wave form (a second wave per SIMD)
-    else if (br8_max_rotations > 0 && count <= std::min(br8_max_rotations, cu_count_) && dp.l >= 2 && !wg_times_dbg_)
-        form = BR_FORM_WAVE8;
-    else form = BR_FORM_WIDE4;
-    // the workgroup-time probe reads stamps only the 4-wave kernel writes
-    if (wg_times_dbg_ && dp.N == 1024) form = BR_FORM_WIDE4;
-    // ... if its magnitude bounds hold for this key's gadget (br_forms.hpp; every built-in set passes in every form of its
-    // ring); else the same form with smaller or no digit tables, else the next form of the order
-    int tables = br_digit_table < 0 || br_digit_table > 2 ? 0 : br_digit_table;
-    if (!key->form_ok[form][tables]) {
-        static const int order[BR_FORM_COUNT] = {BR_FORM_WIDE4, BR_FORM_SPLIT, BR_FORM_WAVE2, BR_FORM_WAVE8};
-        int pick_f = -1, pick_t = 0;
-        for (int k = -1; k < BR_FORM_COUNT && pick_f < 0; ++k) {
-            const int f = k < 0 ? form : order[k];
-            if (f == BR_FORM_WAVE8 && count > cu_count_) continue;          // its LDS allows one workgroup per CU only
-            for (int t : {tables, 2, 0})
-                if (key->form_ok[f][t]) { pick_f = f; pick_t = t; break; }
-        }
-        if (pick_f < 0) fatal("no admissible blind-rotate form (upload_key should have refused this key)");
-        form = pick_f; tables = pick_t;
-    }
-    if (tables_out) *tables_out = tables;
-    return form;
+BrPlan Engine::plan_br_launch(const DeviceKeyImage *key, int count, bool acc_dump) const {
+    const BrPlan plan = plan_br(key->form_ok, key->dp.N, key->dp.l, tunings, cu_count_, count, wg_times_dbg_ != nullptr, acc_dump);
+    if (plan.form < 0) fatal("no admissible blind-rotate form (upload_key should have refused this key)");
+    return plan;
 }
 
-bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const RotDesc *rots, int count, int32_t *u_buf,
-                       int32_t *acc_dbg, hipStream_t stream, const DevKey *mk_keys, const int32_t *mk_rot_keys) {
+void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int32_t *pool, const RotDesc *rots, int count,
+                       int32_t *u_buf, int32_t *acc_dbg, hipStream_t stream, const DevKey *mk_keys, const int32_t *mk_rot_keys,
+                       hipEvent_t *mid) {
     ENGINE_DEVICE_SCOPE();
     if (!stream) stream = stream_;
-    tail_event_ = nullptr;                   // what an earlier launch left is not this one's
-    tail_count_ = 0;
-    DevParams dp = key->dp;
-    int tables = 0;
-    const int form = br_form(key, count, &tables);
+    const int form = plan.form, head = count - plan.tail;
     if (mk_keys && form != BR_FORM_WIDE4 && form != BR_FORM_WAVE8) fatal("launch_br: no multi-key kernel for this form");
-    dp.digit_table = tables;
+    if (plan.tail && (form != BR_FORM_WIDE4 || acc_dbg)) fatal("launch_br: a tail behind a launch that cannot be split");
+    DevParams dp = key->dp;
+    dp.digit_table = plan.tables;
     // per-form and per-table-mode launch counters (TfheHipStats): what ran, whatever the tunings asked for
     auto note = [&](int f) {
         ++(f == BR_FORM_WIDE4 ? stats.br_wide4_launches : f == BR_FORM_SPLIT ? stats.br_split_launches
            : f == BR_FORM_WAVE8 ? stats.br_wave8_launches : stats.br_wave2_launches);
-        ++(tables == 0 ? stats.br_tables0_launches : tables == 1 ? stats.br_tables1_launches : stats.br_tables2_launches);
+        ++(plan.tables == 0 ? stats.br_tables0_launches : plan.tables == 1 ? stats.br_tables1_launches : stats.br_tables2_launches);
     };
     if (kernel_timing) {
         if (!clock_acc_) {
@@ -626,120 +599,43 @@ bool Engine::launch_br(const DeviceKeyImage *key, const int32_t *pool, const Rot
         }
         dp.clock_acc = clock_acc_;
     }
-    if (form == BR_FORM_WAVE2) {
-        note(form);
-        launch_blind_rotate2(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
-        return false;
-    }
-    if (form == BR_FORM_SPLIT) {
-        note(form);
-        launch_blind_rotate_split(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
-        return false;
-    }
-    dp.wg_times = wg_times_dbg_;
-    if (form == BR_FORM_WAVE8) {
-        note(form);
-        if (mk_keys) launch_blind_rotate8_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count, u_buf);
-        else launch_blind_rotate8(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
-        return true;
-    }
-    // the last, at most half-filled round of a wide launch on the 8-wave form (descriptors carry their own output
-    // index, so a level splits anywhere; the debug probes index by workgroup and keep one launch)
-    const int round = 2 * cu_count_, tail = count % round;
-    if (br_tail8 && count > round && tail > 0 && tail <= std::min(br8_max_rotations, cu_count_) && dp.l >= 2 &&
-        !acc_dbg && !wg_times_dbg_ && key->form_ok[BR_FORM_WAVE8][tables]) {
-        note(BR_FORM_WIDE4);
-        note(BR_FORM_WAVE8);
-        if (mk_keys) launch_blind_rotate4_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count - tail, u_buf);
-        else launch_blind_rotate4(stream, dp, key->key, pool, rots, count - tail, u_buf, nullptr);
-        tail_count_ = tail;
-        // the event between the two launches belongs to execute()'s per-flush set (reset there); the raw test paths and
-        // probes have no reader for it and must not grow the set
-        if (kernel_timing && in_execute_) { tail_event_ = next_timing_event(); hip_check(hipEventRecord(tail_event_, stream), "event"); }
-        if (mk_keys)
-            launch_blind_rotate8_mk(stream, dp, key->key, mk_keys, mk_rot_keys + (count - tail), pool, rots + (count - tail), tail, u_buf);
-        else launch_blind_rotate8(stream, dp, key->key, pool, rots + (count - tail), tail, u_buf, nullptr);
-        return false;
-    }
-    note(BR_FORM_WIDE4);
-    if (mk_keys) launch_blind_rotate4_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count, u_buf);
-    else launch_blind_rotate4(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
-    return false;
+    if (form == BR_FORM_WIDE4 || form == BR_FORM_WAVE8) dp.wg_times = wg_times_dbg_;
+    note(form);
+    if (form == BR_FORM_WAVE2) launch_blind_rotate2(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
+    else if (form == BR_FORM_SPLIT) launch_blind_rotate_split(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
+    else if (form == BR_FORM_WAVE8 && mk_keys) launch_blind_rotate8_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count, u_buf);
+    else if (form == BR_FORM_WAVE8) launch_blind_rotate8(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
+    else if (mk_keys) launch_blind_rotate4_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, head, u_buf);
+    else launch_blind_rotate4(stream, dp, key->key, pool, rots, head, u_buf, acc_dbg);
+    if (!plan.tail) return;
+    // the last round on the 8-wave form, with the event between the two launches where the caller has a reader for it
+    if (mid) { *mid = next_timing_event(); hip_check(hipEventRecord(*mid, stream), "event"); }
+    note(BR_FORM_WAVE8);
+    if (mk_keys) launch_blind_rotate8_mk(stream, dp, key->key, mk_keys, mk_rot_keys + head, pool, rots + head, plan.tail, u_buf);
+    else launch_blind_rotate8(stream, dp, key->key, pool, rots + head, plan.tail, u_buf, nullptr);
 }
 
-// The key-switch launch rule, one place for launch_ks and for execute()'s sizing of the partial sums: a launch of `count`
-// gates runs in chunks of at most KS_CHUNK gates when tiled (bounds the partial-sum buffer: 0.66 GB at P128), each chunk of
-// cnt gates in ks_splits(cnt) coefficient ranges.  Tiles of 24 or 32 gates exist in the index form only (kernels.hip
-// keyswitch_index_kernel); tile 0 = per-gate kernel only.
-constexpr int KS_CHUNK = 8192;
-static int ks_tile_size(const Engine &e) { return (e.ks_tile > 16 && !e.ks_index) ? 16 : e.ks_tile; }
+static KsShape ks_shape(const DevParams &dp) { return KsShape{dp.k * dp.N, dp.ks_t, dp.ks_basebit, dp.ct_stride}; }
 
-// the tiled kernel: wide launches, ranges of at most 64 input coefficients
-static bool ks_tiled(const Engine &e, int count, const DevParams &dp) {
-    const int tile = ks_tile_size(e);
-    return tile > 0 && count >= 2 * tile && dp.ks_t == 8 && dp.ks_basebit == 2 && e.ks_max_splits > 1 &&
-           (dp.k * dp.N + e.ks_max_splits - 1) / e.ks_max_splits <= 64;
-}
-
-static int ks_splits(const Engine &e, int cnt, const DevParams &dp) {
-    int splits = 1;
-    if (ks_tiled(e, cnt, dp)) {
-        // the number of coefficient ranges is free between nin/64 and ks_max_splits: take the
-        // one whose grid (tiles x ranges) fills whole rounds of the workgroups the chip holds,
-        // e.g. 36 tiles x 28 ranges = 1008 of 1024 slots in two rounds instead of 36 x 32 = 1152 in three
-        const int tile = ks_tile_size(e);
-        const int threads = ((dp.ct_stride / 4 + 63) / 64) * 64;
-        // index form: no LDS strips; 120 VGPRs at tile 16 (four waves per SIMD), 162 at 24 (three), 204 at 32 (two);
-        // strip form: ~235 VGPRs (two waves per SIMD) and 16 x threads x 16 bytes of strips
-        int per_cu = std::max(1, (tile == 16 ? 16 : tile == 24 ? 12 : 8) / (threads / 64));
-        if (!e.ks_index) {
-            const size_t lds = (size_t)16 * threads * 16 + (size_t)tile * 65 * 4;
-            per_cu = std::max(1, std::min((int)((160 * 1024) / lds), 8 / (threads / 64)));
-        }
-        const long long slots = (long long)e.cu_count() * per_cu;
-        const long long tiles = (cnt + tile - 1) / tile;
-        const int lo = std::max(2, (dp.k * dp.N + 63) / 64);
-        double best = -1.0;
-        for (int sp = lo; sp <= e.ks_max_splits; ++sp) {
-            const long long blocks = tiles * sp, rounds = (blocks + slots - 1) / slots;
-            const double eff = (double)blocks / (double)(rounds * slots);
-            // ties: fewer, longer ranges (less partial-sum traffic) or more, shorter ones (ks_split_ties)
-            if (e.ks_split_ties ? eff >= best - 1e-9 : eff > best + 1e-9) { best = eff; splits = sp; }
-        }
-    } else {
-        // narrow launches: doubling may pass ks_max_splits once (up to 64)
-        while (splits < e.ks_max_splits && cnt * splits * 2 <= e.ks_target_blocks) splits *= 2;
-    }
-    return splits;
-}
-
-// the largest key-switch partial-sum buffer a launch of `count` gates uses
-static size_t ks_partial_bytes(const Engine &e, int count, const DevParams &dp) {
-    size_t most = 0;
-    const int chunk = ks_tiled(e, count, dp) ? KS_CHUNK : count;
-    for (int done = 0; done < count; done += chunk) {
-        const int cnt = std::min(chunk, count - done), splits = ks_splits(e, cnt, dp);
-        if (splits > 1) most = std::max(most, (size_t)cnt * splits * dp.ct_stride * 4);
-    }
-    return most;
-}
-
+// the key switches of `count` gates by the rule of launch_plan.hpp: chunks of at most KS_CHUNK gates when tiled, each in
+// ks_splits coefficient ranges
 void Engine::launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
-                       hipStream_t stream) {
+                       hipStream_t stream, bool presized) {
     ENGINE_DEVICE_SCOPE();
     if (count <= 0) return;
     if (!stream) stream = stream_;
     const DevParams &dp = key->dp;
-    const size_t bytes = ks_partial_bytes(*this, count, dp);
-    if (in_execute_ && bytes > (scratch_size_.size() > 10 ? scratch_size_[10] : 0))
+    const KsShape shape = ks_shape(dp);
+    const size_t bytes = ks_partial_bytes(tunings, cu_count_, count, shape);
+    if (presized && bytes > (scratch_size_.size() > 10 ? scratch_size_[10] : 0))
         fatal("launch_ks: the key-switch partial sums were not sized by execute()");
     int32_t *partial = bytes ? static_cast<int32_t *>(scratch(10, bytes)) : nullptr;
-    const bool tiled = ks_tiled(*this, count, dp);
+    const bool tiled = ks_tiled(tunings, count, shape);
     const int chunk = tiled ? KS_CHUNK : count;
     for (int done = 0; done < count; done += chunk) {
-        const int cnt = std::min(chunk, count - done), splits = ks_splits(*this, cnt, dp);
+        const int cnt = std::min(chunk, count - done), splits = ks_splits(tunings, cu_count_, cnt, shape);
         launch_keyswitch(stream, dp, key->key, u_buf, descs + done, cnt, pool, splits, splits > 1 ? partial : nullptr,
-                         tiled ? ks_tile_size(*this) : 0, ks_index != 0);
+                         tiled ? ks_tile_size(tunings) : 0, tunings.ks_index != 0);
     }
 }
 
@@ -774,13 +670,9 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
     // extract buffer, sized for the widest level, and key-switch partial sums, sized by the split rule launch_ks applies
     int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)(plan_in.max_rots + 1) * key->dp.u_stride * 4));
     size_t partial = 0;
-    if (nkeys == 1) {
-        for (int g = 0; g < plan_in.levels; ++g)
-            partial = std::max(partial, ks_partial_bytes(*this, plan_in.ks_off[g + 1] - plan_in.ks_off[g], key->dp));
-    } else {                                         // one key-switch launch per (level, key)
-        for (size_t sg = 0; sg + 1 < plan_in.ks_koff.size(); ++sg)
-            partial = std::max(partial, ks_partial_bytes(*this, plan_in.ks_koff[sg + 1] - plan_in.ks_koff[sg], key->dp));
-    }
+    const std::vector<int32_t> &ks_shares = nkeys == 1 ? plan_in.ks_off : plan_in.ks_koff;   // one key-switch launch per (level, key)
+    for (size_t sg = 0; sg + 1 < ks_shares.size(); ++sg)
+        partial = std::max(partial, ks_partial_bytes(tunings, cu_count_, ks_shares[sg + 1] - ks_shares[sg], ks_shape(key->dp)));
     if (partial) (void)scratch(10, partial);
     // the key table and the key index of every rotation
     DevKey *dkeys = nullptr;
@@ -819,7 +711,6 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
         timed.reserve((size_t)levels + 1);
     }
     hipEvent_t shared_end = nullptr;
-    in_execute_ = true;
     for (int L = 0; L <= levels; ++L) {
         const size_t gg = L > 0 ? (size_t)(L - 1) : 0;       // gate index
         const int nrot = L > 0 ? plan.rot_off[gg + 1] - plan.rot_off[gg] : 0;
@@ -835,52 +726,38 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
             else { t.e0 = timing_event(); hip_check(hipEventRecord(t.e0, stream_), "event"); }
             shared_end = nullptr;
         }
-        if (nrot && nkeys > 1) {
-            // the form follows the level's total width (as for one key); forms without a multi-key kernel run one launch
-            // per key over that key's contiguous run of the level's rotations
-            const int form = br_form(key, nrot);
-            if (form == BR_FORM_WIDE4 || form == BR_FORM_WAVE8) {
-                t.wide8 = launch_br(key, pool->data(), drots + plan.rot_off[gg], nrot, u_buf, nullptr, stream_, dkeys,
-                                    drot_keys + plan.rot_off[gg]);
+        if (nrot) {
+            // one plan per level, from its total width; the statistics follow from the plan and the launches made
+            const BrPlan bp = plan_br_launch(key, nrot, false);
+            int launches = 0;
+            if (nkeys == 1 || bp.form == BR_FORM_WIDE4 || bp.form == BR_FORM_WAVE8) {
+                // one launch, two with a tail; several keys: each rotation under its own key through the key table
+                launch_br(key, bp, pool->data(), drots + plan.rot_off[gg], nrot, u_buf, nullptr, stream_, dkeys,
+                          dkeys ? drot_keys + plan.rot_off[gg] : nullptr, kernel_timing ? &t.em : nullptr);
+                launches = bp.tail ? 2 : 1;
             } else {
-                int launched = 0;
+                // no multi-key kernel for this form: one launch of it per key over that key's contiguous run of the
+                // level's rotations (bp.tail is 0: only the 4-wave form has one)
                 for (int k = 0; k < nkeys; ++k) {
                     const size_t sg = gg * (size_t)nkeys + (size_t)k;
                     const int n = plan.rot_koff[sg + 1] - plan.rot_koff[sg];
                     if (!n) continue;
-                    launch_br(keys[(size_t)k], pool->data(), drots + plan.rot_koff[sg], n, u_buf, nullptr, stream_);
-                    ++launched;
+                    launch_br(keys[(size_t)k], bp, pool->data(), drots + plan.rot_koff[sg], n, u_buf, nullptr, stream_);
+                    ++launches;
                 }
-                tail_count_ = 0;
-                stats.br_launches += (uint64_t)(launched - 1);   // br_launches counts launches: one per key with a share (the
-                                                                 // level's own +1 is below)
             }
-            if (t.wide8) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)nrot; }
-            if (tail_count_) {
-                t.em = tail_event_;
-                t.tail = tail_count_;
-                ++stats.br8_launches; ++stats.br_launches;
-                stats.br8_rotations += (uint64_t)tail_count_;
-            }
-        } else if (nrot) {
-            t.wide8 = launch_br(key, pool->data(), drots + plan.rot_off[gg], nrot, u_buf, nullptr, stream_);
-            if (t.wide8) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)nrot; }
-            if (tail_count_) {                       // a second launch, of the 8-wave kernel
-                t.em = tail_event_;
-                t.tail = tail_count_;
-                ++stats.br8_launches; ++stats.br_launches;
-                stats.br8_rotations += (uint64_t)tail_count_;
-            }
+            t.wide8 = bp.form == BR_FORM_WAVE8;
+            t.tail = bp.tail;
+            stats.br_launches += (uint64_t)launches;
+            if (t.wide8 || t.tail) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)(t.wide8 ? nrot : t.tail); }
         }
         if (kernel_timing) { t.e1 = timing_event(); hip_check(hipEventRecord(t.e1, stream_), "event"); }
-        if (nks && nkeys > 1) {                      // one key-switch launch per key: the key-switch kernels are single-key
-            for (int k = 0; k < nkeys; ++k) {
-                const size_t sg = gg * (size_t)nkeys + (size_t)k;
-                const int n = plan.ks_koff[sg + 1] - plan.ks_koff[sg];
-                if (n) launch_ks(keys[(size_t)k], u_buf, dks + plan.ks_koff[sg], n, pool->data(), stream_);
-            }
-        } else if (nks) {
-            launch_ks(key, u_buf, dks + plan.ks_off[gg], nks, pool->data(), stream_);
+        // the key-switch kernels are single-key: one launch per key with a share of the level
+        for (int k = 0; k < nkeys && nks; ++k) {
+            const size_t sg = gg * (size_t)nkeys + (size_t)k;
+            const int32_t first = nkeys == 1 ? plan.ks_off[gg] : plan.ks_koff[sg];
+            const int n = nkeys == 1 ? nks : plan.ks_koff[sg + 1] - first;
+            if (n) launch_ks(keys[(size_t)k], u_buf, dks + first, n, pool->data(), stream_, true);
         }
         if (kernel_timing) {
             t.e2 = timing_event(); hip_check(hipEventRecord(t.e2, stream_), "event"); timed.push_back(t);
@@ -890,9 +767,7 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
         stats.blind_rotates += (uint64_t)nrot;
         stats.keyswitches += (uint64_t)nks;
         stats.linear_ops += (uint64_t)nnot;
-        if (nrot) ++stats.br_launches;
     }
-    in_execute_ = false;
     if (const char *trace = std::getenv("TFHE_HIP_TRACE_LEVELS")) {   // diagnostic: rotations per level
         if (FILE *f = std::fopen(trace, "a")) {
             std::fprintf(f, "flush levels=%d lanes=1\n", levels);
@@ -990,7 +865,7 @@ void Engine::run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, i
     hip_check(hipMemcpyAsync(drots, rots.data(), rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream_), "upload rots");
     int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)count * dp.u_stride * 4));
     int32_t *dacc = acc_out ? static_cast<int32_t *>(scratch(7, (size_t)count * 2 * dp.N * 4)) : nullptr;
-    launch_br(key, dpool, drots, count, u_buf, dacc);
+    launch_br(key, plan_br_launch(key, count, dacc != nullptr), dpool, drots, count, u_buf, dacc);
     hip_check(hipGetLastError(), "blind_rotate launch");
     std::vector<int32_t> ubuf((size_t)count * dp.u_stride);
     hip_check(hipMemcpyAsync(ubuf.data(), u_buf, ubuf.size() * 4, hipMemcpyDeviceToHost, stream_), "download u");
@@ -1051,12 +926,12 @@ double Engine::run_wg_times(const DeviceKeyImage *key, int width, unsigned long 
     int warm_count = 1, warm_width = width;
     if (const char *env = std::getenv("TFHE_HIP_PROBE_WARM")) std::sscanf(env, "%d:%d", &warm_count, &warm_width);
     warm_width = std::max(1, std::min(warm_width, width));
-    for (int w = 0; w < warm_count; ++w) launch_br(key, pool, drots, warm_width, ubuf, nullptr, st);
+    for (int w = 0; w < warm_count; ++w) launch_br(key, plan_br_launch(key, warm_width, false), pool, drots, warm_width, ubuf, nullptr, st);
     // cleared first so that a launch which wrote no stamps is noticed instead of read as timings
     hip_check(hipMemsetAsync(dtimes, 0, (size_t)4 * width * 8, st), "clear stamps");
     wg_times_dbg_ = dtimes;
     hip_check(hipEventRecord(e0, st), "probe event record");
-    launch_br(key, pool, drots, width, ubuf, nullptr, st);
+    launch_br(key, plan_br_launch(key, width, false), pool, drots, width, ubuf, nullptr, st);
     hip_check(hipEventRecord(e1, st), "probe event record");
     hip_check(hipStreamSynchronize(st), "probe stamps");
     wg_times_dbg_ = nullptr;
@@ -1074,7 +949,7 @@ void Engine::run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const 
     ENGINE_DEVICE_SCOPE();
     wait_flight();
     DevParams dp = key->dp;
-    dp.br_variant = br_variant == 2 ? 2 : 0;            // 2: through the split transforms
+    dp.br_variant = tunings.br_variant == 2 ? 2 : 0;            // 2: through the split transforms
     const size_t words = (size_t)count * dp.N;
     uint32_t scale[2];
     (void)make_twiddles(dp.N, scale);

@@ -11,6 +11,7 @@
 
 #include "host_keys.hpp"
 #include "br_forms.hpp"
+#include "launch_plan.hpp"
 #include "kernels.hpp"
 #include "../../include/tfhe_hip.h"
 
@@ -140,52 +141,22 @@ public:
 
     TfheHipStats stats{};
     bool kernel_timing = false;
-    // Tunings (tfhe_hip_set_tuning; these six, the recorder's reuse_gates / eliminate_dead / balance_levels / fold_constants /
-    // batch_keys, and sync_deadline_ms above).  HISTORY.md lists the forms and knobs removed in round 6.
-    //
-    // Key switches of a narrow launch are split (power of two <= ks_max_splits) until about ks_target_blocks workgroups
-    // exist: beyond filling the chip, more splits mean the blocks in flight share a KSK sub-table small enough for an
-    // XCD's L2 (measured optimum of the per-gate kernel: 32 splits).  The tiled launches take any count of coefficient
-    // ranges up to ks_max_splits whose grid fills whole rounds of resident workgroups (launch_ks); a cap of 48 measured
-    // 56.1 against 61.0 ms per match at 32 (env TFHE_HIP_KS_BLOCKS, TFHE_HIP_KS_MAX_SPLITS; not tunings)
-    int ks_target_blocks = 32768;
-    int ks_max_splits = 48;
-    // among the range counts that fill the workgroup slots equally well: 1 = the largest (more, shorter ranges), 0 = the smallest
-    // (less partial-sum traffic: one match 55.4 against 56.1 ms; env TFHE_HIP_KS_SPLIT_TIES)
-    int ks_split_ties = 0;
-    // gates per workgroup of the tiled key switch (16, 24 or 32; 0 = per-gate kernel only); tuning "ks_tile"
-    int ks_tile = 16;
-    // 1 (default) = the tiled key switch keeps a thread's column of the staged rows in PINNED registers, picked through the
-    // VGPR index mode (kernels.hip keyswitch_index_kernel): 56 ms per match; 0 = the LDS-strip form (keyswitch_strip_kernel,
-    // tiles of 16): 105 ms -- plain HIP source, the form to fall back on.  Tuning "ks_index", env TFHE_HIP_KS_INDEX
-    int ks_index = 1;
-    // which form of the blind-rotate kernel runs wide launches (kernels.hip): -1 = the fastest measured for the ring size
-    // (N = 1024: 4-wave; N = 2048: split), 0 = 4-wave (N = 1024), 2 = split (8 waves, half transforms), 4 = 2-wave
-    // (N = 1024).  A form whose lazy-arithmetic bounds do not admit the key's gadget is replaced by one that does
-    // (launch_br).  Tuning "br_variant", env TFHE_HIP_BR_VARIANT
-    int br_variant = -1;
-    // launches of at most min(this, CU count) rotations (at most one workgroup per CU) use the 8-wave form
-    // of the kernel, N = 1024 only; 0 = never (env TFHE_HIP_BR8_MAX, tuning "br8_max_rotations")
-    int br8_max_rotations = 1 << 30;
-    // A 4-wave launch whose last round would leave at most one workgroup per CU (count = q * 2 * CUs + r, q >= 1,
-    // 0 < r <= CUs) hands those r rotations to the 8-wave form as a second launch: 2.9 ms instead of the 3.75 ms a
-    // lone 4-wave workgroup per CU takes (env TFHE_HIP_BR_TAIL8, tuning "br_tail8"; 0 = one launch)
-    int br_tail8 = 1;
-    // 1 = the first radix-4 step of the forward transforms looks digit products up in LDS (gadget digits
-    // of at most 7 bits; split form: stage 0, and the first radix-4 step too where digits have at most 6
-    // bits); 2 = split form: stage 0 only; 0 = multiplies (env TFHE_HIP_BR_TABLE, tuning "br_digit_table")
-    int br_digit_table = 1;
-    // stream == nullptr: the engine's stream; inside execute() the partial sums never grow (checked)
+    // the launch rules' tunings (launch_plan.hpp; written by ensure_init()'s environment reads and tfhe_hip_set_tuning)
+    LaunchTunings tunings;
+    // stream == nullptr: the engine's stream; presized (execute()'s levels): the partial sums were sized by the caller
+    // and must not grow (checked)
     void launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
-                   hipStream_t stream = nullptr);
-    // returns true when the launch used the 8-wave form.  mk_keys / mk_rot_keys (device key table and per-rotation key
-    // indices of a multi-key level): the 4- and 8-wave forms run each rotation under its own key; only for those forms
-    // (br_form), and `key` is entry 0 of the table
-    bool launch_br(const DeviceKeyImage *key, const int32_t *pool, const RotDesc *rots, int count, int32_t *u_buf,
-                   int32_t *acc_dbg, hipStream_t stream = nullptr, const DevKey *mk_keys = nullptr,
-                   const int32_t *mk_rot_keys = nullptr);
-    // the form launch_br runs `count` rotations of this key's parameter set on (BR_FORM_*), and its digit-table mode
-    int br_form(const DeviceKeyImage *key, int count, int *tables_out = nullptr) const;
+                   hipStream_t stream = nullptr, bool presized = false);
+    // the launch plan (launch_plan.hpp plan_br) of `count` rotations under this key's parameter set on this card;
+    // acc_dump: the raw accumulators are read back
+    BrPlan plan_br_launch(const DeviceKeyImage *key, int count, bool acc_dump) const;
+    // runs a plan of plan_br_launch on these descriptors: one kernel launch, two with a tail; decides nothing.
+    // mk_keys / mk_rot_keys (device key table and per-rotation key indices of a multi-key level): the 4- and 8-wave
+    // forms run each rotation under its own key; only for those forms, and `key` is entry 0 of the table.  mid: where
+    // the event between the two launches of a plan with a tail goes (kernel timing of a flush), or null
+    void launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int32_t *pool, const RotDesc *rots, int count,
+                   int32_t *u_buf, int32_t *acc_dbg, hipStream_t stream = nullptr, const DevKey *mk_keys = nullptr,
+                   const int32_t *mk_rot_keys = nullptr, hipEvent_t *mid = nullptr);
     // diagnostic (tools/wg_times.py): ONE 4-wave blind-rotate launch of `width` random gates whose workgroups stamp s_memtime
     // and s_memrealtime at start and end into wg_times[4 * width]; returns that launch's event time in ms (< 0: no stamps)
     double run_wg_times(const DeviceKeyImage *key, int width, unsigned long long *wg_times);
@@ -193,15 +164,12 @@ public:
 private:
     Engine() = default;
     void *scratch(size_t idx, size_t bytes);   // grow-only device scratch buffers
-    // em / tail: a level whose last round went to the 8-wave form as a second launch (br_tail8) -- the event between
+    // em / tail: a level whose last round went to the 8-wave form as a second launch (BrPlan::tail) -- the event between
     // the two launches and the rotations of the second, so that each kernel's time and count stay its own
     struct Timed { hipEvent_t e0, e1, e2; bool wide8; int nrot; hipEvent_t em = nullptr; int tail = 0; };
     void note_async_io();
     hipEvent_t io_event_ = nullptr;                     // behind the last stream-ordered transfer that returned without a wait
     bool io_pending_ = false;
-    bool in_execute_ = false;                           // launches of execute()'s levels: the tail event has a reader
-    hipEvent_t tail_event_ = nullptr;                   // set by launch_br when it split a level (kernel_timing only)
-    int tail_count_ = 0;
     std::vector<Timed> flight_timed_;
     hipEvent_t flight_base_ = nullptr;
     LevelPlan flight_plan_;

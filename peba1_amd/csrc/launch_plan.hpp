@@ -1,0 +1,163 @@
+// launch_plan.hpp -- which kernel launches a level of a flush turns into (host side, no device code, no runtime calls).
+//
+// Pure functions of the tunings, the CU count, the parameter set and the level's width: the engine (engine.cpp
+// execute / launch_br / launch_ks) runs what they return, and tests/test_launch_plan_cpu.py drives them through
+// tfhe_hip_test_br_plan / tfhe_hip_test_ks_plan on a machine without a GPU.  Not a file the kernels are built from
+// (peba1_amd/kernel_id.py).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+
+#include "br_forms.hpp"
+
+namespace tfhe_hip {
+
+// Tunings of the launch rules (tfhe_hip_set_tuning: br_variant, br8_max_rotations, br_tail8, br_digit_table, ks_tile and
+// ks_index; beside them the recorder's reuse_gates / eliminate_dead / balance_levels / fold_constants / batch_keys, and
+// the engine's sync_deadline_ms).  HISTORY.md lists the forms and knobs removed in round 6.
+struct LaunchTunings {
+    // which form of the blind-rotate kernel runs wide launches (kernels.hip): -1 = the fastest measured for the ring size
+    // (N = 1024: 4-wave; N = 2048: split), 0 = 4-wave (N = 1024), 2 = split (8 waves, half transforms), 4 = 2-wave
+    // (N = 1024).  A form whose lazy-arithmetic bounds do not admit the key's gadget is replaced by one that does
+    // (plan_br).  Tuning "br_variant", env TFHE_HIP_BR_VARIANT
+    int br_variant = -1;
+    // launches of at most min(this, CU count) rotations (at most one workgroup per CU) use the 8-wave form
+    // of the kernel, N = 1024 only; 0 = never (env TFHE_HIP_BR8_MAX, tuning "br8_max_rotations")
+    int br8_max_rotations = 1 << 30;
+    // A 4-wave launch whose last round would leave at most one workgroup per CU (count = q * 2 * CUs + r, q >= 1,
+    // 0 < r <= CUs) hands those r rotations to the 8-wave form as a second launch: 2.9 ms instead of the 3.75 ms a
+    // lone 4-wave workgroup per CU takes (env TFHE_HIP_BR_TAIL8, tuning "br_tail8"; 0 = one launch)
+    int br_tail8 = 1;
+    // 1 = the first radix-4 step of the forward transforms looks digit products up in LDS (gadget digits
+    // of at most 7 bits; split form: stage 0, and the first radix-4 step too where digits have at most 6
+    // bits); 2 = split form: stage 0 only; 0 = multiplies (env TFHE_HIP_BR_TABLE, tuning "br_digit_table")
+    int br_digit_table = 1;
+    // Key switches of a narrow launch are split (power of two <= ks_max_splits) until about ks_target_blocks workgroups
+    // exist: beyond filling the chip, more splits mean the blocks in flight share a KSK sub-table small enough for an
+    // XCD's L2 (measured optimum of the per-gate kernel: 32 splits).  The tiled launches take any count of coefficient
+    // ranges up to ks_max_splits whose grid fills whole rounds of resident workgroups (ks_splits); a cap of 48 measured
+    // 56.1 against 61.0 ms per match at 32 (env TFHE_HIP_KS_BLOCKS, TFHE_HIP_KS_MAX_SPLITS; not tunings)
+    int ks_target_blocks = 32768;
+    int ks_max_splits = 48;
+    // among the range counts that fill the workgroup slots equally well: 1 = the largest (more, shorter ranges), 0 = the smallest
+    // (less partial-sum traffic: one match 55.4 against 56.1 ms; env TFHE_HIP_KS_SPLIT_TIES)
+    int ks_split_ties = 0;
+    // gates per workgroup of the tiled key switch (16, 24 or 32; 0 = per-gate kernel only); tuning "ks_tile"
+    int ks_tile = 16;
+    // 1 (default) = the tiled key switch keeps a thread's column of the staged rows in PINNED registers, picked through the
+    // VGPR index mode (kernels.hip keyswitch_index_kernel): 56 ms per match; 0 = the LDS-strip form (keyswitch_strip_kernel,
+    // tiles of 16): 105 ms -- plain HIP source, the form to fall back on.  Tuning "ks_index", env TFHE_HIP_KS_INDEX
+    int ks_index = 1;
+};
+
+// form_ok[form][tables]: the kernel form's magnitude bounds hold for the gadget (l, Bgbit) at ring size N (br_forms.hpp)
+inline void fill_form_ok(bool form_ok[BR_FORM_COUNT][3], int N, int l, int Bgbit) {
+    for (int f = 0; f < BR_FORM_COUNT; ++f)
+        for (int t = 0; t < 3; ++t) form_ok[f][t] = br_form_admissible(f, N, l, Bgbit, t);
+}
+
+// The blind-rotate launches of `count` rotations: kernel form (BR_FORM_*; -1 = no form admits the gadget), digit-table
+// mode, and -- 4-wave form only -- tail > 0: the first count - tail rotations on the 4-wave form, the last `tail` on the
+// 8-wave form as a second launch.
+struct BrPlan { int form; int tables; int tail; };
+
+// stamps: the workgroup-time probe is on (forces the 4-wave form at N = 1024, which alone writes the stamps; forbids the
+// 8-wave form and the tail); acc_dump: the caller reads the raw accumulators back (forbids the tail only: the debug
+// probes index by workgroup and keep one launch)
+inline BrPlan plan_br(const bool form_ok[BR_FORM_COUNT][3], int N, int l, const LaunchTunings &t, int cu_count, int count,
+                      bool stamps, bool acc_dump) {
+    // the form the tunings ask for ...
+    int form;
+    if (t.br_variant == 4 && N == 1024) form = BR_FORM_WAVE2;
+    else if (t.br_variant == 2 || N == 2048) form = BR_FORM_SPLIT;
+    // launches that leave CUs with at most one workgroup: the 8-wave form (a second wave per SIMD)
+    else if (t.br8_max_rotations > 0 && count <= std::min(t.br8_max_rotations, cu_count) && l >= 2 && !stamps)
+        form = BR_FORM_WAVE8;
+    else form = BR_FORM_WIDE4;
+    // the workgroup-time probe reads stamps only the 4-wave kernel writes
+    if (stamps && N == 1024) form = BR_FORM_WIDE4;
+    // ... if its magnitude bounds hold for this key's gadget (br_forms.hpp; every built-in set passes in every form of its
+    // ring); else the same form with smaller or no digit tables, else the next form of the order
+    int tables = t.br_digit_table < 0 || t.br_digit_table > 2 ? 0 : t.br_digit_table;
+    if (!form_ok[form][tables]) {
+        static const int order[BR_FORM_COUNT] = {BR_FORM_WIDE4, BR_FORM_SPLIT, BR_FORM_WAVE2, BR_FORM_WAVE8};
+        int pick_f = -1, pick_t = 0;
+        for (int k = -1; k < BR_FORM_COUNT && pick_f < 0; ++k) {
+            const int f = k < 0 ? form : order[k];
+            if (f == BR_FORM_WAVE8 && count > cu_count) continue;          // its LDS allows one workgroup per CU only
+            for (int tt : {tables, 2, 0})
+                if (form_ok[f][tt]) { pick_f = f; pick_t = tt; break; }
+        }
+        if (pick_f < 0) return BrPlan{-1, 0, 0};
+        form = pick_f; tables = pick_t;
+    }
+    // the last, at most half-filled round of a wide launch on the 8-wave form (descriptors carry their own output
+    // index, so a level splits anywhere)
+    const int round = 2 * cu_count, tail = count % round;
+    const bool split = form == BR_FORM_WIDE4 && t.br_tail8 && count > round && tail > 0 &&
+                       tail <= std::min(t.br8_max_rotations, cu_count) && l >= 2 && !acc_dump && !stamps &&
+                       form_ok[BR_FORM_WAVE8][tables];
+    return BrPlan{form, tables, split ? tail : 0};
+}
+
+// The key-switch launch rule, one place for launch_ks and for execute()'s sizing of the partial sums: a launch of `count`
+// gates runs in chunks of at most KS_CHUNK gates when tiled (bounds the partial-sum buffer: 0.66 GB at P128), each chunk of
+// cnt gates in ks_splits(cnt) coefficient ranges.  Tiles of 24 or 32 gates exist in the index form only (kernels.hip
+// keyswitch_index_kernel); tile 0 = per-gate kernel only.
+constexpr int KS_CHUNK = 8192;
+// what the rule reads of a parameter set: nin = k N input coefficients, the key-switch digits, words per ciphertext slot
+struct KsShape { int nin, ks_t, ks_basebit, ct_stride; };
+
+inline int ks_tile_size(const LaunchTunings &t) { return (t.ks_tile > 16 && !t.ks_index) ? 16 : t.ks_tile; }
+
+// the tiled kernel: wide launches, ranges of at most 64 input coefficients
+inline bool ks_tiled(const LaunchTunings &t, int count, const KsShape &p) {
+    const int tile = ks_tile_size(t);
+    return tile > 0 && count >= 2 * tile && p.ks_t == 8 && p.ks_basebit == 2 && t.ks_max_splits > 1 &&
+           (p.nin + t.ks_max_splits - 1) / t.ks_max_splits <= 64;
+}
+
+inline int ks_splits(const LaunchTunings &t, int cu_count, int cnt, const KsShape &p) {
+    int splits = 1;
+    if (ks_tiled(t, cnt, p)) {
+        // the number of coefficient ranges is free between nin/64 and ks_max_splits: take the
+        // one whose grid (tiles x ranges) fills whole rounds of the workgroups the chip holds,
+        // e.g. 36 tiles x 28 ranges = 1008 of 1024 slots in two rounds instead of 36 x 32 = 1152 in three
+        const int tile = ks_tile_size(t);
+        const int threads = ((p.ct_stride / 4 + 63) / 64) * 64;
+        // index form: no LDS strips; 120 VGPRs at tile 16 (four waves per SIMD), 162 at 24 (three), 204 at 32 (two);
+        // strip form: ~235 VGPRs (two waves per SIMD) and 16 x threads x 16 bytes of strips
+        int per_cu = std::max(1, (tile == 16 ? 16 : tile == 24 ? 12 : 8) / (threads / 64));
+        if (!t.ks_index) {
+            const size_t lds = (size_t)16 * threads * 16 + (size_t)tile * 65 * 4;
+            per_cu = std::max(1, std::min((int)((160 * 1024) / lds), 8 / (threads / 64)));
+        }
+        const long long slots = (long long)cu_count * per_cu;
+        const long long tiles = (cnt + tile - 1) / tile;
+        const int lo = std::max(2, (p.nin + 63) / 64);
+        double best = -1.0;
+        for (int sp = lo; sp <= t.ks_max_splits; ++sp) {
+            const long long blocks = tiles * sp, rounds = (blocks + slots - 1) / slots;
+            const double eff = (double)blocks / (double)(rounds * slots);
+            // ties: fewer, longer ranges (less partial-sum traffic) or more, shorter ones (ks_split_ties)
+            if (t.ks_split_ties ? eff >= best - 1e-9 : eff > best + 1e-9) { best = eff; splits = sp; }
+        }
+    } else {
+        // narrow launches: doubling may pass ks_max_splits once (up to 64)
+        while (splits < t.ks_max_splits && cnt * splits * 2 <= t.ks_target_blocks) splits *= 2;
+    }
+    return splits;
+}
+
+// the largest key-switch partial-sum buffer a launch of `count` gates uses
+inline size_t ks_partial_bytes(const LaunchTunings &t, int cu_count, int count, const KsShape &p) {
+    size_t most = 0;
+    const int chunk = ks_tiled(t, count, p) ? KS_CHUNK : count;
+    for (int done = 0; done < count; done += chunk) {
+        const int cnt = std::min(chunk, count - done), splits = ks_splits(t, cu_count, cnt, p);
+        if (splits > 1) most = std::max(most, (size_t)cnt * splits * p.ct_stride * 4);
+    }
+    return most;
+}
+
+}  // namespace tfhe_hip

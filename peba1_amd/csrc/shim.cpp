@@ -579,14 +579,14 @@ int tfhe_hip_set_tuning(const char *name, int64_t value) {
     auto g = recorder_lock();      // the launchers read the tunings under the same lock (flushes)
     if (name && std::strcmp(name, "ks_tile") == 0) {
         if (value != 0 && value != 16 && value != 24 && value != 32) { set_error("ks_tile must be 0, 16, 24 or 32"); return -1; }
-        Engine::get().ks_tile = (int)value;
+        Engine::get().tunings.ks_tile = (int)value;
         return 0;
     }
-    if (name && std::strcmp(name, "ks_index") == 0) { Engine::get().ks_index = value != 0; return 0; }
-    if (name && std::strcmp(name, "br_digit_table") == 0) { Engine::get().br_digit_table = (int)value; return 0; }
-    if (name && std::strcmp(name, "br8_max_rotations") == 0) { Engine::get().br8_max_rotations = (int)value; return 0; }
-    if (name && std::strcmp(name, "br_tail8") == 0) { Engine::get().br_tail8 = (int)value; return 0; }
-    if (name && std::strcmp(name, "br_variant") == 0) { Engine::get().br_variant = (int)value; return 0; }
+    if (name && std::strcmp(name, "ks_index") == 0) { Engine::get().tunings.ks_index = value != 0; return 0; }
+    if (name && std::strcmp(name, "br_digit_table") == 0) { Engine::get().tunings.br_digit_table = (int)value; return 0; }
+    if (name && std::strcmp(name, "br8_max_rotations") == 0) { Engine::get().tunings.br8_max_rotations = (int)value; return 0; }
+    if (name && std::strcmp(name, "br_tail8") == 0) { Engine::get().tunings.br_tail8 = (int)value; return 0; }
+    if (name && std::strcmp(name, "br_variant") == 0) { Engine::get().tunings.br_variant = (int)value; return 0; }
     if (name && set_recorder_tuning_locked(name, value != 0)) return 0;   // reuse_gates, eliminate_dead, fold_constants, balance_levels, batch_keys
     if (name && std::strcmp(name, "sync_deadline_ms") == 0) { Engine::get().sync_deadline_ms = value > 0 ? (long long)value : 0; return 0; }
     set_error(std::string("tfhe_hip_set_tuning: unknown name ") + (name ? name : "(null)"));
@@ -691,6 +691,37 @@ int tfhe_hip_test_level_plan3(const int32_t *ops5, const int32_t *op_keys, int32
                            rot_key, rots8, 8, kss4);
 }
 
+int tfhe_hip_test_br_plan(int32_t N, int32_t l, int32_t Bgbit, const int32_t *tunings4, int32_t cu_count, int32_t count,
+                          int32_t flags, int32_t *out3) {
+    if (!tunings4 || !out3 || cu_count < 1 || count < 1) { set_error("test_br_plan: bad arguments"); return -1; }
+    LaunchTunings t;
+    t.br_variant = tunings4[0]; t.br8_max_rotations = tunings4[1]; t.br_tail8 = tunings4[2]; t.br_digit_table = tunings4[3];
+    bool form_ok[BR_FORM_COUNT][3];
+    fill_form_ok(form_ok, N, l, Bgbit);                       // as upload_key fills a key image's
+    const BrPlan plan = plan_br(form_ok, N, l, t, cu_count, count, (flags & 1) != 0, (flags & 2) != 0);
+    out3[0] = plan.form; out3[1] = plan.tables; out3[2] = plan.tail;
+    return 0;
+}
+
+int tfhe_hip_test_ks_plan(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
+                          int32_t cu_count, int32_t count, int64_t *out6) {
+    if (!tunings5 || !out6 || cu_count < 1 || count < 1) { set_error("test_ks_plan: bad arguments"); return -1; }
+    LaunchTunings t;
+    t.ks_target_blocks = tunings5[0]; t.ks_max_splits = tunings5[1]; t.ks_split_ties = tunings5[2];
+    t.ks_tile = tunings5[3]; t.ks_index = tunings5[4];
+    Params p{};
+    p.n = n;
+    const KsShape shape{k * N, ks_t, ks_basebit, p.ct_stride()};
+    const bool tiled = ks_tiled(t, count, shape);
+    const int chunk = tiled ? KS_CHUNK : count;               // launch_ks's chunks: all of `chunk` gates but the last
+    out6[0] = tiled ? 1 : 0;
+    out6[1] = tiled ? ks_tile_size(t) : 0;
+    out6[2] = chunk;
+    out6[3] = ks_splits(t, cu_count, std::min(chunk, count), shape);
+    out6[4] = ks_splits(t, cu_count, count - (count - 1) / chunk * chunk, shape);
+    out6[5] = (int64_t)ks_partial_bytes(t, cu_count, count, shape);
+    return 0;
+}
 
 int tfhe_hip_test_wg_times(const TFheGateBootstrappingCloudKeySet *bk, int32_t width, uint64_t *times4, double *launch_ms) {
     if (!bk || !bk->bk || !times4 || width <= 0) { set_error("wg_times: bad arguments"); return -1; }

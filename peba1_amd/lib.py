@@ -144,6 +144,8 @@ SIGNATURES = {
     "tfhe_hip_test_schedule": (C.c_int, [I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_level_plan": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [I32P] * 9),
     "tfhe_hip_test_level_plan3": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [I32P] * 9),
+    "tfhe_hip_test_br_plan": (C.c_int, [C.c_int32] * 3 + [I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
+    "tfhe_hip_test_ks_plan": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "tfhe_hip_kernel_negacyclic":(C.c_int, [CK, I32P, I32P, I32P, C.c_int32]),
     "tfhe_hip_kernel_bootstrap_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P]),
     "tfhe_hip_kernel_keyswitch": (C.c_int, [CK, I32P, C.c_int32, I32P]),

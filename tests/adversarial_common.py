@@ -357,7 +357,7 @@ def oracle_accumulators(oks, cs, threads=16):
         return np.stack(list(ex.map(lambda c: oks.blind_rotate(c["bara"], 0, use_ntt=False), cs.cases)))
 
 
-# ---- which kernel form a launch runs: engine.cpp Engine::br_form restated over tfhe_hip_test_form_admissible -----------
+# ---- which kernel form a launch runs: launch_plan.hpp plan_br restated over tfhe_hip_test_form_admissible -------------
 def predicted_form(ok, N, l, Bgbit, count, cu_count, br_variant, br_digit_table, br8_max):
     if br_variant == 4 and N == 1024:
         form = WAVE2

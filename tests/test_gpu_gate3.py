@@ -67,7 +67,8 @@ def _operand_arrays(api, L, pp, ks, pool, count):
 
 
 # (set, tunings, replicas of the 48 distinct cases in the level, expected rise of br_launches, br8_launches,
-# br8_rotations) with 256 CUs: 528 rotations = one full round of the 4-wave kernel and a tail of 16
+# br8_rotations) with 256 CUs: 528 rotations = one full round of the 4-wave kernel and a tail of 16 (the same rows as plans
+# of launch_plan.hpp, without a GPU: tests/test_launch_plan_cpu.py)
 FORM_ROWS = [
     ("P128", {}, 11, 2, 1, 16),                              # 4-wave launch with its 8-wave tail
     ("P128", {"br_tail8": 0}, 11, 1, 0, 0),                  # one 4-wave launch

@@ -421,7 +421,8 @@ def run_wide_row(case, tunings, label):
     return got, d
 
 
-# (set, tunings, expected rise of br8_launches, br_launches, br8_rotations), from Engine::execute() with 256 CUs:
+# (set, tunings, expected rise of br8_launches, br_launches, br8_rotations) with 256 CUs (the same rows as plans of
+# launch_plan.hpp, without a GPU: tests/test_launch_plan_cpu.py):
 #   4- / 8-wave multi-key kernels (N = 1024): level 1 = 558 rotations = one round of 512 on the 4-wave kernel + a tail of
 #   46 on the 8-wave kernel (two launches, one of them 8-wave), levels 2 and 3 (7 and 1 rotations) one 8-wave launch each;
 #   per-key fallback (split and 2-wave forms, all of N = 2048): one single-key launch per key with a share of the level:
