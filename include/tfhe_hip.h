@@ -168,6 +168,44 @@ void tfhe_hip_gate3(int gate, int negate_mask, LweSample *result, const LweSampl
 int tfhe_hip_gate3_batch(int gate, int negate_mask, LweSample *result, const LweSample *a, const LweSample *b,
                          const LweSample *c, int32_t count, const TFheGateBootstrappingCloudKeySet *bk);
 
+/* ---- programmable bootstrap (LUT gates): NOT PART OF UPSTREAM TFHE'S GATE API.  Every gate above starts its blind rotation
+ * from one test polynomial, mu (1 + X + ... + X^(N-1)) with mu = 1/8.  Here the caller supplies it: a LUT is N Torus32 words
+ * v[0..N-1] bound to a parameter set, and a LUT bootstrap evaluates the negacyclic table v on the phase of a linear
+ * combination of up to three samples -- a sign at another amplitude, a re-encoding, a multi-valued table, a noise refresh.
+ * Upstream has the same below its gate API (tfhe_bootstrap_FFT takes any mu, tfhe_blindRotateAndExtract_FFT any test vector).
+ * The words are this library's own, defined by integers:
+ *     t = (0, c0) + coef[0] in[0] (+ coef[1] in[1]) (+ coef[2] in[2])     (wrapping mod 2^32 on all n+1 words)
+ *     (abar_i, bbar) = the modulus switch of t to Z_2N, as for every gate
+ *     ACC = (0, X^-bbar v): body coefficient j is v[j + bbar] for an index (mod 2N) below N, -v[index - N] otherwise
+ *     then the n CMUX steps, the sample extract at index 0 and the key switch of every gate, unchanged.
+ * With v[j] = 2^29 for every j the words are those of the gate with the same prelude (bootsAND: coef (1, 1), c0 = -2^29).
+ * Parity is against the test oracle's pieces (accumulator, CMUX steps, extract, key switch), not against a boots* call.
+ * Decrypted: the result's phase is v[p] for p = bbar - sum abar_i s_i mod 2N below N, -v[p - N] otherwise, plus noise.
+ * A LUT can be made, read and deleted without a GPU; its words reach the device at the first bootstrap that names it
+ * (device memory exhausted there: the error channel, call without effect).  Deleting a LUT runs the recording first if a
+ * recorded bootstrap names it, as deleting a keyset does.
+ * tfhe_hip_new_lut: v[N] is copied.  _constant: v[j] = mu (upstream's tfhe_bootstrap test vector).  _from_table: v[j] =
+ * values[j * slots / N]; slots must divide N.  NULL and the error channel on bad arguments.
+ * tfhe_hip_lut_words: a read-only view of the N words (*count = N).
+ * tfhe_hip_lut_bootstrap: nin in 1..3, in[nin] sample pointers, coef[nin].  Recorded in deferred mode like every gate
+ * (SSA-renamed, levelled, dead results eliminated, batched across keys with "batch_keys"), complete on return in immediate
+ * mode.  "reuse_gates" shares two pending LUT bootstraps only if LUT, operands (in the order given), coefficients, c0 and
+ * key are all equal.  "fold_constants" NEVER folds a LUT bootstrap: a trivial operand is bootstrapped like any other.
+ * Errors (tfhe_hip_last_error(), call without effect): a null or deleted LUT, a LUT of another N than the key's, nin outside
+ * 1..3, and those of every boots* entry.
+ * tfhe_hip_lut_bootstrap_batch: one LUT, result[i] from in[0][i] (, in[1][i], in[2][i]) for i < count -- in[k] is an array of
+ * count samples; 0 / -1. ---- */
+typedef struct TfheHipLut TfheHipLut;
+TfheHipLut *tfhe_hip_new_lut(const TFheGateBootstrappingParameterSet *params, const Torus32 *v);
+TfheHipLut *tfhe_hip_new_lut_constant(const TFheGateBootstrappingParameterSet *params, Torus32 mu);
+TfheHipLut *tfhe_hip_new_lut_from_table(const TFheGateBootstrappingParameterSet *params, const Torus32 *values, int32_t slots);
+void tfhe_hip_delete_lut(TfheHipLut *lut);
+const Torus32 *tfhe_hip_lut_words(const TfheHipLut *lut, int32_t *count);
+void tfhe_hip_lut_bootstrap(const TfheHipLut *lut, LweSample *result, int32_t nin, const LweSample *const *in,
+                            const int32_t *coef, Torus32 c0, const TFheGateBootstrappingCloudKeySet *bk);
+int tfhe_hip_lut_bootstrap_batch(const TfheHipLut *lut, LweSample *result, int32_t nin, const LweSample *const *in,
+                                 const int32_t *coef, Torus32 c0, int32_t count, const TFheGateBootstrappingCloudKeySet *bk);
+
 /* ---- tuning (eleven names that results never depend on, and the opt-in "fold_constants") ----
  * "br_variant": which form of the blind-rotate kernel runs wide launches (env TFHE_HIP_BR_VARIANT): -1 (default) =
  * the fastest measured for the ring size (N = 1024: 4 waves per rotation; N = 2048: split), 0 = 4 waves (N = 1024),
@@ -252,6 +290,9 @@ typedef struct TfheHipStats {
     uint64_t br_tables0_launches;
     uint64_t br_tables1_launches;
     uint64_t br_tables2_launches;
+    /* of blind_rotates, those that started from a caller-supplied test polynomial (tfhe_hip_lut_bootstrap; the raw
+     * entry tfhe_hip_kernel_lut_bootstrap_woks included) */
+    uint64_t lut_rotations;
 } TfheHipStats;
 void tfhe_hip_get_stats(TfheHipStats *out);
 void tfhe_hip_reset_stats(void);
@@ -294,6 +335,15 @@ int tfhe_hip_test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_
 int tfhe_hip_test_level_plan3(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
                               int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
                               int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots8, int32_t *kss4);
+/* The same for recordings that hold LUT bootstraps, with the recorder's sharing rule: ops10 = count x {kind, dst, a, b, c, lut,
+ * sa, sb, sc, c0} (kind 64 = a LUT bootstrap; the last five words are read for that kind only).  reuse != 0: a record equal
+ * to an earlier one in kind, operands, key and -- for a LUT bootstrap -- LUT, coefficients and c0 shares its result exactly
+ * as "reuse_gates" does: shared_with[i] = that record (-1: evaluated), it takes no rotation, and later records that read its
+ * dst read the earlier one's.  rots9 [9 * 2 count]: the eight words above and the LUT index (-1: the constant test vector). */
+int tfhe_hip_test_level_plan_lut(const int32_t *ops10, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                                 int32_t balance, int32_t reuse, int32_t *levels_out, int32_t *shared_with, int32_t *sizes6,
+                                 int32_t *rot_off, int32_t *ks_off, int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key,
+                                 int32_t *rots9, int32_t *kss4);
 /* ---- host-logic test entries: the launch rules of peba1_amd/csrc/launch_plan.hpp, without touching the device.
  * tfhe_hip_test_br_plan: the blind-rotate launches of a level of `count` rotations of gadget (l, Bgbit) at ring size N on
  * a card of `cu_count` CUs under tunings4 = {br_variant, br8_max_rotations, br_tail8, br_digit_table}; flags bit 0 = the
@@ -325,6 +375,11 @@ int tfhe_hip_kernel_negacyclic(const TFheGateBootstrappingCloudKeySet *bk, const
  * accumulator ((k+1)N words) */
 int tfhe_hip_kernel_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *lin,
                                    int32_t count, Torus32 *u_out, Torus32 *acc_out);
+/* the same from caller-supplied test polynomials: combination c starts from polys[lut_index[c]] (polys: npolys x N words; an
+ * index below 0: the constant test vector of the entry above).  Runs whatever kernel form the tunings select. */
+int tfhe_hip_kernel_lut_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *lin, int32_t count,
+                                       const int32_t *lut_index, const Torus32 *polys, int32_t npolys, Torus32 *u_out,
+                                       Torus32 *acc_out);
 /* key switch of `count` extracted samples u[c] (kN+1 words) -> out[c] (n+1 words) */
 int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *u,
                               int32_t count, Torus32 *out);

@@ -257,6 +257,76 @@ def gate3_batch(name, result, a, b, c, key, negate_mask=0):
         raise RuntimeError(last_error())
 
 
+class Lut:
+    """A caller-supplied test polynomial (tfhe_hip_new_lut): N torus words bound to a parameter set.  The bootstrap of a
+    phase p (in 1/2N-ths of the torus) returns v[p] below N and -v[p - N] from N on; the words are defined in
+    include/tfhe_hip.h."""
+
+    def __init__(self, params, words):
+        w = np.ascontiguousarray(words, dtype=np.int32)
+        if w.shape != (params.N,):
+            raise ValueError("a LUT of this parameter set holds %d words" % params.N)
+        self._take(params, _l.load().tfhe_hip_new_lut(params.ptr, _i32p(w)))
+
+    def _take(self, params, ptr):
+        self.params, self.ptr = params, ptr
+        if not ptr:
+            raise ValueError("LUT rejected: " + last_error())
+
+    @classmethod
+    def constant(cls, params, mu):
+        """v[j] = mu: upstream's tfhe_bootstrap test vector; mu = 2^29 is the one every gate uses."""
+        self = cls.__new__(cls)
+        self._take(params, _l.load().tfhe_hip_new_lut_constant(params.ptr, int(mu)))
+        return self
+
+    @classmethod
+    def from_table(cls, params, values):
+        """v[j] = values[j * len(values) / N]; len(values) must divide N."""
+        v = np.ascontiguousarray(values, dtype=np.int32)
+        self = cls.__new__(cls)
+        self._take(params, _l.load().tfhe_hip_new_lut_from_table(params.ptr, _i32p(v), len(v)))
+        return self
+
+    def words(self):
+        cnt = C.c_int32()
+        p = _l.load().tfhe_hip_lut_words(self.ptr, C.byref(cnt))
+        return np.ctypeslib.as_array(p, shape=(cnt.value,)).copy()
+
+    def close(self):
+        if self.ptr:
+            _l.load().tfhe_hip_delete_lut(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lut_bootstrap(lut, result, inputs, coefs, c0, key):
+    """result = LUT bootstrap of (0, c0) + sum coefs[i] inputs[i]; result and inputs are LweSample pointers
+    (CiphertextArray.at), one to three inputs.  Errors go to last_error() and leave the result untouched."""
+    n = len(inputs)
+    ins = (_l.LS * max(n, 1))(*inputs)
+    cf = np.ascontiguousarray(coefs, dtype=np.int32)
+    assert len(cf) == n
+    _l.load().tfhe_hip_lut_bootstrap(lut.ptr if lut is not None else None, result, n, ins, _i32p(cf), int(c0), key.cloud)
+
+
+def lut_bootstrap_batch(lut, result, inputs, coefs, c0, key):
+    """result[i] = LUT bootstrap of (0, c0) + sum coefs[k] inputs[k][i]: CiphertextArrays of result.count samples."""
+    n = len(inputs)
+    ins = (_l.LS * max(n, 1))(*[a.ptr for a in inputs])
+    cf = np.ascontiguousarray(coefs, dtype=np.int32)
+    assert len(cf) == n
+    rc = _l.load().tfhe_hip_lut_bootstrap_batch(lut.ptr if lut is not None else None, result.ptr, n, ins, _i32p(cf), int(c0),
+                                                result.count, key.cloud)
+    if rc != 0:
+        raise RuntimeError(last_error())
+
+
 def set_deferred(on):
     _l.load().tfhe_hip_set_deferred(1 if on else 0)
 
@@ -315,6 +385,22 @@ def kernel_bootstrap_woks(key, lin, want_acc=False):
     acc = np.zeros((lin.shape[0], (p.k + 1) * p.N), dtype=np.int32) if want_acc else None
     rc = _l.load().tfhe_hip_kernel_bootstrap_woks(key.cloud, _i32p(lin), lin.shape[0], _i32p(u),
                                                   _i32p(acc) if want_acc else None)
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return (u, acc) if want_acc else u
+
+
+def kernel_lut_bootstrap_woks(key, lin, lut_index, polys, want_acc=False):
+    """kernel_bootstrap_woks from test polynomials: combination c starts from polys[lut_index[c]] (index < 0: the constant
+    test vector)."""
+    p = key.params
+    lin = np.ascontiguousarray(lin, dtype=np.int32).reshape(-1, p.words)
+    idx = np.ascontiguousarray(lut_index, dtype=np.int32).reshape(lin.shape[0])
+    polys = np.ascontiguousarray(polys, dtype=np.int32).reshape(-1, p.N)
+    u = np.zeros((lin.shape[0], p.k * p.N + 1), dtype=np.int32)
+    acc = np.zeros((lin.shape[0], (p.k + 1) * p.N), dtype=np.int32) if want_acc else None
+    rc = _l.load().tfhe_hip_kernel_lut_bootstrap_woks(key.cloud, _i32p(lin), lin.shape[0], _i32p(idx), _i32p(polys),
+                                                      polys.shape[0], _i32p(u), _i32p(acc) if want_acc else None)
     if rc != 0:
         raise RuntimeError(last_error())
     return (u, acc) if want_acc else u

@@ -40,10 +40,11 @@
     __syncthreads();
     if (q == 0 && !role_b) {
         const int barb = sh.bar[n];
+        const int32_t *lut = lut_of(p, rd);
 #pragma unroll
         for (int r = 0; r < REGS; ++r) {
             const int j = r * 64 + lane;
-            sh.acc.set(u, j, u == 0 ? 0u : testvector_coef<LOGN>(j, barb, p.mu));
+            sh.acc.set(u, j, u == 0 ? 0u : body_coef<LOGN>(lut, j, barb, p.mu));
         }
     }
     __syncthreads();

@@ -368,6 +368,7 @@ static DevParams make_dev_params(const Params &p) {
     d.digit_table = 1;
     d.clock_acc = nullptr;
     d.wg_times = nullptr;
+    d.luts = nullptr;
     return d;
 }
 
@@ -452,6 +453,40 @@ void Engine::free_key(DeviceKeyImage *img) {
     recoverable_free(img->ksk, img->ksk_bytes);
     recoverable_free(img->tw, img->tw_bytes);
     delete img;
+}
+
+// ---- test polynomials ----------------------------------------------------------
+int32_t Engine::lut_add(const Torus32 *words, int n_ring) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    if (n_ring < 1 || n_ring > LUT_STRIDE) api_fail("a test polynomial of more than " + std::to_string(LUT_STRIDE) + " words");
+    constexpr size_t ENTRY = (size_t)LUT_STRIDE * sizeof(int32_t);
+    if (lut_free_.empty() && lut_used_ == lut_cap_) {
+        // (throws ApiError when the card is full: nothing has changed yet)
+        const size_t cap = lut_cap_ ? lut_cap_ * 2 : 16;
+        int32_t *fresh = static_cast<int32_t *>(recoverable_alloc(cap * ENTRY, "growing the table of test polynomials"));
+        if (lut_dev_) {
+            // launches in flight carry the old pointer: wait for all of them, as the slot pool does when it grows
+            sync_stream("sync before LUT table growth");
+            hip_check(hipDeviceSynchronize(), "sync before LUT table growth");
+            hip_check(hipMemcpy(fresh, lut_dev_, lut_cap_ * ENTRY, hipMemcpyDeviceToDevice), "copy LUT table");
+            recoverable_free(lut_dev_, lut_cap_ * ENTRY);
+        }
+        lut_dev_ = fresh;
+        lut_cap_ = cap;
+    }
+    int32_t index;
+    if (!lut_free_.empty()) { index = lut_free_.back(); lut_free_.pop_back(); }
+    else index = (int32_t)lut_used_++;
+    // a blocking copy: no launch enqueued so far names this entry (new, or freed after its last op had run)
+    std::vector<int32_t> padded((size_t)LUT_STRIDE, 0);
+    std::memcpy(padded.data(), words, (size_t)n_ring * sizeof(int32_t));
+    hip_check(hipMemcpy(lut_dev_ + (size_t)index * LUT_STRIDE, padded.data(), ENTRY, hipMemcpyHostToDevice), "upload LUT");
+    return index;
+}
+
+void Engine::lut_free(int32_t index) {
+    if (index >= 0 && (size_t)index < lut_used_) lut_free_.push_back(index);
 }
 
 SlotPool *Engine::find_pool(const Params &p) const {
@@ -578,7 +613,7 @@ BrPlan Engine::plan_br_launch(const DeviceKeyImage *key, int count, bool acc_dum
 
 void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int32_t *pool, const RotDesc *rots, int count,
                        int32_t *u_buf, int32_t *acc_dbg, hipStream_t stream, const DevKey *mk_keys, const int32_t *mk_rot_keys,
-                       hipEvent_t *mid) {
+                       hipEvent_t *mid, const int32_t *luts) {
     ENGINE_DEVICE_SCOPE();
     if (!stream) stream = stream_;
     const int form = plan.form, head = count - plan.tail;
@@ -586,6 +621,7 @@ void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int3
     if (plan.tail && (form != BR_FORM_WIDE4 || acc_dbg)) fatal("launch_br: a tail behind a launch that cannot be split");
     DevParams dp = key->dp;
     dp.digit_table = plan.tables;
+    dp.luts = luts ? luts : lut_dev_;
     // per-form and per-table-mode launch counters (TfheHipStats): what ran, whatever the tunings asked for
     auto note = [&](int f) {
         ++(f == BR_FORM_WIDE4 ? stats.br_wide4_launches : f == BR_FORM_SPLIT ? stats.br_split_launches
@@ -683,6 +719,13 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
         plan_in.dev_keys.resize((size_t)nkeys);
         for (int k = 0; k < nkeys; ++k) plan_in.dev_keys[(size_t)k] = keys[(size_t)k]->key;
     }
+    uint64_t lut_rots = 0;
+    for (const RotDesc &rd : plan_in.rots)
+        if (rd.lut >= 0) {
+            if ((size_t)rd.lut >= lut_used_) fatal("execute: a rotation names a test polynomial the engine does not hold");
+            ++lut_rots;
+        }
+    stats.lut_rotations += lut_rots;
     flight_plan_ = std::move(plan_in);               // owns the host descriptors until the uploads have certainly happened
     const LevelPlan &plan = flight_plan_;
     const int levels = plan.levels;
@@ -849,10 +892,22 @@ void Engine::wait_flight() {
 }
 
 
-void Engine::run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, Torus32 *u_out, Torus32 *acc_out) {
+void Engine::run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, Torus32 *u_out, Torus32 *acc_out,
+                                const int32_t *lut_index, const Torus32 *polys, int npolys) {
     ENGINE_DEVICE_SCOPE();
     wait_flight();
     const DevParams &dp = key->dp;
+    // the call's own table of test polynomials, laid out like the engine's
+    int32_t *dluts = nullptr;
+    std::vector<int32_t> table;
+    if (lut_index) {
+        for (int c = 0; c < count; ++c)
+            if (lut_index[c] >= npolys) api_fail("lut_bootstrap_woks: a LUT index beyond the table");
+        table.assign((size_t)std::max(npolys, 1) * LUT_STRIDE, 0);
+        for (int t = 0; t < npolys; ++t) std::memcpy(&table[(size_t)t * LUT_STRIDE], polys + (size_t)t * dp.N, (size_t)dp.N * 4);
+        dluts = static_cast<int32_t *>(scratch(13, table.size() * 4));
+        hip_check(hipMemcpyAsync(dluts, table.data(), table.size() * 4, hipMemcpyHostToDevice, stream_), "upload LUTs");
+    }
     // temporary "pool": count slots holding lin
     std::vector<int32_t> padded((size_t)count * dp.ct_stride, 0);
     for (int c = 0; c < count; ++c)
@@ -860,12 +915,16 @@ void Engine::run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, i
     int32_t *dpool = static_cast<int32_t *>(scratch(6, padded.size() * 4));
     hip_check(hipMemcpyAsync(dpool, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, stream_), "upload lin");
     std::vector<RotDesc> rots(count);
-    for (int c = 0; c < count; ++c) rots[c] = RotDesc{c, c, 1, 0, 0, c};
+    for (int c = 0; c < count; ++c) {
+        rots[c] = RotDesc{c, c, 1, 0, 0, c};
+        if (lut_index && lut_index[c] >= 0) { rots[c].lut = lut_index[c]; ++stats.lut_rotations; }
+    }
     RotDesc *drots = static_cast<RotDesc *>(scratch(0, rots.size() * sizeof(RotDesc)));
     hip_check(hipMemcpyAsync(drots, rots.data(), rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream_), "upload rots");
     int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)count * dp.u_stride * 4));
     int32_t *dacc = acc_out ? static_cast<int32_t *>(scratch(7, (size_t)count * 2 * dp.N * 4)) : nullptr;
-    launch_br(key, plan_br_launch(key, count, dacc != nullptr), dpool, drots, count, u_buf, dacc);
+    launch_br(key, plan_br_launch(key, count, dacc != nullptr), dpool, drots, count, u_buf, dacc, nullptr, nullptr, nullptr,
+              nullptr, dluts);
     hip_check(hipGetLastError(), "blind_rotate launch");
     std::vector<int32_t> ubuf((size_t)count * dp.u_stride);
     hip_check(hipMemcpyAsync(ubuf.data(), u_buf, ubuf.size() * 4, hipMemcpyDeviceToHost, stream_), "download u");

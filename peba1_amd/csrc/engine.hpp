@@ -134,8 +134,17 @@ public:
     long long sync_deadline_ms = 0;
     std::string diag_label;             // who waits, for the deadline message (tfhe_hip_set_diag_label: "rank 3 of 8")
     bool in_flight() const { return in_flight_; }
-    // raw test paths
-    void run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, Torus32 *u_out, Torus32 *acc_out);
+    // The table of caller-supplied test polynomials (tfhe_hip_new_lut): LUT_STRIDE words per entry in one device array
+    // that doubles on demand; RotDesc::lut indexes it.  lut_add copies n_ring words in and returns the entry (an entry
+    // freed earlier, or a new one); device memory exhausted while the table grows: ApiError, nothing changed.  lut_free
+    // gives the entry back -- the caller has run every recorded op that names it (recorder.cpp forget_lut_locked).
+    int32_t lut_add(const Torus32 *words, int n_ring);
+    void lut_free(int32_t index);
+    size_t lut_capacity() const { return lut_cap_; }
+    // raw test paths.  lut_index / polys (both or neither): combination c starts from test polynomial lut_index[c] of
+    // polys[npolys][N] (uploaded for this call only; an index below 0: the constant test vector)
+    void run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, Torus32 *u_out, Torus32 *acc_out,
+                            const int32_t *lut_index = nullptr, const Torus32 *polys = nullptr, int npolys = 0);
     void run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out);
     void run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const Torus32 *tp, Torus32 *res, int count);
 
@@ -154,9 +163,10 @@ public:
     // mk_keys / mk_rot_keys (device key table and per-rotation key indices of a multi-key level): the 4- and 8-wave
     // forms run each rotation under its own key; only for those forms, and `key` is entry 0 of the table.  mid: where
     // the event between the two launches of a plan with a tail goes (kernel timing of a flush), or null
+    // luts: the test-polynomial table the descriptors' lut indices refer to; null = the engine's own
     void launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int32_t *pool, const RotDesc *rots, int count,
                    int32_t *u_buf, int32_t *acc_dbg, hipStream_t stream = nullptr, const DevKey *mk_keys = nullptr,
-                   const int32_t *mk_rot_keys = nullptr, hipEvent_t *mid = nullptr);
+                   const int32_t *mk_rot_keys = nullptr, hipEvent_t *mid = nullptr, const int32_t *luts = nullptr);
     // diagnostic (tools/wg_times.py): ONE 4-wave blind-rotate launch of `width` random gates whose workgroups stamp s_memtime
     // and s_memrealtime at start and end into wg_times[4 * width]; returns that launch's event time in ms (< 0: no stamps)
     double run_wg_times(const DeviceKeyImage *key, int width, unsigned long long *wg_times);
@@ -189,6 +199,9 @@ private:
     hipEvent_t next_timing_event();
     std::vector<hipEvent_t> timing_events_;             // kernel_timing: up to 3 per level + 1 base
     hipEvent_t ev_[3] = {nullptr, nullptr, nullptr};
+    int32_t *lut_dev_ = nullptr;                        // [lut_cap_][LUT_STRIDE]
+    size_t lut_cap_ = 0, lut_used_ = 0;                 // entries allocated / ever handed out
+    std::vector<int32_t> lut_free_;
     std::vector<SlotPool *> pools_;
     std::vector<void *> scratch_ptr_;
     std::vector<size_t> scratch_size_;

@@ -214,6 +214,28 @@ __device__ __forceinline__ uint32_t testvector_coef(int j, int barb, int32_t mu)
     return (idx & N) ? (uint32_t)(-mu) : (uint32_t)mu;
 }
 
+// The same for a caller-supplied test polynomial v (a LUT: tfhe_hip_lut_bootstrap): coefficient j of X^{-barb} * v is
+// v[j + barb] below N and -v[j + barb - N] from N on, indices mod 2N.  Consecutive lanes read consecutive words of v (one
+// wrap per 2N): coalesced loads of N words, once per rotation.
+template <int LOGN>
+__device__ __forceinline__ uint32_t lut_coef(const int32_t *__restrict__ v, int j, int barb) {
+    constexpr int N = 1 << LOGN;
+    const int idx = (j + barb) & (2 * N - 1);
+    const uint32_t w = (uint32_t)v[idx & (N - 1)];
+    return (idx & N) ? 0u - w : w;
+}
+
+// the test polynomial a rotation starts from, or null for the constant one.  rd comes from a workgroup-uniform address:
+// the test is uniform, and a gate never forms the table's address
+__device__ __forceinline__ const int32_t *lut_of(const DevParams &p, const RotDesc &rd) {
+    return rd.lut >= 0 ? p.luts + (size_t)rd.lut * LUT_STRIDE : nullptr;
+}
+
+template <int LOGN>
+__device__ __forceinline__ uint32_t body_coef(const int32_t *__restrict__ lut, int j, int barb, int32_t mu) {
+    return lut ? lut_coef<LOGN>(lut, j, barb) : testvector_coef<LOGN>(j, barb, mu);
+}
+
 // The accumulator in LDS.  Each polynomial is kept as three runs of N words, (acc, -acc, acc):
 // coefficient (j - abar) mod 2N of the negacyclic rotation X^abar * ACC is then word
 // ((lane - abar) mod 2N) + 64 r of that array -- one address per lane and step, the 64 r being the
@@ -361,10 +383,11 @@ __global__ __launch_bounds__(128) void blind_rotate2_kernel(DevParams p, DevKey 
     __syncthreads();
     {
         const int barb = lds_bar[n];
+        const int32_t *lut = lut_of(p, rd);
 #pragma unroll
         for (int r = 0; r < REGS; ++r) {
             const int j = r * 64 + lane;
-            lds_acc.set(q, j, q == 0 ? 0u : testvector_coef<LOGN>(j, barb, p.mu));
+            lds_acc.set(q, j, q == 0 ? 0u : body_coef<LOGN>(lut, j, barb, p.mu));
         }
     }
     __syncthreads();
@@ -498,10 +521,11 @@ __device__ __forceinline__ void blind_rotate4_body(const DevParams &p, const Dev
     __syncthreads();
     if (q == 0) {
         const int barb = sh.bar[n];
+        const int32_t *lut = lut_of(p, rd);
 #pragma unroll
         for (int r = 0; r < REGS; ++r) {
             const int j = r * 64 + lane;
-            sh.acc.set(u, j, u == 0 ? 0u : testvector_coef<LOGN>(j, barb, p.mu));
+            sh.acc.set(u, j, u == 0 ? 0u : body_coef<LOGN>(lut, j, barb, p.mu));
         }
     }
     __syncthreads();
@@ -826,10 +850,11 @@ __global__ __launch_bounds__(512, (LOGN == 10 ? 4 : 2)) void blind_rotate_split_
     __syncthreads();
     if (q == 0) {
         const int barb = sh.bar[n];
+        const int32_t *lut = lut_of(p, rd);
 #pragma unroll
         for (int r = 0; r < RS; ++r) {
             const int j = h * M + r * 64 + lane;
-            sh.acc.set(u, j, u == 0 ? 0u : testvector_coef<LOGN>(j, barb, p.mu));
+            sh.acc.set(u, j, u == 0 ? 0u : body_coef<LOGN>(lut, j, barb, p.mu));
         }
     }
     __syncthreads();

@@ -21,7 +21,12 @@ struct DevParams {
                                     // clock the launches ran at; or null
     unsigned long long *wg_times;   // diagnostic: [4 * grid] s_memtime (shader cycles) at workgroup start and end, then
                                     // s_memrealtime (100 MHz) at start and end; or null
+    const int32_t *luts;            // table of caller-supplied test polynomials, LUT_STRIDE words apiece (RotDesc::lut indexes
+                                    // it); null when no rotation of the launch names one
 };
+
+// words between two test polynomials of a LUT table: the largest ring, so that one table serves every parameter set
+constexpr int LUT_STRIDE = 2048;
 
 // Device-resident evaluation key.
 struct DevKey {
@@ -36,6 +41,8 @@ struct DevKey {
 // One blind rotation: t = (0, c0) + sa * slot_a + sb * slot_b (+ sc * slot_c), then
 // modswitch, blind rotate, sample extract into u_buf[u_index].  slot_c = -1: no third operand (every upstream gate);
 // the three-input gates of tfhe_hip_gate3 set it.  The kernels read slot_c's words only when it is >= 0.
+// lut < 0: the accumulator starts from the constant test vector mu (1 + X + ... + X^(N-1)) of every gate; lut >= 0
+// (tfhe_hip_lut_bootstrap): from test polynomial `lut` of DevParams::luts, read only then.
 struct RotDesc {
     int32_t slot_a, slot_b;
     int32_t sa, sb;
@@ -43,6 +50,7 @@ struct RotDesc {
     int32_t u_index;
     int32_t slot_c = -1;
     int32_t sc = 0;
+    int32_t lut = -1;
 };
 
 // One key switch: (u_buf[u0] (+ u_buf[u1]) + (0, add_b)) -> pool[dst_slot].

@@ -20,26 +20,6 @@ const uint8_t GATE_TT[10][4] = {
     {0, 1, 0, 0}, {0, 0, 1, 0}, {1, 1, 0, 1}, {1, 0, 1, 1},
 };
 
-// a pending op by what it computes: kind, operand slots (-1 = absent) and the cloud key it bootstraps under (index in the
-// recording's key list): the same gate of the same slots under two keys gives two different ciphertexts
-struct OpKey {
-    int32_t kind, a, b, c, key;
-    bool operator==(const OpKey &o) const { return kind == o.kind && a == o.a && b == o.b && c == o.c && key == o.key; }
-};
-struct OpKeyHash {
-    size_t operator()(const OpKey &k) const {
-        uint64_t h = ((uint64_t)(uint32_t)k.a << 32 | (uint32_t)k.b) * 0x9E3779B97F4A7C15ull;
-        h ^= ((uint64_t)(uint32_t)k.c << 8 | (uint32_t)k.kind) * 0xC2B2AE3D27D4EB4Full;
-        h ^= (uint64_t)(uint32_t)k.key * 0x165667B19E3779F9ull;
-        return (size_t)(h ^ (h >> 29));
-    }
-};
-// symmetric two-input gates (sa == sb in GATE_LIN: t = c0 + s (A + B)) are keyed with ordered operands
-OpKey op_key(int kind, int32_t a, int32_t b, int32_t c, int32_t key) {
-    if (kind < OP_MUX && GATE_LIN[kind].sa == GATE_LIN[kind].sb && b < a) std::swap(a, b);
-    return OpKey{kind, a, b, c, key};
-}
-
 struct Recorder {
     std::recursive_mutex mtx;
     // Default: deferred.  The reference (and any caller that stays inside the tfhe C API) never reads a field of LweSample
@@ -161,11 +141,15 @@ void point_at(LweSample *result, SlotPool *pool, int32_t slot) {
 // 0 / 1 if `slot` is one of the pool's shared trivial samples (a public constant), else -1
 int const_bit(const SlotPool *pool, int32_t slot) { return slot == pool->const_slot[0] ? 0 : slot == pool->const_slot[1] ? 1 : -1; }
 
-// The one record path: share the result of a pending op that computes the same (kind, a, b, c), else append the op.
-// Two-input gates: c = -1; NOT: b = c = -1.
-void record_op(int kind, LweSample *result, SlotPool *pool, const int32_t a, const int32_t b, const int32_t c) {
+// The one record path: share the result of a pending op that computes the same thing (scheduler.hpp OpKey), else append the
+// op.  Two-input gates: c = -1; NOT: b = c = -1.  lut: the test polynomial, coefficients and constant of an OP_LUT (the
+// fields of a PendingOp it carries; the rest is filled in here), else null.
+void record_op(int kind, LweSample *result, SlotPool *pool, const int32_t a, const int32_t b, const int32_t c,
+               const PendingOp *lut = nullptr) {
     Recorder &r = rec();
-    const OpKey key = op_key(kind, a, b, c, r.cur_key);
+    PendingOp op = lut ? *lut : PendingOp{};
+    op.kind = (uint8_t)kind; op.a = a; op.b = b; op.c = c; op.key = r.cur_key;
+    const OpKey key = op_key(op);
     if (r.reuse_gates) {
         auto it = r.index.find(key);
         if (it != r.index.end()) {
@@ -181,7 +165,9 @@ void record_op(int kind, LweSample *result, SlotPool *pool, const int32_t a, con
     pool->level[dst] = level;
     pool->pending[dst] = 1;                   // pending even at level 0 (NOT of a materialised sample)
     pool->retain(dst);
-    r.ops.push_back(PendingOp{(uint8_t)kind, dst, a, b, c, level, r.cur_key});
+    op.dst = dst;
+    op.level = level;
+    r.ops.push_back(op);
     if (r.reuse_gates) r.index.emplace(key, dst);
     if (kind == OP_NOT) r.not_origin.emplace(dst, a);
     r.max_level = std::max(r.max_level, level);
@@ -199,7 +185,7 @@ void eliminate_dead_ops() {
     for (size_t i = r.ops.size(); i-- > 0;) {
         const PendingOp &op = r.ops[i];
         if (pool->refs(op.dst) != 1) continue;          // a handle or a live operation still holds the result
-        auto it = r.index.find(op_key(op.kind, op.a, op.b, op.c, op.key));
+        auto it = r.index.find(op_key(op));
         if (it != r.index.end() && it->second == op.dst) r.index.erase(it);
         if (op.kind == OP_NOT) r.not_origin.erase(op.dst);
         pool->level[op.dst] = 0;
@@ -376,6 +362,31 @@ void record_gate3_locked(int gate, int negate_mask, LweSample *result, const Lwe
     if (in[1].slot < in[0].slot) std::swap(in[0], in[1]);
     const int mask = in[0].neg | in[1].neg << 1 | in[2].neg << 2;
     record_op(OP_GATE3 + 8 * gate + mask, result, pool, in[0].slot, in[1].slot, in[2].slot);
+}
+
+// Programmable bootstrap (tfhe_hip_lut_bootstrap): t = (0, c0) + sum coef[i] in[i] from test polynomial `lut` of the engine's
+// table.  Never folded: a trivial operand is bootstrapped like any other (the result depends on the test polynomial, which
+// the folding rules know nothing about).
+void record_lut_locked(int32_t lut, LweSample *result, int nin, const LweSample *const *in, const int32_t *coef, int32_t c0,
+                       const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    begin_op(bk);
+    SlotPool *pool = r.pool;
+    bind_pool(result, pool);
+    int32_t slot[3] = {-1, -1, -1};
+    for (int i = 0; i < nin; ++i) slot[i] = ensure_slot(in[i], pool);
+    PendingOp op{};
+    op.lut = lut;
+    op.sa = coef[0]; op.sb = nin > 1 ? coef[1] : 0; op.sc = nin > 2 ? coef[2] : 0;
+    op.c0 = c0;
+    record_op(OP_LUT, result, pool, slot[0], slot[1], slot[2], &op);
+}
+
+void forget_lut_locked(int32_t lut) {
+    Recorder &r = rec();
+    auto names = [lut](const PendingOp &op) { return op.kind == OP_LUT && op.lut == lut; };
+    if (std::any_of(r.ops.begin(), r.ops.end(), names)) flush_locked();
+    else if (std::any_of(r.flight_ops.begin(), r.flight_ops.end(), names)) finish_flight_locked();
 }
 
 void record_constant_locked(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk) {

@@ -40,6 +40,11 @@ void record_mux_locked(LweSample *result, const LweSample *a, const LweSample *b
                        const TFheGateBootstrappingCloudKeySet *bk);
 void record_gate3_locked(int gate, int negate_mask, LweSample *result, const LweSample *a, const LweSample *b,
                          const LweSample *c, const TFheGateBootstrappingCloudKeySet *bk);
+// t = (0, c0) + coef[0] in[0] (+ coef[1] in[1]) (+ coef[2] in[2]), nin in 1..3 (checked by the caller), bootstrapped from
+// test polynomial `lut` of the engine's table and key-switched
+void record_lut_locked(int32_t lut, LweSample *result, int nin, const LweSample *const *in, const int32_t *coef, int32_t c0,
+                       const TFheGateBootstrappingCloudKeySet *bk);
+void forget_lut_locked(int32_t lut);   // a test polynomial about to be deleted: run the recording if an op in it names it
 void record_constant_locked(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk);
 void record_copy_locked(LweSample *result, const LweSample *a, const TFheGateBootstrappingCloudKeySet *bk);
 

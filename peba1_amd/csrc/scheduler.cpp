@@ -194,6 +194,13 @@ LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<
             plan.rots[i0] = RotDesc{op.a, op.b, 1, 1, -(mu), i0 - base};
             plan.rots[i1] = RotDesc{op.a, op.c, -1, 1, -(mu), i1 - base};
             plan.kss[kpos[sg]++] = KsDesc{i0 - base, i1 - base, mu, op.dst};
+        } else if (op.kind == OP_LUT) {
+            // t = (0, c0) + sa A (+ sb B) (+ sc C) from test polynomial op.lut: one rotation, one key switch.  The
+            // kernels read slot_b's words whatever sb is, so a one-operand op names A twice with sb = 0
+            const int32_t i0 = rpos[sg]++;
+            plan.rots[i0] = RotDesc{op.a, op.b >= 0 ? op.b : op.a, op.sa, op.b >= 0 ? op.sb : 0, op.c0, i0 - base,
+                                    op.c, op.c >= 0 ? op.sc : 0, op.lut};
+            plan.kss[kpos[sg]++] = KsDesc{i0 - base, -1, 0, op.dst};
         } else if (op_is_gate3(op.kind)) {
             // t = sa A + sb B + sc C, c0 = 0: one rotation, one key switch
             const int32_t i0 = rpos[sg]++;

@@ -10,23 +10,32 @@
 // to the width the kernels run well at.  Only the order among independent gates
 // changes; every gate computes the same integers.
 #pragma once
+#include <cstddef>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 namespace tfhe_hip {
 
 struct PendingOp {
-    uint8_t kind;       // 0..9 two-input gate code, OP_MUX, OP_NOT, OP_GATE3 + 8 gate + negation mask
+    uint8_t kind;       // 0..9 two-input gate code, OP_MUX, OP_NOT, OP_GATE3 + 8 gate + negation mask, OP_LUT
     int32_t dst, a, b, c;   // slots; b, c = -1 when absent
     int32_t level;      // ASAP level (NOT: the level of its operand, 0 = already materialised)
     uint16_t key = 0;   // index of the gate's cloud key in the flush's key list (recorder "batch_keys"; NOT: unused)
+    // OP_LUT only (tfhe_hip_lut_bootstrap): the test polynomial (index in the engine's LUT table) and the prelude
+    // t = (0, c0) + sa A + sb B + sc C; the coefficient of an absent operand is 0
+    int32_t lut = -1;
+    int32_t sa = 0, sb = 0, sc = 0, c0 = 0;
 };
 constexpr uint8_t OP_MUX = 16, OP_NOT = 17;
+// programmable bootstrap (not in upstream's gate API): one rotation from a caller-supplied test polynomial, one key switch
+constexpr uint8_t OP_LUT = 64;
 // three-input gates (tfhe_hip_gate3; not in upstream's API): kind = OP_GATE3 + 8 * gate + mask, gate = enum TfheHipGate3,
 // bit i of mask negates operand i (a = bit 0) -- 32..55.  The mask is part of the kind, hence of the recorder's index key
 constexpr uint8_t OP_GATE3 = 32, OP_GATE3_END = OP_GATE3 + 3 * 8;
 inline bool op_is_gate3(int kind) { return kind >= OP_GATE3 && kind < OP_GATE3_END; }
 inline bool op_kind_valid(int kind) { return (kind >= 0 && kind < 10) || kind == OP_MUX || kind == OP_NOT || op_is_gate3(kind); }
+inline bool op_kind_valid_lut(int kind) { return op_kind_valid(kind) || kind == OP_LUT; }
 
 inline int op_rotations(const PendingOp &op) { return op.kind == OP_NOT ? 0 : (op.kind == OP_MUX ? 2 : 1); }
 
@@ -43,6 +52,39 @@ constexpr int32_t GATE3_LIN[3] = {1, -2, 2};
 inline int32_t gate3_coef(int kind, int operand) {
     const int32_t s = GATE3_LIN[(kind - OP_GATE3) >> 3];
     return ((kind - OP_GATE3) >> operand) & 1 ? -s : s;
+}
+
+// A pending op by what it computes: kind, operand slots (-1 = absent), the cloud key it bootstraps under (index in the
+// recording's key list: the same gate of the same slots under two keys gives two different ciphertexts) and, for a LUT
+// op, the test polynomial, the coefficients and the constant.  The recorder shares the result of two pending ops exactly
+// when these are equal ("reuse_gates").
+struct OpKey {
+    int32_t kind, a, b, c, key;
+    int32_t lut, sa, sb, sc, c0;
+    bool operator==(const OpKey &o) const {
+        return kind == o.kind && a == o.a && b == o.b && c == o.c && key == o.key && lut == o.lut && sa == o.sa &&
+               sb == o.sb && sc == o.sc && c0 == o.c0;
+    }
+};
+struct OpKeyHash {
+    size_t operator()(const OpKey &k) const {
+        uint64_t h = ((uint64_t)(uint32_t)k.a << 32 | (uint32_t)k.b) * 0x9E3779B97F4A7C15ull;
+        h ^= ((uint64_t)(uint32_t)k.c << 8 | (uint32_t)k.kind) * 0xC2B2AE3D27D4EB4Full;
+        h ^= (uint64_t)(uint32_t)k.key * 0x165667B19E3779F9ull;
+        if (k.kind == OP_LUT) {
+            h ^= ((uint64_t)(uint32_t)k.lut << 32 | (uint32_t)k.c0) * 0xD6E8FEB86659FD93ull;
+            h ^= ((uint64_t)(uint32_t)k.sa << 40 ^ (uint64_t)(uint32_t)k.sb << 20 ^ (uint32_t)k.sc) * 0xFF51AFD7ED558CCDull;
+        }
+        return (size_t)(h ^ (h >> 29));
+    }
+};
+// symmetric two-input gates (sa == sb in GATE_LIN: t = c0 + s (A + B)) are keyed with ordered operands; a LUT op is keyed
+// as it was given
+inline OpKey op_key(const PendingOp &op) {
+    int32_t a = op.a, b = op.b;
+    if (op.kind < OP_MUX && GATE_LIN[op.kind].sa == GATE_LIN[op.kind].sb && b < a) std::swap(a, b);
+    if (op.kind != OP_LUT) return OpKey{op.kind, a, b, op.c, op.key, -1, 0, 0, 0, 0};
+    return OpKey{op.kind, a, b, op.c, op.key, op.lut, op.sa, op.sb, op.sc, op.c0};
 }
 
 // Fills lvl[i] with the level at which ops[i] runs (bootstrapped gates: 1..depth,

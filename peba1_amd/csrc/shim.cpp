@@ -6,7 +6,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "br_forms.hpp"
@@ -566,6 +568,120 @@ int tfhe_hip_gate3_batch(int gate, int negate_mask, LweSample *result, const Lwe
     return rc;
 }
 
+// ---- programmable bootstrap: caller-supplied test polynomials ----
+}  // extern "C"
+
+// A test polynomial bound to a ring size.  Its words reach the device at first use (a LUT can be built, read and
+// deleted on a machine without a GPU); `dev` is then its entry in the engine's table.
+struct TfheHipLut {
+    uint32_t magic;
+    int32_t N;
+    std::vector<Torus32> words;
+    int32_t dev;
+};
+
+namespace {
+constexpr uint32_t LUT_MAGIC = 0x4C55547Fu;
+
+TfheHipLut *make_lut(const char *who, const TFheGateBootstrappingParameterSet *params, const Torus32 *v) {
+    if (!params || !params->tgsw_params || !params->tgsw_params->tlwe_params) { set_error(std::string(who) + ": null parameter set"); return nullptr; }
+    const int32_t N = params->tgsw_params->tlwe_params->N;
+    if (N < 1 || N > LUT_STRIDE) { set_error(std::string(who) + ": ring size out of range"); return nullptr; }
+    auto *lut = new TfheHipLut{LUT_MAGIC, N, std::vector<Torus32>(), -1};
+    if (v) lut->words.assign(v, v + N);
+    else lut->words.assign((size_t)N, 0);
+    return lut;
+}
+
+// the checks every LUT bootstrap makes before anything is recorded; the LUT's entry in the engine's table (uploaded here at
+// first use: out of device memory is an ApiError, the call then has no effect)
+int32_t lut_entry(const TfheHipLut *lut, int32_t nin, const void *in, const int32_t *coef,
+                  const TFheGateBootstrappingCloudKeySet *bk) {
+    if (!lut || lut->magic != LUT_MAGIC) api_fail("tfhe_hip_lut_bootstrap: null or deleted LUT");
+    if (nin < 1 || nin > 3) api_fail("tfhe_hip_lut_bootstrap: nin must be 1, 2 or 3");
+    if (!in || !coef) api_fail("tfhe_hip_lut_bootstrap: null operand or coefficient list");
+    if (!bk || !bk->bk) api_fail("null cloud key");
+    if (bk->bk->p.N != lut->N)
+        api_fail("tfhe_hip_lut_bootstrap: the LUT holds " + std::to_string(lut->N) + " words, the key's ring has " +
+                 std::to_string(bk->bk->p.N));
+    if (lut->dev < 0) {
+        pool_of_key(bk);                                  // (the key image first: what initialises the device)
+        const_cast<TfheHipLut *>(lut)->dev = Engine::get().lut_add(lut->words.data(), lut->N);
+    }
+    return lut->dev;
+}
+}  // namespace
+
+extern "C" {
+
+TfheHipLut *tfhe_hip_new_lut(const TFheGateBootstrappingParameterSet *params, const Torus32 *v) {
+    if (!v) { set_error("tfhe_hip_new_lut: null words"); return nullptr; }
+    return make_lut("tfhe_hip_new_lut", params, v);
+}
+
+TfheHipLut *tfhe_hip_new_lut_constant(const TFheGateBootstrappingParameterSet *params, Torus32 mu) {
+    TfheHipLut *lut = make_lut("tfhe_hip_new_lut_constant", params, nullptr);
+    if (lut) std::fill(lut->words.begin(), lut->words.end(), mu);
+    return lut;
+}
+
+TfheHipLut *tfhe_hip_new_lut_from_table(const TFheGateBootstrappingParameterSet *params, const Torus32 *values, int32_t slots) {
+    if (!values) { set_error("tfhe_hip_new_lut_from_table: null values"); return nullptr; }
+    TfheHipLut *lut = make_lut("tfhe_hip_new_lut_from_table", params, nullptr);
+    if (!lut) return nullptr;
+    if (slots < 1 || lut->N % slots != 0) {
+        set_error("tfhe_hip_new_lut_from_table: slots must divide N = " + std::to_string(lut->N));
+        delete lut;
+        return nullptr;
+    }
+    for (int32_t j = 0; j < lut->N; ++j) lut->words[(size_t)j] = values[(int64_t)j * slots / lut->N];
+    return lut;
+}
+
+void tfhe_hip_delete_lut(TfheHipLut *lut) {
+    if (!lut) return;
+    if (lut->magic != LUT_MAGIC) { set_error("tfhe_hip_delete_lut: not a LUT (or already deleted)"); return; }
+    auto g = recorder_lock();
+    if (lut->dev >= 0) {
+        guarded([&] { forget_lut_locked(lut->dev); });    // recorded ops that name it run first, as for a key
+        Engine::get().lut_free(lut->dev);
+    }
+    lut->magic = 0;
+    delete lut;
+}
+
+const Torus32 *tfhe_hip_lut_words(const TfheHipLut *lut, int32_t *count) {
+    if (!lut || lut->magic != LUT_MAGIC) { set_error("tfhe_hip_lut_words: null or deleted LUT"); if (count) *count = 0; return nullptr; }
+    if (count) *count = lut->N;
+    return lut->words.data();
+}
+
+void tfhe_hip_lut_bootstrap(const TfheHipLut *lut, LweSample *result, int32_t nin, const LweSample *const *in,
+                            const int32_t *coef, Torus32 c0, const TFheGateBootstrappingCloudKeySet *bk) {
+    guarded([&] {
+        auto g = recorder_lock();
+        const int32_t entry = lut_entry(lut, nin, in, coef, bk);
+        record_lut_locked(entry, result, nin, in, coef, c0, bk);
+    });
+}
+
+int tfhe_hip_lut_bootstrap_batch(const TfheHipLut *lut, LweSample *result, int32_t nin, const LweSample *const *in,
+                                 const int32_t *coef, Torus32 c0, int32_t count, const TFheGateBootstrappingCloudKeySet *bk) {
+    auto g = recorder_lock();
+    const bool was = set_deferred_locked(true);
+    const int rc = guarded_rc([&] {
+        const int32_t entry = lut_entry(lut, nin, in, coef, bk);
+        for (int32_t i = 0; i < count; ++i) {
+            const LweSample *ops[3] = {&in[0][i], nin > 1 ? &in[1][i] : nullptr, nin > 2 ? &in[2][i] : nullptr};
+            record_lut_locked(entry, &result[i], nin, ops, coef, c0, bk);
+        }
+        return 0;
+    });
+    set_deferred_locked(was);
+    if (!was) flush_locked();      // ops recorded before a refused one still run
+    return rc;
+}
+
 void tfhe_hip_test_set_alloc_cap(int64_t bytes) {
     auto g = recorder_lock();
     set_alloc_cap((long long)bytes);
@@ -644,29 +760,75 @@ int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int
     return d;
 }
 
-// rot_words = 6: the two-operand words of every rotation (the form older callers know); 8: slot_c and sc as well
+// rot_words = 6: the two-operand words of every rotation (the form older callers know); 8: slot_c and sc as well; 9: and
+// the LUT index.  ops = ops5, or records of 10 words when lut_ops (tfhe_hip_test_level_plan_lut)
 static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
                            int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
-                           int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots, int rot_words, int32_t *kss4) {
+                           int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots, int rot_words, int32_t *kss4,
+                           bool lut_ops = false, int32_t reuse = 0, int32_t *shared_with = nullptr) {
     if (count < 0 || nkeys < 1 || nkeys > UINT16_MAX) { set_error("test_level_plan: bad count or nkeys"); return -1; }
     for (int32_t i = 0; i < count; ++i)
         if (op_keys[i] < 0 || op_keys[i] >= nkeys) { set_error("test_level_plan: key index out of range"); return -1; }
     std::vector<PendingOp> ops;
-    const int depth = test_build_ops(ops5, count, ops);
-    if (depth < 0) return -1;
-    for (int32_t i = 0; i < count; ++i) ops[i].key = (uint16_t)op_keys[i];
+    std::vector<int32_t> op_of_record;                   // lut_ops: record -> index in ops (-1: shared, see shared_with)
+    int depth;
+    if (!lut_ops) {
+        depth = test_build_ops(ops5, count, ops);
+        if (depth < 0) return -1;
+        for (int32_t i = 0; i < count; ++i) ops[i].key = (uint16_t)op_keys[i];
+    } else {
+        // As the recorder records them (recorder.cpp record_op): an op equal to a pending one by OpKey shares its result
+        // -- it is dropped, and later ops that read its destination read the earlier op's -- else it is appended with
+        // its ASAP level.  shared_with[i] = the record whose result record i shares, or -1.
+        std::unordered_map<OpKey, int32_t, OpKeyHash> index;       // key -> record
+        std::unordered_map<int32_t, int32_t> alias;                // destination of a dropped op -> the shared destination
+        std::vector<int32_t> slot_level;
+        op_of_record.assign((size_t)count, 0);
+        depth = 0;
+        auto resolve = [&](int32_t slot) { auto it = alias.find(slot); return it == alias.end() ? slot : it->second; };
+        auto level_of = [&](int32_t slot) { return slot >= 0 && (size_t)slot < slot_level.size() ? slot_level[slot] : 0; };
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t *o = ops5 + 10 * (size_t)i;
+            if (!op_kind_valid_lut(o[0])) { set_error("test schedule: unknown op kind"); return -1; }
+            PendingOp op{(uint8_t)o[0], o[1], resolve(o[2]), resolve(o[3]), resolve(o[4]), 0, (uint16_t)op_keys[i]};
+            if (op.kind == OP_LUT) { op.lut = o[5]; op.sa = o[6]; op.sb = o[7]; op.sc = o[8]; op.c0 = o[9]; }
+            if (shared_with) shared_with[i] = -1;
+            if (reuse) {
+                auto hit = index.find(op_key(op));
+                if (hit != index.end()) {
+                    alias[op.dst] = ops5[10 * (size_t)hit->second + 1];
+                    if (shared_with) shared_with[i] = hit->second;
+                    op_of_record[(size_t)i] = -1;
+                    continue;
+                }
+                index.emplace(op_key(op), i);
+            }
+            const int32_t in = std::max(level_of(op.a), std::max(level_of(op.b), level_of(op.c)));
+            op.level = op.kind == OP_NOT ? in : in + 1;
+            if ((size_t)op.dst >= slot_level.size()) slot_level.resize((size_t)op.dst + 1, 0);
+            slot_level[(size_t)op.dst] = op.level;
+            depth = std::max(depth, op.level);
+            op_of_record[(size_t)i] = (int32_t)ops.size();
+            ops.push_back(op);
+        }
+    }
     std::vector<int32_t> lvl;
     const int levels = schedule_levels(ops, depth, balance != 0, unit, lvl);
     const LevelPlan plan = build_level_plan(ops, lvl, levels, nkeys);     // exactly what flush_locked hands to execute()
-    for (int32_t i = 0; i < count; ++i) levels_out[i] = lvl[i];
+    for (int32_t i = 0; i < count; ++i) {
+        if (!lut_ops) { levels_out[i] = lvl[i]; continue; }
+        const int32_t at = op_of_record[(size_t)i] >= 0 ? op_of_record[(size_t)i] : op_of_record[(size_t)shared_with[i]];
+        levels_out[i] = lvl[(size_t)at];
+    }
     sizes6[0] = plan.levels;
     sizes6[1] = (int32_t)plan.rots.size();
     sizes6[2] = (int32_t)plan.kss.size();
     sizes6[3] = (int32_t)plan.rot_koff.size();
     sizes6[4] = (int32_t)plan.ks_koff.size();
     sizes6[5] = (int32_t)plan.rot_key.size();
-    static_assert(sizeof(RotDesc) == 8 * sizeof(int32_t) && offsetof(RotDesc, slot_c) == 6 * sizeof(int32_t) &&
-                      sizeof(KsDesc) == 4 * sizeof(int32_t), "descriptors are plain words, the third operand last");
+    static_assert(sizeof(RotDesc) == 9 * sizeof(int32_t) && offsetof(RotDesc, slot_c) == 6 * sizeof(int32_t) &&
+                      offsetof(RotDesc, lut) == 8 * sizeof(int32_t) && sizeof(KsDesc) == 4 * sizeof(int32_t),
+                  "descriptors are plain words: the third operand behind the first six, the LUT index last");
     auto copy = [](int32_t *dst, const void *src, size_t words) { if (words) std::memcpy(dst, src, words * sizeof(int32_t)); };
     copy(rot_off, plan.rot_off.data(), plan.rot_off.size());
     copy(ks_off, plan.ks_off.data(), plan.ks_off.size());
@@ -689,6 +851,15 @@ int tfhe_hip_test_level_plan3(const int32_t *ops5, const int32_t *op_keys, int32
                               int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots8, int32_t *kss4) {
     return test_level_plan(ops5, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
                            rot_key, rots8, 8, kss4);
+}
+
+int tfhe_hip_test_level_plan_lut(const int32_t *ops10, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                                 int32_t balance, int32_t reuse, int32_t *levels_out, int32_t *shared_with, int32_t *sizes6,
+                                 int32_t *rot_off, int32_t *ks_off, int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key,
+                                 int32_t *rots9, int32_t *kss4) {
+    if (reuse && !shared_with) { set_error("test_level_plan_lut: reuse needs shared_with"); return -1; }
+    return test_level_plan(ops10, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
+                           rot_key, rots9, 9, kss4, true, reuse, shared_with);
 }
 
 int tfhe_hip_test_br_plan(int32_t N, int32_t l, int32_t Bgbit, const int32_t *tunings4, int32_t cu_count, int32_t count,
@@ -748,6 +919,18 @@ int tfhe_hip_kernel_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *bk, c
     pool_of_key(bk);
     Engine::get().run_bootstrap_woks(bk->bk->dev, lin, count, u_out, acc_out);
     return 0;
+}
+int tfhe_hip_kernel_lut_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *lin, int32_t count,
+                                       const int32_t *lut_index, const Torus32 *polys, int32_t npolys, Torus32 *u_out,
+                                       Torus32 *acc_out) {
+    if (!bk || !bk->bk) { set_error("lut_bootstrap_woks: null keyset"); return -1; }
+    if (!lut_index || !polys || npolys < 1) { set_error("lut_bootstrap_woks: null or empty LUT table"); return -1; }
+    auto g = recorder_lock();
+    return guarded_rc([&] {
+        pool_of_key(bk);
+        Engine::get().run_bootstrap_woks(bk->bk->dev, lin, count, u_out, acc_out, lut_index, polys, npolys);
+        return 0;
+    });
 }
 int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *u, int32_t count, Torus32 *out) {
     if (!bk || !bk->bk) { set_error("keyswitch: null keyset"); return -1; }
