@@ -206,6 +206,60 @@ void tfhe_hip_lut_bootstrap(const TfheHipLut *lut, LweSample *result, int32_t ni
 int tfhe_hip_lut_bootstrap_batch(const TfheHipLut *lut, LweSample *result, int32_t nin, const LweSample *const *in,
                                  const int32_t *coef, Torus32 c0, int32_t count, const TFheGateBootstrappingCloudKeySet *bk);
 
+/* ---- several extractions from one rotation (multi-output LUT bootstrap): NOT PART OF UPSTREAM TFHE'S GATE API.  After
+ * the n CMUX steps the accumulator ACC = (A, B) holds X^-p v for the encrypted phase p; coefficient 0, which every entry
+ * above extracts, is one of N.  Coefficient e decrypts to the negacyclic table v read at p + e, and a small-integer
+ * combination of a few coefficients is again one LWE sample under the same key -- so one rotation can feed several key
+ * switches, each a different function of the same input (the multi-value bootstrap of Carpov, Izabachene and Mollimard).
+ * Defined by integers:
+ *     Extract_e(ACC), 0 <= e < N, is the sample with  b = B[e],  a_i = A[e - i] for i <= e,  a_i = -A[N + e - i] for i > e
+ *     (the negacyclic extension of A read at (e - i) mod 2N; Extract_0 is the extract of every entry above)
+ *     u_m = (0, out_c0[m]) + sum_t weight[m][t] * Extract_{index[m][t]}(ACC)        (wrapping mod 2^32 on all N+1 words)
+ *     result[m] = the key switch of u_m, as for every extracted sample.
+ * Prelude, modulus switch, ACC and the CMUX steps are those of tfhe_hip_lut_bootstrap.
+ * Limits: nout in 1..4 outputs; 1..8 taps per output; 0 <= index < N; weight non-zero with |weight| <= 8; the taps of one
+ * output have distinct indices.  One output with the one tap (0, +1) and out_c0 = 0 gives tfhe_hip_lut_bootstrap's words.
+ * Noise (COMPUTED, not measured -- see profiles/lut_multi.txt for what was): the taps multiply the accumulator's noise by
+ * their weights, so to first order an output's variance is sum_t weight^2 times the rotation variance of a gate, plus the
+ * key-switch term, which does not grow.  The caller chooses tables whose weights its margins can bear.
+ * tfhe_hip_new_lut_multi: everything is copied, the LUT's words included (the object holds its own entry in the engine's
+ * table, so the LUT may be deleted afterwards); taps of all outputs are concatenated in output order (tap_index,
+ * tap_weight: sum ntaps words); out_c0 null = zeros.  Like a LUT it is made, read and deleted without a GPU, reaches the
+ * device at its first bootstrap, and deleting it runs the recording first if a recorded bootstrap names it.
+ * tfhe_hip_new_lut_multi_from_tables: the usable form.  For an input phase in sector s of the half torus (`slots` sectors,
+ * slots >= 2 divides N) output m has phase step * levels[m * slots + s].  Construction: the constant polynomial step/2
+ * (step must be even); taps at j N/slots, j = 1..slots-1, with weight levels[m][slots-1-j] - levels[m][slots-j], zero
+ * weights dropped; out_c0[m] = (step/2)(levels[m][0] + levels[m][slots-1]).  Why: for p in sector s coefficient j N/slots
+ * decrypts to +step/2 when j <= slots-1-s and to -step/2 above, the weights up to J telescope to levels[slots-1-J] -
+ * levels[slots-1], and the two partial sums give step levels[s] - (step/2)(levels[0] + levels[slots-1]).  Refused: a
+ * weight beyond the limits, an output that would need no tap (equal levels everywhere), more than 8 taps.
+ * tfhe_hip_lut_multi_nout / _output (taps and constant of output m into caller arrays of 8; returns the tap count) /
+ * _words (the N words of the test polynomial): read-only accessors; -1 / NULL and the error channel on bad arguments.
+ * tfhe_hip_lut_bootstrap_multi: result[nout] sample pointers; a NULL result[m] means "not wanted": that output is neither
+ * extracted nor key-switched.  Recorded like every gate: ONE operation of one level whose wanted results are each
+ * SSA-renamed and become available together; dead results are eliminated per output (the operation goes when all are
+ * dead); "reuse_gates" shares two pending ones only if spec, LUT (the same object), operands, coefficients, c0 and key are
+ * all equal, output by output, and an output the earlier one lacked is ADDED to it (the earlier operation is widened);
+ * never constant-folded; batched across keys like a LUT bootstrap.
+ * Errors (tfhe_hip_last_error(), call without effect): those of tfhe_hip_lut_bootstrap, a null or deleted object, two
+ * results that are the same sample, every result null.
+ * tfhe_hip_lut_bootstrap_multi_batch: result[m] (or NULL) is an array of count samples, in[k] likewise; 0 / -1. ---- */
+typedef struct TfheHipLutMulti TfheHipLutMulti;
+TfheHipLutMulti *tfhe_hip_new_lut_multi(const TfheHipLut *lut, int32_t nout, const int32_t *ntaps, const int32_t *tap_index,
+                                        const int32_t *tap_weight, const Torus32 *out_c0);
+TfheHipLutMulti *tfhe_hip_new_lut_multi_from_tables(const TFheGateBootstrappingParameterSet *params, Torus32 step, int32_t slots,
+                                                    int32_t nout, const int32_t *levels /*[nout][slots]*/);
+void tfhe_hip_delete_lut_multi(TfheHipLutMulti *mo);
+int32_t tfhe_hip_lut_multi_nout(const TfheHipLutMulti *mo);
+int32_t tfhe_hip_lut_multi_output(const TfheHipLutMulti *mo, int32_t m, int32_t *tap_index, int32_t *tap_weight, Torus32 *out_c0);
+const Torus32 *tfhe_hip_lut_multi_words(const TfheHipLutMulti *mo, int32_t *count);
+void tfhe_hip_lut_bootstrap_multi(const TfheHipLutMulti *mo, LweSample *const *result /*[nout]*/, int32_t nin,
+                                  const LweSample *const *in, const int32_t *coef, Torus32 c0,
+                                  const TFheGateBootstrappingCloudKeySet *bk);
+int tfhe_hip_lut_bootstrap_multi_batch(const TfheHipLutMulti *mo, LweSample *const *result /*[nout]*/, int32_t nin,
+                                       const LweSample *const *in, const int32_t *coef, Torus32 c0, int32_t count,
+                                       const TFheGateBootstrappingCloudKeySet *bk);
+
 /* ---- tuning (eleven names that results never depend on, and the opt-in "fold_constants") ----
  * "br_variant": which form of the blind-rotate kernel runs wide launches (env TFHE_HIP_BR_VARIANT): -1 (default) =
  * the fastest measured for the ring size (N = 1024: 4 waves per rotation; N = 2048: split), 0 = 4 waves (N = 1024),
@@ -293,6 +347,11 @@ typedef struct TfheHipStats {
     /* of blind_rotates, those that started from a caller-supplied test polynomial (tfhe_hip_lut_bootstrap; the raw
      * entry tfhe_hip_kernel_lut_bootstrap_woks included) */
     uint64_t lut_rotations;
+    /* of blind_rotates, those that left through an extract spec (tfhe_hip_lut_bootstrap_multi; the raw entry
+     * tfhe_hip_kernel_lut_bootstrap_multi_woks included), and the outputs they wrote.  `keyswitches` counts one per
+     * output written by a flush */
+    uint64_t multi_rotations;
+    uint64_t multi_outputs;
 } TfheHipStats;
 void tfhe_hip_get_stats(TfheHipStats *out);
 void tfhe_hip_reset_stats(void);
@@ -344,6 +403,18 @@ int tfhe_hip_test_level_plan_lut(const int32_t *ops10, const int32_t *op_keys, i
                                  int32_t balance, int32_t reuse, int32_t *levels_out, int32_t *shared_with, int32_t *sizes6,
                                  int32_t *rot_off, int32_t *ks_off, int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key,
                                  int32_t *rots9, int32_t *kss4);
+/* The same for recordings that hold multi-output bootstraps, with the recorder's sharing and elimination rules: ops16 =
+ * count x {kind, dst, a, b, c, lut, sa, sb, sc, c0, spec, nout, d0, d1, d2, d3} (kind 65 = a multi-output bootstrap: dst is
+ * not read, d_m = the destination of output m or -1 when it is not wanted; other kinds as in ops10, the last six words not
+ * read).  reuse != 0: an equal earlier multi-output record serves a later one output by output and gains the outputs it
+ * lacked (shared_with as above).  dead_slots[ndead]: destinations no handle holds at the flush -- one that no surviving
+ * record reads is eliminated, per output for kind 65; a record eliminated altogether gets level -1.  rots10: the nine
+ * words above and the extract spec word (-1, or spec | wanted outputs << 24); a multi-output rotation's output m is sample
+ * u_index + m of its level, and kss4 holds one {u, -1, 0, destination} per wanted output. */
+int tfhe_hip_test_level_plan_multi(const int32_t *ops16, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                                   int32_t balance, int32_t reuse, const int32_t *dead_slots, int32_t ndead,
+                                   int32_t *levels_out, int32_t *shared_with, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
+                                   int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots10, int32_t *kss4);
 /* ---- host-logic test entries: the launch rules of peba1_amd/csrc/launch_plan.hpp, without touching the device.
  * tfhe_hip_test_br_plan: the blind-rotate launches of a level of `count` rotations of gadget (l, Bgbit) at ring size N on
  * a card of `cu_count` CUs under tunings4 = {br_variant, br8_max_rotations, br_tail8, br_digit_table}; flags bit 0 = the
@@ -380,6 +451,15 @@ int tfhe_hip_kernel_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *bk, c
 int tfhe_hip_kernel_lut_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *lin, int32_t count,
                                        const int32_t *lut_index, const Torus32 *polys, int32_t npolys, Torus32 *u_out,
                                        Torus32 *acc_out);
+/* the same with extract specs: combination c leaves through specs[spec_index[c]] (an index below 0: the extract at index 0;
+ * lut_index as above).  specs: nspecs records of TFHE_HIP_EXTRACT_SPEC_WORDS words {nout, ntaps[4], out_c0[4], index[4][8],
+ * weight[4][8]}, checked against the limits.  u_out[count][4][kN+1]: output m of combination c at [c][m] (a plain extract at
+ * [c][0]), the rest untouched; on the device the outputs of all combinations lie back to back.  acc_out as above. */
+#define TFHE_HIP_EXTRACT_SPEC_WORDS 73
+int tfhe_hip_kernel_lut_bootstrap_multi_woks(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *lin, int32_t count,
+                                             const int32_t *lut_index, const Torus32 *polys, int32_t npolys,
+                                             const int32_t *spec_index, const int32_t *specs, int32_t nspecs, Torus32 *u_out,
+                                             Torus32 *acc_out);
 /* key switch of `count` extracted samples u[c] (kN+1 words) -> out[c] (n+1 words) */
 int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *u,
                               int32_t count, Torus32 *out);

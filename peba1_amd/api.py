@@ -327,6 +327,94 @@ def lut_bootstrap_batch(lut, result, inputs, coefs, c0, key):
         raise RuntimeError(last_error())
 
 
+class LutMulti:
+    """A test polynomial with an extract spec (tfhe_hip_new_lut_multi): one blind rotation, several outputs.  `outputs` is
+    a list of (taps, out_c0) with taps = [(index, weight), ...]; output m is (0, out_c0) + sum weight * Extract_index(ACC),
+    key-switched -- the integers are in include/tfhe_hip.h."""
+
+    def __init__(self, lut, outputs):
+        ntaps = np.array([len(t) for t, _ in outputs], dtype=np.int32)
+        idx = np.array([i for t, _ in outputs for i, _ in t] or [0], dtype=np.int32)
+        wgt = np.array([w for t, _ in outputs for _, w in t] or [0], dtype=np.int32)
+        c0 = np.array([_wrap32(c) for _, c in outputs] or [0], dtype=np.int32)
+        self._take(lut.params, _l.load().tfhe_hip_new_lut_multi(lut.ptr, len(outputs), _i32p(ntaps), _i32p(idx), _i32p(wgt),
+                                                               _i32p(c0)))
+
+    def _take(self, params, ptr):
+        self.params, self.ptr = params, ptr
+        if not ptr:
+            raise ValueError("multi-output LUT rejected: " + last_error())
+
+    @classmethod
+    def from_tables(cls, params, step, levels):
+        """For an input phase in sector s of the half torus (len(levels[m]) sectors) output m has phase step * levels[m][s]."""
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        assert lv.ndim == 2
+        self = cls.__new__(cls)
+        self._take(params, _l.load().tfhe_hip_new_lut_multi_from_tables(params.ptr, _wrap32(step), lv.shape[1], lv.shape[0],
+                                                                        _i32p(lv)))
+        return self
+
+    @property
+    def nout(self):
+        return _l.load().tfhe_hip_lut_multi_nout(self.ptr)
+
+    def outputs(self):
+        """[(taps, out_c0)] as the object holds them."""
+        out = []
+        for m in range(self.nout):
+            idx, wgt, c0 = np.zeros(8, np.int32), np.zeros(8, np.int32), C.c_int32()
+            n = _l.load().tfhe_hip_lut_multi_output(self.ptr, m, _i32p(idx), _i32p(wgt), C.byref(c0))
+            out.append(([(int(i), int(w)) for i, w in zip(idx[:n], wgt[:n])], c0.value))
+        return out
+
+    def words(self):
+        cnt = C.c_int32()
+        p = _l.load().tfhe_hip_lut_multi_words(self.ptr, C.byref(cnt))
+        return np.ctypeslib.as_array(p, shape=(cnt.value,)).copy()
+
+    def close(self):
+        if self.ptr:
+            _l.load().tfhe_hip_delete_lut_multi(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _wrap32(x):
+    x = int(x) & 0xFFFFFFFF
+    return x - (1 << 32) if x >= 1 << 31 else x
+
+
+def lut_bootstrap_multi(mo, results, inputs, coefs, c0, key):
+    """results[m] = output m of the multi-output LUT bootstrap of (0, c0) + sum coefs[i] inputs[i]; results and inputs are
+    LweSample pointers, a result of None is not wanted.  Errors go to last_error() and leave the results untouched."""
+    n = len(inputs)
+    ins = (_l.LS * max(n, 1))(*inputs)
+    res = (_l.LS * max(len(results), 4))(*results)
+    cf = np.ascontiguousarray(coefs, dtype=np.int32)
+    assert len(cf) == n
+    _l.load().tfhe_hip_lut_bootstrap_multi(mo.ptr if mo is not None else None, res, n, ins, _i32p(cf), _wrap32(c0), key.cloud)
+
+
+def lut_bootstrap_multi_batch(mo, results, inputs, coefs, c0, key):
+    """results[m][i] = output m for inputs[k][i]: CiphertextArrays of equal count (a result of None is not wanted)."""
+    n = len(inputs)
+    ins = (_l.LS * max(n, 1))(*[a.ptr for a in inputs])
+    res = (_l.LS * max(len(results), 4))(*[r.ptr if r is not None else None for r in results])
+    cf = np.ascontiguousarray(coefs, dtype=np.int32)
+    assert len(cf) == n
+    count = next(r.count for r in results if r is not None)
+    rc = _l.load().tfhe_hip_lut_bootstrap_multi_batch(mo.ptr if mo is not None else None, res, n, ins, _i32p(cf), _wrap32(c0),
+                                                      count, key.cloud)
+    if rc != 0:
+        raise RuntimeError(last_error())
+
+
 def set_deferred(on):
     _l.load().tfhe_hip_set_deferred(1 if on else 0)
 
@@ -401,6 +489,44 @@ def kernel_lut_bootstrap_woks(key, lin, lut_index, polys, want_acc=False):
     acc = np.zeros((lin.shape[0], (p.k + 1) * p.N), dtype=np.int32) if want_acc else None
     rc = _l.load().tfhe_hip_kernel_lut_bootstrap_woks(key.cloud, _i32p(lin), lin.shape[0], _i32p(idx), _i32p(polys),
                                                       polys.shape[0], _i32p(u), _i32p(acc) if want_acc else None)
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return (u, acc) if want_acc else u
+
+
+EXTRACT_SPEC_WORDS = 73
+
+
+def pack_extract_specs(specs):
+    """[[(taps, out_c0), ...], ...] -> the records of kernel_lut_bootstrap_multi_woks: {nout, ntaps[4], out_c0[4],
+    index[4][8], weight[4][8]} per spec."""
+    out = np.zeros((len(specs), EXTRACT_SPEC_WORDS), dtype=np.int32)
+    for rec, outputs in zip(out, specs):
+        rec[0] = len(outputs)
+        for m, (taps, c0) in enumerate(outputs):
+            rec[1 + m] = len(taps)
+            rec[5 + m] = _wrap32(c0)
+            for t, (i, w) in enumerate(taps):
+                rec[9 + 8 * m + t] = i
+                rec[41 + 8 * m + t] = w
+    return out
+
+
+def kernel_lut_bootstrap_multi_woks(key, lin, lut_index, polys, spec_index, specs, want_acc=False):
+    """kernel_lut_bootstrap_woks with extract specs: combination c leaves through specs[spec_index[c]] (index < 0: the
+    extract at index 0).  Returns u[count][4][kN+1] -- output m of combination c at [c][m], zeros where there is none --
+    and, if asked, the raw accumulators."""
+    p = key.params
+    lin = np.ascontiguousarray(lin, dtype=np.int32).reshape(-1, p.words)
+    idx = np.ascontiguousarray(lut_index, dtype=np.int32).reshape(lin.shape[0])
+    sidx = np.ascontiguousarray(spec_index, dtype=np.int32).reshape(lin.shape[0])
+    polys = np.ascontiguousarray(polys, dtype=np.int32).reshape(-1, p.N)
+    recs = pack_extract_specs(specs)
+    u = np.zeros((lin.shape[0], 4, p.k * p.N + 1), dtype=np.int32)
+    acc = np.zeros((lin.shape[0], (p.k + 1) * p.N), dtype=np.int32) if want_acc else None
+    rc = _l.load().tfhe_hip_kernel_lut_bootstrap_multi_woks(key.cloud, _i32p(lin), lin.shape[0], _i32p(idx), _i32p(polys),
+                                                            polys.shape[0], _i32p(sidx), _i32p(recs), recs.shape[0], _i32p(u),
+                                                            _i32p(acc) if want_acc else None)
     if rc != 0:
         raise RuntimeError(last_error())
     return (u, acc) if want_acc else u

@@ -369,6 +369,7 @@ static DevParams make_dev_params(const Params &p) {
     d.clock_acc = nullptr;
     d.wg_times = nullptr;
     d.luts = nullptr;
+    d.specs = nullptr;
     return d;
 }
 
@@ -487,6 +488,38 @@ int32_t Engine::lut_add(const Torus32 *words, int n_ring) {
 
 void Engine::lut_free(int32_t index) {
     if (index >= 0 && (size_t)index < lut_used_) lut_free_.push_back(index);
+}
+
+// ---- extract specs ---------------------------------------------------------------
+int32_t Engine::spec_add(const ExtractSpec &xs) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    if (spec_free_.empty() && spec_used_ == spec_cap_) {
+        if (spec_cap_ > (size_t)XS_ENTRY_MASK / 2) api_fail("too many extract specs");
+        const size_t cap = spec_cap_ ? spec_cap_ * 2 : 16;
+        ExtractSpec *fresh = static_cast<ExtractSpec *>(recoverable_alloc(cap * sizeof(ExtractSpec), "growing the table of extract specs"));
+        if (spec_dev_) {
+            // launches in flight carry the old pointer: wait for all of them, as for the table of test polynomials
+            sync_stream("sync before spec table growth");
+            hip_check(hipDeviceSynchronize(), "sync before spec table growth");
+            hip_check(hipMemcpy(fresh, spec_dev_, spec_cap_ * sizeof(ExtractSpec), hipMemcpyDeviceToDevice), "copy spec table");
+            recoverable_free(spec_dev_, spec_cap_ * sizeof(ExtractSpec));
+        }
+        spec_dev_ = fresh;
+        spec_cap_ = cap;
+    }
+    int32_t index;
+    if (!spec_free_.empty()) { index = spec_free_.back(); spec_free_.pop_back(); }
+    else index = (int32_t)spec_used_++;
+    // a blocking copy: no launch enqueued so far names this entry
+    hip_check(hipMemcpy(spec_dev_ + index, &xs, sizeof(ExtractSpec), hipMemcpyHostToDevice), "upload extract spec");
+    if (spec_nout_.size() <= (size_t)index) spec_nout_.resize((size_t)index + 1, 0);
+    spec_nout_[(size_t)index] = xs.nout;
+    return index;
+}
+
+void Engine::spec_free(int32_t index) {
+    if (index >= 0 && (size_t)index < spec_used_) spec_free_.push_back(index);
 }
 
 SlotPool *Engine::find_pool(const Params &p) const {
@@ -613,7 +646,7 @@ BrPlan Engine::plan_br_launch(const DeviceKeyImage *key, int count, bool acc_dum
 
 void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int32_t *pool, const RotDesc *rots, int count,
                        int32_t *u_buf, int32_t *acc_dbg, hipStream_t stream, const DevKey *mk_keys, const int32_t *mk_rot_keys,
-                       hipEvent_t *mid, const int32_t *luts) {
+                       hipEvent_t *mid, const int32_t *luts, const ExtractSpec *specs) {
     ENGINE_DEVICE_SCOPE();
     if (!stream) stream = stream_;
     const int form = plan.form, head = count - plan.tail;
@@ -622,6 +655,7 @@ void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int3
     DevParams dp = key->dp;
     dp.digit_table = plan.tables;
     dp.luts = luts ? luts : lut_dev_;
+    dp.specs = specs ? specs : spec_dev_;
     // per-form and per-table-mode launch counters (TfheHipStats): what ran, whatever the tunings asked for
     auto note = [&](int f) {
         ++(f == BR_FORM_WIDE4 ? stats.br_wide4_launches : f == BR_FORM_SPLIT ? stats.br_split_launches
@@ -704,7 +738,7 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
     KsDesc *dks = static_cast<KsDesc *>(scratch(1, plan_in.kss.size() * sizeof(KsDesc) + 16));
     NotDesc *dnots = static_cast<NotDesc *>(scratch(2, plan_in.nots.size() * sizeof(NotDesc) + 16));
     // extract buffer, sized for the widest level, and key-switch partial sums, sized by the split rule launch_ks applies
-    int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)(plan_in.max_rots + 1) * key->dp.u_stride * 4));
+    int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)(std::max(plan_in.max_rots, plan_in.max_extracts) + 1) * key->dp.u_stride * 4));
     size_t partial = 0;
     const std::vector<int32_t> &ks_shares = nkeys == 1 ? plan_in.ks_off : plan_in.ks_koff;   // one key-switch launch per (level, key)
     for (size_t sg = 0; sg + 1 < ks_shares.size(); ++sg)
@@ -725,7 +759,20 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
             if ((size_t)rd.lut >= lut_used_) fatal("execute: a rotation names a test polynomial the engine does not hold");
             ++lut_rots;
         }
+    // multi-output rotations: the spec is the engine's and every output it writes lies inside the extract buffer sized
+    // above (checked here, before anything is enqueued)
+    uint64_t multi_rots = 0, multi_outs = 0;
+    for (const RotDesc &rd : plan_in.rots)
+        if (rd.spec >= 0) {
+            if ((size_t)(rd.spec & XS_ENTRY_MASK) >= spec_used_) fatal("execute: a rotation names an extract spec the engine does not hold");
+            if (rd.u_index < 0 || rd.u_index + spec_nout_[(size_t)(rd.spec & XS_ENTRY_MASK)] > plan_in.max_extracts)
+                fatal("execute: a multi-output rotation writes beyond the extract buffer");
+            ++multi_rots;
+            multi_outs += (uint64_t)__builtin_popcount((unsigned)(rd.spec >> XS_WANTED_SHIFT));
+        }
     stats.lut_rotations += lut_rots;
+    stats.multi_rotations += multi_rots;
+    stats.multi_outputs += multi_outs;
     flight_plan_ = std::move(plan_in);               // owns the host descriptors until the uploads have certainly happened
     const LevelPlan &plan = flight_plan_;
     const int levels = plan.levels;
@@ -932,6 +979,68 @@ void Engine::run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, i
     sync_stream("bootstrap_woks");
     for (int c = 0; c < count; ++c)
         std::memcpy(u_out + (size_t)c * (dp.k * dp.N + 1), &ubuf[(size_t)c * dp.u_stride], (size_t)(dp.k * dp.N + 1) * 4);
+    stats.blind_rotates += (uint64_t)count;
+}
+
+void Engine::run_bootstrap_multi_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, const int32_t *lut_index,
+                                      const Torus32 *polys, int npolys, const int32_t *spec_index, const ExtractSpec *specs,
+                                      int nspecs, Torus32 *u_out, Torus32 *acc_out) {
+    ENGINE_DEVICE_SCOPE();
+    wait_flight();
+    const DevParams &dp = key->dp;
+    for (int c = 0; c < count; ++c) {
+        if (lut_index[c] >= npolys) api_fail("lut_bootstrap_multi_woks: a LUT index beyond the table");
+        if (spec_index[c] >= nspecs) api_fail("lut_bootstrap_multi_woks: a spec index beyond the table");
+    }
+    for (int t = 0; t < nspecs; ++t)
+        if (const char *why = extract_spec_error(specs[t], dp.N)) api_fail(std::string("lut_bootstrap_multi_woks: ") + why);
+    // the call's own tables, laid out like the engine's
+    std::vector<int32_t> table((size_t)std::max(npolys, 1) * LUT_STRIDE, 0);
+    for (int t = 0; t < npolys; ++t) std::memcpy(&table[(size_t)t * LUT_STRIDE], polys + (size_t)t * dp.N, (size_t)dp.N * 4);
+    int32_t *dluts = static_cast<int32_t *>(scratch(13, table.size() * 4));
+    hip_check(hipMemcpyAsync(dluts, table.data(), table.size() * 4, hipMemcpyHostToDevice, stream_), "upload LUTs");
+    ExtractSpec *dspecs = static_cast<ExtractSpec *>(scratch(14, (size_t)std::max(nspecs, 1) * sizeof(ExtractSpec)));
+    if (nspecs) hip_check(hipMemcpyAsync(dspecs, specs, (size_t)nspecs * sizeof(ExtractSpec), hipMemcpyHostToDevice, stream_), "upload specs");
+    std::vector<int32_t> padded((size_t)count * dp.ct_stride, 0);
+    for (int c = 0; c < count; ++c)
+        std::memcpy(&padded[(size_t)c * dp.ct_stride], lin + (size_t)c * (dp.n + 1), (size_t)(dp.n + 1) * 4);
+    int32_t *dpool = static_cast<int32_t *>(scratch(6, padded.size() * 4));
+    hip_check(hipMemcpyAsync(dpool, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, stream_), "upload lin");
+    // u_index: the outputs of the combinations before this one
+    std::vector<RotDesc> rots(count);
+    std::vector<int32_t> first(count);
+    int32_t total = 0;
+    for (int c = 0; c < count; ++c) {
+        rots[c] = RotDesc{c, c, 1, 0, 0, total};
+        first[c] = total;
+        if (lut_index[c] >= 0) { rots[c].lut = lut_index[c]; ++stats.lut_rotations; }
+        if (spec_index[c] >= 0) {
+            const int nout = specs[spec_index[c]].nout;
+            rots[c].spec = spec_index[c] | ((1 << nout) - 1) << XS_WANTED_SHIFT;
+            total += nout;
+            ++stats.multi_rotations;
+            stats.multi_outputs += (uint64_t)nout;
+        } else {
+            ++total;
+        }
+    }
+    RotDesc *drots = static_cast<RotDesc *>(scratch(0, rots.size() * sizeof(RotDesc)));
+    hip_check(hipMemcpyAsync(drots, rots.data(), rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream_), "upload rots");
+    int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)(total + 1) * dp.u_stride * 4));
+    int32_t *dacc = acc_out ? static_cast<int32_t *>(scratch(7, (size_t)count * 2 * dp.N * 4)) : nullptr;
+    launch_br(key, plan_br_launch(key, count, dacc != nullptr), dpool, drots, count, u_buf, dacc, nullptr, nullptr, nullptr,
+              nullptr, dluts, dspecs);
+    hip_check(hipGetLastError(), "blind_rotate launch");
+    std::vector<int32_t> ubuf((size_t)total * dp.u_stride);
+    hip_check(hipMemcpyAsync(ubuf.data(), u_buf, ubuf.size() * 4, hipMemcpyDeviceToHost, stream_), "download u");
+    if (acc_out) hip_check(hipMemcpyAsync(acc_out, dacc, (size_t)count * 2 * dp.N * 4, hipMemcpyDeviceToHost, stream_), "download acc");
+    sync_stream("bootstrap_multi_woks");
+    const size_t uw = (size_t)dp.k * dp.N + 1;
+    for (int c = 0; c < count; ++c) {
+        const int nout = spec_index[c] >= 0 ? specs[spec_index[c]].nout : 1;
+        for (int m = 0; m < nout; ++m)
+            std::memcpy(u_out + ((size_t)c * XS_MAX_OUT + m) * uw, &ubuf[(size_t)(first[c] + m) * dp.u_stride], uw * 4);
+    }
     stats.blind_rotates += (uint64_t)count;
 }
 

@@ -86,7 +86,9 @@ struct LevelPlan {
     int levels = 0;
     std::vector<int32_t> rot_off, ks_off;   // size levels + 1; gates of level L (1-based): index L - 1
     std::vector<int32_t> not_off;           // size levels + 2; NOTs riding on level L (0 = inputs): index L
-    int32_t max_rots = 0;                   // widest level (sizes the extract buffer)
+    int32_t max_rots = 0;                   // widest level, in rotations
+    int32_t max_extracts = 0;               // the most extracted samples of a level (sizes the extract buffer): max_rots,
+                                            // or more with multi-output rotations
     // several cloud keys of one parameter set (recorder "batch_keys"; nkeys > 1 only): the key index of every rotation,
     // and the descriptors of level L (1-based) under key k at [rot_koff / ks_koff][(L - 1) nkeys + k, ... + 1)
     int nkeys = 1;
@@ -141,10 +143,23 @@ public:
     int32_t lut_add(const Torus32 *words, int n_ring);
     void lut_free(int32_t index);
     size_t lut_capacity() const { return lut_cap_; }
+    // The table of extract specs (tfhe_hip_new_lut_multi), managed like the table of test polynomials: one device array of
+    // ExtractSpec that doubles on demand, entries reused after spec_free; RotDesc::spec indexes it.  The spec has passed
+    // extract_spec_error for its ring.
+    int32_t spec_add(const ExtractSpec &xs);
+    void spec_free(int32_t index);
+    size_t spec_capacity() const { return spec_cap_; }
     // raw test paths.  lut_index / polys (both or neither): combination c starts from test polynomial lut_index[c] of
     // polys[npolys][N] (uploaded for this call only; an index below 0: the constant test vector)
     void run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, Torus32 *u_out, Torus32 *acc_out,
                             const int32_t *lut_index = nullptr, const Torus32 *polys = nullptr, int npolys = 0);
+    // the same with extract specs: combination c leaves through specs[spec_index[c]] (uploaded for this call only, every
+    // output wanted; an index below 0: the extract at index 0).  The device writes the outputs of all combinations back
+    // to back (u_index = outputs before it); u_out[count][XS_MAX_OUT][kN+1] receives output m of combination c at
+    // [c][m], the rest is left as it was
+    void run_bootstrap_multi_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, const int32_t *lut_index,
+                                  const Torus32 *polys, int npolys, const int32_t *spec_index, const ExtractSpec *specs,
+                                  int nspecs, Torus32 *u_out, Torus32 *acc_out);
     void run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out);
     void run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const Torus32 *tp, Torus32 *res, int count);
 
@@ -166,7 +181,8 @@ public:
     // luts: the test-polynomial table the descriptors' lut indices refer to; null = the engine's own
     void launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int32_t *pool, const RotDesc *rots, int count,
                    int32_t *u_buf, int32_t *acc_dbg, hipStream_t stream = nullptr, const DevKey *mk_keys = nullptr,
-                   const int32_t *mk_rot_keys = nullptr, hipEvent_t *mid = nullptr, const int32_t *luts = nullptr);
+                   const int32_t *mk_rot_keys = nullptr, hipEvent_t *mid = nullptr, const int32_t *luts = nullptr,
+                   const ExtractSpec *specs = nullptr);     // specs: likewise for the descriptors' extract specs
     // diagnostic (tools/wg_times.py): ONE 4-wave blind-rotate launch of `width` random gates whose workgroups stamp s_memtime
     // and s_memrealtime at start and end into wg_times[4 * width]; returns that launch's event time in ms (< 0: no stamps)
     double run_wg_times(const DeviceKeyImage *key, int width, unsigned long long *wg_times);
@@ -202,6 +218,10 @@ private:
     int32_t *lut_dev_ = nullptr;                        // [lut_cap_][LUT_STRIDE]
     size_t lut_cap_ = 0, lut_used_ = 0;                 // entries allocated / ever handed out
     std::vector<int32_t> lut_free_;
+    ExtractSpec *spec_dev_ = nullptr;                   // [spec_cap_]
+    size_t spec_cap_ = 0, spec_used_ = 0;
+    std::vector<int32_t> spec_free_;
+    std::vector<int32_t> spec_nout_;                    // outputs of every entry (execute() checks the extract buffer with it)
     std::vector<SlotPool *> pools_;
     std::vector<void *> scratch_ptr_;
     std::vector<size_t> scratch_size_;

@@ -337,16 +337,54 @@ __device__ __forceinline__ void forward_poly(const DevParams &p, const DevKey &k
     }
 }
 
-// sample extract at index 0 (tfhe tLweExtractLweSampleIndex) + optional raw accumulator dump
+// The outputs of an extract spec (tfhe_hip_lut_bootstrap_multi; kernels.hpp ExtractSpec): output m is
+// (0, out_c0[m]) + sum_t weight[m][t] Extract_{index[m][t]}(ACC), where Extract_e has b = B[e] and a_i = the negacyclic
+// extension of A read at (e - i) mod 2N: A[e - i] for i <= e, -A[N + e - i] above.  Everything read from the spec is
+// workgroup-uniform (scalar loads); per output and word a thread makes one LDS read and one multiply-add per tap.
+// Bounds: nout <= 4, ntaps <= 8 and 0 <= index < N are checked on the host before a spec reaches a table
+// (extract_spec_error), and the host sizes u_buf for u_index + nout samples.
+template <int LOGN, int THREADS, typename AccT>
+__device__ __forceinline__ void extract_outputs(const DevParams &p, const RotDesc &rd, const AccT &acc,
+                                                int32_t *__restrict__ u_buf, int tid) {
+    constexpr int N = 1 << LOGN;
+    const ExtractSpec &xs = p.specs[rd.spec & XS_ENTRY_MASK];
+    const int wanted = rd.spec >> XS_WANTED_SHIFT, nout = xs.nout;
+    for (int m = 0; m < nout; ++m) {
+        if (!((wanted >> m) & 1)) continue;
+        int32_t *u = u_buf + (size_t)(rd.u_index + m) * p.u_stride;
+        const int nt = xs.ntaps[m];
+        for (int i = tid; i < N; i += THREADS) {
+            uint32_t sum = 0;
+            for (int t = 0; t < nt; ++t) {
+                const int d = xs.index[m][t] - i;                       // in (-N, N)
+                const uint32_t a = acc.get(0, d & (N - 1));
+                sum += (uint32_t)xs.weight[m][t] * (d < 0 ? 0u - a : a);
+            }
+            u[i] = (int32_t)sum;
+        }
+        if (tid == 0) {
+            uint32_t b = (uint32_t)xs.out_c0[m];
+            for (int t = 0; t < nt; ++t) b += (uint32_t)xs.weight[m][t] * acc.get(1, xs.index[m][t]);
+            u[N] = (int32_t)b;
+        }
+    }
+}
+
+// sample extract at index 0 (tfhe tLweExtractLweSampleIndex) + optional raw accumulator dump.  A rotation that names an
+// extract spec (a workgroup-uniform test on a descriptor word) writes that spec's outputs instead.
 template <int LOGN, int THREADS, typename AccT>
 __device__ __forceinline__ void extract_sample(const DevParams &p, const RotDesc &rd,
                                                const AccT &acc,
                                                int32_t *__restrict__ u_buf, int32_t *__restrict__ acc_dbg, int tid) {
     constexpr int N = 1 << LOGN;
-    int32_t *u = u_buf + (size_t)rd.u_index * p.u_stride;
-    for (int j = tid; j < N; j += THREADS)
-        u[j] = (int32_t)(j == 0 ? acc.get(0, 0) : 0u - acc.get(0, N - j));
-    if (tid == 0) u[N] = (int32_t)acc.get(1, 0);
+    if (rd.spec >= 0) {
+        extract_outputs<LOGN, THREADS>(p, rd, acc, u_buf, tid);
+    } else {
+        int32_t *u = u_buf + (size_t)rd.u_index * p.u_stride;
+        for (int j = tid; j < N; j += THREADS)
+            u[j] = (int32_t)(j == 0 ? acc.get(0, 0) : 0u - acc.get(0, N - j));
+        if (tid == 0) u[N] = (int32_t)acc.get(1, 0);
+    }
     if (acc_dbg) {
         int32_t *d = acc_dbg + (size_t)blockIdx.x * 2 * N;
         for (int j = tid; j < 2 * N; j += THREADS) d[j] = (int32_t)acc.get(j >> LOGN, j & (N - 1));

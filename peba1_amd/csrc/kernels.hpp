@@ -5,6 +5,8 @@
 
 namespace tfhe_hip {
 
+struct ExtractSpec;
+
 // Parameters of one key as the kernels see them.
 struct DevParams {
     int32_t n, N, k, l, Bgbit, ks_t, ks_basebit;
@@ -23,10 +25,44 @@ struct DevParams {
                                     // s_memrealtime (100 MHz) at start and end; or null
     const int32_t *luts;            // table of caller-supplied test polynomials, LUT_STRIDE words apiece (RotDesc::lut indexes
                                     // it); null when no rotation of the launch names one
+    const ExtractSpec *specs;       // table of extract specs (RotDesc::spec indexes it); null when no rotation of the launch
+                                    // names one
 };
 
 // words between two test polynomials of a LUT table: the largest ring, so that one table serves every parameter set
 constexpr int LUT_STRIDE = 2048;
+
+// What leaves one blind rotation when more than coefficient 0 is wanted (tfhe_hip_lut_bootstrap_multi): output m is
+//     (0, out_c0[m]) + sum_{t < ntaps[m]} weight[m][t] * Extract_{index[m][t]}(ACC)          (include/tfhe_hip.h)
+// Plain words, the same on host and device; the limits are checked before a spec reaches a table (extract_spec_error).
+constexpr int XS_MAX_OUT = 4, XS_MAX_TAPS = 8, XS_MAX_WEIGHT = 8;
+struct ExtractSpec {
+    int32_t nout;
+    int32_t ntaps[XS_MAX_OUT];
+    int32_t out_c0[XS_MAX_OUT];
+    int32_t index[XS_MAX_OUT][XS_MAX_TAPS];
+    int32_t weight[XS_MAX_OUT][XS_MAX_TAPS];
+};
+constexpr int XS_WORDS = sizeof(ExtractSpec) / sizeof(int32_t);
+// RotDesc::spec, when >= 0: the table entry in the low bits, above them the set of outputs that are written (bit m =
+// output m; an output nobody reads -- a null result, a dead one -- is neither extracted nor key-switched)
+constexpr int XS_WANTED_SHIFT = 24;
+constexpr int32_t XS_ENTRY_MASK = (1 << XS_WANTED_SHIFT) - 1;
+// null if `xs` is within the limits for ring size N, else what is wrong with it
+inline const char *extract_spec_error(const ExtractSpec &xs, int N) {
+    if (xs.nout < 1 || xs.nout > XS_MAX_OUT) return "nout must be 1..4";
+    for (int m = 0; m < xs.nout; ++m) {
+        if (xs.ntaps[m] < 1 || xs.ntaps[m] > XS_MAX_TAPS) return "an output takes 1..8 taps";
+        for (int t = 0; t < xs.ntaps[m]; ++t) {
+            if (xs.index[m][t] < 0 || xs.index[m][t] >= N) return "a tap index outside 0..N-1";
+            if (xs.weight[m][t] == 0 || xs.weight[m][t] > XS_MAX_WEIGHT || xs.weight[m][t] < -XS_MAX_WEIGHT)
+                return "a tap weight that is zero or beyond +-8";
+            for (int s = 0; s < t; ++s)
+                if (xs.index[m][s] == xs.index[m][t]) return "two taps of one output at the same index";
+        }
+    }
+    return nullptr;
+}
 
 // Device-resident evaluation key.
 struct DevKey {
@@ -43,6 +79,9 @@ struct DevKey {
 // the three-input gates of tfhe_hip_gate3 set it.  The kernels read slot_c's words only when it is >= 0.
 // lut < 0: the accumulator starts from the constant test vector mu (1 + X + ... + X^(N-1)) of every gate; lut >= 0
 // (tfhe_hip_lut_bootstrap): from test polynomial `lut` of DevParams::luts, read only then.
+// spec < 0: the sample extract at index 0 into u_buf[u_index]; spec >= 0 (tfhe_hip_lut_bootstrap_multi): the outputs of
+// extract spec `spec & XS_ENTRY_MASK` of DevParams::specs, output m into u_buf[u_index + m] if bit m of
+// spec >> XS_WANTED_SHIFT is set.  Read after the step loop only.
 struct RotDesc {
     int32_t slot_a, slot_b;
     int32_t sa, sb;
@@ -51,6 +90,7 @@ struct RotDesc {
     int32_t slot_c = -1;
     int32_t sc = 0;
     int32_t lut = -1;
+    int32_t spec = -1;
 };
 
 // One key switch: (u_buf[u0] (+ u_buf[u1]) + (0, add_b)) -> pool[dst_slot].

@@ -52,6 +52,9 @@ struct Recorder {
     bool reuse_gates = true;
     std::unordered_map<OpKey, int32_t, OpKeyHash> index;   // key -> result slot (reuse_gates only)
     std::unordered_map<int32_t, int32_t> not_origin;       // pending NOT output slot -> its operand slot
+    // pending multi-output ops (OP_LUTM) by OpKey -> position in `ops` (reuse_gates only): an equal op recorded again
+    // shares output by output and WIDENS the pending op by the outputs it did not have.  Rebuilt when ops are compacted
+    std::unordered_map<OpKey, int32_t, OpKeyHash> index_multi;
     // Dead-gate elimination at flush: an op whose destination slot is held by nothing but the op's own pending reference
     // -- every handle that pointed at it was re-pointed or freed, no live op reads it -- can never be observed, so it is
     // dropped (and with it, transitively, what only it read).  The reference's ripple adders compute a carry out of their
@@ -82,6 +85,7 @@ Recorder &rec() {
 void release_refs(SlotPool *pool, const PendingOp &op) {    // the pending references an op holds
     for (const int32_t s : {op.dst, op.a, op.b, op.c})
         if (s >= 0) pool->release(s);
+    if (op.kind == OP_LUTM) for_each_dst(op, [&](int32_t d) { pool->release(d); });
 }
 
 // "Same parameter set" for a multi-key flush: every field that evaluation reads, by VALUE (two separately allocated sets
@@ -183,7 +187,23 @@ void eliminate_dead_ops() {
     size_t dead = 0;
     std::vector<uint8_t> is_dead(r.ops.size(), 0);
     for (size_t i = r.ops.size(); i-- > 0;) {
-        const PendingOp &op = r.ops[i];
+        PendingOp &op = r.ops[i];
+        if (op.kind == OP_LUTM) {
+            // per output: a dead one loses its destination (no extracted sample, no key switch); the op dies with its last
+            for (int m = 0; m < op.nout; ++m) {
+                const int32_t d = op.dsts[m];
+                if (d < 0 || pool->refs(d) != 1) continue;
+                pool->level[d] = 0;
+                pool->pending[d] = 0;
+                pool->release(d);
+                op.dsts[m] = -1;
+            }
+            if (op_wanted(op)) continue;
+            release_refs(pool, op);                     // (the operands: no destination is left)
+            is_dead[i] = 1;
+            ++dead;
+            continue;
+        }
         if (pool->refs(op.dst) != 1) continue;          // a handle or a live operation still holds the result
         auto it = r.index.find(op_key(op));
         if (it != r.index.end() && it->second == op.dst) r.index.erase(it);
@@ -201,6 +221,10 @@ void eliminate_dead_ops() {
         if (!is_dead[i]) { depth = std::max(depth, r.ops[i].level); r.ops[w++] = r.ops[i]; }
     r.ops.resize(w);
     r.max_level = depth;
+    r.index_multi.clear();
+    if (r.reuse_gates)
+        for (size_t i = 0; i < r.ops.size(); ++i)
+            if (r.ops[i].kind == OP_LUTM) r.index_multi.emplace(op_key(r.ops[i]), (int32_t)i);
     Engine::get().stats.dead_gates += dead;
 }
 
@@ -382,6 +406,83 @@ void record_lut_locked(int32_t lut, LweSample *result, int nin, const LweSample 
     record_op(OP_LUT, result, pool, slot[0], slot[1], slot[2], &op);
 }
 
+// Multi-output programmable bootstrap (tfhe_hip_lut_bootstrap_multi): ONE op with up to four destinations -- the
+// outputs of extract spec `spec` (nout of them) that the caller wants (result[m] non-null), each renamed to a fresh slot
+// like a gate's result; all become available at the op's level.  "reuse_gates": a pending op equal in spec, LUT,
+// operands, coefficients, c0 and key serves this one output by output, and is widened by the outputs it lacks.
+void record_lutm_locked(int32_t lut, int32_t spec, int nout, LweSample *const *result, int nin, const LweSample *const *in,
+                        const int32_t *coef, int32_t c0, const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    begin_op(bk);
+    SlotPool *pool = r.pool;
+    for (int m = 0; m < nout; ++m)
+        if (result[m]) bind_pool(result[m], pool);      // refuse a foreign / mismatched result before anything changes
+    int32_t slot[3] = {-1, -1, -1};
+    for (int i = 0; i < nin; ++i) slot[i] = ensure_slot(in[i], pool);
+    PendingOp op{};
+    op.kind = OP_LUTM; op.dst = -1; op.a = slot[0]; op.b = slot[1]; op.c = slot[2]; op.key = r.cur_key;
+    op.lut = lut; op.spec = spec; op.nout = nout;
+    op.sa = coef[0]; op.sb = nin > 1 ? coef[1] : 0; op.sc = nin > 2 ? coef[2] : 0;
+    op.c0 = c0;
+    // the destinations first: a dry pool runs the pending ops (alloc_slot), and what is looked up below must survive that
+    int32_t fresh[4] = {-1, -1, -1, -1};
+    try {
+        for (int m = 0; m < nout; ++m)
+            if (result[m]) fresh[m] = alloc_slot(pool);
+    } catch (...) {
+        for (const int32_t d : fresh) if (d >= 0) pool->release(d);
+        throw;
+    }
+    const OpKey key = op_key(op);
+    auto hit = r.reuse_gates ? r.index_multi.find(key) : r.index_multi.end();
+    if (hit != r.index_multi.end()) {
+        PendingOp &have = r.ops[(size_t)hit->second];
+        ++Engine::get().stats.reused_gates;
+        for (int m = 0; m < nout; ++m) {
+            if (!result[m]) continue;
+            if (have.dsts[m] >= 0) {                    // shared: the fresh slot goes back
+                pool->release(fresh[m]);
+                pool->retain(have.dsts[m]);
+            } else {                                    // widened: the pending op gains this output
+                have.dsts[m] = fresh[m];
+                pool->level[fresh[m]] = have.level;
+                pool->pending[fresh[m]] = 1;
+                pool->retain(fresh[m]);
+            }
+            repoint(result[m], pool, have.dsts[m]);
+        }
+    } else {
+        int32_t level = 0;
+        for (const int32_t s : slot)
+            if (s >= 0) { level = std::max(level, pool->level[s]); pool->retain(s); }
+        op.level = ++level;
+        for (int m = 0; m < nout; ++m) {
+            if (!result[m]) continue;
+            op.dsts[m] = fresh[m];
+            pool->level[fresh[m]] = level;
+            pool->pending[fresh[m]] = 1;
+            pool->retain(fresh[m]);
+        }
+        r.ops.push_back(op);
+        if (r.reuse_gates) r.index_multi.emplace(key, (int32_t)r.ops.size() - 1);
+        r.max_level = std::max(r.max_level, level);
+        for (int m = 0; m < nout; ++m)
+            if (result[m]) repoint(result[m], pool, fresh[m]);
+    }
+    if (!r.deferred) {
+        flush_locked();
+        for (int m = 0; m < nout; ++m)
+            if (result[m]) sync_sample_locked(result[m]);
+    }
+}
+
+void forget_lutm_locked(int32_t lut, int32_t spec) {
+    Recorder &r = rec();
+    auto names = [lut, spec](const PendingOp &op) { return op.kind == OP_LUTM && (op.spec == spec || op.lut == lut); };
+    if (std::any_of(r.ops.begin(), r.ops.end(), names)) flush_locked();
+    else if (std::any_of(r.flight_ops.begin(), r.flight_ops.end(), names)) finish_flight_locked();
+}
+
 void forget_lut_locked(int32_t lut) {
     Recorder &r = rec();
     auto names = [lut](const PendingOp &op) { return op.kind == OP_LUT && op.lut == lut; };
@@ -458,13 +559,16 @@ int flush_locked(bool wait) {
     finish_flight_locked();
     Engine::get().execute(images, pool, std::move(plan), wait);    // throws before anything runs, or runs it all
     for (const PendingOp &op : r.ops) {
-        pool->level[op.dst] = 0;          // a later recording reads these slots as inputs: the stream orders it behind
-        pool->pending[op.dst] = 0;
+        for_each_dst(op, [&](int32_t d) {
+            pool->level[d] = 0;           // a later recording reads these slots as inputs: the stream orders it behind
+            pool->pending[d] = 0;
+        });
         if (wait) release_refs(pool, op);
     }
     if (!wait) { r.flight_ops.swap(r.ops); r.flight_pool = pool; r.flight_keys = std::move(used); }
     r.ops.clear();
     r.index.clear();
+    r.index_multi.clear();
     r.not_origin.clear();
     r.max_level = 0;
     return levels;

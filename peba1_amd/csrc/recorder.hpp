@@ -44,6 +44,11 @@ void record_gate3_locked(int gate, int negate_mask, LweSample *result, const Lwe
 // test polynomial `lut` of the engine's table and key-switched
 void record_lut_locked(int32_t lut, LweSample *result, int nin, const LweSample *const *in, const int32_t *coef, int32_t c0,
                        const TFheGateBootstrappingCloudKeySet *bk);
+// the same with several destinations: result[m] (null: not wanted; at least one is, and no two are the same sample --
+// checked by the caller) = key switch of output m of extract spec `spec` (nout outputs) of the engine's table
+void record_lutm_locked(int32_t lut, int32_t spec, int nout, LweSample *const *result, int nin, const LweSample *const *in,
+                        const int32_t *coef, int32_t c0, const TFheGateBootstrappingCloudKeySet *bk);
+void forget_lutm_locked(int32_t lut, int32_t spec);   // likewise for a multi-output LUT about to be deleted
 void forget_lut_locked(int32_t lut);   // a test polynomial about to be deleted: run the recording if an op in it names it
 void record_constant_locked(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk);
 void record_copy_locked(LweSample *result, const LweSample *a, const TFheGateBootstrappingCloudKeySet *bk);

@@ -28,10 +28,10 @@ int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool bala
     // producer of each pending slot (destinations are unique: SSA; slot ids are pool indices, so a flat
     // table replaces the hash map that used to cost a third of a match's scheduling time)
     int32_t max_slot = -1;
-    for (int i = 0; i < n; ++i) max_slot = std::max(max_slot, ops[i].dst);
+    for (int i = 0; i < n; ++i) for_each_dst(ops[i], [&](int32_t d) { max_slot = std::max(max_slot, d); });
     std::vector<int32_t> producer((size_t)max_slot + 1, -1);
     for (int i = 0; i < n; ++i)
-        if (producer[ops[i].dst] < 0) producer[ops[i].dst] = i;       // (first writer, as emplace kept it)
+        for_each_dst(ops[i], [&](int32_t d) { if (producer[d] < 0) producer[d] = i; });   // (first writer, as emplace kept it)
 
     // predecessor lists (<= 3 each) and successor lists in CSR form
     std::vector<int32_t> pred(3 * (size_t)n, -1), npred(n, 0), succ_off(n + 1, 0);
@@ -153,22 +153,27 @@ LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<
     // Several keys: gates of level L under key k in sub-group (L - 1) nkeys + k, so that a level's descriptors are
     // contiguous per key (rot_koff / ks_koff); with one key the sub-groups are the groups.
     const size_t groups = (size_t)levels * nkeys;
-    std::vector<int32_t> roff(groups + 1, 0), koff(groups + 1, 0);
+    // uoff: samples of the level's extract buffer.  One per rotation, so that u_index is the rotation's place in its
+    // level -- except behind a multi-output op, which takes one sample per output of its spec
+    std::vector<int32_t> roff(groups + 1, 0), koff(groups + 1, 0), uoff(groups + 1, 0);
     plan.not_off.assign((size_t)levels + 2, 0);
     for (size_t i = 0; i < ops.size(); ++i) {
         if (ops[i].kind == OP_NOT) { ++plan.not_off[(size_t)lvl[i] + 1]; continue; }
         const size_t sg = (size_t)(lvl[i] - 1) * nkeys + ops[i].key;
         roff[sg + 1] += op_rotations(ops[i]);
-        ++koff[sg + 1];
+        koff[sg + 1] += op_keyswitches(ops[i]);
+        uoff[sg + 1] += op_extracts(ops[i]);
     }
-    for (size_t sg = 0; sg < groups; ++sg) { roff[sg + 1] += roff[sg]; koff[sg + 1] += koff[sg]; }
+    for (size_t sg = 0; sg < groups; ++sg) { roff[sg + 1] += roff[sg]; koff[sg + 1] += koff[sg]; uoff[sg + 1] += uoff[sg]; }
     plan.rot_off.assign((size_t)levels + 1, 0);
     plan.ks_off.assign((size_t)levels + 1, 0);
     plan.max_rots = 0;
+    plan.max_extracts = 0;
     for (size_t g = 0; g <= (size_t)levels; ++g) {
         plan.rot_off[g] = roff[g * nkeys];
         plan.ks_off[g] = koff[g * nkeys];
         if (g > 0) plan.max_rots = std::max(plan.max_rots, plan.rot_off[g] - plan.rot_off[g - 1]);
+        if (g > 0) plan.max_extracts = std::max(plan.max_extracts, uoff[g * nkeys] - uoff[(g - 1) * nkeys]);
     }
     for (size_t g = 0; g <= (size_t)levels; ++g) plan.not_off[g + 1] += plan.not_off[g];
     plan.rots.resize(plan.rot_off.back());
@@ -177,6 +182,7 @@ LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<
     if (nkeys > 1) plan.rot_key.resize(plan.rots.size());
     std::vector<int32_t> rpos(roff.begin(), roff.end() - 1);   // cursor per sub-group
     std::vector<int32_t> kpos(koff.begin(), koff.end() - 1);
+    std::vector<int32_t> upos(uoff.begin(), uoff.end() - 1);
     std::vector<int32_t> npos(plan.not_off.begin(), plan.not_off.end() - 1);
     const int32_t mu = 1 << 29;
     for (size_t i = 0; i < ops.size(); ++i) {
@@ -188,30 +194,44 @@ LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<
         const size_t g = (size_t)(lvl[i] - 1), sg = g * nkeys + op.key;
         const int32_t base = plan.rot_off[g];
         const int32_t r0 = rpos[sg];
+        if (op.kind == OP_LUTM) {
+            // the prelude and test polynomial of an OP_LUT; output m of spec op.spec goes to sample u0 + m of the level's
+            // extract buffer and, if somebody wants it, through a key switch of its own
+            const int32_t i0 = rpos[sg]++, u0 = upos[sg] - uoff[g * nkeys];
+            plan.rots[i0] = RotDesc{op.a, op.b >= 0 ? op.b : op.a, op.sa, op.b >= 0 ? op.sb : 0, op.c0, u0,
+                                    op.c, op.c >= 0 ? op.sc : 0, op.lut, op.spec | op_wanted(op) << XS_WANTED_SHIFT};
+            for (int m = 0; m < op.nout; ++m)
+                if (op.dsts[m] >= 0) plan.kss[kpos[sg]++] = KsDesc{u0 + m, -1, 0, op.dsts[m]};
+            upos[sg] += op.nout;
+            if (nkeys > 1) plan.rot_key[i0] = op.key;
+            continue;
+        }
+        const int32_t ub = upos[sg] - uoff[g * nkeys] - (r0 - base);    // 0 unless a multi-output op stands before
+        upos[sg] += op_rotations(op);
         if (op.kind == OP_MUX) {
             // tfhe bootsMUX: u1 = BR(-1/8 + a + b), u2 = BR(-1/8 - a + c), KS(u1 + u2 + 1/8)
             const int32_t i0 = rpos[sg]++, i1 = rpos[sg]++;
-            plan.rots[i0] = RotDesc{op.a, op.b, 1, 1, -(mu), i0 - base};
-            plan.rots[i1] = RotDesc{op.a, op.c, -1, 1, -(mu), i1 - base};
-            plan.kss[kpos[sg]++] = KsDesc{i0 - base, i1 - base, mu, op.dst};
+            plan.rots[i0] = RotDesc{op.a, op.b, 1, 1, -(mu), i0 - base + ub};
+            plan.rots[i1] = RotDesc{op.a, op.c, -1, 1, -(mu), i1 - base + ub};
+            plan.kss[kpos[sg]++] = KsDesc{i0 - base + ub, i1 - base + ub, mu, op.dst};
         } else if (op.kind == OP_LUT) {
             // t = (0, c0) + sa A (+ sb B) (+ sc C) from test polynomial op.lut: one rotation, one key switch.  The
             // kernels read slot_b's words whatever sb is, so a one-operand op names A twice with sb = 0
             const int32_t i0 = rpos[sg]++;
-            plan.rots[i0] = RotDesc{op.a, op.b >= 0 ? op.b : op.a, op.sa, op.b >= 0 ? op.sb : 0, op.c0, i0 - base,
+            plan.rots[i0] = RotDesc{op.a, op.b >= 0 ? op.b : op.a, op.sa, op.b >= 0 ? op.sb : 0, op.c0, i0 - base + ub,
                                     op.c, op.c >= 0 ? op.sc : 0, op.lut};
-            plan.kss[kpos[sg]++] = KsDesc{i0 - base, -1, 0, op.dst};
+            plan.kss[kpos[sg]++] = KsDesc{i0 - base + ub, -1, 0, op.dst};
         } else if (op_is_gate3(op.kind)) {
             // t = sa A + sb B + sc C, c0 = 0: one rotation, one key switch
             const int32_t i0 = rpos[sg]++;
-            plan.rots[i0] = RotDesc{op.a, op.b, gate3_coef(op.kind, 0), gate3_coef(op.kind, 1), 0, i0 - base,
+            plan.rots[i0] = RotDesc{op.a, op.b, gate3_coef(op.kind, 0), gate3_coef(op.kind, 1), 0, i0 - base + ub,
                                     op.c, gate3_coef(op.kind, 2)};
-            plan.kss[kpos[sg]++] = KsDesc{i0 - base, -1, 0, op.dst};
+            plan.kss[kpos[sg]++] = KsDesc{i0 - base + ub, -1, 0, op.dst};
         } else {
             const GateLin &gl = GATE_LIN[op.kind];
             const int32_t i0 = rpos[sg]++;
-            plan.rots[i0] = RotDesc{op.a, op.b, gl.sa, gl.sb, gl.c8 * mu, i0 - base};
-            plan.kss[kpos[sg]++] = KsDesc{i0 - base, -1, 0, op.dst};
+            plan.rots[i0] = RotDesc{op.a, op.b, gl.sa, gl.sb, gl.c8 * mu, i0 - base + ub};
+            plan.kss[kpos[sg]++] = KsDesc{i0 - base + ub, -1, 0, op.dst};
         }
         for (int32_t r = r0; r < rpos[sg] && nkeys > 1; ++r) plan.rot_key[r] = op.key;
     }

@@ -26,6 +26,12 @@ struct PendingOp {
     // t = (0, c0) + sa A + sb B + sc C; the coefficient of an absent operand is 0
     int32_t lut = -1;
     int32_t sa = 0, sb = 0, sc = 0, c0 = 0;
+    // OP_LUTM only (tfhe_hip_lut_bootstrap_multi): lut and the prelude as for OP_LUT; the extract spec (index in the
+    // engine's spec table), its number of outputs, and the destination slot of every output -- -1 for one that nobody
+    // wants (a null result, or dead at the flush).  `dst` is unused (-1): for_each_dst visits the destinations of any op
+    int32_t spec = -1;
+    int32_t nout = 0;
+    int32_t dsts[4] = {-1, -1, -1, -1};
 };
 constexpr uint8_t OP_MUX = 16, OP_NOT = 17;
 // programmable bootstrap (not in upstream's gate API): one rotation from a caller-supplied test polynomial, one key switch
@@ -36,8 +42,27 @@ constexpr uint8_t OP_GATE3 = 32, OP_GATE3_END = OP_GATE3 + 3 * 8;
 inline bool op_is_gate3(int kind) { return kind >= OP_GATE3 && kind < OP_GATE3_END; }
 inline bool op_kind_valid(int kind) { return (kind >= 0 && kind < 10) || kind == OP_MUX || kind == OP_NOT || op_is_gate3(kind); }
 inline bool op_kind_valid_lut(int kind) { return op_kind_valid(kind) || kind == OP_LUT; }
+// multi-output programmable bootstrap: one rotation, then one extracted sample and one key switch per WANTED output
+constexpr uint8_t OP_LUTM = 65;
 
 inline int op_rotations(const PendingOp &op) { return op.kind == OP_NOT ? 0 : (op.kind == OP_MUX ? 2 : 1); }
+// samples of the level's extract buffer an op takes (a multi-output op: one per output of its spec, wanted or not, so
+// that output m sits at u_index + m) and key switches it needs
+inline int op_extracts(const PendingOp &op) { return op.kind == OP_LUTM ? op.nout : op_rotations(op); }
+inline int op_wanted(const PendingOp &op) {
+    int w = 0;
+    for (int m = 0; m < op.nout; ++m) w |= (op.dsts[m] >= 0) << m;
+    return w;
+}
+inline int op_keyswitches(const PendingOp &op) {
+    return op.kind == OP_NOT ? 0 : op.kind == OP_LUTM ? __builtin_popcount((unsigned)op_wanted(op)) : 1;
+}
+template <class F>
+inline void for_each_dst(const PendingOp &op, F &&f) {
+    if (op.kind != OP_LUTM) return (void)f(op.dst);
+    for (int m = 0; m < op.nout; ++m)
+        if (op.dsts[m] >= 0) f(op.dsts[m]);
+}
 
 // prelude constants of the two-input gates: (c0 in eighths, sa, sb), tfhe boot-gates.cpp
 struct GateLin { int32_t c8, sa, sb; };
@@ -56,14 +81,16 @@ inline int32_t gate3_coef(int kind, int operand) {
 
 // A pending op by what it computes: kind, operand slots (-1 = absent), the cloud key it bootstraps under (index in the
 // recording's key list: the same gate of the same slots under two keys gives two different ciphertexts) and, for a LUT
-// op, the test polynomial, the coefficients and the constant.  The recorder shares the result of two pending ops exactly
-// when these are equal ("reuse_gates").
+// op, the test polynomial, the coefficients and the constant; for a multi-output one the extract spec as well (NOT the
+// set of outputs wanted: an equal op that wants another output widens the pending one).  The recorder shares the result
+// of two pending ops exactly when these are equal ("reuse_gates").
 struct OpKey {
     int32_t kind, a, b, c, key;
     int32_t lut, sa, sb, sc, c0;
+    int32_t spec = -1;
     bool operator==(const OpKey &o) const {
         return kind == o.kind && a == o.a && b == o.b && c == o.c && key == o.key && lut == o.lut && sa == o.sa &&
-               sb == o.sb && sc == o.sc && c0 == o.c0;
+               sb == o.sb && sc == o.sc && c0 == o.c0 && spec == o.spec;
     }
 };
 struct OpKeyHash {
@@ -71,8 +98,9 @@ struct OpKeyHash {
         uint64_t h = ((uint64_t)(uint32_t)k.a << 32 | (uint32_t)k.b) * 0x9E3779B97F4A7C15ull;
         h ^= ((uint64_t)(uint32_t)k.c << 8 | (uint32_t)k.kind) * 0xC2B2AE3D27D4EB4Full;
         h ^= (uint64_t)(uint32_t)k.key * 0x165667B19E3779F9ull;
-        if (k.kind == OP_LUT) {
+        if (k.kind == OP_LUT || k.kind == OP_LUTM) {
             h ^= ((uint64_t)(uint32_t)k.lut << 32 | (uint32_t)k.c0) * 0xD6E8FEB86659FD93ull;
+            h ^= (uint64_t)(uint32_t)(k.spec + 1) * 0x9FB21C651E98DF25ull;
             h ^= ((uint64_t)(uint32_t)k.sa << 40 ^ (uint64_t)(uint32_t)k.sb << 20 ^ (uint32_t)k.sc) * 0xFF51AFD7ED558CCDull;
         }
         return (size_t)(h ^ (h >> 29));
@@ -83,8 +111,8 @@ struct OpKeyHash {
 inline OpKey op_key(const PendingOp &op) {
     int32_t a = op.a, b = op.b;
     if (op.kind < OP_MUX && GATE_LIN[op.kind].sa == GATE_LIN[op.kind].sb && b < a) std::swap(a, b);
-    if (op.kind != OP_LUT) return OpKey{op.kind, a, b, op.c, op.key, -1, 0, 0, 0, 0};
-    return OpKey{op.kind, a, b, op.c, op.key, op.lut, op.sa, op.sb, op.sc, op.c0};
+    if (op.kind != OP_LUT && op.kind != OP_LUTM) return OpKey{op.kind, a, b, op.c, op.key, -1, 0, 0, 0, 0};
+    return OpKey{op.kind, a, b, op.c, op.key, op.lut, op.sa, op.sb, op.sc, op.c0, op.kind == OP_LUTM ? op.spec : -1};
 }
 
 // Fills lvl[i] with the level at which ops[i] runs (bootstrapped gates: 1..depth,

@@ -682,6 +682,170 @@ int tfhe_hip_lut_bootstrap_batch(const TfheHipLut *lut, LweSample *result, int32
     return rc;
 }
 
+// ---- multi-output programmable bootstrap: several extractions from one rotation ----
+}  // extern "C"
+
+// A test polynomial (the object's own copy of the LUT's words, with an entry of its own in the engine's table) and an
+// extract spec.  Both reach the device at first use.
+struct TfheHipLutMulti {
+    uint32_t magic;
+    TfheHipLut lut;
+    ExtractSpec spec;
+    int32_t dev_spec;
+};
+
+namespace {
+constexpr uint32_t LUTM_MAGIC = 0x4C554D7Fu;
+
+TfheHipLutMulti *make_lut_multi(const char *who, int32_t N, const Torus32 *words, const ExtractSpec &xs) {
+    if (const char *why = extract_spec_error(xs, N)) { set_error(std::string(who) + ": " + why); return nullptr; }
+    auto *mo = new TfheHipLutMulti{LUTM_MAGIC, TfheHipLut{LUT_MAGIC, N, std::vector<Torus32>(words, words + N), -1}, xs, -1};
+    return mo;
+}
+
+// the checks every multi-output bootstrap makes before anything is recorded (the LUT entry's, then the results');
+// both table entries are uploaded here at first use
+void lutm_entry(const TfheHipLutMulti *mo, int32_t nin, const void *in, const int32_t *coef,
+                const TFheGateBootstrappingCloudKeySet *bk) {
+    if (!mo || mo->magic != LUTM_MAGIC) api_fail("tfhe_hip_lut_bootstrap_multi: null or deleted multi-output LUT");
+    lut_entry(&mo->lut, nin, in, coef, bk);
+    if (mo->dev_spec < 0) const_cast<TfheHipLutMulti *>(mo)->dev_spec = Engine::get().spec_add(mo->spec);
+}
+void lutm_check_results(const TfheHipLutMulti *mo, LweSample *const *result) {
+    if (!mo || mo->magic != LUTM_MAGIC) api_fail("tfhe_hip_lut_bootstrap_multi: null or deleted multi-output LUT");
+    if (!result) api_fail("tfhe_hip_lut_bootstrap_multi: null result list");
+    bool any = false;
+    for (int m = 0; m < mo->spec.nout; ++m) {
+        any |= result[m] != nullptr;
+        for (int o = 0; o < m; ++o)
+            if (result[m] && result[m] == result[o]) api_fail("tfhe_hip_lut_bootstrap_multi: two results are the same sample");
+    }
+    if (!any) api_fail("tfhe_hip_lut_bootstrap_multi: every result is null");
+}
+}  // namespace
+
+extern "C" {
+
+TfheHipLutMulti *tfhe_hip_new_lut_multi(const TfheHipLut *lut, int32_t nout, const int32_t *ntaps, const int32_t *tap_index,
+                                        const int32_t *tap_weight, const Torus32 *out_c0) {
+    const char *who = "tfhe_hip_new_lut_multi";
+    if (!lut || lut->magic != LUT_MAGIC) { set_error(std::string(who) + ": null or deleted LUT"); return nullptr; }
+    if (!ntaps || !tap_index || !tap_weight) { set_error(std::string(who) + ": null tap list"); return nullptr; }
+    if (nout < 1 || nout > XS_MAX_OUT) { set_error(std::string(who) + ": nout must be 1..4"); return nullptr; }
+    ExtractSpec xs{};
+    xs.nout = nout;
+    size_t at = 0;
+    for (int m = 0; m < nout; ++m) {
+        if (ntaps[m] < 1 || ntaps[m] > XS_MAX_TAPS) { set_error(std::string(who) + ": an output takes 1..8 taps"); return nullptr; }
+        xs.ntaps[m] = ntaps[m];
+        xs.out_c0[m] = out_c0 ? out_c0[m] : 0;
+        for (int t = 0; t < ntaps[m]; ++t, ++at) { xs.index[m][t] = tap_index[at]; xs.weight[m][t] = tap_weight[at]; }
+    }
+    return make_lut_multi(who, lut->N, lut->words.data(), xs);
+}
+
+TfheHipLutMulti *tfhe_hip_new_lut_multi_from_tables(const TFheGateBootstrappingParameterSet *params, Torus32 step, int32_t slots,
+                                                    int32_t nout, const int32_t *levels) {
+    const char *who = "tfhe_hip_new_lut_multi_from_tables";
+    if (!params || !params->tgsw_params || !params->tgsw_params->tlwe_params) { set_error(std::string(who) + ": null parameter set"); return nullptr; }
+    const int32_t N = params->tgsw_params->tlwe_params->N;
+    if (N < 1 || N > LUT_STRIDE) { set_error(std::string(who) + ": ring size out of range"); return nullptr; }
+    if (!levels) { set_error(std::string(who) + ": null levels"); return nullptr; }
+    if (step & 1) { set_error(std::string(who) + ": step must be even (the test polynomial is the constant step/2)"); return nullptr; }
+    if (slots < 2 || N % slots != 0) { set_error(std::string(who) + ": slots must be at least 2 and divide N = " + std::to_string(N)); return nullptr; }
+    if (nout < 1 || nout > XS_MAX_OUT) { set_error(std::string(who) + ": nout must be 1..4"); return nullptr; }
+    // Coefficient j N/slots of X^-p (step/2) decrypts to +step/2 for p in a sector s <= slots-1-j and to -step/2 above:
+    // with weights L[slots-1-j] - L[slots-j] the taps sum to step L[s] - (step/2)(L[0] + L[slots-1]) (include/tfhe_hip.h)
+    ExtractSpec xs{};
+    xs.nout = nout;
+    const uint32_t half = (uint32_t)(step / 2);
+    for (int m = 0; m < nout; ++m) {
+        const int32_t *L = levels + (size_t)m * slots;
+        int nt = 0;
+        for (int j = 1; j < slots; ++j) {
+            const int64_t w = (int64_t)L[slots - 1 - j] - (int64_t)L[slots - j];
+            if (w == 0) continue;
+            if (w > XS_MAX_WEIGHT || w < -XS_MAX_WEIGHT) { set_error(std::string(who) + ": neighbouring levels differ by more than 8"); return nullptr; }
+            if (nt == XS_MAX_TAPS) { set_error(std::string(who) + ": an output would need more than 8 taps"); return nullptr; }
+            xs.index[m][nt] = j * (N / slots);
+            xs.weight[m][nt] = (int32_t)w;
+            ++nt;
+        }
+        if (nt == 0) { set_error(std::string(who) + ": an output with equal levels in every sector needs no tap (it is a constant)"); return nullptr; }
+        xs.ntaps[m] = nt;
+        xs.out_c0[m] = (int32_t)(half * ((uint32_t)L[0] + (uint32_t)L[slots - 1]));
+    }
+    const std::vector<Torus32> words((size_t)N, (Torus32)half);
+    return make_lut_multi(who, N, words.data(), xs);
+}
+
+void tfhe_hip_delete_lut_multi(TfheHipLutMulti *mo) {
+    if (!mo) return;
+    if (mo->magic != LUTM_MAGIC) { set_error("tfhe_hip_delete_lut_multi: not a multi-output LUT (or already deleted)"); return; }
+    auto g = recorder_lock();
+    if (mo->lut.dev >= 0 || mo->dev_spec >= 0) {
+        guarded([&] { forget_lutm_locked(mo->lut.dev, mo->dev_spec); });    // recorded ops that name it run first
+        if (mo->lut.dev >= 0) Engine::get().lut_free(mo->lut.dev);
+        if (mo->dev_spec >= 0) Engine::get().spec_free(mo->dev_spec);
+    }
+    mo->magic = 0;
+    mo->lut.magic = 0;
+    delete mo;
+}
+
+int32_t tfhe_hip_lut_multi_nout(const TfheHipLutMulti *mo) {
+    if (!mo || mo->magic != LUTM_MAGIC) { set_error("tfhe_hip_lut_multi_nout: null or deleted multi-output LUT"); return -1; }
+    return mo->spec.nout;
+}
+
+int32_t tfhe_hip_lut_multi_output(const TfheHipLutMulti *mo, int32_t m, int32_t *tap_index, int32_t *tap_weight, Torus32 *out_c0) {
+    if (!mo || mo->magic != LUTM_MAGIC) { set_error("tfhe_hip_lut_multi_output: null or deleted multi-output LUT"); return -1; }
+    if (m < 0 || m >= mo->spec.nout) { set_error("tfhe_hip_lut_multi_output: no such output"); return -1; }
+    for (int t = 0; t < mo->spec.ntaps[m]; ++t) {
+        if (tap_index) tap_index[t] = mo->spec.index[m][t];
+        if (tap_weight) tap_weight[t] = mo->spec.weight[m][t];
+    }
+    if (out_c0) *out_c0 = mo->spec.out_c0[m];
+    return mo->spec.ntaps[m];
+}
+
+const Torus32 *tfhe_hip_lut_multi_words(const TfheHipLutMulti *mo, int32_t *count) {
+    if (!mo || mo->magic != LUTM_MAGIC) { set_error("tfhe_hip_lut_multi_words: null or deleted multi-output LUT"); if (count) *count = 0; return nullptr; }
+    if (count) *count = mo->lut.N;
+    return mo->lut.words.data();
+}
+
+void tfhe_hip_lut_bootstrap_multi(const TfheHipLutMulti *mo, LweSample *const *result, int32_t nin, const LweSample *const *in,
+                                  const int32_t *coef, Torus32 c0, const TFheGateBootstrappingCloudKeySet *bk) {
+    guarded([&] {
+        auto g = recorder_lock();
+        lutm_check_results(mo, result);
+        lutm_entry(mo, nin, in, coef, bk);
+        record_lutm_locked(mo->lut.dev, mo->dev_spec, mo->spec.nout, result, nin, in, coef, c0, bk);
+    });
+}
+
+int tfhe_hip_lut_bootstrap_multi_batch(const TfheHipLutMulti *mo, LweSample *const *result, int32_t nin,
+                                       const LweSample *const *in, const int32_t *coef, Torus32 c0, int32_t count,
+                                       const TFheGateBootstrappingCloudKeySet *bk) {
+    auto g = recorder_lock();
+    const bool was = set_deferred_locked(true);
+    const int rc = guarded_rc([&] {
+        lutm_check_results(mo, result);
+        lutm_entry(mo, nin, in, coef, bk);
+        for (int32_t i = 0; i < count; ++i) {
+            const LweSample *ops[3] = {&in[0][i], nin > 1 ? &in[1][i] : nullptr, nin > 2 ? &in[2][i] : nullptr};
+            LweSample *res[XS_MAX_OUT] = {nullptr, nullptr, nullptr, nullptr};
+            for (int m = 0; m < mo->spec.nout; ++m) res[m] = result[m] ? &result[m][i] : nullptr;
+            record_lutm_locked(mo->lut.dev, mo->dev_spec, mo->spec.nout, res, nin, ops, coef, c0, bk);
+        }
+        return 0;
+    });
+    set_deferred_locked(was);
+    if (!was) flush_locked();      // ops recorded before a refused one still run
+    return rc;
+}
+
 void tfhe_hip_test_set_alloc_cap(int64_t bytes) {
     auto g = recorder_lock();
     set_alloc_cap((long long)bytes);
@@ -761,11 +925,13 @@ int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int
 }
 
 // rot_words = 6: the two-operand words of every rotation (the form older callers know); 8: slot_c and sc as well; 9: and
-// the LUT index.  ops = ops5, or records of 10 words when lut_ops (tfhe_hip_test_level_plan_lut)
+// the LUT index; 10: and the extract spec word.  ops = ops5, or records of 10 words when lut_ops
+// (tfhe_hip_test_level_plan_lut), or of 16 when rec_words = 16 (tfhe_hip_test_level_plan_multi: dead_slots as well)
 static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
                            int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
                            int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots, int rot_words, int32_t *kss4,
-                           bool lut_ops = false, int32_t reuse = 0, int32_t *shared_with = nullptr) {
+                           bool lut_ops = false, int32_t reuse = 0, int32_t *shared_with = nullptr, int rec_words = 10,
+                           const int32_t *dead_slots = nullptr, int32_t ndead = 0) {
     if (count < 0 || nkeys < 1 || nkeys > UINT16_MAX) { set_error("test_level_plan: bad count or nkeys"); return -1; }
     for (int32_t i = 0; i < count; ++i)
         if (op_keys[i] < 0 || op_keys[i] >= nkeys) { set_error("test_level_plan: key index out of range"); return -1; }
@@ -787,16 +953,50 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
         depth = 0;
         auto resolve = [&](int32_t slot) { auto it = alias.find(slot); return it == alias.end() ? slot : it->second; };
         auto level_of = [&](int32_t slot) { return slot >= 0 && (size_t)slot < slot_level.size() ? slot_level[slot] : 0; };
+        auto set_level = [&](int32_t slot, int32_t level) {
+            if ((size_t)slot >= slot_level.size()) slot_level.resize((size_t)slot + 1, 0);
+            slot_level[(size_t)slot] = level;
+        };
         for (int32_t i = 0; i < count; ++i) {
-            const int32_t *o = ops5 + 10 * (size_t)i;
-            if (!op_kind_valid_lut(o[0])) { set_error("test schedule: unknown op kind"); return -1; }
+            const int32_t *o = ops5 + (size_t)rec_words * (size_t)i;
+            const bool multi = rec_words == 16 && o[0] == OP_LUTM;
+            if (!op_kind_valid_lut(o[0]) && !multi) { set_error("test schedule: unknown op kind"); return -1; }
             PendingOp op{(uint8_t)o[0], o[1], resolve(o[2]), resolve(o[3]), resolve(o[4]), 0, (uint16_t)op_keys[i]};
-            if (op.kind == OP_LUT) { op.lut = o[5]; op.sa = o[6]; op.sb = o[7]; op.sc = o[8]; op.c0 = o[9]; }
+            if (op.kind == OP_LUT || multi) { op.lut = o[5]; op.sa = o[6]; op.sb = o[7]; op.sc = o[8]; op.c0 = o[9]; }
             if (shared_with) shared_with[i] = -1;
+            if (multi) {
+                // as record_lutm_locked records it: one op, a destination per wanted output; an equal pending op serves
+                // it output by output and is widened by the outputs it lacks
+                op.dst = -1; op.spec = o[10]; op.nout = o[11];
+                bool any = false;
+                if (op.nout < 1 || op.nout > XS_MAX_OUT) { set_error("test_level_plan_multi: nout must be 1..4"); return -1; }
+                for (int m = 0; m < op.nout; ++m) { op.dsts[m] = o[12 + m]; any |= op.dsts[m] >= 0; }
+                if (!any) { set_error("test_level_plan_multi: an op without a destination"); return -1; }
+                auto hit = reuse ? index.find(op_key(op)) : index.end();
+                if (hit != index.end()) {
+                    PendingOp &have = ops[(size_t)op_of_record[(size_t)hit->second]];
+                    for (int m = 0; m < op.nout; ++m) {
+                        if (op.dsts[m] < 0) continue;
+                        if (have.dsts[m] >= 0) alias[op.dsts[m]] = have.dsts[m];
+                        else { have.dsts[m] = op.dsts[m]; set_level(op.dsts[m], have.level); }
+                    }
+                    if (shared_with) shared_with[i] = hit->second;
+                    op_of_record[(size_t)i] = -1;
+                    continue;
+                }
+                if (reuse) index.emplace(op_key(op), i);
+                op.level = std::max(level_of(op.a), std::max(level_of(op.b), level_of(op.c))) + 1;
+                for (int m = 0; m < op.nout; ++m)
+                    if (op.dsts[m] >= 0) set_level(op.dsts[m], op.level);
+                depth = std::max(depth, op.level);
+                op_of_record[(size_t)i] = (int32_t)ops.size();
+                ops.push_back(op);
+                continue;
+            }
             if (reuse) {
                 auto hit = index.find(op_key(op));
                 if (hit != index.end()) {
-                    alias[op.dst] = ops5[10 * (size_t)hit->second + 1];
+                    alias[op.dst] = ops5[(size_t)rec_words * (size_t)hit->second + 1];
                     if (shared_with) shared_with[i] = hit->second;
                     op_of_record[(size_t)i] = -1;
                     continue;
@@ -811,14 +1011,45 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
             op_of_record[(size_t)i] = (int32_t)ops.size();
             ops.push_back(op);
         }
+        if (ndead > 0) {
+            // As the flush eliminates (recorder.cpp eliminate_dead_ops): in reverse recording order, a destination that
+            // no handle holds (dead_slots) and no surviving op reads is dropped -- a multi-output op output by output,
+            // dying with its last -- and a dropped op reads nothing
+            std::vector<uint8_t> unheld(slot_level.size(), 0), read(slot_level.size(), 0);
+            for (int32_t d = 0; d < ndead; ++d)
+                if (dead_slots[d] >= 0 && (size_t)dead_slots[d] < unheld.size()) unheld[(size_t)dead_slots[d]] = 1;
+            auto gone = [&](int32_t slot) { return unheld[(size_t)slot] && !read[(size_t)slot]; };
+            std::vector<int32_t> keep_at(ops.size(), -1);
+            std::vector<PendingOp> kept;
+            for (size_t i = ops.size(); i-- > 0;) {
+                PendingOp &op = ops[i];
+                bool alive;
+                if (op.kind == OP_LUTM) {
+                    for (int m = 0; m < op.nout; ++m)
+                        if (op.dsts[m] >= 0 && gone(op.dsts[m])) op.dsts[m] = -1;
+                    alive = op_wanted(op) != 0;
+                } else {
+                    alive = !gone(op.dst);
+                }
+                if (!alive) { keep_at[i] = -2; continue; }
+                for (const int32_t src : {op.a, op.b, op.c})
+                    if (src >= 0 && (size_t)src < read.size()) read[(size_t)src] = 1;
+            }
+            depth = 0;
+            for (size_t i = 0; i < ops.size(); ++i)
+                if (keep_at[i] != -2) { keep_at[i] = (int32_t)kept.size(); depth = std::max(depth, ops[i].level); kept.push_back(ops[i]); }
+            for (int32_t &at : op_of_record)
+                if (at >= 0) at = keep_at[(size_t)at];          // -2: eliminated
+            ops.swap(kept);
+        }
     }
     std::vector<int32_t> lvl;
     const int levels = schedule_levels(ops, depth, balance != 0, unit, lvl);
     const LevelPlan plan = build_level_plan(ops, lvl, levels, nkeys);     // exactly what flush_locked hands to execute()
     for (int32_t i = 0; i < count; ++i) {
         if (!lut_ops) { levels_out[i] = lvl[i]; continue; }
-        const int32_t at = op_of_record[(size_t)i] >= 0 ? op_of_record[(size_t)i] : op_of_record[(size_t)shared_with[i]];
-        levels_out[i] = lvl[(size_t)at];
+        const int32_t at = op_of_record[(size_t)i] != -1 ? op_of_record[(size_t)i] : op_of_record[(size_t)shared_with[i]];
+        levels_out[i] = at >= 0 ? lvl[(size_t)at] : -1;      // -1: eliminated (tfhe_hip_test_level_plan_multi's dead_slots)
     }
     sizes6[0] = plan.levels;
     sizes6[1] = (int32_t)plan.rots.size();
@@ -826,9 +1057,10 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
     sizes6[3] = (int32_t)plan.rot_koff.size();
     sizes6[4] = (int32_t)plan.ks_koff.size();
     sizes6[5] = (int32_t)plan.rot_key.size();
-    static_assert(sizeof(RotDesc) == 9 * sizeof(int32_t) && offsetof(RotDesc, slot_c) == 6 * sizeof(int32_t) &&
-                      offsetof(RotDesc, lut) == 8 * sizeof(int32_t) && sizeof(KsDesc) == 4 * sizeof(int32_t),
-                  "descriptors are plain words: the third operand behind the first six, the LUT index last");
+    static_assert(sizeof(RotDesc) == 10 * sizeof(int32_t) && offsetof(RotDesc, slot_c) == 6 * sizeof(int32_t) &&
+                      offsetof(RotDesc, lut) == 8 * sizeof(int32_t) && offsetof(RotDesc, spec) == 9 * sizeof(int32_t) &&
+                      sizeof(KsDesc) == 4 * sizeof(int32_t),
+                  "descriptors are plain words: the third operand behind the first six, then the LUT index, the extract spec last");
     auto copy = [](int32_t *dst, const void *src, size_t words) { if (words) std::memcpy(dst, src, words * sizeof(int32_t)); };
     copy(rot_off, plan.rot_off.data(), plan.rot_off.size());
     copy(ks_off, plan.ks_off.data(), plan.ks_off.size());
@@ -860,6 +1092,16 @@ int tfhe_hip_test_level_plan_lut(const int32_t *ops10, const int32_t *op_keys, i
     if (reuse && !shared_with) { set_error("test_level_plan_lut: reuse needs shared_with"); return -1; }
     return test_level_plan(ops10, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
                            rot_key, rots9, 9, kss4, true, reuse, shared_with);
+}
+
+int tfhe_hip_test_level_plan_multi(const int32_t *ops16, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                                   int32_t balance, int32_t reuse, const int32_t *dead_slots, int32_t ndead,
+                                   int32_t *levels_out, int32_t *shared_with, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
+                                   int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots10, int32_t *kss4) {
+    if (!shared_with) { set_error("test_level_plan_multi: shared_with is needed"); return -1; }
+    if (ndead < 0 || (ndead > 0 && !dead_slots)) { set_error("test_level_plan_multi: bad dead_slots"); return -1; }
+    return test_level_plan(ops16, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
+                           rot_key, rots10, 10, kss4, true, reuse, shared_with, 16, dead_slots, ndead);
 }
 
 int tfhe_hip_test_br_plan(int32_t N, int32_t l, int32_t Bgbit, const int32_t *tunings4, int32_t cu_count, int32_t count,
@@ -929,6 +1171,22 @@ int tfhe_hip_kernel_lut_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *b
     return guarded_rc([&] {
         pool_of_key(bk);
         Engine::get().run_bootstrap_woks(bk->bk->dev, lin, count, u_out, acc_out, lut_index, polys, npolys);
+        return 0;
+    });
+}
+int tfhe_hip_kernel_lut_bootstrap_multi_woks(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *lin, int32_t count,
+                                             const int32_t *lut_index, const Torus32 *polys, int32_t npolys,
+                                             const int32_t *spec_index, const int32_t *specs, int32_t nspecs, Torus32 *u_out,
+                                             Torus32 *acc_out) {
+    if (!bk || !bk->bk) { set_error("lut_bootstrap_multi_woks: null keyset"); return -1; }
+    if (!lut_index || !polys || npolys < 1) { set_error("lut_bootstrap_multi_woks: null or empty LUT table"); return -1; }
+    if (!spec_index || !specs || nspecs < 1) { set_error("lut_bootstrap_multi_woks: null or empty spec table"); return -1; }
+    static_assert(XS_WORDS == TFHE_HIP_EXTRACT_SPEC_WORDS, "the spec records of the raw entry are ExtractSpec's words");
+    auto g = recorder_lock();
+    return guarded_rc([&] {
+        pool_of_key(bk);
+        Engine::get().run_bootstrap_multi_woks(bk->bk->dev, lin, count, lut_index, polys, npolys, spec_index,
+                                               reinterpret_cast<const ExtractSpec *>(specs), nspecs, u_out, acc_out);
         return 0;
     });
 }

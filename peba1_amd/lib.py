@@ -58,7 +58,8 @@ class Stats(C.Structure):
                 ("br_wide4_launches", C.c_uint64), ("br_split_launches", C.c_uint64),
                 ("br_wave8_launches", C.c_uint64), ("br_wave2_launches", C.c_uint64),
                 ("br_tables0_launches", C.c_uint64), ("br_tables1_launches", C.c_uint64),
-                ("br_tables2_launches", C.c_uint64), ("lut_rotations", C.c_uint64)]
+                ("br_tables2_launches", C.c_uint64), ("lut_rotations", C.c_uint64),
+                ("multi_rotations", C.c_uint64), ("multi_outputs", C.c_uint64)]
 
 
 PS = C.POINTER(ParameterSet)
@@ -140,6 +141,15 @@ SIGNATURES = {
     "tfhe_hip_lut_words": (I32P, [C.c_void_p, I32P]),
     "tfhe_hip_lut_bootstrap": (None, [C.c_void_p, LS, C.c_int32, C.POINTER(LS), I32P, C.c_int32, CK]),
     "tfhe_hip_lut_bootstrap_batch": (C.c_int, [C.c_void_p, LS, C.c_int32, C.POINTER(LS), I32P, C.c_int32, C.c_int32, CK]),
+    "tfhe_hip_new_lut_multi": (C.c_void_p, [C.c_void_p, C.c_int32, I32P, I32P, I32P, I32P]),
+    "tfhe_hip_new_lut_multi_from_tables": (C.c_void_p, [PS, C.c_int32, C.c_int32, C.c_int32, I32P]),
+    "tfhe_hip_delete_lut_multi": (None, [C.c_void_p]),
+    "tfhe_hip_lut_multi_nout": (C.c_int32, [C.c_void_p]),
+    "tfhe_hip_lut_multi_output": (C.c_int32, [C.c_void_p, C.c_int32, I32P, I32P, I32P]),
+    "tfhe_hip_lut_multi_words": (I32P, [C.c_void_p, I32P]),
+    "tfhe_hip_lut_bootstrap_multi": (None, [C.c_void_p, C.POINTER(LS), C.c_int32, C.POINTER(LS), I32P, C.c_int32, CK]),
+    "tfhe_hip_lut_bootstrap_multi_batch": (C.c_int, [C.c_void_p, C.POINTER(LS), C.c_int32, C.POINTER(LS), I32P, C.c_int32,
+                                                     C.c_int32, CK]),
     "tfhe_hip_set_tuning": (C.c_int, [C.c_char_p, C.c_int64]),
     "tfhe_hip_test_form_admissible": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int]),
     "tfhe_hip_test_set_alloc_cap": (None, [C.c_int64]),
@@ -152,11 +162,15 @@ SIGNATURES = {
     "tfhe_hip_test_level_plan": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [I32P] * 9),
     "tfhe_hip_test_level_plan3": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [I32P] * 9),
     "tfhe_hip_test_level_plan_lut": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [I32P] * 10),
+    "tfhe_hip_test_level_plan_multi": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P,
+                                                 C.c_int32] + [I32P] * 10),
     "tfhe_hip_test_br_plan": (C.c_int, [C.c_int32] * 3 + [I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_ks_plan": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "tfhe_hip_kernel_negacyclic":(C.c_int, [CK, I32P, I32P, I32P, C.c_int32]),
     "tfhe_hip_kernel_bootstrap_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P]),
     "tfhe_hip_kernel_lut_bootstrap_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P, C.c_int32, I32P, I32P]),
+    "tfhe_hip_kernel_lut_bootstrap_multi_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P, C.c_int32, I32P, I32P, C.c_int32,
+                                                           I32P, I32P]),
     "tfhe_hip_kernel_keyswitch": (C.c_int, [CK, I32P, C.c_int32, I32P]),
 }
 for _g in _GATE2:
