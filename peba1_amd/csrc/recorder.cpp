@@ -5,11 +5,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <unordered_map>
 #include <utility>
 #include <vector>
 
-#include "scheduler.hpp"
+#include "op_graph.hpp"
 
 namespace tfhe_hip {
 namespace {
@@ -39,27 +38,14 @@ struct Recorder {
     // circuits fill the levels of one flush instead of running as K narrow flushes.  A key of another parameter set still
     // flushes.  Results are the same words either way.
     bool batch_keys = false;
-    std::vector<PendingOp> ops;
-    int32_t max_level = 0;
+    // the pending ops, their one index (tuning "reuse_gates": OpGraph::reuse) and the NOT-origin table (op_graph.hpp)
+    OpGraph<SlotPool> graph;
     bool balance_levels = true;   // slack-aware level filling (scheduler.hpp)
     // operations of a flush launched without waiting (tfhe_hip_flush_async): released when it is complete
     std::vector<PendingOp> flight_ops;
     SlotPool *flight_pool = nullptr;
     std::vector<const TFheGateBootstrappingCloudKeySet *> flight_keys;   // keys it runs under: not deleted before it completes
-    // Pending ops by (kind, operand slots): an op recorded again with the same operands before the flush is the same
-    // function of the same ciphertexts, so its result slot is shared instead of evaluated twice (the reference's circuits
-    // do this 12,545 times per match, mostly AND / XOR against the shared constant samples).  Results are unchanged.
-    bool reuse_gates = true;
-    std::unordered_map<OpKey, int32_t, OpKeyHash> index;   // key -> result slot (reuse_gates only)
-    std::unordered_map<int32_t, int32_t> not_origin;       // pending NOT output slot -> its operand slot
-    // pending multi-output ops (OP_LUTM) by OpKey -> position in `ops` (reuse_gates only): an equal op recorded again
-    // shares output by output and WIDENS the pending op by the outputs it did not have.  Rebuilt when ops are compacted
-    std::unordered_map<OpKey, int32_t, OpKeyHash> index_multi;
-    // Dead-gate elimination at flush: an op whose destination slot is held by nothing but the op's own pending reference
-    // -- every handle that pointed at it was re-pointed or freed, no live op reads it -- can never be observed, so it is
-    // dropped (and with it, transitively, what only it read).  The reference's ripple adders compute a carry out of their
-    // last bit and drop it (Math.cpp:60-64 into a freed temporary): 5 of the 7 gates of that bit, ~55 gates per slot.
-    bool eliminate_dead = true;
+    bool eliminate_dead = true;   // dead-op elimination at flush (OpGraph::eliminate_dead)
     // Constant folding at record time (round 6; OPT-IN: tuning "fold_constants", env TFHE_HIP_FOLD_CONSTANTS).  A trivial
     // sample -- bootsCONSTANT, a fresh sample, a copy of either -- is a PUBLIC constant, and a gate with such an operand
     // needs no bootstrap to be evaluated: its result is a constant, the other operand, or its negation (linear); a MUX with
@@ -83,9 +69,9 @@ Recorder &rec() {
 }
 
 void release_refs(SlotPool *pool, const PendingOp &op) {    // the pending references an op holds
-    for (const int32_t s : {op.dst, op.a, op.b, op.c})
+    for (const int32_t s : {op.a, op.b, op.c})
         if (s >= 0) pool->release(s);
-    if (op.kind == OP_LUTM) for_each_dst(op, [&](int32_t d) { pool->release(d); });
+    for_each_dst(op, [&](int32_t d) { pool->release(d); });
 }
 
 // "Same parameter set" for a multi-key flush: every field that evaluation reads, by VALUE (two separately allocated sets
@@ -102,17 +88,17 @@ bool same_evaluation_params(const Params &a, const Params &b) {
 void select_key(const TFheGateBootstrappingCloudKeySet *bk) {
     Recorder &r = rec();
     auto known = std::find(r.keys.begin(), r.keys.end(), bk);
-    if (known == r.keys.end() && !r.ops.empty()) {
+    if (known == r.keys.end() && !r.graph.ops().empty()) {
         // a key the recording does not hold yet: one more key of the flush (batch_keys, same parameter set) or a flush.
         // Every key of the list passed this test against the first, so comparing with the first compares with all
         if (!r.batch_keys || pool_of_key(bk) != r.pool || !same_evaluation_params(bk->bk->p, r.keys.front()->bk->p))
             flush_locked();
     }
-    if (r.ops.empty()) r.keys.clear();            // nothing pending: the list starts afresh with this key
+    if (r.graph.ops().empty()) r.keys.clear();            // nothing pending: the list starts afresh with this key
     known = std::find(r.keys.begin(), r.keys.end(), bk);
     if (known == r.keys.end()) {
         if (r.keys.size() > UINT16_MAX) flush_locked();   // (PendingOp::key) -- a flush empties the list below
-        if (r.ops.empty()) r.keys.clear();
+        if (r.graph.ops().empty()) r.keys.clear();
         r.keys.push_back(bk);
         known = r.keys.end() - 1;
     }
@@ -125,107 +111,56 @@ void begin_op(const TFheGateBootstrappingCloudKeySet *bk) {
     r.pool = pool_of_key(bk);
     // pending operations pin their slots until they run: flush before the pool runs dry, so
     // arbitrarily long recordings need only bounded device memory
-    if (!r.ops.empty() && r.pool->capacity() - r.pool->in_use() < 4096) flush_locked();
+    if (!r.graph.ops().empty() && r.pool->capacity() - r.pool->in_use() < 4096) flush_locked();
 }
 
-void finish_op(LweSample *result) {
-    if (!rec().deferred) {
-        flush_locked();
-        sync_sample_locked(result);   // immediate mode: host mirror valid on return, as upstream
-    }
+// the one tail of every record: immediate mode runs the op and refreshes the host mirrors, as upstream has them on return
+void finish_op(LweSample *const *result, int count) {
+    if (rec().deferred) return;
+    flush_locked();
+    for (int m = 0; m < count; ++m)
+        if (result[m]) sync_sample_locked(result[m]);
 }
 
 // result becomes (a handle of) `slot`: a COPY
 void point_at(LweSample *result, SlotPool *pool, int32_t slot) {
     pool->retain(slot);
     repoint(result, pool, slot);
-    finish_op(result);
+    finish_op(&result, 1);
 }
 
 // 0 / 1 if `slot` is one of the pool's shared trivial samples (a public constant), else -1
 int const_bit(const SlotPool *pool, int32_t slot) { return slot == pool->const_slot[0] ? 0 : slot == pool->const_slot[1] ? 1 : -1; }
 
-// The one record path: share the result of a pending op that computes the same thing (scheduler.hpp OpKey), else append the
-// op.  Two-input gates: c = -1; NOT: b = c = -1.  lut: the test polynomial, coefficients and constant of an OP_LUT (the
-// fields of a PendingOp it carries; the rest is filled in here), else null.
-void record_op(int kind, LweSample *result, SlotPool *pool, const int32_t a, const int32_t b, const int32_t c,
-               const PendingOp *lut = nullptr) {
-    Recorder &r = rec();
-    PendingOp op = lut ? *lut : PendingOp{};
-    op.kind = (uint8_t)kind; op.a = a; op.b = b; op.c = c; op.key = r.cur_key;
-    const OpKey key = op_key(op);
-    if (r.reuse_gates) {
-        auto it = r.index.find(key);
-        if (it != r.index.end()) {
-            ++Engine::get().stats.reused_gates;
-            return point_at(result, pool, it->second);
-        }
-    }
-    const int32_t dst = alloc_slot(pool);     // may flush: levels are read after it
-    int32_t level = 0;
-    for (const int32_t s : {a, b, c})
-        if (s >= 0) { level = std::max(level, pool->level[s]); pool->retain(s); }   // and the pending references
-    if (kind != OP_NOT) ++level;              // a NOT is linear: it rides on its operand's level
-    pool->level[dst] = level;
-    pool->pending[dst] = 1;                   // pending even at level 0 (NOT of a materialised sample)
-    pool->retain(dst);
-    op.dst = dst;
-    op.level = level;
-    r.ops.push_back(op);
-    if (r.reuse_gates) r.index.emplace(key, dst);
-    if (kind == OP_NOT) r.not_origin.emplace(dst, a);
-    r.max_level = std::max(r.max_level, level);
-    repoint(result, pool, dst);
-    finish_op(result);
+PendingOp make_op(int kind, int32_t a, int32_t b, int32_t c) {    // two-input gates: c = -1; NOT: b = c = -1
+    PendingOp op{};
+    op.kind = (uint8_t)kind; op.dst = -1; op.a = a; op.b = b; op.c = c;
+    return op;
+}
+PendingOp make_lut_op(int kind, SlotPool *pool, int32_t lut, int nin, const LweSample *const *in, const int32_t *coef, int32_t c0) {
+    int32_t slot[3] = {-1, -1, -1};
+    for (int i = 0; i < nin; ++i) slot[i] = ensure_slot(in[i], pool);
+    PendingOp op = make_op(kind, slot[0], slot[1], slot[2]);
+    op.lut = lut;
+    op.sa = coef[0]; op.sb = nin > 1 ? coef[1] : 0; op.sc = nin > 2 ? coef[2] : 0;
+    op.c0 = c0;
+    return op;
 }
 
-// Recorder::eliminate_dead.  An op is dropped with its index and NOT-origin entries (recorder.hpp: the invariant).
-void eliminate_dead_ops() {
+// The one record path: the graph shares, widens or appends the op (op_graph.hpp) for the outputs with a result sample
+// (result[m] non-null; a single-destination op has result[0] alone), and the handles are re-pointed at what it reports.
+void record_op(PendingOp op, LweSample *const *result) {
     Recorder &r = rec();
     SlotPool *pool = r.pool;
-    // reverse recording order = reverse topological order: dropping a consumer first lets its producers die too
-    size_t dead = 0;
-    std::vector<uint8_t> is_dead(r.ops.size(), 0);
-    for (size_t i = r.ops.size(); i-- > 0;) {
-        PendingOp &op = r.ops[i];
-        if (op.kind == OP_LUTM) {
-            // per output: a dead one loses its destination (no extracted sample, no key switch); the op dies with its last
-            for (int m = 0; m < op.nout; ++m) {
-                const int32_t d = op.dsts[m];
-                if (d < 0 || pool->refs(d) != 1) continue;
-                pool->level[d] = 0;
-                pool->pending[d] = 0;
-                pool->release(d);
-                op.dsts[m] = -1;
-            }
-            if (op_wanted(op)) continue;
-            release_refs(pool, op);                     // (the operands: no destination is left)
-            is_dead[i] = 1;
-            ++dead;
-            continue;
-        }
-        if (pool->refs(op.dst) != 1) continue;          // a handle or a live operation still holds the result
-        auto it = r.index.find(op_key(op));
-        if (it != r.index.end() && it->second == op.dst) r.index.erase(it);
-        if (op.kind == OP_NOT) r.not_origin.erase(op.dst);
-        pool->level[op.dst] = 0;
-        pool->pending[op.dst] = 0;
-        release_refs(pool, op);
-        is_dead[i] = 1;
-        ++dead;
-    }
-    if (!dead) return;
-    size_t w = 0;
-    int32_t depth = 0;
-    for (size_t i = 0; i < r.ops.size(); ++i)
-        if (!is_dead[i]) { depth = std::max(depth, r.ops[i].level); r.ops[w++] = r.ops[i]; }
-    r.ops.resize(w);
-    r.max_level = depth;
-    r.index_multi.clear();
-    if (r.reuse_gates)
-        for (size_t i = 0; i < r.ops.size(); ++i)
-            if (r.ops[i].kind == OP_LUTM) r.index_multi.emplace(op_key(r.ops[i]), (int32_t)i);
-    Engine::get().stats.dead_gates += dead;
+    op.key = r.cur_key;
+    const int nout = op_outputs(op);
+    unsigned wanted = 0;
+    for (int m = 0; m < nout; ++m) wanted |= (result[m] ? 1u : 0u) << m;
+    int32_t out[4];
+    if (r.graph.record(*pool, op, wanted, [pool](int) { return alloc_slot(pool); }, out) >= 0) ++Engine::get().stats.reused_gates;
+    for (int m = 0; m < nout; ++m)
+        if (result[m]) repoint(result[m], pool, out[m]);
+    finish_op(result, nout);
 }
 
 }  // namespace
@@ -246,7 +181,7 @@ int32_t alloc_slot(SlotPool *pool) {
     Recorder &r = rec();
     if (pool->in_use() == pool->capacity()) {
         finish_flight_locked();                          // a completed asynchronous flush still pins its slots
-        if (pool->in_use() == pool->capacity() && !r.ops.empty() && r.pool == pool) flush_locked();
+        if (pool->in_use() == pool->capacity() && !r.graph.ops().empty() && r.pool == pool) flush_locked();
     }
     return pool->alloc();
 }
@@ -279,7 +214,7 @@ void sync_sample_locked(const LweSample *cs) {
     SlotPool *pool = pool_of_sample(s);
     // pending = written by a recorded operation that has not run (a gate, or a NOT riding on
     // level 0 of an already materialised operand)
-    if (pool->pending[s->slot] && !r.ops.empty()) flush_locked();
+    if (pool->pending[s->slot] && !r.graph.ops().empty()) flush_locked();
     Engine::get().read_slot(pool, s->slot, s->a, &s->b);
 }
 
@@ -303,7 +238,7 @@ void record_gate2_locked(int code, LweSample *result, const LweSample *ca, const
             return record_not_locked(result, ka >= 0 ? cb : ca, bk);                      // NOT x: linear, no bootstrap
         }
     }
-    record_op(code, result, pool, sa, sb, -1);
+    record_op(make_op(code, sa, sb, -1), &result);
 }
 
 void record_not_locked(LweSample *result, const LweSample *ca, const TFheGateBootstrappingCloudKeySet *bk) {
@@ -316,9 +251,8 @@ void record_not_locked(LweSample *result, const LweSample *ca, const TFheGateBoo
         return point_at(result, pool, pool->const_slot[1 - const_bit(pool, sa)]);
     // NOT of a still-pending NOT: -(-x) = x exactly, so alias the original operand; two NOTs
     // of one level would otherwise sit in the same launch and race
-    auto it = r.not_origin.find(sa);
-    if (it != r.not_origin.end()) return point_at(result, pool, it->second);
-    record_op(OP_NOT, result, pool, sa, -1, -1);
+    if (r.graph.not_origin(sa) >= 0) return point_at(result, pool, r.graph.not_origin(sa));
+    record_op(make_op(OP_NOT, sa, -1, -1), &result);
 }
 
 void record_mux_locked(LweSample *result, const LweSample *a, const LweSample *b, const LweSample *c,
@@ -343,7 +277,7 @@ void record_mux_locked(LweSample *result, const LweSample *a, const LweSample *b
             return record_gate2_locked(kb == 0 ? TFHE_HIP_ANDNY : TFHE_HIP_OR, result, a, c, bk);               // !a & c | a | c
         }
     }
-    record_op(OP_MUX, result, pool, sa, sb, sc);
+    record_op(make_op(OP_MUX, sa, sb, sc), &result);
 }
 
 // Three-input gates (tfhe_hip_gate3): gate = enum TfheHipGate3, bit i of negate_mask negates operand i.  The operands are
@@ -385,7 +319,7 @@ void record_gate3_locked(int gate, int negate_mask, LweSample *result, const Lwe
     if (in[2].slot < in[1].slot) std::swap(in[1], in[2]);
     if (in[1].slot < in[0].slot) std::swap(in[0], in[1]);
     const int mask = in[0].neg | in[1].neg << 1 | in[2].neg << 2;
-    record_op(OP_GATE3 + 8 * gate + mask, result, pool, in[0].slot, in[1].slot, in[2].slot);
+    record_op(make_op(OP_GATE3 + 8 * gate + mask, in[0].slot, in[1].slot, in[2].slot), &result);
 }
 
 // Programmable bootstrap (tfhe_hip_lut_bootstrap): t = (0, c0) + sum coef[i] in[i] from test polynomial `lut` of the engine's
@@ -397,19 +331,12 @@ void record_lut_locked(int32_t lut, LweSample *result, int nin, const LweSample 
     begin_op(bk);
     SlotPool *pool = r.pool;
     bind_pool(result, pool);
-    int32_t slot[3] = {-1, -1, -1};
-    for (int i = 0; i < nin; ++i) slot[i] = ensure_slot(in[i], pool);
-    PendingOp op{};
-    op.lut = lut;
-    op.sa = coef[0]; op.sb = nin > 1 ? coef[1] : 0; op.sc = nin > 2 ? coef[2] : 0;
-    op.c0 = c0;
-    record_op(OP_LUT, result, pool, slot[0], slot[1], slot[2], &op);
+    record_op(make_lut_op(OP_LUT, pool, lut, nin, in, coef, c0), &result);
 }
 
 // Multi-output programmable bootstrap (tfhe_hip_lut_bootstrap_multi): ONE op with up to four destinations -- the
 // outputs of extract spec `spec` (nout of them) that the caller wants (result[m] non-null), each renamed to a fresh slot
-// like a gate's result; all become available at the op's level.  "reuse_gates": a pending op equal in spec, LUT,
-// operands, coefficients, c0 and key serves this one output by output, and is widened by the outputs it lacks.
+// like a gate's result; all become available at the op's level.
 void record_lutm_locked(int32_t lut, int32_t spec, int nout, LweSample *const *result, int nin, const LweSample *const *in,
                         const int32_t *coef, int32_t c0, const TFheGateBootstrappingCloudKeySet *bk) {
     Recorder &r = rec();
@@ -417,77 +344,23 @@ void record_lutm_locked(int32_t lut, int32_t spec, int nout, LweSample *const *r
     SlotPool *pool = r.pool;
     for (int m = 0; m < nout; ++m)
         if (result[m]) bind_pool(result[m], pool);      // refuse a foreign / mismatched result before anything changes
-    int32_t slot[3] = {-1, -1, -1};
-    for (int i = 0; i < nin; ++i) slot[i] = ensure_slot(in[i], pool);
-    PendingOp op{};
-    op.kind = OP_LUTM; op.dst = -1; op.a = slot[0]; op.b = slot[1]; op.c = slot[2]; op.key = r.cur_key;
-    op.lut = lut; op.spec = spec; op.nout = nout;
-    op.sa = coef[0]; op.sb = nin > 1 ? coef[1] : 0; op.sc = nin > 2 ? coef[2] : 0;
-    op.c0 = c0;
-    // the destinations first: a dry pool runs the pending ops (alloc_slot), and what is looked up below must survive that
-    int32_t fresh[4] = {-1, -1, -1, -1};
-    try {
-        for (int m = 0; m < nout; ++m)
-            if (result[m]) fresh[m] = alloc_slot(pool);
-    } catch (...) {
-        for (const int32_t d : fresh) if (d >= 0) pool->release(d);
-        throw;
-    }
-    const OpKey key = op_key(op);
-    auto hit = r.reuse_gates ? r.index_multi.find(key) : r.index_multi.end();
-    if (hit != r.index_multi.end()) {
-        PendingOp &have = r.ops[(size_t)hit->second];
-        ++Engine::get().stats.reused_gates;
-        for (int m = 0; m < nout; ++m) {
-            if (!result[m]) continue;
-            if (have.dsts[m] >= 0) {                    // shared: the fresh slot goes back
-                pool->release(fresh[m]);
-                pool->retain(have.dsts[m]);
-            } else {                                    // widened: the pending op gains this output
-                have.dsts[m] = fresh[m];
-                pool->level[fresh[m]] = have.level;
-                pool->pending[fresh[m]] = 1;
-                pool->retain(fresh[m]);
-            }
-            repoint(result[m], pool, have.dsts[m]);
-        }
-    } else {
-        int32_t level = 0;
-        for (const int32_t s : slot)
-            if (s >= 0) { level = std::max(level, pool->level[s]); pool->retain(s); }
-        op.level = ++level;
-        for (int m = 0; m < nout; ++m) {
-            if (!result[m]) continue;
-            op.dsts[m] = fresh[m];
-            pool->level[fresh[m]] = level;
-            pool->pending[fresh[m]] = 1;
-            pool->retain(fresh[m]);
-        }
-        r.ops.push_back(op);
-        if (r.reuse_gates) r.index_multi.emplace(key, (int32_t)r.ops.size() - 1);
-        r.max_level = std::max(r.max_level, level);
-        for (int m = 0; m < nout; ++m)
-            if (result[m]) repoint(result[m], pool, fresh[m]);
-    }
-    if (!r.deferred) {
-        flush_locked();
-        for (int m = 0; m < nout; ++m)
-            if (result[m]) sync_sample_locked(result[m]);
-    }
+    PendingOp op = make_lut_op(OP_LUTM, pool, lut, nin, in, coef, c0);
+    op.spec = spec; op.nout = nout;
+    record_op(op, result);
 }
 
+// something the recorded ops name by index is about to be deleted: run the recording (or finish the flight) if one does
+template <typename Names>
+static void run_if_named(Names names) {
+    Recorder &r = rec();
+    if (std::any_of(r.graph.ops().begin(), r.graph.ops().end(), names)) flush_locked();
+    else if (std::any_of(r.flight_ops.begin(), r.flight_ops.end(), names)) finish_flight_locked();
+}
 void forget_lutm_locked(int32_t lut, int32_t spec) {
-    Recorder &r = rec();
-    auto names = [lut, spec](const PendingOp &op) { return op.kind == OP_LUTM && (op.spec == spec || op.lut == lut); };
-    if (std::any_of(r.ops.begin(), r.ops.end(), names)) flush_locked();
-    else if (std::any_of(r.flight_ops.begin(), r.flight_ops.end(), names)) finish_flight_locked();
+    run_if_named([=](const PendingOp &op) { return op.kind == OP_LUTM && (op.spec == spec || op.lut == lut); });
 }
-
 void forget_lut_locked(int32_t lut) {
-    Recorder &r = rec();
-    auto names = [lut](const PendingOp &op) { return op.kind == OP_LUT && op.lut == lut; };
-    if (std::any_of(r.ops.begin(), r.ops.end(), names)) flush_locked();
-    else if (std::any_of(r.flight_ops.begin(), r.flight_ops.end(), names)) finish_flight_locked();
+    run_if_named([=](const PendingOp &op) { return op.kind == OP_LUT && op.lut == lut; });
 }
 
 void record_constant_locked(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk) {
@@ -525,56 +398,53 @@ void finish_flight_locked() {
 
 int flush_locked(bool wait) {
     Recorder &r = rec();
-    if (!r.ops.empty() && r.eliminate_dead) eliminate_dead_ops();
-    if (r.ops.empty()) { r.max_level = 0; if (wait) finish_flight_locked(); return 0; }
+    if (!r.graph.ops().empty() && r.eliminate_dead) Engine::get().stats.dead_gates += r.graph.eliminate_dead(*r.pool);
+    if (r.graph.ops().empty()) { if (wait) finish_flight_locked(); return 0; }
     SlotPool *pool = r.pool;
+    const std::vector<PendingOp> &ops = r.graph.ops();
     // level of every op: ASAP, or slack-aware balanced (same depth, fuller narrow levels)
     std::vector<int32_t> lvl, alap;
-    const int levels = schedule_levels(r.ops, r.max_level, r.balance_levels, Engine::get().cu_count(), lvl, &alap);
+    const int levels = schedule_levels(ops, r.graph.max_level(), r.balance_levels, Engine::get().cu_count(), lvl, &alap);
     if (const char *trace = std::getenv("TFHE_HIP_TRACE_DAG")) {      // diagnostic: per op "kind asap alap level dst a b c" (slots)
         if (FILE *f = std::fopen(trace, "w")) {
-            for (size_t i = 0; i < r.ops.size(); ++i)
-                std::fprintf(f, "%d %d %d %d %d %d %d %d\n", (int)r.ops[i].kind, r.ops[i].level, alap[i], lvl[i],
-                             r.ops[i].dst, r.ops[i].a, r.ops[i].b, r.ops[i].c);
+            for (size_t i = 0; i < ops.size(); ++i)
+                std::fprintf(f, "%d %d %d %d %d %d %d %d\n", (int)ops[i].kind, ops[i].level, alap[i], lvl[i],
+                             ops[i].dst, ops[i].a, ops[i].b, ops[i].c);
             std::fclose(f);
         }
     }
     // the keys the ops use, in list order (a flush in the middle of recording an op can leave keys of no pending op)
     std::vector<int32_t> remap(r.keys.size(), -1);
-    for (const PendingOp &op : r.ops) remap[op.key] = 0;
+    for (const PendingOp &op : ops) remap[op.key] = 0;
     std::vector<const TFheGateBootstrappingCloudKeySet *> used;
     std::vector<const DeviceKeyImage *> images;
     for (size_t k = 0; k < r.keys.size(); ++k)
         if (remap[k] == 0) { remap[k] = (int32_t)used.size(); used.push_back(r.keys[k]); images.push_back(r.keys[k]->bk->dev); }
     LevelPlan plan;
     if (used.size() == r.keys.size()) {
-        plan = build_level_plan(r.ops, lvl, levels, (int)used.size());
-    } else {
-        std::vector<PendingOp> ops = r.ops;
-        for (PendingOp &op : ops) op.key = (uint16_t)remap[op.key];
         plan = build_level_plan(ops, lvl, levels, (int)used.size());
+    } else {
+        std::vector<PendingOp> rekeyed = ops;
+        for (PendingOp &op : rekeyed) op.key = (uint16_t)remap[op.key];
+        plan = build_level_plan(rekeyed, lvl, levels, (int)used.size());
     }
     // everything above -- elimination, levelling, the plan -- ran while the device was busy with the previous asynchronous
     // flush, if any; execute() would wait for it first anyway
     finish_flight_locked();
     Engine::get().execute(images, pool, std::move(plan), wait);    // throws before anything runs, or runs it all
-    for (const PendingOp &op : r.ops) {
+    for (const PendingOp &op : ops) {
         for_each_dst(op, [&](int32_t d) {
             pool->level[d] = 0;           // a later recording reads these slots as inputs: the stream orders it behind
             pool->pending[d] = 0;
         });
         if (wait) release_refs(pool, op);
     }
-    if (!wait) { r.flight_ops.swap(r.ops); r.flight_pool = pool; r.flight_keys = std::move(used); }
-    r.ops.clear();
-    r.index.clear();
-    r.index_multi.clear();
-    r.not_origin.clear();
-    r.max_level = 0;
+    if (!wait) { r.flight_pool = pool; r.flight_keys = std::move(used); }
+    r.graph.clear(wait ? nullptr : &r.flight_ops);
     return levels;
 }
 
-void flush_pending_locked(bool wait) { if (!rec().ops.empty()) flush_locked(wait); }
+void flush_pending_locked(bool wait) { if (!rec().graph.ops().empty()) flush_locked(wait); }
 
 void forget_key_locked(const TFheGateBootstrappingCloudKeySet *bk) {
     Recorder &r = rec();
@@ -592,7 +462,7 @@ bool set_batch_keys_locked(bool on) { return std::exchange(rec().batch_keys, on)
 
 bool set_recorder_tuning_locked(const char *name, bool on) {
     Recorder &r = rec();
-    bool *knob = std::strcmp(name, "reuse_gates") == 0      ? &r.reuse_gates
+    bool *knob = std::strcmp(name, "reuse_gates") == 0      ? &r.graph.reuse
                  : std::strcmp(name, "eliminate_dead") == 0 ? &r.eliminate_dead
                  : std::strcmp(name, "fold_constants") == 0 ? &r.fold_constants
                  : std::strcmp(name, "balance_levels") == 0 ? &r.balance_levels

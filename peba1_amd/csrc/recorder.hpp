@@ -6,10 +6,12 @@
 // temporaries freed right after use (Math.cpp:47-49).  An op's level is 1 + the maximum level of its operand slots; a
 // flush executes level 1, 2, ... as batched kernel launches.  bootsCOPY and bootsCONSTANT only re-point handles.
 //
-// Every op is recorded through one path (record_op) and looked up in ONE index keyed by (kind, a, b, c, key): a hit shares the
-// pending result, a miss appends the op.  Invariant: every entry of the index and of the NOT-origin table names the
-// destination of an op still recorded.  Dead-gate elimination drops an op's entries in the loop that drops the op, and a
-// successful flush clears both tables with the ops, so a flush refused for want of device memory can be retried.
+// The pending ops live in one graph over slots (op_graph.hpp), which alone shares, widens, levels and eliminates them and
+// keeps the one index (OpKey -> the op) and the NOT-origin table.  A record_*_locked binds the pool, gets the operands'
+// slots, folds constants, and hands the op to the one record path (record_op in recorder.cpp), single- or
+// multi-destination alike: the graph reports the slot of every wanted result, the handles are re-pointed, and immediate
+// mode runs the op.  A flush refused for want of device memory changes nothing but what elimination dropped, so it can
+// be retried; a successful one clears the graph.
 //
 // Every function here expects the recorder lock (recorder_lock()) to be held.
 #pragma once

@@ -18,7 +18,7 @@
 namespace tfhe_hip {
 
 struct PendingOp {
-    uint8_t kind;       // 0..9 two-input gate code, OP_MUX, OP_NOT, OP_GATE3 + 8 gate + negation mask, OP_LUT
+    uint8_t kind;       // 0..9 two-input gate code, OP_MUX, OP_NOT, OP_GATE3 + 8 gate + negation mask, OP_LUT, OP_LUTM
     int32_t dst, a, b, c;   // slots; b, c = -1 when absent
     int32_t level;      // ASAP level (NOT: the level of its operand, 0 = already materialised)
     uint16_t key = 0;   // index of the gate's cloud key in the flush's key list (recorder "batch_keys"; NOT: unused)
@@ -28,7 +28,7 @@ struct PendingOp {
     int32_t sa = 0, sb = 0, sc = 0, c0 = 0;
     // OP_LUTM only (tfhe_hip_lut_bootstrap_multi): lut and the prelude as for OP_LUT; the extract spec (index in the
     // engine's spec table), its number of outputs, and the destination slot of every output -- -1 for one that nobody
-    // wants (a null result, or dead at the flush).  `dst` is unused (-1): for_each_dst visits the destinations of any op
+    // wants (a null result, or dead at the flush).  `dst` is unused (-1): op_outputs / op_dst name the outputs of any op
     int32_t spec = -1;
     int32_t nout = 0;
     int32_t dsts[4] = {-1, -1, -1, -1};
@@ -57,11 +57,14 @@ inline int op_wanted(const PendingOp &op) {
 inline int op_keyswitches(const PendingOp &op) {
     return op.kind == OP_NOT ? 0 : op.kind == OP_LUTM ? __builtin_popcount((unsigned)op_wanted(op)) : 1;
 }
+// the outputs of any op: a single-destination op is the one-output case
+inline int op_outputs(const PendingOp &op) { return op.kind == OP_LUTM ? op.nout : 1; }
+inline int32_t &op_dst(PendingOp &op, int m) { return op.kind == OP_LUTM ? op.dsts[m] : op.dst; }
+inline int32_t op_dst(const PendingOp &op, int m) { return op.kind == OP_LUTM ? op.dsts[m] : op.dst; }
 template <class F>
 inline void for_each_dst(const PendingOp &op, F &&f) {
-    if (op.kind != OP_LUTM) return (void)f(op.dst);
-    for (int m = 0; m < op.nout; ++m)
-        if (op.dsts[m] >= 0) f(op.dsts[m]);
+    for (int m = 0; m < op_outputs(op); ++m)
+        if (op_dst(op, m) >= 0) f(op_dst(op, m));
 }
 
 // prelude constants of the two-input gates: (c0 in eighths, sa, sb), tfhe boot-gates.cpp

@@ -7,12 +7,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <numeric>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "br_forms.hpp"
 #include "engine.hpp"
+#include "op_graph.hpp"
 #include "recorder.hpp"
 #include "scheduler.hpp"
 #include "../../include/tfhe/tfhe.h"
@@ -68,6 +69,18 @@ void guarded(F &&body) {
 template <typename F>
 int guarded_rc(F &&body) {
     try { return body(); } catch (const ApiError &e) { set_error(e.msg); return -1; }
+}
+
+// Every *_batch entry: `body` records its ops deferred whatever the caller's mode; a caller in immediate mode has them run
+// before the call returns -- those recorded before a refused one included.
+template <typename F>
+int record_batch(F &&body) {
+    auto g = recorder_lock();
+    const bool was = set_deferred_locked(true);
+    const int rc = guarded_rc([&] { body(); return 0; });
+    set_deferred_locked(was);
+    if (!was) flush_locked();
+    return rc;
 }
 
 void record_gate2(int code, LweSample *result, const LweSample *ca, const LweSample *cb,
@@ -528,15 +541,9 @@ void tfhe_hip_set_diag_label(const char *label) {
 int tfhe_hip_gate_batch(int gate, LweSample *result, const LweSample *a, const LweSample *b, int32_t count,
                         const TFheGateBootstrappingCloudKeySet *bk) {
     if (gate < 0 || gate > TFHE_HIP_ORYN) { set_error("tfhe_hip_gate_batch: bad gate code"); return -1; }
-    auto g = recorder_lock();
-    const bool was = set_deferred_locked(true);
-    const int rc = guarded_rc([&] {
+    return record_batch([&] {
         for (int32_t i = 0; i < count; ++i) record_gate2_locked(gate, &result[i], &a[i], &b[i], bk);
-        return 0;
     });
-    set_deferred_locked(was);
-    if (!was) flush_locked();      // gates recorded before a refused one still run
-    return rc;
 }
 
 static bool gate3_args_ok(const char *who, int gate, int negate_mask) {
@@ -557,15 +564,9 @@ void tfhe_hip_gate3(int gate, int negate_mask, LweSample *result, const LweSampl
 int tfhe_hip_gate3_batch(int gate, int negate_mask, LweSample *result, const LweSample *a, const LweSample *b,
                          const LweSample *c, int32_t count, const TFheGateBootstrappingCloudKeySet *bk) {
     if (!gate3_args_ok("tfhe_hip_gate3_batch", gate, negate_mask)) return -1;
-    auto g = recorder_lock();
-    const bool was = set_deferred_locked(true);
-    const int rc = guarded_rc([&] {
+    return record_batch([&] {
         for (int32_t i = 0; i < count; ++i) record_gate3_locked(gate, negate_mask, &result[i], &a[i], &b[i], &c[i], bk);
-        return 0;
     });
-    set_deferred_locked(was);
-    if (!was) flush_locked();      // gates recorded before a refused one still run
-    return rc;
 }
 
 // ---- programmable bootstrap: caller-supplied test polynomials ----
@@ -667,19 +668,13 @@ void tfhe_hip_lut_bootstrap(const TfheHipLut *lut, LweSample *result, int32_t ni
 
 int tfhe_hip_lut_bootstrap_batch(const TfheHipLut *lut, LweSample *result, int32_t nin, const LweSample *const *in,
                                  const int32_t *coef, Torus32 c0, int32_t count, const TFheGateBootstrappingCloudKeySet *bk) {
-    auto g = recorder_lock();
-    const bool was = set_deferred_locked(true);
-    const int rc = guarded_rc([&] {
+    return record_batch([&] {
         const int32_t entry = lut_entry(lut, nin, in, coef, bk);
         for (int32_t i = 0; i < count; ++i) {
             const LweSample *ops[3] = {&in[0][i], nin > 1 ? &in[1][i] : nullptr, nin > 2 ? &in[2][i] : nullptr};
             record_lut_locked(entry, &result[i], nin, ops, coef, c0, bk);
         }
-        return 0;
     });
-    set_deferred_locked(was);
-    if (!was) flush_locked();      // ops recorded before a refused one still run
-    return rc;
 }
 
 // ---- multi-output programmable bootstrap: several extractions from one rotation ----
@@ -828,9 +823,7 @@ void tfhe_hip_lut_bootstrap_multi(const TfheHipLutMulti *mo, LweSample *const *r
 int tfhe_hip_lut_bootstrap_multi_batch(const TfheHipLutMulti *mo, LweSample *const *result, int32_t nin,
                                        const LweSample *const *in, const int32_t *coef, Torus32 c0, int32_t count,
                                        const TFheGateBootstrappingCloudKeySet *bk) {
-    auto g = recorder_lock();
-    const bool was = set_deferred_locked(true);
-    const int rc = guarded_rc([&] {
+    return record_batch([&] {
         lutm_check_results(mo, result);
         lutm_entry(mo, nin, in, coef, bk);
         for (int32_t i = 0; i < count; ++i) {
@@ -839,11 +832,7 @@ int tfhe_hip_lut_bootstrap_multi_batch(const TfheHipLutMulti *mo, LweSample *con
             for (int m = 0; m < mo->spec.nout; ++m) res[m] = result[m] ? &result[m][i] : nullptr;
             record_lutm_locked(mo->lut.dev, mo->dev_spec, mo->spec.nout, res, nin, ops, coef, c0, bk);
         }
-        return 0;
     });
-    set_deferred_locked(was);
-    if (!was) flush_locked();      // ops recorded before a refused one still run
-    return rc;
 }
 
 void tfhe_hip_test_set_alloc_cap(int64_t bytes) {
@@ -936,119 +925,84 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
     for (int32_t i = 0; i < count; ++i)
         if (op_keys[i] < 0 || op_keys[i] >= nkeys) { set_error("test_level_plan: key index out of range"); return -1; }
     std::vector<PendingOp> ops;
-    std::vector<int32_t> op_of_record;                   // lut_ops: record -> index in ops (-1: shared, see shared_with)
+    std::vector<int32_t> op_of_record;                   // lut_ops: record -> index in ops (-1: eliminated)
     int depth;
     if (!lut_ops) {
         depth = test_build_ops(ops5, count, ops);
         if (depth < 0) return -1;
         for (int32_t i = 0; i < count; ++i) ops[i].key = (uint16_t)op_keys[i];
     } else {
-        // As the recorder records them (recorder.cpp record_op): an op equal to a pending one by OpKey shares its result
-        // -- it is dropped, and later ops that read its destination read the earlier op's -- else it is appended with
-        // its ASAP level.  shared_with[i] = the record whose result record i shares, or -1.
-        std::unordered_map<OpKey, int32_t, OpKeyHash> index;       // key -> record
-        std::unordered_map<int32_t, int32_t> alias;                // destination of a dropped op -> the shared destination
-        std::vector<int32_t> slot_level;
-        op_of_record.assign((size_t)count, 0);
-        depth = 0;
-        auto resolve = [&](int32_t slot) { auto it = alias.find(slot); return it == alias.end() ? slot : it->second; };
-        auto level_of = [&](int32_t slot) { return slot >= 0 && (size_t)slot < slot_level.size() ? slot_level[slot] : 0; };
-        auto set_level = [&](int32_t slot, int32_t level) {
-            if ((size_t)slot >= slot_level.size()) slot_level.resize((size_t)slot + 1, 0);
-            slot_level[(size_t)slot] = level;
+        // The records go through the recorder's own graph (op_graph.hpp) over a plain slot table.  Every id of the records
+        // is a handle that holds the slot of its own number; the destination ids of a record are the fresh slots the graph
+        // is offered, and a record that was shared re-points its handles, so later records read what the recorder's
+        // would.  shared_with[i] = the record whose op record i shares or widens, or -1.
+        struct SlotTable {
+            std::vector<int32_t> ref, level;
+            std::vector<uint8_t> pending;
+            void retain(int32_t s) { ++ref[(size_t)s]; }
+            void release(int32_t s) { --ref[(size_t)s]; }
+            int32_t refs(int32_t s) const { return ref[(size_t)s]; }
         };
+        const int id_words = rec_words == 16 ? 4 : 0;            // the destinations of a multi-output record: words 12..15
+        int32_t top = 0;
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t *o = ops5 + (size_t)rec_words * (size_t)i;
+            for (int w = 1; w <= 4; ++w) top = std::max(top, o[w] + 1);
+            for (int w = 12; w < 12 + id_words; ++w) top = std::max(top, o[w] + 1);
+        }
+        SlotTable slots{std::vector<int32_t>((size_t)top, 1), std::vector<int32_t>((size_t)top, 0), std::vector<uint8_t>((size_t)top, 0)};
+        std::vector<int32_t> handle((size_t)top), record_of_op;
+        std::iota(handle.begin(), handle.end(), 0);
+        OpGraph<SlotTable> graph;
+        graph.reuse = reuse != 0;
+        op_of_record.assign((size_t)count, -1);
         for (int32_t i = 0; i < count; ++i) {
             const int32_t *o = ops5 + (size_t)rec_words * (size_t)i;
             const bool multi = rec_words == 16 && o[0] == OP_LUTM;
             if (!op_kind_valid_lut(o[0]) && !multi) { set_error("test schedule: unknown op kind"); return -1; }
-            PendingOp op{(uint8_t)o[0], o[1], resolve(o[2]), resolve(o[3]), resolve(o[4]), 0, (uint16_t)op_keys[i]};
+            auto slot_of = [&](int32_t id) { return id >= 0 ? handle[(size_t)id] : -1; };
+            PendingOp op{(uint8_t)o[0], -1, slot_of(o[2]), slot_of(o[3]), slot_of(o[4]), 0, (uint16_t)op_keys[i]};
             if (op.kind == OP_LUT || multi) { op.lut = o[5]; op.sa = o[6]; op.sb = o[7]; op.sc = o[8]; op.c0 = o[9]; }
-            if (shared_with) shared_with[i] = -1;
+            int32_t ids[4] = {o[1], -1, -1, -1}, out[4];
             if (multi) {
-                // as record_lutm_locked records it: one op, a destination per wanted output; an equal pending op serves
-                // it output by output and is widened by the outputs it lacks
-                op.dst = -1; op.spec = o[10]; op.nout = o[11];
-                bool any = false;
+                op.spec = o[10]; op.nout = o[11];
                 if (op.nout < 1 || op.nout > XS_MAX_OUT) { set_error("test_level_plan_multi: nout must be 1..4"); return -1; }
-                for (int m = 0; m < op.nout; ++m) { op.dsts[m] = o[12 + m]; any |= op.dsts[m] >= 0; }
-                if (!any) { set_error("test_level_plan_multi: an op without a destination"); return -1; }
-                auto hit = reuse ? index.find(op_key(op)) : index.end();
-                if (hit != index.end()) {
-                    PendingOp &have = ops[(size_t)op_of_record[(size_t)hit->second]];
-                    for (int m = 0; m < op.nout; ++m) {
-                        if (op.dsts[m] < 0) continue;
-                        if (have.dsts[m] >= 0) alias[op.dsts[m]] = have.dsts[m];
-                        else { have.dsts[m] = op.dsts[m]; set_level(op.dsts[m], have.level); }
-                    }
-                    if (shared_with) shared_with[i] = hit->second;
-                    op_of_record[(size_t)i] = -1;
-                    continue;
-                }
-                if (reuse) index.emplace(op_key(op), i);
-                op.level = std::max(level_of(op.a), std::max(level_of(op.b), level_of(op.c))) + 1;
-                for (int m = 0; m < op.nout; ++m)
-                    if (op.dsts[m] >= 0) set_level(op.dsts[m], op.level);
-                depth = std::max(depth, op.level);
-                op_of_record[(size_t)i] = (int32_t)ops.size();
-                ops.push_back(op);
-                continue;
+                std::copy(o + 12, o + 12 + op.nout, ids);
             }
-            if (reuse) {
-                auto hit = index.find(op_key(op));
-                if (hit != index.end()) {
-                    alias[op.dst] = ops5[(size_t)rec_words * (size_t)hit->second + 1];
-                    if (shared_with) shared_with[i] = hit->second;
-                    op_of_record[(size_t)i] = -1;
-                    continue;
+            unsigned wanted = 0;
+            for (int m = 0; m < op_outputs(op); ++m) {
+                if (ids[m] < 0) continue;
+                if (handle[(size_t)ids[m]] != ids[m] || slots.pending[(size_t)ids[m]] || std::count(ids, ids + m, ids[m])) {
+                    set_error("test_level_plan: a destination id used twice");
+                    return -1;
                 }
-                index.emplace(op_key(op), i);
+                wanted |= 1u << m;
             }
-            const int32_t in = std::max(level_of(op.a), std::max(level_of(op.b), level_of(op.c)));
-            op.level = op.kind == OP_NOT ? in : in + 1;
-            if ((size_t)op.dst >= slot_level.size()) slot_level.resize((size_t)op.dst + 1, 0);
-            slot_level[(size_t)op.dst] = op.level;
-            depth = std::max(depth, op.level);
-            op_of_record[(size_t)i] = (int32_t)ops.size();
-            ops.push_back(op);
+            if (!wanted) { set_error("test_level_plan: an op without a destination"); return -1; }
+            const int32_t shared = graph.record(slots, op, wanted, [&](int m) { return ids[m]; }, out);
+            if (shared < 0) record_of_op.push_back(i);
+            if (shared_with) shared_with[i] = shared < 0 ? -1 : record_of_op[(size_t)shared];
+            op_of_record[(size_t)i] = shared < 0 ? (int32_t)record_of_op.size() - 1 : shared;
+            for (int m = 0; m < op_outputs(op); ++m)
+                if ((wanted >> m & 1) && out[m] != ids[m]) { slots.release(ids[m]); handle[(size_t)ids[m]] = out[m]; }   // (recorder.cpp repoint)
         }
-        if (ndead > 0) {
-            // As the flush eliminates (recorder.cpp eliminate_dead_ops): in reverse recording order, a destination that
-            // no handle holds (dead_slots) and no surviving op reads is dropped -- a multi-output op output by output,
-            // dying with its last -- and a dropped op reads nothing
-            std::vector<uint8_t> unheld(slot_level.size(), 0), read(slot_level.size(), 0);
-            for (int32_t d = 0; d < ndead; ++d)
-                if (dead_slots[d] >= 0 && (size_t)dead_slots[d] < unheld.size()) unheld[(size_t)dead_slots[d]] = 1;
-            auto gone = [&](int32_t slot) { return unheld[(size_t)slot] && !read[(size_t)slot]; };
-            std::vector<int32_t> keep_at(ops.size(), -1);
-            std::vector<PendingOp> kept;
-            for (size_t i = ops.size(); i-- > 0;) {
-                PendingOp &op = ops[i];
-                bool alive;
-                if (op.kind == OP_LUTM) {
-                    for (int m = 0; m < op.nout; ++m)
-                        if (op.dsts[m] >= 0 && gone(op.dsts[m])) op.dsts[m] = -1;
-                    alive = op_wanted(op) != 0;
-                } else {
-                    alive = !gone(op.dst);
-                }
-                if (!alive) { keep_at[i] = -2; continue; }
-                for (const int32_t src : {op.a, op.b, op.c})
-                    if (src >= 0 && (size_t)src < read.size()) read[(size_t)src] = 1;
-            }
-            depth = 0;
-            for (size_t i = 0; i < ops.size(); ++i)
-                if (keep_at[i] != -2) { keep_at[i] = (int32_t)kept.size(); depth = std::max(depth, ops[i].level); kept.push_back(ops[i]); }
-            for (int32_t &at : op_of_record)
-                if (at >= 0) at = keep_at[(size_t)at];          // -2: eliminated
-            ops.swap(kept);
+        for (int32_t d = 0; d < ndead; ++d) {                    // these handles are gone before the flush
+            const int32_t id = dead_slots[d];
+            if (id < 0 || id >= top || handle[(size_t)id] < 0) continue;
+            slots.release(handle[(size_t)id]);
+            handle[(size_t)id] = -1;
         }
+        std::vector<int32_t> moved_to;
+        graph.eliminate_dead(slots, &moved_to);
+        for (int32_t &at : op_of_record) at = moved_to[(size_t)at];
+        ops = graph.ops();
+        depth = graph.max_level();
     }
     std::vector<int32_t> lvl;
     const int levels = schedule_levels(ops, depth, balance != 0, unit, lvl);
     const LevelPlan plan = build_level_plan(ops, lvl, levels, nkeys);     // exactly what flush_locked hands to execute()
     for (int32_t i = 0; i < count; ++i) {
-        if (!lut_ops) { levels_out[i] = lvl[i]; continue; }
-        const int32_t at = op_of_record[(size_t)i] != -1 ? op_of_record[(size_t)i] : op_of_record[(size_t)shared_with[i]];
+        const int32_t at = lut_ops ? op_of_record[(size_t)i] : i;
         levels_out[i] = at >= 0 ? lvl[(size_t)at] : -1;      // -1: eliminated (tfhe_hip_test_level_plan_multi's dead_slots)
     }
     sizes6[0] = plan.levels;

@@ -219,8 +219,11 @@ assert api.flush() >= 1 and L.tfhe_hip_last_error().decode() == ""
 assert (r.decrypt(ks) == (xa & xb)).all()
 # (1b) a refused flush with dead gates pending: elimination has released their result slots, which the next gates of the
 # retry get again (the pool's free list is LIFO).  Recording the same gates again must not share those freed slots, and a
-# NOT of a gate that got a dead NOT's slot must not be aliased to that NOT's operand.
+# NOT of a gate that got a dead NOT's slot must not be aliased to that NOT's operand.  A multi-output op (AND and NAND
+# of a[j], b[j] from one rotation of t = a + b + 1/8) loses its dead output at the refused flush and is widened by it again.
 K = 8
+and_nand = api.LutMulti.from_tables(pp, 1 << 29, [[-1, 1], [1, -1]])
+mand, mnand = api.CiphertextArray(pp, K), api.CiphertextArray(pp, K)
 w = api.CiphertextArray(pp, G)                                 # with r: a level twice as wide as (1)'s, so its scratch must grow
 dead2, deadmux, deadnot, notnot = (api.CiphertextArray(pp, K) for _ in range(4))
 for i in range(G):
@@ -232,8 +235,9 @@ def record_dying():
         L.bootsMUX(deadmux.at(j), a.at(j), b.at(j), b.at(j + 1), ks.cloud)
         L.bootsNOT(deadnot.at(j), a.at(j), ks.cloud)
         L.bootsNOT(notnot.at(j), deadnot.at(j), ks.cloud)         # NOT of a pending NOT: aliases a[j]
+        api.lut_bootstrap_multi(and_nand, [mand.at(j), mnand.at(j)], [a.at(j), b.at(j)], [1, 1], 1 << 29, ks)
 record_dying()
-for arr in (dead2, deadmux, deadnot):                          # overwritten before the flush: the gates above are dead
+for arr in (dead2, deadmux, deadnot, mnand):                        # overwritten before the flush: the gates above are dead
     for j in range(K):
         L.bootsCONSTANT(arr.at(j), 0, ks.cloud)
 L.tfhe_hip_test_set_alloc_cap(64 << 20)
@@ -251,9 +255,10 @@ assert (r.decrypt(ks) == (xa ^ xb)).all() and (w.decrypt(ks) == (xa | xb)).all()
 assert (dead2.decrypt(ks) == 1 - (xa[:K] & xb[:K])).all()
 assert (deadmux.decrypt(ks) == np.where(xs == 1, xb[:K], xs1)).all()
 assert (deadnot.decrypt(ks) == 1 - xs).all() and (notnot.decrypt(ks) == xs).all()
+assert (mand.decrypt(ks) == (xa[:K] & xb[:K])).all() and (mnand.decrypt(ks) == 1 - (xa[:K] & xb[:K])).all()
 want_fresh = xa[K:4 * K] & (1 - xb[2 * K:5 * K])
 assert (fresh.decrypt(ks) == want_fresh).all() and (freshnot.decrypt(ks) == 1 - want_fresh).all()
-for arr in (w, dead2, deadmux, deadnot, notnot, fresh, freshnot):
+for arr in (w, dead2, deadmux, deadnot, notnot, fresh, freshnot, mand, mnand, and_nand):
     arr.close()
 # (2) the slot pool's growth (it starts at 65,536 slots): the gate that needs slot 65,537 is refused and has no effect;
 # with the cap lifted the same call works and every gate recorded before it still evaluates

@@ -1,7 +1,7 @@
 """CPU tests of the multi-output LUT bootstrap (tfhe_hip_lut_bootstrap_multi): the numpy restatement of the extract at
 index e against the oracle's own extract, the builders and accessors, the error channel, the construction from tables
 against the decrypt rule, the level plan of recordings that hold multi-output ops (through the host-logic entry
-tfhe_hip_test_level_plan_multi, which applies the recorder's sharing and elimination rules), and the committed digests."""
+tfhe_hip_test_level_plan_multi, which runs the recorder's own sharing and elimination code), and the committed digests."""
 import ctypes as C
 
 import numpy as np
@@ -303,6 +303,44 @@ def test_sharing_is_output_by_output_and_widens_the_earlier_op(L):
     # an output added by widening and then dead is dropped again
     pl = plan_multi(L, [base, later], dead=[21])
     assert pl["rots"][0][9] == word(6, 0, 2) and len(pl["kss"]) == 2
+
+
+def test_a_dead_reader_releases_its_operands_exactly_once(L):
+    """The AND's result (10) lost its handle and is read by a live multi-output op and by two dead gates: each dead reader
+    gives back its own reference and no more, so the AND stays exactly as long as the multi-output op does."""
+    ops = [gate(2, 10, 1, 2), multi_op([20, 21], [10, 3], 0, [1, 1], 0, 5), gate(4, 11, 10, 3), gate(0, 12, 10, 4)]
+    pl = plan_multi(L, ops, dead=[10, 11, 12])
+    assert pl["levels"].tolist() == [1, 2, -1, -1] and len(pl["rots"]) == 2
+    assert pl["kss"].tolist() == [[0, -1, 0, 10], [0, -1, 0, 20], [1, -1, 0, 21]]
+    pl = plan_multi(L, ops, dead=[10, 11])               # the second reader alive: it and the AND stay
+    assert pl["levels"].tolist() == [1, 2, -1, 2] and len(pl["rots"]) == 3
+    pl = plan_multi(L, ops, dead=[10, 11, 12, 20, 21])   # the last reader gone: the AND goes with it
+    assert pl["levels"].tolist() == [-1, -1, -1, -1] and len(pl["rots"]) == 0 and len(pl["kss"]) == 0
+
+
+def test_a_shared_op_lives_as_long_as_one_handle_of_its_result(L):
+    """An XOR recorded three times is one op whose result three handles hold (11, and 12 and 13 re-pointed at it); it is
+    dead when the last of them is, and then its producer, which only it read, is dead too."""
+    ops = [gate(2, 10, 1, 2), gate(4, 11, 10, 3), gate(4, 12, 10, 3), gate(4, 13, 3, 10)]
+    for dead in ([10, 11, 12], [10, 11, 13], [10, 12, 13], [10, 11]):
+        pl = plan_multi(L, ops, dead=dead)
+        assert pl["shared"].tolist() == [-1, -1, 1, 1] and pl["levels"].tolist() == [1, 2, 2, 2], dead
+        assert pl["kss"].tolist() == [[0, -1, 0, 10], [0, -1, 0, 11]], dead
+    pl = plan_multi(L, ops, dead=[10, 11, 12, 13])
+    assert pl["levels"].tolist() == [-1, -1, -1, -1] and len(pl["rots"]) == 0
+    pl = plan_multi(L, ops, dead=[11, 12, 13])           # the producer's own handle lives: it stays alone
+    assert pl["levels"].tolist() == [1, -1, -1, -1] and pl["kss"].tolist() == [[0, -1, 0, 10]]
+
+
+def test_a_dead_widened_output_costs_its_key_switch_not_the_rotation(L):
+    base = multi_op([10, -1], [1], 0, [1], 0, 3)
+    later = multi_op([-1, 21], [1], 0, [1], 0, 3)                    # widens the op by output 1 (slot 21)
+    ops = [base, later, gate(2, 30, 10, 2)]
+    pl = plan_multi(L, ops)
+    assert pl["shared"].tolist() == [-1, 0, -1] and pl["rots"][0][9] == word(3, 0, 1) and len(pl["kss"]) == 3
+    pl = plan_multi(L, ops, dead=[10, 21])                           # 10 is still read by the AND
+    assert pl["levels"].tolist() == [1, 1, 2] and len(pl["rots"]) == 2
+    assert pl["rots"][0][9] == word(3, 0) and pl["kss"].tolist() == [[0, -1, 0, 10], [0, -1, 0, 30]]
 
 
 def test_grouping_by_key_with_several_keys(L):
