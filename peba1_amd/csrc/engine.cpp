@@ -189,7 +189,6 @@ void Engine::ensure_init() {
     // a caller that cannot reach tfhe_hip_set_kernel_timing (the reference's unmodified program) asks for the per-level
     // times by naming the trace file
     if (std::getenv("TFHE_HIP_TRACE_TIMES")) kernel_timing = true;
-    for (auto &e : ev_) hip_check(hipEventCreate(&e), "hipEventCreate");
     inited_.store(true, std::memory_order_release);
 }
 
@@ -261,7 +260,7 @@ void Engine::sync_io() {
     io_pending_ = false;
 }
 
-void *Engine::scratch(size_t idx, size_t bytes) {
+void *Engine::scratch(Scratch idx, size_t bytes) {
     if (scratch_ptr_.size() <= idx) { scratch_ptr_.resize(idx + 1, nullptr); scratch_size_.resize(idx + 1, 0); }
     if (scratch_size_[idx] < bytes) {
         sync_stream("sync before scratch realloc");
@@ -456,71 +455,72 @@ void Engine::free_key(DeviceKeyImage *img) {
     delete img;
 }
 
-// ---- test polynomials ----------------------------------------------------------
+// ---- growable device tables -------------------------------------------------------
+// `rows` rows of `words` words laid out at `stride` words a row (the rest of a row zero), and back
+static std::vector<int32_t> pad_rows(const int32_t *src, size_t rows, size_t words, size_t stride) {
+    std::vector<int32_t> padded(rows * stride, 0);
+    for (size_t r = 0; r < rows; ++r) std::memcpy(&padded[r * stride], src + r * words, words * 4);
+    return padded;
+}
+static void unpad_rows(int32_t *dst, const int32_t *src, size_t rows, size_t words, size_t stride) {
+    for (size_t r = 0; r < rows; ++r) std::memcpy(dst + r * words, src + r * stride, words * 4);
+}
+
+// A device array of fixed-size entries that starts at 16 and doubles on demand; entries are handed out from a free list
+// first.  The test polynomials and the extract specs of the caller's objects live in one each.
+namespace {
+struct DeviceTable {
+    const size_t entry;                  // bytes
+    const char *const grow_what, *const sync_what;
+    char *dev = nullptr;
+    size_t cap = 0, used = 0;            // entries allocated / ever handed out
+    std::vector<int32_t> free;
+    int32_t add(const void *src) {
+        if (free.empty() && used == cap) {
+            // (throws ApiError when the card is full: nothing has changed yet)
+            const size_t fresh_cap = cap ? cap * 2 : 16;
+            char *fresh = static_cast<char *>(recoverable_alloc(fresh_cap * entry, grow_what));
+            if (dev) {
+                // launches in flight carry the old pointer: wait for all of them, as the slot pool does when it grows
+                Engine::get().sync_stream(sync_what);
+                hip_check(hipDeviceSynchronize(), sync_what);
+                hip_check(hipMemcpy(fresh, dev, cap * entry, hipMemcpyDeviceToDevice), grow_what);
+                recoverable_free(dev, cap * entry);
+            }
+            dev = fresh;
+            cap = fresh_cap;
+        }
+        int32_t index;
+        if (!free.empty()) { index = free.back(); free.pop_back(); }
+        else index = (int32_t)used++;
+        // a blocking copy: no launch enqueued so far names this entry (new, or freed after its last op had run)
+        hip_check(hipMemcpy(dev + (size_t)index * entry, src, entry, hipMemcpyHostToDevice), "upload a table entry");
+        return index;
+    }
+    void release(int32_t index) { if (index >= 0 && (size_t)index < used) free.push_back(index); }
+};
+DeviceTable g_luts{(size_t)LUT_STRIDE * sizeof(int32_t), "growing the table of test polynomials", "sync before LUT table growth"};
+DeviceTable g_specs{sizeof(ExtractSpec), "growing the table of extract specs", "sync before spec table growth"};
+}  // namespace
+
 int32_t Engine::lut_add(const Torus32 *words, int n_ring) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
     if (n_ring < 1 || n_ring > LUT_STRIDE) api_fail("a test polynomial of more than " + std::to_string(LUT_STRIDE) + " words");
-    constexpr size_t ENTRY = (size_t)LUT_STRIDE * sizeof(int32_t);
-    if (lut_free_.empty() && lut_used_ == lut_cap_) {
-        // (throws ApiError when the card is full: nothing has changed yet)
-        const size_t cap = lut_cap_ ? lut_cap_ * 2 : 16;
-        int32_t *fresh = static_cast<int32_t *>(recoverable_alloc(cap * ENTRY, "growing the table of test polynomials"));
-        if (lut_dev_) {
-            // launches in flight carry the old pointer: wait for all of them, as the slot pool does when it grows
-            sync_stream("sync before LUT table growth");
-            hip_check(hipDeviceSynchronize(), "sync before LUT table growth");
-            hip_check(hipMemcpy(fresh, lut_dev_, lut_cap_ * ENTRY, hipMemcpyDeviceToDevice), "copy LUT table");
-            recoverable_free(lut_dev_, lut_cap_ * ENTRY);
-        }
-        lut_dev_ = fresh;
-        lut_cap_ = cap;
-    }
-    int32_t index;
-    if (!lut_free_.empty()) { index = lut_free_.back(); lut_free_.pop_back(); }
-    else index = (int32_t)lut_used_++;
-    // a blocking copy: no launch enqueued so far names this entry (new, or freed after its last op had run)
-    std::vector<int32_t> padded((size_t)LUT_STRIDE, 0);
-    std::memcpy(padded.data(), words, (size_t)n_ring * sizeof(int32_t));
-    hip_check(hipMemcpy(lut_dev_ + (size_t)index * LUT_STRIDE, padded.data(), ENTRY, hipMemcpyHostToDevice), "upload LUT");
-    return index;
+    return g_luts.add(pad_rows(words, 1, (size_t)n_ring, LUT_STRIDE).data());
 }
+void Engine::lut_free(int32_t index) { g_luts.release(index); }
 
-void Engine::lut_free(int32_t index) {
-    if (index >= 0 && (size_t)index < lut_used_) lut_free_.push_back(index);
-}
-
-// ---- extract specs ---------------------------------------------------------------
 int32_t Engine::spec_add(const ExtractSpec &xs) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
-    if (spec_free_.empty() && spec_used_ == spec_cap_) {
-        if (spec_cap_ > (size_t)XS_ENTRY_MASK / 2) api_fail("too many extract specs");
-        const size_t cap = spec_cap_ ? spec_cap_ * 2 : 16;
-        ExtractSpec *fresh = static_cast<ExtractSpec *>(recoverable_alloc(cap * sizeof(ExtractSpec), "growing the table of extract specs"));
-        if (spec_dev_) {
-            // launches in flight carry the old pointer: wait for all of them, as for the table of test polynomials
-            sync_stream("sync before spec table growth");
-            hip_check(hipDeviceSynchronize(), "sync before spec table growth");
-            hip_check(hipMemcpy(fresh, spec_dev_, spec_cap_ * sizeof(ExtractSpec), hipMemcpyDeviceToDevice), "copy spec table");
-            recoverable_free(spec_dev_, spec_cap_ * sizeof(ExtractSpec));
-        }
-        spec_dev_ = fresh;
-        spec_cap_ = cap;
-    }
-    int32_t index;
-    if (!spec_free_.empty()) { index = spec_free_.back(); spec_free_.pop_back(); }
-    else index = (int32_t)spec_used_++;
-    // a blocking copy: no launch enqueued so far names this entry
-    hip_check(hipMemcpy(spec_dev_ + index, &xs, sizeof(ExtractSpec), hipMemcpyHostToDevice), "upload extract spec");
+    if (g_specs.free.empty() && g_specs.used == g_specs.cap && g_specs.cap > (size_t)XS_ENTRY_MASK / 2) api_fail("too many extract specs");
+    const int32_t index = g_specs.add(&xs);
     if (spec_nout_.size() <= (size_t)index) spec_nout_.resize((size_t)index + 1, 0);
     spec_nout_[(size_t)index] = xs.nout;
     return index;
 }
-
-void Engine::spec_free(int32_t index) {
-    if (index >= 0 && (size_t)index < spec_used_) spec_free_.push_back(index);
-}
+void Engine::spec_free(int32_t index) { g_specs.release(index); }
 
 SlotPool *Engine::find_pool(const Params &p) const {
     for (SlotPool *pl : pools_)
@@ -602,11 +602,11 @@ void Engine::write_slots_packed(SlotPool *pool, const int32_t *slots, int count,
     ENGINE_DEVICE_SCOPE();
     if (count <= 0) return;
     const size_t wbytes = (size_t)count * pool->ct_words() * 4;
-    int32_t *dslots = static_cast<int32_t *>(scratch(3, (size_t)count * 4));
+    int32_t *dslots = static_cast<int32_t *>(scratch(S_SLOTS, (size_t)count * 4));
     hip_check(hipMemcpyAsync(dslots, stage_slots(slots, count), (size_t)count * 4, hipMemcpyHostToDevice, stream_), "upload slot list");
     const int32_t *src = words;
     if (!on_device) {
-        int32_t *dw = static_cast<int32_t *>(scratch(4, wbytes));
+        int32_t *dw = static_cast<int32_t *>(scratch(S_WORDS, wbytes));
         hip_check(hipMemcpyAsync(dw, words, wbytes, hipMemcpyHostToDevice, stream_), "upload packed words");
         src = dw;
     }
@@ -620,9 +620,9 @@ void Engine::read_slots_packed(SlotPool *pool, const int32_t *slots, int count, 
     if (count <= 0) return;
     const size_t wbytes = (size_t)count * pool->ct_words() * 4;
     // (a list in flight from an earlier stream-ordered call is read by its kernel before this copy lands: one stream)
-    int32_t *dslots = static_cast<int32_t *>(scratch(3, (size_t)count * 4));
+    int32_t *dslots = static_cast<int32_t *>(scratch(S_SLOTS, (size_t)count * 4));
     hip_check(hipMemcpyAsync(dslots, stage_slots(slots, count), (size_t)count * 4, hipMemcpyHostToDevice, stream_), "upload slot list");
-    int32_t *dst = on_device ? words : static_cast<int32_t *>(scratch(4, wbytes));
+    int32_t *dst = on_device ? words : static_cast<int32_t *>(scratch(S_WORDS, wbytes));
     launch_gather_slots(stream_, pool->data(), pool->ct_stride(), pool->ct_words(), dslots, count, dst);
     if (!on_device) hip_check(hipMemcpyAsync(words, dst, wbytes, hipMemcpyDeviceToHost, stream_), "download packed words");
     if (wait || !on_device) sync_stream("gather slots");
@@ -644,18 +644,16 @@ BrPlan Engine::plan_br_launch(const DeviceKeyImage *key, int count, bool acc_dum
     return plan;
 }
 
-void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int32_t *pool, const RotDesc *rots, int count,
-                       int32_t *u_buf, int32_t *acc_dbg, hipStream_t stream, const DevKey *mk_keys, const int32_t *mk_rot_keys,
-                       hipEvent_t *mid, const int32_t *luts, const ExtractSpec *specs) {
+void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const BrLaunch &a) {
     ENGINE_DEVICE_SCOPE();
-    if (!stream) stream = stream_;
-    const int form = plan.form, head = count - plan.tail;
-    if (mk_keys && form != BR_FORM_WIDE4 && form != BR_FORM_WAVE8) fatal("launch_br: no multi-key kernel for this form");
-    if (plan.tail && (form != BR_FORM_WIDE4 || acc_dbg)) fatal("launch_br: a tail behind a launch that cannot be split");
+    const hipStream_t stream = a.stream ? a.stream : stream_;
+    const int form = plan.form, head = a.count - plan.tail;
+    if (a.mk_keys && form != BR_FORM_WIDE4 && form != BR_FORM_WAVE8) fatal("launch_br: no multi-key kernel for this form");
+    if (plan.tail && (form != BR_FORM_WIDE4 || a.acc_dbg)) fatal("launch_br: a tail behind a launch that cannot be split");
     DevParams dp = key->dp;
     dp.digit_table = plan.tables;
-    dp.luts = luts ? luts : lut_dev_;
-    dp.specs = specs ? specs : spec_dev_;
+    dp.luts = a.luts ? a.luts : reinterpret_cast<const int32_t *>(g_luts.dev);
+    dp.specs = a.specs ? a.specs : reinterpret_cast<const ExtractSpec *>(g_specs.dev);
     // per-form and per-table-mode launch counters (TfheHipStats): what ran, whatever the tunings asked for
     auto note = [&](int f) {
         ++(f == BR_FORM_WIDE4 ? stats.br_wide4_launches : f == BR_FORM_SPLIT ? stats.br_split_launches
@@ -671,18 +669,18 @@ void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int3
     }
     if (form == BR_FORM_WIDE4 || form == BR_FORM_WAVE8) dp.wg_times = wg_times_dbg_;
     note(form);
-    if (form == BR_FORM_WAVE2) launch_blind_rotate2(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
-    else if (form == BR_FORM_SPLIT) launch_blind_rotate_split(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
-    else if (form == BR_FORM_WAVE8 && mk_keys) launch_blind_rotate8_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, count, u_buf);
-    else if (form == BR_FORM_WAVE8) launch_blind_rotate8(stream, dp, key->key, pool, rots, count, u_buf, acc_dbg);
-    else if (mk_keys) launch_blind_rotate4_mk(stream, dp, key->key, mk_keys, mk_rot_keys, pool, rots, head, u_buf);
-    else launch_blind_rotate4(stream, dp, key->key, pool, rots, head, u_buf, acc_dbg);
+    if (form == BR_FORM_WAVE2) launch_blind_rotate2(stream, dp, key->key, a.pool, a.rots, a.count, a.u_buf, a.acc_dbg);
+    else if (form == BR_FORM_SPLIT) launch_blind_rotate_split(stream, dp, key->key, a.pool, a.rots, a.count, a.u_buf, a.acc_dbg);
+    else if (form == BR_FORM_WAVE8 && a.mk_keys) launch_blind_rotate8_mk(stream, dp, key->key, a.mk_keys, a.mk_rot_keys, a.pool, a.rots, a.count, a.u_buf);
+    else if (form == BR_FORM_WAVE8) launch_blind_rotate8(stream, dp, key->key, a.pool, a.rots, a.count, a.u_buf, a.acc_dbg);
+    else if (a.mk_keys) launch_blind_rotate4_mk(stream, dp, key->key, a.mk_keys, a.mk_rot_keys, a.pool, a.rots, head, a.u_buf);
+    else launch_blind_rotate4(stream, dp, key->key, a.pool, a.rots, head, a.u_buf, a.acc_dbg);
     if (!plan.tail) return;
     // the last round on the 8-wave form, with the event between the two launches where the caller has a reader for it
-    if (mid) { *mid = next_timing_event(); hip_check(hipEventRecord(*mid, stream), "event"); }
+    if (a.mid) { *a.mid = next_timing_event(); hip_check(hipEventRecord(*a.mid, stream), "event"); }
     note(BR_FORM_WAVE8);
-    if (mk_keys) launch_blind_rotate8_mk(stream, dp, key->key, mk_keys, mk_rot_keys + head, pool, rots + head, plan.tail, u_buf);
-    else launch_blind_rotate8(stream, dp, key->key, pool, rots + head, plan.tail, u_buf, nullptr);
+    if (a.mk_keys) launch_blind_rotate8_mk(stream, dp, key->key, a.mk_keys, a.mk_rot_keys + head, a.pool, a.rots + head, plan.tail, a.u_buf);
+    else launch_blind_rotate8(stream, dp, key->key, a.pool, a.rots + head, plan.tail, a.u_buf, nullptr);
 }
 
 static KsShape ks_shape(const DevParams &dp) { return KsShape{dp.k * dp.N, dp.ks_t, dp.ks_basebit, dp.ct_stride}; }
@@ -697,9 +695,9 @@ void Engine::launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const Ks
     const DevParams &dp = key->dp;
     const KsShape shape = ks_shape(dp);
     const size_t bytes = ks_partial_bytes(tunings, cu_count_, count, shape);
-    if (presized && bytes > (scratch_size_.size() > 10 ? scratch_size_[10] : 0))
+    if (presized && bytes > (scratch_size_.size() > S_KS_PARTIAL ? scratch_size_[S_KS_PARTIAL] : 0))
         fatal("launch_ks: the key-switch partial sums were not sized by execute()");
-    int32_t *partial = bytes ? static_cast<int32_t *>(scratch(10, bytes)) : nullptr;
+    int32_t *partial = bytes ? static_cast<int32_t *>(scratch(S_KS_PARTIAL, bytes)) : nullptr;
     const bool tiled = ks_tiled(tunings, count, shape);
     const int chunk = tiled ? KS_CHUNK : count;
     for (int done = 0; done < count; done += chunk) {
@@ -707,6 +705,149 @@ void Engine::launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const Ks
         launch_keyswitch(stream, dp, key->key, u_buf, descs + done, cnt, pool, splits, splits > 1 ? partial : nullptr,
                          tiled ? ks_tile_size(tunings) : 0, tunings.ks_index != 0);
     }
+}
+
+// Step one of a flush, and the only one that can throw or fatal() on a bad plan: the checks of the plan and the sizing of
+// every device buffer the flush uses.  scratch() may reallocate, which must not happen under a running launch -- and it
+// may throw (out of device memory: recoverable_alloc), in which case nothing has been enqueued, the plan is still the
+// caller's, its recorded gates are still pending and its flush returns -1 (recorder.cpp flush_locked releases nothing of
+// the flush before execute() returns).
+Engine::FlushBuffers Engine::prepare_flush(const std::vector<const DeviceKeyImage *> &keys, LevelPlan &plan) {
+    // several keys (recorder "batch_keys"): all of one parameter set, so the descriptors, the extract buffer, the twiddles
+    // and the form rules are those of keys[0]; each rotation and each key switch runs under its own gate's key
+    const DeviceKeyImage *key = keys.at(0);
+    const int nkeys = plan.nkeys;
+    if (nkeys < 1 || (size_t)nkeys != keys.size()) fatal("execute: the plan's key count differs from the flush's key list");
+    // (recorder.cpp select_key keeps keys of another set out of a recording; checked again here, before any launch, because
+    // a key with a larger ring or gadget than keys[0]'s would be read beyond its image and write beyond the extract buffer)
+    for (const DeviceKeyImage *k : keys) {
+        const DevParams &a = key->dp, &b = k->dp;
+        if (a.n != b.n || a.N != b.N || a.k != b.k || a.l != b.l || a.Bgbit != b.Bgbit || a.ks_t != b.ks_t ||
+            a.ks_basebit != b.ks_basebit)
+            fatal("execute: the keys of a multi-key flush differ in a parameter that evaluation reads");
+    }
+    FlushBuffers fb{};
+    fb.rots = static_cast<RotDesc *>(scratch(S_ROTS, plan.rots.size() * sizeof(RotDesc) + 16));
+    fb.ks = static_cast<KsDesc *>(scratch(S_KS, plan.kss.size() * sizeof(KsDesc) + 16));
+    fb.nots = static_cast<NotDesc *>(scratch(S_NOTS, plan.nots.size() * sizeof(NotDesc) + 16));
+    // extract buffer, sized for the widest level, and key-switch partial sums, sized by the split rule launch_ks applies
+    fb.u_buf = static_cast<int32_t *>(scratch(S_EXTRACT, (size_t)(std::max(plan.max_rots, plan.max_extracts) + 1) * key->dp.u_stride * 4));
+    size_t partial = 0;
+    const std::vector<int32_t> &ks_shares = nkeys == 1 ? plan.ks_off : plan.ks_koff;   // one key-switch launch per (level, key)
+    for (size_t sg = 0; sg + 1 < ks_shares.size(); ++sg)
+        partial = std::max(partial, ks_partial_bytes(tunings, cu_count_, ks_shares[sg + 1] - ks_shares[sg], ks_shape(key->dp)));
+    if (partial) (void)scratch(S_KS_PARTIAL, partial);
+    // the key table and the key index of every rotation
+    if (nkeys > 1) {
+        fb.keys = static_cast<DevKey *>(scratch(S_KEYS, (size_t)nkeys * sizeof(DevKey)));
+        fb.rot_keys = static_cast<int32_t *>(scratch(S_ROT_KEYS, plan.rot_key.size() * sizeof(int32_t) + 16));
+        plan.dev_keys.resize((size_t)nkeys);
+        for (int k = 0; k < nkeys; ++k) plan.dev_keys[(size_t)k] = keys[(size_t)k]->key;
+    }
+    // every table entry a rotation names is the engine's, and every output of a multi-output rotation lies inside the
+    // extract buffer sized above
+    uint64_t lut_rots = 0, multi_rots = 0, multi_outs = 0;
+    for (const RotDesc &rd : plan.rots) {
+        if (rd.lut >= 0) {
+            if ((size_t)rd.lut >= g_luts.used) fatal("execute: a rotation names a test polynomial the engine does not hold");
+            ++lut_rots;
+        }
+        if (rd.spec >= 0) {
+            if ((size_t)(rd.spec & XS_ENTRY_MASK) >= g_specs.used) fatal("execute: a rotation names an extract spec the engine does not hold");
+            if (rd.u_index < 0 || rd.u_index + spec_nout_[(size_t)(rd.spec & XS_ENTRY_MASK)] > plan.max_extracts)
+                fatal("execute: a multi-output rotation writes beyond the extract buffer");
+            ++multi_rots;
+            multi_outs += (uint64_t)__builtin_popcount((unsigned)(rd.spec >> XS_WANTED_SHIFT));
+        }
+    }
+    stats.lut_rotations += lut_rots;
+    stats.multi_rotations += multi_rots;
+    stats.multi_outputs += multi_outs;
+    return fb;
+}
+
+// Step two: the plan changes hands and its descriptors and key table go to the device.
+void Engine::upload_flush(const FlushBuffers &fb, LevelPlan &&plan_in) {
+    flight_plan_ = std::move(plan_in);               // owns the host descriptors until the uploads have certainly happened
+    const LevelPlan &plan = flight_plan_;
+    if (!plan.rots.empty())
+        hip_check(hipMemcpyAsync(fb.rots, plan.rots.data(), plan.rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream_), "upload rots");
+    if (!plan.kss.empty())
+        hip_check(hipMemcpyAsync(fb.ks, plan.kss.data(), plan.kss.size() * sizeof(KsDesc), hipMemcpyHostToDevice, stream_), "upload ks");
+    if (!plan.nots.empty())
+        hip_check(hipMemcpyAsync(fb.nots, plan.nots.data(), plan.nots.size() * sizeof(NotDesc), hipMemcpyHostToDevice, stream_), "upload nots");
+    if (plan.nkeys > 1) {
+        hip_check(hipMemcpyAsync(fb.keys, plan.dev_keys.data(), plan.dev_keys.size() * sizeof(DevKey), hipMemcpyHostToDevice, stream_), "upload keys");
+        if (!plan.rot_key.empty())
+            hip_check(hipMemcpyAsync(fb.rot_keys, plan.rot_key.data(), plan.rot_key.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "upload rot keys");
+    }
+}
+
+// Step three, once per level L of flight_plan_ (0: the NOTs riding on the inputs): the blind rotations, the key switches
+// and the NOTs of the level.  shared_end: the previous level's end event where it can serve as this level's start.
+void Engine::run_level(const std::vector<const DeviceKeyImage *> &keys, SlotPool *pool, const FlushBuffers &fb, int L, hipEvent_t &shared_end) {
+    const LevelPlan &plan = flight_plan_;
+    const DeviceKeyImage *key = keys[0];
+    const int nkeys = plan.nkeys;
+    const size_t gg = L > 0 ? (size_t)(L - 1) : 0;       // gate index
+    const int nrot = L > 0 ? plan.rot_off[gg + 1] - plan.rot_off[gg] : 0;
+    const int nks = L > 0 ? plan.ks_off[gg + 1] - plan.ks_off[gg] : 0;
+    const int nnot = plan.not_off[(size_t)L + 1] - plan.not_off[(size_t)L];
+    if (nrot == 0 && nks == 0 && nnot == 0) return;
+    Timed t{nullptr, nullptr, nullptr, false, nrot};
+    // a level's start event is the previous level's end event where nothing was enqueued in between (no NOT launch
+    // behind the key switch): two events per level instead of three -- an event costs the stream a few
+    // microseconds, 1,131 of them 4-15 ms of a match
+    if (kernel_timing) {
+        if (shared_end) t.e0 = shared_end;
+        else { t.e0 = next_timing_event(); hip_check(hipEventRecord(t.e0, stream_), "event"); }
+        shared_end = nullptr;
+    }
+    if (nrot) {
+        // one plan per level, from its total width; the statistics follow from the plan and the launches made
+        const BrPlan bp = plan_br_launch(key, nrot, false);
+        int launches = 0;
+        BrLaunch a{pool->data(), fb.rots + plan.rot_off[gg], nrot, fb.u_buf, nullptr, stream_};
+        if (nkeys == 1 || bp.form == BR_FORM_WIDE4 || bp.form == BR_FORM_WAVE8) {
+            // one launch, two with a tail; several keys: each rotation under its own key through the key table
+            a.mk_keys = fb.keys;
+            a.mk_rot_keys = fb.keys ? fb.rot_keys + plan.rot_off[gg] : nullptr;
+            a.mid = kernel_timing ? &t.em : nullptr;
+            launch_br(key, bp, a);
+            launches = bp.tail ? 2 : 1;
+        } else {
+            // no multi-key kernel for this form: one launch of it per key over that key's contiguous run of the
+            // level's rotations (bp.tail is 0: only the 4-wave form has one)
+            for (int k = 0; k < nkeys; ++k) {
+                const size_t sg = gg * (size_t)nkeys + (size_t)k;
+                a.rots = fb.rots + plan.rot_koff[sg];
+                a.count = plan.rot_koff[sg + 1] - plan.rot_koff[sg];
+                if (!a.count) continue;
+                launch_br(keys[(size_t)k], bp, a);
+                ++launches;
+            }
+        }
+        t.wide8 = bp.form == BR_FORM_WAVE8;
+        t.tail = bp.tail;
+        stats.br_launches += (uint64_t)launches;
+        if (t.wide8 || t.tail) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)(t.wide8 ? nrot : t.tail); }
+    }
+    if (kernel_timing) { t.e1 = next_timing_event(); hip_check(hipEventRecord(t.e1, stream_), "event"); }
+    // the key-switch kernels are single-key: one launch per key with a share of the level
+    for (int k = 0; k < nkeys && nks; ++k) {
+        const size_t sg = gg * (size_t)nkeys + (size_t)k;
+        const int32_t first = nkeys == 1 ? plan.ks_off[gg] : plan.ks_koff[sg];
+        const int n = nkeys == 1 ? nks : plan.ks_koff[sg + 1] - first;
+        if (n) launch_ks(keys[(size_t)k], fb.u_buf, fb.ks + first, n, pool->data(), stream_, true);
+    }
+    if (kernel_timing) {
+        t.e2 = next_timing_event(); hip_check(hipEventRecord(t.e2, stream_), "event"); flight_timed_.push_back(t);
+        if (nnot == 0) shared_end = t.e2;
+    }
+    launch_not(stream_, key->dp, fb.nots + plan.not_off[(size_t)L], nnot, pool->data());
+    stats.blind_rotates += (uint64_t)nrot;
+    stats.keyswitches += (uint64_t)nks;
+    stats.linear_ops += (uint64_t)nnot;
 }
 
 // wait = false: the launches are enqueued and the call returns; the flush is "in flight" until wait_flight() (called by
@@ -717,152 +858,25 @@ void Engine::execute(const std::vector<const DeviceKeyImage *> &keys, SlotPool *
     ENGINE_DEVICE_SCOPE();
     wait_flight();                                   // at most one flush in flight: its descriptors and scratch are in use
     flight_t0_ = std::chrono::steady_clock::now();
-    // several keys (recorder "batch_keys"): all of one parameter set, so the descriptors, the extract buffer, the twiddles
-    // and the form rules are those of keys[0]; each rotation and each key switch runs under its own gate's key
-    const DeviceKeyImage *key = keys.at(0);
-    const int nkeys = plan_in.nkeys;
-    if (nkeys < 1 || (size_t)nkeys != keys.size()) fatal("execute: the plan's key count differs from the flush's key list");
-    // (recorder.cpp select_key keeps keys of another set out of a recording; checked again here, before any launch, because
-    // a key with a larger ring or gadget than keys[0]'s would be read beyond its image and write beyond the extract buffer)
-    for (const DeviceKeyImage *k : keys) {
-        const DevParams &a = key->dp, &b = k->dp;
-        if (a.n != b.n || a.N != b.N || a.k != b.k || a.l != b.l || a.Bgbit != b.Bgbit || a.ks_t != b.ks_t ||
-            a.ks_basebit != b.ks_basebit)
-            fatal("execute: the keys of a multi-key flush differ in a parameter that evaluation reads");
-    }
-    // Every device buffer of the flush is sized here, before anything is enqueued and before the plan changes hands:
-    // scratch() may reallocate, which must not happen under a running launch -- and it may throw (out of device memory:
-    // recoverable_alloc), in which case nothing has run, the caller's recorded gates are still pending and its flush
-    // returns -1 (recorder.cpp flush_locked releases nothing of the flush before this call returns)
-    RotDesc *drots = static_cast<RotDesc *>(scratch(0, plan_in.rots.size() * sizeof(RotDesc) + 16));
-    KsDesc *dks = static_cast<KsDesc *>(scratch(1, plan_in.kss.size() * sizeof(KsDesc) + 16));
-    NotDesc *dnots = static_cast<NotDesc *>(scratch(2, plan_in.nots.size() * sizeof(NotDesc) + 16));
-    // extract buffer, sized for the widest level, and key-switch partial sums, sized by the split rule launch_ks applies
-    int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)(std::max(plan_in.max_rots, plan_in.max_extracts) + 1) * key->dp.u_stride * 4));
-    size_t partial = 0;
-    const std::vector<int32_t> &ks_shares = nkeys == 1 ? plan_in.ks_off : plan_in.ks_koff;   // one key-switch launch per (level, key)
-    for (size_t sg = 0; sg + 1 < ks_shares.size(); ++sg)
-        partial = std::max(partial, ks_partial_bytes(tunings, cu_count_, ks_shares[sg + 1] - ks_shares[sg], ks_shape(key->dp)));
-    if (partial) (void)scratch(10, partial);
-    // the key table and the key index of every rotation
-    DevKey *dkeys = nullptr;
-    int32_t *drot_keys = nullptr;
-    if (nkeys > 1) {
-        dkeys = static_cast<DevKey *>(scratch(11, (size_t)nkeys * sizeof(DevKey)));
-        drot_keys = static_cast<int32_t *>(scratch(12, plan_in.rot_key.size() * sizeof(int32_t) + 16));
-        plan_in.dev_keys.resize((size_t)nkeys);
-        for (int k = 0; k < nkeys; ++k) plan_in.dev_keys[(size_t)k] = keys[(size_t)k]->key;
-    }
-    uint64_t lut_rots = 0;
-    for (const RotDesc &rd : plan_in.rots)
-        if (rd.lut >= 0) {
-            if ((size_t)rd.lut >= lut_used_) fatal("execute: a rotation names a test polynomial the engine does not hold");
-            ++lut_rots;
-        }
-    // multi-output rotations: the spec is the engine's and every output it writes lies inside the extract buffer sized
-    // above (checked here, before anything is enqueued)
-    uint64_t multi_rots = 0, multi_outs = 0;
-    for (const RotDesc &rd : plan_in.rots)
-        if (rd.spec >= 0) {
-            if ((size_t)(rd.spec & XS_ENTRY_MASK) >= spec_used_) fatal("execute: a rotation names an extract spec the engine does not hold");
-            if (rd.u_index < 0 || rd.u_index + spec_nout_[(size_t)(rd.spec & XS_ENTRY_MASK)] > plan_in.max_extracts)
-                fatal("execute: a multi-output rotation writes beyond the extract buffer");
-            ++multi_rots;
-            multi_outs += (uint64_t)__builtin_popcount((unsigned)(rd.spec >> XS_WANTED_SHIFT));
-        }
-    stats.lut_rotations += lut_rots;
-    stats.multi_rotations += multi_rots;
-    stats.multi_outputs += multi_outs;
-    flight_plan_ = std::move(plan_in);               // owns the host descriptors until the uploads have certainly happened
-    const LevelPlan &plan = flight_plan_;
-    const int levels = plan.levels;
-    if (!plan.rots.empty())
-        hip_check(hipMemcpyAsync(drots, plan.rots.data(), plan.rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream_), "upload rots");
-    if (!plan.kss.empty())
-        hip_check(hipMemcpyAsync(dks, plan.kss.data(), plan.kss.size() * sizeof(KsDesc), hipMemcpyHostToDevice, stream_), "upload ks");
-    if (!plan.nots.empty())
-        hip_check(hipMemcpyAsync(dnots, plan.nots.data(), plan.nots.size() * sizeof(NotDesc), hipMemcpyHostToDevice, stream_), "upload nots");
-    if (nkeys > 1) {
-        hip_check(hipMemcpyAsync(dkeys, plan.dev_keys.data(), plan.dev_keys.size() * sizeof(DevKey), hipMemcpyHostToDevice, stream_), "upload keys");
-        if (!plan.rot_key.empty())
-            hip_check(hipMemcpyAsync(drot_keys, plan.rot_key.data(), plan.rot_key.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "upload rot keys");
-    }
-    last_flush_keys = nkeys;
-
-    timing_used_ = 0;                                    // timing events used: base, then 2-3 (one more with a tail launch) per level
-    auto timing_event = [&]() { return next_timing_event(); };
-    std::vector<Timed> &timed = flight_timed_;
-    timed.clear();
-    hipEvent_t &base = flight_base_;
-    base = nullptr;
+    const FlushBuffers fb = prepare_flush(keys, plan_in);
+    upload_flush(fb, std::move(plan_in));
+    const int levels = flight_plan_.levels;
+    last_flush_keys = flight_plan_.nkeys;
+    timing_used_ = 0;                                // timing events used: base, then 2-3 (one more with a tail launch) per level
+    flight_timed_.clear();
+    flight_base_ = nullptr;
     if (kernel_timing) {
-        base = timing_event();
-        hip_check(hipEventRecord(base, stream_), "event");
-        timed.reserve((size_t)levels + 1);
+        flight_base_ = next_timing_event();
+        hip_check(hipEventRecord(flight_base_, stream_), "event");
+        flight_timed_.reserve((size_t)levels + 1);
     }
     hipEvent_t shared_end = nullptr;
-    for (int L = 0; L <= levels; ++L) {
-        const size_t gg = L > 0 ? (size_t)(L - 1) : 0;       // gate index
-        const int nrot = L > 0 ? plan.rot_off[gg + 1] - plan.rot_off[gg] : 0;
-        const int nks = L > 0 ? plan.ks_off[gg + 1] - plan.ks_off[gg] : 0;
-        const int nnot = plan.not_off[(size_t)L + 1] - plan.not_off[(size_t)L];
-        if (nrot == 0 && nks == 0 && nnot == 0) continue;
-        Timed t{nullptr, nullptr, nullptr, false, nrot};
-        // a level's start event is the previous level's end event where nothing was enqueued in between (no NOT launch
-        // behind the key switch): two events per level instead of three -- an event costs the stream a few
-        // microseconds, 1,131 of them 4-15 ms of a match
-        if (kernel_timing) {
-            if (shared_end) t.e0 = shared_end;
-            else { t.e0 = timing_event(); hip_check(hipEventRecord(t.e0, stream_), "event"); }
-            shared_end = nullptr;
-        }
-        if (nrot) {
-            // one plan per level, from its total width; the statistics follow from the plan and the launches made
-            const BrPlan bp = plan_br_launch(key, nrot, false);
-            int launches = 0;
-            if (nkeys == 1 || bp.form == BR_FORM_WIDE4 || bp.form == BR_FORM_WAVE8) {
-                // one launch, two with a tail; several keys: each rotation under its own key through the key table
-                launch_br(key, bp, pool->data(), drots + plan.rot_off[gg], nrot, u_buf, nullptr, stream_, dkeys,
-                          dkeys ? drot_keys + plan.rot_off[gg] : nullptr, kernel_timing ? &t.em : nullptr);
-                launches = bp.tail ? 2 : 1;
-            } else {
-                // no multi-key kernel for this form: one launch of it per key over that key's contiguous run of the
-                // level's rotations (bp.tail is 0: only the 4-wave form has one)
-                for (int k = 0; k < nkeys; ++k) {
-                    const size_t sg = gg * (size_t)nkeys + (size_t)k;
-                    const int n = plan.rot_koff[sg + 1] - plan.rot_koff[sg];
-                    if (!n) continue;
-                    launch_br(keys[(size_t)k], bp, pool->data(), drots + plan.rot_koff[sg], n, u_buf, nullptr, stream_);
-                    ++launches;
-                }
-            }
-            t.wide8 = bp.form == BR_FORM_WAVE8;
-            t.tail = bp.tail;
-            stats.br_launches += (uint64_t)launches;
-            if (t.wide8 || t.tail) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)(t.wide8 ? nrot : t.tail); }
-        }
-        if (kernel_timing) { t.e1 = timing_event(); hip_check(hipEventRecord(t.e1, stream_), "event"); }
-        // the key-switch kernels are single-key: one launch per key with a share of the level
-        for (int k = 0; k < nkeys && nks; ++k) {
-            const size_t sg = gg * (size_t)nkeys + (size_t)k;
-            const int32_t first = nkeys == 1 ? plan.ks_off[gg] : plan.ks_koff[sg];
-            const int n = nkeys == 1 ? nks : plan.ks_koff[sg + 1] - first;
-            if (n) launch_ks(keys[(size_t)k], u_buf, dks + first, n, pool->data(), stream_, true);
-        }
-        if (kernel_timing) {
-            t.e2 = timing_event(); hip_check(hipEventRecord(t.e2, stream_), "event"); timed.push_back(t);
-            if (nnot == 0) shared_end = t.e2;
-        }
-        launch_not(stream_, key->dp, dnots + plan.not_off[(size_t)L], nnot, pool->data());
-        stats.blind_rotates += (uint64_t)nrot;
-        stats.keyswitches += (uint64_t)nks;
-        stats.linear_ops += (uint64_t)nnot;
-    }
+    for (int L = 0; L <= levels; ++L) run_level(keys, pool, fb, L, shared_end);
     if (const char *trace = std::getenv("TFHE_HIP_TRACE_LEVELS")) {   // diagnostic: rotations per level
         if (FILE *f = std::fopen(trace, "a")) {
             std::fprintf(f, "flush levels=%d lanes=1\n", levels);
             for (int L = 1; L <= levels; ++L)
-                std::fprintf(f, "%d 0 %d\n", L, plan.rot_off[(size_t)L] - plan.rot_off[(size_t)L - 1]);
+                std::fprintf(f, "%d 0 %d\n", L, flight_plan_.rot_off[(size_t)L] - flight_plan_.rot_off[(size_t)L - 1]);
             std::fclose(f);
         }
     }
@@ -938,108 +952,67 @@ void Engine::wait_flight() {
     flight_plan_ = LevelPlan{};
 }
 
-
-void Engine::run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, Torus32 *u_out, Torus32 *acc_out,
-                                const int32_t *lut_index, const Torus32 *polys, int npolys) {
+void Engine::run_raw_rotations(const DeviceKeyImage *key, const Torus32 *lin, int count, const int32_t *lut_index,
+                               const Torus32 *polys, int npolys, const int32_t *spec_index, const ExtractSpec *specs, int nspecs,
+                               int out_rows, Torus32 *u_out, Torus32 *acc_out, const char *name) {
     ENGINE_DEVICE_SCOPE();
     wait_flight();
     const DevParams &dp = key->dp;
-    // the call's own table of test polynomials, laid out like the engine's
-    int32_t *dluts = nullptr;
-    std::vector<int32_t> table;
-    if (lut_index) {
-        for (int c = 0; c < count; ++c)
-            if (lut_index[c] >= npolys) api_fail("lut_bootstrap_woks: a LUT index beyond the table");
-        table.assign((size_t)std::max(npolys, 1) * LUT_STRIDE, 0);
-        for (int t = 0; t < npolys; ++t) std::memcpy(&table[(size_t)t * LUT_STRIDE], polys + (size_t)t * dp.N, (size_t)dp.N * 4);
-        dluts = static_cast<int32_t *>(scratch(13, table.size() * 4));
-        hip_check(hipMemcpyAsync(dluts, table.data(), table.size() * 4, hipMemcpyHostToDevice, stream_), "upload LUTs");
-    }
-    // temporary "pool": count slots holding lin
-    std::vector<int32_t> padded((size_t)count * dp.ct_stride, 0);
-    for (int c = 0; c < count; ++c)
-        std::memcpy(&padded[(size_t)c * dp.ct_stride], lin + (size_t)c * (dp.n + 1), (size_t)(dp.n + 1) * 4);
-    int32_t *dpool = static_cast<int32_t *>(scratch(6, padded.size() * 4));
-    hip_check(hipMemcpyAsync(dpool, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, stream_), "upload lin");
-    std::vector<RotDesc> rots(count);
+    const std::string who = std::string(name) + ": ";
     for (int c = 0; c < count; ++c) {
-        rots[c] = RotDesc{c, c, 1, 0, 0, c};
-        if (lut_index && lut_index[c] >= 0) { rots[c].lut = lut_index[c]; ++stats.lut_rotations; }
-    }
-    RotDesc *drots = static_cast<RotDesc *>(scratch(0, rots.size() * sizeof(RotDesc)));
-    hip_check(hipMemcpyAsync(drots, rots.data(), rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream_), "upload rots");
-    int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)count * dp.u_stride * 4));
-    int32_t *dacc = acc_out ? static_cast<int32_t *>(scratch(7, (size_t)count * 2 * dp.N * 4)) : nullptr;
-    launch_br(key, plan_br_launch(key, count, dacc != nullptr), dpool, drots, count, u_buf, dacc, nullptr, nullptr, nullptr,
-              nullptr, dluts);
-    hip_check(hipGetLastError(), "blind_rotate launch");
-    std::vector<int32_t> ubuf((size_t)count * dp.u_stride);
-    hip_check(hipMemcpyAsync(ubuf.data(), u_buf, ubuf.size() * 4, hipMemcpyDeviceToHost, stream_), "download u");
-    if (acc_out) hip_check(hipMemcpyAsync(acc_out, dacc, (size_t)count * 2 * dp.N * 4, hipMemcpyDeviceToHost, stream_), "download acc");
-    sync_stream("bootstrap_woks");
-    for (int c = 0; c < count; ++c)
-        std::memcpy(u_out + (size_t)c * (dp.k * dp.N + 1), &ubuf[(size_t)c * dp.u_stride], (size_t)(dp.k * dp.N + 1) * 4);
-    stats.blind_rotates += (uint64_t)count;
-}
-
-void Engine::run_bootstrap_multi_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, const int32_t *lut_index,
-                                      const Torus32 *polys, int npolys, const int32_t *spec_index, const ExtractSpec *specs,
-                                      int nspecs, Torus32 *u_out, Torus32 *acc_out) {
-    ENGINE_DEVICE_SCOPE();
-    wait_flight();
-    const DevParams &dp = key->dp;
-    for (int c = 0; c < count; ++c) {
-        if (lut_index[c] >= npolys) api_fail("lut_bootstrap_multi_woks: a LUT index beyond the table");
-        if (spec_index[c] >= nspecs) api_fail("lut_bootstrap_multi_woks: a spec index beyond the table");
+        if (lut_index && lut_index[c] >= npolys) api_fail(who + "a LUT index beyond the table");
+        if (spec_index && spec_index[c] >= nspecs) api_fail(who + "a spec index beyond the table");
     }
     for (int t = 0; t < nspecs; ++t)
-        if (const char *why = extract_spec_error(specs[t], dp.N)) api_fail(std::string("lut_bootstrap_multi_woks: ") + why);
-    // the call's own tables, laid out like the engine's
-    std::vector<int32_t> table((size_t)std::max(npolys, 1) * LUT_STRIDE, 0);
-    for (int t = 0; t < npolys; ++t) std::memcpy(&table[(size_t)t * LUT_STRIDE], polys + (size_t)t * dp.N, (size_t)dp.N * 4);
-    int32_t *dluts = static_cast<int32_t *>(scratch(13, table.size() * 4));
-    hip_check(hipMemcpyAsync(dluts, table.data(), table.size() * 4, hipMemcpyHostToDevice, stream_), "upload LUTs");
-    ExtractSpec *dspecs = static_cast<ExtractSpec *>(scratch(14, (size_t)std::max(nspecs, 1) * sizeof(ExtractSpec)));
-    if (nspecs) hip_check(hipMemcpyAsync(dspecs, specs, (size_t)nspecs * sizeof(ExtractSpec), hipMemcpyHostToDevice, stream_), "upload specs");
-    std::vector<int32_t> padded((size_t)count * dp.ct_stride, 0);
-    for (int c = 0; c < count; ++c)
-        std::memcpy(&padded[(size_t)c * dp.ct_stride], lin + (size_t)c * (dp.n + 1), (size_t)(dp.n + 1) * 4);
-    int32_t *dpool = static_cast<int32_t *>(scratch(6, padded.size() * 4));
+        if (const char *why = extract_spec_error(specs[t], dp.N)) api_fail(who + why);
+    // the call's own tables, laid out like the engine's (without one: the engine's, which no descriptor here names)
+    BrLaunch a{};
+    std::vector<int32_t> table;
+    if (lut_index) {
+        table = pad_rows(polys, (size_t)npolys, (size_t)dp.N, LUT_STRIDE);
+        int32_t *dluts = static_cast<int32_t *>(scratch(S_RAW_LUTS, table.size() * 4));
+        hip_check(hipMemcpyAsync(dluts, table.data(), table.size() * 4, hipMemcpyHostToDevice, stream_), "upload LUTs");
+        a.luts = dluts;
+    }
+    if (spec_index) {
+        ExtractSpec *dspecs = static_cast<ExtractSpec *>(scratch(S_RAW_SPECS, (size_t)nspecs * sizeof(ExtractSpec)));
+        hip_check(hipMemcpyAsync(dspecs, specs, (size_t)nspecs * sizeof(ExtractSpec), hipMemcpyHostToDevice, stream_), "upload specs");
+        a.specs = dspecs;
+    }
+    // temporary "pool": count slots holding lin
+    const std::vector<int32_t> padded = pad_rows(lin, (size_t)count, (size_t)dp.n + 1, (size_t)dp.ct_stride);
+    int32_t *dpool = static_cast<int32_t *>(scratch(S_RAW_POOL, padded.size() * 4));
     hip_check(hipMemcpyAsync(dpool, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, stream_), "upload lin");
-    // u_index: the outputs of the combinations before this one
+    // u_index: the outputs of the combinations before this one (a combination without a spec has one)
     std::vector<RotDesc> rots(count);
-    std::vector<int32_t> first(count);
     int32_t total = 0;
     for (int c = 0; c < count; ++c) {
         rots[c] = RotDesc{c, c, 1, 0, 0, total};
-        first[c] = total;
-        if (lut_index[c] >= 0) { rots[c].lut = lut_index[c]; ++stats.lut_rotations; }
-        if (spec_index[c] >= 0) {
-            const int nout = specs[spec_index[c]].nout;
+        if (lut_index && lut_index[c] >= 0) { rots[c].lut = lut_index[c]; ++stats.lut_rotations; }
+        int nout = 1;
+        if (spec_index && spec_index[c] >= 0) {
+            nout = specs[spec_index[c]].nout;
             rots[c].spec = spec_index[c] | ((1 << nout) - 1) << XS_WANTED_SHIFT;
-            total += nout;
             ++stats.multi_rotations;
             stats.multi_outputs += (uint64_t)nout;
-        } else {
-            ++total;
         }
+        total += nout;
     }
-    RotDesc *drots = static_cast<RotDesc *>(scratch(0, rots.size() * sizeof(RotDesc)));
+    RotDesc *drots = static_cast<RotDesc *>(scratch(S_ROTS, rots.size() * sizeof(RotDesc)));
     hip_check(hipMemcpyAsync(drots, rots.data(), rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream_), "upload rots");
-    int32_t *u_buf = static_cast<int32_t *>(scratch(5, (size_t)(total + 1) * dp.u_stride * 4));
-    int32_t *dacc = acc_out ? static_cast<int32_t *>(scratch(7, (size_t)count * 2 * dp.N * 4)) : nullptr;
-    launch_br(key, plan_br_launch(key, count, dacc != nullptr), dpool, drots, count, u_buf, dacc, nullptr, nullptr, nullptr,
-              nullptr, dluts, dspecs);
+    a.pool = dpool; a.rots = drots; a.count = count;
+    a.u_buf = static_cast<int32_t *>(scratch(S_EXTRACT, (size_t)(total + 1) * dp.u_stride * 4));
+    a.acc_dbg = acc_out ? static_cast<int32_t *>(scratch(S_RAW_ACC, (size_t)count * 2 * dp.N * 4)) : nullptr;
+    launch_br(key, plan_br_launch(key, count, a.acc_dbg != nullptr), a);
     hip_check(hipGetLastError(), "blind_rotate launch");
     std::vector<int32_t> ubuf((size_t)total * dp.u_stride);
-    hip_check(hipMemcpyAsync(ubuf.data(), u_buf, ubuf.size() * 4, hipMemcpyDeviceToHost, stream_), "download u");
-    if (acc_out) hip_check(hipMemcpyAsync(acc_out, dacc, (size_t)count * 2 * dp.N * 4, hipMemcpyDeviceToHost, stream_), "download acc");
-    sync_stream("bootstrap_multi_woks");
+    hip_check(hipMemcpyAsync(ubuf.data(), a.u_buf, ubuf.size() * 4, hipMemcpyDeviceToHost, stream_), "download u");
+    if (acc_out) hip_check(hipMemcpyAsync(acc_out, a.acc_dbg, (size_t)count * 2 * dp.N * 4, hipMemcpyDeviceToHost, stream_), "download acc");
+    sync_stream(name);
     const size_t uw = (size_t)dp.k * dp.N + 1;
     for (int c = 0; c < count; ++c) {
-        const int nout = spec_index[c] >= 0 ? specs[spec_index[c]].nout : 1;
-        for (int m = 0; m < nout; ++m)
-            std::memcpy(u_out + ((size_t)c * XS_MAX_OUT + m) * uw, &ubuf[(size_t)(first[c] + m) * dp.u_stride], uw * 4);
+        const size_t nout = (size_t)((c + 1 < count ? rots[c + 1].u_index : total) - rots[c].u_index);
+        unpad_rows(u_out + (size_t)c * out_rows * uw, &ubuf[(size_t)rots[c].u_index * dp.u_stride], nout, uw, (size_t)dp.u_stride);
     }
     stats.blind_rotates += (uint64_t)count;
 }
@@ -1048,22 +1021,20 @@ void Engine::run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int coun
     ENGINE_DEVICE_SCOPE();
     wait_flight();
     const DevParams &dp = key->dp;
-    const int uw = dp.k * dp.N + 1;
-    std::vector<int32_t> padded((size_t)count * dp.u_stride, 0);
-    for (int c = 0; c < count; ++c) std::memcpy(&padded[(size_t)c * dp.u_stride], u + (size_t)c * uw, (size_t)uw * 4);
-    int32_t *u_buf = static_cast<int32_t *>(scratch(5, padded.size() * 4));
+    const std::vector<int32_t> padded = pad_rows(u, (size_t)count, (size_t)dp.k * dp.N + 1, (size_t)dp.u_stride);
+    int32_t *u_buf = static_cast<int32_t *>(scratch(S_EXTRACT, padded.size() * 4));
     hip_check(hipMemcpyAsync(u_buf, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, stream_), "upload u");
     std::vector<KsDesc> ks(count);
     for (int c = 0; c < count; ++c) ks[c] = KsDesc{c, -1, 0, c};
-    KsDesc *dks = static_cast<KsDesc *>(scratch(1, ks.size() * sizeof(KsDesc)));
+    KsDesc *dks = static_cast<KsDesc *>(scratch(S_KS, ks.size() * sizeof(KsDesc)));
     hip_check(hipMemcpyAsync(dks, ks.data(), ks.size() * sizeof(KsDesc), hipMemcpyHostToDevice, stream_), "upload ks");
-    int32_t *dpool = static_cast<int32_t *>(scratch(6, (size_t)count * dp.ct_stride * 4));
+    int32_t *dpool = static_cast<int32_t *>(scratch(S_RAW_POOL, (size_t)count * dp.ct_stride * 4));
     launch_ks(key, u_buf, dks, count, dpool);
     hip_check(hipGetLastError(), "keyswitch launch");
     std::vector<int32_t> res((size_t)count * dp.ct_stride);
     hip_check(hipMemcpyAsync(res.data(), dpool, res.size() * 4, hipMemcpyDeviceToHost, stream_), "download ks");
     sync_stream("keyswitch");
-    for (int c = 0; c < count; ++c) std::memcpy(out + (size_t)c * (dp.n + 1), &res[(size_t)c * dp.ct_stride], (size_t)(dp.n + 1) * 4);
+    unpad_rows(out, res.data(), (size_t)count, (size_t)dp.n + 1, (size_t)dp.ct_stride);
     stats.keyswitches += (uint64_t)count;
 }
 
@@ -1076,14 +1047,14 @@ double Engine::run_wg_times(const DeviceKeyImage *key, int width, unsigned long 
     std::vector<int32_t> host((size_t)width * dp.ct_stride);
     uint64_t x = 0x9E3779B97F4A7C15ull;
     for (auto &w : host) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; w = (int32_t)(x >> 16); }
-    int32_t *pool = static_cast<int32_t *>(scratch(40, (size_t)width * dp.ct_stride * 4));
+    int32_t *pool = static_cast<int32_t *>(scratch(S_PROBE_POOL, (size_t)width * dp.ct_stride * 4));
     hip_check(hipMemcpy(pool, host.data(), host.size() * 4, hipMemcpyHostToDevice), "probe pool");
     std::vector<RotDesc> rots(width);
     for (int i = 0; i < width; ++i) rots[i] = RotDesc{i, (i + 1) % width, 1, 1, -dp.mu, i};
-    RotDesc *drots = static_cast<RotDesc *>(scratch(41, rots.size() * sizeof(RotDesc)));
+    RotDesc *drots = static_cast<RotDesc *>(scratch(S_PROBE_ROTS, rots.size() * sizeof(RotDesc)));
     hip_check(hipMemcpy(drots, rots.data(), rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice), "probe rots");
-    int32_t *ubuf = static_cast<int32_t *>(scratch(50, (size_t)(width + 1) * dp.u_stride * 4));
-    unsigned long long *dtimes = static_cast<unsigned long long *>(scratch(43, (size_t)4 * width * 8));
+    int32_t *ubuf = static_cast<int32_t *>(scratch(S_PROBE_EXTRACT, (size_t)(width + 1) * dp.u_stride * 4));
+    unsigned long long *dtimes = static_cast<unsigned long long *>(scratch(S_PROBE_TIMES, (size_t)4 * width * 8));
     hipStream_t st;
     hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "probe stream");
     hipEvent_t e0, e1;
@@ -1094,12 +1065,14 @@ double Engine::run_wg_times(const DeviceKeyImage *key, int width, unsigned long 
     int warm_count = 1, warm_width = width;
     if (const char *env = std::getenv("TFHE_HIP_PROBE_WARM")) std::sscanf(env, "%d:%d", &warm_count, &warm_width);
     warm_width = std::max(1, std::min(warm_width, width));
-    for (int w = 0; w < warm_count; ++w) launch_br(key, plan_br_launch(key, warm_width, false), pool, drots, warm_width, ubuf, nullptr, st);
+    BrLaunch a{pool, drots, warm_width, ubuf, nullptr, st};
+    for (int w = 0; w < warm_count; ++w) launch_br(key, plan_br_launch(key, warm_width, false), a);
     // cleared first so that a launch which wrote no stamps is noticed instead of read as timings
     hip_check(hipMemsetAsync(dtimes, 0, (size_t)4 * width * 8, st), "clear stamps");
     wg_times_dbg_ = dtimes;
     hip_check(hipEventRecord(e0, st), "probe event record");
-    launch_br(key, plan_br_launch(key, width, false), pool, drots, width, ubuf, nullptr, st);
+    a.count = width;
+    launch_br(key, plan_br_launch(key, width, false), a);
     hip_check(hipEventRecord(e1, st), "probe event record");
     hip_check(hipStreamSynchronize(st), "probe stamps");
     wg_times_dbg_ = nullptr;
@@ -1121,10 +1094,10 @@ void Engine::run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const 
     const size_t words = (size_t)count * dp.N;
     uint32_t scale[2];
     (void)make_twiddles(dp.N, scale);
-    int32_t *dtp = static_cast<int32_t *>(scratch(6, words * 4));
-    int32_t *dip = static_cast<int32_t *>(scratch(7, words * 4));
-    uint32_t *dimg = static_cast<uint32_t *>(scratch(8, words * 2 * 4));
-    int32_t *dres = static_cast<int32_t *>(scratch(9, words * 4));
+    int32_t *dtp = static_cast<int32_t *>(scratch(S_NEGA_TP, words * 4));
+    int32_t *dip = static_cast<int32_t *>(scratch(S_NEGA_IP, words * 4));
+    uint32_t *dimg = static_cast<uint32_t *>(scratch(S_NEGA_IMG, words * 2 * 4));
+    int32_t *dres = static_cast<int32_t *>(scratch(S_NEGA_RES, words * 4));
     hip_check(hipMemcpyAsync(dtp, tp, words * 4, hipMemcpyHostToDevice, stream_), "upload tp");
     hip_check(hipMemcpyAsync(dip, ip, words * 4, hipMemcpyHostToDevice, stream_), "upload ip");
     launch_bk_transform(stream_, dp, dtp, dimg, key->tw, count, 1, scale);

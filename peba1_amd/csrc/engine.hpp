@@ -142,24 +142,20 @@ public:
     // gives the entry back -- the caller has run every recorded op that names it (recorder.cpp forget_lut_locked).
     int32_t lut_add(const Torus32 *words, int n_ring);
     void lut_free(int32_t index);
-    size_t lut_capacity() const { return lut_cap_; }
-    // The table of extract specs (tfhe_hip_new_lut_multi), managed like the table of test polynomials: one device array of
-    // ExtractSpec that doubles on demand, entries reused after spec_free; RotDesc::spec indexes it.  The spec has passed
-    // extract_spec_error for its ring.
+    // The table of extract specs (tfhe_hip_new_lut_multi), the same mechanism (engine.cpp DeviceTable) over ExtractSpec
+    // entries; RotDesc::spec indexes it.  The spec has passed extract_spec_error for its ring.
     int32_t spec_add(const ExtractSpec &xs);
     void spec_free(int32_t index);
-    size_t spec_capacity() const { return spec_cap_; }
-    // raw test paths.  lut_index / polys (both or neither): combination c starts from test polynomial lut_index[c] of
-    // polys[npolys][N] (uploaded for this call only; an index below 0: the constant test vector)
-    void run_bootstrap_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, Torus32 *u_out, Torus32 *acc_out,
-                            const int32_t *lut_index = nullptr, const Torus32 *polys = nullptr, int npolys = 0);
-    // the same with extract specs: combination c leaves through specs[spec_index[c]] (uploaded for this call only, every
-    // output wanted; an index below 0: the extract at index 0).  The device writes the outputs of all combinations back
-    // to back (u_index = outputs before it); u_out[count][XS_MAX_OUT][kN+1] receives output m of combination c at
-    // [c][m], the rest is left as it was
-    void run_bootstrap_multi_woks(const DeviceKeyImage *key, const Torus32 *lin, int count, const int32_t *lut_index,
-                                  const Torus32 *polys, int npolys, const int32_t *spec_index, const ExtractSpec *specs,
-                                  int nspecs, Torus32 *u_out, Torus32 *acc_out);
+    // raw test paths.  The one blind-rotate path of the three *bootstrap*_woks entries: `count` combinations of lin through
+    // one planned launch from call-owned tables.  lut_index / polys / npolys (all or none): combination c starts from test
+    // polynomial lut_index[c] of polys[npolys][N] (uploaded for this call only; an index below 0: the constant test
+    // vector).  spec_index / specs / nspecs (all or none): it leaves through specs[spec_index[c]] (uploaded for this call
+    // only, every output wanted; an index below 0, or no specs: the extract at index 0).  The device writes the outputs of
+    // all combinations back to back (u_index = outputs before it); u_out[count][out_rows][kN+1] receives output m of
+    // combination c at [c][m], the rest is left as it was.  name: the entry, for error messages
+    void run_raw_rotations(const DeviceKeyImage *key, const Torus32 *lin, int count, const int32_t *lut_index,
+                           const Torus32 *polys, int npolys, const int32_t *spec_index, const ExtractSpec *specs, int nspecs,
+                           int out_rows, Torus32 *u_out, Torus32 *acc_out, const char *name);
     void run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out);
     void run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const Torus32 *tp, Torus32 *res, int count);
 
@@ -167,29 +163,66 @@ public:
     bool kernel_timing = false;
     // the launch rules' tunings (launch_plan.hpp; written by ensure_init()'s environment reads and tfhe_hip_set_tuning)
     LaunchTunings tunings;
-    // stream == nullptr: the engine's stream; presized (execute()'s levels): the partial sums were sized by the caller
+    // stream == nullptr: the engine's stream; presized (a flush's levels): the partial sums were sized by the caller
     // and must not grow (checked)
     void launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
                    hipStream_t stream = nullptr, bool presized = false);
     // the launch plan (launch_plan.hpp plan_br) of `count` rotations under this key's parameter set on this card;
     // acc_dump: the raw accumulators are read back
     BrPlan plan_br_launch(const DeviceKeyImage *key, int count, bool acc_dump) const;
-    // runs a plan of plan_br_launch on these descriptors: one kernel launch, two with a tail; decides nothing.
-    // mk_keys / mk_rot_keys (device key table and per-rotation key indices of a multi-key level): the 4- and 8-wave
-    // forms run each rotation under its own key; only for those forms, and `key` is entry 0 of the table.  mid: where
-    // the event between the two launches of a plan with a tail goes (kernel timing of a flush), or null
-    // luts: the test-polynomial table the descriptors' lut indices refer to; null = the engine's own
-    void launch_br(const DeviceKeyImage *key, const BrPlan &plan, const int32_t *pool, const RotDesc *rots, int count,
-                   int32_t *u_buf, int32_t *acc_dbg, hipStream_t stream = nullptr, const DevKey *mk_keys = nullptr,
-                   const int32_t *mk_rot_keys = nullptr, hipEvent_t *mid = nullptr, const int32_t *luts = nullptr,
-                   const ExtractSpec *specs = nullptr);     // specs: likewise for the descriptors' extract specs
+    // What one blind-rotate launch works on.  mk_keys / mk_rot_keys (device key table and per-rotation key indices of a
+    // multi-key level): the 4- and 8-wave forms run each rotation under its own key; only for those forms, and `key` is
+    // entry 0 of the table.  mid: where the event between the two launches of a plan with a tail goes (kernel timing of a
+    // flush).  luts / specs: the tables the descriptors' lut and spec indices refer to; null = the engine's own
+    struct BrLaunch {
+        const int32_t *pool;
+        const RotDesc *rots;
+        int count;
+        int32_t *u_buf;
+        int32_t *acc_dbg = nullptr;
+        hipStream_t stream = nullptr;            // null: the engine's stream
+        const DevKey *mk_keys = nullptr;
+        const int32_t *mk_rot_keys = nullptr;
+        hipEvent_t *mid = nullptr;
+        const int32_t *luts = nullptr;
+        const ExtractSpec *specs = nullptr;
+    };
+    // runs a plan of plan_br_launch on these descriptors: one kernel launch, two with a tail; decides nothing
+    void launch_br(const DeviceKeyImage *key, const BrPlan &plan, const BrLaunch &a);
     // diagnostic (tools/wg_times.py): ONE 4-wave blind-rotate launch of `width` random gates whose workgroups stamp s_memtime
     // and s_memrealtime at start and end into wg_times[4 * width]; returns that launch's event time in ms (< 0: no stamps)
     double run_wg_times(const DeviceKeyImage *key, int width, unsigned long long *wg_times);
 
 private:
     Engine() = default;
-    void *scratch(size_t idx, size_t bytes);   // grow-only device scratch buffers
+    // The grow-only device scratch buffers, by name.  "flush": sized by prepare_flush() and owned by the flush in flight
+    // until wait_flight().  "raw": sized and used by a raw test path, which waits for the flight first and for its own
+    // work before it returns.  "io": sized by write_/read_slots_packed, used on the stream behind any flight.
+    enum Scratch : size_t {
+        S_ROTS,           // flush, raw rotations: the rotation descriptors
+        S_KS,             // flush, run_keyswitch: the key-switch descriptors
+        S_NOTS,           // flush: the descriptors of the linear ops
+        S_SLOTS,          // io: the slot list of a packed transfer
+        S_WORDS,          // io: the packed words of a host transfer
+        S_EXTRACT,        // flush, raw rotations, run_keyswitch: the extracted samples
+        S_RAW_POOL,       // raw rotations: the padded inputs; run_keyswitch: the padded results
+        S_RAW_ACC,        // raw rotations: the accumulators read back
+        S_NEGA_TP = S_RAW_POOL, S_NEGA_IP = S_RAW_ACC,     // run_negacyclic's two operands share those buffers
+        S_NEGA_IMG,       // raw, run_negacyclic: the transform of tp
+        S_NEGA_RES,       // raw, run_negacyclic: the products
+        S_KS_PARTIAL,     // flush (launch_ks checks that it never grows under one), run_keyswitch: partial sums of split key switches
+        S_KEYS,           // flush of several keys: the key table
+        S_ROT_KEYS,       // flush of several keys: the key index of every rotation
+        S_RAW_LUTS,       // raw rotations: the call's own test polynomials
+        S_RAW_SPECS,      // raw rotations: the call's own extract specs
+        S_PROBE_POOL, S_PROBE_ROTS, S_PROBE_TIMES, S_PROBE_EXTRACT,     // run_wg_times only (it waits for the flight first)
+    };
+    void *scratch(Scratch idx, size_t bytes);
+    // execute() in three steps (engine.cpp): everything that can throw, then the uploads, then one call per level
+    struct FlushBuffers { RotDesc *rots; KsDesc *ks; NotDesc *nots; int32_t *u_buf; DevKey *keys; int32_t *rot_keys; };
+    FlushBuffers prepare_flush(const std::vector<const DeviceKeyImage *> &keys, LevelPlan &plan);
+    void upload_flush(const FlushBuffers &fb, LevelPlan &&plan);
+    void run_level(const std::vector<const DeviceKeyImage *> &keys, SlotPool *pool, const FlushBuffers &fb, int L, hipEvent_t &shared_end);
     // em / tail: a level whose last round went to the 8-wave form as a second launch (BrPlan::tail) -- the event between
     // the two launches and the rotations of the second, so that each kernel's time and count stay its own
     struct Timed { hipEvent_t e0, e1, e2; bool wide8; int nrot; hipEvent_t em = nullptr; int tail = 0; };
@@ -214,13 +247,6 @@ private:
     size_t timing_used_ = 0;
     hipEvent_t next_timing_event();
     std::vector<hipEvent_t> timing_events_;             // kernel_timing: up to 3 per level + 1 base
-    hipEvent_t ev_[3] = {nullptr, nullptr, nullptr};
-    int32_t *lut_dev_ = nullptr;                        // [lut_cap_][LUT_STRIDE]
-    size_t lut_cap_ = 0, lut_used_ = 0;                 // entries allocated / ever handed out
-    std::vector<int32_t> lut_free_;
-    ExtractSpec *spec_dev_ = nullptr;                   // [spec_cap_]
-    size_t spec_cap_ = 0, spec_used_ = 0;
-    std::vector<int32_t> spec_free_;
     std::vector<int32_t> spec_nout_;                    // outputs of every entry (execute() checks the extract buffer with it)
     std::vector<SlotPool *> pools_;
     std::vector<void *> scratch_ptr_;

@@ -1113,7 +1113,7 @@ int tfhe_hip_kernel_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *bk, c
     if (!bk || !bk->bk) { set_error("bootstrap_woks: null keyset"); return -1; }
     auto g = recorder_lock();
     pool_of_key(bk);
-    Engine::get().run_bootstrap_woks(bk->bk->dev, lin, count, u_out, acc_out);
+    Engine::get().run_raw_rotations(bk->bk->dev, lin, count, nullptr, nullptr, 0, nullptr, nullptr, 0, 1, u_out, acc_out, "bootstrap_woks");
     return 0;
 }
 int tfhe_hip_kernel_lut_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *lin, int32_t count,
@@ -1124,7 +1124,7 @@ int tfhe_hip_kernel_lut_bootstrap_woks(const TFheGateBootstrappingCloudKeySet *b
     auto g = recorder_lock();
     return guarded_rc([&] {
         pool_of_key(bk);
-        Engine::get().run_bootstrap_woks(bk->bk->dev, lin, count, u_out, acc_out, lut_index, polys, npolys);
+        Engine::get().run_raw_rotations(bk->bk->dev, lin, count, lut_index, polys, npolys, nullptr, nullptr, 0, 1, u_out, acc_out, "lut_bootstrap_woks");
         return 0;
     });
 }
@@ -1139,8 +1139,8 @@ int tfhe_hip_kernel_lut_bootstrap_multi_woks(const TFheGateBootstrappingCloudKey
     auto g = recorder_lock();
     return guarded_rc([&] {
         pool_of_key(bk);
-        Engine::get().run_bootstrap_multi_woks(bk->bk->dev, lin, count, lut_index, polys, npolys, spec_index,
-                                               reinterpret_cast<const ExtractSpec *>(specs), nspecs, u_out, acc_out);
+        Engine::get().run_raw_rotations(bk->bk->dev, lin, count, lut_index, polys, npolys, spec_index, reinterpret_cast<const ExtractSpec *>(specs),
+                                        nspecs, XS_MAX_OUT, u_out, acc_out, "lut_bootstrap_multi_woks");
         return 0;
     });
 }

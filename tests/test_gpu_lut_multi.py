@@ -341,6 +341,68 @@ def test_dead_outputs_and_sharing_are_seen_in_the_counters(api, sets, oracle):
     inputs.close()
 
 
+def test_spec_table_grows_and_entries_are_reused_between_flushes(api, sets, oracle):
+    """The twin of test_gpu_lut.py::test_lut_table_grows_and_entries_are_reused_between_flushes for the table of extract
+    specs: 40 one-tap specs that differ in out_c0 alone, so output i is the lut_bootstrap sample with out_c0[i] added to
+    its body (the key switch passes the body through) -- an op that read a neighbour's spec shows in that one word."""
+    pp, ks, oks = sets("P128")
+    cases = M.load_digests()["sets"]["P128"]["cases"]
+    case = cases[1]
+    c0s = [int(T.wrap32((i * 0x9E3779B1 + 12345) & 0xFFFFFFFF)) for i in range(60)]       # distinct: an odd multiplier
+    keep = []
+
+    def check_reads_own_spec(results, want):
+        want = want.words()[0].astype(np.int64)
+        for r, c0 in results:
+            got = r.words()[0].astype(np.int64)
+            assert (got[:-1] == want[:-1]).all(), c0
+            assert (got[-1] - want[-1] - c0) % (1 << 32) == 0, c0
+
+    with deferred(api):
+        first = record_case(api, pp, ks, oracle, oks, case, keep)
+        assert api.flush() == 1
+        check_case(first, case)
+        # 40 specs more, each used once: the device table (16 entries at first) doubles twice within this recording
+        lut = api.Lut(pp, T.lut_words(cases[0]["lut"], pp.N))
+        a = api.CiphertextArray(pp, 1).encrypt([1], ks)
+        want = api.CiphertextArray(pp, 1)
+
+        def record(c0):
+            mo, r = api.LutMulti(lut, [([(0, 1)], c0)]), api.CiphertextArray(pp, 1)
+            api.lut_bootstrap_multi(mo, [r.at(0)], [a.at(0)], [1], 0, ks)
+            assert api.last_error() == ""
+            return mo, r
+
+        before = api.stats()
+        fill = [record(c0) for c0 in c0s[:40]]
+        api.lut_bootstrap(lut, want.at(0), [a.at(0)], [1], 0, ks)
+        again = record_case(api, pp, ks, oracle, oks, case, keep)
+        assert api.flush() == 1
+        d = delta(api, before)
+        # (nothing is shared: every object holds its own copy of the polynomial and its own spec)
+        assert (d["multi_rotations"], d["multi_outputs"]) == (40 + 1, 40 + sum(case["wanted"]))
+        assert d["blind_rotates"] == 40 + 1 + 1
+        check_reads_own_spec([(r, c0) for (_, r), c0 in zip(fill, c0s)], want)
+        check_case(again, case)
+        check_case(first, case)
+        # 20 objects go, 20 new ones take their entries; the survivors are recorded again beside them
+        for mo, _ in fill[0::2]:
+            mo.close()
+        before = api.stats()
+        fresh = [record(c0) for c0 in c0s[40:]]
+        survivors = []
+        for (mo, _), c0 in zip(fill[1::2], c0s[1:40:2]):
+            r = api.CiphertextArray(pp, 1)
+            api.lut_bootstrap_multi(mo, [r.at(0)], [a.at(0)], [1], 0, ks)
+            survivors.append((r, c0))
+        assert api.flush() == 1
+        d = delta(api, before)
+        assert (d["multi_rotations"], d["multi_outputs"], d["blind_rotates"]) == (40, 40, 40)
+        check_reads_own_spec([(r, c0) for (_, r), c0 in zip(fresh, c0s[40:])] + survivors, want)
+    for x in keep + [mo for mo, _ in fill[1::2] + fresh] + [lut, a]:
+        x.close()
+
+
 def fresh_at(O, oks, values, seed):
     """Fresh encryptions at given torus phases: an oracle encryption of bit 1 (phase 1/8 + e) moved there."""
     cts = oks.encrypt(O.Rng(seed), [1] * len(values))
