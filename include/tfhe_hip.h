@@ -260,6 +260,40 @@ int tfhe_hip_lut_bootstrap_multi_batch(const TfheHipLutMulti *mo, LweSample *con
                                        const LweSample *const *in, const int32_t *coef, Torus32 c0, int32_t count,
                                        const TFheGateBootstrappingCloudKeySet *bk);
 
+/* ---- linear combinations of samples: NOT PART OF UPSTREAM TFHE'S GATE API (upstream has them below it: lweAddTo,
+ * lweAddMulTo).  The free operations every programmable bootstrap is paired with: sums of more than the three samples a
+ * bootstrap's prelude holds (the parity of five bits is ONE bootstrap of 1/4 + 2 * sum), weighted sums of bootstrapped
+ * results as samples of their own (recombining a decomposition, a partial sum to export).  Defined by integers:
+ *     result = (0, c0) + sum_{i < nin} coef[i] * in[i]           (wrapping mod 2^32 on all n+1 words)
+ * nin in 1..TFHE_HIP_LINEAR_MAX_IN; any int32_t coefficient (0, -1, INT32_MIN included); the same sample may appear more
+ * than once; result may be one of the operands (SSA renaming, as for every gate).  No bootstrap, no key switch, no noise
+ * reset: the noise variance of the result is sum coef[i]^2 times the operands'.  bk only names the parameter set and the
+ * slot pool, as it does for bootsNOT; with "batch_keys" the operands may be results under different keys of one set (the
+ * words are defined whatever they mean).
+ * Recorded in deferred mode like bootsNOT: it rides on the highest level of its operands (level 0: all materialised) and
+ * runs after that level's key switches; a linear combination that reads another one of the same level runs one launch
+ * later (its rank), so trees of them -- 128 terms as eight 16-term sums and a sum of those -- stay one recording.  An
+ * operand that a pending bootsNOT writes is read as the NOT's operand with the coefficient negated, and bootsNOT of a
+ * pending linear result is recorded as that result times -1: the same words.  Dead results are eliminated; "reuse_gates"
+ * never shares one and "fold_constants" never folds one (nor treats its result as a constant).  Complete on return, host
+ * mirror refreshed, in immediate mode.
+ * Errors (tfhe_hip_last_error(), call without effect): nin outside 1..16, a null pointer, and those of every boots* entry
+ * (a foreign sample, a sample of another LWE dimension, the slot pool exhausted).
+ * tfhe_hip_linear_batch: result[i] from in[0][i], ..., in[nin-1][i] for i < count -- in[k] is an array of count samples;
+ * 0 / -1.
+ * tfhe_hip_sym_encrypt_torus: bootsSymEncrypt's path with the message mu in place of +-2^29 -- the same noise deviation,
+ * the same two ChaCha20 streams (or the seeded generator after tfhe_hip_set_encrypt_seed, in the same draw order: mu =
+ * +-2^29 gives bootsSymEncrypt's words for the same seed).
+ * tfhe_hip_sym_phase: b - <a, s> mod 2^32 of the sample, after running pending operations exactly where bootsSymDecrypt
+ * does (which returns phase > 0); 0 and the error channel on a null key or a foreign sample. ---- */
+#define TFHE_HIP_LINEAR_MAX_IN 16
+void tfhe_hip_linear(LweSample *result, int32_t nin, const LweSample *const *in, const int32_t *coef, Torus32 c0,
+                     const TFheGateBootstrappingCloudKeySet *bk);
+int tfhe_hip_linear_batch(LweSample *result, int32_t nin, const LweSample *const *in, const int32_t *coef, Torus32 c0,
+                          int32_t count, const TFheGateBootstrappingCloudKeySet *bk);
+void tfhe_hip_sym_encrypt_torus(LweSample *result, Torus32 mu, const TFheGateBootstrappingSecretKeySet *key);
+Torus32 tfhe_hip_sym_phase(const LweSample *sample, const TFheGateBootstrappingSecretKeySet *key);
+
 /* ---- tuning (eleven names that results never depend on, and the opt-in "fold_constants") ----
  * "br_variant": which form of the blind-rotate kernel runs wide launches (env TFHE_HIP_BR_VARIANT): -1 (default) =
  * the fastest measured for the ring size (N = 1024: 4 waves per rotation; N = 2048: split), 0 = 4 waves (N = 1024),
@@ -308,7 +342,7 @@ int tfhe_hip_set_tuning(const char *name, int64_t value);
 typedef struct TfheHipStats {
     uint64_t blind_rotates;     /* K2 instances */
     uint64_t keyswitches;       /* K3 instances */
-    uint64_t linear_ops;        /* NOT */
+    uint64_t linear_ops;        /* NOTs and linear combinations (tfhe_hip_linear) run */
     uint64_t levels;            /* batched levels executed */
     uint64_t flushes;
     uint64_t br_launches;       /* blind-rotate kernel launches */
@@ -352,6 +386,10 @@ typedef struct TfheHipStats {
      * output written by a flush */
     uint64_t multi_rotations;
     uint64_t multi_outputs;
+    /* of linear_ops, the linear combinations (tfhe_hip_linear, and a bootsNOT recorded as one), and the kernel launches they
+     * took: one per (level, rank) present in a flush */
+    uint64_t lincomb_ops;
+    uint64_t lincomb_launches;
 } TfheHipStats;
 void tfhe_hip_get_stats(TfheHipStats *out);
 void tfhe_hip_reset_stats(void);
@@ -415,6 +453,19 @@ int tfhe_hip_test_level_plan_multi(const int32_t *ops16, const int32_t *op_keys,
                                    int32_t balance, int32_t reuse, const int32_t *dead_slots, int32_t ndead,
                                    int32_t *levels_out, int32_t *shared_with, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
                                    int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots10, int32_t *kss4);
+/* The same for recordings that hold linear combinations: a record of kind 66 is {66, dst, -1, -1, -1, first term, nin, 0, 0,
+ * c0, ...} and its nin terms are lin_terms2[2 * (first term + t)] = {operand id, coefficient} (nterms pairs in all); a
+ * record of kind 17 (NOT) whose operand a pending linear combination writes becomes one, as in the recorder.  ranks_out[i]:
+ * the rank of record i (0 for all but linear combinations; -1: eliminated).  lin_sizes2 = {launches, descriptors};
+ * lin_level_off [levels + 2]: the launches of level L (0 = inputs) are [L], [L + 1]); lin_launch_off [launches + 1] and
+ * lin_launch_rank [launches]: the descriptor range and the rank of every launch; lins35 [35 * descriptors]: {dst, nin, c0,
+ * slot[16], coef[16]} each, operands as the recorder rewrote them.  Room for `count` launches and descriptors. */
+int tfhe_hip_test_level_plan_lin(const int32_t *ops16, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                                 int32_t balance, int32_t reuse, const int32_t *dead_slots, int32_t ndead,
+                                 const int32_t *lin_terms2, int32_t nterms, int32_t *levels_out, int32_t *ranks_out,
+                                 int32_t *shared_with, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off, int32_t *rot_koff,
+                                 int32_t *ks_koff, int32_t *rot_key, int32_t *rots10, int32_t *kss4, int32_t *lin_sizes2,
+                                 int32_t *lin_level_off, int32_t *lin_launch_off, int32_t *lin_launch_rank, int32_t *lins35);
 /* ---- host-logic test entries: the launch rules of peba1_amd/csrc/launch_plan.hpp, without touching the device.
  * tfhe_hip_test_br_plan: the blind-rotate launches of a level of `count` rotations of gadget (l, Bgbit) at ring size N on
  * a card of `cu_count` CUs under tunings4 = {br_variant, br8_max_rotations, br_tail8, br_digit_table}; flags bit 0 = the

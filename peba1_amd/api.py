@@ -415,6 +415,42 @@ def lut_bootstrap_multi_batch(mo, results, inputs, coefs, c0, key):
         raise RuntimeError(last_error())
 
 
+LINEAR_MAX_IN = 16
+
+
+def linear(result, inputs, coefs, c0, key):
+    """result = (0, c0) + sum coefs[i] inputs[i], wrapping mod 2^32 on all n + 1 words (tfhe_hip_linear): no bootstrap, no
+    key switch.  result and inputs are LweSample pointers (CiphertextArray.at), 1 to 16 inputs, any int32 coefficients.
+    Errors go to last_error() and leave the result untouched."""
+    n = len(inputs)
+    ins = (_l.LS * max(n, 1))(*inputs)
+    cf = np.ascontiguousarray([_wrap32(c) for c in coefs] or [0], dtype=np.int32)
+    assert len(coefs) == n
+    _l.load().tfhe_hip_linear(result, n, ins, _i32p(cf), _wrap32(c0), key.cloud)
+
+
+def linear_batch(result, inputs, coefs, c0, key):
+    """result[i] = (0, c0) + sum coefs[k] inputs[k][i]: CiphertextArrays of result.count samples."""
+    n = len(inputs)
+    ins = (_l.LS * max(n, 1))(*[a.ptr for a in inputs])
+    cf = np.ascontiguousarray([_wrap32(c) for c in coefs] or [0], dtype=np.int32)
+    assert len(coefs) == n
+    rc = _l.load().tfhe_hip_linear_batch(result.ptr, n, ins, _i32p(cf), _wrap32(c0), result.count, key.cloud)
+    if rc != 0:
+        raise RuntimeError(last_error())
+
+
+def encrypt_torus(sample, mu, key):
+    """sample = a fresh encryption of the torus message mu (tfhe_hip_sym_encrypt_torus): bootsSymEncrypt with mu in place
+    of +-2^29."""
+    _l.load().tfhe_hip_sym_encrypt_torus(sample, _wrap32(mu), key.ptr)
+
+
+def phase(sample, key):
+    """b - <a, s> mod 2^32 of the sample as a signed word (tfhe_hip_sym_phase); pending operations run first."""
+    return int(_l.load().tfhe_hip_sym_phase(sample, key.ptr))
+
+
 def set_deferred(on):
     _l.load().tfhe_hip_set_deferred(1 if on else 0)
 
@@ -442,9 +478,9 @@ def set_tuning(name, value):
 
 
 def stats():
-    s = _l.Stats()
+    s = _l.StatsAll()
     _l.load().tfhe_hip_get_stats(C.byref(s))
-    return {f: getattr(s, f) for f, _ in s._fields_}
+    return {f: getattr(s, f) for f in _l.STATS_FIELDS}
 
 
 def last_flush_keys():

@@ -730,6 +730,18 @@ Engine::FlushBuffers Engine::prepare_flush(const std::vector<const DeviceKeyImag
     fb.rots = static_cast<RotDesc *>(scratch(S_ROTS, plan.rots.size() * sizeof(RotDesc) + 16));
     fb.ks = static_cast<KsDesc *>(scratch(S_KS, plan.kss.size() * sizeof(KsDesc) + 16));
     fb.nots = static_cast<NotDesc *>(scratch(S_NOTS, plan.nots.size() * sizeof(NotDesc) + 16));
+    if (!plan.lins.empty()) {
+        // (every launch range lies inside the descriptors, every descriptor inside its own arrays and inside the pool)
+        if (plan.lin_level_off.size() != (size_t)plan.levels + 2 || plan.lin_launch_off.empty() ||
+            (size_t)plan.lin_level_off.back() + 1 != plan.lin_launch_off.size() || (size_t)plan.lin_launch_off.back() != plan.lins.size())
+            fatal("execute: the launch ranges of the linear combinations do not cover their descriptors");
+        for (const LinDesc &d : plan.lins) {
+            if (d.nin < 1 || d.nin > LIN_DESC_MAX_IN || d.dst_slot < 0) fatal("execute: a malformed linear combination");
+            for (int t = 0; t < d.nin; ++t)
+                if (d.slot[t] < 0 || d.slot[t] == d.dst_slot) fatal("execute: a linear combination reads a slot it may not");
+        }
+        fb.lins = static_cast<LinDesc *>(scratch(S_LINS, plan.lins.size() * sizeof(LinDesc)));
+    }
     // extract buffer, sized for the widest level, and key-switch partial sums, sized by the split rule launch_ks applies
     fb.u_buf = static_cast<int32_t *>(scratch(S_EXTRACT, (size_t)(std::max(plan.max_rots, plan.max_extracts) + 1) * key->dp.u_stride * 4));
     size_t partial = 0;
@@ -776,6 +788,8 @@ void Engine::upload_flush(const FlushBuffers &fb, LevelPlan &&plan_in) {
         hip_check(hipMemcpyAsync(fb.ks, plan.kss.data(), plan.kss.size() * sizeof(KsDesc), hipMemcpyHostToDevice, stream_), "upload ks");
     if (!plan.nots.empty())
         hip_check(hipMemcpyAsync(fb.nots, plan.nots.data(), plan.nots.size() * sizeof(NotDesc), hipMemcpyHostToDevice, stream_), "upload nots");
+    if (!plan.lins.empty())
+        hip_check(hipMemcpyAsync(fb.lins, plan.lins.data(), plan.lins.size() * sizeof(LinDesc), hipMemcpyHostToDevice, stream_), "upload lins");
     if (plan.nkeys > 1) {
         hip_check(hipMemcpyAsync(fb.keys, plan.dev_keys.data(), plan.dev_keys.size() * sizeof(DevKey), hipMemcpyHostToDevice, stream_), "upload keys");
         if (!plan.rot_key.empty())
@@ -783,8 +797,9 @@ void Engine::upload_flush(const FlushBuffers &fb, LevelPlan &&plan_in) {
     }
 }
 
-// Step three, once per level L of flight_plan_ (0: the NOTs riding on the inputs): the blind rotations, the key switches
-// and the NOTs of the level.  shared_end: the previous level's end event where it can serve as this level's start.
+// Step three, once per level L of flight_plan_ (0: the linear ops riding on the inputs): the blind rotations, the key switches,
+// the NOTs and then, rank by rank, the linear combinations of the level.  shared_end: the previous level's end event where it
+// can serve as this level's start.
 void Engine::run_level(const std::vector<const DeviceKeyImage *> &keys, SlotPool *pool, const FlushBuffers &fb, int L, hipEvent_t &shared_end) {
     const LevelPlan &plan = flight_plan_;
     const DeviceKeyImage *key = keys[0];
@@ -793,7 +808,8 @@ void Engine::run_level(const std::vector<const DeviceKeyImage *> &keys, SlotPool
     const int nrot = L > 0 ? plan.rot_off[gg + 1] - plan.rot_off[gg] : 0;
     const int nks = L > 0 ? plan.ks_off[gg + 1] - plan.ks_off[gg] : 0;
     const int nnot = plan.not_off[(size_t)L + 1] - plan.not_off[(size_t)L];
-    if (nrot == 0 && nks == 0 && nnot == 0) return;
+    const int lin0 = plan.lins.empty() ? 0 : plan.lin_level_off[(size_t)L], lin1 = plan.lins.empty() ? 0 : plan.lin_level_off[(size_t)L + 1];
+    if (nrot == 0 && nks == 0 && nnot == 0 && lin0 == lin1) return;
     Timed t{nullptr, nullptr, nullptr, false, nrot};
     // a level's start event is the previous level's end event where nothing was enqueued in between (no NOT launch
     // behind the key switch): two events per level instead of three -- an event costs the stream a few
@@ -842,9 +858,17 @@ void Engine::run_level(const std::vector<const DeviceKeyImage *> &keys, SlotPool
     }
     if (kernel_timing) {
         t.e2 = next_timing_event(); hip_check(hipEventRecord(t.e2, stream_), "event"); flight_timed_.push_back(t);
-        if (nnot == 0) shared_end = t.e2;
+        if (nnot == 0 && lin0 == lin1) shared_end = t.e2;
     }
     launch_not(stream_, key->dp, fb.nots + plan.not_off[(size_t)L], nnot, pool->data());
+    // a rank reads what the ranks before it wrote: one launch each, in stream order
+    for (int j = lin0; j < lin1; ++j) {
+        const int first = plan.lin_launch_off[(size_t)j], n = plan.lin_launch_off[(size_t)j + 1] - first;
+        launch_linear(stream_, key->dp, fb.lins + first, n, pool->data());
+        stats.linear_ops += (uint64_t)n;
+        stats.lincomb_ops += (uint64_t)n;
+        ++stats.lincomb_launches;
+    }
     stats.blind_rotates += (uint64_t)nrot;
     stats.keyswitches += (uint64_t)nks;
     stats.linear_ops += (uint64_t)nnot;

@@ -86,6 +86,12 @@ struct LevelPlan {
     int levels = 0;
     std::vector<int32_t> rot_off, ks_off;   // size levels + 1; gates of level L (1-based): index L - 1
     std::vector<int32_t> not_off;           // size levels + 2; NOTs riding on level L (0 = inputs): index L
+    // linear combinations (tfhe_hip_linear; all empty without one), ordered by (level, rank): the launches of level L
+    // (0 = inputs) are [lin_level_off[L], lin_level_off[L + 1]) (size levels + 2), launch j runs the descriptors
+    // [lin_launch_off[j], lin_launch_off[j + 1]) and holds the ops of rank lin_launch_rank[j]; a level's launches go in
+    // this order behind its NOTs.  op_rank: the rank of every op of the flush (0 for all but linear combinations)
+    std::vector<LinDesc> lins;
+    std::vector<int32_t> lin_level_off, lin_launch_off, lin_launch_rank, op_rank;
     int32_t max_rots = 0;                   // widest level, in rotations
     int32_t max_extracts = 0;               // the most extracted samples of a level (sizes the extract buffer): max_rots,
                                             // or more with multi-output rotations
@@ -201,7 +207,8 @@ private:
     enum Scratch : size_t {
         S_ROTS,           // flush, raw rotations: the rotation descriptors
         S_KS,             // flush, run_keyswitch: the key-switch descriptors
-        S_NOTS,           // flush: the descriptors of the linear ops
+        S_NOTS,           // flush: the descriptors of the NOTs
+        S_LINS,           // flush: the descriptors of the linear combinations
         S_SLOTS,          // io: the slot list of a packed transfer
         S_WORDS,          // io: the packed words of a host transfer
         S_EXTRACT,        // flush, raw rotations, run_keyswitch: the extracted samples
@@ -219,7 +226,7 @@ private:
     };
     void *scratch(Scratch idx, size_t bytes);
     // execute() in three steps (engine.cpp): everything that can throw, then the uploads, then one call per level
-    struct FlushBuffers { RotDesc *rots; KsDesc *ks; NotDesc *nots; int32_t *u_buf; DevKey *keys; int32_t *rot_keys; };
+    struct FlushBuffers { RotDesc *rots; KsDesc *ks; NotDesc *nots; int32_t *u_buf; DevKey *keys; int32_t *rot_keys; LinDesc *lins; };
     FlushBuffers prepare_flush(const std::vector<const DeviceKeyImage *> &keys, LevelPlan &plan);
     void upload_flush(const FlushBuffers &fb, LevelPlan &&plan);
     void run_level(const std::vector<const DeviceKeyImage *> &keys, SlotPool *pool, const FlushBuffers &fb, int L, hipEvent_t &shared_end);

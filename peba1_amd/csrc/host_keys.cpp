@@ -244,8 +244,11 @@ void generate_keys(const Params &p, Rng &secret, Rng &mask, TfheHipSecretKey &sk
 }
 
 void encrypt_bit(const TfheHipSecretKey &sk, Rng &secret, Rng &mask, int32_t message, Torus32 *a, Torus32 *b) {
-    const uint32_t mu = message ? (1u << 29) : 0u - (1u << 29);
-    uint32_t body = mu + (uint32_t)dtot32(secret.gauss(sk.p.ks_stdev));
+    encrypt_torus(sk, secret, mask, (Torus32)(message ? (1u << 29) : 0u - (1u << 29)), a, b);
+}
+
+void encrypt_torus(const TfheHipSecretKey &sk, Rng &secret, Rng &mask, Torus32 mu, Torus32 *a, Torus32 *b) {
+    uint32_t body = (uint32_t)mu + (uint32_t)dtot32(secret.gauss(sk.p.ks_stdev));
     for (int i = 0; i < sk.p.n; ++i) {
         a[i] = mask.torus();
         body += (uint32_t)a[i] * (uint32_t)sk.lwe_key[i];

@@ -94,5 +94,7 @@ namespace tfhe_hip {
 // generator for both (the draw order of DESIGN.md, which the oracle regenerates); the default path two secure ones.
 void generate_keys(const Params &p, Rng &secret, Rng &mask, TfheHipSecretKey &sk, TfheHipCloudKey &ck);
 void encrypt_bit(const TfheHipSecretKey &sk, Rng &secret, Rng &mask, int32_t message, Torus32 *a, Torus32 *b);
+// the same with any message mu in place of +-1/8: the noise draw first, then the n mask words
+void encrypt_torus(const TfheHipSecretKey &sk, Rng &secret, Rng &mask, Torus32 mu, Torus32 *a, Torus32 *b);
 Torus32 phase_of(const TfheHipSecretKey &sk, const Torus32 *a, Torus32 b);
 }  // namespace tfhe_hip

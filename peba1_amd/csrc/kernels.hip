@@ -18,6 +18,7 @@
 //         keyswitch_kernel        per-gate form for narrow launches; ks_reduce_kernel adds the
 //                                 partial sums of the ranges
 //   K5    not_kernel              negation
+//   K5b   linear_kernel           integer linear combination of up to 16 samples
 //         gather/scatter_slots    packed words <-> ciphertext pool (import, export, collectives)
 //
 // Restates (does not translate) tfhe's tfhe_bootstrap_woKS_FFT / tfhe_blindRotate_FFT
@@ -1420,6 +1421,20 @@ __global__ __launch_bounds__(256) void not_kernel(DevParams p, const NotDesc *__
     for (int i = threadIdx.x; i < p.ct_stride; i += 256) dst[i] = (int32_t)(0u - (uint32_t)src[i]);
 }
 
+// K5b: tfhe_hip_linear.  One workgroup per descriptor, which every thread reads at the same address (scalar loads);
+// a thread owns the words tid, tid + 256, ...: per term one coalesced load and one wrapping multiply-add, c0 on the body
+// word.  The padding words beyond n come out as the same combination of the operands' padding, as not_kernel leaves them.
+__global__ __launch_bounds__(256) void linear_kernel(DevParams p, const LinDesc *__restrict__ descs, int32_t *pool) {
+    const LinDesc &d = descs[blockIdx.x];
+    const int nin = d.nin;
+    int32_t *dst = pool + (size_t)d.dst_slot * p.ct_stride;
+    for (int i = threadIdx.x; i < p.ct_stride; i += 256) {
+        uint32_t acc = i == p.n ? (uint32_t)d.c0 : 0u;
+        for (int t = 0; t < nin; ++t) acc += (uint32_t)d.coef[t] * (uint32_t)pool[(size_t)d.slot[t] * p.ct_stride + i];
+        dst[i] = (int32_t)acc;
+    }
+}
+
 // packed words <-> pool slots (import/export of ciphertexts, collectives)
 __global__ __launch_bounds__(256) void gather_slots_kernel(const int32_t *__restrict__ pool, int stride, int words,
                                                            const int32_t *__restrict__ slots, int32_t *__restrict__ packed) {
@@ -1564,6 +1579,11 @@ void launch_keyswitch(hipStream_t s, const DevParams &p, const DevKey &key, cons
 void launch_not(hipStream_t s, const DevParams &p, const NotDesc *descs, int count, int32_t *pool) {
     if (count <= 0) return;
     hipLaunchKernelGGL(not_kernel, dim3(count), dim3(256), 0, s, p, descs, pool);
+}
+
+void launch_linear(hipStream_t s, const DevParams &p, const LinDesc *descs, int count, int32_t *pool) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(linear_kernel, dim3(count), dim3(256), 0, s, p, descs, pool);
 }
 
 void launch_negacyclic(hipStream_t s, const DevParams &p, const uint32_t *tw, const int32_t *ip,

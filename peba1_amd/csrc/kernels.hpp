@@ -102,6 +102,15 @@ struct KsDesc {
 
 struct NotDesc { int32_t src_slot, dst_slot; };
 
+// One linear combination (tfhe_hip_linear): pool[dst_slot] = (0, c0) + sum_{t < nin} coef[t] * pool[slot[t]], wrapping
+// mod 2^32 on every word; dst_slot is none of slot[].  Entries from nin on are not read.
+constexpr int LIN_DESC_MAX_IN = 16;
+struct LinDesc {
+    int32_t dst_slot, nin, c0;
+    int32_t slot[LIN_DESC_MAX_IN];
+    int32_t coef[LIN_DESC_MAX_IN];
+};
+
 
 void launch_bk_transform(hipStream_t s, const DevParams &p, const int32_t *raw_polys, uint32_t *img,
                          const uint32_t *tw, int npoly_per_w, int nw, const uint32_t scale[2]);
@@ -133,6 +142,7 @@ void launch_keyswitch(hipStream_t s, const DevParams &p, const DevKey &key, cons
                       const KsDesc *descs, int count, int32_t *pool, int splits, int32_t *partial, int tile,
                       bool index = true);
 void launch_not(hipStream_t s, const DevParams &p, const NotDesc *descs, int count, int32_t *pool);
+void launch_linear(hipStream_t s, const DevParams &p, const LinDesc *descs, int count, int32_t *pool);
 // res[c] = ip[c] * (poly whose image is img[c]) through the device NTT
 void launch_negacyclic(hipStream_t s, const DevParams &p, const uint32_t *tw, const int32_t *ip,
                        const uint32_t *img, int32_t *res, int count);

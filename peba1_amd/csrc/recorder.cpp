@@ -43,6 +43,7 @@ struct Recorder {
     bool balance_levels = true;   // slack-aware level filling (scheduler.hpp)
     // operations of a flush launched without waiting (tfhe_hip_flush_async): released when it is complete
     std::vector<PendingOp> flight_ops;
+    std::vector<LinTerm> flight_terms;      // the term table its linear combinations name
     SlotPool *flight_pool = nullptr;
     std::vector<const TFheGateBootstrappingCloudKeySet *> flight_keys;   // keys it runs under: not deleted before it completes
     bool eliminate_dead = true;   // dead-op elimination at flush (OpGraph::eliminate_dead)
@@ -68,9 +69,8 @@ Recorder &rec() {
     return r;
 }
 
-void release_refs(SlotPool *pool, const PendingOp &op) {    // the pending references an op holds
-    for (const int32_t s : {op.a, op.b, op.c})
-        if (s >= 0) pool->release(s);
+void release_refs(SlotPool *pool, const PendingOp &op, const LinTerm *terms) {    // the pending references an op holds
+    for_each_src(op, terms, [&](int32_t s) { pool->release(s); });
     for_each_dst(op, [&](int32_t d) { pool->release(d); });
 }
 
@@ -149,7 +149,7 @@ PendingOp make_lut_op(int kind, SlotPool *pool, int32_t lut, int nin, const LweS
 
 // The one record path: the graph shares, widens or appends the op (op_graph.hpp) for the outputs with a result sample
 // (result[m] non-null; a single-destination op has result[0] alone), and the handles are re-pointed at what it reports.
-void record_op(PendingOp op, LweSample *const *result) {
+void record_op(PendingOp op, LweSample *const *result, const LinTerm *lin = nullptr) {
     Recorder &r = rec();
     SlotPool *pool = r.pool;
     op.key = r.cur_key;
@@ -157,7 +157,7 @@ void record_op(PendingOp op, LweSample *const *result) {
     unsigned wanted = 0;
     for (int m = 0; m < nout; ++m) wanted |= (result[m] ? 1u : 0u) << m;
     int32_t out[4];
-    if (r.graph.record(*pool, op, wanted, [pool](int) { return alloc_slot(pool); }, out) >= 0) ++Engine::get().stats.reused_gates;
+    if (r.graph.record(*pool, op, wanted, [pool](int) { return alloc_slot(pool); }, out, lin) >= 0) ++Engine::get().stats.reused_gates;
     for (int m = 0; m < nout; ++m)
         if (result[m]) repoint(result[m], pool, out[m]);
     finish_op(result, nout);
@@ -349,6 +349,24 @@ void record_lutm_locked(int32_t lut, int32_t spec, int nout, LweSample *const *r
     record_op(op, result);
 }
 
+// Linear combination (tfhe_hip_linear): result = (0, c0) + sum coef[i] in[i], nin in 1..LIN_MAX_IN (checked by the caller).
+// No bootstrap and no key: bk names the parameter set and the pool.  Never folded, never shared; the graph replaces
+// operands that pending NOTs write (op_graph.hpp).
+void record_linear_locked(LweSample *result, int nin, const LweSample *const *in, const int32_t *coef, int32_t c0,
+                          const TFheGateBootstrappingCloudKeySet *bk) {
+    Recorder &r = rec();
+    begin_op(bk);
+    SlotPool *pool = r.pool;
+    bind_pool(result, pool);                                   // refuse a foreign / mismatched sample before anything changes
+    for (int i = 0; i < nin; ++i) bind_pool(in[i], pool);
+    LinTerm terms[LIN_MAX_IN];
+    for (int i = 0; i < nin; ++i) terms[i] = LinTerm{ensure_slot(in[i], pool), coef[i]};
+    PendingOp op = make_op(OP_LIN, -1, -1, -1);
+    op.nout = nin;
+    op.c0 = c0;
+    record_op(op, &result, terms);
+}
+
 // something the recorded ops name by index is about to be deleted: run the recording (or finish the flight) if one does
 template <typename Names>
 static void run_if_named(Names names) {
@@ -390,8 +408,9 @@ void record_copy_locked(LweSample *result, const LweSample *ca, const TFheGateBo
 void finish_flight_locked() {
     Recorder &r = rec();
     Engine::get().wait_flight();
-    for (const PendingOp &op : r.flight_ops) release_refs(r.flight_pool, op);
+    for (const PendingOp &op : r.flight_ops) release_refs(r.flight_pool, op, r.flight_terms.data());
     r.flight_ops.clear();
+    r.flight_terms.clear();
     r.flight_pool = nullptr;
     r.flight_keys.clear();
 }
@@ -404,7 +423,7 @@ int flush_locked(bool wait) {
     const std::vector<PendingOp> &ops = r.graph.ops();
     // level of every op: ASAP, or slack-aware balanced (same depth, fuller narrow levels)
     std::vector<int32_t> lvl, alap;
-    const int levels = schedule_levels(ops, r.graph.max_level(), r.balance_levels, Engine::get().cu_count(), lvl, &alap);
+    const int levels = schedule_levels(ops, r.graph.max_level(), r.balance_levels, Engine::get().cu_count(), lvl, &alap, r.graph.terms());
     if (const char *trace = std::getenv("TFHE_HIP_TRACE_DAG")) {      // diagnostic: per op "kind asap alap level dst a b c" (slots)
         if (FILE *f = std::fopen(trace, "w")) {
             for (size_t i = 0; i < ops.size(); ++i)
@@ -422,11 +441,11 @@ int flush_locked(bool wait) {
         if (remap[k] == 0) { remap[k] = (int32_t)used.size(); used.push_back(r.keys[k]); images.push_back(r.keys[k]->bk->dev); }
     LevelPlan plan;
     if (used.size() == r.keys.size()) {
-        plan = build_level_plan(ops, lvl, levels, (int)used.size());
+        plan = build_level_plan(ops, lvl, levels, (int)used.size(), r.graph.terms());
     } else {
         std::vector<PendingOp> rekeyed = ops;
         for (PendingOp &op : rekeyed) op.key = (uint16_t)remap[op.key];
-        plan = build_level_plan(rekeyed, lvl, levels, (int)used.size());
+        plan = build_level_plan(rekeyed, lvl, levels, (int)used.size(), r.graph.terms());
     }
     // everything above -- elimination, levelling, the plan -- ran while the device was busy with the previous asynchronous
     // flush, if any; execute() would wait for it first anyway
@@ -437,10 +456,10 @@ int flush_locked(bool wait) {
             pool->level[d] = 0;           // a later recording reads these slots as inputs: the stream orders it behind
             pool->pending[d] = 0;
         });
-        if (wait) release_refs(pool, op);
+        if (wait) release_refs(pool, op, r.graph.terms());
     }
     if (!wait) { r.flight_pool = pool; r.flight_keys = std::move(used); }
-    r.graph.clear(wait ? nullptr : &r.flight_ops);
+    r.graph.clear(wait ? nullptr : &r.flight_ops, wait ? nullptr : &r.flight_terms);
     return levels;
 }
 

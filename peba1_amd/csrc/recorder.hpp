@@ -50,6 +50,9 @@ void record_lut_locked(int32_t lut, LweSample *result, int nin, const LweSample 
 // checked by the caller) = key switch of output m of extract spec `spec` (nout outputs) of the engine's table
 void record_lutm_locked(int32_t lut, int32_t spec, int nout, LweSample *const *result, int nin, const LweSample *const *in,
                         const int32_t *coef, int32_t c0, const TFheGateBootstrappingCloudKeySet *bk);
+// result = (0, c0) + sum coef[i] in[i], nin in 1..16 (checked by the caller): no bootstrap, no key switch
+void record_linear_locked(LweSample *result, int nin, const LweSample *const *in, const int32_t *coef, int32_t c0,
+                          const TFheGateBootstrappingCloudKeySet *bk);
 void forget_lutm_locked(int32_t lut, int32_t spec);   // likewise for a multi-output LUT about to be deleted
 void forget_lut_locked(int32_t lut);   // a test polynomial about to be deleted: run the recording if an op in it names it
 void record_constant_locked(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk);

@@ -18,7 +18,7 @@ struct HeapItem {
 
 
 int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool balance, int unit,
-                    std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out) {
+                    std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out, const LinTerm *terms) {
     const int n = (int)ops.size();
     lvl.resize(n);
     for (int i = 0; i < n; ++i) lvl[i] = ops[i].level;
@@ -33,32 +33,33 @@ int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool bala
     for (int i = 0; i < n; ++i)
         for_each_dst(ops[i], [&](int32_t d) { if (producer[d] < 0) producer[d] = i; });   // (first writer, as emplace kept it)
 
-    // predecessor lists (<= 3 each) and successor lists in CSR form
-    std::vector<int32_t> pred(3 * (size_t)n, -1), npred(n, 0), succ_off(n + 1, 0);
+    // predecessor lists (<= 3 each; a linear combination: one per term) and successor lists in CSR form
+    std::vector<size_t> pred_at(n);
+    size_t pred_room = 0;
+    for (int i = 0; i < n; ++i) { pred_at[i] = pred_room; pred_room += 3 + (size_t)op_terms(ops[i]); }
+    std::vector<int32_t> pred(pred_room, -1), npred(n, 0), succ_off(n + 1, 0);
     for (int i = 0; i < n; ++i) {
-        const int32_t src[3] = {ops[i].a, ops[i].b, ops[i].c};
-        for (int s = 0; s < 3; ++s) {
-            if (src[s] < 0) continue;
-            const int32_t pr = src[s] <= max_slot ? producer[src[s]] : -1;
-            if (pr < 0 || pr >= i) continue;                         // materialised before this flush
+        for_each_src(ops[i], terms, [&](int32_t src) {
+            const int32_t pr = src <= max_slot ? producer[src] : -1;
+            if (pr < 0 || pr >= i) return;                           // materialised before this flush
             bool dup = false;
-            for (int t = 0; t < npred[i]; ++t) dup |= pred[3 * (size_t)i + t] == pr;
-            if (dup) continue;
-            pred[3 * (size_t)i + npred[i]++] = pr;
+            for (int t = 0; t < npred[i]; ++t) dup |= pred[pred_at[i] + t] == pr;
+            if (dup) return;
+            pred[pred_at[i] + npred[i]++] = pr;
             ++succ_off[pr + 1];
-        }
+        });
     }
     for (int i = 0; i < n; ++i) succ_off[i + 1] += succ_off[i];
     std::vector<int32_t> succ(succ_off[n]), cursor(succ_off.begin(), succ_off.end() - 1);
     for (int i = 0; i < n; ++i)
-        for (int t = 0; t < npred[i]; ++t) succ[cursor[pred[3 * (size_t)i + t]]++] = i;
+        for (int t = 0; t < npred[i]; ++t) succ[cursor[pred[pred_at[i] + t]]++] = i;
 
     // ALAP: recording order is topological, so one reverse sweep suffices
     std::vector<int32_t> alap(n, asap_depth);
     for (int i = n - 1; i >= 0; --i) {
-        const int32_t need = ops[i].kind == OP_NOT ? alap[i] : alap[i] - 1;   // a NOT runs after its level's gates
+        const int32_t need = op_is_linear(ops[i].kind) ? alap[i] : alap[i] - 1;   // a linear op runs after its level's gates
         for (int t = 0; t < npred[i]; ++t) {
-            int32_t &a = alap[pred[3 * (size_t)i + t]];
+            int32_t &a = alap[pred[pred_at[i] + t]];
             a = std::min(a, need);
         }
     }
@@ -68,12 +69,15 @@ int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool bala
     // list scheduling, least slack first
     long long remaining = 0;
     for (const PendingOp &op : ops) remaining += op_rotations(op);
+    // (earliest level: 1 for a gate; a linear op takes the highest level of what it reads, 0 if all of it is materialised)
     std::vector<int32_t> left(npred), est(n, 1);
+    for (int i = 0; i < n; ++i)
+        if (op_is_linear(ops[i].kind)) est[i] = 0;
     std::vector<std::vector<int32_t>> avail(asap_depth + 2);
     auto release_successors = [&](int32_t i, int32_t level_done, auto &&self) -> void {
         for (int32_t e = succ_off[i]; e < succ_off[i + 1]; ++e) {
             const int32_t s = succ[e];
-            const bool is_not = ops[s].kind == OP_NOT;
+            const bool is_not = op_is_linear(ops[s].kind);
             est[s] = std::max(est[s], is_not ? level_done : level_done + 1);
             if (--left[s] != 0) continue;
             if (is_not) {                       // linear: rides along with its operand's level
@@ -86,15 +90,15 @@ int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool bala
     };
     for (int i = 0; i < n; ++i) {
         if (left[i] != 0) continue;
-        if (ops[i].kind == OP_NOT) {
+        if (op_is_linear(ops[i].kind)) {
             if (npred[i] == 0) { lvl[i] = 0; est[i] = 0; }
         } else {
             avail[1].push_back(i);
         }
     }
-    // NOTs of materialised inputs release their successors now (level 0 is "before level 1")
+    // linear ops of materialised inputs release their successors now (level 0 is "before level 1")
     for (int i = 0; i < n; ++i)
-        if (ops[i].kind == OP_NOT && npred[i] == 0) release_successors(i, 0, release_successors);
+        if (op_is_linear(ops[i].kind) && npred[i] == 0) release_successors(i, 0, release_successors);
 
     std::priority_queue<HeapItem, std::vector<HeapItem>, std::greater<HeapItem>> heap;
     std::vector<int32_t> batch;
@@ -145,10 +149,59 @@ int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool bala
     return asap_depth;
 }
 
-LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<int32_t> &lvl, int levels, int nkeys) {
+// The linear combinations of a plan: each op's rank from the levels the ops really run at, the descriptors ordered by
+// (level, rank), one launch range per pair present.
+static void plan_linear_ops(LevelPlan &plan, const std::vector<PendingOp> &ops, const std::vector<int32_t> &lvl, int levels,
+                            const LinTerm *terms) {
+    int32_t max_slot = -1;
+    size_t nlin = 0;
+    for (const PendingOp &op : ops)
+        if (op.kind == OP_LIN) { max_slot = std::max(max_slot, op.dst); ++nlin; }
+    if (!nlin) return;
+    // recording order is topological: the producer of a term's slot, if a linear combination, has its rank already
+    std::vector<int32_t> producer((size_t)max_slot + 1, -1);
+    plan.op_rank.assign(ops.size(), 0);
+    std::vector<std::pair<int64_t, int32_t>> order;       // (level, rank) -> op
+    order.reserve(nlin);
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const PendingOp &op = ops[i];
+        if (op.kind != OP_LIN) continue;
+        int32_t rank = 0;
+        for (int t = 0; t < op.nout; ++t) {
+            const int32_t s = terms[op.spec + t].slot;
+            const int32_t pr = s <= max_slot ? producer[(size_t)s] : -1;
+            if (pr >= 0 && lvl[(size_t)pr] == lvl[i]) rank = std::max(rank, plan.op_rank[(size_t)pr] + 1);
+        }
+        plan.op_rank[i] = rank;
+        producer[(size_t)op.dst] = (int32_t)i;
+        order.emplace_back((int64_t)lvl[i] << 32 | (uint32_t)rank, (int32_t)i);
+    }
+    std::stable_sort(order.begin(), order.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+    plan.lins.resize(nlin);
+    plan.lin_level_off.assign((size_t)levels + 2, 0);
+    plan.lin_launch_off.assign(1, 0);
+    for (size_t j = 0; j < nlin; ++j) {
+        const PendingOp &op = ops[(size_t)order[j].second];
+        LinDesc &d = plan.lins[j];
+        d = LinDesc{};
+        d.dst_slot = op.dst; d.nin = op.nout; d.c0 = op.c0;
+        for (int t = 0; t < op.nout; ++t) { d.slot[t] = terms[op.spec + t].slot; d.coef[t] = terms[op.spec + t].coef; }
+        if (j > 0 && order[j].first != order[j - 1].first) plan.lin_launch_off.push_back((int32_t)j);
+        if (j == 0 || order[j].first != order[j - 1].first) {
+            plan.lin_launch_rank.push_back((int32_t)(order[j].first & 0xFFFFFFFF));
+            ++plan.lin_level_off[(size_t)(order[j].first >> 32) + 1];
+        }
+    }
+    plan.lin_launch_off.push_back((int32_t)nlin);
+    for (size_t L = 0; L <= (size_t)levels; ++L) plan.lin_level_off[L + 1] += plan.lin_level_off[L];
+}
+
+LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<int32_t> &lvl, int levels, int nkeys,
+                           const LinTerm *terms) {
     LevelPlan plan;
     plan.levels = levels;
     plan.nkeys = nkeys;
+    plan_linear_ops(plan, ops, lvl, levels, terms);
     // counting sort by level: gates of level L (1-based) in group L - 1, NOTs riding on level L (0 = inputs) in group L.
     // Several keys: gates of level L under key k in sub-group (L - 1) nkeys + k, so that a level's descriptors are
     // contiguous per key (rot_koff / ks_koff); with one key the sub-groups are the groups.
@@ -159,6 +212,7 @@ LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<
     plan.not_off.assign((size_t)levels + 2, 0);
     for (size_t i = 0; i < ops.size(); ++i) {
         if (ops[i].kind == OP_NOT) { ++plan.not_off[(size_t)lvl[i] + 1]; continue; }
+        if (ops[i].kind == OP_LIN) continue;                   // (plan_linear_ops)
         const size_t sg = (size_t)(lvl[i] - 1) * nkeys + ops[i].key;
         roff[sg + 1] += op_rotations(ops[i]);
         koff[sg + 1] += op_keyswitches(ops[i]);
@@ -191,6 +245,7 @@ LevelPlan build_level_plan(const std::vector<PendingOp> &ops, const std::vector<
             plan.nots[npos[(size_t)lvl[i]]++] = NotDesc{op.a, op.dst};
             continue;
         }
+        if (op.kind == OP_LIN) continue;
         const size_t g = (size_t)(lvl[i] - 1), sg = g * nkeys + op.key;
         const int32_t base = plan.rot_off[g];
         const int32_t r0 = rpos[sg];

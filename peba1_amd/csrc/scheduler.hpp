@@ -18,7 +18,7 @@
 namespace tfhe_hip {
 
 struct PendingOp {
-    uint8_t kind;       // 0..9 two-input gate code, OP_MUX, OP_NOT, OP_GATE3 + 8 gate + negation mask, OP_LUT, OP_LUTM
+    uint8_t kind;       // 0..9 two-input gate code, OP_MUX, OP_NOT, OP_GATE3 + 8 gate + negation mask, OP_LUT, OP_LUTM, OP_LIN
     int32_t dst, a, b, c;   // slots; b, c = -1 when absent
     int32_t level;      // ASAP level (NOT: the level of its operand, 0 = already materialised)
     uint16_t key = 0;   // index of the gate's cloud key in the flush's key list (recorder "batch_keys"; NOT: unused)
@@ -32,6 +32,8 @@ struct PendingOp {
     int32_t spec = -1;
     int32_t nout = 0;
     int32_t dsts[4] = {-1, -1, -1, -1};
+    // OP_LIN only (tfhe_hip_linear): dst = (0, c0) + sum of `nout` terms (1..LIN_MAX_IN of them; op_terms) that start at
+    // entry `spec` of the recording's term table (OpGraph::terms).  a, b, c are -1: the operands are the terms' slots
 };
 constexpr uint8_t OP_MUX = 16, OP_NOT = 17;
 // programmable bootstrap (not in upstream's gate API): one rotation from a caller-supplied test polynomial, one key switch
@@ -44,8 +46,23 @@ inline bool op_kind_valid(int kind) { return (kind >= 0 && kind < 10) || kind ==
 inline bool op_kind_valid_lut(int kind) { return op_kind_valid(kind) || kind == OP_LUT; }
 // multi-output programmable bootstrap: one rotation, then one extracted sample and one key switch per WANTED output
 constexpr uint8_t OP_LUTM = 65;
+// linear combination of up to LIN_MAX_IN samples with integer coefficients (tfhe_hip_linear): no rotation, no extract, no
+// key switch.  Like a NOT it rides on the highest level of its operands (0: all materialised) and runs after that level's
+// key switches; its (slot, coefficient) pairs live in a side table so that PendingOp does not grow for the gates
+constexpr uint8_t OP_LIN = 66;
+constexpr int LIN_MAX_IN = 16;
+struct LinTerm { int32_t slot, coef; };
+inline bool op_is_linear(int kind) { return kind == OP_NOT || kind == OP_LIN; }
+inline int op_terms(const PendingOp &op) { return op.kind == OP_LIN ? op.nout : 0; }
+// every slot an op reads: a, b, c where present, then the terms of a linear combination (`terms`: the recording's table)
+template <class F>
+inline void for_each_src(const PendingOp &op, const LinTerm *terms, F &&f) {
+    for (const int32_t s : {op.a, op.b, op.c})
+        if (s >= 0) f(s);
+    for (int t = 0; t < op_terms(op); ++t) f(terms[op.spec + t].slot);
+}
 
-inline int op_rotations(const PendingOp &op) { return op.kind == OP_NOT ? 0 : (op.kind == OP_MUX ? 2 : 1); }
+inline int op_rotations(const PendingOp &op) { return op_is_linear(op.kind) ? 0 : (op.kind == OP_MUX ? 2 : 1); }
 // samples of the level's extract buffer an op takes (a multi-output op: one per output of its spec, wanted or not, so
 // that output m sits at u_index + m) and key switches it needs
 inline int op_extracts(const PendingOp &op) { return op.kind == OP_LUTM ? op.nout : op_rotations(op); }
@@ -55,7 +72,7 @@ inline int op_wanted(const PendingOp &op) {
     return w;
 }
 inline int op_keyswitches(const PendingOp &op) {
-    return op.kind == OP_NOT ? 0 : op.kind == OP_LUTM ? __builtin_popcount((unsigned)op_wanted(op)) : 1;
+    return op_is_linear(op.kind) ? 0 : op.kind == OP_LUTM ? __builtin_popcount((unsigned)op_wanted(op)) : 1;
 }
 // the outputs of any op: a single-destination op is the one-output case
 inline int op_outputs(const PendingOp &op) { return op.kind == OP_LUTM ? op.nout : 1; }
@@ -119,18 +136,22 @@ inline OpKey op_key(const PendingOp &op) {
 }
 
 // Fills lvl[i] with the level at which ops[i] runs (bootstrapped gates: 1..depth,
-// NOTs: 0..depth, executed after the gates of that level).  `unit` = rotations one
+// NOTs and linear combinations: 0..depth, executed after the gates of that level; `terms`: the
+// table the linear combinations' operands are in, null when there are none).  `unit` = rotations one
 // full pass of the latency kernel holds (the CU count); levels are filled to 1, 2
 // or 4 units depending on how much work is left per remaining level.  With
 // balance == false, or for trivial DAGs, lvl = ASAP.  Returns the depth.
 // If alap_out is given it receives each op's ALAP level (== lvl when not balancing).
 int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool balance, int unit,
-                    std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out = nullptr);
+                    std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out = nullptr, const LinTerm *terms = nullptr);
 
 // The descriptors of a flush (engine.hpp): ops[i] runs at level lvl[i] (schedule_levels), levels in all.  nkeys > 1 (a
-// flush of gates under several cloud keys): within a level, descriptors are grouped by ops[i].key.
+// flush of gates under several cloud keys): within a level, descriptors are grouped by ops[i].key.  Linear combinations
+// (terms: their table) get their rank here, from the levels they really run at: 1 + the rank of a linear combination of
+// the same level whose result they read, else 0; a level's descriptors are ordered by rank, one launch range per rank.
 struct LevelPlan;
 __attribute__((visibility("hidden"))) LevelPlan build_level_plan(const std::vector<PendingOp> &ops,
-                                                                 const std::vector<int32_t> &lvl, int levels, int nkeys = 1);
+                                                                 const std::vector<int32_t> &lvl, int levels, int nkeys = 1,
+                                                                 const LinTerm *terms = nullptr);
 
 }  // namespace tfhe_hip

@@ -265,6 +265,32 @@ int32_t bootsSymDecrypt(const LweSample *sample, const TFheGateBootstrappingSecr
     return bit;
 }
 
+// bootsSymEncrypt's path with any message: the same deviation, the same streams, the same draw order
+void tfhe_hip_sym_encrypt_torus(LweSample *result, Torus32 mu, const TFheGateBootstrappingSecretKeySet *key) {
+    guarded([&] {
+        if (!key || !key->lwe_key) api_fail("tfhe_hip_sym_encrypt_torus: null key");
+        auto g = recorder_lock();
+        EncryptRng &e = enc_rng();
+        ArrayHeader *h = header_of(result);                  // (refuses a null or foreign sample)
+        if (h->n != key->lwe_key->p.n) api_fail("tfhe_hip_sym_encrypt_torus: the sample and the key differ in LWE dimension");
+        if (result->slot >= 0) h->pool->release(result->slot);
+        result->slot = SLOT_HOST;
+        encrypt_torus(*key->lwe_key, e.secret, e.seeded ? e.secret : e.mask, mu, result->a, &result->b);
+    });
+}
+
+Torus32 tfhe_hip_sym_phase(const LweSample *sample, const TFheGateBootstrappingSecretKeySet *key) {
+    Torus32 phase = 0;
+    guarded([&] {
+        if (!key || !key->lwe_key) api_fail("tfhe_hip_sym_phase: null key");
+        auto g = recorder_lock();
+        if (header_of(sample)->n != key->lwe_key->p.n) api_fail("tfhe_hip_sym_phase: the sample and the key differ in LWE dimension");
+        sync_sample_locked(sample);
+        phase = phase_of(*key->lwe_key, sample->a, sample->b);
+    });
+    return phase;
+}
+
 void bootsCONSTANT(LweSample *result, int32_t value, const TFheGateBootstrappingCloudKeySet *bk) {
     guarded([&] {
         auto g = recorder_lock();
@@ -835,6 +861,54 @@ int tfhe_hip_lut_bootstrap_multi_batch(const TfheHipLutMulti *mo, LweSample *con
     });
 }
 
+// ---- linear combinations of samples: no bootstrap, no key switch ----
+static void linear_args_check(const char *who, const void *result, int32_t nin, const void *in, const int32_t *coef,
+                              const TFheGateBootstrappingCloudKeySet *bk) {
+    if (nin < 1 || nin > TFHE_HIP_LINEAR_MAX_IN) api_fail(std::string(who) + ": nin must be 1..16");
+    if (!result) api_fail(std::string(who) + ": null result");
+    if (!in || !coef) api_fail(std::string(who) + ": null operand or coefficient list");
+    for (int32_t i = 0; i < nin; ++i)
+        if (!static_cast<const void *const *>(in)[i]) api_fail(std::string(who) + ": null operand");
+    if (!bk || !bk->bk) api_fail("null cloud key");
+}
+// a sample of the call, before the key is touched: ours, and of the key's LWE dimension
+static void linear_sample_check(const LweSample *s, const TFheGateBootstrappingCloudKeySet *bk) {
+    if (header_of(s)->n != bk->bk->p.n) api_fail("ciphertext used with a key of different LWE dimension than the one it was allocated for");
+}
+
+void tfhe_hip_linear(LweSample *result, int32_t nin, const LweSample *const *in, const int32_t *coef, Torus32 c0,
+                     const TFheGateBootstrappingCloudKeySet *bk) {
+    static_assert(TFHE_HIP_LINEAR_MAX_IN == LIN_MAX_IN && LIN_MAX_IN == LIN_DESC_MAX_IN, "one limit, from the header to the kernel");
+    guarded([&] {
+        linear_args_check("tfhe_hip_linear", result, nin, in, coef, bk);
+        linear_sample_check(result, bk);
+        for (int32_t i = 0; i < nin; ++i) linear_sample_check(in[i], bk);
+        auto g = recorder_lock();
+        record_linear_locked(result, nin, in, coef, c0, bk);
+    });
+}
+
+int tfhe_hip_linear_batch(LweSample *result, int32_t nin, const LweSample *const *in, const int32_t *coef, Torus32 c0,
+                          int32_t count, const TFheGateBootstrappingCloudKeySet *bk) {
+    auto g = recorder_lock();
+    const int rc = record_batch([&] {
+        linear_args_check("tfhe_hip_linear_batch", result, nin, in, coef, bk);
+        if (count > 0) {
+            linear_sample_check(result, bk);
+            for (int32_t k = 0; k < nin; ++k) linear_sample_check(in[k], bk);
+        }
+        for (int32_t i = 0; i < count; ++i) {
+            const LweSample *ops[LIN_MAX_IN];
+            for (int32_t k = 0; k < nin; ++k) ops[k] = &in[k][i];
+            record_linear_locked(&result[i], nin, ops, coef, c0, bk);
+        }
+    });
+    // immediate mode: complete on return, host mirrors refreshed like tfhe_hip_linear's
+    if (rc == 0 && !deferred_mode())
+        return guarded_rc([&] { for (int32_t i = 0; i < count; ++i) sync_sample_locked(&result[i]); return 0; });
+    return rc;
+}
+
 void tfhe_hip_test_set_alloc_cap(int64_t bytes) {
     auto g = recorder_lock();
     set_alloc_cap((long long)bytes);
@@ -915,17 +989,23 @@ int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int
 
 // rot_words = 6: the two-operand words of every rotation (the form older callers know); 8: slot_c and sc as well; 9: and
 // the LUT index; 10: and the extract spec word.  ops = ops5, or records of 10 words when lut_ops
-// (tfhe_hip_test_level_plan_lut), or of 16 when rec_words = 16 (tfhe_hip_test_level_plan_multi: dead_slots as well)
+// (tfhe_hip_test_level_plan_lut), or of 16 when rec_words = 16 (tfhe_hip_test_level_plan_multi: dead_slots as well).
+// lin (tfhe_hip_test_level_plan_lin): records of kind 66 name terms of lin->terms2; their part of the plan goes to lin->*
+struct TestLinPlan {
+    const int32_t *terms2; int32_t nterms;
+    int32_t *ranks_out, *sizes2, *level_off, *launch_off, *launch_rank, *descs35;
+};
 static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
                            int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
                            int32_t *rot_koff, int32_t *ks_koff, int32_t *rot_key, int32_t *rots, int rot_words, int32_t *kss4,
                            bool lut_ops = false, int32_t reuse = 0, int32_t *shared_with = nullptr, int rec_words = 10,
-                           const int32_t *dead_slots = nullptr, int32_t ndead = 0) {
+                           const int32_t *dead_slots = nullptr, int32_t ndead = 0, const TestLinPlan *lin = nullptr) {
     if (count < 0 || nkeys < 1 || nkeys > UINT16_MAX) { set_error("test_level_plan: bad count or nkeys"); return -1; }
     for (int32_t i = 0; i < count; ++i)
         if (op_keys[i] < 0 || op_keys[i] >= nkeys) { set_error("test_level_plan: key index out of range"); return -1; }
     std::vector<PendingOp> ops;
     std::vector<int32_t> op_of_record;                   // lut_ops: record -> index in ops (-1: eliminated)
+    std::vector<LinTerm> terms;                          // the graph's term table (records of kind 66)
     int depth;
     if (!lut_ops) {
         depth = test_build_ops(ops5, count, ops);
@@ -949,6 +1029,13 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
             const int32_t *o = ops5 + (size_t)rec_words * (size_t)i;
             for (int w = 1; w <= 4; ++w) top = std::max(top, o[w] + 1);
             for (int w = 12; w < 12 + id_words; ++w) top = std::max(top, o[w] + 1);
+            if (lin && o[0] == OP_LIN) {
+                if (o[5] < 0 || o[6] < 1 || o[6] > LIN_MAX_IN || o[5] > lin->nterms - o[6]) { set_error("test_level_plan_lin: bad term range"); return -1; }
+                for (int t = 0; t < o[6]; ++t) {
+                    if (lin->terms2[2 * (size_t)(o[5] + t)] < 0) { set_error("test_level_plan_lin: a term without an operand"); return -1; }
+                    top = std::max(top, lin->terms2[2 * (size_t)(o[5] + t)] + 1);
+                }
+            }
         }
         SlotTable slots{std::vector<int32_t>((size_t)top, 1), std::vector<int32_t>((size_t)top, 0), std::vector<uint8_t>((size_t)top, 0)};
         std::vector<int32_t> handle((size_t)top), record_of_op;
@@ -959,7 +1046,8 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
         for (int32_t i = 0; i < count; ++i) {
             const int32_t *o = ops5 + (size_t)rec_words * (size_t)i;
             const bool multi = rec_words == 16 && o[0] == OP_LUTM;
-            if (!op_kind_valid_lut(o[0]) && !multi) { set_error("test schedule: unknown op kind"); return -1; }
+            const bool is_lin = lin && o[0] == OP_LIN;
+            if (!op_kind_valid_lut(o[0]) && !multi && !is_lin) { set_error("test schedule: unknown op kind"); return -1; }
             auto slot_of = [&](int32_t id) { return id >= 0 ? handle[(size_t)id] : -1; };
             PendingOp op{(uint8_t)o[0], -1, slot_of(o[2]), slot_of(o[3]), slot_of(o[4]), 0, (uint16_t)op_keys[i]};
             if (op.kind == OP_LUT || multi) { op.lut = o[5]; op.sa = o[6]; op.sb = o[7]; op.sc = o[8]; op.c0 = o[9]; }
@@ -968,6 +1056,12 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
                 op.spec = o[10]; op.nout = o[11];
                 if (op.nout < 1 || op.nout > XS_MAX_OUT) { set_error("test_level_plan_multi: nout must be 1..4"); return -1; }
                 std::copy(o + 12, o + 12 + op.nout, ids);
+            }
+            LinTerm lt[LIN_MAX_IN];
+            if (is_lin) {
+                op.a = op.b = op.c = -1;
+                op.nout = o[6]; op.c0 = o[9];
+                for (int t = 0; t < op.nout; ++t) lt[t] = LinTerm{slot_of(lin->terms2[2 * (size_t)(o[5] + t)]), lin->terms2[2 * (size_t)(o[5] + t) + 1]};
             }
             unsigned wanted = 0;
             for (int m = 0; m < op_outputs(op); ++m) {
@@ -979,7 +1073,7 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
                 wanted |= 1u << m;
             }
             if (!wanted) { set_error("test_level_plan: an op without a destination"); return -1; }
-            const int32_t shared = graph.record(slots, op, wanted, [&](int m) { return ids[m]; }, out);
+            const int32_t shared = graph.record(slots, op, wanted, [&](int m) { return ids[m]; }, out, is_lin ? lt : nullptr);
             if (shared < 0) record_of_op.push_back(i);
             if (shared_with) shared_with[i] = shared < 0 ? -1 : record_of_op[(size_t)shared];
             op_of_record[(size_t)i] = shared < 0 ? (int32_t)record_of_op.size() - 1 : shared;
@@ -996,14 +1090,27 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
         graph.eliminate_dead(slots, &moved_to);
         for (int32_t &at : op_of_record) at = moved_to[(size_t)at];
         ops = graph.ops();
+        terms.assign(graph.terms(), graph.terms() + graph.term_count());
         depth = graph.max_level();
     }
     std::vector<int32_t> lvl;
-    const int levels = schedule_levels(ops, depth, balance != 0, unit, lvl);
-    const LevelPlan plan = build_level_plan(ops, lvl, levels, nkeys);     // exactly what flush_locked hands to execute()
+    const int levels = schedule_levels(ops, depth, balance != 0, unit, lvl, nullptr, terms.data());
+    const LevelPlan plan = build_level_plan(ops, lvl, levels, nkeys, terms.data());     // exactly what flush_locked hands to execute()
     for (int32_t i = 0; i < count; ++i) {
         const int32_t at = lut_ops ? op_of_record[(size_t)i] : i;
         levels_out[i] = at >= 0 ? lvl[(size_t)at] : -1;      // -1: eliminated (tfhe_hip_test_level_plan_multi's dead_slots)
+        if (lin) lin->ranks_out[i] = at < 0 ? -1 : plan.op_rank.empty() ? 0 : plan.op_rank[(size_t)at];
+    }
+    if (lin) {
+        static_assert(sizeof(LinDesc) == 35 * sizeof(int32_t), "a linear descriptor is 35 plain words");
+        lin->sizes2[0] = plan.lins.empty() ? 0 : (int32_t)plan.lin_launch_off.size() - 1;
+        lin->sizes2[1] = (int32_t)plan.lins.size();
+        for (size_t L = 0; L < (size_t)levels + 2; ++L) lin->level_off[L] = plan.lins.empty() ? 0 : plan.lin_level_off[L];
+        if (!plan.lins.empty()) {
+            std::memcpy(lin->launch_off, plan.lin_launch_off.data(), plan.lin_launch_off.size() * sizeof(int32_t));
+            std::memcpy(lin->launch_rank, plan.lin_launch_rank.data(), plan.lin_launch_rank.size() * sizeof(int32_t));
+            std::memcpy(lin->descs35, plan.lins.data(), plan.lins.size() * sizeof(LinDesc));
+        }
     }
     sizes6[0] = plan.levels;
     sizes6[1] = (int32_t)plan.rots.size();
@@ -1056,6 +1163,23 @@ int tfhe_hip_test_level_plan_multi(const int32_t *ops16, const int32_t *op_keys,
     if (ndead < 0 || (ndead > 0 && !dead_slots)) { set_error("test_level_plan_multi: bad dead_slots"); return -1; }
     return test_level_plan(ops16, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
                            rot_key, rots10, 10, kss4, true, reuse, shared_with, 16, dead_slots, ndead);
+}
+
+int tfhe_hip_test_level_plan_lin(const int32_t *ops16, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                                 int32_t balance, int32_t reuse, const int32_t *dead_slots, int32_t ndead,
+                                 const int32_t *lin_terms2, int32_t nterms, int32_t *levels_out, int32_t *ranks_out,
+                                 int32_t *shared_with, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off, int32_t *rot_koff,
+                                 int32_t *ks_koff, int32_t *rot_key, int32_t *rots10, int32_t *kss4, int32_t *lin_sizes2,
+                                 int32_t *lin_level_off, int32_t *lin_launch_off, int32_t *lin_launch_rank, int32_t *lins35) {
+    if (!shared_with || !ranks_out || !lin_sizes2 || !lin_level_off || !lin_launch_off || !lin_launch_rank || !lins35) {
+        set_error("test_level_plan_lin: null output");
+        return -1;
+    }
+    if (ndead < 0 || (ndead > 0 && !dead_slots)) { set_error("test_level_plan_lin: bad dead_slots"); return -1; }
+    if (nterms < 0 || (nterms > 0 && !lin_terms2)) { set_error("test_level_plan_lin: bad term table"); return -1; }
+    const TestLinPlan lin{lin_terms2, nterms, ranks_out, lin_sizes2, lin_level_off, lin_launch_off, lin_launch_rank, lins35};
+    return test_level_plan(ops16, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
+                           rot_key, rots10, 10, kss4, true, reuse, shared_with, 16, dead_slots, ndead, &lin);
 }
 
 int tfhe_hip_test_br_plan(int32_t N, int32_t l, int32_t Bgbit, const int32_t *tunings4, int32_t cu_count, int32_t count,

@@ -48,6 +48,8 @@ class SecretKeySet(C.Structure):
 
 
 class Stats(C.Structure):
+    """TfheHipStats up to multi_outputs.  The header only ever appends fields, so this stays a prefix of the struct;
+    StatsAll below is the whole of it."""
     _fields_ = [("blind_rotates", C.c_uint64), ("keyswitches", C.c_uint64), ("linear_ops", C.c_uint64),
                 ("levels", C.c_uint64), ("flushes", C.c_uint64), ("br_launches", C.c_uint64),
                 ("ms_blind_rotate", C.c_double), ("ms_keyswitch", C.c_double), ("ms_flush_wall", C.c_double),
@@ -60,6 +62,15 @@ class Stats(C.Structure):
                 ("br_tables0_launches", C.c_uint64), ("br_tables1_launches", C.c_uint64),
                 ("br_tables2_launches", C.c_uint64), ("lut_rotations", C.c_uint64),
                 ("multi_rotations", C.c_uint64), ("multi_outputs", C.c_uint64)]
+
+
+class StatsAll(Stats):
+    """The whole of TfheHipStats, what tfhe_hip_get_stats fills: ctypes lays a subclass's fields out behind its base's,
+    as the header appended them (every field is 8 bytes wide: no padding in between)."""
+    _fields_ = [("lincomb_ops", C.c_uint64), ("lincomb_launches", C.c_uint64)]
+
+
+STATS_FIELDS = [f for f, _ in Stats._fields_] + [f for f, _ in StatsAll._fields_]
 
 
 PS = C.POINTER(ParameterSet)
@@ -150,10 +161,14 @@ SIGNATURES = {
     "tfhe_hip_lut_bootstrap_multi": (None, [C.c_void_p, C.POINTER(LS), C.c_int32, C.POINTER(LS), I32P, C.c_int32, CK]),
     "tfhe_hip_lut_bootstrap_multi_batch": (C.c_int, [C.c_void_p, C.POINTER(LS), C.c_int32, C.POINTER(LS), I32P, C.c_int32,
                                                      C.c_int32, CK]),
+    "tfhe_hip_linear": (None, [LS, C.c_int32, C.POINTER(LS), I32P, C.c_int32, CK]),
+    "tfhe_hip_linear_batch": (C.c_int, [LS, C.c_int32, C.POINTER(LS), I32P, C.c_int32, C.c_int32, CK]),
+    "tfhe_hip_sym_encrypt_torus": (None, [LS, C.c_int32, SK]),
+    "tfhe_hip_sym_phase": (C.c_int32, [LS, SK]),
     "tfhe_hip_set_tuning": (C.c_int, [C.c_char_p, C.c_int64]),
     "tfhe_hip_test_form_admissible": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int]),
     "tfhe_hip_test_set_alloc_cap": (None, [C.c_int64]),
-    "tfhe_hip_get_stats": (None, [C.POINTER(Stats)]),
+    "tfhe_hip_get_stats": (None, [C.POINTER(StatsAll)]),
     "tfhe_hip_reset_stats": (None, []),
     "tfhe_hip_set_kernel_timing": (None, [C.c_int]),
     "tfhe_hip_last_flush_keys": (C.c_int, []),
@@ -164,6 +179,8 @@ SIGNATURES = {
     "tfhe_hip_test_level_plan_lut": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [I32P] * 10),
     "tfhe_hip_test_level_plan_multi": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P,
                                                  C.c_int32] + [I32P] * 10),
+    "tfhe_hip_test_level_plan_lin": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P,
+                                               C.c_int32, I32P, C.c_int32] + [I32P] * 16),
     "tfhe_hip_test_br_plan": (C.c_int, [C.c_int32] * 3 + [I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_ks_plan": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "tfhe_hip_kernel_negacyclic":(C.c_int, [CK, I32P, I32P, I32P, C.c_int32]),
