@@ -10,6 +10,13 @@
 //   Montgomery reduction of T:       |r| <= |T| / 2^32 + P/2
 //   forward radix-4 step:            b <- b (1 + 3q) + 1,   radix-2 stage: b <- b (1 + q) + 1/2,   q = P / 2^32
 //   a digit-table entry d w mod P:   |e| <= 1/2 + |d| q     (split form, mode 2: centred, |e| <= 1/2)
+//
+// What holds the bounds to the kernels: tests/test_gpu_gadget_sweep.py takes EVERY gadget this predicate and the CRT
+// range admit (the enumeration comes from the library, no list), and runs each (form, table mode) the planner can reach
+// for it against the oracle word for word, on a generated key; every gadget outside is refused at key upload there.
+// tests/test_gpu_adversarial.py drives the frontier gadgets of each form (adversarial_common.SETS: the last l of the
+// 4-wave, 8-wave, split and 2-wave forms, l = 1, a lowest digit field at bit 2) with crafted keys to the corner
+// magnitudes of the model.  A change to a bound below changes what those two files run.
 #pragma once
 #include <cstdint>
 
@@ -83,6 +90,15 @@ inline bool br_form_admissible(int form, int N, int l, int Bgbit, int tables) {
     default: return false;
     }
     return into_inverse < 4.0;
+}
+
+// The table mode a launch of `form` planned with `tables` really runs: the launchers (kernels.hip digit_table_usable)
+// multiply wherever the digits do not index the LDS tables -- digits wider than 7 bits, a lowest field below bit 3 -- and
+// the 2-wave form has no tables at all.  The predicate above treats such a mode as "no tables" too, so a plan may carry
+// mode 1 or 2 for a gadget that runs mode 0; the launch counters (TfheHipStats br_tables*_launches) count this.
+inline int br_tables_run(int form, int l, int Bgbit, int tables) {
+    if (form == BR_FORM_WAVE2 || Bgbit > 7 || 32 - l * Bgbit < 3) return 0;
+    return tables;
 }
 
 }  // namespace tfhe_hip

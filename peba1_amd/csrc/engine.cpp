@@ -658,7 +658,9 @@ void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const BrLa
     auto note = [&](int f) {
         ++(f == BR_FORM_WIDE4 ? stats.br_wide4_launches : f == BR_FORM_SPLIT ? stats.br_split_launches
            : f == BR_FORM_WAVE8 ? stats.br_wave8_launches : stats.br_wave2_launches);
-        ++(plan.tables == 0 ? stats.br_tables0_launches : plan.tables == 1 ? stats.br_tables1_launches : stats.br_tables2_launches);
+        // (the mode the launchers run, not the one planned: a gadget whose digits cannot index the tables multiplies)
+        const int ran = br_tables_run(f, dp.l, dp.Bgbit, plan.tables);
+        ++(ran == 0 ? stats.br_tables0_launches : ran == 1 ? stats.br_tables1_launches : stats.br_tables2_launches);
     };
     if (kernel_timing) {
         if (!clock_acc_) {

@@ -30,7 +30,18 @@ SETS = {
     "P128": (1024, 3, 7, 57), "P80": (1024, 2, 10, 58), "P2048": (2048, 3, 6, 59),
     "l4_Bg8": (1024, 4, 8, 60), "N2048_l6_Bg4": (2048, 6, 4, 61), "l8_Bg4": (1024, 8, 4, 62),
     "N2048_l2_Bg9": (2048, 2, 9, 63),
+    # the frontier of every kernel form's admissible range (br_forms.hpp) and the digit-field edges:
+    "l9_Bg3": (1024, 9, 3, 65),             # the 2-wave form only
+    "l7_Bg4": (1024, 7, 4, 66),             # the last l of the 4-wave form (model: 3.95 of < 4), tables usable
+    "l5_Bg5": (1024, 5, 5, 67),             # the last l of the 8-wave form (3.88), which takes it only without tables
+    "l5_Bg6": (1024, 5, 6, 68),             # lowest digit field at bit 2: tables off by DIGIT_TAB_MIN_SHIFT, Bgbit <= 7
+    "l1_Bg11": (1024, 1, 11, 69),           # l = 1 (one gadget row, no 8-wave form), the widest digits the CRT range takes
+    "N2048_l7_Bg4": (2048, 7, 4, 70),       # the last l of the split form (3.98), table mode 1 excluded
+    "N2048_l4_Bg6": (2048, 4, 6, 71),       # the largest l with the split form's eleven-table first step
+    "N2048_l1_Bg10": (2048, 1, 10, 72),     # l = 1 at N = 2048, at the CRT magnitude 2^52
 }
+# the sets' seeds: the first seven keep the ones they were first checked with (their rank by name among themselves)
+_SEED_RANK = {name: i for i, name in enumerate(sorted(list(SETS)[:7]) + list(SETS)[7:])}
 KS_T, KS_BASEBIT = 8, 2
 WIDE4, SPLIT, WAVE8, WAVE2 = range(4)
 FORM_NAMES = ["4-wave", "split", "8-wave", "2-wave"]
@@ -229,7 +240,8 @@ def build_set(name, key_variant=0, with_cases=True):
     words (the multi-key test's second and third key), same case list."""
     N, l, Bgbit, n = SETS[name]
     half = 1 << (Bgbit - 1)
-    seed = 1000 * sorted(SETS).index(name) + key_variant
+    assert Bgbit >= 2, "the loads need the digit 2^(Bgbit-2)"
+    seed = 1000 * _SEED_RANK[name] + key_variant
     rng = np.random.default_rng(seed)
     cs = CraftedSet()
     cs.name, cs.N, cs.l, cs.Bgbit, cs.n = name, N, l, Bgbit, n
@@ -377,3 +389,10 @@ def predicted_form(ok, N, l, Bgbit, count, cu_count, br_variant, br_digit_table,
                 return f, hit[0]
         return None
     return form, tables
+
+
+def tables_run(form, l, Bgbit, tables):
+    """br_forms.hpp br_tables_run restated: the digit-table mode a launch planned with `tables` really runs, which is what
+    the br_tables*_launches counters count.  The launchers (kernels.hip digit_table_usable) multiply where the digits do
+    not index the LDS tables: wider than 7 bits, or a lowest field below bit 3; the 2-wave form has no tables."""
+    return 0 if form == WAVE2 or Bgbit > 7 or 32 - l * Bgbit < 3 else tables

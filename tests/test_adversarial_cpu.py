@@ -108,6 +108,31 @@ def test_reach_is_the_bound_itself(name):
     assert (A.w32(hi["expected"].astype(np.int64) - hi["target"]) != 0).sum() > N
 
 
+def test_frontier_sets_sit_on_the_frontier_they_are_named_for():
+    """The eight frontier sets are what adversarial_common.SETS says of them, by the library's own predicate: the next l
+    (or the table mode named) is outside the form, so a change to a bound of br_forms.hpp that moves a frontier fails
+    here instead of leaving a set that no longer probes one."""
+    from peba1_amd import lib
+    fn = lib.load().tfhe_hip_test_form_admissible
+    forms = lambda N, l, B: [[fn(f, N, l, B, t) for t in range(3)] for f in range(4)]
+    none, every = [0, 0, 0], [1, 1, 1]
+    S = {k: v[:3] for k, v in A.SETS.items()}
+    assert forms(*S["l9_Bg3"]) == [none, none, none, every] and not any(map(any, forms(1024, 10, 3)))
+    assert forms(*S["l7_Bg4"])[A.WIDE4] == every and forms(1024, 8, 4)[A.WIDE4] == none
+    assert A.tables_run(A.WIDE4, 7, 4, 1) == 1
+    assert forms(*S["l5_Bg5"])[A.WAVE8] == [1, 0, 0] and forms(*S["l5_Bg5"])[A.WIDE4] == every
+    assert forms(1024, 6, 5)[A.WAVE8] == none
+    # a lowest field at bit 2: every mode is admitted as the one without tables, and none is run with tables
+    assert forms(*S["l5_Bg6"]) == [every] * 4 and forms(1024, 5, 5)[A.WAVE8] != every
+    assert [A.tables_run(f, 5, 6, t) for f in range(4) for t in range(3)] == [0] * 12
+    assert forms(*S["l1_Bg11"]) == [every, every, none, every]
+    assert A.crt_bound(*S["l1_Bg11"]) == A.crt_bound(*S["N2048_l1_Bg10"]) == 1 << 52
+    assert forms(*S["N2048_l7_Bg4"]) == [none, [1, 0, 1], none, none] and not any(map(any, forms(2048, 8, 4)))
+    assert forms(*S["N2048_l4_Bg6"])[A.SPLIT] == every and forms(2048, 5, 5)[A.SPLIT] == [1, 0, 1]
+    assert forms(*S["N2048_l1_Bg10"]) == [none, every, none, none]
+    assert len({v[3] for v in A.SETS.values()}) == len(A.SETS) == 15
+
+
 def _load(tmp_path, fname, chunks):
     from peba1_amd import api
     with open(tmp_path / fname, "wb") as f:

@@ -34,11 +34,13 @@ def counters(api):
     return np.array([s[f] for f in A.FORM_COUNTERS + A.TABLE_COUNTERS], dtype=np.int64)
 
 
-def expect_counters(forms, tables):
+def expect_counters(forms, tables, l, Bgbit):
+    """One launch per form, each counted under the table mode it really runs with (A.tables_run): a planned mode the
+    gadget's digits cannot index (Bgbit > 7, lowest field below bit 3, the 2-wave form) counts as mode 0."""
     want = np.zeros(7, dtype=np.int64)
     for f in forms:
         want[f] += 1
-        want[4 + tables] += 1
+        want[4 + A.tables_run(f, l, Bgbit, tables)] += 1
     return want
 
 
@@ -122,7 +124,7 @@ def test_crafted_corners_in_every_kernel_form(crafted, name):
             before = counters(api)
             u, acc = api.kernel_bootstrap_woks(c.cloud, cs.lin, want_acc=True)
             what = "%s form, table mode %d (br_variant %d, br_digit_table %d, br8_max_rotations %d)" % (A.FORM_NAMES[form], tables, v, t, b8)
-            assert (counters(api) - before == expect_counters([form], tables)).all(), what
+            assert (counters(api) - before == expect_counters([form], tables, l, Bgbit)).all(), what
             print("%s: %s: %d cases, %d tunings collapse here" % (name, what, count, len(tunings)))
             assert_rows(acc, c.acc, cs, what + ", accumulator")
             assert_rows(u, c.u, cs, what + ", extracted sample")
@@ -151,7 +153,7 @@ def test_crafted_corners_in_the_full_round_and_in_the_8_wave_tail(crafted, name)
             before = counters(api)
             u = api.kernel_bootstrap_woks(c.cloud, lin)
             what = "%d rotations, br_tail8 %d, forms %s" % (total, tail8, [A.FORM_NAMES[f] for f in forms])
-            assert (counters(api) - before == expect_counters(forms, tb)).all(), what
+            assert (counters(api) - before == expect_counters(forms, tb, l, Bgbit)).all(), what
             print("\n%s: %s" % (name, what))
             assert_rows(u, c.u, cs, what, rows)
     finally:
