@@ -539,6 +539,83 @@ struct WaveNtt {
         wave_lds_fence();
         inv_pass<steps_in(LC) + steps_in(RB)>(x, c, t0);
     }
+    // The same transform in two parts, for a caller that hands half of the outputs on (the 4-wave blind rotation:
+    // its CRT partner recombines registers [REGS/2, REGS) or [0, REGS/2)).  inverse_head runs everything but the last
+    // step and leaves the last pass's twiddles in t0; inverse_last runs that step -- a radix-4 step on the register
+    // groups {r, r + REGS/4, r + REGS/2, r + 3 REGS/4}, so every group ends in two registers of either half -- and makes
+    // the half named by UPPER_FIRST final first, calls emit() (the caller's stores of that half), then finishes the
+    // other half: the stores and whoever waits for them run under the rest of the step.  Same operations on the same
+    // operands as inverse(): every output word is what it was.
+    static __device__ __forceinline__ void inverse_head(int32_t (&x)[REGS], const PrimeCtx &c, uint32_t *scr, int lane,
+                                                        const InvTw2 &t2, InvTw0 &t0) {
+        inv_pass<0>(x, c, t2);
+        InvTw1 t1;
+        t1.load(c, lane);
+        write_row_h(x, scr, lane);
+        wave_lds_fence();
+#pragma unroll
+        for (int r = 0; r < REGS; ++r) x[r] = (int32_t)scr[h_t2_addr(lane, r)];
+        wave_lds_fence();
+        inv_pass<steps_in(LC)>(x, c, t1);
+        t0.load(c, lane);
+        write_row_h(x, scr, lane);
+        wave_lds_fence();
+#pragma unroll
+        for (int r = 0; r < REGS; ++r) x[r] = (int32_t)scr[h_t1_addr(lane, r)];
+        wave_lds_fence();
+        inv_pass_head<steps_in(LC) + steps_in(RB)>(x, c, t0);
+    }
+    template <bool UPPER_FIRST, typename EMIT>
+    static __device__ __forceinline__ void inverse_last(int32_t (&x)[REGS], const PrimeCtx &c, const InvTw0 &t0, EMIT emit) {
+        inv_pass_last<steps_in(LC) + steps_in(RB), UPPER_FIRST>(x, c, t0, emit);
+    }
+    template <int K, int S, int END>
+    static __device__ __forceinline__ void inv_pass_head(int32_t (&x)[REGS], const PrimeCtx &c, const PassTw<S, END, false> &t) {
+        using T = PassTw<S, END, false>;
+        constexpr InvPlan plan = make_inv_plan(LOGN);
+        if constexpr (END - (T::PAIR ? 2 : 1) > S) {
+            step<T::STAGE, T::PAIR, false, plan.renorm[K], T::CNT>(x, t.tw, t.q, c);
+            inv_pass_head<K + 1>(x, c, t.rest);
+        }
+    }
+    template <int K, bool UPPER_FIRST, int S, int END, typename EMIT>
+    static __device__ __forceinline__ void inv_pass_last(int32_t (&x)[REGS], const PrimeCtx &c, const PassTw<S, END, false> &t,
+                                                         EMIT emit) {
+        using T = PassTw<S, END, false>;
+        constexpr InvPlan plan = make_inv_plan(LOGN);
+        if constexpr (END - (T::PAIR ? 2 : 1) > S) {
+            inv_pass_last<K + 1, UPPER_FIRST>(x, c, t.rest, emit);
+        } else {
+            static_assert(T::PAIR && T::STAGE == 0 && T::CNT == 1 && K == plan.nsteps - 1 && plan.renorm[K],
+                          "the last step is one renormalising radix-4 block over the register halves");
+            constexpr int h = REGS / 2, l = REGS / 4;
+            const uint32_t w1 = t.tw[0];
+            const uint4 q = t.q[0];
+            int32_t s0[l], s1[l], d0[l], d1[l];
+#pragma unroll
+            for (int r = 0; r < l; ++r) {
+                s0[r] = x[r] + x[r | l]; s1[r] = x[r | h] + x[r | h | l];
+                d0[r] = x[r] - x[r | l]; d1[r] = x[r | h] - x[r | h | l];
+            }
+            // gs_bfly4<true>, its outputs in two halves
+            auto lower = [&] {
+#pragma unroll
+                for (int r = 0; r < l; ++r) {
+                    x[r] = mont_mul(s0[r] + s1[r], c.rmod, c.P, c.pinv);
+                    x[r | l] = mont_mul2(d0[r], q.x, d1[r], q.y, c);
+                }
+            };
+            auto upper = [&] {
+#pragma unroll
+                for (int r = 0; r < l; ++r) {
+                    x[r | h] = mont_mul(s0[r] - s1[r], w1, c.P, c.pinv);
+                    x[r | h | l] = mont_mul2(d0[r], q.z, d1[r], q.w, c);
+                }
+            };
+            if constexpr (UPPER_FIRST) { upper(); emit(); lower(); }
+            else { lower(); emit(); upper(); }
+        }
+    }
     static __device__ __forceinline__ void inverse(int32_t (&x)[REGS], const PrimeCtx &c, uint32_t *scr, int lane) {
         InvTw2 t2;
         t2.load(c, lane);
