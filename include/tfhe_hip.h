@@ -333,8 +333,9 @@ Torus32 tfhe_hip_sym_phase(const LweSample *sample, const TFheGateBootstrappingS
  * with equal numbers are one set; the noise deviations do not matter).  The words are the same as with 0; every key of
  * such a flush stays alive until it has run (deleting a keyset runs the whole recording first).
  * "sync_deadline_ms": see "bounded host waits" above.
- * (Environment only: TFHE_HIP_KS_BLOCKS / TFHE_HIP_KS_MAX_SPLITS / TFHE_HIP_KS_SPLIT_TIES, how key switches are cut into
- * coefficient ranges -- peba1_amd/csrc/launch_plan.hpp.)
+ * "ks_max_splits": 1 .. 64, default 48 (env TFHE_HIP_KS_MAX_SPLITS): the most coefficient ranges a key switch is cut into; 1 =
+ * never cut, every result goes straight to its slot (peba1_amd/csrc/launch_plan.hpp).
+ * (Environment only: TFHE_HIP_KS_BLOCKS / TFHE_HIP_KS_SPLIT_TIES, the rest of how key switches are cut into ranges.)
  * Returns 0, or -1 for an unknown name. */
 int tfhe_hip_set_tuning(const char *name, int64_t value);
 
@@ -390,6 +391,14 @@ typedef struct TfheHipStats {
      * took: one per (level, rank) present in a flush */
     uint64_t lincomb_ops;
     uint64_t lincomb_launches;
+    /* key-switch kernel launches by the form that ran, counted where the launch is issued, from its plan
+     * (peba1_amd/csrc/launch_plan.hpp plan_ks) -- the raw test path (tfhe_hip_kernel_keyswitch) included: the per-gate kernel
+     * (narrow launches, every key-switch decomposition other than t = 8, base 4, and row widths the tiled kernels are not
+     * built for), the LDS-strip form, the index form.  A tiled launch counts one per chunk of 8,192 gates; the reduce
+     * launches behind split forms are not counted */
+    uint64_t ks_pergate_launches;
+    uint64_t ks_strip_launches;
+    uint64_t ks_index_launches;
 } TfheHipStats;
 void tfhe_hip_get_stats(TfheHipStats *out);
 void tfhe_hip_reset_stats(void);
@@ -476,11 +485,15 @@ int tfhe_hip_test_level_plan_lin(const int32_t *ops16, const int32_t *op_keys, i
  * digits (ks_t, ks_basebit) under tunings5 = {ks_target_blocks, ks_max_splits, ks_split_ties, ks_tile, ks_index}.
  * out6 = {tiled kernel 1 / 0, gates per tile (0: per-gate kernel), gates per launch (all launches but the last), coefficient
  * ranges of the first launch, of the last launch, bytes of partial sums the whole sequence needs}.
- * Both return 0, -1 on bad arguments. ---- */
+ * tfhe_hip_test_ks_plan_form: the same six words and, seventh, the kernel form: 0 = per gate, 1 = LDS strips, 2 = index
+ * (out7).  What Engine::launch_ks runs and counts (ks_*_launches) is this plan.
+ * All return 0, -1 on bad arguments. ---- */
 int tfhe_hip_test_br_plan(int32_t N, int32_t l, int32_t Bgbit, const int32_t *tunings4, int32_t cu_count, int32_t count,
                           int32_t flags, int32_t *out3);
 int tfhe_hip_test_ks_plan(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
                           int32_t cu_count, int32_t count, int64_t *out6);
+int tfhe_hip_test_ks_plan_form(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
+                               int32_t cu_count, int32_t count, int64_t *out7);
 /* Diagnostic (tools/wg_times.py): a 4-wave blind-rotate launch of `width` random gates (the second of two back to back);
  * times4[4i .. 4i+3] = s_memtime (shader cycles; the start stamp carries the XCC / CU id in its top 16
  * bits) at the start and end of workgroup i, then s_memrealtime (constant 100 MHz) at its start and

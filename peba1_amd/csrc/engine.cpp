@@ -687,8 +687,8 @@ void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const BrLa
 
 static KsShape ks_shape(const DevParams &dp) { return KsShape{dp.k * dp.N, dp.ks_t, dp.ks_basebit, dp.ct_stride}; }
 
-// the key switches of `count` gates by the rule of launch_plan.hpp: chunks of at most KS_CHUNK gates when tiled, each in
-// ks_splits coefficient ranges
+// the key switches of `count` gates by the rule of launch_plan.hpp: the form plan_ks names, in chunks of at most KS_CHUNK
+// gates when tiled, each in ks_splits coefficient ranges
 void Engine::launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
                        hipStream_t stream, bool presized) {
     ENGINE_DEVICE_SCOPE();
@@ -700,12 +700,18 @@ void Engine::launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const Ks
     if (presized && bytes > (scratch_size_.size() > S_KS_PARTIAL ? scratch_size_[S_KS_PARTIAL] : 0))
         fatal("launch_ks: the key-switch partial sums were not sized by execute()");
     int32_t *partial = bytes ? static_cast<int32_t *>(scratch(S_KS_PARTIAL, bytes)) : nullptr;
-    const bool tiled = ks_tiled(tunings, count, shape);
-    const int chunk = tiled ? KS_CHUNK : count;
+    // the form is the plan's (launch_plan.hpp plan_ks), decided once for the whole launch; the counters say what ran
+    const KsPlan plan = plan_ks(tunings, count, shape);
+    const int chunk = plan.form != KS_FORM_PERGATE ? KS_CHUNK : count;
     for (int done = 0; done < count; done += chunk) {
         const int cnt = std::min(chunk, count - done), splits = ks_splits(tunings, cu_count_, cnt, shape);
-        launch_keyswitch(stream, dp, key->key, u_buf, descs + done, cnt, pool, splits, splits > 1 ? partial : nullptr,
-                         tiled ? ks_tile_size(tunings) : 0, tunings.ks_index != 0);
+        // (the last chunk of a tiled launch may be narrower than two tiles: it runs what the rule gives its own width)
+        const KsPlan part = done ? plan_ks(tunings, cnt, shape) : plan;
+        ++(part.form == KS_FORM_INDEX ? stats.ks_index_launches : part.form == KS_FORM_STRIP ? stats.ks_strip_launches
+                                                                                             : stats.ks_pergate_launches);
+        if (!launch_keyswitch(stream, dp, key->key, u_buf, descs + done, cnt, pool, splits, splits > 1 ? partial : nullptr,
+                              part.tile, part.form != KS_FORM_STRIP))
+            fatal("launch_ks: the planned key-switch form has no kernel instantiation");
     }
 }
 

@@ -1554,20 +1554,28 @@ void launch_blind_rotate4(hipStream_t s, const DevParams &p, const DevKey &key, 
         hipLaunchKernelGGL((blind_rotate4_kernel<10, false>), dim3(count), dim3(256), 0, s, p, key, pool, rots, u_buf, acc_dbg);
 }
 
-// tile = 0 or splits <= 1: one workgroup per (gate, range) [keyswitch_kernel].  tile = 16 / 24 / 32 with the key switch of
-// the built-in sets (t = 8, base 4) and ranges of at most 64 coefficients: the tiled kernels -- the index form, or the
-// LDS-strip form (tile 16) when `index` is false.  Every form with splits > 1 leaves partial sums for ks_reduce_kernel.
-void launch_keyswitch(hipStream_t s, const DevParams &p, const DevKey &key, const int32_t *u_buf,
+// Runs the form the planner chose (launch_plan.hpp plan_ks) and decides nothing.  tile = 0: one workgroup per (gate, range)
+// [keyswitch_kernel]; tile = 16 / 24 / 32: the tiled kernels -- the index form, or the LDS-strip form (tile 16) when `index`
+// is false -- which exist for the key switch of the built-in sets (t = 8, base 4), ranges of at most 64 coefficients and
+// workgroups of 128, 192 or 320 threads.  Every form with splits > 1 leaves partial sums for ks_reduce_kernel.  Returns
+// false, with nothing launched, for a form there is no instantiation for.
+bool launch_keyswitch(hipStream_t s, const DevParams &p, const DevKey &key, const int32_t *u_buf,
                       const KsDesc *descs, int count, int32_t *pool, int splits, int32_t *partial, int tile, bool index) {
-    if (count <= 0) return;
-    const int threads = ((p.ct_stride / 4 + 63) / 64) * 64;      // one 16-byte lane per 4 output words: 128, 192 or 320
-    if (splits <= 1 || !partial) {
+    if (count <= 0) return true;
+    const int threads = ((p.ct_stride / 4 + 63) / 64) * 64;      // one 16-byte lane per 4 output words: 64 .. 320
+    if (threads > KS_MAX_THREADS) return false;
+    if (tile == 0 && (splits <= 1 || !partial)) {
         hipLaunchKernelGGL(keyswitch_kernel, dim3(count, 1), dim3(threads), 0, s, p, key, u_buf, descs, pool, nullptr);
-        return;
+        return true;
     }
-    const int range = (p.k * p.N + splits - 1) / splits;
-    const bool tiled = (tile == 16 || ((tile == 24 || tile == 32) && index)) && count >= 2 * tile && p.ks_t == 8 &&
-                       p.ks_basebit == 2 && range <= 64 && (threads == 128 || threads == 192 || threads == 320);
+    if (splits <= 1 || !partial) return false;
+    const bool tiled = tile != 0;
+    if (tiled) {
+        const int range = (p.k * p.N + splits - 1) / splits;
+        if (!(tile == 16 || ((tile == 24 || tile == 32) && index)) || count < 2 * tile || p.ks_t != 8 || p.ks_basebit != 2 ||
+            range > 64 || (threads != 128 && threads != 192 && threads != 320))
+            return false;
+    }
     const dim3 grid((count + (tiled ? tile : 1) - 1) / (tiled ? tile : 1), splits);
 #define KS_FORM(K, GT)                                                                                                      \
     do {                                                                                                                    \
@@ -1582,6 +1590,7 @@ void launch_keyswitch(hipStream_t s, const DevParams &p, const DevKey &key, cons
     else KS_FORM(keyswitch_index_kernel, 32);
 #undef KS_FORM
     hipLaunchKernelGGL(ks_reduce_kernel, dim3(count), dim3(threads), 0, s, p, descs, splits, partial, pool);
+    return true;
 }
 
 void launch_not(hipStream_t s, const DevParams &p, const NotDesc *descs, int count, int32_t *pool) {

@@ -132,13 +132,13 @@ void launch_blind_rotate8_mk(hipStream_t s, const DevParams &p, const DevKey &ke
 // split form (8 waves per rotation, every transform as two half-size ones; N = 1024 or 2048)
 void launch_blind_rotate_split(hipStream_t s, const DevParams &p, const DevKey &key, const int32_t *pool,
                                const RotDesc *rots, int count, int32_t *u_buf, int32_t *acc_dbg);
-// splits > 1: each gate's key switch is cut into `splits` ranges of input coefficients
-// (partial sums in `partial[count][splits][ct_stride]`, then a reduce launch).  tile = 16, 24 or
-// 32: launches of at least 2*tile gates use a tiled kernel (one pass over the KSK rows of
-// a range serves `tile` gates); 0 = always one workgroup per (gate, range).  index: the tiled launch is the
-// index form (rows in pinned registers picked through the VGPR index mode: keyswitch_index_kernel), else the
-// LDS-strip form (tile 16 only: keyswitch_strip_kernel)
-void launch_keyswitch(hipStream_t s, const DevParams &p, const DevKey &key, const int32_t *u_buf,
+// The key switches of `count` gates in the form the planner chose (launch_plan.hpp plan_ks; nothing is decided here).
+// splits > 1: each gate's key switch is cut into `splits` ranges of input coefficients (partial sums in
+// `partial[count][splits][ct_stride]`, then a reduce launch).  tile = 0: one workgroup per (gate, range); tile = 16, 24 or
+// 32: a tiled kernel (one pass over the KSK rows of a range serves `tile` gates) -- the index form (rows in pinned registers
+// picked through the VGPR index mode: keyswitch_index_kernel) or, index = false, the LDS-strip form (tile 16 only:
+// keyswitch_strip_kernel).  Returns false and launches nothing for a form without an instantiation.
+bool launch_keyswitch(hipStream_t s, const DevParams &p, const DevKey &key, const int32_t *u_buf,
                       const KsDesc *descs, int count, int32_t *pool, int splits, int32_t *partial, int tile,
                       bool index = true);
 void launch_not(hipStream_t s, const DevParams &p, const NotDesc *descs, int count, int32_t *pool);

@@ -12,8 +12,8 @@
 
 namespace tfhe_hip {
 
-// Tunings of the launch rules (tfhe_hip_set_tuning: br_variant, br8_max_rotations, br_tail8, br_digit_table, ks_tile and
-// ks_index; beside them the recorder's reuse_gates / eliminate_dead / balance_levels / fold_constants / batch_keys, and
+// Tunings of the launch rules (tfhe_hip_set_tuning: br_variant, br8_max_rotations, br_tail8, br_digit_table, ks_tile,
+// ks_index and ks_max_splits; beside them the recorder's reuse_gates / eliminate_dead / balance_levels / fold_constants / batch_keys, and
 // the engine's sync_deadline_ms).  HISTORY.md lists the forms and knobs removed in round 6.
 struct LaunchTunings {
     // which form of the blind-rotate kernel runs wide launches (kernels.hip): -1 = the fastest measured for the ring size
@@ -36,7 +36,8 @@ struct LaunchTunings {
     // exist: beyond filling the chip, more splits mean the blocks in flight share a KSK sub-table small enough for an
     // XCD's L2 (measured optimum of the per-gate kernel: 32 splits).  The tiled launches take any count of coefficient
     // ranges up to ks_max_splits whose grid fills whole rounds of resident workgroups (ks_splits); a cap of 48 measured
-    // 56.1 against 61.0 ms per match at 32 (env TFHE_HIP_KS_BLOCKS, TFHE_HIP_KS_MAX_SPLITS; not tunings)
+    // 56.1 against 61.0 ms per match at 32 (env TFHE_HIP_KS_BLOCKS, not a tuning; tuning "ks_max_splits", env
+    // TFHE_HIP_KS_MAX_SPLITS)
     int ks_target_blocks = 32768;
     int ks_max_splits = 48;
     // among the range counts that fill the workgroup slots equally well: 1 = the largest (more, shorter ranges), 0 = the smallest
@@ -100,35 +101,55 @@ inline BrPlan plan_br(const bool form_ok[BR_FORM_COUNT][3], int N, int l, const 
     return BrPlan{form, tables, split ? tail : 0};
 }
 
-// The key-switch launch rule, one place for launch_ks and for execute()'s sizing of the partial sums: a launch of `count`
-// gates runs in chunks of at most KS_CHUNK gates when tiled (bounds the partial-sum buffer: 0.66 GB at P128), each chunk of
-// cnt gates in ks_splits(cnt) coefficient ranges.  Tiles of 24 or 32 gates exist in the index form only (kernels.hip
-// keyswitch_index_kernel); tile 0 = per-gate kernel only.
+// The key-switch launch rule, one place for launch_ks, for execute()'s sizing of the partial sums and for the test entry: a
+// launch of `count` gates runs in chunks of at most KS_CHUNK gates when tiled (bounds the partial-sum buffer: 0.66 GB at
+// P128), each chunk of cnt gates in ks_splits(cnt) coefficient ranges.  Tiles of 24 or 32 gates exist in the index form only
+// (kernels.hip keyswitch_index_kernel); tile 0 = per-gate kernel only.
 constexpr int KS_CHUNK = 8192;
 // what the rule reads of a parameter set: nin = k N input coefficients, the key-switch digits, words per ciphertext slot
 struct KsShape { int nin, ks_t, ks_basebit, ct_stride; };
 
+// one 16-byte lane per 4 output words, rounded up to a wave: 64 .. 320 threads a workgroup
+inline int ks_threads(const KsShape &p) { return ((p.ct_stride / 4 + 63) / 64) * 64; }
+
+// The kernel a launch of `count` gates runs (kernels.hip): one workgroup per (gate, range) [keyswitch_kernel], or a tile of
+// gates per workgroup with the staged rows in LDS strips [keyswitch_strip_kernel, tile 16] or in pinned registers
+// [keyswitch_index_kernel, tile 16 / 24 / 32].  tile = gates per workgroup, 0 for the per-gate kernel.
+enum KsForm { KS_FORM_PERGATE = 0, KS_FORM_STRIP = 1, KS_FORM_INDEX = 2 };
+struct KsPlan { int form; int tile; };
+
 inline int ks_tile_size(const LaunchTunings &t) { return (t.ks_tile > 16 && !t.ks_index) ? 16 : t.ks_tile; }
 
-// the tiled kernel: wide launches, ranges of at most 64 input coefficients
-inline bool ks_tiled(const LaunchTunings &t, int count, const KsShape &p) {
-    const int tile = ks_tile_size(t);
-    return tile > 0 && count >= 2 * tile && p.ks_t == 8 && p.ks_basebit == 2 && t.ks_max_splits > 1 &&
-           (p.nin + t.ks_max_splits - 1) / t.ks_max_splits <= 64;
+// The whole decision (launch_keyswitch decides nothing).  The tiled kernels are built for the key switch of the built-in
+// sets only -- t = 8, base 4 -- for ranges of at most 64 input coefficients and for workgroups of 128, 192 or 320 threads
+// (n in 256 .. 511, in 512 .. 767, and n = 1024); they take wide launches, from two tiles on.
+// Everything else -- every other accepted (ks_t, ks_basebit), row widths of 64 and 256 threads -- is the per-gate kernel,
+// planned as such: the narrow-launch split rule, one chunk.
+inline KsPlan plan_ks(const LaunchTunings &t, int count, const KsShape &p) {
+    const int tile = ks_tile_size(t), threads = ks_threads(p);
+    const bool tiled = (tile == 16 || tile == 24 || tile == 32) && count >= 2 * tile && p.ks_t == 8 && p.ks_basebit == 2 &&
+                       t.ks_max_splits > 1 && (p.nin + t.ks_max_splits - 1) / t.ks_max_splits <= 64 &&
+                       (threads == 128 || threads == 192 || threads == 320);
+    if (!tiled) return KsPlan{KS_FORM_PERGATE, 0};
+    return KsPlan{t.ks_index ? KS_FORM_INDEX : KS_FORM_STRIP, tile};
 }
+
+// the tiled kernels: wide launches, ranges of at most 64 input coefficients
+inline bool ks_tiled(const LaunchTunings &t, int count, const KsShape &p) { return plan_ks(t, count, p).form != KS_FORM_PERGATE; }
 
 inline int ks_splits(const LaunchTunings &t, int cu_count, int cnt, const KsShape &p) {
     int splits = 1;
-    if (ks_tiled(t, cnt, p)) {
+    const KsPlan plan = plan_ks(t, cnt, p);
+    if (plan.form != KS_FORM_PERGATE) {
         // the number of coefficient ranges is free between nin/64 and ks_max_splits: take the
         // one whose grid (tiles x ranges) fills whole rounds of the workgroups the chip holds,
         // e.g. 36 tiles x 28 ranges = 1008 of 1024 slots in two rounds instead of 36 x 32 = 1152 in three
-        const int tile = ks_tile_size(t);
-        const int threads = ((p.ct_stride / 4 + 63) / 64) * 64;
+        const int tile = plan.tile;
+        const int threads = ks_threads(p);
         // index form: no LDS strips; 120 VGPRs at tile 16 (four waves per SIMD), 162 at 24 (three), 204 at 32 (two);
         // strip form: ~235 VGPRs (two waves per SIMD) and 16 x threads x 16 bytes of strips
         int per_cu = std::max(1, (tile == 16 ? 16 : tile == 24 ? 12 : 8) / (threads / 64));
-        if (!t.ks_index) {
+        if (plan.form == KS_FORM_STRIP) {
             const size_t lds = (size_t)16 * threads * 16 + (size_t)tile * 65 * 4;
             per_cu = std::max(1, std::min((int)((160 * 1024) / lds), 8 / (threads / 64)));
         }

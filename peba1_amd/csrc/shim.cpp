@@ -926,6 +926,11 @@ int tfhe_hip_set_tuning(const char *name, int64_t value) {
         return 0;
     }
     if (name && std::strcmp(name, "ks_index") == 0) { Engine::get().tunings.ks_index = value != 0; return 0; }
+    if (name && std::strcmp(name, "ks_max_splits") == 0) {
+        if (value < 1 || value > 64) { set_error("ks_max_splits must be in [1, 64]"); return -1; }
+        Engine::get().tunings.ks_max_splits = (int)value;
+        return 0;
+    }
     if (name && std::strcmp(name, "br_digit_table") == 0) { Engine::get().tunings.br_digit_table = (int)value; return 0; }
     if (name && std::strcmp(name, "br8_max_rotations") == 0) { Engine::get().tunings.br8_max_rotations = (int)value; return 0; }
     if (name && std::strcmp(name, "br_tail8") == 0) { Engine::get().tunings.br_tail8 = (int)value; return 0; }
@@ -1194,24 +1199,36 @@ int tfhe_hip_test_br_plan(int32_t N, int32_t l, int32_t Bgbit, const int32_t *tu
     return 0;
 }
 
-int tfhe_hip_test_ks_plan(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
-                          int32_t cu_count, int32_t count, int64_t *out6) {
-    if (!tunings5 || !out6 || cu_count < 1 || count < 1) { set_error("test_ks_plan: bad arguments"); return -1; }
+int tfhe_hip_test_ks_plan_form(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
+                               int32_t cu_count, int32_t count, int64_t *out7) {
+    if (!tunings5 || !out7 || cu_count < 1 || count < 1) { set_error("test_ks_plan: bad arguments"); return -1; }
     LaunchTunings t;
     t.ks_target_blocks = tunings5[0]; t.ks_max_splits = tunings5[1]; t.ks_split_ties = tunings5[2];
     t.ks_tile = tunings5[3]; t.ks_index = tunings5[4];
     Params p{};
     p.n = n;
     const KsShape shape{k * N, ks_t, ks_basebit, p.ct_stride()};
-    const bool tiled = ks_tiled(t, count, shape);
+    const KsPlan plan = plan_ks(t, count, shape);             // what Engine::launch_ks runs
+    const bool tiled = plan.form != KS_FORM_PERGATE;
     const int chunk = tiled ? KS_CHUNK : count;               // launch_ks's chunks: all of `chunk` gates but the last
-    out6[0] = tiled ? 1 : 0;
-    out6[1] = tiled ? ks_tile_size(t) : 0;
-    out6[2] = chunk;
-    out6[3] = ks_splits(t, cu_count, std::min(chunk, count), shape);
-    out6[4] = ks_splits(t, cu_count, count - (count - 1) / chunk * chunk, shape);
-    out6[5] = (int64_t)ks_partial_bytes(t, cu_count, count, shape);
+    out7[0] = tiled ? 1 : 0;
+    out7[1] = plan.tile;
+    out7[2] = chunk;
+    out7[3] = ks_splits(t, cu_count, std::min(chunk, count), shape);
+    out7[4] = ks_splits(t, cu_count, count - (count - 1) / chunk * chunk, shape);
+    out7[5] = (int64_t)ks_partial_bytes(t, cu_count, count, shape);
+    out7[6] = plan.form;
     return 0;
+}
+
+// the first six words of the entry above: callers of this one provide room for six
+int tfhe_hip_test_ks_plan(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
+                          int32_t cu_count, int32_t count, int64_t *out6) {
+    int64_t out7[7];
+    if (!out6) { set_error("test_ks_plan: bad arguments"); return -1; }
+    const int rc = tfhe_hip_test_ks_plan_form(n, N, k, ks_t, ks_basebit, tunings5, cu_count, count, out7);
+    if (rc == 0) std::copy(out7, out7 + 6, out6);
+    return rc;
 }
 
 int tfhe_hip_test_wg_times(const TFheGateBootstrappingCloudKeySet *bk, int32_t width, uint64_t *times4, double *launch_ms) {

@@ -67,7 +67,8 @@ class Stats(C.Structure):
 class StatsAll(Stats):
     """The whole of TfheHipStats, what tfhe_hip_get_stats fills: ctypes lays a subclass's fields out behind its base's,
     as the header appended them (every field is 8 bytes wide: no padding in between)."""
-    _fields_ = [("lincomb_ops", C.c_uint64), ("lincomb_launches", C.c_uint64)]
+    _fields_ = [("lincomb_ops", C.c_uint64), ("lincomb_launches", C.c_uint64),
+                ("ks_pergate_launches", C.c_uint64), ("ks_strip_launches", C.c_uint64), ("ks_index_launches", C.c_uint64)]
 
 
 STATS_FIELDS = [f for f, _ in Stats._fields_] + [f for f, _ in StatsAll._fields_]
@@ -183,6 +184,7 @@ SIGNATURES = {
                                                C.c_int32, I32P, C.c_int32] + [I32P] * 16),
     "tfhe_hip_test_br_plan": (C.c_int, [C.c_int32] * 3 + [I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_ks_plan": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "tfhe_hip_test_ks_plan_form": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "tfhe_hip_kernel_negacyclic":(C.c_int, [CK, I32P, I32P, I32P, C.c_int32]),
     "tfhe_hip_kernel_bootstrap_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P]),
     "tfhe_hip_kernel_lut_bootstrap_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P, C.c_int32, I32P, I32P]),

@@ -207,19 +207,56 @@ def test_key_material_has_the_tgsw_and_key_switch_semantics_independently(oracle
             sigma = pp.bk_stdev * 2.0 ** 32 if hasattr(pp, "bk_stdev") else 2.0 ** 7
             assert worst < 8 * sigma, (who, "bootstrapping-key rows are not TGSW(s_i) under the TLWE key", worst, sigma)
 
-            K = np.asarray(ksk, dtype=np.int64).reshape(k * N, t, base, n + 1) % (1 << 32)
-            assert not K[:, :, 0, :].any()              # digit 0 subtracts nothing
-            Sf = S.reshape(-1)
-            idx = np.arange(0, k * N, 37)
-            ph = K[idx][:, :, 1:, n] - (K[idx][:, :, 1:, :n] * s).sum(axis=-1)          # [i][j][v-1]
-            jj = np.arange(t).reshape(1, t, 1)
-            vv = np.arange(1, base).reshape(1, 1, base - 1)
-            want = (Sf[idx].reshape(-1, 1, 1) * vv) << (32 - (jj + 1) * bb)
-            err = np.abs(centred(ph - want))
-            assert err.max() < 8 * 2.0 ** 17, (who, "key-switch rows are not LWE(v * S_i / base^(j+1))", int(err.max()))
-            assert err.std() > 2.0 ** 14                # ... with real noise of about 2^-15 on them
+            _assert_key_switch_rows_are_lwe_samples(who, s, S, ksk, n, N, k, t, bb)
     finally:
         ks.close()
+
+
+def _assert_key_switch_rows_are_lwe_samples(who, s, S, ksk, n, N, k, t, bb):
+    """Every key-switch row (i, j, v) is an LWE sample of v * S_i / base^(j+1) under the LWE key s, with noise of about
+    2^-15 on it; row v = 0 subtracts nothing."""
+    def centred(x):                                 # Torus32 difference as a signed integer
+        return ((x + (1 << 31)) % (1 << 32)) - (1 << 31)
+
+    base = 1 << bb
+    K = np.asarray(ksk, dtype=np.int64).reshape(k * N, t, base, n + 1) % (1 << 32)
+    assert not K[:, :, 0, :].any()              # digit 0 subtracts nothing
+    Sf = S.reshape(-1)
+    idx = np.arange(0, k * N, 37)
+    ph = K[idx][:, :, 1:, n] - (K[idx][:, :, 1:, :n] * s).sum(axis=-1)          # [i][j][v-1]
+    jj = np.arange(t).reshape(1, t, 1)
+    vv = np.arange(1, base).reshape(1, 1, base - 1)
+    want = (Sf[idx].reshape(-1, 1, 1) * vv) << (32 - (jj + 1) * bb)
+    err = np.abs(centred(ph - want))
+    assert err.max() < 8 * 2.0 ** 17, (who, "key-switch rows are not LWE(v * S_i / base^(j+1))", int(err.max()))
+    assert err.std() > 2.0 ** 14                # ... with real noise of about 2^-15 on them
+
+
+# every ks_basebit the library accepts, each with one digit and with the most digits it takes (t * bb = 31 at base 2)
+KS_STATEMENT_DECOMPOSITIONS = [(t, bb) for bb in range(1, 9) for t in sorted({1, 31 // bb})]
+
+
+@pytest.mark.parametrize("t,bb", KS_STATEMENT_DECOMPOSITIONS)
+def test_key_switch_rows_have_their_semantics_independently_in_every_base(oracle, t, bb):
+    """The key-switch half of the independent statement above, at the decompositions the built-in sets do not use: a wrong
+    digit order, message scale or row layout for a base other than 4 or a digit count other than 8 would pass the equality
+    with the oracle (one specification, written twice) and fail here.  N = 1024, n = 10, ks_stdev 2^-15 as in P128; product
+    and oracle."""
+    from peba1_amd import api
+    assert (31, 1) in KS_STATEMENT_DECOMPOSITIONS and {b for _, b in KS_STATEMENT_DECOMPOSITIONS} == set(range(1, 9))
+    n, N, k, seed = 10, 1024, 1, 0x5E7 + 64 * t + bb
+    pp = api.ParameterSet(custom=(n, N, k, 3, 7, t, bb, 2.0 ** -15, 2.0 ** -25, 0.012467))
+    ks = api.SecretKeySet(pp, seed, device=False)
+    oks = oracle.KeySet(oracle.custom_params(n=n, N=N, l=3, Bgbit=7, ks_t=t, ks_basebit=bb), seed)
+    try:
+        for who, kk in (("product", ks), ("oracle", oks)):
+            s = np.asarray(kk.lwe_key(), dtype=np.int64)
+            S = np.asarray(kk.tlwe_key(), dtype=np.int64).reshape(k, N)
+            assert set(np.unique(s)) <= {0, 1} and set(np.unique(S)) <= {0, 1} and 0.4 < S.mean() < 0.6
+            _assert_key_switch_rows_are_lwe_samples((who, t, bb), s, S, kk.ksk(), n, N, k, t, bb)
+    finally:
+        ks.close()
+        oks.close()
 
 
 def test_arith_helper_fixture_is_what_the_oracle_produces(oracle):

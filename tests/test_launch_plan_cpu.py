@@ -53,6 +53,16 @@ def ks_plan(shape, tunings, cu_count, count):
     return tuple(out)
 
 
+def ks_plan7(shape, tunings, cu_count, count):
+    """the same six words and the kernel form (tfhe_hip_test_ks_plan_form)"""
+    t = dict(KS_DEFAULTS, **tunings)
+    t5 = (C.c_int32 * 5)(*(t[k] for k in KS_DEFAULTS))
+    out = (C.c_int64 * 7)()
+    assert lib().tfhe_hip_test_ks_plan_form(*shape, t5, cu_count, count, out) == 0
+    assert tuple(out)[:6] == ks_plan(shape, tunings, cu_count, count)
+    return tuple(out)
+
+
 def counters(plans_and_keys):
     """(br_launches, br8_launches, br8_rotations) a flush adds whose levels have these (count, plan, keys with a share):
     the meaning of the three statistics in include/tfhe_hip.h, as Engine::execute() derives them from a level's plan"""
@@ -214,6 +224,25 @@ def test_ks_tile_clamp_chunks_and_narrow_launches():
     for count in (1, 31, 32, 8192, 20000):
         assert ks_plan(p128, {"ks_max_splits": 1}, 256, count)[3:] == (1, 1, 0)
     assert ks_plan(p128, {"ks_target_blocks": 1}, 256, 31)[3:] == (1, 1, 0)
+
+
+def test_ks_form_of_the_built_in_sets():
+    """The kernel form Engine::launch_ks runs and counts (ks_pergate / ks_strip / ks_index_launches) is the plan's seventh
+    word: 0 = per gate, 1 = LDS strips, 2 = index.  The built-in sets all have a tiled row width (128, 192, 320 threads)."""
+    PERGATE, STRIP, INDEX = 0, 1, 2
+    for shape in KS_SETS.values():
+        assert ks_plan7(shape, {}, 256, 32)[6] == INDEX and ks_plan7(shape, {}, 256, 31)[6] == PERGATE
+        assert ks_plan7(shape, {"ks_index": 0}, 256, 4096)[6] == STRIP
+        assert ks_plan7(shape, {"ks_index": 0, "ks_tile": 32}, 256, 4096)[:2] + ks_plan7(shape, {"ks_index": 0, "ks_tile": 32}, 256, 4096)[6:] == (1, 16, STRIP)
+        for tile in (24, 32):
+            assert ks_plan7(shape, {"ks_tile": tile}, 256, 2 * tile)[6] == INDEX
+            assert ks_plan7(shape, {"ks_tile": tile}, 256, 2 * tile - 1)[6] == PERGATE
+        for tunings in ({"ks_tile": 0}, {"ks_max_splits": 8}, {"ks_max_splits": 1}):
+            assert ks_plan7(shape, tunings, 256, 20000)[6] == PERGATE
+        for tunings in ({}, {"ks_index": 0}, {"ks_tile": 24}, {"ks_tile": 0}):
+            for count in (1, 31, 32, 64, 8192, 20000):
+                p = ks_plan7(shape, tunings, 256, count)
+                assert p[0] == (p[6] != PERGATE) and (p[1] > 0) == (p[6] != PERGATE)
 
 
 @pytest.mark.parametrize("pname", sorted(KS_SETS))

@@ -238,15 +238,19 @@ def test_ranks_follow_the_levels_the_balancer_really_gives(L):
 
 
 def test_stats_end_with_the_two_new_counters(api):
-    """The two counters stand at the END of TfheHipStats: behind everything the mirror held before, 8 bytes each."""
+    """The two counters were appended at the END of TfheHipStats as it was then: behind everything the mirror held before,
+    8 bytes each.  What was appended since (the key-switch form counters) stands behind them in turn, at the new end."""
     from peba1_amd import lib
-    assert lib.STATS_FIELDS[-3:] == ["multi_outputs", "lincomb_ops", "lincomb_launches"] and lib.STATS_FIELDS[2] == "linear_ops"
+    ks = ["ks_pergate_launches", "ks_strip_launches", "ks_index_launches"]
+    assert lib.STATS_FIELDS[-6:] == ["multi_outputs", "lincomb_ops", "lincomb_launches"] + ks and lib.STATS_FIELDS[2] == "linear_ops"
     assert len(set(lib.STATS_FIELDS)) == len(lib.STATS_FIELDS)
     assert lib.StatsAll.lincomb_ops.offset == C.sizeof(lib.Stats) == 8 * len(lib.Stats._fields_)
     assert lib.StatsAll.lincomb_launches.offset == C.sizeof(lib.Stats) + 8 and C.sizeof(lib.StatsAll) == 8 * len(lib.STATS_FIELDS)
     assert lib.StatsAll.multi_outputs.offset == C.sizeof(lib.Stats) - 8
+    assert [getattr(lib.StatsAll, f).offset for f in ks] == [C.sizeof(lib.Stats) + 16 + 8 * i for i in range(3)]
     s = api.stats()                                    # reads the whole struct, without a device
     assert list(s) == lib.STATS_FIELDS and s["lincomb_ops"] == 0 == s["lincomb_launches"]
+    assert all(s[f] == 0 for f in ks)
 
 
 # ---- refusals that need no device -------------------------------------------------------------------------------------
