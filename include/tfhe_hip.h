@@ -475,6 +475,16 @@ int tfhe_hip_test_level_plan_lin(const int32_t *ops16, const int32_t *op_keys, i
                                  int32_t *shared_with, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off, int32_t *rot_koff,
                                  int32_t *ks_koff, int32_t *rot_key, int32_t *rots10, int32_t *kss4, int32_t *lin_sizes2,
                                  int32_t *lin_level_off, int32_t *lin_launch_off, int32_t *lin_launch_rank, int32_t *lins35);
+/* The same, and the NOT launches as well -- the whole plan, so that a test can execute it: not_off [levels + 2]: the NOTs
+ * that ride on level L (0 = inputs) are descriptors [not_off[L], not_off[L + 1]); nots2 [2 * count]: {source slot,
+ * destination slot} each.  A level runs its rotations, its key switches, its NOT launch and then its linear launches. */
+int tfhe_hip_test_level_plan_full(const int32_t *ops16, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                                  int32_t balance, int32_t reuse, const int32_t *dead_slots, int32_t ndead,
+                                  const int32_t *lin_terms2, int32_t nterms, int32_t *levels_out, int32_t *ranks_out,
+                                  int32_t *shared_with, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off, int32_t *rot_koff,
+                                  int32_t *ks_koff, int32_t *rot_key, int32_t *rots10, int32_t *kss4, int32_t *lin_sizes2,
+                                  int32_t *lin_level_off, int32_t *lin_launch_off, int32_t *lin_launch_rank, int32_t *lins35,
+                                  int32_t *not_off, int32_t *nots2);
 /* ---- host-logic test entries: the launch rules of peba1_amd/csrc/launch_plan.hpp, without touching the device.
  * tfhe_hip_test_br_plan: the blind-rotate launches of a level of `count` rotations of gadget (l, Bgbit) at ring size N on
  * a card of `cu_count` CUs under tunings4 = {br_variant, br8_max_rotations, br_tail8, br_digit_table}; flags bit 0 = the

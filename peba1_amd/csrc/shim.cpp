@@ -996,9 +996,11 @@ int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int
 // the LUT index; 10: and the extract spec word.  ops = ops5, or records of 10 words when lut_ops
 // (tfhe_hip_test_level_plan_lut), or of 16 when rec_words = 16 (tfhe_hip_test_level_plan_multi: dead_slots as well).
 // lin (tfhe_hip_test_level_plan_lin): records of kind 66 name terms of lin->terms2; their part of the plan goes to lin->*
+// (tfhe_hip_test_level_plan_full: lin->not_off and lin->nots2 are set and receive LevelPlan::not_off / nots)
 struct TestLinPlan {
     const int32_t *terms2; int32_t nterms;
     int32_t *ranks_out, *sizes2, *level_off, *launch_off, *launch_rank, *descs35;
+    int32_t *not_off = nullptr, *nots2 = nullptr;            // tfhe_hip_test_level_plan_full: the NOT descriptors as well
 };
 static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
                            int32_t balance, int32_t *levels_out, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off,
@@ -1116,6 +1118,11 @@ static int test_level_plan(const int32_t *ops5, const int32_t *op_keys, int32_t 
             std::memcpy(lin->launch_rank, plan.lin_launch_rank.data(), plan.lin_launch_rank.size() * sizeof(int32_t));
             std::memcpy(lin->descs35, plan.lins.data(), plan.lins.size() * sizeof(LinDesc));
         }
+        if (lin->not_off) {
+            static_assert(sizeof(NotDesc) == 2 * sizeof(int32_t), "a NOT descriptor is two plain words");
+            std::memcpy(lin->not_off, plan.not_off.data(), plan.not_off.size() * sizeof(int32_t));
+            if (!plan.nots.empty()) std::memcpy(lin->nots2, plan.nots.data(), plan.nots.size() * sizeof(NotDesc));
+        }
     }
     sizes6[0] = plan.levels;
     sizes6[1] = (int32_t)plan.rots.size();
@@ -1183,6 +1190,26 @@ int tfhe_hip_test_level_plan_lin(const int32_t *ops16, const int32_t *op_keys, i
     if (ndead < 0 || (ndead > 0 && !dead_slots)) { set_error("test_level_plan_lin: bad dead_slots"); return -1; }
     if (nterms < 0 || (nterms > 0 && !lin_terms2)) { set_error("test_level_plan_lin: bad term table"); return -1; }
     const TestLinPlan lin{lin_terms2, nterms, ranks_out, lin_sizes2, lin_level_off, lin_launch_off, lin_launch_rank, lins35};
+    return test_level_plan(ops16, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
+                           rot_key, rots10, 10, kss4, true, reuse, shared_with, 16, dead_slots, ndead, &lin);
+}
+
+int tfhe_hip_test_level_plan_full(const int32_t *ops16, const int32_t *op_keys, int32_t count, int32_t nkeys, int32_t unit,
+                                  int32_t balance, int32_t reuse, const int32_t *dead_slots, int32_t ndead,
+                                  const int32_t *lin_terms2, int32_t nterms, int32_t *levels_out, int32_t *ranks_out,
+                                  int32_t *shared_with, int32_t *sizes6, int32_t *rot_off, int32_t *ks_off, int32_t *rot_koff,
+                                  int32_t *ks_koff, int32_t *rot_key, int32_t *rots10, int32_t *kss4, int32_t *lin_sizes2,
+                                  int32_t *lin_level_off, int32_t *lin_launch_off, int32_t *lin_launch_rank, int32_t *lins35,
+                                  int32_t *not_off, int32_t *nots2) {
+    if (!shared_with || !ranks_out || !lin_sizes2 || !lin_level_off || !lin_launch_off || !lin_launch_rank || !lins35 ||
+        !not_off || !nots2) {
+        set_error("test_level_plan_full: null output");
+        return -1;
+    }
+    if (ndead < 0 || (ndead > 0 && !dead_slots)) { set_error("test_level_plan_full: bad dead_slots"); return -1; }
+    if (nterms < 0 || (nterms > 0 && !lin_terms2)) { set_error("test_level_plan_full: bad term table"); return -1; }
+    const TestLinPlan lin{lin_terms2, nterms, ranks_out, lin_sizes2, lin_level_off, lin_launch_off, lin_launch_rank, lins35,
+                          not_off, nots2};
     return test_level_plan(ops16, op_keys, count, nkeys, unit, balance, levels_out, sizes6, rot_off, ks_off, rot_koff, ks_koff,
                            rot_key, rots10, 10, kss4, true, reuse, shared_with, 16, dead_slots, ndead, &lin);
 }

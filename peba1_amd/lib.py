@@ -182,6 +182,8 @@ SIGNATURES = {
                                                  C.c_int32] + [I32P] * 10),
     "tfhe_hip_test_level_plan_lin": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P,
                                                C.c_int32, I32P, C.c_int32] + [I32P] * 16),
+    "tfhe_hip_test_level_plan_full": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P,
+                                                C.c_int32, I32P, C.c_int32] + [I32P] * 18),
     "tfhe_hip_test_br_plan": (C.c_int, [C.c_int32] * 3 + [I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_ks_plan": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "tfhe_hip_test_ks_plan_form": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
