@@ -510,6 +510,73 @@ int tfhe_hip_test_ks_plan_form(int32_t n, int32_t N, int32_t k, int32_t ks_t, in
  * end; *launch_ms = the launch's duration between two stream events. */
 int tfhe_hip_test_wg_times(const TFheGateBootstrappingCloudKeySet *bk, int32_t width, uint64_t *times4, double *launch_ms);
 
+/* ---- packing key switch: up to N LWE samples under the LWE key -> ONE TLWE sample under the ring key ----
+ * A server returns M result bits as M samples of n + 1 words; packed, up to N of them travel as (k+1) N words and the
+ * client runs one ring decryption: coefficient j of the packed sample's phase is the phase of sample j (plus noise).
+ *
+ * A packing key belongs to a keyset and a decomposition (pk_t, pk_basebit); 0, 0 = the set's own (ks_t, ks_basebit).
+ * For i < n and p < pk_t, row[i][p] is a TLWE sample under the keyset's ring key -- uniform masks, noise of the set's
+ * bk_stdev (NOT ks_stdev: see the variance below), message the constant polynomial lwe_key[i] << (32 - (p+1) pk_basebit)
+ * -- laid out [n][t][k+1][N], the k mask polynomials of a row first, then its body; phase = body - sum_u mask_u * S_u.
+ * For samples c_0 .. c_{count-1}, 1 <= count <= N, c_j = (a_j, b_j), with t = pk_t, basebit = pk_basebit, base = 2^basebit:
+ *     prec       = 2^(32 - (1 + basebit t))                 (0 when basebit t = 32: nothing is rounded away)
+ *     d[j][i][p] = ((a_j[i] + prec) >> (32 - (p+1) basebit)) & (base - 1)        -- the digits of the existing key switch
+ *     D[i][p](X) = sum_{j < count} d[j][i][p] X^j
+ *     packed     = (0, ..., 0, sum_j b_j X^j) - sum_{i, p} D[i][p](X) * row[i][p]
+ * in Z[X]/(X^N + 1), wrapping mod 2^32 on all (k+1) N words.  Coefficient j of the phase B - sum_u A_u S_u is the phase
+ * of c_j plus noise for j < count, noise only from `count` on.
+ * Variance added to every coefficient, to first order -- COMPUTED from the definition, not measured (torus units):
+ *     key term       n t count E[d^2] bk_stdev^2,   E[d^2] = (base - 1)(2 base - 1) / 6 for uniform digits
+ *     rounding term  (n / 2) prec^2 / 3             (a uniform residue below prec in magnitude on each of the n/2 key bits
+ *                                                    that are set, on average; prec as a fraction of the torus)
+ * P128 (n = 630, t = 8, base = 4, bk_stdev = 2^-25), count = 1,024: 1.60e-8 + 6.1e-9, sigma = 1.5e-4 -- a gate output
+ * stands 1/8 from the decision boundary.  With ks_stdev = 2^-15 in its place the key term alone would be 1.7e-2,
+ * sigma = 0.13: about ONE sigma from the boundary, which is why the rows carry bk_stdev.
+ *
+ * Key generation.  tfhe_hip_new_packing_key draws the noise and the masks from two fresh ChaCha20 streams keyed by the
+ * OS, as a new keyset does; tfhe_hip_new_packing_key_seeded from ONE seeded generator (xoshiro256** through splitmix64,
+ * as the seeded keysets) started from `seed` for this key alone.  Neither touches the streams a keyset was or will be
+ * drawn from: a seeded keyset's words are the same with or without packing keys made from it.  Draw order, both forms:
+ * for i < n, for p < t: the k N mask words of row[i][p] (one `torus` draw each), then its N noise samples (one `gauss`
+ * draw each).  NULL (and the error set) for a null keyset or a refused decomposition: basebit outside 1..4,
+ * t basebit > 32, or t beyond what the kernel's accumulators take (t <= 18 at N = 1024, t <= 16 at N = 2048:
+ * peba1_amd/csrc/pack.hpp derives that bound and the CRT bound beside it).  Host only: no GPU is needed to make a
+ * key, read its words or decrypt a packed sample.
+ * tfhe_hip_new_packing_key_from_words: the cloud side -- a server that received the raw rows builds its key from them
+ * (the words are copied).  tfhe_hip_packing_key_words: a read-only view of the raw rows, *count = n t (k+1) N. */
+typedef struct TfheHipPackingKey TfheHipPackingKey;
+TfheHipPackingKey *tfhe_hip_new_packing_key(const TFheGateBootstrappingSecretKeySet *secret, int32_t pk_t, int32_t pk_basebit);
+TfheHipPackingKey *tfhe_hip_new_packing_key_seeded(const TFheGateBootstrappingSecretKeySet *secret, int32_t pk_t,
+                                                   int32_t pk_basebit, uint64_t seed);
+TfheHipPackingKey *tfhe_hip_new_packing_key_from_words(const TFheGateBootstrappingParameterSet *params, int32_t pk_t,
+                                                       int32_t pk_basebit, const Torus32 *words);
+void tfhe_hip_delete_packing_key(TfheHipPackingKey *key);
+const Torus32 *tfhe_hip_packing_key_words(const TfheHipPackingKey *key, int64_t *count);
+/* the decomposition the key was made with (0, 0 resolved); 0 / -1 */
+int tfhe_hip_packing_key_decomposition(const TfheHipPackingKey *key, int32_t *pk_t, int32_t *pk_basebit);
+/* Pack samples[0..count) (consecutive elements of one array) under cloud key `bk` of the key's parameter set into the
+ * (k+1) N words of out_words.  An observation point like tfhe_hip_export_samples: the pending recorded operations run
+ * first, then the pack is enqueued on tfhe_hip_stream(); the host form returns with the words in place.  The device
+ * form writes device memory and is stream-ordered like tfhe_hip_export_samples_device_async: it returns with the pack
+ * enqueued, and whatever the caller enqueues on that stream afterwards is ordered behind it (tfhe_hip_stream_sync()
+ * waits for it).  The key's words and their NTT image (2 n t (k+1) N words: 83 MB at P128, t = 8) reach the device at
+ * the first pack; device memory exhausted there is reported like every failure below.
+ * Return 0, or -1 with tfhe_hip_last_error() set and the call without effect: count outside 1..N, a null pointer, a
+ * sample this library did not allocate, samples or a cloud key of another parameter set than the packing key's. */
+int tfhe_hip_pack_samples(const TfheHipPackingKey *key, const LweSample *samples, int32_t count,
+                          const TFheGateBootstrappingCloudKeySet *bk, Torus32 *out_words);
+int tfhe_hip_pack_samples_device(const TfheHipPackingKey *key, const LweSample *samples, int32_t count,
+                                 const TFheGateBootstrappingCloudKeySet *bk, void *device_words);
+/* Decryption of a packed sample ((k+1) N words) on the host: the phases of all N coefficients; the bits (phase > 0) of
+ * the first `count`, 1 <= count <= N.  0 / -1. */
+int tfhe_hip_packed_phase(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *words, Torus32 *out_phases);
+int tfhe_hip_packed_decrypt_bits(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *words, int32_t count,
+                                 int32_t *out_bits);
+/* host-logic test entry: the two magnitude bounds of the pack kernel (peba1_amd/csrc/pack.hpp) for a chunk of `rows` key rows
+ * of ring size N (1024 or 2048) and digits of `basebit` bits (1..4): bit 0 set = the MAC bound refuses it, bit 1 set =
+ * the CRT bound refuses it; -1 on bad arguments.  The kernel's chunk is one mask index: rows = t. */
+int tfhe_hip_test_pack_bounds(int32_t N, int32_t rows, int32_t basebit);
+
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through
  * the device NTT (two 27-bit primes + CRT); |ip| must be < 2^12 */
@@ -537,6 +604,10 @@ int tfhe_hip_kernel_lut_bootstrap_multi_woks(const TFheGateBootstrappingCloudKey
 /* key switch of `count` extracted samples u[c] (kN+1 words) -> out[c] (n+1 words) */
 int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *u,
                               int32_t count, Torus32 *out);
+/* the pack of `count` caller-supplied samples sample_words[count][n+1] (crafted operands; no slots involved) under
+ * `key`, the twiddles of `bk`; idx_per_wg = mask indices per workgroup, 0 = what tfhe_hip_pack_samples uses */
+int tfhe_hip_kernel_pack(const TfheHipPackingKey *key, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *sample_words,
+                         int32_t count, int32_t idx_per_wg, Torus32 *out_words);
 
 #ifdef __cplusplus
 }

@@ -415,6 +415,104 @@ def lut_bootstrap_multi_batch(mo, results, inputs, coefs, c0, key):
         raise RuntimeError(last_error())
 
 
+class PackingKey:
+    """A packing key (tfhe_hip_new_packing_key*): rows [n][t][k+1][N] under the keyset's ring key that turn up to N LWE
+    samples into one ring sample -- the integers are in include/tfhe_hip.h.  t = basebit = 0: the set's own key-switch
+    decomposition.  seed: the reproducible form (tests); None draws from the OS-keyed streams."""
+
+    def __init__(self, secret, t=0, basebit=0, seed=None):
+        L = _l.load()
+        if seed is None:
+            ptr = L.tfhe_hip_new_packing_key(secret.ptr, int(t), int(basebit))
+        else:
+            ptr = L.tfhe_hip_new_packing_key_seeded(secret.ptr, int(t), int(basebit), int(seed))
+        self._take(secret.params, ptr)
+
+    def _take(self, params, ptr):
+        self.params, self.ptr = params, ptr
+        if not ptr:
+            raise ValueError("packing key rejected: " + last_error())
+        t, b = C.c_int32(), C.c_int32()
+        _l.load().tfhe_hip_packing_key_decomposition(ptr, C.byref(t), C.byref(b))
+        self.t, self.basebit = t.value, b.value
+
+    @classmethod
+    def from_words(cls, params, t, basebit, words):
+        """The cloud side: a key from the raw rows it received (n t (k+1) N words, copied)."""
+        w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+        tt, bb = (int(t), int(basebit)) if (t or basebit) else (params.ks_t, params.ks_basebit)
+        if w.size != params.n * tt * (params.k + 1) * params.N:
+            raise ValueError("a packing key of this set and decomposition holds %d words" % (params.n * tt * (params.k + 1) * params.N))
+        self = cls.__new__(cls)
+        self._take(params, _l.load().tfhe_hip_new_packing_key_from_words(params.ptr, int(t), int(basebit), _i32p(w)))
+        return self
+
+    def words(self):
+        """The raw rows, [n][t][k+1][N] (a copy)."""
+        cnt = C.c_int64()
+        p = _l.load().tfhe_hip_packing_key_words(self.ptr, C.byref(cnt))
+        pp = self.params
+        return np.ctypeslib.as_array(p, shape=(cnt.value,)).copy().reshape(pp.n, self.t, pp.k + 1, pp.N)
+
+    def close(self):
+        if self.ptr:
+            _l.load().tfhe_hip_delete_packing_key(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pack(pkey, samples, count, key, first=0):
+    """The (k+1) N words of samples[first .. first + count) packed under `pkey` (tfhe_hip_pack_samples); `samples` is a
+    CiphertextArray, `key` the keyset whose cloud key evaluates.  Pending operations run first."""
+    p = pkey.params
+    out = np.zeros((p.k + 1) * p.N, dtype=np.int32)
+    rc = _l.load().tfhe_hip_pack_samples(pkey.ptr, samples.at(first), int(count), key.cloud, _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def pack_device(pkey, samples, count, key, device_ptr, first=0):
+    """The same into device memory at `device_ptr` ((k+1) N int32 words), stream-ordered on tfhe_hip_stream()."""
+    rc = _l.load().tfhe_hip_pack_samples_device(pkey.ptr, samples.at(first), int(count), key.cloud, C.c_void_p(int(device_ptr)))
+    if rc != 0:
+        raise RuntimeError(last_error())
+
+
+def packed_phases(words, key):
+    """The phases of all N coefficients of a packed sample under the secret keyset `key` (host)."""
+    w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+    out = np.zeros(key.params.N, dtype=np.int32)
+    if _l.load().tfhe_hip_packed_phase(key.ptr, _i32p(w), _i32p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def packed_decrypt(words, count, key):
+    """The bits (phase > 0) of the first `count` coefficients of a packed sample (host)."""
+    w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+    out = np.zeros(max(int(count), 1), dtype=np.int32)
+    if _l.load().tfhe_hip_packed_decrypt_bits(key.ptr, _i32p(w), int(count), _i32p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out[:count]
+
+
+def kernel_pack(pkey, key, sample_words, idx_per_wg=0):
+    """The pack of caller-supplied sample words [count][n+1] (tfhe_hip_kernel_pack: crafted operands, no slots)."""
+    p = pkey.params
+    sw = np.ascontiguousarray(sample_words, dtype=np.int32).reshape(-1, p.words)
+    out = np.zeros((p.k + 1) * p.N, dtype=np.int32)
+    rc = _l.load().tfhe_hip_kernel_pack(pkey.ptr, key.cloud, _i32p(sw), sw.shape[0], int(idx_per_wg), _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
 LINEAR_MAX_IN = 16
 
 

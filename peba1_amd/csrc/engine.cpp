@@ -1139,4 +1139,72 @@ void Engine::run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const 
     sync_stream("negacyclic");
 }
 
+// ---- packing key switch (pack.hpp, pack.hip) ------------------------------------------------
+uint32_t *Engine::upload_pack_image(const DeviceKeyImage *key, const Torus32 *rows, int t, size_t *bytes) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const DevParams &dp = key->dp;
+    const size_t words = (size_t)dp.n * t * 2 * dp.N;
+    uint32_t scale[2];
+    (void)make_twiddles(dp.N, scale);
+    // both buffers first: a card without room for them fails here, recoverably, with nothing held
+    uint32_t *img = static_cast<uint32_t *>(recoverable_alloc(words * 2 * 4, "the NTT image of a packing key"));
+    int32_t *raw = nullptr;
+    try {
+        raw = static_cast<int32_t *>(recoverable_alloc(words * 4, "the staging copy of a packing key"));
+    } catch (const ApiError &) {
+        recoverable_free(img, words * 2 * 4);
+        throw;
+    }
+    hip_check(hipMemcpy(raw, rows, words * 4, hipMemcpyHostToDevice), "upload packing key");
+    launch_bk_transform(stream_, dp, raw, img, key->tw, dp.n * t, 2, scale);
+    hip_check(hipGetLastError(), "packing key transform launch");
+    sync_stream("packing key transform");
+    recoverable_free(raw, words * 4);
+    *bytes = words * 2 * 4;
+    return img;
+}
+
+void Engine::free_pack_image(uint32_t *img, size_t bytes) {
+    ENGINE_DEVICE_SCOPE();
+    if (!img) return;
+    if (inited_) sync_stream("sync before packing key free");
+    recoverable_free(img, bytes);
+}
+
+void Engine::run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int basebit, SlotPool *pool, const int32_t *slots,
+                      const Torus32 *raw_words, int count, int idx_per_wg, Torus32 *out, bool out_on_device, bool wait) {
+    ENGINE_DEVICE_SCOPE();
+    const DevParams &dp = key->dp;
+    PackArgs a{};
+    a.N = dp.N; a.n = dp.n; a.t = t; a.basebit = basebit; a.count = count;
+    // one mask index per workgroup: n workgroups of two waves (630 at P128) over the chip's 1,024 SIMDs
+    a.idx_per_wg = idx_per_wg > 0 ? idx_per_wg : 1;
+    a.img = img;
+    a.tw = key->tw;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    const size_t out_bytes = (size_t)2 * dp.N * 4;
+    a.partial = static_cast<int32_t *>(scratch(S_PACK_PARTIAL, (size_t)pack_groups(a.n, a.idx_per_wg) * out_bytes));
+    int32_t *dslots = slots ? static_cast<int32_t *>(scratch(S_PACK_SLOTS, (size_t)count * 4)) : nullptr;
+    int32_t *draw = slots ? nullptr : static_cast<int32_t *>(scratch(S_PACK_RAW, (size_t)count * (dp.n + 1) * 4));
+    a.out = out_on_device ? out : static_cast<int32_t *>(scratch(S_PACK_OUT, out_bytes));
+    if (slots) {
+        hip_check(hipMemcpyAsync(dslots, stage_slots(slots, count), (size_t)count * 4, hipMemcpyHostToDevice, stream_), "upload slot list");
+        a.samples = pool->data();
+        a.stride = pool->ct_stride();
+        a.slots = dslots;
+    } else {
+        hip_check(hipMemcpyAsync(draw, raw_words, (size_t)count * (dp.n + 1) * 4, hipMemcpyHostToDevice, stream_), "upload sample words");
+        a.samples = draw;
+        a.stride = dp.n + 1;
+        a.slots = nullptr;
+    }
+    if (!launch_pack(stream_, a)) api_fail("pack: arguments outside what the kernel was built for");
+    hip_check(hipGetLastError(), "pack launch");
+    if (!out_on_device) hip_check(hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, stream_), "download packed words");
+    // (the raw form's upload reads the caller's pageable memory: it waits like a host destination)
+    if (wait || !out_on_device || !slots) sync_stream("pack");
+    else note_async_io();
+}
+
 }  // namespace tfhe_hip

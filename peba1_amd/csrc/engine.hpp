@@ -13,6 +13,7 @@
 #include "br_forms.hpp"
 #include "launch_plan.hpp"
 #include "kernels.hpp"
+#include "pack.hpp"
 #include "../../include/tfhe_hip.h"
 
 // Device image of one cloud key: NTT image of BK, compact KSK, twiddles.
@@ -164,6 +165,17 @@ public:
                            int out_rows, Torus32 *u_out, Torus32 *acc_out, const char *name);
     void run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out);
     void run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const Torus32 *tp, Torus32 *res, int count);
+    // Packing key switch (pack.hpp).  upload_pack_image: the NTT image of a packing key's raw rows [n][t][2][N] under the
+    // twiddles of `key` (a cloud key of the same ring); device memory exhausted: ApiError, nothing held.  *bytes: what the
+    // image holds, for free_pack_image.
+    uint32_t *upload_pack_image(const DeviceKeyImage *key, const Torus32 *rows, int t, size_t *bytes);
+    void free_pack_image(uint32_t *img, size_t bytes);
+    // One pack of `count` samples, enqueued on the engine's stream behind whatever is there.  slots (the slot form): sample
+    // j is pool slot slots[j]; raw_words (the test form, slots null): sample j is raw_words[j][n + 1], uploaded for this
+    // call.  idx_per_wg: mask indices per workgroup, 0 = the engine's choice.  out: 2N words, host or device; a host
+    // destination, or wait, makes the call return with the words in place.
+    void run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int basebit, SlotPool *pool, const int32_t *slots,
+                  const Torus32 *raw_words, int count, int idx_per_wg, Torus32 *out, bool out_on_device, bool wait);
 
     TfheHipStats stats{};
     bool kernel_timing = false;
@@ -223,6 +235,10 @@ private:
         S_RAW_LUTS,       // raw rotations: the call's own test polynomials
         S_RAW_SPECS,      // raw rotations: the call's own extract specs
         S_PROBE_POOL, S_PROBE_ROTS, S_PROBE_TIMES, S_PROBE_EXTRACT,     // run_wg_times only (it waits for the flight first)
+        S_PACK_SLOTS,     // run_pack: the slot list
+        S_PACK_RAW,       // run_pack, raw form: the caller's sample words
+        S_PACK_PARTIAL,   // run_pack: the partial sums of the workgroups
+        S_PACK_OUT,       // run_pack: the result on its way to a host destination
     };
     void *scratch(Scratch idx, size_t bytes);
     // execute() in three steps (engine.cpp): everything that can throw, then the uploads, then one call per level

@@ -55,3 +55,12 @@ def identify(params, key, probe, templates, bound, bitsize, group=4, on_group=No
     if comm is not None:
         pd.gather_samples(comm, all_bits.ptr if all_bits is not None else None, bits.ptr, M, params.ptr)
     return bits
+
+
+def pack_match_bits(pkey, bits, key):
+    """The match bits identify() returned, packed for the way back (api.pack): one ring sample of (k+1) N words per N
+    match bits instead of n + 1 words per bit.  Returns [(words, count), ...], one entry per started N bits;
+    api.packed_decrypt(words, count, secret) gives the bits back on the client."""
+    N = pkey.params.N
+    return [(api.pack(pkey, bits, min(N, bits.count - first), key, first=first), min(N, bits.count - first))
+            for first in range(0, bits.count, N)]

@@ -193,6 +193,18 @@ SIGNATURES = {
     "tfhe_hip_kernel_lut_bootstrap_multi_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P, C.c_int32, I32P, I32P, C.c_int32,
                                                            I32P, I32P]),
     "tfhe_hip_kernel_keyswitch": (C.c_int, [CK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_new_packing_key": (C.c_void_p, [SK, C.c_int32, C.c_int32]),
+    "tfhe_hip_new_packing_key_seeded": (C.c_void_p, [SK, C.c_int32, C.c_int32, C.c_uint64]),
+    "tfhe_hip_new_packing_key_from_words": (C.c_void_p, [PS, C.c_int32, C.c_int32, I32P]),
+    "tfhe_hip_delete_packing_key": (None, [C.c_void_p]),
+    "tfhe_hip_packing_key_words": (I32P, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "tfhe_hip_packing_key_decomposition": (C.c_int, [C.c_void_p, I32P, I32P]),
+    "tfhe_hip_pack_samples": (C.c_int, [C.c_void_p, LS, C.c_int32, CK, I32P]),
+    "tfhe_hip_pack_samples_device": (C.c_int, [C.c_void_p, LS, C.c_int32, CK, C.c_void_p]),
+    "tfhe_hip_packed_phase": (C.c_int, [SK, I32P, I32P]),
+    "tfhe_hip_packed_decrypt_bits": (C.c_int, [SK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_test_pack_bounds": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "tfhe_hip_kernel_pack": (C.c_int, [C.c_void_p, CK, I32P, C.c_int32, C.c_int32, I32P]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])
