@@ -399,6 +399,11 @@ typedef struct TfheHipStats {
     uint64_t ks_pergate_launches;
     uint64_t ks_strip_launches;
     uint64_t ks_index_launches;
+    /* ring-encrypted inputs (tfhe_hip_unpack_samples*): the samples written into slots -- each also counts one in
+     * `keyswitches` -- and the extract kernel launches they took, one per chunk of 8,192 (the raw entry
+     * tfhe_hip_kernel_ring_extract counts its launches too) */
+    uint64_t unpacked_samples;
+    uint64_t unpack_launches;
 } TfheHipStats;
 void tfhe_hip_get_stats(TfheHipStats *out);
 void tfhe_hip_reset_stats(void);
@@ -577,6 +582,61 @@ int tfhe_hip_packed_decrypt_bits(const TFheGateBootstrappingSecretKeySet *secret
  * the CRT bound refuses it; -1 on bad arguments.  The kernel's chunk is one mask index: rows = t. */
 int tfhe_hip_test_pack_bounds(int32_t N, int32_t rows, int32_t basebit);
 
+/* ---- ring-encrypted inputs: ONE TLWE sample under the ring key -> up to N LWE samples under the LWE key ----
+ * The way in, as the packing key switch is the way out: a client sends N input bits as one ring sample of (k+1) N words
+ * (8 KB at N = 1,024) instead of N LWE samples of n + 1 words (2.5 MB at P128); the server opens it on the device with the
+ * sample extract and the key switch every gate ends with.  No key material beyond the cloud key is needed.  k = 1.
+ *
+ * Ring encryption (host only, no GPU is needed).  out_words is one TLWE sample under the keyset's ring key, laid out as a
+ * row of a packing key: the k mask polynomials first, then the body = sum_u mask_u * S_u + mu + e in Z[X]/(X^N + 1),
+ * wrapping mod 2^32.  The masks are uniform; the noise e has the set's bk_stdev, the ring's own fresh-sample deviation
+ * (the one the packing rows carry).  The _bits forms set mu[j] = +2^29 for a bit of 1 and -2^29 for a bit of 0 for
+ * j < count and mu[j] = 0 from `count` on, 1 <= count <= N.  The default forms draw from two fresh ChaCha20 streams keyed
+ * by the OS, as a packing key does; the seeded forms from ONE seeded generator (xoshiro256** through splitmix64) started
+ * from `seed` for this sample alone.  Draw order, both forms: the k N mask words (one `torus` draw each), then the N
+ * noise samples (one `gauss` draw each).  Neither form touches the streams a keyset or a packing key is drawn from.
+ * tfhe_hip_packed_phase and tfhe_hip_packed_decrypt_bits above decrypt such a sample: it has the layout and the key of a
+ * packed one.  Return 0, or -1 with tfhe_hip_last_error() set and out_words untouched: a null argument, count outside 1..N. */
+int tfhe_hip_ring_encrypt(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *mu, Torus32 *out_words);
+int tfhe_hip_ring_encrypt_seeded(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *mu, Torus32 *out_words,
+                                 uint64_t seed);
+int tfhe_hip_ring_encrypt_bits(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                               Torus32 *out_words);
+int tfhe_hip_ring_encrypt_bits_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                                      Torus32 *out_words, uint64_t seed);
+/* The unpack.  ring_words holds nring samples of (k+1) N words; index[j] = r N + e names coefficient e of sample r,
+ * 0 <= index[j] < nring N; index = NULL means 0, 1, ..., count - 1; an index may repeat and the list may come in any
+ * order.  result[j] = KeySwitch(Extract_e(ring sample r)) under the cloud key's own (ks_t, ks_basebit) -- the key switch
+ * of every extracted sample, the one a gate ends with -- and Extract_e as defined for the multi-output bootstrap above:
+ *     b = B[e],   a_i = A[e - i] for i <= e,   a_i = -A[N + e - i] for i > e,   everything wrapping mod 2^32.
+ * Coefficient e of the ring sample's phase is the phase of result[j], plus the key switch's noise.
+ * Variance, to first order -- COMPUTED from the definition, not measured (torus units): the ring sample's own, bk_stdev^2
+ * for a fresh one, plus the key-switch term of a gate output, N t ks_stdev^2 + (the rounding of the N / 2 key bits that are
+ * set on average, (N / 2) prec^2 / 3 with prec = 2^-(1 + basebit t)); there is NO rotation term, nothing was bootstrapped.
+ * P128 (N = 1,024, t = 8, ks_stdev = 2^-15, basebit t = 16): key term 7.6e-6, rounding term 9.9e-9, sigma = 2.8e-3.  An
+ * operand of a two-input gate may err by 1/16 (its share of the gate's 1/8 margin): 22 sigma.
+ *
+ * Semantics, as tfhe_hip_import_samples: every result is renamed into a fresh slot; all arguments are checked before
+ * anything changes.  A flush in flight is completed first (the key switch's partial-sum scratch belongs to it); recorded
+ * operations that have not run stay recorded -- they cannot name the new slots.  The host form returns with the slots
+ * written; the device form reads device memory and returns with the work enqueued on tfhe_hip_stream(), like
+ * tfhe_hip_import_samples_device_async (the caller keeps device_ring_words until the stream has passed, e.g.
+ * tfhe_hip_stream_sync()).  Host mirrors are stale until a decrypt, an export or tfhe_hip_sync_samples; in immediate mode
+ * they are refreshed on return.  Work proceeds in chunks of at most 8,192 samples: the extract scratch stays below
+ * 8,192 u_stride words whatever `count` is.
+ * result: `count` consecutive samples of one array; the scattered form takes `count` sample pointers instead (samples of
+ * several arrays, any order; a pointer given twice ends with its last value).
+ * Return 0, or -1 with tfhe_hip_last_error() set and the call without effect (results keep values and slots): a null
+ * pointer, count < 1 or nring < 1 (or nring N beyond 2^31 - 1), an index out of range, a result sample this library did
+ * not allocate or of another LWE dimension than the key's, count past the end of the result array, a null cloud key, the
+ * slot pool exhausted, device memory exhausted (tfhe_hip_test_set_alloc_cap). */
+int tfhe_hip_unpack_samples(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
+                            const int32_t *index, int32_t count, LweSample *result);
+int tfhe_hip_unpack_samples_scattered(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
+                                      const int32_t *index, int32_t count, LweSample *const *result);
+int tfhe_hip_unpack_samples_device(const TFheGateBootstrappingCloudKeySet *bk, const void *device_ring_words, int32_t nring,
+                                   const int32_t *index, int32_t count, LweSample *result);
+
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through
  * the device NTT (two 27-bit primes + CRT); |ip| must be < 2^12 */
@@ -608,6 +668,10 @@ int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const 
  * `key`, the twiddles of `bk`; idx_per_wg = mask indices per workgroup, 0 = what tfhe_hip_pack_samples uses */
 int tfhe_hip_kernel_pack(const TfheHipPackingKey *key, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *sample_words,
                          int32_t count, int32_t idx_per_wg, Torus32 *out_words);
+/* the extract kernel's output alone: u_out[j] (kN+1 words) = Extract_e(ring sample r) for index[j] = r N + e, arguments as
+ * for tfhe_hip_unpack_samples (index = NULL: 0 .. count - 1); no key switch, no slots involved */
+int tfhe_hip_kernel_ring_extract(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
+                                 const int32_t *index, int32_t count, Torus32 *u_out);
 
 #ifdef __cplusplus
 }

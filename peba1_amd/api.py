@@ -513,6 +513,95 @@ def kernel_pack(pkey, key, sample_words, idx_per_wg=0):
     return out
 
 
+def _ring_words(words, p):
+    return np.ascontiguousarray(words, dtype=np.int32).reshape(-1, (p.k + 1) * p.N)
+
+
+def ring_encrypt(mu, key, seed=None):
+    """One ring (TLWE) sample, (k+1) N words, encrypting the N torus words `mu` under the ring key of the secret keyset
+    `key` (tfhe_hip_ring_encrypt; host only).  seed: the reproducible form (tests); None draws from OS-keyed streams.
+    packed_phases / packed_decrypt decrypt it."""
+    p = key.params
+    m = np.ascontiguousarray([_wrap32(x) for x in np.asarray(mu).reshape(-1)], dtype=np.int32)
+    if m.shape != (p.N,):
+        raise ValueError("a ring sample of this parameter set carries %d words" % p.N)
+    out = np.zeros((p.k + 1) * p.N, dtype=np.int32)
+    L = _l.load()
+    rc = (L.tfhe_hip_ring_encrypt(key.ptr, _i32p(m), _i32p(out)) if seed is None
+          else L.tfhe_hip_ring_encrypt_seeded(key.ptr, _i32p(m), _i32p(out), int(seed)))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def ring_encrypt_bits(bits, key, seed=None):
+    """The same for 1..N bits: coefficient j carries +-2^29 for bit j, coefficients from len(bits) on carry 0."""
+    p = key.params
+    b = np.ascontiguousarray(bits, dtype=np.int32).reshape(-1)
+    out = np.zeros((p.k + 1) * p.N, dtype=np.int32)
+    L = _l.load()
+    rc = (L.tfhe_hip_ring_encrypt_bits(key.ptr, _i32p(b), len(b), _i32p(out)) if seed is None
+          else L.tfhe_hip_ring_encrypt_bits_seeded(key.ptr, _i32p(b), len(b), _i32p(out), int(seed)))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def _unpack_index(index, count):
+    if index is None:
+        if count is None:
+            raise ValueError("unpack needs an index list or a count")
+        return None, int(count)
+    idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+    if count is not None and int(count) != len(idx):
+        raise ValueError("count differs from the length of the index list")
+    return idx, len(idx)
+
+
+def unpack(words, key, result, index=None, count=None, first=0):
+    """Opens ring samples on the device (tfhe_hip_unpack_samples): words holds nring samples of (k+1) N words, index[j] =
+    r N + e names coefficient e of sample r (None: 0 .. count - 1), and the key switch of Extract_e lands in a fresh slot
+    of result[first + j].  result: a CiphertextArray, or a list of LweSample pointers (CiphertextArray.at) for the
+    scattered form.  key: the keyset whose cloud key evaluates.  Recorded operations stay recorded."""
+    p = key.params
+    w = _ring_words(words, p)
+    idx, n = _unpack_index(index, count)
+    L = _l.load()
+    if isinstance(result, CiphertextArray):
+        rc = L.tfhe_hip_unpack_samples(key.cloud, _i32p(w), w.shape[0], _i32p(idx) if idx is not None else None, n, result.at(first))
+    else:
+        if len(result) - first < n:
+            raise ValueError("fewer result samples than indices")
+        ptrs = (_l.LS * max(len(result) - first, 1))(*result[first:])
+        rc = L.tfhe_hip_unpack_samples_scattered(key.cloud, _i32p(w), w.shape[0], _i32p(idx) if idx is not None else None, n, ptrs)
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def unpack_device(device_ptr, nring, key, result, index=None, count=None, first=0):
+    """The same from device memory at `device_ptr` (nring (k+1) N int32 words), stream-ordered on tfhe_hip_stream(): the
+    call returns with the work enqueued; keep the memory until the stream has passed."""
+    idx, n = _unpack_index(index, count)
+    rc = _l.load().tfhe_hip_unpack_samples_device(key.cloud, C.c_void_p(int(device_ptr)), int(nring),
+                                                  _i32p(idx) if idx is not None else None, n, result.at(first))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def kernel_ring_extract(key, words, index=None, count=None):
+    """The extract kernel's rows alone (tfhe_hip_kernel_ring_extract): u[count][kN+1], no key switch."""
+    p = key.params
+    w = _ring_words(words, p)
+    idx, n = _unpack_index(index, count)
+    u = np.zeros((n, p.k * p.N + 1), dtype=np.int32)
+    rc = _l.load().tfhe_hip_kernel_ring_extract(key.cloud, _i32p(w), w.shape[0], _i32p(idx) if idx is not None else None, n, _i32p(u))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return u
+
+
 LINEAR_MAX_IN = 16
 
 
@@ -576,9 +665,16 @@ def set_tuning(name, value):
 
 
 def stats():
-    s = _l.StatsAll()
+    s = _l.StatsWhole()
     _l.load().tfhe_hip_get_stats(C.byref(s))
     return {f: getattr(s, f) for f in _l.STATS_FIELDS}
+
+
+def unpack_stats():
+    """The counters of the ring-encrypted inputs at the end of TfheHipStats: unpacked_samples, unpack_launches."""
+    s = _l.StatsWhole()
+    _l.load().tfhe_hip_get_stats(C.byref(s))
+    return {f: getattr(s, f) for f in _l.UNPACK_STATS_FIELDS}
 
 
 def last_flush_keys():

@@ -84,6 +84,26 @@ class EncryptedVector:
             a.set_words(a.words())
         return self
 
+    @classmethod
+    def from_ring(cls, params, words, nslots, bitsize, key):
+        """The server side of ring_encrypt_vector: the nslots arrays of `bitsize` samples of a template that arrived as ONE
+        ring sample of (k+1) N words, through a single scattered unpack (api.unpack).  Bit j of slot s is coefficient
+        s * bitsize + j.  key: the keyset whose cloud key evaluates."""
+        if nslots * bitsize > params.N:
+            raise ValueError("a ring sample of this parameter set carries %d bits" % params.N)
+        self = cls.__new__(cls)
+        self.slots = [api.CiphertextArray(params, bitsize) for _ in range(nslots)]
+        api.unpack(words, key, [a.at(j) for a in self.slots for j in range(bitsize)], count=nslots * bitsize)
+        return self
+
+
+def ring_encrypt_vector(values, bitsize, key, seed=None):
+    """The client side of EncryptedVector.from_ring: len(values) features of `bitsize` bits as ONE ring sample under the
+    secret keyset `key` -- bit j of value s at coefficient s * bitsize + j (8 KB for 128 x 8 bits at N = 1,024, where the
+    samples of an EncryptedVector are 2.5 MB)."""
+    bits = [(int(v) >> j) & 1 for v in values for j in range(bitsize)]
+    return api.ring_encrypt_bits(bits, key, seed=seed)
+
 
 def encrypt_number(params, value, bits, key):
     a = api.CiphertextArray(params, bits)

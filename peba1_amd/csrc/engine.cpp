@@ -1207,4 +1207,75 @@ void Engine::run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int
     else note_async_io();
 }
 
+// ---- ring-encrypted inputs (unpack.hpp, unpack.hip) -----------------------------------------
+void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, int nring, bool ring_on_device, const int32_t *index,
+                        int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait) {
+    ENGINE_DEVICE_SCOPE();
+    const DevParams &dp = key->dp;
+    const size_t ring_bytes = (size_t)nring * 2 * dp.N * 4, uw = (size_t)dp.k * dp.N + 1;
+    const int widest = std::min(count, UNPACK_CHUNK);
+    // every buffer first (scratch() may throw: nothing has been enqueued then).  The partial sums of the key switches are
+    // sized for the widest chunk and for the last one, which may be cut into more ranges
+    int32_t *dring = ring_on_device ? nullptr : static_cast<int32_t *>(scratch(S_UNPACK_RING, ring_bytes));
+    int32_t *dindex = static_cast<int32_t *>(scratch(S_UNPACK_INDEX, (size_t)count * 4));
+    KsDesc *dks = u_out ? nullptr : static_cast<KsDesc *>(scratch(S_UNPACK_KS, (size_t)count * sizeof(KsDesc)));
+    int32_t *u_buf = static_cast<int32_t *>(scratch(S_UNPACK_EXTRACT, (size_t)widest * dp.u_stride * 4));
+    if (!u_out) {
+        const int last = count - (count - 1) / UNPACK_CHUNK * UNPACK_CHUNK;
+        const size_t partial = std::max(ks_partial_bytes(tunings, cu_count_, widest, ks_shape(dp)),
+                                        ks_partial_bytes(tunings, cu_count_, last, ks_shape(dp)));
+        if (partial) (void)scratch(S_KS_PARTIAL, partial);
+    }
+    // the host copies of the index list and the descriptors: pinned, and free of the previous unpack's uploads
+    if (unpack_upload_pending_) {
+        wait_event(unpack_uploaded_, "the uploads of the previous unpack", sync_deadline_ms, diag_label);
+        unpack_upload_pending_ = false;
+    }
+    const size_t index_bytes = ((size_t)count * 4 + 15) & ~(size_t)15, host_bytes = index_bytes + (u_out ? 0 : (size_t)count * sizeof(KsDesc));
+    if (unpack_host_bytes_ < host_bytes) {
+        if (unpack_host_) hip_check(hipHostFree(unpack_host_), "free pinned unpack staging");
+        unpack_host_ = nullptr;
+        unpack_host_bytes_ = 0;
+        hip_check(hipHostMalloc(&unpack_host_, host_bytes + host_bytes / 2, hipHostMallocDefault), "pinned unpack staging");
+        unpack_host_bytes_ = host_bytes + host_bytes / 2;
+    }
+    int32_t *hindex = static_cast<int32_t *>(unpack_host_);
+    std::memcpy(hindex, index, (size_t)count * 4);
+    hip_check(hipMemcpyAsync(dindex, hindex, (size_t)count * 4, hipMemcpyHostToDevice, stream_), "upload unpack index");
+    if (!u_out) {
+        KsDesc *hks = reinterpret_cast<KsDesc *>(static_cast<char *>(unpack_host_) + index_bytes);
+        for (int j = 0; j < count; ++j) hks[j] = KsDesc{j % UNPACK_CHUNK, -1, 0, slots[j]};
+        hip_check(hipMemcpyAsync(dks, hks, (size_t)count * sizeof(KsDesc), hipMemcpyHostToDevice, stream_), "upload unpack ks");
+    }
+    if (!unpack_uploaded_) hip_check(hipEventCreateWithFlags(&unpack_uploaded_, hipEventDisableTiming), "unpack upload event");
+    hip_check(hipEventRecord(unpack_uploaded_, stream_), "unpack upload event record");
+    unpack_upload_pending_ = true;
+    if (!ring_on_device) hip_check(hipMemcpyAsync(dring, ring_words, ring_bytes, hipMemcpyHostToDevice, stream_), "upload ring words");
+    std::vector<int32_t> rows;
+    if (u_out) rows.resize((size_t)widest * dp.u_stride);
+    for (int done = 0; done < count; done += UNPACK_CHUNK) {
+        const int cnt = std::min(UNPACK_CHUNK, count - done);
+        const UnpackArgs a{dp.N, cnt, dp.u_stride, ring_on_device ? ring_words : dring, dindex + done, u_buf};
+        if (!launch_ring_extract(stream_, a)) api_fail("unpack: arguments outside what the extract kernel was built for");
+        hip_check(hipGetLastError(), "ring extract launch");
+        ++stats.unpack_launches;
+        if (u_out) {
+            hip_check(hipMemcpyAsync(rows.data(), u_buf, (size_t)cnt * dp.u_stride * 4, hipMemcpyDeviceToHost, stream_), "download extracted rows");
+            sync_stream("ring extract");
+            unpack_upload_pending_ = false;
+            unpad_rows(u_out + (size_t)done * uw, rows.data(), (size_t)cnt, uw, (size_t)dp.u_stride);
+        } else {
+            // (the next chunk's extract is ordered behind this key switch: one stream, one buffer)
+            launch_ks(key, u_buf, dks + done, cnt, pool->data());
+            hip_check(hipGetLastError(), "unpack keyswitch launch");
+        }
+    }
+    if (u_out) return;
+    stats.unpacked_samples += (uint64_t)count;
+    stats.keyswitches += (uint64_t)count;
+    // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
+    if (wait || !ring_on_device) { sync_stream("unpack"); unpack_upload_pending_ = false; }
+    else note_async_io();
+}
+
 }  // namespace tfhe_hip

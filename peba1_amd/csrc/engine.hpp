@@ -14,6 +14,7 @@
 #include "launch_plan.hpp"
 #include "kernels.hpp"
 #include "pack.hpp"
+#include "unpack.hpp"
 #include "../../include/tfhe_hip.h"
 
 // Device image of one cloud key: NTT image of BK, compact KSK, twiddles.
@@ -177,6 +178,15 @@ public:
     void run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int basebit, SlotPool *pool, const int32_t *slots,
                   const Torus32 *raw_words, int count, int idx_per_wg, Torus32 *out, bool out_on_device, bool wait);
 
+    // Ring-encrypted inputs (unpack.hpp): coefficient index[j] = r N + e of the nring ring samples ring_words (host, or
+    // device memory the caller keeps until the stream has passed) becomes Extract_e, in chunks of at most UNPACK_CHUNK.
+    // The slot form (u_out null): the key switch of row j goes straight into pool slot slots[j]; wait = false returns with
+    // the work enqueued on the engine's stream.  The raw test form (u_out [count][kN+1]): the extract kernel's rows alone,
+    // no key switch.  The caller has checked every index and waited for the flight.  Every buffer is sized before
+    // anything is enqueued: an ApiError (device memory exhausted) leaves nothing written.
+    void run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, int nring, bool ring_on_device, const int32_t *index,
+                    int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait);
+
     TfheHipStats stats{};
     bool kernel_timing = false;
     // the launch rules' tunings (launch_plan.hpp; written by ensure_init()'s environment reads and tfhe_hip_set_tuning)
@@ -229,7 +239,7 @@ private:
         S_NEGA_TP = S_RAW_POOL, S_NEGA_IP = S_RAW_ACC,     // run_negacyclic's two operands share those buffers
         S_NEGA_IMG,       // raw, run_negacyclic: the transform of tp
         S_NEGA_RES,       // raw, run_negacyclic: the products
-        S_KS_PARTIAL,     // flush (launch_ks checks that it never grows under one), run_keyswitch: partial sums of split key switches
+        S_KS_PARTIAL,     // flush (launch_ks checks that it never grows under one), run_keyswitch, run_unpack: partial sums of split key switches
         S_KEYS,           // flush of several keys: the key table
         S_ROT_KEYS,       // flush of several keys: the key index of every rotation
         S_RAW_LUTS,       // raw rotations: the call's own test polynomials
@@ -239,6 +249,10 @@ private:
         S_PACK_RAW,       // run_pack, raw form: the caller's sample words
         S_PACK_PARTIAL,   // run_pack: the partial sums of the workgroups
         S_PACK_OUT,       // run_pack: the result on its way to a host destination
+        S_UNPACK_RING,    // run_unpack: the ring words on their way from a host source
+        S_UNPACK_INDEX,   // run_unpack: the index list
+        S_UNPACK_KS,      // run_unpack: the key-switch descriptors (row j -> slot j)
+        S_UNPACK_EXTRACT, // run_unpack: the extracted samples of one chunk
     };
     void *scratch(Scratch idx, size_t bytes);
     // execute() in three steps (engine.cpp): everything that can throw, then the uploads, then one call per level
@@ -259,6 +273,12 @@ private:
     bool in_flight_ = false;
     std::chrono::steady_clock::time_point flight_t0_;
     int32_t *stage_slots(const int32_t *slots, int count);
+    // run_unpack's index list and descriptors on the host, in pinned memory that grows on demand: an upload nobody waited
+    // for reads it, so the next unpack waits for the event behind the uploads (not for the stream) before it writes there
+    void *unpack_host_ = nullptr;
+    size_t unpack_host_bytes_ = 0;
+    hipEvent_t unpack_uploaded_ = nullptr;
+    bool unpack_upload_pending_ = false;
     int32_t *slot_ring_ = nullptr;
     size_t slot_ring_pos_ = 0;
     int device_ = 0;

@@ -1324,6 +1324,8 @@ int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const 
 
 // The host side of the packing key switch is compiled as part of this object too (it uses the array headers above).
 #include "pack_host.cpp"
+// and that of the ring-encrypted inputs, behind it (it uses the negacyclic product defined there)
+#include "unpack_host.cpp"
 
 // The recorder is compiled as part of this object.  build.sh is one of the files kernels_sha16 hashes (kernel_id.py): a new
 // host source named there would mark every committed counter summary stale although no kernel changed.

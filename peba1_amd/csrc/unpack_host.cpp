@@ -1,0 +1,169 @@
+// unpack_host.cpp -- host side of the ring-encrypted inputs: the ring encryption and the C ABI of the unpack
+// (include/tfhe_hip.h "ring-encrypted inputs").  Compiled as part of shim.cpp's object behind pack_host.cpp: it uses the
+// array headers and the guarded entry wrappers defined there and pack_host.cpp's negacyclic product.  No arithmetic of
+// the unpack itself happens here (unpack.hip, then the key-switch kernels); encryption runs on the CPU like that of the
+// LWE samples.
+
+namespace {
+
+// The draw order (include/tfhe_hip.h): the kN mask words, then the N noise samples.
+void ring_encrypt_into(const TfheHipSecretKey &sk, const Torus32 *mu, Rng &secret, Rng &mask, Torus32 *out) {
+    const int N = sk.p.N, k = sk.p.k;
+    uint32_t *smp = reinterpret_cast<uint32_t *>(out), *body = smp + (size_t)k * N;
+    for (int u = 0; u < k; ++u)
+        for (int j = 0; j < N; ++j) smp[(size_t)u * N + j] = (uint32_t)mask.torus();
+    for (int j = 0; j < N; ++j) body[j] = (uint32_t)dtot32(secret.gauss(sk.p.bk_stdev)) + (uint32_t)mu[j];
+    for (int u = 0; u < k; ++u) pack_add_mul_by_bits(body, smp + (size_t)u * N, sk.tlwe_key.data() + (size_t)u * N, N, 1u);
+}
+
+int ring_encrypt_impl(const char *who, const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *mu, const int32_t *bits,
+                      int32_t count, Torus32 *out, const uint64_t *seed) {
+    if (!secret || !secret->lwe_key || (!mu && !bits) || !out) { set_error(std::string(who) + ": null argument"); return -1; }
+    const TfheHipSecretKey &sk = *secret->lwe_key;
+    const int N = sk.p.N;
+    std::vector<Torus32> msg;
+    if (bits) {
+        if (count < 1 || count > N) { set_error(std::string(who) + ": count must be in 1.." + std::to_string(N)); return -1; }
+        msg.assign((size_t)N, 0);
+        for (int32_t j = 0; j < count; ++j) msg[(size_t)j] = bits[j] ? (1 << 29) : -(1 << 29);
+        mu = msg.data();
+    }
+    if (seed) {
+        Rng both(*seed);                                  // a stream of its own, for this sample alone
+        ring_encrypt_into(sk, mu, both, both, out);
+    } else {
+        Rng noise = Rng::secure(), mask = Rng::secure();  // two fresh ChaCha20 streams, as for a packing key
+        ring_encrypt_into(sk, mu, noise, mask, out);
+    }
+    return 0;
+}
+
+// result_at(j): sample j of the results, consecutive or scattered
+template <typename At>
+int unpack_impl(const char *who, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring, int32_t nring,
+                const int32_t *index, int32_t count, bool have_result, bool consecutive, At result_at, bool device_src) {
+    const std::string w = std::string(who) + ": ";
+    if (!ring || !have_result) api_fail(w + "null ring words or result");
+    if (!bk || !bk->bk) api_fail(w + "null cloud key");
+    if (count < 1 || nring < 1) api_fail(w + "count and nring must be at least 1");
+    const Params &p = bk->bk->p;
+    const int64_t ncoef = (int64_t)nring * p.N;
+    if (ncoef > INT32_MAX) api_fail(w + "nring * N must stay below 2^31");
+    if (!index && count > ncoef) api_fail(w + "count runs past the last coefficient of the ring samples");
+    for (int32_t j = 0; index && j < count; ++j)
+        if (index[j] < 0 || index[j] >= ncoef)
+            api_fail(w + "index " + std::to_string(index[j]) + " at " + std::to_string(j) + " is outside 0.." + std::to_string(ncoef - 1));
+    auto g = recorder_lock();
+    // every result is ours, of the key's LWE dimension and not bound to the pool of another shape -- before the device is
+    // looked at and before anything changes
+    std::vector<ArrayHeader *> heads((size_t)(consecutive ? 1 : count));
+    for (int32_t j = 0; j < (consecutive ? 1 : count); ++j) {
+        LweSample *s = result_at(j);
+        if (!s) api_fail(w + "null result sample at " + std::to_string(j));
+        ArrayHeader *h = header_of(s);                    // (refuses a foreign sample)
+        if (h->n != p.n) api_fail(w + "a result belongs to a parameter set of LWE dimension " + std::to_string(h->n) +
+                                  ", the cloud key to one of " + std::to_string(p.n));
+        heads[(size_t)j] = h;
+    }
+    if (consecutive &&
+        result_at(0) - reinterpret_cast<LweSample *>(reinterpret_cast<char *>(heads[0]) + sizeof(ArrayHeader)) + count > heads[0]->count)
+        api_fail(w + "count runs past the end of the result array");
+    SlotPool *pool = pool_of_key(bk);
+    for (ArrayHeader *h : heads)
+        if (h->pool && h->pool != pool) api_fail(w + "a result lives in the pool of another ciphertext shape");
+    // a flush in flight owns the key switch's partial sums; what is recorded and has not run stays recorded
+    finish_flight_locked();
+    std::vector<int32_t> iota;
+    if (!index) {
+        iota.resize((size_t)count);
+        std::iota(iota.begin(), iota.end(), 0);
+        index = iota.data();
+    }
+    std::vector<int32_t> slots;
+    slots.reserve((size_t)count);
+    try {
+        for (int32_t j = 0; j < count; ++j) slots.push_back(alloc_slot(pool));
+        Engine::get().run_unpack(bk->bk->dev, ring, nring, device_src, index, count, pool, slots.data(), nullptr, !device_src);
+    } catch (const ApiError &) {
+        for (int32_t s : slots) pool->release(s);         // the pool or the device is full: nothing was enqueued
+        throw;
+    }
+    for (int32_t j = 0; j < count; ++j) repoint(result_at(j), pool, slots[(size_t)j]);
+    if (!deferred_mode())
+        for (int32_t j = 0; j < count; ++j) sync_sample_locked(result_at(j));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tfhe_hip_ring_encrypt(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *mu, Torus32 *out_words) {
+    if (!mu) { set_error("tfhe_hip_ring_encrypt: null argument"); return -1; }
+    return ring_encrypt_impl("tfhe_hip_ring_encrypt", secret, mu, nullptr, 0, out_words, nullptr);
+}
+int tfhe_hip_ring_encrypt_seeded(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *mu, Torus32 *out_words,
+                                 uint64_t seed) {
+    if (!mu) { set_error("tfhe_hip_ring_encrypt_seeded: null argument"); return -1; }
+    return ring_encrypt_impl("tfhe_hip_ring_encrypt_seeded", secret, mu, nullptr, 0, out_words, &seed);
+}
+int tfhe_hip_ring_encrypt_bits(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                               Torus32 *out_words) {
+    if (!bits) { set_error("tfhe_hip_ring_encrypt_bits: null argument"); return -1; }
+    return ring_encrypt_impl("tfhe_hip_ring_encrypt_bits", secret, nullptr, bits, count, out_words, nullptr);
+}
+int tfhe_hip_ring_encrypt_bits_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                                      Torus32 *out_words, uint64_t seed) {
+    if (!bits) { set_error("tfhe_hip_ring_encrypt_bits_seeded: null argument"); return -1; }
+    return ring_encrypt_impl("tfhe_hip_ring_encrypt_bits_seeded", secret, nullptr, bits, count, out_words, &seed);
+}
+
+int tfhe_hip_unpack_samples(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
+                            const int32_t *index, int32_t count, LweSample *result) {
+    return guarded_rc([&] {
+        return unpack_impl("tfhe_hip_unpack_samples", bk, ring_words, nring, index, count, result != nullptr, true,
+                           [&](int32_t j) { return result + j; }, false);
+    });
+}
+int tfhe_hip_unpack_samples_scattered(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
+                                      const int32_t *index, int32_t count, LweSample *const *result) {
+    return guarded_rc([&] {
+        return unpack_impl("tfhe_hip_unpack_samples_scattered", bk, ring_words, nring, index, count, result != nullptr, false,
+                           [&](int32_t j) { return result[j]; }, false);
+    });
+}
+int tfhe_hip_unpack_samples_device(const TFheGateBootstrappingCloudKeySet *bk, const void *device_ring_words, int32_t nring,
+                                   const int32_t *index, int32_t count, LweSample *result) {
+    return guarded_rc([&] {
+        return unpack_impl("tfhe_hip_unpack_samples_device", bk, static_cast<const Torus32 *>(device_ring_words), nring, index,
+                           count, result != nullptr, true, [&](int32_t j) { return result + j; }, true);
+    });
+}
+
+int tfhe_hip_kernel_ring_extract(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
+                                 const int32_t *index, int32_t count, Torus32 *u_out) {
+    return guarded_rc([&] {
+        const std::string w = "tfhe_hip_kernel_ring_extract: ";
+        if (!ring_words || !u_out) api_fail(w + "null argument");
+        if (!bk || !bk->bk) api_fail(w + "null cloud key");
+        if (count < 1 || nring < 1) api_fail(w + "count and nring must be at least 1");
+        const int64_t ncoef = (int64_t)nring * bk->bk->p.N;
+        if (ncoef > INT32_MAX) api_fail(w + "nring * N must stay below 2^31");
+        if (!index && count > ncoef) api_fail(w + "count runs past the last coefficient of the ring samples");
+        for (int32_t j = 0; index && j < count; ++j)
+            if (index[j] < 0 || index[j] >= ncoef) api_fail(w + "index " + std::to_string(index[j]) + " is out of range");
+        auto g = recorder_lock();
+        pool_of_key(bk);
+        finish_flight_locked();
+        std::vector<int32_t> iota;
+        if (!index) {
+            iota.resize((size_t)count);
+            std::iota(iota.begin(), iota.end(), 0);
+            index = iota.data();
+        }
+        Engine::get().run_unpack(bk->bk->dev, ring_words, nring, false, index, count, nullptr, nullptr, u_out, true);
+        return 0;
+    });
+}
+
+}  // extern "C"

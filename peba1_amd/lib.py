@@ -49,7 +49,7 @@ class SecretKeySet(C.Structure):
 
 class Stats(C.Structure):
     """TfheHipStats up to multi_outputs.  The header only ever appends fields, so this stays a prefix of the struct;
-    StatsAll below is the whole of it."""
+    StatsAll and StatsWhole below append what came since, StatsWhole being the whole of it."""
     _fields_ = [("blind_rotates", C.c_uint64), ("keyswitches", C.c_uint64), ("linear_ops", C.c_uint64),
                 ("levels", C.c_uint64), ("flushes", C.c_uint64), ("br_launches", C.c_uint64),
                 ("ms_blind_rotate", C.c_double), ("ms_keyswitch", C.c_double), ("ms_flush_wall", C.c_double),
@@ -65,13 +65,21 @@ class Stats(C.Structure):
 
 
 class StatsAll(Stats):
-    """The whole of TfheHipStats, what tfhe_hip_get_stats fills: ctypes lays a subclass's fields out behind its base's,
-    as the header appended them (every field is 8 bytes wide: no padding in between)."""
+    """TfheHipStats up to ks_index_launches: ctypes lays a subclass's fields out behind its base's, as the header appended
+    them (every field is 8 bytes wide: no padding in between).  STATS_FIELDS names these; StatsWhole below is the whole
+    struct, what tfhe_hip_get_stats fills."""
     _fields_ = [("lincomb_ops", C.c_uint64), ("lincomb_launches", C.c_uint64),
                 ("ks_pergate_launches", C.c_uint64), ("ks_strip_launches", C.c_uint64), ("ks_index_launches", C.c_uint64)]
 
 
+class StatsWhole(StatsAll):
+    """The whole of TfheHipStats: the counters of the ring-encrypted inputs stand at its end.  api.stats() reads this and
+    returns STATS_FIELDS, api.unpack_stats() the two below."""
+    _fields_ = [("unpacked_samples", C.c_uint64), ("unpack_launches", C.c_uint64)]
+
+
 STATS_FIELDS = [f for f, _ in Stats._fields_] + [f for f, _ in StatsAll._fields_]
+UNPACK_STATS_FIELDS = [f for f, _ in StatsWhole._fields_]
 
 
 PS = C.POINTER(ParameterSet)
@@ -169,7 +177,7 @@ SIGNATURES = {
     "tfhe_hip_set_tuning": (C.c_int, [C.c_char_p, C.c_int64]),
     "tfhe_hip_test_form_admissible": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int]),
     "tfhe_hip_test_set_alloc_cap": (None, [C.c_int64]),
-    "tfhe_hip_get_stats": (None, [C.POINTER(StatsAll)]),
+    "tfhe_hip_get_stats": (None, [C.POINTER(StatsWhole)]),
     "tfhe_hip_reset_stats": (None, []),
     "tfhe_hip_set_kernel_timing": (None, [C.c_int]),
     "tfhe_hip_last_flush_keys": (C.c_int, []),
@@ -205,6 +213,14 @@ SIGNATURES = {
     "tfhe_hip_packed_decrypt_bits": (C.c_int, [SK, I32P, C.c_int32, I32P]),
     "tfhe_hip_test_pack_bounds": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "tfhe_hip_kernel_pack": (C.c_int, [C.c_void_p, CK, I32P, C.c_int32, C.c_int32, I32P]),
+    "tfhe_hip_ring_encrypt": (C.c_int, [SK, I32P, I32P]),
+    "tfhe_hip_ring_encrypt_seeded": (C.c_int, [SK, I32P, I32P, C.c_uint64]),
+    "tfhe_hip_ring_encrypt_bits": (C.c_int, [SK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_ring_encrypt_bits_seeded": (C.c_int, [SK, I32P, C.c_int32, I32P, C.c_uint64]),
+    "tfhe_hip_unpack_samples": (C.c_int, [CK, I32P, C.c_int32, I32P, C.c_int32, LS]),
+    "tfhe_hip_unpack_samples_scattered": (C.c_int, [CK, I32P, C.c_int32, I32P, C.c_int32, C.POINTER(LS)]),
+    "tfhe_hip_unpack_samples_device": (C.c_int, [CK, C.c_void_p, C.c_int32, I32P, C.c_int32, LS]),
+    "tfhe_hip_kernel_ring_extract": (C.c_int, [CK, I32P, C.c_int32, I32P, C.c_int32, I32P]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])
