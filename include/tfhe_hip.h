@@ -77,7 +77,8 @@ const Torus32 *tfhe_hip_key_ksk(const TFheGateBootstrappingCloudKeySet *cloud, i
 /* ---- raw ciphertext words: n mask words then the body ---- */
 int32_t tfhe_hip_sample_words(const TFheGateBootstrappingParameterSet *params);
 /* samples[0..count) are consecutive elements of one array; words are packed
- * [count][n+1] */
+ * [count][n+1].  One call moves at most 65,536 samples through the device: more are refused ("too many samples in one
+ * packed transfer") with nothing changed. */
 int tfhe_hip_export_samples(const LweSample *samples, int32_t count,
                             const TFheGateBootstrappingParameterSet *params, Torus32 *out_words);
 int tfhe_hip_import_samples(LweSample *samples, int32_t count,
@@ -419,6 +420,12 @@ int tfhe_hip_set_batch_keys(int on);
  * `tables` (0, 1, 2 as "br_digit_table")?  A key is refused at upload when no form does; a launch falls back to an
  * admissible form (peba1_amd/csrc/br_forms.hpp).  Returns 1 or 0. ---- */
 int tfhe_hip_test_form_admissible(int form, int32_t N, int32_t l, int32_t Bgbit, int tables);
+
+/* ---- host-logic test entry: where the engine's pinned staging area (peba1_amd/csrc/host_stage.hpp) puts a reservation of
+ * `bytes`, given its write position, its capacity and whether an upload from it is outstanding, without touching the
+ * device.  out4 = {offset, 1 = the area's event is waited for first, capacity afterwards, write position afterwards}.
+ * Returns 0, -1 on bad arguments. ---- */
+int tfhe_hip_test_stage_place(int64_t pos, int64_t capacity, int32_t outstanding, int64_t bytes, int64_t *out4);
 
 /* ---- test entry: device allocations of key images, the ciphertext slot pool and the per-flush scratch that would bring their total
  * above `bytes` fail as if the card were full (0 = no cap).  Running out of device memory there is RECOVERABLE: the call

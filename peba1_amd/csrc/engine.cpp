@@ -228,17 +228,9 @@ void Engine::sync_stream(const char *what) {
     ENGINE_DEVICE_SCOPE();
     if (sync_deadline_ms <= 0) hip_check(hipStreamSynchronize(stream_), what);
     else bounded_wait([&] { return hipStreamQuery(stream_); }, what, sync_deadline_ms, diag_label);
-    io_pending_ = false;                     // whatever was enqueued without a host wait has completed too
+    stage_.idle();                           // whatever was enqueued without a host wait has completed too
 }
 
-// Stream-ordered transfers that returned without a host wait (write_/read_slots_packed with wait = false) leave an
-// event behind; host accesses of slot memory that do not go through the stream wait for it first (a
-// decrypt of a sample imported behind an ncclGather read the slot before the scatter had written it).
-void Engine::note_async_io() {
-    if (!io_event_) hip_check(hipEventCreateWithFlags(&io_event_, hipEventDisableTiming), "io event");
-    hip_check(hipEventRecord(io_event_, stream_), "io event record");
-    io_pending_ = true;
-}
 // a caller's own event (libpeba1-dist: the status words of a collective, on a stream of their own), bounded like every
 // other host wait of the library.  Takes no engine state: safe beside a flush in flight.
 void Engine::wait_event(hipEvent_t ev, const char *what, long long deadline_ms, const std::string &label) {
@@ -252,12 +244,32 @@ bool Engine::pci_bus_id(char *out, int len) {
     return hipDeviceGetPCIBusId(out, len, device_) == hipSuccess;
 }
 
-void Engine::sync_io() {
+// The pinned staging area (host_stage.hpp).  Host accesses of slot memory that do not go through the stream wait for its
+// event too (sync_io; ADVICE r3: a decrypt of a sample imported behind an ncclGather read the slot before the scatter
+// had written it): a transfer that returned without a host wait staged a list and left the event behind its launches.
+void *HostStage::reserve(size_t bytes) {
+    const StagePlace p = stage_place(pos_, capacity_, outstanding_, bytes);
+    if (p.wait) wait();
+    if (p.capacity != capacity_) {
+        if (base_) hip_check(hipHostFree(base_), "free the pinned staging area");
+        hip_check(hipHostMalloc(reinterpret_cast<void **>(&base_), p.capacity, hipHostMallocDefault), "the pinned staging area");
+        capacity_ = p.capacity;
+    }
+    pos_ = p.next;
+    outstanding_ = true, recorded_ = false;  // from here on, until a wait or a synchronised stream
+    return base_ + p.offset;
+}
+void HostStage::uploaded() {
+    if (!event_) hip_check(hipEventCreateWithFlags(&event_, hipEventDisableTiming), "staging event");
+    hip_check(hipEventRecord(event_, owner_.stream()), "staging event record");
+    outstanding_ = recorded_ = true;
+}
+void HostStage::wait() {
     ENGINE_DEVICE_SCOPE();
-    if (!io_pending_) return;
-    if (sync_deadline_ms <= 0) hip_check(hipEventSynchronize(io_event_), "stream-ordered transfer");
-    else bounded_wait([&] { return hipEventQuery(io_event_); }, "stream-ordered transfer", sync_deadline_ms, diag_label);
-    io_pending_ = false;
+    if (!outstanding_) return;
+    if (!recorded_) uploaded();              // (a call that failed behind its uploads left no event)
+    owner_.wait_event(event_, "stream-ordered transfer", owner_.sync_deadline_ms, owner_.diag_label);
+    outstanding_ = false;
 }
 
 void *Engine::scratch(Scratch idx, size_t bytes) {
@@ -571,62 +583,38 @@ void Engine::read_slot(SlotPool *pool, int32_t slot, Torus32 *a, Torus32 *b) {
     // on the engine's stream, then waited for: ordered behind everything enqueued there -- a flush, and a stream-ordered
     // import that nobody waited for (the scatter behind an ncclGather of tfhe_hip_import_samples_device_async)
     std::vector<int32_t> tmp(pool->ct_stride());
-    hip_check(hipMemcpyAsync(tmp.data(), pool->data() + (size_t)slot * pool->ct_stride(), tmp.size() * 4, hipMemcpyDeviceToHost, stream_),
-              "read_slot");
+    d2h(tmp.data(), pool->data() + (size_t)slot * pool->ct_stride(), tmp.size(), "read_slot");
     sync_stream("read_slot");
     std::memcpy(a, tmp.data(), (size_t)(pool->ct_words() - 1) * 4);
     *b = tmp[pool->ct_words() - 1];
 }
 
-// Slot lists travel through a pinned host ring, so that the stream-ordered (no host wait) forms below never read
+// The slot list goes up through the pinned staging area, so that the stream-ordered (no host wait) forms never read
 // host memory the caller has already released.
-int32_t *Engine::stage_slots(const int32_t *slots, int count) {
-    constexpr size_t RING = 1 << 16;                         // words; one transfer may use at most a quarter
-    if (!slot_ring_) hip_check(hipHostMalloc(reinterpret_cast<void **>(&slot_ring_), RING * 4, hipHostMallocDefault), "pinned slot ring");
-    if ((size_t)count > RING / 4) {                          // large lists: synchronous staging through the stream
-        sync_stream("sync before large slot list");
-        slot_ring_pos_ = 0;
-        if ((size_t)count > RING) api_fail("too many samples in one packed transfer");
-    }
-    if (slot_ring_pos_ + (size_t)count > RING) {             // wrap: everything queued so far must have read its list
-        sync_stream("sync at slot ring wrap");
-        slot_ring_pos_ = 0;
-    }
-    int32_t *h = slot_ring_ + slot_ring_pos_;
-    std::memcpy(h, slots, (size_t)count * 4);
-    slot_ring_pos_ += (size_t)count;
-    return h;
-}
-
 void Engine::write_slots_packed(SlotPool *pool, const int32_t *slots, int count, const Torus32 *words, bool on_device, bool wait) {
     ENGINE_DEVICE_SCOPE();
     if (count <= 0) return;
-    const size_t wbytes = (size_t)count * pool->ct_words() * 4;
-    int32_t *dslots = static_cast<int32_t *>(scratch(S_SLOTS, (size_t)count * 4));
-    hip_check(hipMemcpyAsync(dslots, stage_slots(slots, count), (size_t)count * 4, hipMemcpyHostToDevice, stream_), "upload slot list");
-    const int32_t *src = words;
-    if (!on_device) {
-        int32_t *dw = static_cast<int32_t *>(scratch(S_WORDS, wbytes));
-        hip_check(hipMemcpyAsync(dw, words, wbytes, hipMemcpyHostToDevice, stream_), "upload packed words");
-        src = dw;
-    }
+    if (count > MAX_PACKED_SAMPLES) api_fail("too many samples in one packed transfer");
+    const size_t nwords = (size_t)count * pool->ct_words();
+    int32_t *dslots = scratch_as<int32_t>(S_SLOTS, (size_t)count);
+    h2d_staged(dslots, slots, (size_t)count, "upload slot list");
+    const int32_t *src = on_device ? words : scratch_upload(S_WORDS, words, nwords, "upload packed words");
     launch_scatter_slots(stream_, pool->data(), pool->ct_stride(), pool->ct_words(), dslots, count, src);
-    if (wait || !on_device) sync_stream("scatter slots");
-    else note_async_io();
+    finish(wait || !on_device, "scatter slots");             // (a host source is the caller's pageable memory)
 }
 
 void Engine::read_slots_packed(SlotPool *pool, const int32_t *slots, int count, Torus32 *words, bool on_device, bool wait) {
     ENGINE_DEVICE_SCOPE();
     if (count <= 0) return;
-    const size_t wbytes = (size_t)count * pool->ct_words() * 4;
+    if (count > MAX_PACKED_SAMPLES) api_fail("too many samples in one packed transfer");
+    const size_t nwords = (size_t)count * pool->ct_words();
     // (a list in flight from an earlier stream-ordered call is read by its kernel before this copy lands: one stream)
-    int32_t *dslots = static_cast<int32_t *>(scratch(S_SLOTS, (size_t)count * 4));
-    hip_check(hipMemcpyAsync(dslots, stage_slots(slots, count), (size_t)count * 4, hipMemcpyHostToDevice, stream_), "upload slot list");
-    int32_t *dst = on_device ? words : static_cast<int32_t *>(scratch(S_WORDS, wbytes));
+    int32_t *dslots = scratch_as<int32_t>(S_SLOTS, (size_t)count);
+    h2d_staged(dslots, slots, (size_t)count, "upload slot list");
+    int32_t *dst = on_device ? words : scratch_as<int32_t>(S_WORDS, nwords);
     launch_gather_slots(stream_, pool->data(), pool->ct_stride(), pool->ct_words(), dslots, count, dst);
-    if (!on_device) hip_check(hipMemcpyAsync(words, dst, wbytes, hipMemcpyDeviceToHost, stream_), "download packed words");
-    if (wait || !on_device) sync_stream("gather slots");
-    else note_async_io();
+    if (!on_device) d2h(words, dst, nwords, "download packed words");
+    finish(wait || !on_device, "gather slots");              // (a host destination has its words on return)
 }
 
 hipEvent_t Engine::next_timing_event() {
@@ -735,9 +723,9 @@ Engine::FlushBuffers Engine::prepare_flush(const std::vector<const DeviceKeyImag
             fatal("execute: the keys of a multi-key flush differ in a parameter that evaluation reads");
     }
     FlushBuffers fb{};
-    fb.rots = static_cast<RotDesc *>(scratch(S_ROTS, plan.rots.size() * sizeof(RotDesc) + 16));
-    fb.ks = static_cast<KsDesc *>(scratch(S_KS, plan.kss.size() * sizeof(KsDesc) + 16));
-    fb.nots = static_cast<NotDesc *>(scratch(S_NOTS, plan.nots.size() * sizeof(NotDesc) + 16));
+    fb.rots = scratch_as<RotDesc>(S_ROTS, plan.rots.size(), 16);
+    fb.ks = scratch_as<KsDesc>(S_KS, plan.kss.size(), 16);
+    fb.nots = scratch_as<NotDesc>(S_NOTS, plan.nots.size(), 16);
     if (!plan.lins.empty()) {
         // (every launch range lies inside the descriptors, every descriptor inside its own arrays and inside the pool)
         if (plan.lin_level_off.size() != (size_t)plan.levels + 2 || plan.lin_launch_off.empty() ||
@@ -748,10 +736,10 @@ Engine::FlushBuffers Engine::prepare_flush(const std::vector<const DeviceKeyImag
             for (int t = 0; t < d.nin; ++t)
                 if (d.slot[t] < 0 || d.slot[t] == d.dst_slot) fatal("execute: a linear combination reads a slot it may not");
         }
-        fb.lins = static_cast<LinDesc *>(scratch(S_LINS, plan.lins.size() * sizeof(LinDesc)));
+        fb.lins = scratch_as<LinDesc>(S_LINS, plan.lins.size());
     }
     // extract buffer, sized for the widest level, and key-switch partial sums, sized by the split rule launch_ks applies
-    fb.u_buf = static_cast<int32_t *>(scratch(S_EXTRACT, (size_t)(std::max(plan.max_rots, plan.max_extracts) + 1) * key->dp.u_stride * 4));
+    fb.u_buf = scratch_as<int32_t>(S_EXTRACT, (size_t)(std::max(plan.max_rots, plan.max_extracts) + 1) * key->dp.u_stride);
     size_t partial = 0;
     const std::vector<int32_t> &ks_shares = nkeys == 1 ? plan.ks_off : plan.ks_koff;   // one key-switch launch per (level, key)
     for (size_t sg = 0; sg + 1 < ks_shares.size(); ++sg)
@@ -759,8 +747,8 @@ Engine::FlushBuffers Engine::prepare_flush(const std::vector<const DeviceKeyImag
     if (partial) (void)scratch(S_KS_PARTIAL, partial);
     // the key table and the key index of every rotation
     if (nkeys > 1) {
-        fb.keys = static_cast<DevKey *>(scratch(S_KEYS, (size_t)nkeys * sizeof(DevKey)));
-        fb.rot_keys = static_cast<int32_t *>(scratch(S_ROT_KEYS, plan.rot_key.size() * sizeof(int32_t) + 16));
+        fb.keys = scratch_as<DevKey>(S_KEYS, (size_t)nkeys);
+        fb.rot_keys = scratch_as<int32_t>(S_ROT_KEYS, plan.rot_key.size(), 16);
         plan.dev_keys.resize((size_t)nkeys);
         for (int k = 0; k < nkeys; ++k) plan.dev_keys[(size_t)k] = keys[(size_t)k]->key;
     }
@@ -790,18 +778,13 @@ Engine::FlushBuffers Engine::prepare_flush(const std::vector<const DeviceKeyImag
 void Engine::upload_flush(const FlushBuffers &fb, LevelPlan &&plan_in) {
     flight_plan_ = std::move(plan_in);               // owns the host descriptors until the uploads have certainly happened
     const LevelPlan &plan = flight_plan_;
-    if (!plan.rots.empty())
-        hip_check(hipMemcpyAsync(fb.rots, plan.rots.data(), plan.rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream_), "upload rots");
-    if (!plan.kss.empty())
-        hip_check(hipMemcpyAsync(fb.ks, plan.kss.data(), plan.kss.size() * sizeof(KsDesc), hipMemcpyHostToDevice, stream_), "upload ks");
-    if (!plan.nots.empty())
-        hip_check(hipMemcpyAsync(fb.nots, plan.nots.data(), plan.nots.size() * sizeof(NotDesc), hipMemcpyHostToDevice, stream_), "upload nots");
-    if (!plan.lins.empty())
-        hip_check(hipMemcpyAsync(fb.lins, plan.lins.data(), plan.lins.size() * sizeof(LinDesc), hipMemcpyHostToDevice, stream_), "upload lins");
+    if (!plan.rots.empty()) h2d(fb.rots, plan.rots.data(), plan.rots.size(), "upload rots");
+    if (!plan.kss.empty()) h2d(fb.ks, plan.kss.data(), plan.kss.size(), "upload ks");
+    if (!plan.nots.empty()) h2d(fb.nots, plan.nots.data(), plan.nots.size(), "upload nots");
+    if (!plan.lins.empty()) h2d(fb.lins, plan.lins.data(), plan.lins.size(), "upload lins");
     if (plan.nkeys > 1) {
-        hip_check(hipMemcpyAsync(fb.keys, plan.dev_keys.data(), plan.dev_keys.size() * sizeof(DevKey), hipMemcpyHostToDevice, stream_), "upload keys");
-        if (!plan.rot_key.empty())
-            hip_check(hipMemcpyAsync(fb.rot_keys, plan.rot_key.data(), plan.rot_key.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "upload rot keys");
+        h2d(fb.keys, plan.dev_keys.data(), plan.dev_keys.size(), "upload keys");
+        if (!plan.rot_key.empty()) h2d(fb.rot_keys, plan.rot_key.data(), plan.rot_key.size(), "upload rot keys");
     }
 }
 
@@ -999,22 +982,12 @@ void Engine::run_raw_rotations(const DeviceKeyImage *key, const Torus32 *lin, in
         if (const char *why = extract_spec_error(specs[t], dp.N)) api_fail(who + why);
     // the call's own tables, laid out like the engine's (without one: the engine's, which no descriptor here names)
     BrLaunch a{};
-    std::vector<int32_t> table;
-    if (lut_index) {
-        table = pad_rows(polys, (size_t)npolys, (size_t)dp.N, LUT_STRIDE);
-        int32_t *dluts = static_cast<int32_t *>(scratch(S_RAW_LUTS, table.size() * 4));
-        hip_check(hipMemcpyAsync(dluts, table.data(), table.size() * 4, hipMemcpyHostToDevice, stream_), "upload LUTs");
-        a.luts = dluts;
-    }
-    if (spec_index) {
-        ExtractSpec *dspecs = static_cast<ExtractSpec *>(scratch(S_RAW_SPECS, (size_t)nspecs * sizeof(ExtractSpec)));
-        hip_check(hipMemcpyAsync(dspecs, specs, (size_t)nspecs * sizeof(ExtractSpec), hipMemcpyHostToDevice, stream_), "upload specs");
-        a.specs = dspecs;
-    }
+    const std::vector<int32_t> table = lut_index ? pad_rows(polys, (size_t)npolys, (size_t)dp.N, LUT_STRIDE) : std::vector<int32_t>();
+    if (lut_index) a.luts = scratch_upload(S_RAW_LUTS, table.data(), table.size(), "upload LUTs");
+    if (spec_index) a.specs = scratch_upload(S_RAW_SPECS, specs, (size_t)nspecs, "upload specs");
     // temporary "pool": count slots holding lin
     const std::vector<int32_t> padded = pad_rows(lin, (size_t)count, (size_t)dp.n + 1, (size_t)dp.ct_stride);
-    int32_t *dpool = static_cast<int32_t *>(scratch(S_RAW_POOL, padded.size() * 4));
-    hip_check(hipMemcpyAsync(dpool, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, stream_), "upload lin");
+    a.pool = scratch_upload(S_RAW_POOL, padded.data(), padded.size(), "upload lin");
     // u_index: the outputs of the combinations before this one (a combination without a spec has one)
     std::vector<RotDesc> rots(count);
     int32_t total = 0;
@@ -1030,16 +1003,15 @@ void Engine::run_raw_rotations(const DeviceKeyImage *key, const Torus32 *lin, in
         }
         total += nout;
     }
-    RotDesc *drots = static_cast<RotDesc *>(scratch(S_ROTS, rots.size() * sizeof(RotDesc)));
-    hip_check(hipMemcpyAsync(drots, rots.data(), rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream_), "upload rots");
-    a.pool = dpool; a.rots = drots; a.count = count;
-    a.u_buf = static_cast<int32_t *>(scratch(S_EXTRACT, (size_t)(total + 1) * dp.u_stride * 4));
-    a.acc_dbg = acc_out ? static_cast<int32_t *>(scratch(S_RAW_ACC, (size_t)count * 2 * dp.N * 4)) : nullptr;
+    a.rots = scratch_upload(S_ROTS, rots.data(), rots.size(), "upload rots");
+    a.count = count;
+    a.u_buf = scratch_as<int32_t>(S_EXTRACT, (size_t)(total + 1) * dp.u_stride);
+    a.acc_dbg = acc_out ? scratch_as<int32_t>(S_RAW_ACC, (size_t)count * 2 * dp.N) : nullptr;
     launch_br(key, plan_br_launch(key, count, a.acc_dbg != nullptr), a);
     hip_check(hipGetLastError(), "blind_rotate launch");
     std::vector<int32_t> ubuf((size_t)total * dp.u_stride);
-    hip_check(hipMemcpyAsync(ubuf.data(), a.u_buf, ubuf.size() * 4, hipMemcpyDeviceToHost, stream_), "download u");
-    if (acc_out) hip_check(hipMemcpyAsync(acc_out, a.acc_dbg, (size_t)count * 2 * dp.N * 4, hipMemcpyDeviceToHost, stream_), "download acc");
+    d2h(ubuf.data(), a.u_buf, ubuf.size(), "download u");
+    if (acc_out) d2h(acc_out, a.acc_dbg, (size_t)count * 2 * dp.N, "download acc");
     sync_stream(name);
     const size_t uw = (size_t)dp.k * dp.N + 1;
     for (int c = 0; c < count; ++c) {
@@ -1054,17 +1026,15 @@ void Engine::run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int coun
     wait_flight();
     const DevParams &dp = key->dp;
     const std::vector<int32_t> padded = pad_rows(u, (size_t)count, (size_t)dp.k * dp.N + 1, (size_t)dp.u_stride);
-    int32_t *u_buf = static_cast<int32_t *>(scratch(S_EXTRACT, padded.size() * 4));
-    hip_check(hipMemcpyAsync(u_buf, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, stream_), "upload u");
+    const int32_t *u_buf = scratch_upload(S_EXTRACT, padded.data(), padded.size(), "upload u");
     std::vector<KsDesc> ks(count);
     for (int c = 0; c < count; ++c) ks[c] = KsDesc{c, -1, 0, c};
-    KsDesc *dks = static_cast<KsDesc *>(scratch(S_KS, ks.size() * sizeof(KsDesc)));
-    hip_check(hipMemcpyAsync(dks, ks.data(), ks.size() * sizeof(KsDesc), hipMemcpyHostToDevice, stream_), "upload ks");
-    int32_t *dpool = static_cast<int32_t *>(scratch(S_RAW_POOL, (size_t)count * dp.ct_stride * 4));
+    const KsDesc *dks = scratch_upload(S_KS, ks.data(), ks.size(), "upload ks");
+    int32_t *dpool = scratch_as<int32_t>(S_RAW_POOL, (size_t)count * dp.ct_stride);
     launch_ks(key, u_buf, dks, count, dpool);
     hip_check(hipGetLastError(), "keyswitch launch");
     std::vector<int32_t> res((size_t)count * dp.ct_stride);
-    hip_check(hipMemcpyAsync(res.data(), dpool, res.size() * 4, hipMemcpyDeviceToHost, stream_), "download ks");
+    d2h(res.data(), dpool, res.size(), "download ks");
     sync_stream("keyswitch");
     unpad_rows(out, res.data(), (size_t)count, (size_t)dp.n + 1, (size_t)dp.ct_stride);
     stats.keyswitches += (uint64_t)count;
@@ -1079,14 +1049,14 @@ double Engine::run_wg_times(const DeviceKeyImage *key, int width, unsigned long 
     std::vector<int32_t> host((size_t)width * dp.ct_stride);
     uint64_t x = 0x9E3779B97F4A7C15ull;
     for (auto &w : host) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; w = (int32_t)(x >> 16); }
-    int32_t *pool = static_cast<int32_t *>(scratch(S_PROBE_POOL, (size_t)width * dp.ct_stride * 4));
+    int32_t *pool = scratch_as<int32_t>(S_PROBE_POOL, (size_t)width * dp.ct_stride);
     hip_check(hipMemcpy(pool, host.data(), host.size() * 4, hipMemcpyHostToDevice), "probe pool");
     std::vector<RotDesc> rots(width);
     for (int i = 0; i < width; ++i) rots[i] = RotDesc{i, (i + 1) % width, 1, 1, -dp.mu, i};
-    RotDesc *drots = static_cast<RotDesc *>(scratch(S_PROBE_ROTS, rots.size() * sizeof(RotDesc)));
+    RotDesc *drots = scratch_as<RotDesc>(S_PROBE_ROTS, rots.size());
     hip_check(hipMemcpy(drots, rots.data(), rots.size() * sizeof(RotDesc), hipMemcpyHostToDevice), "probe rots");
-    int32_t *ubuf = static_cast<int32_t *>(scratch(S_PROBE_EXTRACT, (size_t)(width + 1) * dp.u_stride * 4));
-    unsigned long long *dtimes = static_cast<unsigned long long *>(scratch(S_PROBE_TIMES, (size_t)4 * width * 8));
+    int32_t *ubuf = scratch_as<int32_t>(S_PROBE_EXTRACT, (size_t)(width + 1) * dp.u_stride);
+    unsigned long long *dtimes = scratch_as<unsigned long long>(S_PROBE_TIMES, (size_t)4 * width);
     hipStream_t st;
     hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "probe stream");
     hipEvent_t e0, e1;
@@ -1126,16 +1096,14 @@ void Engine::run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const 
     const size_t words = (size_t)count * dp.N;
     uint32_t scale[2];
     (void)make_twiddles(dp.N, scale);
-    int32_t *dtp = static_cast<int32_t *>(scratch(S_NEGA_TP, words * 4));
-    int32_t *dip = static_cast<int32_t *>(scratch(S_NEGA_IP, words * 4));
-    uint32_t *dimg = static_cast<uint32_t *>(scratch(S_NEGA_IMG, words * 2 * 4));
-    int32_t *dres = static_cast<int32_t *>(scratch(S_NEGA_RES, words * 4));
-    hip_check(hipMemcpyAsync(dtp, tp, words * 4, hipMemcpyHostToDevice, stream_), "upload tp");
-    hip_check(hipMemcpyAsync(dip, ip, words * 4, hipMemcpyHostToDevice, stream_), "upload ip");
+    const int32_t *dtp = scratch_upload(S_NEGA_TP, tp, words, "upload tp");
+    const int32_t *dip = scratch_upload(S_NEGA_IP, ip, words, "upload ip");
+    uint32_t *dimg = scratch_as<uint32_t>(S_NEGA_IMG, words * 2);
+    int32_t *dres = scratch_as<int32_t>(S_NEGA_RES, words);
     launch_bk_transform(stream_, dp, dtp, dimg, key->tw, count, 1, scale);
     launch_negacyclic(stream_, dp, key->tw, dip, dimg, dres, count);
     hip_check(hipGetLastError(), "negacyclic launch");
-    hip_check(hipMemcpyAsync(res, dres, words * 4, hipMemcpyDeviceToHost, stream_), "download res");
+    d2h(res, dres, words, "download res");
     sync_stream("negacyclic");
 }
 
@@ -1180,31 +1148,23 @@ void Engine::run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int
     a.N = dp.N; a.n = dp.n; a.t = t; a.basebit = basebit; a.count = count;
     // one mask index per workgroup: n workgroups of two waves (630 at P128) over the chip's 1,024 SIMDs
     a.idx_per_wg = idx_per_wg > 0 ? idx_per_wg : 1;
-    a.img = img;
-    a.tw = key->tw;
+    a.img = img; a.tw = key->tw;
     // every buffer first (scratch() may throw: nothing has been enqueued then)
-    const size_t out_bytes = (size_t)2 * dp.N * 4;
-    a.partial = static_cast<int32_t *>(scratch(S_PACK_PARTIAL, (size_t)pack_groups(a.n, a.idx_per_wg) * out_bytes));
-    int32_t *dslots = slots ? static_cast<int32_t *>(scratch(S_PACK_SLOTS, (size_t)count * 4)) : nullptr;
-    int32_t *draw = slots ? nullptr : static_cast<int32_t *>(scratch(S_PACK_RAW, (size_t)count * (dp.n + 1) * 4));
-    a.out = out_on_device ? out : static_cast<int32_t *>(scratch(S_PACK_OUT, out_bytes));
-    if (slots) {
-        hip_check(hipMemcpyAsync(dslots, stage_slots(slots, count), (size_t)count * 4, hipMemcpyHostToDevice, stream_), "upload slot list");
-        a.samples = pool->data();
-        a.stride = pool->ct_stride();
-        a.slots = dslots;
-    } else {
-        hip_check(hipMemcpyAsync(draw, raw_words, (size_t)count * (dp.n + 1) * 4, hipMemcpyHostToDevice, stream_), "upload sample words");
-        a.samples = draw;
-        a.stride = dp.n + 1;
-        a.slots = nullptr;
-    }
+    const size_t out_words = (size_t)2 * dp.N, raw_words_n = (size_t)count * (dp.n + 1);
+    a.partial = scratch_as<int32_t>(S_PACK_PARTIAL, (size_t)pack_groups(a.n, a.idx_per_wg) * out_words);
+    int32_t *dslots = slots ? scratch_as<int32_t>(S_PACK_SLOTS, (size_t)count) : nullptr;
+    int32_t *draw = slots ? nullptr : scratch_as<int32_t>(S_PACK_RAW, raw_words_n);
+    a.out = out_on_device ? out : scratch_as<int32_t>(S_PACK_OUT, out_words);
+    a.samples = slots ? pool->data() : draw;
+    a.stride = slots ? pool->ct_stride() : dp.n + 1;
+    a.slots = dslots;
+    if (slots) h2d_staged(dslots, slots, (size_t)count, "upload slot list");
+    else h2d(draw, raw_words, raw_words_n, "upload sample words");
     if (!launch_pack(stream_, a)) api_fail("pack: arguments outside what the kernel was built for");
     hip_check(hipGetLastError(), "pack launch");
-    if (!out_on_device) hip_check(hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, stream_), "download packed words");
+    if (!out_on_device) d2h(out, a.out, out_words, "download packed words");
     // (the raw form's upload reads the caller's pageable memory: it waits like a host destination)
-    if (wait || !out_on_device || !slots) sync_stream("pack");
-    else note_async_io();
+    finish(wait || !out_on_device || !slots, "pack");
 }
 
 // ---- ring-encrypted inputs (unpack.hpp, unpack.hip) -----------------------------------------
@@ -1212,47 +1172,28 @@ void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, in
                         int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait) {
     ENGINE_DEVICE_SCOPE();
     const DevParams &dp = key->dp;
-    const size_t ring_bytes = (size_t)nring * 2 * dp.N * 4, uw = (size_t)dp.k * dp.N + 1;
+    const size_t ring_count = (size_t)nring * 2 * dp.N, uw = (size_t)dp.k * dp.N + 1;
     const int widest = std::min(count, UNPACK_CHUNK);
     // every buffer first (scratch() may throw: nothing has been enqueued then).  The partial sums of the key switches are
     // sized for the widest chunk and for the last one, which may be cut into more ranges
-    int32_t *dring = ring_on_device ? nullptr : static_cast<int32_t *>(scratch(S_UNPACK_RING, ring_bytes));
-    int32_t *dindex = static_cast<int32_t *>(scratch(S_UNPACK_INDEX, (size_t)count * 4));
-    KsDesc *dks = u_out ? nullptr : static_cast<KsDesc *>(scratch(S_UNPACK_KS, (size_t)count * sizeof(KsDesc)));
-    int32_t *u_buf = static_cast<int32_t *>(scratch(S_UNPACK_EXTRACT, (size_t)widest * dp.u_stride * 4));
+    int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_UNPACK_RING, ring_count);
+    int32_t *dindex = scratch_as<int32_t>(S_UNPACK_INDEX, (size_t)count);
+    KsDesc *dks = u_out ? nullptr : scratch_as<KsDesc>(S_UNPACK_KS, (size_t)count);
+    int32_t *u_buf = scratch_as<int32_t>(S_UNPACK_EXTRACT, (size_t)widest * dp.u_stride);
     if (!u_out) {
         const int last = count - (count - 1) / UNPACK_CHUNK * UNPACK_CHUNK;
         const size_t partial = std::max(ks_partial_bytes(tunings, cu_count_, widest, ks_shape(dp)),
                                         ks_partial_bytes(tunings, cu_count_, last, ks_shape(dp)));
         if (partial) (void)scratch(S_KS_PARTIAL, partial);
     }
-    // the host copies of the index list and the descriptors: pinned, and free of the previous unpack's uploads
-    if (unpack_upload_pending_) {
-        wait_event(unpack_uploaded_, "the uploads of the previous unpack", sync_deadline_ms, diag_label);
-        unpack_upload_pending_ = false;
-    }
-    const size_t index_bytes = ((size_t)count * 4 + 15) & ~(size_t)15, host_bytes = index_bytes + (u_out ? 0 : (size_t)count * sizeof(KsDesc));
-    if (unpack_host_bytes_ < host_bytes) {
-        if (unpack_host_) hip_check(hipHostFree(unpack_host_), "free pinned unpack staging");
-        unpack_host_ = nullptr;
-        unpack_host_bytes_ = 0;
-        hip_check(hipHostMalloc(&unpack_host_, host_bytes + host_bytes / 2, hipHostMallocDefault), "pinned unpack staging");
-        unpack_host_bytes_ = host_bytes + host_bytes / 2;
-    }
-    int32_t *hindex = static_cast<int32_t *>(unpack_host_);
-    std::memcpy(hindex, index, (size_t)count * 4);
-    hip_check(hipMemcpyAsync(dindex, hindex, (size_t)count * 4, hipMemcpyHostToDevice, stream_), "upload unpack index");
+    h2d_staged(dindex, index, (size_t)count, "upload unpack index");
     if (!u_out) {
-        KsDesc *hks = reinterpret_cast<KsDesc *>(static_cast<char *>(unpack_host_) + index_bytes);
+        std::vector<KsDesc> hks((size_t)count);
         for (int j = 0; j < count; ++j) hks[j] = KsDesc{j % UNPACK_CHUNK, -1, 0, slots[j]};
-        hip_check(hipMemcpyAsync(dks, hks, (size_t)count * sizeof(KsDesc), hipMemcpyHostToDevice, stream_), "upload unpack ks");
+        h2d_staged(dks, hks.data(), hks.size(), "upload unpack ks");
     }
-    if (!unpack_uploaded_) hip_check(hipEventCreateWithFlags(&unpack_uploaded_, hipEventDisableTiming), "unpack upload event");
-    hip_check(hipEventRecord(unpack_uploaded_, stream_), "unpack upload event record");
-    unpack_upload_pending_ = true;
-    if (!ring_on_device) hip_check(hipMemcpyAsync(dring, ring_words, ring_bytes, hipMemcpyHostToDevice, stream_), "upload ring words");
-    std::vector<int32_t> rows;
-    if (u_out) rows.resize((size_t)widest * dp.u_stride);
+    if (!ring_on_device) h2d(dring, ring_words, ring_count, "upload ring words");
+    std::vector<int32_t> rows(u_out ? (size_t)widest * dp.u_stride : 0);
     for (int done = 0; done < count; done += UNPACK_CHUNK) {
         const int cnt = std::min(UNPACK_CHUNK, count - done);
         const UnpackArgs a{dp.N, cnt, dp.u_stride, ring_on_device ? ring_words : dring, dindex + done, u_buf};
@@ -1260,9 +1201,8 @@ void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, in
         hip_check(hipGetLastError(), "ring extract launch");
         ++stats.unpack_launches;
         if (u_out) {
-            hip_check(hipMemcpyAsync(rows.data(), u_buf, (size_t)cnt * dp.u_stride * 4, hipMemcpyDeviceToHost, stream_), "download extracted rows");
+            d2h(rows.data(), u_buf, (size_t)cnt * dp.u_stride, "download extracted rows");
             sync_stream("ring extract");
-            unpack_upload_pending_ = false;
             unpad_rows(u_out + (size_t)done * uw, rows.data(), (size_t)cnt, uw, (size_t)dp.u_stride);
         } else {
             // (the next chunk's extract is ordered behind this key switch: one stream, one buffer)
@@ -1274,8 +1214,7 @@ void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, in
     stats.unpacked_samples += (uint64_t)count;
     stats.keyswitches += (uint64_t)count;
     // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
-    if (wait || !ring_on_device) { sync_stream("unpack"); unpack_upload_pending_ = false; }
-    else note_async_io();
+    finish(wait || !ring_on_device, "unpack");
 }
 
 }  // namespace tfhe_hip

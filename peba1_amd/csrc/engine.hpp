@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "host_keys.hpp"
+#include "host_stage.hpp"
 #include "br_forms.hpp"
 #include "launch_plan.hpp"
 #include "kernels.hpp"
@@ -53,6 +54,8 @@ void set_alloc_cap(long long bytes);
 // counted, and recycled through a free list.
 // the most slots a pool may hold (TFHE_HIP_POOL_SLOTS is clamped to it)
 constexpr size_t MAX_POOL_SLOTS = (size_t)1 << 29;
+// the most samples one export or import may name (write_ / read_slots_packed refuse more; include/tfhe_hip.h states it)
+constexpr int MAX_PACKED_SAMPLES = 1 << 16;
 
 class SlotPool {
 public:
@@ -134,7 +137,7 @@ public:
     void wait_flight();                 // completes an asynchronous execute(): waits, then reads the timing events
     // host waits (engine.cpp "host waits"): bounded by sync_deadline_ms when that is set
     void sync_stream(const char *what); // everything enqueued on the engine's stream has completed
-    void sync_io();                     // the stream-ordered transfers nobody waited for have completed
+    void sync_io() { stage_.wait(); }   // the stream-ordered transfers nobody waited for have completed
     void wait_all() { wait_flight(); sync_io(); }
     // a caller's event, bounded like the waits above (deadline and label passed in: read by the caller under the recorder lock)
     void wait_event(hipEvent_t ev, const char *what, long long deadline_ms, const std::string &label);
@@ -255,6 +258,26 @@ private:
         S_UNPACK_EXTRACT, // run_unpack: the extracted samples of one chunk
     };
     void *scratch(Scratch idx, size_t bytes);
+    // the same by element count (and `margin` bytes), and `count` elements between host and device on the engine's stream
+    template <class T> T *scratch_as(Scratch idx, size_t count, size_t margin = 0) { return static_cast<T *>(scratch(idx, count * sizeof(T) + margin)); }
+    template <class T> void h2d(T *dst, const T *src, size_t count, const char *what) {
+        hip_check(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, stream_), what);
+    }
+    template <class T> void d2h(T *dst, const T *src, size_t count, const char *what) {
+        hip_check(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, stream_), what);
+    }
+    // a host list the caller may release as soon as the call returns: up through the pinned staging area
+    template <class T> void h2d_staged(T *dst, const T *src, size_t count, const char *what) {
+        T *h = static_cast<T *>(stage_.reserve(count * sizeof(T)));
+        std::copy(src, src + count, h);
+        h2d(dst, h, count, what);
+    }
+    // size a buffer and fill it in one step -- never in a flush, a pack or an unpack: they size everything before they enqueue
+    template <class T> T *scratch_upload(Scratch idx, const T *src, size_t count, const char *what) {
+        T *d = scratch_as<T>(idx, count);
+        h2d(d, src, count, what);
+        return d;
+    }
     // execute() in three steps (engine.cpp): everything that can throw, then the uploads, then one call per level
     struct FlushBuffers { RotDesc *rots; KsDesc *ks; NotDesc *nots; int32_t *u_buf; DevKey *keys; int32_t *rot_keys; LinDesc *lins; };
     FlushBuffers prepare_flush(const std::vector<const DeviceKeyImage *> &keys, LevelPlan &plan);
@@ -263,24 +286,15 @@ private:
     // em / tail: a level whose last round went to the 8-wave form as a second launch (BrPlan::tail) -- the event between
     // the two launches and the rotations of the second, so that each kernel's time and count stay its own
     struct Timed { hipEvent_t e0, e1, e2; bool wide8; int nrot; hipEvent_t em = nullptr; int tail = 0; };
-    void note_async_io();
-    hipEvent_t io_event_ = nullptr;                     // behind the last stream-ordered transfer that returned without a wait
-    bool io_pending_ = false;
+    // the one tail of the stream-ordered entries: the stream is waited for, or the staging area's event is left behind them
+    void finish(bool host_wait, const char *what) { host_wait ? sync_stream(what) : stage_.uploaded(); }
     std::vector<Timed> flight_timed_;
     hipEvent_t flight_base_ = nullptr;
     LevelPlan flight_plan_;
     int flight_levels_ = 0;
     bool in_flight_ = false;
     std::chrono::steady_clock::time_point flight_t0_;
-    int32_t *stage_slots(const int32_t *slots, int count);
-    // run_unpack's index list and descriptors on the host, in pinned memory that grows on demand: an upload nobody waited
-    // for reads it, so the next unpack waits for the event behind the uploads (not for the stream) before it writes there
-    void *unpack_host_ = nullptr;
-    size_t unpack_host_bytes_ = 0;
-    hipEvent_t unpack_uploaded_ = nullptr;
-    bool unpack_upload_pending_ = false;
-    int32_t *slot_ring_ = nullptr;
-    size_t slot_ring_pos_ = 0;
+    HostStage stage_{*this};                            // the host lists of calls that return without a wait (host_stage.hpp)
     int device_ = 0;
     int cu_count_ = 256;
     std::atomic<bool> inited_{false};

@@ -95,13 +95,8 @@ int pack_impl(const TfheHipPackingKey *key, const LweSample *samples, int32_t co
     if (count < 1 || count > p.N) api_fail(std::string(who) + ": count must be in 1.." + std::to_string(p.N));
     if (!pack_same_set(p, bk->bk->p)) api_fail(std::string(who) + ": the cloud key belongs to another parameter set than the packing key");
     auto g = recorder_lock();
-    ArrayHeader *h = header_of(samples);                  // (refuses a foreign sample)
-    if (h->n != p.n) api_fail(std::string(who) + ": the samples belong to a parameter set of LWE dimension " + std::to_string(h->n) +
-                              ", the packing key to one of " + std::to_string(p.n));
-    if (samples - reinterpret_cast<const LweSample *>(reinterpret_cast<const char *>(h) + sizeof(ArrayHeader)) + count > h->count)
-        api_fail(std::string(who) + ": count runs past the end of the samples' array");
+    check_runs(std::string(who) + ": ", PACK_SAMPLES, [&](int32_t) { return samples; }, 1, count, p);
     SlotPool *pool = pool_of_key(bk);
-    if (h->pool && h->pool != pool) api_fail(std::string(who) + ": the samples live in the pool of another ciphertext shape");
     const uint32_t *img = pack_image(key, bk);            // out of device memory: ApiError, nothing has changed
     // an observation point like the exports: what is recorded runs first (the device form only enqueues it)
     flush_pending_locked(!device_dst);

@@ -60,6 +60,49 @@ ArrayHeader *header_of(const LweSample *sample) {
     return h;
 }
 
+// Argument checks the pack and unpack entries share (pack_host.cpp, unpack_host.cpp); w: "entry name: ".
+// Each of the `runs` runs of `count` consecutive samples from first_of(j) lies inside one array of ours, of LWE dimension
+// p.n and not bound to the pool of another ciphertext shape: the arrays first, then the pools, in the caller's words.
+// Never initialises the device.
+struct RunMessages { const char *dimension, *key_has, *past_end, *other_pool; };
+constexpr RunMessages PACK_SAMPLES{"the samples belong to a parameter set of LWE dimension ", ", the packing key to one of ",
+                                   "count runs past the end of the samples' array",
+                                   "the samples live in the pool of another ciphertext shape"};
+constexpr RunMessages UNPACK_RESULT{"a result belongs to a parameter set of LWE dimension ", ", the cloud key to one of ",
+                                    "count runs past the end of the result array",
+                                    "a result lives in the pool of another ciphertext shape"};
+template <typename At>
+void check_runs(const std::string &w, const RunMessages &say, At first_of, int32_t runs, int32_t count, const Params &p) {
+    for (int32_t j = 0; j < runs; ++j) {
+        const LweSample *first = first_of(j);
+        if (!first) api_fail(w + "null result sample at " + std::to_string(j));
+        const ArrayHeader *h = header_of(first);          // (refuses a foreign sample)
+        if (h->n != p.n) api_fail(w + say.dimension + std::to_string(h->n) + say.key_has + std::to_string(p.n));
+        if (first - reinterpret_cast<const LweSample *>(reinterpret_cast<const char *>(h) + sizeof(ArrayHeader)) + count > h->count)
+            api_fail(w + say.past_end);
+    }
+    const SlotPool *pool = Engine::get().find_pool(p);
+    for (int32_t j = 0; j < runs; ++j)
+        if (const SlotPool *bound = header_of(first_of(j))->pool; bound && bound != pool) api_fail(w + say.other_pool);
+}
+// The coefficient list of an unpack of nring ring samples of N: every index inside them, or -- index null -- 0 .. count - 1,
+// which `iota` then holds.  at: the refusal of an index names its position and the range
+const int32_t *ring_index_checked(const std::string &w, const int32_t *index, int32_t count, int32_t nring, int32_t N, bool at,
+                                  std::vector<int32_t> &iota) {
+    if (count < 1 || nring < 1) api_fail(w + "count and nring must be at least 1");
+    const int64_t ncoef = (int64_t)nring * N;
+    if (ncoef > INT32_MAX) api_fail(w + "nring * N must stay below 2^31");
+    if (!index && count > ncoef) api_fail(w + "count runs past the last coefficient of the ring samples");
+    for (int32_t j = 0; index && j < count; ++j)
+        if (index[j] < 0 || index[j] >= ncoef)
+            api_fail(at ? w + "index " + std::to_string(index[j]) + " at " + std::to_string(j) + " is outside 0.." + std::to_string(ncoef - 1)
+                        : w + "index " + std::to_string(index[j]) + " is out of range");
+    if (index) return index;
+    iota.resize((size_t)count);
+    std::iota(iota.begin(), iota.end(), 0);
+    return iota.data();
+}
+
 // Every extern "C" entry runs its body through one of these: an ApiError becomes
 // tfhe_hip_last_error() and the call has no effect (void entries) or returns -1.
 template <typename F>
@@ -453,7 +496,9 @@ static int import_impl(LweSample *samples, int32_t count, const TFheGateBootstra
         }
         return 0;
     }
-    for (int32_t i = 0; i < count; ++i) bind_pool(&samples[i], pool);    // refuse before anything changes
+    // refuse before anything changes (Engine::write_slots_packed would refuse the count with the slots already taken)
+    if (count > MAX_PACKED_SAMPLES) api_fail("too many samples in one packed transfer");
+    for (int32_t i = 0; i < count; ++i) bind_pool(&samples[i], pool);
     std::vector<int32_t> slots(count);
     for (int32_t i = 0; i < count; ++i) {
         repoint(&samples[i], pool, alloc_slot(pool));
@@ -912,6 +957,13 @@ int tfhe_hip_linear_batch(LweSample *result, int32_t nin, const LweSample *const
 void tfhe_hip_test_set_alloc_cap(int64_t bytes) {
     auto g = recorder_lock();
     set_alloc_cap((long long)bytes);
+}
+
+int tfhe_hip_test_stage_place(int64_t pos, int64_t capacity, int32_t outstanding, int64_t bytes, int64_t *out4) {
+    if (pos < 0 || capacity < 0 || bytes < 0 || !out4) { set_error("test_stage_place: bad arguments"); return -1; }
+    const StagePlace p = stage_place((size_t)pos, (size_t)capacity, outstanding != 0, (size_t)bytes);
+    out4[0] = (int64_t)p.offset; out4[1] = p.wait ? 1 : 0; out4[2] = (int64_t)p.capacity; out4[3] = (int64_t)p.next;
+    return 0;
 }
 
 int tfhe_hip_test_form_admissible(int form, int32_t N, int32_t l, int32_t Bgbit, int tables) {

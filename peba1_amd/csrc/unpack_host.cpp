@@ -45,40 +45,16 @@ int unpack_impl(const char *who, const TFheGateBootstrappingCloudKeySet *bk, con
     const std::string w = std::string(who) + ": ";
     if (!ring || !have_result) api_fail(w + "null ring words or result");
     if (!bk || !bk->bk) api_fail(w + "null cloud key");
-    if (count < 1 || nring < 1) api_fail(w + "count and nring must be at least 1");
     const Params &p = bk->bk->p;
-    const int64_t ncoef = (int64_t)nring * p.N;
-    if (ncoef > INT32_MAX) api_fail(w + "nring * N must stay below 2^31");
-    if (!index && count > ncoef) api_fail(w + "count runs past the last coefficient of the ring samples");
-    for (int32_t j = 0; index && j < count; ++j)
-        if (index[j] < 0 || index[j] >= ncoef)
-            api_fail(w + "index " + std::to_string(index[j]) + " at " + std::to_string(j) + " is outside 0.." + std::to_string(ncoef - 1));
+    std::vector<int32_t> iota;
+    index = ring_index_checked(w, index, count, nring, p.N, true, iota);
     auto g = recorder_lock();
     // every result is ours, of the key's LWE dimension and not bound to the pool of another shape -- before the device is
     // looked at and before anything changes
-    std::vector<ArrayHeader *> heads((size_t)(consecutive ? 1 : count));
-    for (int32_t j = 0; j < (consecutive ? 1 : count); ++j) {
-        LweSample *s = result_at(j);
-        if (!s) api_fail(w + "null result sample at " + std::to_string(j));
-        ArrayHeader *h = header_of(s);                    // (refuses a foreign sample)
-        if (h->n != p.n) api_fail(w + "a result belongs to a parameter set of LWE dimension " + std::to_string(h->n) +
-                                  ", the cloud key to one of " + std::to_string(p.n));
-        heads[(size_t)j] = h;
-    }
-    if (consecutive &&
-        result_at(0) - reinterpret_cast<LweSample *>(reinterpret_cast<char *>(heads[0]) + sizeof(ArrayHeader)) + count > heads[0]->count)
-        api_fail(w + "count runs past the end of the result array");
+    check_runs(w, UNPACK_RESULT, result_at, consecutive ? 1 : count, consecutive ? count : 1, p);
     SlotPool *pool = pool_of_key(bk);
-    for (ArrayHeader *h : heads)
-        if (h->pool && h->pool != pool) api_fail(w + "a result lives in the pool of another ciphertext shape");
     // a flush in flight owns the key switch's partial sums; what is recorded and has not run stays recorded
     finish_flight_locked();
-    std::vector<int32_t> iota;
-    if (!index) {
-        iota.resize((size_t)count);
-        std::iota(iota.begin(), iota.end(), 0);
-        index = iota.data();
-    }
     std::vector<int32_t> slots;
     slots.reserve((size_t)count);
     try {
@@ -146,21 +122,11 @@ int tfhe_hip_kernel_ring_extract(const TFheGateBootstrappingCloudKeySet *bk, con
         const std::string w = "tfhe_hip_kernel_ring_extract: ";
         if (!ring_words || !u_out) api_fail(w + "null argument");
         if (!bk || !bk->bk) api_fail(w + "null cloud key");
-        if (count < 1 || nring < 1) api_fail(w + "count and nring must be at least 1");
-        const int64_t ncoef = (int64_t)nring * bk->bk->p.N;
-        if (ncoef > INT32_MAX) api_fail(w + "nring * N must stay below 2^31");
-        if (!index && count > ncoef) api_fail(w + "count runs past the last coefficient of the ring samples");
-        for (int32_t j = 0; index && j < count; ++j)
-            if (index[j] < 0 || index[j] >= ncoef) api_fail(w + "index " + std::to_string(index[j]) + " is out of range");
+        std::vector<int32_t> iota;
+        index = ring_index_checked(w, index, count, nring, bk->bk->p.N, false, iota);
         auto g = recorder_lock();
         pool_of_key(bk);
         finish_flight_locked();
-        std::vector<int32_t> iota;
-        if (!index) {
-            iota.resize((size_t)count);
-            std::iota(iota.begin(), iota.end(), 0);
-            index = iota.data();
-        }
         Engine::get().run_unpack(bk->bk->dev, ring_words, nring, false, index, count, nullptr, nullptr, u_out, true);
         return 0;
     });

@@ -224,6 +224,93 @@ def test_device_form_agrees_with_the_host_form(L, small):
         o.close()
 
 
+def test_staging_area_wraps_under_stream_ordered_calls(L, small):
+    """Twelve calls back to back with no host wait in between -- four rounds of a device-form import of 12,000 samples, a
+    device-form unpack of 12,000 and a device-form export of the imported samples -- every one with a slot or index list
+    of its own.  Their host lists (48 KB, 240 KB and 48 KB a round) pass through the engine's pinned staging area, which
+    starts at 256 KB: it starts again from offset 0 at least four times and grows never.  A list written over before the
+    device had read it would move other words: every exported word is the imported one, every unpacked word the
+    reference's.  The pool is grown beforehand, so that no growth (a host wait) falls into the sequence."""
+    import torch
+    from peba1_amd import api
+    pp, ks = small
+    count, rounds = 12000, 4
+    rng = np.random.default_rng(15)
+    for warm in [api.CiphertextArray(pp, 50000) for _ in range(2)]:
+        warm.set_words(np.zeros((50000, pp.words), dtype=np.int32))
+        warm.close()
+    ring = random_ring(rng, 2, pp.N)
+    ref = U.unpack_ref(ks.ksk(), pp, ring, np.arange(2 * pp.N))          # every coefficient once; a list picks its rows
+    words = [rng.integers(U.I32_MIN, U.I32_MAX + 1, (count, pp.words), dtype=np.int64).astype(np.int32) for _ in range(rounds)]
+    index = [rng.integers(0, 2 * pp.N, count).astype(np.int32) for _ in range(rounds)]
+    dring = torch.from_numpy(ring.reshape(-1)).to("cuda:0")
+    src = [torch.from_numpy(w.reshape(-1)).to("cuda:0") for w in words]
+    dst = [torch.zeros(count * pp.words, dtype=torch.int32, device="cuda:0") for _ in range(rounds)]
+    arrays = [api.CiphertextArray(pp, count) for _ in range(rounds)]
+    results = [api.CiphertextArray(pp, count) for _ in range(rounds)]
+    torch.cuda.synchronize()
+    for r in range(rounds):
+        assert L.tfhe_hip_import_samples_device_async(arrays[r].ptr, count, pp.ptr, C.c_void_p(src[r].data_ptr())) == 0
+        api.unpack_device(dring.data_ptr(), 2, ks, results[r], index=index[r])
+        assert L.tfhe_hip_export_samples_device_async(arrays[r].ptr, count, pp.ptr, C.c_void_p(dst[r].data_ptr())) == 0
+    assert L.tfhe_hip_stream_sync() == 0
+    assert api.last_error() == ""
+    for r in range(rounds):
+        assert_words(dst[r].cpu().numpy().reshape(count, pp.words), words[r], ("exported against imported, round", r))
+        assert_words(results[r].words(), ref[index[r]], ("unpacked, round", r))
+    del dring, src, dst
+    for o in arrays + results:
+        o.close()
+
+
+def test_an_export_or_import_of_more_than_65536_samples_is_refused(L, small):
+    """65,537 samples in one export: -1 and the message, the destination, the samples and the statistics as they were;
+    65,536 of them go through.  An import of 65,537, from host or device words: refused the same way before a sample is
+    touched -- every sample keeps its slot and its value"""
+    import torch
+    from peba1_amd import api
+    pp, ks = small
+    most = 1 << 16
+    r = api.CiphertextArray(pp, most + 1)
+    tail = np.random.default_rng(16).integers(U.I32_MIN, U.I32_MAX + 1, (8, pp.words), dtype=np.int64).astype(np.int32)
+    tail_p = tail.ctypes.data_as(C.POINTER(C.c_int32))
+    assert L.tfhe_hip_import_samples(r.at(most - 7), 8, pp.ptr, tail_p) == 0
+
+    def tail_words():
+        out = np.zeros((8, pp.words), dtype=np.int32)
+        assert L.tfhe_hip_export_samples(r.at(most - 7), 8, pp.ptr, out.ctypes.data_as(C.POINTER(C.c_int32))) == 0
+        return out
+
+    dst = torch.full(((most + 1) * pp.words,), 0x5A5A5A5A, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    assert L.tfhe_hip_export_samples_device(r.ptr, most, pp.ptr, C.c_void_p(dst.data_ptr())) == 0
+    got = dst.cpu().numpy()
+    assert_words(got[(most - 7) * pp.words:most * pp.words].reshape(7, pp.words), tail[:7], "the last of 65,536")
+    assert (got[most * pp.words:] == 0x5A5A5A5A).all()
+    dst.fill_(0x5A5A5A5A)
+    torch.cuda.synchronize()
+    before = api.stats()
+    for entry in (L.tfhe_hip_export_samples_device, L.tfhe_hip_export_samples_device_async):
+        assert entry(r.ptr, most + 1, pp.ptr, C.c_void_p(dst.data_ptr())) == -1
+        assert api.last_error() == "too many samples in one packed transfer"
+        L.tfhe_hip_clear_error()
+    assert L.tfhe_hip_stream_sync() == 0
+    assert (dst.cpu().numpy() == 0x5A5A5A5A).all() and api.stats() == before
+    assert_words(tail_words(), tail, "samples after the refused export")
+    slots = [r.at(j).contents.slot for j in range(most + 1)]
+    host = np.full(((most + 1), pp.words), 0x33333333, dtype=np.int32)
+    for entry, src in ((L.tfhe_hip_import_samples, host.ctypes.data_as(C.POINTER(C.c_int32))),
+                       (L.tfhe_hip_import_samples_device, C.c_void_p(dst.data_ptr())),
+                       (L.tfhe_hip_import_samples_device_async, C.c_void_p(dst.data_ptr()))):
+        assert entry(r.ptr, most + 1, pp.ptr, src) == -1
+        assert api.last_error() == "too many samples in one packed transfer"
+        L.tfhe_hip_clear_error()
+    assert [r.at(j).contents.slot for j in range(most + 1)] == slots and api.stats() == before
+    assert_words(tail_words(), tail, "samples after the refused imports")
+    del dst
+    r.close()
+
+
 def test_exhausted_device_refuses_without_effect(L, small):
     """no room for the call's scratch: -1, the message, results with their old values and slots; fine once there is room.
     The scratch only grows, by half again plus 4 KB beyond what a call needs, and this file holds every caller of the unpack
