@@ -10,6 +10,8 @@
 #ifndef TFHE_HIP_H
 #define TFHE_HIP_H
 
+#include <stdio.h>
+
 #include "tfhe/tfhe_core.h"
 
 #ifdef __cplusplus
@@ -408,6 +410,16 @@ typedef struct TfheHipStats {
 } TfheHipStats;
 void tfhe_hip_get_stats(TfheHipStats *out);
 void tfhe_hip_reset_stats(void);
+/* seed-compressed cloud keys: the keysets whose masks were made on the device (tfhe_hip_expand_cloud_key, at first use)
+ * and the expand kernel launches that took, two per key (the raw entry tfhe_hip_kernel_expand_masks counts its one launch
+ * too); a host-expanded keyset counts nothing.  A struct and an entry of their own: TfheHipStats is allocated by the
+ * caller and filled whole, so it cannot grow under a caller built against this header's earlier form.
+ * tfhe_hip_reset_stats() clears these too. */
+typedef struct TfheHipExpandStats {
+    uint64_t expanded_keys;
+    uint64_t expand_launches;
+} TfheHipExpandStats;
+void tfhe_hip_get_expand_stats(TfheHipExpandStats *out);
 /* when on, every kernel launch is bracketed by HIP events, read back after the flush */
 void tfhe_hip_set_kernel_timing(int on);
 /* distinct cloud keys the last executed flush ran under (1 unless "batch_keys" is on; 0 before the first flush) */
@@ -643,6 +655,69 @@ int tfhe_hip_unpack_samples_scattered(const TFheGateBootstrappingCloudKeySet *bk
                                       const int32_t *index, int32_t count, LweSample *const *result);
 int tfhe_hip_unpack_samples_device(const TFheGateBootstrappingCloudKeySet *bk, const void *device_ring_words, int32_t nring,
                                    const int32_t *index, int32_t count, LweSample *result);
+
+/* ---- seed-compressed cloud keys: the public masks travel as a 40-byte seed ----
+ * More than 90 % of a cloud key's words are public masks: uniform words that carry no information.  A compressed cloud key
+ * holds the parameter set, a mask seed of ten words (ChaCha20 key[8], nonce[2]) and the bodies alone:
+ *     bk_body[n][(k+1)l][N]        one body polynomial per TGSW row
+ *     ksk_body[kN][t][base-1]      one body word per key-switch row of digit v = 1 .. base-1 (the digit-0 row is all zero
+ *                                  and is never drawn, as in a plain key)
+ * P128: 2,580,480 + 24,576 words = 10,420,224 bytes against the 103,350,272 of a plain cloud key.
+ * The stream.  Mask word number m of the key is word 2 (m mod 8) + 1 of ChaCha20 block floor(m / 8) under (key, nonce)
+ * (RFC 8439 block function with the 64-bit block counter starting at 0 in words 12, 13 and the nonce in words 14, 15:
+ * tfhe_hip_test_chacha20_block) -- what the default generator's mask stream yields on its m-th draw.  Masks are numbered
+ * in the order generate_keys draws them: first the BK in [i][row][u < k][j] order (n (k+1)l k N words), then the KSK in
+ * [i][j][v = 1 .. base-1][q < n] order.  A sequential host loop and a random-access device kernel give the same words.
+ * The expanded key is a cloud key in the plain layouts (bk [n][(k+1)l][k+1][N], ksk [kN][t][base][n+1]) whose mask words
+ * are the stream words verbatim and whose bodies are the transmitted ones.
+ * The rows.  A plain key adds the gadget term of a TGSW row with bloc < k to a MASK polynomial; a mask that comes from
+ * a public seed cannot carry it ("mask + gadget" beside the seed would publish the key bit).  Here, for row = bloc l + jj
+ * of BK_i, with mu = lwe_key[i] << (32 - (jj+1) Bgbit), in Z[X]/(X^N + 1) wrapping mod 2^32:
+ *     body = sum_u mask_u S_u + e + mu              (on coefficient 0)     for bloc = k
+ *     body = sum_u mask_u S_u + e - mu S_bloc(X)                           for bloc < k
+ * the same phase body - sum_u mask_u S_u as a plain key's row, not the same words.  KSK rows are a plain key's:
+ * body = <mask, lwe_key> + (v S_i << (32 - (j+1) basebit)) + e.
+ * tfhe_hip_new_compressed_cloud_key: a fresh cloud key for an existing secret keyset -- noise from a fresh ChaCha20 stream
+ * keyed by the OS, the mask seed ten fresh words of OS entropy.  _seeded (fixtures; NOT for keys that protect data): noise
+ * from the seeded generator (xoshiro256** through splitmix64) started from noise_seed, N gaussians per BK row, then one
+ * per KSK row, as generate_keys orders them; the mask seed as given.  _from_words: the cloud side (everything is copied).
+ * NULL and the error set: a null argument, a parameter set the kernels cannot run (the message of a refused keyset).
+ * Host only: no GPU is needed to make, read, save or host-expand one.
+ * Accessors: the seed (10 words), the two body arrays (*count set), the bytes that travel (40 + 4 * both counts).
+ * tfhe_hip_expand_cloud_key_host: a plain cloud keyset, bk and ksk filled on the host from a sequential stream; it reaches
+ * the device like any loaded keyset.  The reference, and the way for a caller without a GPU.
+ * tfhe_hip_expand_cloud_key: a cloud keyset that holds only seed and bodies.  At its first use the bodies are uploaded
+ * (10 MB at P128) and the masks are written on the card, straight into the image the kernels read; device memory
+ * exhausted there is recoverable like every key upload.  tfhe_hip_key_bk / _ksk and the cloud-key file export
+ * materialise the host words on demand; everything else works on it unchanged.  Both are deleted with
+ * delete_gate_bootstrapping_cloud_keyset; the compressed key may be deleted as soon as the call returns.
+ * Files: one more kind of the container of tfhe_io.h (parameter record, seed, both body arrays), refused like the other
+ * kinds on a wrong magic / version / kind, a declared size that does not match the parameters, or truncation. */
+typedef struct TfheHipCompressedCloudKey TfheHipCompressedCloudKey;
+TfheHipCompressedCloudKey *tfhe_hip_new_compressed_cloud_key(const TFheGateBootstrappingSecretKeySet *secret);
+TfheHipCompressedCloudKey *tfhe_hip_new_compressed_cloud_key_seeded(const TFheGateBootstrappingSecretKeySet *secret,
+                                                                    uint64_t noise_seed, const uint32_t *mask_seed10);
+TfheHipCompressedCloudKey *tfhe_hip_new_compressed_cloud_key_from_words(const TFheGateBootstrappingParameterSet *params,
+                                                                        const uint32_t *mask_seed10, const Torus32 *bk_body,
+                                                                        const Torus32 *ksk_body);
+void tfhe_hip_delete_compressed_cloud_key(TfheHipCompressedCloudKey *key);
+const uint32_t *tfhe_hip_compressed_key_seed(const TfheHipCompressedCloudKey *key);
+const Torus32 *tfhe_hip_compressed_key_bk_body(const TfheHipCompressedCloudKey *key, int64_t *count);
+const Torus32 *tfhe_hip_compressed_key_ksk_body(const TfheHipCompressedCloudKey *key, int64_t *count);
+int64_t tfhe_hip_compressed_key_bytes(const TfheHipCompressedCloudKey *key);
+TFheGateBootstrappingCloudKeySet *tfhe_hip_expand_cloud_key_host(const TfheHipCompressedCloudKey *key);
+TFheGateBootstrappingCloudKeySet *tfhe_hip_expand_cloud_key(const TfheHipCompressedCloudKey *key);
+void tfhe_hip_export_compressed_cloud_key_toFile(FILE *F, const TfheHipCompressedCloudKey *key);
+TfheHipCompressedCloudKey *tfhe_hip_new_compressed_cloud_key_fromFile(FILE *F);
+/* test entries.  tfhe_hip_kernel_expand_masks: stream words first_word .. first_word + count - 1 (count in 1 .. 2^24)
+ * from the device kernels' block function; 0 / -1.  tfhe_hip_test_key_image: the device BK image (which = 0) or the
+ * compact KSK, row padding and zero row included (which = 1), of a keyset -- uploaded now if it was not yet -- copied into
+ * out[capacity]; returns the word count (out may be NULL to ask for it), -1 on error.
+ * tfhe_hip_last_expand_ms: device time of the two expand kernels of the last device expansion, between two stream events;
+ * measured when kernel timing is on (tfhe_hip_set_kernel_timing), -1 before the first. */
+int tfhe_hip_kernel_expand_masks(const uint32_t *mask_seed10, int64_t first_word, int32_t count, uint32_t *out);
+int64_t tfhe_hip_test_key_image(const TFheGateBootstrappingCloudKeySet *cloud, int which, Torus32 *out, int64_t capacity);
+double tfhe_hip_last_expand_ms(void);
 
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through

@@ -175,6 +175,122 @@ class CloudKeySet(SecretKeySet):
     tlwe_key = lwe_key
 
 
+class CompressedCloudKey:
+    """A seed-compressed cloud key (include/tfhe_hip.h): a 40-byte mask seed and the bodies -- what a client sends in place
+    of a cloud-key file.  expand() gives a cloud keyset whose masks are made on the device at its first use, expand_host()
+    one expanded on the CPU; both are CloudKeySets (close() them)."""
+
+    def __init__(self, ptr, params):
+        if not ptr:
+            raise RuntimeError("compressed cloud key refused: " + last_error())
+        self.ptr, self.params = ptr, params
+
+    @classmethod
+    def generate(cls, secret):
+        return cls(_l.load().tfhe_hip_new_compressed_cloud_key(secret.ptr), secret.params)
+
+    @classmethod
+    def generate_seeded(cls, secret, noise_seed, mask_seed):
+        seed = np.ascontiguousarray(mask_seed, dtype=np.uint32).reshape(10)
+        return cls(_l.load().tfhe_hip_new_compressed_cloud_key_seeded(secret.ptr, noise_seed, seed.ctypes.data_as(_l.U32P)),
+                   secret.params)
+
+    @classmethod
+    def from_words(cls, params, mask_seed, bk_body, ksk_body):
+        seed = np.ascontiguousarray(mask_seed, dtype=np.uint32).reshape(10)
+        base = (1 << params.ks_basebit) - 1
+        bk = np.ascontiguousarray(bk_body, dtype=np.int32).reshape(params.n * (params.k + 1) * params.l * params.N)
+        ksk = np.ascontiguousarray(ksk_body, dtype=np.int32).reshape(params.k * params.N * params.ks_t * base)
+        return cls(_l.load().tfhe_hip_new_compressed_cloud_key_from_words(params.ptr, seed.ctypes.data_as(_l.U32P), _i32p(bk),
+                                                                          _i32p(ksk)), params)
+
+    def seed(self):
+        return np.ctypeslib.as_array(_l.load().tfhe_hip_compressed_key_seed(self.ptr), shape=(10,)).copy()
+
+    def _body(self, f):
+        cnt = C.c_int64()
+        p = f(self.ptr, C.byref(cnt))
+        return np.ctypeslib.as_array(p, shape=(cnt.value,))
+
+    def bk_body(self):
+        """int32 [n (k+1)l N]: a view of the key's words (valid until close())"""
+        return self._body(_l.load().tfhe_hip_compressed_key_bk_body)
+
+    def ksk_body(self):
+        """int32 [kN t (base-1)]: likewise"""
+        return self._body(_l.load().tfhe_hip_compressed_key_ksk_body)
+
+    @property
+    def nbytes(self):
+        """the bytes that travel: the seed and both body arrays"""
+        return int(_l.load().tfhe_hip_compressed_key_bytes(self.ptr))
+
+    def expand(self):
+        ptr = _l.load().tfhe_hip_expand_cloud_key(self.ptr)
+        if not ptr:
+            raise RuntimeError("expand failed: " + last_error())
+        return CloudKeySet(ptr)
+
+    def expand_host(self):
+        ptr = _l.load().tfhe_hip_expand_cloud_key_host(self.ptr)
+        if not ptr:
+            raise RuntimeError("expand_host failed: " + last_error())
+        return CloudKeySet(ptr)
+
+    def save(self, path):
+        with _CFile(path, "wb") as fp:
+            _l.load().tfhe_hip_export_compressed_cloud_key_toFile(fp, self.ptr)
+
+    @classmethod
+    def load(cls, path):
+        with _CFile(path, "rb") as fp:
+            ptr = _l.load().tfhe_hip_new_compressed_cloud_key_fromFile(fp)
+        if not ptr:
+            raise ValueError("cannot load a compressed cloud key from %s: %s" % (path, last_error()))
+        return cls(ptr, None)       # (the parameter set is in the file: expand().params has it)
+
+    def close(self):
+        if self.ptr:
+            _l.load().tfhe_hip_delete_compressed_cloud_key(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def kernel_expand_masks(mask_seed, first_word, count):
+    """stream words first_word .. first_word + count - 1 from the device kernels' block function (uint32 [count])"""
+    seed = np.ascontiguousarray(mask_seed, dtype=np.uint32).reshape(10)
+    out = np.zeros(count, dtype=np.uint32)
+    rc = _l.load().tfhe_hip_kernel_expand_masks(seed.ctypes.data_as(_l.U32P), first_word, count, out.ctypes.data_as(_l.U32P))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def key_image(key, which):
+    """the device BK image (which = 0) or the compact KSK with padding and zero row (which = 1) of a keyset, int32"""
+    L = _l.load()
+    L.tfhe_hip_clear_error()
+    words = L.tfhe_hip_test_key_image(key.cloud, which, None, 0)
+    if words < 0:
+        raise RuntimeError(last_error())
+    out = np.zeros(words, dtype=np.int32)
+    if L.tfhe_hip_test_key_image(key.cloud, which, _i32p(out), words) != words:
+        raise RuntimeError(last_error())
+    return out
+
+
+def expand_stats():
+    """expanded_keys, expand_launches (tfhe_hip_get_expand_stats)"""
+    s = _l.ExpandStats()
+    _l.load().tfhe_hip_get_expand_stats(C.byref(s))
+    return {f: getattr(s, f) for f in _l.EXPAND_STATS_FIELDS}
+
+
 class CiphertextArray:
     """new_gate_bootstrapping_ciphertext_array / delete_... (Math.cpp:28-30,47-49)."""
 

@@ -457,6 +457,109 @@ DeviceKeyImage *Engine::upload_key(const TfheHipCloudKey &ck) {
     return img;
 }
 
+// ---- seed-compressed cloud keys (expand.hpp, expand.hip) ------------------------------------
+DeviceKeyImage *Engine::upload_compressed_key(const TfheHipCloudKey &ck) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const Params &p = ck.p;
+    if (const char *why = unsupported_reason(p)) api_fail(why);
+    auto *img = new DeviceKeyImage();
+    img->dp = make_dev_params(p);
+    fill_form_ok(img->form_ok, p.N, p.l, p.Bgbit);
+    uint32_t scale[2];
+    const std::vector<uint32_t> tw = make_twiddles(p.N, scale);
+    const size_t bk_words = p.bk_words(), bk_body = p.bk_body_words() * 4, ksk_body = p.ksk_body_words() * 4;
+    const int stride = p.ct_stride();
+    const size_t rows = p.ksk_body_words();                   // kN t (base-1) compact rows, and the zero row behind them
+    int32_t *raw = nullptr, *dbk = nullptr, *dksk = nullptr;
+    try {
+        img->tw_bytes = tw.size() * 4;
+        img->tw = static_cast<uint32_t *>(recoverable_alloc(img->tw_bytes, "the twiddle tables of a key"));
+        img->bk_img_bytes = bk_words * 2 * 4;
+        img->bk_img = static_cast<uint32_t *>(recoverable_alloc(img->bk_img_bytes, "the bootstrapping-key image"));
+        img->ksk_bytes = (rows + 1) * (size_t)stride * 4;
+        img->ksk = static_cast<int32_t *>(recoverable_alloc(img->ksk_bytes, "the key-switching key"));
+        raw = static_cast<int32_t *>(recoverable_alloc(bk_words * 4, "the staging copy of the bootstrapping key"));
+        dbk = static_cast<int32_t *>(recoverable_alloc(bk_body, "the bodies of a compressed bootstrapping key"));
+        dksk = static_cast<int32_t *>(recoverable_alloc(ksk_body, "the bodies of a compressed key-switching key"));
+    } catch (const ApiError &) {
+        recoverable_free(dbk, bk_body);
+        recoverable_free(raw, bk_words * 4);
+        recoverable_free(img->tw, img->tw_bytes);
+        recoverable_free(img->bk_img, img->bk_img_bytes);
+        recoverable_free(img->ksk, img->ksk_bytes);
+        delete img;
+        throw;
+    }
+    hip_check(hipMemcpy(img->tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice), "upload twiddles");
+    hip_check(hipMemcpy(dbk, ck.bk_body.data(), bk_body, hipMemcpyHostToDevice), "upload bk bodies");
+    hip_check(hipMemcpy(dksk, ck.ksk_body.data(), ksk_body, hipMemcpyHostToDevice), "upload ksk bodies");
+
+    ExpandSeed seed;
+    std::memcpy(seed.key, ck.mask_seed.data(), sizeof seed.key);
+    seed.nonce[0] = ck.mask_seed[8]; seed.nonce[1] = ck.mask_seed[9];
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (kernel_timing) {
+        hip_check(hipEventCreate(&e0), "expand event");
+        hip_check(hipEventCreate(&e1), "expand event");
+        hip_check(hipEventRecord(e0, stream_), "expand event");
+    }
+    const ExpandBkArgs ba{seed, p.n * p.kpl(), p.k, p.N, dbk, raw};
+    const ExpandKskArgs ka{seed, (uint64_t)(p.bk_mask_words() / 8), (int64_t)rows, p.n, stride, dksk, img->ksk};
+    if (!launch_expand_bk(stream_, ba) || !launch_expand_ksk(stream_, ka)) fatal("expand: arguments outside what the kernels were built for");
+    hip_check(hipGetLastError(), "expand launch");
+    if (kernel_timing) hip_check(hipEventRecord(e1, stream_), "expand event");
+    // the all-zero digit-0 row
+    hip_check(hipMemsetAsync(img->ksk + rows * stride, 0, (size_t)stride * 4, stream_), "clear the zero row");
+    launch_bk_transform(stream_, img->dp, raw, img->bk_img, img->tw, p.n * p.kpl(), p.k + 1, scale);
+    hip_check(hipGetLastError(), "bk_transform launch");
+    sync_stream("key expansion");
+    if (kernel_timing) {
+        float ms = 0.f;
+        hip_check(hipEventElapsedTime(&ms, e0, e1), "expand event");
+        last_expand_ms = ms;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    recoverable_free(raw, bk_words * 4);
+    recoverable_free(dbk, bk_body);
+    recoverable_free(dksk, ksk_body);
+    ++expand_stats.expanded_keys;
+    expand_stats.expand_launches += 2;
+
+    img->key.bk_img = img->bk_img;
+    img->key.ksk = img->ksk;
+    img->key.ksk_zero = img->ksk + rows * stride;
+    img->key.tw = img->tw;
+    return img;
+}
+
+void Engine::run_expand_masks(const uint32_t seed10[10], int64_t first_word, int count, uint32_t *out) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    wait_flight();
+    ExpandSeed seed;
+    std::memcpy(seed.key, seed10, sizeof seed.key);
+    seed.nonce[0] = seed10[8]; seed.nonce[1] = seed10[9];
+    uint32_t *d = scratch_as<uint32_t>(S_EXPAND_WORDS, (size_t)count);
+    if (!launch_expand_masks(stream_, seed, first_word, count, d)) api_fail("expand_masks: arguments outside what the kernel was built for");
+    hip_check(hipGetLastError(), "expand_masks launch");
+    ++expand_stats.expand_launches;
+    d2h(out, d, (size_t)count, "download stream words");
+    sync_stream("expand_masks");
+}
+
+size_t Engine::read_key_image(const DeviceKeyImage *img, int which, Torus32 *out, size_t capacity) {
+    ENGINE_DEVICE_SCOPE();
+    const size_t words = (which == 0 ? img->bk_img_bytes : img->ksk_bytes) / 4;
+    if (!out || capacity < words) return words;
+    wait_flight();
+    const void *src = which == 0 ? static_cast<const void *>(img->bk_img) : static_cast<const void *>(img->ksk);
+    hip_check(hipMemcpyAsync(out, src, words * 4, hipMemcpyDeviceToHost, stream_), "download key image");
+    sync_stream("key image");
+    return words;
+}
+
 void Engine::free_key(DeviceKeyImage *img) {
     ENGINE_DEVICE_SCOPE();
     if (!img) return;

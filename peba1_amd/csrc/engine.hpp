@@ -16,6 +16,7 @@
 #include "kernels.hpp"
 #include "pack.hpp"
 #include "unpack.hpp"
+#include "expand.hpp"
 #include "../../include/tfhe_hip.h"
 
 // Device image of one cloud key: NTT image of BK, compact KSK, twiddles.
@@ -118,7 +119,16 @@ public:
     hipStream_t stream() const { return stream_; }
 
     DeviceKeyImage *upload_key(const TfheHipCloudKey &ck);
+    // The image of a device-expanded keyset (ck.mask_seed set; expand.hpp): the bodies are uploaded, the two expand kernels
+    // write the raw BK staging buffer and the compact KSK from the seed, launch_bk_transform follows.  Every buffer is
+    // allocated before anything is enqueued: device memory exhausted = ApiError with nothing held, as upload_key.
+    DeviceKeyImage *upload_compressed_key(const TfheHipCloudKey &ck);
+    double last_expand_ms = -1.0;       // the two expand kernels of the last such upload between stream events (kernel timing on)
     void free_key(DeviceKeyImage *img);
+    // test paths: stream words through the kernels' block function; an uploaded key's BK image (which = 0) or compact KSK,
+    // padding and zero row included (which = 1), copied back -- returns the word count, copies only if it fits `capacity`
+    void run_expand_masks(const uint32_t seed10[10], int64_t first_word, int count, uint32_t *out);
+    size_t read_key_image(const DeviceKeyImage *img, int which, Torus32 *out, size_t capacity);
     SlotPool *pool_for(const Params &p);
     SlotPool *find_pool(const Params &p) const;   // the pool of this ciphertext shape if one exists; never initialises the device
 
@@ -191,6 +201,7 @@ public:
                     int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait);
 
     TfheHipStats stats{};
+    TfheHipExpandStats expand_stats{};  // the device expansions of seed-compressed cloud keys (tfhe_hip_get_expand_stats)
     bool kernel_timing = false;
     // the launch rules' tunings (launch_plan.hpp; written by ensure_init()'s environment reads and tfhe_hip_set_tuning)
     LaunchTunings tunings;
@@ -256,6 +267,7 @@ private:
         S_UNPACK_INDEX,   // run_unpack: the index list
         S_UNPACK_KS,      // run_unpack: the key-switch descriptors (row j -> slot j)
         S_UNPACK_EXTRACT, // run_unpack: the extracted samples of one chunk
+        S_EXPAND_WORDS,   // raw, run_expand_masks: the stream words
     };
     void *scratch(Scratch idx, size_t bytes);
     // the same by element count (and `margin` bytes), and `count` elements between host and device on the engine's stream

@@ -1,0 +1,137 @@
+// expand.hip -- the public masks of a seed-compressed cloud key, regenerated on gfx950 (expand.hpp has the definition).
+//
+//   chacha_mask_words   one lane computes one ChaCha20 block in registers: 16 words of state, 20 rounds of add / xor /
+//                       rotate, the feed-forward; the eight odd words are the block's mask words (Rng::torus() takes the
+//                       high half of each 64-bit draw).
+//   expand_bk_kernel    a lane per group of eight consecutive words of the raw [rows][k+1][N] staging buffer: a mask
+//                       group is one block, a body group eight uploaded words; either leaves as two 16-byte stores.  A
+//                       polynomial is N/8 >= 128 groups, so a wave never holds both kinds.
+//   expand_ksk_kernel   a lane per block of the KSK's part of the stream; its eight words go to (row, q) = (m / n, m % n)
+//                       of the compact layout -- n is generally no multiple of 8 (630), so a block falls into two rows, or
+//                       nine when n = 1.  Behind the blocks, a lane per row writes the body at word n and the padding.
+//
+// Compute-bound on integer VALU (about 350 add / xor / rotate triples a block) with 32 bytes out per lane.  Every word of both
+// images is written here exactly once, with plain vector stores; the KSK's zero row is cleared by the caller.
+//
+// kernels.hip is not touched by this file.
+#include "expand.hpp"
+
+namespace tfhe_hip {
+
+namespace {
+
+#define EXPAND_QR(a, b, c, d)                                   \
+    a += b; d = __builtin_rotateleft32(d ^ a, 16);              \
+    c += d; b = __builtin_rotateleft32(b ^ c, 12);              \
+    a += b; d = __builtin_rotateleft32(d ^ a, 8);               \
+    c += d; b = __builtin_rotateleft32(b ^ c, 7)
+
+// the eight mask words of block `counter`: words 1, 3, ..., 15 of the ChaCha20 block (RFC 8439 2.3 with the original
+// 64-bit counter / 64-bit nonce split: the counter's high half is word 13)
+__device__ __forceinline__ void chacha_mask_words(const ExpandSeed &s, uint64_t counter, uint32_t w[8]) {
+    const uint32_t c0 = (uint32_t)counter, c1 = (uint32_t)(counter >> 32);
+    uint32_t x0 = 0x61707865u, x1 = 0x3320646eu, x2 = 0x79622d32u, x3 = 0x6b206574u;
+    uint32_t x4 = s.key[0], x5 = s.key[1], x6 = s.key[2], x7 = s.key[3];
+    uint32_t x8 = s.key[4], x9 = s.key[5], x10 = s.key[6], x11 = s.key[7];
+    uint32_t x12 = c0, x13 = c1, x14 = s.nonce[0], x15 = s.nonce[1];
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        EXPAND_QR(x0, x4, x8, x12); EXPAND_QR(x1, x5, x9, x13); EXPAND_QR(x2, x6, x10, x14); EXPAND_QR(x3, x7, x11, x15);
+        EXPAND_QR(x0, x5, x10, x15); EXPAND_QR(x1, x6, x11, x12); EXPAND_QR(x2, x7, x8, x13); EXPAND_QR(x3, x4, x9, x14);
+    }
+    w[0] = x1 + 0x3320646eu; w[1] = x3 + 0x6b206574u;
+    w[2] = x5 + s.key[1];    w[3] = x7 + s.key[3];
+    w[4] = x9 + s.key[5];    w[5] = x11 + s.key[7];
+    w[6] = x13 + c1;         w[7] = x15 + s.nonce[1];
+}
+#undef EXPAND_QR
+
+__global__ __launch_bounds__(256) void expand_bk_kernel(ExpandBkArgs a) {
+    const uint32_t gpp = (uint32_t)a.N / 8;                   // groups per polynomial
+    const uint64_t groups = (uint64_t)a.rows * (uint32_t)(a.k + 1) * gpp;
+    const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= groups) return;
+    const uint64_t poly = g / gpp;
+    const uint32_t jg = (uint32_t)(g % gpp);
+    const uint64_t row = poly / (uint32_t)(a.k + 1);
+    const uint32_t u = (uint32_t)(poly % (uint32_t)(a.k + 1));
+    uint4 lo, hi;
+    if (u < (uint32_t)a.k) {
+        uint32_t w[8];
+        chacha_mask_words(a.seed, (row * (uint32_t)a.k + u) * gpp + jg, w);
+        lo = make_uint4(w[0], w[1], w[2], w[3]);
+        hi = make_uint4(w[4], w[5], w[6], w[7]);
+    } else {
+        const uint4 *src = reinterpret_cast<const uint4 *>(a.body + row * (uint32_t)a.N + (size_t)jg * 8);
+        lo = src[0];
+        hi = src[1];
+    }
+    uint4 *dst = reinterpret_cast<uint4 *>(a.raw + g * 8);
+    dst[0] = lo;
+    dst[1] = hi;
+}
+
+__global__ __launch_bounds__(256) void expand_ksk_kernel(ExpandKskArgs a) {
+    const uint64_t words = (uint64_t)a.rows * (uint32_t)a.n;          // mask words of the KSK
+    const uint64_t blocks = (words + 7) / 8;
+    const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t *ksk = reinterpret_cast<uint32_t *>(a.ksk);
+    if (idx < blocks) {
+        uint32_t w[8];
+        chacha_mask_words(a.seed, a.first_block + idx, w);
+        uint64_t m = idx * 8, row = m / (uint32_t)a.n;
+        uint32_t q = (uint32_t)(m % (uint32_t)a.n);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            if (m + c < words) ksk[row * (uint32_t)a.stride + q] = w[c];
+            if (++q == (uint32_t)a.n) { q = 0; ++row; }
+        }
+    } else if (idx - blocks < (uint64_t)a.rows) {
+        const uint64_t row = idx - blocks;
+        uint32_t *tail = ksk + row * (uint32_t)a.stride;
+        tail[a.n] = (uint32_t)a.body[row];
+        for (int q = a.n + 1; q < a.stride; ++q) tail[q] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(256) void expand_masks_kernel(ExpandSeed seed, uint64_t first_word, uint32_t count, uint32_t *out) {
+    const uint64_t counter = first_word / 8 + ((uint64_t)blockIdx.x * 256 + threadIdx.x);     // base + block index, 64-bit
+    if (counter > (first_word + count - 1) / 8) return;
+    uint32_t w[8];
+    chacha_mask_words(seed, counter, w);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const uint64_t m = counter * 8 + c;
+        if (m >= first_word && m - first_word < count) out[m - first_word] = w[c];
+    }
+}
+
+bool aligned16(const void *p) { return p && !(reinterpret_cast<uintptr_t>(p) & 15u); }
+
+}  // namespace
+
+bool launch_expand_bk(hipStream_t s, const ExpandBkArgs &a) {
+    if (a.rows < 1 || a.k < 1 || a.N < 8 || (a.N & 7) || !aligned16(a.body) || !aligned16(a.raw)) return false;
+    const uint64_t groups = (uint64_t)a.rows * (uint32_t)(a.k + 1) * ((uint32_t)a.N / 8);
+    if ((groups + 255) / 256 > 0x7fffffffull) return false;
+    hipLaunchKernelGGL(expand_bk_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, a);
+    return true;
+}
+
+bool launch_expand_ksk(hipStream_t s, const ExpandKskArgs &a) {
+    if (a.rows < 1 || a.n < 1 || a.stride < a.n + 1 || (a.first_block >> 60) || !a.body || !a.ksk) return false;
+    const uint64_t lanes = ((uint64_t)a.rows * (uint32_t)a.n + 7) / 8 + (uint64_t)a.rows;
+    if ((lanes + 255) / 256 > 0x7fffffffull) return false;
+    hipLaunchKernelGGL(expand_ksk_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a);
+    return true;
+}
+
+bool launch_expand_masks(hipStream_t s, const ExpandSeed &seed, int64_t first_word, int32_t count, uint32_t *out) {
+    if (first_word < 0 || (first_word >> 60) || count < 1 || count > EXPAND_MASKS_MAX || !out) return false;
+    const uint64_t blocks = ((uint64_t)first_word + (uint32_t)count - 1) / 8 - (uint64_t)first_word / 8 + 1;
+    hipLaunchKernelGGL(expand_masks_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, s, seed, (uint64_t)first_word,
+                       (uint32_t)count, out);
+    return true;
+}
+
+}  // namespace tfhe_hip

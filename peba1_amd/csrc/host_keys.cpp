@@ -137,6 +137,18 @@ Rng Rng::secure() {
     return r;
 }
 
+Rng Rng::keyed(const uint32_t seed10[10]) {
+    register_fork_handler();
+    Rng r(0);
+    std::memcpy(r.key_, seed10, sizeof r.key_);
+    r.nonce_[0] = seed10[8]; r.nonce_[1] = seed10[9];
+    r.counter_ = 0;
+    r.pos_ = 16;
+    r.chacha_ = true;
+    r.fork_gen_ = g_fork_generation.load(std::memory_order_relaxed);
+    return r;
+}
+
 static inline uint32_t rotl32(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
 
 // one ChaCha20 block (RFC 8439 section 2.3, with the original 64-bit counter / 64-bit nonce split)
@@ -241,6 +253,63 @@ void generate_keys(const Params &p, Rng &secret, Rng &mask, TfheHipSecretKey &sk
                 b += (uint32_t)dtot32(secret.gauss(p.ks_stdev));
                 row[n] = b;
             }
+}
+
+// The masks are the stream words verbatim, so the gadget term mu = s_i 2^(32 - (jj+1) Bgbit) of a TGSW row cannot sit on
+// a mask polynomial as in generate_keys: it goes on body coefficient 0 for bloc = k and as -mu S_bloc(X) on the body
+// otherwise -- the same phase, e - mu S_bloc(X) resp. e + mu (DESIGN.md section 2 "Key material").
+void generate_compressed_key(const TfheHipSecretKey &sk, Rng &noise, TfheHipCompressedCloudKey &out) {
+    const Params &p = sk.p;
+    const int n = p.n, N = p.N, k = p.k, l = p.l, kpl = p.kpl(), t = p.ks_t, base = 1 << p.ks_basebit;
+    out.p = p;
+    Rng mask = Rng::keyed(out.seed);
+    out.bk_body.assign(p.bk_body_words(), 0);
+    std::vector<uint32_t> m((size_t)k * N);
+    for (int i = 0; i < n; ++i)
+        for (int row = 0; row < kpl; ++row) {
+            uint32_t *body = reinterpret_cast<uint32_t *>(out.bk_body.data()) + ((size_t)i * kpl + row) * N;
+            for (auto &w : m) w = (uint32_t)mask.torus();
+            for (int j = 0; j < N; ++j) body[j] = (uint32_t)dtot32(noise.gauss(p.bk_stdev));
+            for (int u = 0; u < k; ++u) add_mul_by_bits(body, m.data() + (size_t)u * N, sk.tlwe_key.data() + (size_t)u * N, N);
+            const int bloc = row / l, jj = row % l;
+            const uint32_t mu = (uint32_t)sk.lwe_key[i] << (32 - (jj + 1) * p.Bgbit);
+            if (bloc == k) body[0] += mu;
+            else for (int j = 0; j < N; ++j) body[j] -= mu * (uint32_t)sk.tlwe_key[(size_t)bloc * N + j];
+        }
+    out.ksk_body.assign(p.ksk_body_words(), 0);
+    for (int i = 0; i < k * N; ++i)
+        for (int j = 0; j < t; ++j)
+            for (int v = 1; v < base; ++v) {
+                uint32_t b = 0;
+                for (int q = 0; q < n; ++q) b += (uint32_t)mask.torus() * (uint32_t)sk.lwe_key[q];
+                b += (uint32_t)(sk.tlwe_key[i] * v) << (32 - (j + 1) * p.ks_basebit);
+                b += (uint32_t)dtot32(noise.gauss(p.ks_stdev));
+                out.ksk_body[((size_t)i * t + j) * (base - 1) + (v - 1)] = (Torus32)b;
+            }
+}
+
+void expand_masks_host(const Params &p, const uint32_t seed10[10], const Torus32 *bk_body, const Torus32 *ksk_body,
+                       std::vector<Torus32> &bk, std::vector<Torus32> &ksk) {
+    const int n = p.n, N = p.N, k = p.k, kpl = p.kpl(), t = p.ks_t, base = 1 << p.ks_basebit;
+    Rng mask = Rng::keyed(seed10);
+    bk.assign(p.bk_words(), 0);
+    for (size_t r = 0; r < (size_t)n * kpl; ++r) {
+        Torus32 *smp = bk.data() + r * (size_t)(k + 1) * N;
+        for (size_t j = 0; j < (size_t)k * N; ++j) smp[j] = mask.torus();
+        std::memcpy(smp + (size_t)k * N, bk_body + r * N, (size_t)N * sizeof(Torus32));
+    }
+    ksk.assign(p.ksk_words(), 0);          // (the digit-0 rows stay zero and are never drawn)
+    for (size_t r = 0; r < (size_t)k * N * t; ++r)
+        for (int v = 1; v < base; ++v) {
+            Torus32 *row = ksk.data() + (r * base + v) * (size_t)(n + 1);
+            for (int q = 0; q < n; ++q) row[q] = mask.torus();
+            row[n] = ksk_body[r * (base - 1) + (v - 1)];
+        }
+}
+
+void materialise_host_words(TfheHipCloudKey &ck) {
+    if (ck.mask_seed.empty() || !ck.bk.empty()) return;
+    expand_masks_host(ck.p, ck.mask_seed.data(), ck.bk_body.data(), ck.ksk_body.data(), ck.bk, ck.ksk);
 }
 
 void encrypt_bit(const TfheHipSecretKey &sk, Rng &secret, Rng &mask, int32_t message, Torus32 *a, Torus32 *b) {

@@ -22,6 +22,12 @@ struct Params {
     uint32_t ks_prec_offset() const { return 1u << (32 - (1 + ks_basebit * ks_t)); }
     size_t bk_words() const { return (size_t)n * kpl() * (k + 1) * N; }
     size_t ksk_words() const { return (size_t)k * N * ks_t * (size_t)(1 << ks_basebit) * (n + 1); }
+    // what a seed-compressed cloud key transmits: one body polynomial per BK row, one body word per non-zero KSK row
+    size_t bk_body_words() const { return (size_t)n * kpl() * N; }
+    size_t ksk_body_words() const { return (size_t)k * N * ks_t * (size_t)((1 << ks_basebit) - 1); }
+    // the public mask words the seed stands for: the BK's first, then the KSK's
+    size_t bk_mask_words() const { return (size_t)n * kpl() * k * N; }
+    size_t ksk_mask_words() const { return ksk_body_words() * (size_t)n; }
 };
 
 // The C structs behind a TFheGateBootstrappingParameterSet allocated by this library.
@@ -49,6 +55,8 @@ class Rng {
 public:
     explicit Rng(uint64_t seed = 0) { reseed(seed); }
     static Rng secure();             // aborts with a message if the OS offers no entropy
+    // the ChaCha20 stream of a given (key[8], nonce[2]) from counter 0: the public mask stream of a seed-compressed cloud key
+    static Rng keyed(const uint32_t seed10[10]);
     void reseed(uint64_t seed);      // (re)start the seeded generator
     uint64_t next();
     Torus32 torus() { return (Torus32)(uint32_t)(next() >> 32); }
@@ -87,6 +95,21 @@ struct TfheHipCloudKey {
     std::vector<Torus32> bk;         // [n][(k+1)l][k+1][N]
     std::vector<Torus32> ksk;        // [kN][t][base][n+1]
     DeviceKeyImage *dev = nullptr;   // null for host-only keysets
+    // a device-expanded keyset (tfhe_hip_expand_cloud_key) holds the mask seed and the bodies alone: bk / ksk stay empty
+    // until tfhe_hip_key_bk / _ksk or the cloud-key file export asks for the words (materialise_host_words)
+    std::vector<uint32_t> mask_seed; // [10] or empty (a plain keyset)
+    std::vector<Torus32> bk_body;    // [n][(k+1)l][N]
+    std::vector<Torus32> ksk_body;   // [kN][t][base-1]
+};
+// A cloud key as it travels (include/tfhe_hip.h "seed-compressed cloud keys"): the masks are the words of the ChaCha20
+// stream of `seed`, only the bodies are held.
+constexpr uint32_t COMPRESSED_KEY_MAGIC = 0x43434B59u;
+struct TfheHipCompressedCloudKey {
+    uint32_t magic;
+    tfhe_hip::Params p;
+    uint32_t seed[10];               // ChaCha20 key[8], nonce[2]
+    std::vector<Torus32> bk_body;    // [n][(k+1)l][N]
+    std::vector<Torus32> ksk_body;   // [kN][t][base-1]
 };
 
 namespace tfhe_hip {
@@ -97,4 +120,13 @@ void encrypt_bit(const TfheHipSecretKey &sk, Rng &secret, Rng &mask, int32_t mes
 // the same with any message mu in place of +-1/8: the noise draw first, then the n mask words
 void encrypt_torus(const TfheHipSecretKey &sk, Rng &secret, Rng &mask, Torus32 mu, Torus32 *a, Torus32 *b);
 Torus32 phase_of(const TfheHipSecretKey &sk, const Torus32 *a, Torus32 b);
+// Seed-compressed cloud keys.  generate_compressed_key: the bodies of a fresh cloud key for `sk` whose masks are the stream
+// of out.seed (set by the caller) and nothing else -- the gadget term of every BK row is on the body; `noise` yields N
+// gaussians per BK row, then one per KSK row.  expand_masks_host: today's bk / ksk layouts from seed and bodies, the
+// masks drawn from a sequential Rng::keyed.  materialise_host_words: the same into the keyset itself, if it is a
+// device-expanded one whose words nobody has asked for yet.
+void generate_compressed_key(const TfheHipSecretKey &sk, Rng &noise, TfheHipCompressedCloudKey &out);
+void expand_masks_host(const Params &p, const uint32_t seed10[10], const Torus32 *bk_body, const Torus32 *ksk_body,
+                       std::vector<Torus32> &bk, std::vector<Torus32> &ksk);
+void materialise_host_words(TfheHipCloudKey &ck);
 }  // namespace tfhe_hip

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "recorder.hpp"
 #include "../../include/tfhe/tfhe.h"
 #include "../../include/tfhe/tfhe_io.h"
 
@@ -18,7 +19,7 @@ using namespace tfhe_hip;
 
 namespace {
 
-enum : uint32_t { KIND_PARAMS = 1, KIND_CLOUD = 2, KIND_SECRET = 3, KIND_SAMPLE = 4 };
+enum : uint32_t { KIND_PARAMS = 1, KIND_CLOUD = 2, KIND_SECRET = 3, KIND_SAMPLE = 4, KIND_COMPRESSED_CLOUD = 5 };
 constexpr uint32_t VERSION = 1;
 
 struct Header { char magic[4]; uint32_t version, kind, reserved; uint64_t bytes; };
@@ -96,9 +97,25 @@ TfheHipCloudKey *get_cloud_payload(FILE *F, uint64_t declared, bool with_secret_
     return ck.release();
 }
 
+// a seed-compressed cloud key: parameter record, the ten seed words, both body arrays
+uint64_t compressed_bytes(const Params &p) {
+    return sizeof(ParamsRecord) + 10 * sizeof(uint32_t) + (p.bk_body_words() + p.ksk_body_words()) * sizeof(Torus32);
+}
+
 }  // namespace
 
 namespace tfhe_hip {
+// a cloud keyset of its own around `ck` (the loader's, and those expanded from a compressed key): it owns a parameter
+// bundle and is released by delete_gate_bootstrapping_cloud_keyset
+TFheGateBootstrappingCloudKeySet *io_adopt_cloud(TfheHipCloudKey *ck) {
+    auto *ks = new TFheGateBootstrappingCloudKeySet();
+    ks->params = &make_param_bundle(ck->p)->set;
+    ks->bk = ck;
+    ks->bkFFT = ck;
+    std::lock_guard<std::mutex> g(g_mtx);
+    g_owned_cloud.insert(ks);
+    return ks;
+}
 // called by the delete_* functions of shim.cpp: true if the keyset came from a loader
 bool io_forget_owned_cloud(const void *ks) { std::lock_guard<std::mutex> g(g_mtx); return g_owned_cloud.erase(ks) != 0; }
 bool io_forget_owned_secret(const void *ks) { std::lock_guard<std::mutex> g(g_mtx); return g_owned_secret.erase(ks) != 0; }
@@ -133,21 +150,45 @@ TFheGateBootstrappingParameterSet *new_tfheGateBootstrappingParameterSet_fromFil
 
 void export_tfheGateBootstrappingCloudKeySet_toFile(FILE *F, const TFheGateBootstrappingCloudKeySet *keyset) {
     io_guard([&] {
+        {   // a device-expanded keyset holds no mask words until somebody asks for them
+            auto g = recorder_lock();
+            materialise_host_words(*const_cast<TfheHipCloudKey *>(keyset->bk));
+        }
         put_header(F, KIND_CLOUD, cloud_bytes(keyset->bk->p));
         put_cloud_payload(F, *keyset->bk);
         return Done{};
     });
 }
+
+void tfhe_hip_export_compressed_cloud_key_toFile(FILE *F, const TfheHipCompressedCloudKey *key) {
+    io_guard([&] {
+        if (!F || !key || key->magic != COMPRESSED_KEY_MAGIC) api_fail("tfhe_io: null or deleted compressed cloud key");
+        put_header(F, KIND_COMPRESSED_CLOUD, compressed_bytes(key->p));
+        put_params(F, key->p);
+        put(F, key->seed, sizeof key->seed);
+        put_vec(F, key->bk_body);
+        put_vec(F, key->ksk_body);
+        return Done{};
+    });
+}
+TfheHipCompressedCloudKey *tfhe_hip_new_compressed_cloud_key_fromFile(FILE *F) {
+    return io_guard([&]() -> TfheHipCompressedCloudKey * {
+        if (!F) api_fail("tfhe_io: null file");
+        const uint64_t declared = get_header(F, KIND_COMPRESSED_CLOUD);
+        std::unique_ptr<TfheHipCompressedCloudKey> key(new TfheHipCompressedCloudKey());
+        key->p = get_params(F);
+        // the sizes the file's own parameter record implies must agree with the header before anything is allocated
+        if (declared != compressed_bytes(key->p)) api_fail("tfhe_io: payload size does not match the file's parameter record (corrupt file)");
+        get(F, key->seed, sizeof key->seed);
+        get_vec(F, key->bk_body, key->p.bk_body_words());
+        get_vec(F, key->ksk_body, key->p.ksk_body_words());
+        key->magic = COMPRESSED_KEY_MAGIC;
+        return key.release();
+    });
+}
 static TFheGateBootstrappingCloudKeySet *load_cloud(FILE *F) {
     const uint64_t declared = get_header(F, KIND_CLOUD);
-    TfheHipCloudKey *ck = get_cloud_payload(F, declared, false);
-    auto *ks = new TFheGateBootstrappingCloudKeySet();
-    ks->params = &make_param_bundle(ck->p)->set;
-    ks->bk = ck;
-    ks->bkFFT = ck;
-    std::lock_guard<std::mutex> g(g_mtx);
-    g_owned_cloud.insert(ks);
-    return ks;
+    return io_adopt_cloud(get_cloud_payload(F, declared, false));
 }
 TFheGateBootstrappingCloudKeySet *new_tfheGateBootstrappingCloudKeySet_fromFile(FILE *F) {
     return io_guard([&] { return load_cloud(F); });

@@ -171,7 +171,9 @@ SlotPool *pool_of_key(const TFheGateBootstrappingCloudKeySet *bk) {
     if (!bk || !bk->bk) api_fail("null cloud key");
     // keysets made host-only or loaded from a file get their device image at first use
     // (aborts with a clear message when there is no GPU: gates are never evaluated on the CPU)
-    if (!bk->bk->dev) bk->bk->dev = Engine::get().upload_key(*bk->bk);
+    // (a device-expanded keyset holds seed and bodies only: its masks are made on the card)
+    if (!bk->bk->dev)
+        bk->bk->dev = bk->bk->mask_seed.empty() ? Engine::get().upload_key(*bk->bk) : Engine::get().upload_compressed_key(*bk->bk);
     return Engine::get().pool_for(bk->bk->p);
 }
 

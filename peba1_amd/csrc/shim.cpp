@@ -24,6 +24,7 @@ namespace tfhe_hip {
 const std::string &last_error_ref();
 bool io_forget_owned_cloud(const void *ks);     // io.cpp: keysets created by the file loaders
 bool io_forget_owned_secret(const void *ks);
+TFheGateBootstrappingCloudKeySet *io_adopt_cloud(TfheHipCloudKey *ck);   // io.cpp: a cloud keyset of its own around ck
 }
 
 namespace {
@@ -423,11 +424,14 @@ const int32_t *tfhe_hip_key_tlwe(const TFheGateBootstrappingSecretKeySet *key, i
     if (count) *count = (int64_t)key->lwe_key->tlwe_key.size();
     return key->lwe_key->tlwe_key.data();
 }
+// (a device-expanded keyset gets its host words here, under the library's lock, the first time they are asked for)
 const Torus32 *tfhe_hip_key_bk(const TFheGateBootstrappingCloudKeySet *cloud, int64_t *count) {
+    { auto g = recorder_lock(); materialise_host_words(*const_cast<TfheHipCloudKey *>(cloud->bk)); }
     if (count) *count = (int64_t)cloud->bk->bk.size();
     return cloud->bk->bk.data();
 }
 const Torus32 *tfhe_hip_key_ksk(const TFheGateBootstrappingCloudKeySet *cloud, int64_t *count) {
+    { auto g = recorder_lock(); materialise_host_words(*const_cast<TfheHipCloudKey *>(cloud->bk)); }
     if (count) *count = (int64_t)cloud->bk->ksk.size();
     return cloud->bk->ksk.data();
 }
@@ -1002,6 +1006,11 @@ void tfhe_hip_get_stats(TfheHipStats *out) {
 void tfhe_hip_reset_stats(void) {
     auto g = recorder_lock();
     Engine::get().stats = TfheHipStats{};
+    Engine::get().expand_stats = TfheHipExpandStats{};
+}
+void tfhe_hip_get_expand_stats(TfheHipExpandStats *out) {
+    auto g = recorder_lock();
+    if (out) *out = Engine::get().expand_stats;
 }
 void tfhe_hip_set_kernel_timing(int on) { Engine::get().kernel_timing = on != 0; }
 int tfhe_hip_last_flush_keys(void) {
@@ -1378,6 +1387,9 @@ int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const 
 #include "pack_host.cpp"
 // and that of the ring-encrypted inputs, behind it (it uses the negacyclic product defined there)
 #include "unpack_host.cpp"
+
+// and that of the seed-compressed cloud keys
+#include "compressed_host.cpp"
 
 // The recorder is compiled as part of this object.  build.sh is one of the files kernels_sha16 hashes (kernel_id.py): a new
 // host source named there would mark every committed counter summary stale although no kernel changed.

@@ -78,8 +78,15 @@ class StatsWhole(StatsAll):
     _fields_ = [("unpacked_samples", C.c_uint64), ("unpack_launches", C.c_uint64)]
 
 
+class ExpandStats(C.Structure):
+    """TfheHipExpandStats: the counters of the seed-compressed cloud keys, read through an entry of their own
+    (tfhe_hip_get_expand_stats) -- TfheHipStats, which callers allocate, keeps its size."""
+    _fields_ = [("expanded_keys", C.c_uint64), ("expand_launches", C.c_uint64)]
+
+
 STATS_FIELDS = [f for f, _ in Stats._fields_] + [f for f, _ in StatsAll._fields_]
 UNPACK_STATS_FIELDS = [f for f, _ in StatsWhole._fields_]
+EXPAND_STATS_FIELDS = [f for f, _ in ExpandStats._fields_]
 
 
 PS = C.POINTER(ParameterSet)
@@ -87,6 +94,7 @@ CK = C.POINTER(CloudKeySet)
 SK = C.POINTER(SecretKeySet)
 LS = C.POINTER(LweSample)
 I32P = C.POINTER(C.c_int32)
+U32P = C.POINTER(C.c_uint32)
 
 # every symbol include/tfhe/tfhe_gate_bootstrapping_functions.h and include/tfhe_hip.h declare
 _GATE2 = ["bootsAND", "bootsOR", "bootsXOR", "bootsXNOR", "bootsNAND", "bootsNOR", "bootsANDNY", "bootsANDYN",
@@ -222,6 +230,22 @@ SIGNATURES = {
     "tfhe_hip_unpack_samples_scattered": (C.c_int, [CK, I32P, C.c_int32, I32P, C.c_int32, C.POINTER(LS)]),
     "tfhe_hip_unpack_samples_device": (C.c_int, [CK, C.c_void_p, C.c_int32, I32P, C.c_int32, LS]),
     "tfhe_hip_kernel_ring_extract": (C.c_int, [CK, I32P, C.c_int32, I32P, C.c_int32, I32P]),
+    "tfhe_hip_new_compressed_cloud_key": (C.c_void_p, [SK]),
+    "tfhe_hip_new_compressed_cloud_key_seeded": (C.c_void_p, [SK, C.c_uint64, U32P]),
+    "tfhe_hip_new_compressed_cloud_key_from_words": (C.c_void_p, [PS, U32P, I32P, I32P]),
+    "tfhe_hip_delete_compressed_cloud_key": (None, [C.c_void_p]),
+    "tfhe_hip_compressed_key_seed": (U32P, [C.c_void_p]),
+    "tfhe_hip_compressed_key_bk_body": (I32P, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "tfhe_hip_compressed_key_ksk_body": (I32P, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "tfhe_hip_compressed_key_bytes": (C.c_int64, [C.c_void_p]),
+    "tfhe_hip_expand_cloud_key_host": (CK, [C.c_void_p]),
+    "tfhe_hip_expand_cloud_key": (CK, [C.c_void_p]),
+    "tfhe_hip_export_compressed_cloud_key_toFile": (None, [C.c_void_p, C.c_void_p]),
+    "tfhe_hip_new_compressed_cloud_key_fromFile": (C.c_void_p, [C.c_void_p]),
+    "tfhe_hip_kernel_expand_masks": (C.c_int, [U32P, C.c_int64, C.c_int32, U32P]),
+    "tfhe_hip_test_key_image": (C.c_int64, [CK, C.c_int, I32P, C.c_int64]),
+    "tfhe_hip_last_expand_ms": (C.c_double, []),
+    "tfhe_hip_get_expand_stats": (None, [C.POINTER(ExpandStats)]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])

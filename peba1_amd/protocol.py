@@ -15,6 +15,7 @@ that follows it.
 
     python -m peba1_amd.protocol --nslots 128            # genuine and impostor run, one GPU
     python -m peba1_amd.protocol --clients 4             # four clients, each with a key pair of its own, batched
+    python -m peba1_amd.protocol --compressed-keys       # the cloud key travels as a seed and the bodies (10x fewer bytes)
 
 With --clients K the server side runs as a multi-user server does: Function_f of all K clients in ONE flush and
 Function_g of all K in a second one (multi-key flushes, tuning "batch_keys"), one JSON line per client.
@@ -60,11 +61,13 @@ def run_p1(params, key, sample, template, bound_match, r0, r1, bitsize=8, cloud=
             "levels": {"function_f": levels_f, "function_g": levels_g}}
 
 
-def run_p1_clients(params, keys, samples, templates, bounds, r0s, r1s, bitsize=8, fast=False):
+def run_p1_clients(params, keys, samples, templates, bounds, r0s, r1s, bitsize=8, fast=False, clouds=None):
     """run_p1 for K clients at once, client c with its own secret keyset keys[c]: every client's Function_f in one flush,
-    every Function_g in a second.  Returns one dict per client, as run_p1's (the timings are the batch's)."""
+    every Function_g in a second.  clouds[c] (default: the cloud keyset embedded in keys[c]) is all the evaluating side
+    uses.  Returns one dict per client, as run_p1's (the timings are the batch's)."""
     from . import lib
     k = len(keys)
+    ev = keys if clouds is None else clouds
     t0 = time.perf_counter()
     enc_t = [circuits.EncryptedVector(params, templates[c], bitsize, keys[c]).to_device() for c in range(k)]
     enc_s = [circuits.EncryptedVector(params, samples[c], bitsize, keys[c]).to_device() for c in range(k)]
@@ -73,7 +76,7 @@ def run_p1_clients(params, keys, samples, templates, bounds, r0s, r1s, bitsize=8
     enc_r1 = [circuits.encrypt_number(params, r1s[c], bitsize, keys[c]) for c in range(k)]
     t_enc = time.perf_counter()
     enc_b = [api.CiphertextArray(params, MAX_BITSIZE) for _ in range(k)]
-    levels_f = circuits.function_f_batch(enc_b, enc_s, enc_t, enc_bound, bitsize, keys, fast=fast)
+    levels_f = circuits.function_f_batch(enc_b, enc_s, enc_t, enc_bound, bitsize, ev, fast=fast)
     t_f = time.perf_counter()
     enc_y = [api.CiphertextArray(params, bitsize + 1) for _ in range(k)]
     L = lib.load()
@@ -81,7 +84,7 @@ def run_p1_clients(params, keys, samples, templates, bounds, r0s, r1s, bitsize=8
     api.set_deferred(True)
     try:
         for c in range(k):
-            circuits.function_g(enc_y[c], enc_b[c], enc_r0[c], enc_r1[c], bitsize, keys[c])
+            circuits.function_g(enc_y[c], enc_b[c], enc_r0[c], enc_r1[c], bitsize, ev[c])
         levels_g = api.flush()
     finally:
         api.set_deferred(was_deferred)
@@ -113,24 +116,38 @@ def parse_args(argv=None):
     ap.add_argument("--fast", action="store_true", help="Function_f through the optimised DAG (circuits_fast.cpp)")
     ap.add_argument("--clients", type=int, default=0,
                     help="K > 0: K clients with key pairs of their own, Function_f and Function_g batched over them")
+    ap.add_argument("--compressed-keys", action="store_true",
+                    help="each client ships a seed-compressed cloud key; the server expands it on the device at first use")
     a = ap.parse_args(argv)
     if a.clients < 0:
         ap.error("--clients must be >= 0")
     return a
 
 
+def shipped_cloud(key):
+    """What --compressed-keys puts between client and server: the client makes a compressed cloud key for its secret
+    keyset (40 bytes of seed and the bodies), the server expands it -- the masks are written on the device at first use."""
+    ck = api.CompressedCloudKey.generate(key)
+    try:
+        return api.CompressedCloudKey.from_words(key.params, ck.seed(), ck.bk_body(), ck.ksk_body()).expand()
+    finally:
+        ck.close()
+
+
 def main_clients(a):
     params = api.ParameterSet(128)
     inputs = [client_inputs(c, a.nslots, a.seed) for c in range(a.clients)]
-    keys = [api.SecretKeySet(params, x["key_seed"]) for x in inputs]
+    keys = [api.SecretKeySet(params, x["key_seed"], device=not a.compressed_keys) for x in inputs]
+    clouds = [shipped_cloud(k) for k in keys] if a.compressed_keys else None
     try:
         outs = run_p1_clients(params, keys, [x["sample"] for x in inputs], [x["template"] for x in inputs],
-                              [a.bound] * a.clients, [x["r0"] for x in inputs], [x["r1"] for x in inputs], fast=a.fast)
+                              [a.bound] * a.clients, [x["r0"] for x in inputs], [x["r1"] for x in inputs], fast=a.fast,
+                              clouds=clouds)
         for x, out in zip(inputs, outs):
             out["distance"] = sum((s - t) ** 2 for s, t in zip(x["sample"], x["template"]))
             print(json.dumps(out))
     finally:
-        for k in keys:
+        for k in (clouds or []) + keys:
             k.close()
 
 
@@ -139,14 +156,17 @@ def main():
     if a.clients:
         return main_clients(a)
     params = api.ParameterSet(128)
-    key = api.SecretKeySet(params, a.seed + 1)
+    key = api.SecretKeySet(params, a.seed + 1, device=not a.compressed_keys)
+    cloud = shipped_cloud(key) if a.compressed_keys else None
     template = [(37 * i + 11) % 255 for i in range(a.nslots)]             # SURVEY 8c inputs
     runs = {"genuine": [t + 1 for t in template], "impostor": [(91 * i + 5) % 256 for i in range(a.nslots)]}
     for name, sample in runs.items():
-        out = run_p1(params, key, sample, template, a.bound, r0=17, r1=99,
+        out = run_p1(params, key, sample, template, a.bound, r0=17, r1=99, cloud=cloud,
                      function_f=circuits.function_f_fast if a.fast else None)
         out["distance"] = sum((x - y) ** 2 for x, y in zip(sample, template))
         print(json.dumps({"run": name, **out}))
+    if cloud is not None:
+        cloud.close()
     key.close()
 
 
