@@ -420,6 +420,18 @@ typedef struct TfheHipExpandStats {
     uint64_t expand_launches;
 } TfheHipExpandStats;
 void tfhe_hip_get_expand_stats(TfheHipExpandStats *out);
+/* seed-compressed packing keys and ring samples, a struct of their own for the same reason: the packing keys whose masks
+ * were made on the device (tfhe_hip_expand_packing_key, at the first pack) and the expand kernel launches that took, one per
+ * key -- a host-expanded or plain key counts nothing; the samples opened by the seeded unpack entries and their extract
+ * launches (tfhe_hip_kernel_ring_extract_seeded counts its launches too).  A seeded unpack also counts in unpacked_samples,
+ * unpack_launches and keyswitches of TfheHipStats, as a plain one does.  tfhe_hip_reset_stats() clears these too. */
+typedef struct TfheHipSeededStats {
+    uint64_t expanded_packing_keys;
+    uint64_t packing_expand_launches;
+    uint64_t seeded_unpacked_samples;
+    uint64_t seeded_unpack_launches;
+} TfheHipSeededStats;
+void tfhe_hip_get_seeded_stats(TfheHipSeededStats *out);
 /* when on, every kernel launch is bracketed by HIP events, read back after the flush */
 void tfhe_hip_set_kernel_timing(int on);
 /* distinct cloud keys the last executed flush ran under (1 unless "batch_keys" is on; 0 before the first flush) */
@@ -567,7 +579,8 @@ int tfhe_hip_test_wg_times(const TFheGateBootstrappingCloudKeySet *bk, int32_t w
  * peba1_amd/csrc/pack.hpp derives that bound and the CRT bound beside it).  Host only: no GPU is needed to make a
  * key, read its words or decrypt a packed sample.
  * tfhe_hip_new_packing_key_from_words: the cloud side -- a server that received the raw rows builds its key from them
- * (the words are copied).  tfhe_hip_packing_key_words: a read-only view of the raw rows, *count = n t (k+1) N. */
+ * (the words are copied).  tfhe_hip_packing_key_words: a read-only view of the raw rows, *count = n t (k+1) N.
+ * "Seed-compressed packing keys and ring samples" below: the same key travelling as a mask seed and its bodies. */
 typedef struct TfheHipPackingKey TfheHipPackingKey;
 TfheHipPackingKey *tfhe_hip_new_packing_key(const TFheGateBootstrappingSecretKeySet *secret, int32_t pk_t, int32_t pk_basebit);
 TfheHipPackingKey *tfhe_hip_new_packing_key_seeded(const TFheGateBootstrappingSecretKeySet *secret, int32_t pk_t,
@@ -719,6 +732,94 @@ int tfhe_hip_kernel_expand_masks(const uint32_t *mask_seed10, int64_t first_word
 int64_t tfhe_hip_test_key_image(const TFheGateBootstrappingCloudKeySet *cloud, int which, Torus32 *out, int64_t capacity);
 double tfhe_hip_last_expand_ms(void);
 
+/* ---- seed-compressed packing keys and ring samples: everything a client sends is bodies plus seeds ----
+ * Half the words of a packing key and of a ring sample are uniform public masks.  Both travel with a mask seed of ten words
+ * (ChaCha20 key[8], nonce[2]) in their place; the stream is the compressed cloud key's: mask word m is word 2 (m mod 8) + 1
+ * of ChaCha20 block floor(m / 8) under (key, nonce), 64-bit block counter from 0 (tfhe_hip_test_chacha20_block).  k = 1.
+ *
+ * Compressed packing key.  It holds the parameter set, (pk_t, pk_basebit), the seed and the bodies body[n][t][N]:
+ * P128, t = 8: 40 + 20,643,840 bytes against the 41,287,680 of the raw rows.  Masks are numbered in [i][p][j] order: the mask
+ * polynomial of row (i, p) is stream words (i t + p) N .. + N - 1, blocks (i t + p) N/8 .. + N/8 - 1.  A row is the plain
+ * key's row: body = mask * S + e + mu with mu = lwe_key[i] << (32 - (p+1) pk_basebit) on coefficient 0 and noise e of the
+ * set's bk_stdev, in Z[X]/(X^N + 1) wrapping mod 2^32 -- the message sits on the body already, so unlike the cloud key's
+ * TGSW rows no new row form is needed.  The expanded key IS a plain packing key: it equals
+ * tfhe_hip_new_packing_key_from_words applied to the expanded rows [n][t][k+1][N] (mask = the stream words verbatim, body =
+ * the transmitted one), word for word, and the packing definition above applies to it unchanged.
+ * tfhe_hip_new_compressed_packing_key: noise from a fresh ChaCha20 stream keyed by the OS, the mask seed ten fresh words of
+ * OS entropy.  _seeded (fixtures; NOT for keys that protect data): noise from the seeded generator (xoshiro256** through
+ * splitmix64) started from noise_seed, N gaussians per row, rows in [i][p] order; the mask seed as given.  _from_words: the
+ * cloud side (everything is copied; body holds n t N words).  pk_t = pk_basebit = 0: the set's own (ks_t, ks_basebit).
+ * NULL and the error set, nothing made: a null argument, or a decomposition tfhe_hip_new_packing_key refuses.  None of this
+ * touches the streams a keyset, a plain packing key or a compressed cloud key is drawn from.  Host only.
+ * Accessors: the seed (10 words), the bodies (*count = n t N), the decomposition, the bytes that travel (40 + 4 * count).
+ * tfhe_hip_expand_packing_key_host: a plain packing key with all rows filled on the host from a sequential stream -- the
+ * reference, and the way for a caller without a GPU.
+ * tfhe_hip_expand_packing_key: a packing key that holds only seed and bodies.  At its first pack the bodies are uploaded
+ * (20.6 MB at P128 instead of 41.3 MB) and the masks are written on the card into the staging buffer the NTT transform
+ * reads; device memory exhausted there is recoverable as for a plain key (the pack has no effect, nothing is held, a later
+ * pack tries again).  tfhe_hip_packing_key_words materialises the host rows on demand; everything else that takes a
+ * packing key works on it unchanged.  Both are deleted with tfhe_hip_delete_packing_key; the compressed key may be deleted
+ * as soon as the call returns.
+ * Files: one more kind of the container of tfhe_io.h (parameter record, decomposition, seed, bodies), refused like the other
+ * kinds on a wrong magic / version / kind, a declared size that does not match, a refused decomposition, or truncation. */
+typedef struct TfheHipCompressedPackingKey TfheHipCompressedPackingKey;
+TfheHipCompressedPackingKey *tfhe_hip_new_compressed_packing_key(const TFheGateBootstrappingSecretKeySet *secret, int32_t pk_t,
+                                                                 int32_t pk_basebit);
+TfheHipCompressedPackingKey *tfhe_hip_new_compressed_packing_key_seeded(const TFheGateBootstrappingSecretKeySet *secret,
+                                                                        int32_t pk_t, int32_t pk_basebit, uint64_t noise_seed,
+                                                                        const uint32_t *mask_seed10);
+TfheHipCompressedPackingKey *tfhe_hip_new_compressed_packing_key_from_words(const TFheGateBootstrappingParameterSet *params,
+                                                                            int32_t pk_t, int32_t pk_basebit,
+                                                                            const uint32_t *mask_seed10, const Torus32 *body);
+void tfhe_hip_delete_compressed_packing_key(TfheHipCompressedPackingKey *key);
+const uint32_t *tfhe_hip_compressed_packing_key_seed(const TfheHipCompressedPackingKey *key);
+const Torus32 *tfhe_hip_compressed_packing_key_body(const TfheHipCompressedPackingKey *key, int64_t *count);
+int tfhe_hip_compressed_packing_key_decomposition(const TfheHipCompressedPackingKey *key, int32_t *pk_t, int32_t *pk_basebit);
+int64_t tfhe_hip_compressed_packing_key_bytes(const TfheHipCompressedPackingKey *key);
+TfheHipPackingKey *tfhe_hip_expand_packing_key_host(const TfheHipCompressedPackingKey *key);
+TfheHipPackingKey *tfhe_hip_expand_packing_key(const TfheHipCompressedPackingKey *key);
+void tfhe_hip_export_compressed_packing_key_toFile(FILE *F, const TfheHipCompressedPackingKey *key);
+TfheHipCompressedPackingKey *tfhe_hip_new_compressed_packing_key_fromFile(FILE *F);
+/* Compressed ring samples.  A compressed ring sample is TFHE_HIP_RING_COMPRESSED_WORDS(N) = 10 + N words: the mask seed,
+ * then the body (4,136 bytes instead of 8,192 at N = 1,024).  Mask word j of the sample is stream word j under that seed;
+ * body = mask * S + mu + e with the set's bk_stdev, as tfhe_hip_ring_encrypt defines it.
+ * ONE SEED PER SAMPLE: two samples under one key must never share mask words -- their difference would be the difference
+ * of their messages plus noise.  The default forms therefore draw ten fresh words of OS entropy for every call (and the
+ * noise from a fresh OS-keyed stream), and no entry takes a block offset into a shared stream.  The _compressed_seeded
+ * forms (fixtures only) take the seed and draw the N noise samples from xoshiro256** started from noise_seed.
+ * tfhe_hip_ring_expand_host: the plain (k+1) N words of a compressed sample of ring size N >= 1 -- the stream words, then
+ * the body -- which tfhe_hip_packed_phase / _decrypt_bits decrypt and tfhe_hip_unpack_samples opens.  Needs no key.
+ * Return 0, or -1 with tfhe_hip_last_error() set and the output untouched: a null argument, count outside 1..N. */
+#define TFHE_HIP_RING_COMPRESSED_WORDS(N) (10 + (N))
+int tfhe_hip_ring_encrypt_compressed(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *mu, Torus32 *out_words);
+int tfhe_hip_ring_encrypt_compressed_seeded(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *mu,
+                                            Torus32 *out_words, const uint32_t *mask_seed10, uint64_t noise_seed);
+int tfhe_hip_ring_encrypt_bits_compressed(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                                          Torus32 *out_words);
+int tfhe_hip_ring_encrypt_bits_compressed_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits,
+                                                 int32_t count, Torus32 *out_words, const uint32_t *mask_seed10,
+                                                 uint64_t noise_seed);
+int tfhe_hip_ring_expand_host(const Torus32 *compressed_words, int32_t N, Torus32 *out_words);
+/* The seeded unpack: tfhe_hip_unpack_samples and its scattered and device forms on nring compressed records of 10 + N words
+ * each.  Semantics, argument checks, chunks of 8,192, slot renaming and errors are those of the plain forms; the result
+ * words are those of tfhe_hip_unpack_samples on the host-expanded samples, word for word.  The mask polynomial is
+ * regenerated on the card inside the extract kernel and never lies in global memory. */
+int tfhe_hip_unpack_samples_seeded(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *compressed_words, int32_t nring,
+                                   const int32_t *index, int32_t count, LweSample *result);
+int tfhe_hip_unpack_samples_seeded_scattered(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *compressed_words,
+                                             int32_t nring, const int32_t *index, int32_t count, LweSample *const *result);
+int tfhe_hip_unpack_samples_seeded_device(const TFheGateBootstrappingCloudKeySet *bk, const void *device_compressed_words,
+                                          int32_t nring, const int32_t *index, int32_t count, LweSample *result);
+/* test entry.  tfhe_hip_test_pack_image: the device NTT image of a packing key (2 n t (k+1) N words) under the twiddles of
+ * cloud key `bk` of the same set -- made now if it was not yet -- copied into out[capacity]; returns the word count (out may
+ * be NULL to ask for it), -1 on error.  Mirrors tfhe_hip_test_key_image. */
+int64_t tfhe_hip_test_pack_image(const TfheHipPackingKey *key, const TFheGateBootstrappingCloudKeySet *bk, Torus32 *out,
+                                 int64_t capacity);
+/* tfhe_hip_test_extract_rows: the rows of the last extract launch (plain or seeded; of an unpack, its last chunk) as the kernel
+ * stored them, [rows][u_stride] with the padding behind word N -- the raw entries above return the rows without it.  Returns
+ * the word count (0 before the first launch; out may be NULL to ask for it), copies only if it fits `capacity`; -1 on error. */
+int64_t tfhe_hip_test_extract_rows(Torus32 *out, int64_t capacity);
+
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through
  * the device NTT (two 27-bit primes + CRT); |ip| must be < 2^12 */
@@ -754,6 +855,9 @@ int tfhe_hip_kernel_pack(const TfheHipPackingKey *key, const TFheGateBootstrappi
  * for tfhe_hip_unpack_samples (index = NULL: 0 .. count - 1); no key switch, no slots involved */
 int tfhe_hip_kernel_ring_extract(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
                                  const int32_t *index, int32_t count, Torus32 *u_out);
+/* the same rows from nring seed-compressed records of 10 + N words through the seeded extract kernel */
+int tfhe_hip_kernel_ring_extract_seeded(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *compressed_words, int32_t nring,
+                                        const int32_t *index, int32_t count, Torus32 *u_out);
 
 #ifdef __cplusplus
 }

@@ -582,6 +582,116 @@ class PackingKey:
             pass
 
 
+def _taken_packing_key(params, ptr):
+    self = PackingKey.__new__(PackingKey)
+    self._take(params, ptr)
+    return self
+
+
+class CompressedPackingKey:
+    """A seed-compressed packing key (include/tfhe_hip.h): a 40-byte mask seed and the bodies [n][t][N] -- what a client
+    sends in place of the raw rows, half their bytes.  expand() gives a PackingKey whose masks are made on the device at
+    its first pack, expand_host() one expanded on the CPU; close() both."""
+
+    def __init__(self, ptr, params):
+        if not ptr:
+            raise ValueError("compressed packing key rejected: " + last_error())
+        self.ptr, self.params = ptr, params
+        t, b = C.c_int32(), C.c_int32()
+        _l.load().tfhe_hip_compressed_packing_key_decomposition(ptr, C.byref(t), C.byref(b))
+        self.t, self.basebit = t.value, b.value
+
+    @classmethod
+    def generate(cls, secret, t=0, basebit=0):
+        return cls(_l.load().tfhe_hip_new_compressed_packing_key(secret.ptr, int(t), int(basebit)), secret.params)
+
+    @classmethod
+    def generate_seeded(cls, secret, noise_seed, mask_seed, t=0, basebit=0):
+        seed = np.ascontiguousarray(mask_seed, dtype=np.uint32).reshape(10)
+        return cls(_l.load().tfhe_hip_new_compressed_packing_key_seeded(secret.ptr, int(t), int(basebit), int(noise_seed),
+                                                                        seed.ctypes.data_as(_l.U32P)), secret.params)
+
+    @classmethod
+    def from_words(cls, params, t, basebit, mask_seed, body):
+        """The cloud side: a key from the seed and the bodies it received (n t N words, copied)."""
+        seed = np.ascontiguousarray(mask_seed, dtype=np.uint32).reshape(10)
+        w = np.ascontiguousarray(body, dtype=np.int32).reshape(-1)
+        tt = int(t) if (t or basebit) else params.ks_t
+        if tt >= 1 and w.size != params.n * tt * params.N:
+            raise ValueError("a compressed packing key of this set and decomposition holds %d body words" % (params.n * tt * params.N))
+        return cls(_l.load().tfhe_hip_new_compressed_packing_key_from_words(params.ptr, int(t), int(basebit),
+                                                                            seed.ctypes.data_as(_l.U32P), _i32p(w)), params)
+
+    def seed(self):
+        return np.ctypeslib.as_array(_l.load().tfhe_hip_compressed_packing_key_seed(self.ptr), shape=(10,)).copy()
+
+    def body(self):
+        """int32 [n t N]: a view of the key's words (valid until close())"""
+        cnt = C.c_int64()
+        p = _l.load().tfhe_hip_compressed_packing_key_body(self.ptr, C.byref(cnt))
+        return np.ctypeslib.as_array(p, shape=(cnt.value,))
+
+    @property
+    def nbytes(self):
+        """the bytes that travel: the seed and the bodies"""
+        return int(_l.load().tfhe_hip_compressed_packing_key_bytes(self.ptr))
+
+    def _params(self):
+        if self.params is None:
+            raise ValueError("a key loaded from a file carries no ParameterSet object: pass params= to load()")
+        return self.params
+
+    def expand(self):
+        return _taken_packing_key(self._params(), _l.load().tfhe_hip_expand_packing_key(self.ptr))
+
+    def expand_host(self):
+        return _taken_packing_key(self._params(), _l.load().tfhe_hip_expand_packing_key_host(self.ptr))
+
+    def save(self, path):
+        with _CFile(path, "wb") as fp:
+            _l.load().tfhe_hip_export_compressed_packing_key_toFile(fp, self.ptr)
+
+    @classmethod
+    def load(cls, path, params=None):
+        """params: the ParameterSet the key belongs to (the file holds its record; expand() hands it to the PackingKey)"""
+        with _CFile(path, "rb") as fp:
+            ptr = _l.load().tfhe_hip_new_compressed_packing_key_fromFile(fp)
+        if not ptr:
+            raise ValueError("cannot load a compressed packing key from %s: %s" % (path, last_error()))
+        return cls(ptr, params)
+
+    def close(self):
+        if self.ptr:
+            _l.load().tfhe_hip_delete_compressed_packing_key(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pack_image(pkey, key):
+    """the device NTT image of a packing key under the twiddles of `key`'s cloud key (made now if it was not yet), int32"""
+    L = _l.load()
+    L.tfhe_hip_clear_error()
+    words = L.tfhe_hip_test_pack_image(pkey.ptr, key.cloud, None, 0)
+    if words < 0:
+        raise RuntimeError(last_error())
+    out = np.zeros(words, dtype=np.int32)
+    if L.tfhe_hip_test_pack_image(pkey.ptr, key.cloud, _i32p(out), words) != words:
+        raise RuntimeError(last_error())
+    return out
+
+
+def seeded_stats():
+    """expanded_packing_keys, packing_expand_launches, seeded_unpacked_samples, seeded_unpack_launches"""
+    s = _l.SeededStats()
+    _l.load().tfhe_hip_get_seeded_stats(C.byref(s))
+    return {f: getattr(s, f) for f in _l.SEEDED_STATS_FIELDS}
+
+
 def pack(pkey, samples, count, key, first=0):
     """The (k+1) N words of samples[first .. first + count) packed under `pkey` (tfhe_hip_pack_samples); `samples` is a
     CiphertextArray, `key` the keyset whose cloud key evaluates.  Pending operations run first."""
@@ -633,33 +743,66 @@ def _ring_words(words, p):
     return np.ascontiguousarray(words, dtype=np.int32).reshape(-1, (p.k + 1) * p.N)
 
 
-def ring_encrypt(mu, key, seed=None):
+def _compressed_fixture(seed, mask_seed):
+    """(mask seed as uint32 [10] or None, noise seed) of a compressed ring encryption: both given, or neither"""
+    if (seed is None) != (mask_seed is None):
+        raise ValueError("the reproducible compressed form takes both seed (the noise) and mask_seed (ten words)")
+    return (None, 0) if seed is None else (np.ascontiguousarray(mask_seed, dtype=np.uint32).reshape(10), int(seed))
+
+
+def ring_encrypt(mu, key, seed=None, compressed=False, mask_seed=None):
     """One ring (TLWE) sample, (k+1) N words, encrypting the N torus words `mu` under the ring key of the secret keyset
     `key` (tfhe_hip_ring_encrypt; host only).  seed: the reproducible form (tests); None draws from OS-keyed streams.
-    packed_phases / packed_decrypt decrypt it."""
+    packed_phases / packed_decrypt decrypt it.
+    compressed: the 10 + N words of a seed-compressed sample instead (mask seed, body), a fresh seed per call; its
+    reproducible form takes seed (the noise) and mask_seed.  ring_expand gives the plain words, unpack_seeded opens it."""
     p = key.params
     m = np.ascontiguousarray([_wrap32(x) for x in np.asarray(mu).reshape(-1)], dtype=np.int32)
     if m.shape != (p.N,):
         raise ValueError("a ring sample of this parameter set carries %d words" % p.N)
-    out = np.zeros((p.k + 1) * p.N, dtype=np.int32)
     L = _l.load()
-    rc = (L.tfhe_hip_ring_encrypt(key.ptr, _i32p(m), _i32p(out)) if seed is None
-          else L.tfhe_hip_ring_encrypt_seeded(key.ptr, _i32p(m), _i32p(out), int(seed)))
+    if compressed:
+        ms, ns = _compressed_fixture(seed, mask_seed)
+        out = np.zeros(10 + p.N, dtype=np.int32)
+        rc = (L.tfhe_hip_ring_encrypt_compressed(key.ptr, _i32p(m), _i32p(out)) if ms is None
+              else L.tfhe_hip_ring_encrypt_compressed_seeded(key.ptr, _i32p(m), _i32p(out), ms.ctypes.data_as(_l.U32P), ns))
+    else:
+        out = np.zeros((p.k + 1) * p.N, dtype=np.int32)
+        rc = (L.tfhe_hip_ring_encrypt(key.ptr, _i32p(m), _i32p(out)) if seed is None
+              else L.tfhe_hip_ring_encrypt_seeded(key.ptr, _i32p(m), _i32p(out), int(seed)))
     if rc != 0:
         raise RuntimeError(last_error())
     return out
 
 
-def ring_encrypt_bits(bits, key, seed=None):
+def ring_encrypt_bits(bits, key, seed=None, compressed=False, mask_seed=None):
     """The same for 1..N bits: coefficient j carries +-2^29 for bit j, coefficients from len(bits) on carry 0."""
     p = key.params
     b = np.ascontiguousarray(bits, dtype=np.int32).reshape(-1)
-    out = np.zeros((p.k + 1) * p.N, dtype=np.int32)
     L = _l.load()
-    rc = (L.tfhe_hip_ring_encrypt_bits(key.ptr, _i32p(b), len(b), _i32p(out)) if seed is None
-          else L.tfhe_hip_ring_encrypt_bits_seeded(key.ptr, _i32p(b), len(b), _i32p(out), int(seed)))
+    if compressed:
+        ms, ns = _compressed_fixture(seed, mask_seed)
+        out = np.zeros(10 + p.N, dtype=np.int32)
+        rc = (L.tfhe_hip_ring_encrypt_bits_compressed(key.ptr, _i32p(b), len(b), _i32p(out)) if ms is None
+              else L.tfhe_hip_ring_encrypt_bits_compressed_seeded(key.ptr, _i32p(b), len(b), _i32p(out),
+                                                                  ms.ctypes.data_as(_l.U32P), ns))
+    else:
+        out = np.zeros((p.k + 1) * p.N, dtype=np.int32)
+        rc = (L.tfhe_hip_ring_encrypt_bits(key.ptr, _i32p(b), len(b), _i32p(out)) if seed is None
+              else L.tfhe_hip_ring_encrypt_bits_seeded(key.ptr, _i32p(b), len(b), _i32p(out), int(seed)))
     if rc != 0:
         raise RuntimeError(last_error())
+    return out
+
+
+def ring_expand(words, N):
+    """The plain 2 N words of every seed-compressed sample in `words` ([nring][10 + N]): the stream words of its seed, then
+    its body (tfhe_hip_ring_expand_host; host only, no key) -> int32 [nring][2 N]"""
+    w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1, 10 + N)
+    out = np.zeros((w.shape[0], 2 * N), dtype=np.int32)
+    for r in range(w.shape[0]):
+        if _l.load().tfhe_hip_ring_expand_host(_i32p(w[r]), int(N), _i32p(out[r])) != 0:
+            raise RuntimeError(last_error())
     return out
 
 
@@ -704,6 +847,59 @@ def unpack_device(device_ptr, nring, key, result, index=None, count=None, first=
     if rc != 0:
         raise RuntimeError(last_error())
     return result
+
+
+def unpack_seeded(words, key, result, index=None, count=None, first=0):
+    """unpack() of seed-compressed ring samples (tfhe_hip_unpack_samples_seeded): words holds nring records of 10 + N
+    words; the mask of each is regenerated on the device.  The result words are those of unpack() on ring_expand(words)."""
+    p = key.params
+    w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1, 10 + p.N)
+    idx, n = _unpack_index(index, count)
+    ip = _i32p(idx) if idx is not None else None
+    L = _l.load()
+    if isinstance(result, CiphertextArray):
+        rc = L.tfhe_hip_unpack_samples_seeded(key.cloud, _i32p(w), w.shape[0], ip, n, result.at(first))
+    else:
+        if len(result) - first < n:
+            raise ValueError("fewer result samples than indices")
+        ptrs = (_l.LS * max(len(result) - first, 1))(*result[first:])
+        rc = L.tfhe_hip_unpack_samples_seeded_scattered(key.cloud, _i32p(w), w.shape[0], ip, n, ptrs)
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def unpack_seeded_device(device_ptr, nring, key, result, index=None, count=None, first=0):
+    """The same from device memory at `device_ptr` (nring (10 + N) int32 words), stream-ordered like unpack_device."""
+    idx, n = _unpack_index(index, count)
+    rc = _l.load().tfhe_hip_unpack_samples_seeded_device(key.cloud, C.c_void_p(int(device_ptr)), int(nring),
+                                                         _i32p(idx) if idx is not None else None, n, result.at(first))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def kernel_ring_extract_seeded(key, words, index=None, count=None):
+    """The seeded extract kernel's rows alone (tfhe_hip_kernel_ring_extract_seeded): u[count][N+1], no key switch."""
+    p = key.params
+    w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1, 10 + p.N)
+    idx, n = _unpack_index(index, count)
+    u = np.zeros((n, p.k * p.N + 1), dtype=np.int32)
+    rc = _l.load().tfhe_hip_kernel_ring_extract_seeded(key.cloud, _i32p(w), w.shape[0], _i32p(idx) if idx is not None else None,
+                                                       n, _i32p(u))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return u
+
+
+def extract_rows(u_stride):
+    """the rows of the last extract launch as the kernel stored them, padding included: int32 [rows][u_stride]"""
+    L = _l.load()
+    words = L.tfhe_hip_test_extract_rows(None, 0)
+    out = np.zeros(max(words, 0), dtype=np.int32)
+    if words < 0 or (words and L.tfhe_hip_test_extract_rows(_i32p(out), words) != words):
+        raise RuntimeError(last_error())
+    return out.reshape(-1, u_stride)
 
 
 def kernel_ring_extract(key, words, index=None, count=None):

@@ -3,6 +3,8 @@ encrypted circuits and protocol function f (Math.cpp:27-417) over the boots* gat
 import ctypes as C
 import os
 
+import numpy as np
+
 from . import api
 from . import lib as _l
 
@@ -93,16 +95,19 @@ class EncryptedVector:
             raise ValueError("a ring sample of this parameter set carries %d bits" % params.N)
         self = cls.__new__(cls)
         self.slots = [api.CiphertextArray(params, bitsize) for _ in range(nslots)]
-        api.unpack(words, key, [a.at(j) for a in self.slots for j in range(bitsize)], count=nslots * bitsize)
+        # a seed-compressed record (10 + N words: ring_encrypt_vector(compressed=True)) is told from a plain sample by its size
+        seeded = np.asarray(words).size == 10 + params.N
+        (api.unpack_seeded if seeded else api.unpack)(words, key, [a.at(j) for a in self.slots for j in range(bitsize)],
+                                                      count=nslots * bitsize)
         return self
 
 
-def ring_encrypt_vector(values, bitsize, key, seed=None):
+def ring_encrypt_vector(values, bitsize, key, seed=None, compressed=False, mask_seed=None):
     """The client side of EncryptedVector.from_ring: len(values) features of `bitsize` bits as ONE ring sample under the
     secret keyset `key` -- bit j of value s at coefficient s * bitsize + j (8 KB for 128 x 8 bits at N = 1,024, where the
-    samples of an EncryptedVector are 2.5 MB)."""
+    samples of an EncryptedVector are 2.5 MB).  compressed: as a seed-compressed sample, 10 + N words (4,136 bytes)."""
     bits = [(int(v) >> j) & 1 for v in values for j in range(bitsize)]
-    return api.ring_encrypt_bits(bits, key, seed=seed)
+    return api.ring_encrypt_bits(bits, key, seed=seed, compressed=compressed, mask_seed=mask_seed)
 
 
 def encrypt_number(params, value, bits, key):

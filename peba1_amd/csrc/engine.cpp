@@ -1236,6 +1236,53 @@ uint32_t *Engine::upload_pack_image(const DeviceKeyImage *key, const Torus32 *ro
     return img;
 }
 
+uint32_t *Engine::expand_pack_image(const DeviceKeyImage *key, const uint32_t seed10[10], const Torus32 *body, int t, size_t *bytes) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const DevParams &dp = key->dp;
+    const size_t body_words = (size_t)dp.n * t * dp.N, words = body_words * 2;
+    uint32_t scale[2];
+    (void)make_twiddles(dp.N, scale);
+    // all three buffers first: a card without room for them fails here, recoverably, with nothing held
+    uint32_t *img = nullptr;
+    int32_t *raw = nullptr, *dbody = nullptr;
+    try {
+        img = static_cast<uint32_t *>(recoverable_alloc(words * 2 * 4, "the NTT image of a packing key"));
+        raw = static_cast<int32_t *>(recoverable_alloc(words * 4, "the staging copy of a packing key"));
+        dbody = static_cast<int32_t *>(recoverable_alloc(body_words * 4, "the bodies of a compressed packing key"));
+    } catch (const ApiError &) {
+        recoverable_free(raw, words * 4);
+        recoverable_free(img, words * 2 * 4);
+        throw;
+    }
+    h2d_staged(dbody, body, body_words, "upload packing key bodies");
+    ExpandBkArgs ea{};
+    std::memcpy(ea.seed.key, seed10, sizeof ea.seed.key);
+    ea.seed.nonce[0] = seed10[8]; ea.seed.nonce[1] = seed10[9];
+    ea.rows = dp.n * t; ea.k = 1; ea.N = dp.N; ea.body = dbody; ea.raw = raw;
+    if (!launch_expand_bk(stream_, ea)) fatal("packing key expand: arguments outside what the kernel was built for");
+    hip_check(hipGetLastError(), "packing key expand launch");
+    launch_bk_transform(stream_, dp, raw, img, key->tw, dp.n * t, 2, scale);
+    hip_check(hipGetLastError(), "packing key transform launch");
+    sync_stream("packing key expansion");
+    recoverable_free(raw, words * 4);
+    recoverable_free(dbody, body_words * 4);
+    ++seeded_stats.expanded_packing_keys;
+    ++seeded_stats.packing_expand_launches;
+    *bytes = words * 2 * 4;
+    return img;
+}
+
+size_t Engine::read_pack_image(const uint32_t *img, size_t bytes, Torus32 *out, size_t capacity) {
+    ENGINE_DEVICE_SCOPE();
+    const size_t words = bytes / 4;
+    if (!out || capacity < words) return words;
+    wait_flight();
+    hip_check(hipMemcpyAsync(out, img, bytes, hipMemcpyDeviceToHost, stream_), "download packing key image");
+    sync_stream("packing key image");
+    return words;
+}
+
 void Engine::free_pack_image(uint32_t *img, size_t bytes) {
     ENGINE_DEVICE_SCOPE();
     if (!img) return;
@@ -1272,10 +1319,10 @@ void Engine::run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int
 
 // ---- ring-encrypted inputs (unpack.hpp, unpack.hip) -----------------------------------------
 void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, int nring, bool ring_on_device, const int32_t *index,
-                        int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait) {
+                        int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait, bool seeded) {
     ENGINE_DEVICE_SCOPE();
     const DevParams &dp = key->dp;
-    const size_t ring_count = (size_t)nring * 2 * dp.N, uw = (size_t)dp.k * dp.N + 1;
+    const size_t ring_count = (size_t)nring * (seeded ? RING_SEED_WORDS + dp.N : 2 * dp.N), uw = (size_t)dp.k * dp.N + 1;
     const int widest = std::min(count, UNPACK_CHUNK);
     // every buffer first (scratch() may throw: nothing has been enqueued then).  The partial sums of the key switches are
     // sized for the widest chunk and for the last one, which may be cut into more ranges
@@ -1299,10 +1346,14 @@ void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, in
     std::vector<int32_t> rows(u_out ? (size_t)widest * dp.u_stride : 0);
     for (int done = 0; done < count; done += UNPACK_CHUNK) {
         const int cnt = std::min(UNPACK_CHUNK, count - done);
-        const UnpackArgs a{dp.N, cnt, dp.u_stride, ring_on_device ? ring_words : dring, dindex + done, u_buf};
-        if (!launch_ring_extract(stream_, a)) api_fail("unpack: arguments outside what the extract kernel was built for");
+        const int32_t *src = ring_on_device ? ring_words : dring;
+        if (seeded ? !launch_ring_extract_seeded(stream_, UnpackSeededArgs{dp.N, cnt, dp.u_stride, src, dindex + done, u_buf})
+                   : !launch_ring_extract(stream_, UnpackArgs{dp.N, cnt, dp.u_stride, src, dindex + done, u_buf}))
+            api_fail("unpack: arguments outside what the extract kernel was built for");
         hip_check(hipGetLastError(), "ring extract launch");
         ++stats.unpack_launches;
+        if (seeded) ++seeded_stats.seeded_unpack_launches;
+        last_extract_words_ = (size_t)cnt * dp.u_stride;
         if (u_out) {
             d2h(rows.data(), u_buf, (size_t)cnt * dp.u_stride, "download extracted rows");
             sync_stream("ring extract");
@@ -1316,8 +1367,19 @@ void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, in
     if (u_out) return;
     stats.unpacked_samples += (uint64_t)count;
     stats.keyswitches += (uint64_t)count;
+    if (seeded) seeded_stats.seeded_unpacked_samples += (uint64_t)count;
     // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
     finish(wait || !ring_on_device, "unpack");
+}
+
+size_t Engine::read_extract_rows(Torus32 *out, size_t capacity) {
+    ENGINE_DEVICE_SCOPE();
+    const size_t words = last_extract_words_;
+    if (!out || capacity < words || !words) return words;
+    wait_flight();
+    d2h(out, scratch_as<int32_t>(S_UNPACK_EXTRACT, words), words, "download extract rows");     // (sized by that launch: no growth)
+    sync_stream("extract rows");
+    return words;
 }
 
 }  // namespace tfhe_hip

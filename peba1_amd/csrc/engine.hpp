@@ -183,7 +183,14 @@ public:
     // twiddles of `key` (a cloud key of the same ring); device memory exhausted: ApiError, nothing held.  *bytes: what the
     // image holds, for free_pack_image.
     uint32_t *upload_pack_image(const DeviceKeyImage *key, const Torus32 *rows, int t, size_t *bytes);
+    // The same image for a key that holds a mask seed and bodies [n][t][N] alone (tfhe_hip_expand_packing_key): the bodies go
+    // up through the pinned staging area (half the bytes of the raw rows), launch_expand_bk (rows = n t, k = 1) writes the raw
+    // staging buffer -- masks from the stream, bodies from the upload -- and launch_bk_transform follows.  All three buffers
+    // are allocated before anything is enqueued: device memory exhausted = ApiError with nothing held.
+    uint32_t *expand_pack_image(const DeviceKeyImage *key, const uint32_t seed10[10], const Torus32 *body, int t, size_t *bytes);
     void free_pack_image(uint32_t *img, size_t bytes);
+    // test path: a packing key's image copied back -- returns the word count, copies only if it fits `capacity`
+    size_t read_pack_image(const uint32_t *img, size_t bytes, Torus32 *out, size_t capacity);
     // One pack of `count` samples, enqueued on the engine's stream behind whatever is there.  slots (the slot form): sample
     // j is pool slot slots[j]; raw_words (the test form, slots null): sample j is raw_words[j][n + 1], uploaded for this
     // call.  idx_per_wg: mask indices per workgroup, 0 = the engine's choice.  out: 2N words, host or device; a host
@@ -197,11 +204,17 @@ public:
     // the work enqueued on the engine's stream.  The raw test form (u_out [count][kN+1]): the extract kernel's rows alone,
     // no key switch.  The caller has checked every index and waited for the flight.  Every buffer is sized before
     // anything is enqueued: an ApiError (device memory exhausted) leaves nothing written.
+    // seeded: ring_words holds seed-compressed records of RING_SEED_WORDS + N words, opened by the seeded extract kernel.
     void run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, int nring, bool ring_on_device, const int32_t *index,
-                    int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait);
+                    int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait, bool seeded = false);
+
+    // test path: the padded rows the last extract launch wrote, [rows][u_stride] as the kernel stored them -- returns the
+    // word count, copies only if it fits `capacity`
+    size_t read_extract_rows(Torus32 *out, size_t capacity);
 
     TfheHipStats stats{};
     TfheHipExpandStats expand_stats{};  // the device expansions of seed-compressed cloud keys (tfhe_hip_get_expand_stats)
+    TfheHipSeededStats seeded_stats{};  // device-expanded packing keys and seeded unpacks (tfhe_hip_get_seeded_stats)
     bool kernel_timing = false;
     // the launch rules' tunings (launch_plan.hpp; written by ensure_init()'s environment reads and tfhe_hip_set_tuning)
     LaunchTunings tunings;
@@ -306,6 +319,7 @@ private:
     int flight_levels_ = 0;
     bool in_flight_ = false;
     std::chrono::steady_clock::time_point flight_t0_;
+    size_t last_extract_words_ = 0;                     // rows * u_stride of the last extract launch (read_extract_rows)
     HostStage stage_{*this};                            // the host lists of calls that return without a wait (host_stage.hpp)
     int device_ = 0;
     int cu_count_ = 256;

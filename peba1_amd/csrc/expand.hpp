@@ -5,6 +5,8 @@
 // Mask word m of a key is word 2 (m mod 8) + 1 of ChaCha20 block floor(m / 8) under (key, nonce), 64-bit block counter
 // from 0 -- what Rng::torus() yields on its m-th call (host_keys.cpp).  The BK's masks come first, in [i][row][u < k][j]
 // order, then the KSK's in [i][j][v = 1 .. base-1][q < n] order.  A block is therefore eight mask words.
+// A seed-compressed packing key has a stream of its own seed: its masks in [i][p][j] order, which launch_expand_bk writes
+// with rows = n t, k = 1.  A seed-compressed ring sample likewise, N words (unpack.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

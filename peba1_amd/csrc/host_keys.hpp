@@ -111,6 +111,16 @@ struct TfheHipCompressedCloudKey {
     std::vector<Torus32> bk_body;    // [n][(k+1)l][N]
     std::vector<Torus32> ksk_body;   // [kN][t][base-1]
 };
+// A packing key as it travels (include/tfhe_hip.h "seed-compressed packing keys and ring samples"): the mask polynomial of
+// row (i, p) is words (i t + p) N .. of the ChaCha20 stream of `seed`, only the bodies are held.
+constexpr uint32_t COMPRESSED_PACK_MAGIC = 0x4350414Bu;
+struct TfheHipCompressedPackingKey {
+    uint32_t magic;
+    tfhe_hip::Params p;
+    int32_t t, basebit;
+    uint32_t seed[10];               // ChaCha20 key[8], nonce[2]
+    std::vector<Torus32> body;       // [n][t][N]
+};
 
 namespace tfhe_hip {
 // `secret` yields the key bits and every noise sample, `mask` the public uniform masks.  The seeded path passes ONE

@@ -19,7 +19,7 @@ using namespace tfhe_hip;
 
 namespace {
 
-enum : uint32_t { KIND_PARAMS = 1, KIND_CLOUD = 2, KIND_SECRET = 3, KIND_SAMPLE = 4, KIND_COMPRESSED_CLOUD = 5 };
+enum : uint32_t { KIND_PARAMS = 1, KIND_CLOUD = 2, KIND_SECRET = 3, KIND_SAMPLE = 4, KIND_COMPRESSED_CLOUD = 5, KIND_COMPRESSED_PACKING = 6 };
 constexpr uint32_t VERSION = 1;
 
 struct Header { char magic[4]; uint32_t version, kind, reserved; uint64_t bytes; };
@@ -100,6 +100,10 @@ TfheHipCloudKey *get_cloud_payload(FILE *F, uint64_t declared, bool with_secret_
 // a seed-compressed cloud key: parameter record, the ten seed words, both body arrays
 uint64_t compressed_bytes(const Params &p) {
     return sizeof(ParamsRecord) + 10 * sizeof(uint32_t) + (p.bk_body_words() + p.ksk_body_words()) * sizeof(Torus32);
+}
+// a seed-compressed packing key: parameter record, (t, basebit), the ten seed words, the bodies [n][t][N]
+uint64_t compressed_packing_bytes(const Params &p, int32_t t) {
+    return sizeof(ParamsRecord) + 2 * sizeof(int32_t) + 10 * sizeof(uint32_t) + (uint64_t)p.n * (uint64_t)t * (uint64_t)p.N * sizeof(Torus32);
 }
 
 }  // namespace
@@ -183,6 +187,38 @@ TfheHipCompressedCloudKey *tfhe_hip_new_compressed_cloud_key_fromFile(FILE *F) {
         get_vec(F, key->bk_body, key->p.bk_body_words());
         get_vec(F, key->ksk_body, key->p.ksk_body_words());
         key->magic = COMPRESSED_KEY_MAGIC;
+        return key.release();
+    });
+}
+void tfhe_hip_export_compressed_packing_key_toFile(FILE *F, const TfheHipCompressedPackingKey *key) {
+    io_guard([&] {
+        if (!F || !key || key->magic != COMPRESSED_PACK_MAGIC) api_fail("tfhe_io: null or deleted compressed packing key");
+        put_header(F, KIND_COMPRESSED_PACKING, compressed_packing_bytes(key->p, key->t));
+        put_params(F, key->p);
+        const int32_t decomp[2] = {key->t, key->basebit};
+        put(F, decomp, sizeof decomp);
+        put(F, key->seed, sizeof key->seed);
+        put_vec(F, key->body);
+        return Done{};
+    });
+}
+TfheHipCompressedPackingKey *tfhe_hip_new_compressed_packing_key_fromFile(FILE *F) {
+    return io_guard([&]() -> TfheHipCompressedPackingKey * {
+        if (!F) api_fail("tfhe_io: null file");
+        const uint64_t declared = get_header(F, KIND_COMPRESSED_PACKING);
+        std::unique_ptr<TfheHipCompressedPackingKey> key(new TfheHipCompressedPackingKey());
+        key->p = get_params(F);
+        int32_t decomp[2];
+        get(F, decomp, sizeof decomp);
+        // what the constructors refuse is refused here, and the sizes must agree, before anything is allocated
+        if (const char *why = pack_decomp_error(key->p.N, key->p.k, decomp[0], decomp[1])) api_fail(std::string("tfhe_io: packing decomposition in file: ") + why);
+        if (key->p.n > 1024) api_fail("tfhe_io: a packing key takes an LWE dimension n in [1, 1024]");
+        key->t = decomp[0];
+        key->basebit = decomp[1];
+        if (declared != compressed_packing_bytes(key->p, key->t)) api_fail("tfhe_io: payload size does not match the file's parameter record (corrupt file)");
+        get(F, key->seed, sizeof key->seed);
+        get_vec(F, key->body, (size_t)key->p.n * key->t * key->p.N);
+        key->magic = COMPRESSED_PACK_MAGIC;
         return key.release();
     });
 }

@@ -12,6 +12,10 @@ struct TfheHipPackingKey {
     std::vector<Torus32> rows;
     uint32_t *img;
     size_t img_bytes;
+    // a device-expanded key (tfhe_hip_expand_packing_key, seeded_host.cpp) holds the mask seed and the bodies alone: rows
+    // stays empty until tfhe_hip_packing_key_words asks for the words
+    std::vector<uint32_t> mask_seed; // [10] or empty (a plain key)
+    std::vector<Torus32> body;       // [n][t][N]
 };
 
 namespace {
@@ -27,12 +31,13 @@ void pack_add_mul_by_bits(uint32_t *body, const uint32_t *mask, const int32_t *b
 }
 
 // 0, 0 = the set's own key-switch decomposition; null if the pair is refused (the error is set)
-TfheHipPackingKey *new_packing_key_object(const char *who, const Params &p, int32_t pk_t, int32_t pk_basebit) {
+// with_rows false: the rows stay empty (a device-expanded key, seeded_host.cpp)
+TfheHipPackingKey *new_packing_key_object(const char *who, const Params &p, int32_t pk_t, int32_t pk_basebit, bool with_rows = true) {
     if (pk_t == 0 && pk_basebit == 0) { pk_t = p.ks_t; pk_basebit = p.ks_basebit; }
     if (const char *why = pack_decomp_error(p.N, p.k, pk_t, pk_basebit)) { set_error(std::string(who) + ": " + why); return nullptr; }
     if (p.n < 1 || p.n > 1024) { set_error(std::string(who) + ": LWE dimension n must be in [1, 1024]"); return nullptr; }
     auto *key = new TfheHipPackingKey{PACK_MAGIC, p, pk_t, pk_basebit, std::vector<Torus32>(), nullptr, 0};
-    key->rows.assign((size_t)p.n * pk_t * (p.k + 1) * p.N, 0);
+    if (with_rows) key->rows.assign((size_t)p.n * pk_t * (p.k + 1) * p.N, 0);
     return key;
 }
 
@@ -81,7 +86,10 @@ const TfheHipPackingKey *pack_key_checked(const char *who, const TfheHipPackingK
 // the key's image, made at first use (under the recorder lock, the cloud key's image in place)
 const uint32_t *pack_image(const TfheHipPackingKey *ckey, const TFheGateBootstrappingCloudKeySet *bk) {
     auto *key = const_cast<TfheHipPackingKey *>(ckey);
-    if (!key->img) key->img = Engine::get().upload_pack_image(bk->bk->dev, key->rows.data(), key->t, &key->img_bytes);
+    if (!key->img)
+        key->img = key->mask_seed.empty()
+                       ? Engine::get().upload_pack_image(bk->bk->dev, key->rows.data(), key->t, &key->img_bytes)
+                       : Engine::get().expand_pack_image(bk->bk->dev, key->mask_seed.data(), key->body.data(), key->t, &key->img_bytes);
     return key->img;
 }
 
@@ -113,6 +121,18 @@ void packed_phases(const TfheHipSecretKey &sk, const Torus32 *words, uint32_t *p
     std::memcpy(ph, w + (size_t)k * N, (size_t)N * 4);
     for (int u = 0; u < k; ++u) pack_add_mul_by_bits(ph, w + (size_t)u * N, sk.tlwe_key.data() + (size_t)u * N, N, 0u - 1u);
 }
+
+// [n][t][2][N] from seed and bodies [n][t][N]: the mask polynomials are consecutive stretches of one sequential stream
+void expand_packing_rows_host(const Params &p, int t, const uint32_t seed10[10], const Torus32 *body, std::vector<Torus32> &rows) {
+    const size_t N = (size_t)p.N, nrows = (size_t)p.n * t;
+    Rng mask = Rng::keyed(seed10);
+    rows.assign(nrows * 2 * N, 0);
+    for (size_t r = 0; r < nrows; ++r) {
+        Torus32 *smp = rows.data() + r * 2 * N;
+        for (size_t j = 0; j < N; ++j) smp[j] = mask.torus();
+        std::memcpy(smp + N, body + r * N, N * sizeof(Torus32));
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -142,6 +162,11 @@ void tfhe_hip_delete_packing_key(TfheHipPackingKey *key) {
 }
 const Torus32 *tfhe_hip_packing_key_words(const TfheHipPackingKey *key, int64_t *count) {
     if (!key || key->magic != PACK_MAGIC) { set_error("tfhe_hip_packing_key_words: null or deleted packing key"); if (count) *count = 0; return nullptr; }
+    if (!key->mask_seed.empty() && key->rows.empty()) {   // a device-expanded key: the host rows are made when asked for
+        auto g = recorder_lock();
+        auto *k = const_cast<TfheHipPackingKey *>(key);
+        if (k->rows.empty()) expand_packing_rows_host(k->p, k->t, k->mask_seed.data(), k->body.data(), k->rows);
+    }
     if (count) *count = (int64_t)key->rows.size();
     return key->rows.data();
 }

@@ -1007,6 +1007,11 @@ void tfhe_hip_reset_stats(void) {
     auto g = recorder_lock();
     Engine::get().stats = TfheHipStats{};
     Engine::get().expand_stats = TfheHipExpandStats{};
+    Engine::get().seeded_stats = TfheHipSeededStats{};
+}
+void tfhe_hip_get_seeded_stats(TfheHipSeededStats *out) {
+    auto g = recorder_lock();
+    if (out) *out = Engine::get().seeded_stats;
 }
 void tfhe_hip_get_expand_stats(TfheHipExpandStats *out) {
     auto g = recorder_lock();
@@ -1390,6 +1395,8 @@ int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const 
 
 // and that of the seed-compressed cloud keys
 #include "compressed_host.cpp"
+// and that of the seed-compressed packing keys and ring samples (it uses the packing key and the unpack defined above)
+#include "seeded_host.cpp"
 
 // The recorder is compiled as part of this object.  build.sh is one of the files kernels_sha16 hashes (kernel_id.py): a new
 // host source named there would mark every committed counter summary stale although no kernel changed.

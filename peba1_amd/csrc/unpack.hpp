@@ -28,4 +28,18 @@ struct UnpackArgs {
 // false, and nothing launched, for arguments outside what the kernel was built for
 bool launch_ring_extract(hipStream_t s, const UnpackArgs &a);
 
+// A seed-compressed ring sample (include/tfhe_hip.h "seed-compressed packing keys and ring samples") is a record of
+// RING_SEED_WORDS + N words: the mask seed (ChaCha20 key[8], nonce[2]), then the body.  Mask word j of the sample is word j
+// of the stream of its own seed (expand.hpp: word 2 (j mod 8) + 1 of block j / 8).
+constexpr int RING_SEED_WORDS = 10;
+// One seeded extract launch: as UnpackArgs, with ring = nring records of RING_SEED_WORDS + N words.  The rows it writes
+// are those launch_ring_extract writes from the expanded samples.
+struct UnpackSeededArgs {
+    int32_t N, count, u_stride;
+    const int32_t *ring;
+    const int32_t *index;
+    int32_t *u_buf;
+};
+bool launch_ring_extract_seeded(hipStream_t s, const UnpackSeededArgs &a);
+
 }  // namespace tfhe_hip

@@ -38,10 +38,12 @@ int ring_encrypt_impl(const char *who, const TFheGateBootstrappingSecretKeySet *
     return 0;
 }
 
-// result_at(j): sample j of the results, consecutive or scattered
+// result_at(j): sample j of the results, consecutive or scattered; seeded: `ring` holds seed-compressed records
+// (seeded_host.cpp)
 template <typename At>
 int unpack_impl(const char *who, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring, int32_t nring,
-                const int32_t *index, int32_t count, bool have_result, bool consecutive, At result_at, bool device_src) {
+                const int32_t *index, int32_t count, bool have_result, bool consecutive, At result_at, bool device_src,
+                bool seeded = false) {
     const std::string w = std::string(who) + ": ";
     if (!ring || !have_result) api_fail(w + "null ring words or result");
     if (!bk || !bk->bk) api_fail(w + "null cloud key");
@@ -59,7 +61,7 @@ int unpack_impl(const char *who, const TFheGateBootstrappingCloudKeySet *bk, con
     slots.reserve((size_t)count);
     try {
         for (int32_t j = 0; j < count; ++j) slots.push_back(alloc_slot(pool));
-        Engine::get().run_unpack(bk->bk->dev, ring, nring, device_src, index, count, pool, slots.data(), nullptr, !device_src);
+        Engine::get().run_unpack(bk->bk->dev, ring, nring, device_src, index, count, pool, slots.data(), nullptr, !device_src, seeded);
     } catch (const ApiError &) {
         for (int32_t s : slots) pool->release(s);         // the pool or the device is full: nothing was enqueued
         throw;

@@ -68,6 +68,7 @@ def pack_match_bits(pkey, bits, key):
 
 def unpack_templates(ring_words_list, params, nslots, bitsize, key):
     """The way in for a gallery that travels and rests as ring samples: one EncryptedVector per entry of ring_words_list
-    (each the (k+1) N words circuits.ring_encrypt_vector made on the client), ready for identify().  One unpack per
+    (each the (k+1) N words circuits.ring_encrypt_vector made on the client, or the 10 + N words of its compressed form --
+    told apart by their count -- in which a gallery rests in half the bytes), ready for identify().  One unpack per
     template; LWE samples exist only on the device."""
     return [circuits.EncryptedVector.from_ring(params, w, nslots, bitsize, key) for w in ring_words_list]

@@ -84,9 +84,16 @@ class ExpandStats(C.Structure):
     _fields_ = [("expanded_keys", C.c_uint64), ("expand_launches", C.c_uint64)]
 
 
+class SeededStats(C.Structure):
+    """TfheHipSeededStats: device-expanded packing keys and seeded unpacks (tfhe_hip_get_seeded_stats)."""
+    _fields_ = [("expanded_packing_keys", C.c_uint64), ("packing_expand_launches", C.c_uint64),
+                ("seeded_unpacked_samples", C.c_uint64), ("seeded_unpack_launches", C.c_uint64)]
+
+
 STATS_FIELDS = [f for f, _ in Stats._fields_] + [f for f, _ in StatsAll._fields_]
 UNPACK_STATS_FIELDS = [f for f, _ in StatsWhole._fields_]
 EXPAND_STATS_FIELDS = [f for f, _ in ExpandStats._fields_]
+SEEDED_STATS_FIELDS = [f for f, _ in SeededStats._fields_]
 
 
 PS = C.POINTER(ParameterSet)
@@ -246,6 +253,30 @@ SIGNATURES = {
     "tfhe_hip_test_key_image": (C.c_int64, [CK, C.c_int, I32P, C.c_int64]),
     "tfhe_hip_last_expand_ms": (C.c_double, []),
     "tfhe_hip_get_expand_stats": (None, [C.POINTER(ExpandStats)]),
+    "tfhe_hip_get_seeded_stats": (None, [C.POINTER(SeededStats)]),
+    "tfhe_hip_new_compressed_packing_key": (C.c_void_p, [SK, C.c_int32, C.c_int32]),
+    "tfhe_hip_new_compressed_packing_key_seeded": (C.c_void_p, [SK, C.c_int32, C.c_int32, C.c_uint64, U32P]),
+    "tfhe_hip_new_compressed_packing_key_from_words": (C.c_void_p, [PS, C.c_int32, C.c_int32, U32P, I32P]),
+    "tfhe_hip_delete_compressed_packing_key": (None, [C.c_void_p]),
+    "tfhe_hip_compressed_packing_key_seed": (U32P, [C.c_void_p]),
+    "tfhe_hip_compressed_packing_key_body": (I32P, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "tfhe_hip_compressed_packing_key_decomposition": (C.c_int, [C.c_void_p, I32P, I32P]),
+    "tfhe_hip_compressed_packing_key_bytes": (C.c_int64, [C.c_void_p]),
+    "tfhe_hip_expand_packing_key_host": (C.c_void_p, [C.c_void_p]),
+    "tfhe_hip_expand_packing_key": (C.c_void_p, [C.c_void_p]),
+    "tfhe_hip_export_compressed_packing_key_toFile": (None, [C.c_void_p, C.c_void_p]),
+    "tfhe_hip_new_compressed_packing_key_fromFile": (C.c_void_p, [C.c_void_p]),
+    "tfhe_hip_ring_encrypt_compressed": (C.c_int, [SK, I32P, I32P]),
+    "tfhe_hip_ring_encrypt_compressed_seeded": (C.c_int, [SK, I32P, I32P, U32P, C.c_uint64]),
+    "tfhe_hip_ring_encrypt_bits_compressed": (C.c_int, [SK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_ring_encrypt_bits_compressed_seeded": (C.c_int, [SK, I32P, C.c_int32, I32P, U32P, C.c_uint64]),
+    "tfhe_hip_ring_expand_host": (C.c_int, [I32P, C.c_int32, I32P]),
+    "tfhe_hip_unpack_samples_seeded": (C.c_int, [CK, I32P, C.c_int32, I32P, C.c_int32, LS]),
+    "tfhe_hip_unpack_samples_seeded_scattered": (C.c_int, [CK, I32P, C.c_int32, I32P, C.c_int32, C.POINTER(LS)]),
+    "tfhe_hip_unpack_samples_seeded_device": (C.c_int, [CK, C.c_void_p, C.c_int32, I32P, C.c_int32, LS]),
+    "tfhe_hip_kernel_ring_extract_seeded": (C.c_int, [CK, I32P, C.c_int32, I32P, C.c_int32, I32P]),
+    "tfhe_hip_test_pack_image": (C.c_int64, [C.c_void_p, CK, I32P, C.c_int64]),
+    "tfhe_hip_test_extract_rows": (C.c_int64, [I32P, C.c_int64]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])

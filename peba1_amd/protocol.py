@@ -16,6 +16,7 @@ that follows it.
     python -m peba1_amd.protocol --nslots 128            # genuine and impostor run, one GPU
     python -m peba1_amd.protocol --clients 4             # four clients, each with a key pair of its own, batched
     python -m peba1_amd.protocol --compressed-keys       # the cloud key travels as a seed and the bodies (10x fewer bytes)
+    python -m peba1_amd.protocol --seeded-inputs         # template and sample travel as seed-compressed ring samples
 
 With --clients K the server side runs as a multi-user server does: Function_f of all K clients in ONE flush and
 Function_g of all K in a second one (multi-key flushes, tuning "batch_keys"), one JSON line per client.
@@ -29,14 +30,26 @@ from . import api, circuits
 MAX_BITSIZE = 24        # 3 * bitsize: width of the distance and of result_b (main.cpp:46)
 
 
-def run_p1(params, key, sample, template, bound_match, r0, r1, bitsize=8, cloud=None, function_f=None):
+def shipped_vector(params, values, bitsize, key, ev):
+    """What --seeded-inputs puts between client and server: the client encrypts the features as ONE seed-compressed ring
+    sample (10 + N words: a fresh mask seed and the body), the server opens it on the device under its cloud key."""
+    words = circuits.ring_encrypt_vector(values, bitsize, key, compressed=True)
+    return circuits.EncryptedVector.from_ring(params, words, len(values), bitsize, ev)
+
+
+def run_p1(params, key, sample, template, bound_match, r0, r1, bitsize=8, cloud=None, function_f=None, seeded_inputs=False):
     """One protocol run.  `key` is the client's secret keyset (encrypts, decrypts); `cloud`
     (default: its embedded cloud keyset) is all the evaluating side uses.  Returns a dict with
-    the decrypted y, whether the client was authenticated (y == r1, main.cpp:578) and timings."""
+    the decrypted y, whether the client was authenticated (y == r1, main.cpp:578) and timings.
+    seeded_inputs: template and sample travel as seed-compressed ring samples (shipped_vector)."""
     ev = key if cloud is None else cloud
     t0 = time.perf_counter()
-    enc_template = circuits.EncryptedVector(params, template, bitsize, key).to_device()
-    enc_sample = circuits.EncryptedVector(params, sample, bitsize, key).to_device()
+    if seeded_inputs:
+        enc_template = shipped_vector(params, template, bitsize, key, ev)
+        enc_sample = shipped_vector(params, sample, bitsize, key, ev)
+    else:
+        enc_template = circuits.EncryptedVector(params, template, bitsize, key).to_device()
+        enc_sample = circuits.EncryptedVector(params, sample, bitsize, key).to_device()
     enc_bound = circuits.encrypt_number(params, bound_match, MAX_BITSIZE, key)
     enc_r0 = circuits.encrypt_number(params, r0, bitsize, key)           # main.cpp:553-559
     enc_r1 = circuits.encrypt_number(params, r1, bitsize, key)
@@ -118,9 +131,15 @@ def parse_args(argv=None):
                     help="K > 0: K clients with key pairs of their own, Function_f and Function_g batched over them")
     ap.add_argument("--compressed-keys", action="store_true",
                     help="each client ships a seed-compressed cloud key; the server expands it on the device at first use")
+    ap.add_argument("--seeded-inputs", action="store_true",
+                    help="template and sample travel as seed-compressed ring samples and are opened on the device")
     a = ap.parse_args(argv)
     if a.clients < 0:
         ap.error("--clients must be >= 0")
+    if a.seeded_inputs and a.clients:
+        ap.error("--seeded-inputs runs the single-client form")
+    if a.seeded_inputs and a.nslots * 8 > 1024:
+        ap.error("--seeded-inputs carries nslots * 8 bits in one ring sample of 1,024")
     return a
 
 
@@ -162,7 +181,7 @@ def main():
     runs = {"genuine": [t + 1 for t in template], "impostor": [(91 * i + 5) % 256 for i in range(a.nslots)]}
     for name, sample in runs.items():
         out = run_p1(params, key, sample, template, a.bound, r0=17, r1=99, cloud=cloud,
-                     function_f=circuits.function_f_fast if a.fast else None)
+                     function_f=circuits.function_f_fast if a.fast else None, seeded_inputs=a.seeded_inputs)
         out["distance"] = sum((x - y) ** 2 for x, y in zip(sample, template))
         print(json.dumps({"run": name, **out}))
     if cloud is not None:
