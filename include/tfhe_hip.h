@@ -432,6 +432,15 @@ typedef struct TfheHipSeededStats {
     uint64_t seeded_unpack_launches;
 } TfheHipSeededStats;
 void tfhe_hip_get_seeded_stats(TfheHipSeededStats *out);
+/* seed-compressed LWE sample arrays, a struct of their own for the same reason: the samples written into slots by the
+ * seeded import entries and the expand kernel launches they took, one per chunk of 8,192 (the raw entry
+ * tfhe_hip_kernel_lwe_expand counts its launches too, and no samples).  A seeded import switches no key and runs no flush:
+ * nothing in TfheHipStats moves.  tfhe_hip_reset_stats() clears these too. */
+typedef struct TfheHipSeededLweStats {
+    uint64_t seeded_imported_samples;
+    uint64_t seeded_import_launches;
+} TfheHipSeededLweStats;
+void tfhe_hip_get_seeded_lwe_stats(TfheHipSeededLweStats *out);
 /* when on, every kernel launch is bracketed by HIP events, read back after the flush */
 void tfhe_hip_set_kernel_timing(int on);
 /* distinct cloud keys the last executed flush ran under (1 unless "batch_keys" is on; 0 before the first flush) */
@@ -819,6 +828,76 @@ int64_t tfhe_hip_test_pack_image(const TfheHipPackingKey *key, const TFheGateBoo
  * stored them, [rows][u_stride] with the padding behind word N -- the raw entries above return the rows without it.  Returns
  * the word count (0 before the first launch; out may be NULL to ask for it), copies only if it fits `capacity`; -1 on error. */
 int64_t tfhe_hip_test_extract_rows(Torus32 *out, int64_t capacity);
+
+/* ---- seed-compressed LWE sample arrays: what bootsSymEncrypt makes, as one seed and one word per sample ----
+ * An LWE sample is n uniform public mask words and one body: 631 words at P128, of which 630 carry no information.  An
+ * array of `count` fresh samples travels as ONE record of TFHE_HIP_LWE_COMPRESSED_WORDS(count) = 10 + count words: the
+ * mask seed (ChaCha20 key[8], nonce[2]), then body[0 .. count).  1,024 bits at P128: 4,136 bytes against 2,584,576.
+ * The stream is the compressed cloud key's.  Mask word i of sample j (i < n) is stream word m = j n + i: word
+ * 2 (m mod 8) + 1 of ChaCha20 block floor(m / 8) under (key, nonce), 64-bit block counter from 0
+ * (tfhe_hip_test_chacha20_block).  With s the secret LWE key,
+ *     body[j] = sum_i a[j][i] s[i] + mu[j] + e[j]   mod 2^32,
+ * e[j] gaussian of the set's ks_stdev: the deviation bootsSymEncrypt uses.  Expanded sample j is (a[j][0 .. n), body[j]):
+ * exactly a fresh bootsSymEncrypt sample -- no key switch was paid, no cloud key is involved, any parameter set with
+ * n <= 1,024 will do -- and word for word what tfhe_hip_import_samples takes.
+ * A record holds at most TFHE_HIP_LWE_RECORD_MAX = 2^20 samples; more are refused.  With n <= 2^10 the last stream word
+ * index is 2^20 * 2^10 - 1 = 2^30 - 1: every word index, and the end j n + n of every sample's run, stays below 2^31.
+ * ONE SEED PER RECORD: two samples under one key must never share mask words -- their difference would be the difference
+ * of their messages plus noise.  Within a record distinct samples use disjoint stream words by construction (sample j owns
+ * words j n .. j n + n - 1).  The default encryptors therefore draw ten fresh words of OS entropy for every call (and the
+ * noise from a fresh OS-keyed stream), and no entry takes an offset into a stream shared between records.  The _seeded
+ * forms (fixtures only; NOT for samples that protect data) take the seed and draw the noise from xoshiro256** started from
+ * noise_seed, one gaussian per sample in order.
+ * tfhe_hip_sym_encrypt_bits_compressed: mu[j] = +-2^29 for bit j, as bootsSymEncrypt.  _torus_compressed: any messages
+ * mu[0 .. count), the array twin of tfhe_hip_sym_encrypt_torus.  Host only: neither the device nor the streams of
+ * bootsSymEncrypt, a keyset or any other object are touched.
+ * tfhe_hip_lwe_expand_host: out_words[j] (n + 1 words) = expanded sample index[j] of a record of record_count samples;
+ * index = NULL means 0 .. count - 1; any order, repeats allowed.  Needs no key.  The reference, and the way in for a caller
+ * without a GPU.
+ * Return 0, or -1 with tfhe_hip_last_error() set and the output untouched: a null argument, count < 1, a record_count (for
+ * the encryptors: count) outside 1 .. 2^20, an index outside the record, n outside 1 .. 1,024. */
+#define TFHE_HIP_LWE_COMPRESSED_WORDS(count) (10 + (count))
+#define TFHE_HIP_LWE_RECORD_MAX (1 << 20)
+int tfhe_hip_sym_encrypt_bits_compressed(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                                         Torus32 *out_words);
+int tfhe_hip_sym_encrypt_bits_compressed_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                                                Torus32 *out_words, const uint32_t *mask_seed10, uint64_t noise_seed);
+int tfhe_hip_sym_encrypt_torus_compressed(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *mu, int32_t count,
+                                          Torus32 *out_words);
+int tfhe_hip_sym_encrypt_torus_compressed_seeded(const TFheGateBootstrappingSecretKeySet *secret, const Torus32 *mu, int32_t count,
+                                                 Torus32 *out_words, const uint32_t *mask_seed10, uint64_t noise_seed);
+int tfhe_hip_lwe_expand_host(const Torus32 *compressed_words, int32_t n, int32_t record_count, const int32_t *index, int32_t count,
+                             Torus32 *out_words);
+/* The seeded import: result[j] becomes sample index[j] of the record (index = NULL: 0 .. count - 1; any order, repeats
+ * allowed), its masks regenerated on the card straight into the sample's slot -- no expanded array ever lies in global
+ * memory, and count words cross the bus instead of count (n + 1).  The result words are those of tfhe_hip_import_samples
+ * applied to tfhe_hip_lwe_expand_host of the same record and index, word for word, the slot's padding included.
+ * Semantics, as the unpack entries: every argument is checked before the device is looked at and before anything changes;
+ * every result is renamed into a fresh slot; a flush in flight is completed first; recorded operations that have not run
+ * stay recorded -- they cannot name the new slots.  The host form returns with the slots written (seed, the bodies the
+ * index names and the lists went up through the pinned staging area); the device form reads the whole record from device
+ * memory and returns with the work enqueued on tfhe_hip_stream() (the caller keeps device_compressed_words until the stream
+ * has passed).  Host mirrors are stale until a decrypt, an export or tfhe_hip_sync_samples; in immediate mode they are
+ * refreshed on return.  Any count is accepted; work proceeds in chunks of at most 8,192 samples.
+ * result: `count` consecutive samples of one array; the scattered form takes `count` sample pointers instead.
+ * Return 0, or -1 with tfhe_hip_last_error() set and the call without effect (results keep values and slots): a null
+ * pointer, count < 1, record_count outside 1 .. 2^20, an index outside the record, n above 1,024, a result sample this
+ * library did not allocate or of another LWE dimension than the set's, count past the end of the result array, the slot
+ * pool exhausted, device memory exhausted while the pool grows (tfhe_hip_test_set_alloc_cap). */
+int tfhe_hip_import_samples_seeded(const TFheGateBootstrappingParameterSet *params, const Torus32 *compressed_words,
+                                   int32_t record_count, const int32_t *index, int32_t count, LweSample *result);
+int tfhe_hip_import_samples_seeded_scattered(const TFheGateBootstrappingParameterSet *params, const Torus32 *compressed_words,
+                                             int32_t record_count, const int32_t *index, int32_t count, LweSample *const *result);
+int tfhe_hip_import_samples_seeded_device(const TFheGateBootstrappingParameterSet *params, const void *device_compressed_words,
+                                          int32_t record_count, const int32_t *index, int32_t count, LweSample *result);
+/* test entries.  tfhe_hip_kernel_lwe_expand: the expand kernel alone, into scratch rows in place of pool slots;
+ * out_words[count][n + 1], arguments as for the import; counts its launches.  tfhe_hip_test_expand_slots: the scratch rows of
+ * the last such launch (of a call of several chunks, its last) as the kernel stored them, [rows][slot stride] with the
+ * padding behind word n.  Returns the word count (0 before the first launch; out may be NULL to ask for it), copies only if
+ * it fits `capacity`; -1 on error.  Mirrors tfhe_hip_test_extract_rows. */
+int tfhe_hip_kernel_lwe_expand(const TFheGateBootstrappingParameterSet *params, const Torus32 *compressed_words, int32_t record_count,
+                               const int32_t *index, int32_t count, Torus32 *out_words);
+int64_t tfhe_hip_test_expand_slots(Torus32 *out, int64_t capacity);
 
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through

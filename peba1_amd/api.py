@@ -914,6 +914,112 @@ def kernel_ring_extract(key, words, index=None, count=None):
     return u
 
 
+def _lwe_record(words):
+    """a record as int32 [10 + record_count] and its record_count"""
+    w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+    if w.size < 11:
+        raise ValueError("a seed-compressed LWE record is ten seed words and at least one body")
+    return w, w.size - 10
+
+
+def _encrypt_compressed(plain, fixture, key, values, seed, mask_seed):
+    ms, ns = _compressed_fixture(seed, mask_seed)
+    v = np.ascontiguousarray(values, dtype=np.int32).reshape(-1)
+    out = np.zeros(10 + len(v), dtype=np.int32)
+    rc = (plain(key.ptr, _i32p(v), len(v), _i32p(out)) if ms is None
+          else fixture(key.ptr, _i32p(v), len(v), _i32p(out), ms.ctypes.data_as(_l.U32P), ns))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def encrypt_bits_compressed(bits, key, seed=None, mask_seed=None):
+    """len(bits) fresh bootsSymEncrypt samples as ONE seed-compressed record of 10 + len(bits) words: a fresh mask seed, then
+    one body per bit (tfhe_hip_sym_encrypt_bits_compressed; host only).  The reproducible form (tests) takes seed (the
+    noise) and mask_seed (ten words).  lwe_expand gives the plain samples, import_seeded opens the record on the device."""
+    L = _l.load()
+    return _encrypt_compressed(L.tfhe_hip_sym_encrypt_bits_compressed, L.tfhe_hip_sym_encrypt_bits_compressed_seeded, key, bits,
+                               seed, mask_seed)
+
+
+def encrypt_torus_compressed(mu, key, seed=None, mask_seed=None):
+    """The same for any torus messages mu (tfhe_hip_sym_encrypt_torus_compressed)."""
+    L = _l.load()
+    return _encrypt_compressed(L.tfhe_hip_sym_encrypt_torus_compressed, L.tfhe_hip_sym_encrypt_torus_compressed_seeded, key,
+                               [_wrap32(x) for x in np.asarray(mu).reshape(-1)], seed, mask_seed)
+
+
+def lwe_expand(words, n, index=None, count=None):
+    """Samples index[j] (None: 0 .. count - 1, by default the whole record) of a seed-compressed record as plain words
+    (tfhe_hip_lwe_expand_host; host only, no key) -> int32 [count][n + 1], what CiphertextArray.set_words takes."""
+    w, rc_ = _lwe_record(words)
+    idx, cnt = _unpack_index(index, rc_ if index is None and count is None else count)
+    out = np.zeros((cnt, n + 1), dtype=np.int32)
+    if _l.load().tfhe_hip_lwe_expand_host(_i32p(w), int(n), rc_, _i32p(idx) if idx is not None else None, cnt, _i32p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def import_seeded(words, params, result, index=None, count=None, first=0):
+    """Opens a seed-compressed LWE record on the device (tfhe_hip_import_samples_seeded): result[first + j] becomes sample
+    index[j] of the record (None: 0 .. count - 1, by default the whole record), its mask regenerated on the card inside its
+    slot.  result: a CiphertextArray, or a list of LweSample pointers (CiphertextArray.at) for the scattered form.  The
+    result words are those of set_words(lwe_expand(words, n, index)).  Recorded operations stay recorded."""
+    w, rc_ = _lwe_record(words)
+    idx, cnt = _unpack_index(index, rc_ if index is None and count is None else count)
+    ip = _i32p(idx) if idx is not None else None
+    L = _l.load()
+    if isinstance(result, CiphertextArray):
+        rc = L.tfhe_hip_import_samples_seeded(params.ptr, _i32p(w), rc_, ip, cnt, result.at(first))
+    else:
+        if len(result) - first < cnt:
+            raise ValueError("fewer result samples than indices")
+        ptrs = (_l.LS * max(len(result) - first, 1))(*result[first:])
+        rc = L.tfhe_hip_import_samples_seeded_scattered(params.ptr, _i32p(w), rc_, ip, cnt, ptrs)
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def import_seeded_device(device_ptr, record_count, params, result, index=None, count=None, first=0):
+    """The same from device memory at `device_ptr` (10 + record_count int32 words), stream-ordered on tfhe_hip_stream():
+    the call returns with the work enqueued; keep the memory until the stream has passed."""
+    idx, cnt = _unpack_index(index, int(record_count) if index is None and count is None else count)
+    rc = _l.load().tfhe_hip_import_samples_seeded_device(params.ptr, C.c_void_p(int(device_ptr)), int(record_count),
+                                                         _i32p(idx) if idx is not None else None, cnt, result.at(first))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def seeded_lwe_stats():
+    """seeded_imported_samples, seeded_import_launches"""
+    s = _l.SeededLweStats()
+    _l.load().tfhe_hip_get_seeded_lwe_stats(C.byref(s))
+    return {f: getattr(s, f) for f in _l.SEEDED_LWE_STATS_FIELDS}
+
+
+def kernel_lwe_expand(params, words, index=None, count=None):
+    """The expand kernel's rows alone (tfhe_hip_kernel_lwe_expand), written into scratch rows: int32 [count][n + 1]."""
+    w, rc_ = _lwe_record(words)
+    idx, cnt = _unpack_index(index, rc_ if index is None and count is None else count)
+    out = np.zeros((cnt, params.n + 1), dtype=np.int32)
+    rc = _l.load().tfhe_hip_kernel_lwe_expand(params.ptr, _i32p(w), rc_, _i32p(idx) if idx is not None else None, cnt, _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def expand_slots(stride):
+    """the scratch rows of the last kernel_lwe_expand launch as the kernel stored them, padding included: int32 [rows][stride]"""
+    L = _l.load()
+    words = L.tfhe_hip_test_expand_slots(None, 0)
+    out = np.zeros(max(words, 0), dtype=np.int32)
+    if words < 0 or (words and L.tfhe_hip_test_expand_slots(_i32p(out), words) != words):
+        raise RuntimeError(last_error())
+    return out.reshape(-1, stride)
+
+
 LINEAR_MAX_IN = 16
 
 

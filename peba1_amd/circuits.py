@@ -101,6 +101,26 @@ class EncryptedVector:
                                                       count=nslots * bitsize)
         return self
 
+    @classmethod
+    def from_seeded_lwe(cls, params, words, nslots, bitsize):
+        """The server side of seeded_lwe_encrypt_vector: the nslots arrays of `bitsize` samples of a template that arrived
+        as ONE seed-compressed LWE record of 10 + nslots * bitsize words, through a single scattered seeded import
+        (api.import_seeded).  Bit j of slot s is sample s * bitsize + j.  Needs no key: the samples are fresh encryptions."""
+        if np.asarray(words).size != 10 + nslots * bitsize:
+            raise ValueError("a record of %d samples has %d words" % (nslots * bitsize, 10 + nslots * bitsize))
+        self = cls.__new__(cls)
+        self.slots = [api.CiphertextArray(params, bitsize) for _ in range(nslots)]
+        api.import_seeded(words, params, [a.at(j) for a in self.slots for j in range(bitsize)])
+        return self
+
+
+def seeded_lwe_encrypt_vector(values, bitsize, key, seed=None, mask_seed=None):
+    """The client side of EncryptedVector.from_seeded_lwe: len(values) features of `bitsize` bits as ONE seed-compressed
+    record of fresh LWE samples under the secret keyset `key` -- bit j of value s is sample s * bitsize + j (4,136 bytes for
+    128 x 8 bits, where the samples of an EncryptedVector are 2.5 MB at P128)."""
+    bits = [(int(v) >> j) & 1 for v in values for j in range(bitsize)]
+    return api.encrypt_bits_compressed(bits, key, seed=seed, mask_seed=mask_seed)
+
 
 def ring_encrypt_vector(values, bitsize, key, seed=None, compressed=False, mask_seed=None):
     """The client side of EncryptedVector.from_ring: len(values) features of `bitsize` bits as ONE ring sample under the

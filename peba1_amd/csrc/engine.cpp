@@ -1382,4 +1382,61 @@ size_t Engine::read_extract_rows(Torus32 *out, size_t capacity) {
     return words;
 }
 
+// ---- seed-compressed LWE sample arrays (expand.hpp, expand.hip) ------------------------------
+void Engine::run_lwe_expand(int n, int stride, const Torus32 *record, bool record_on_device, const int32_t *index, int count,
+                            SlotPool *pool, const int32_t *slots, Torus32 *rows_out, bool wait) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const int widest = std::min(count, LWE_EXPAND_CHUNK);
+    // the seed in front of the gathered bodies, padded so that they start on a 16-byte boundary
+    constexpr size_t HEAD = (LWE_SEED_WORDS + 3) & ~(size_t)3;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    int32_t *drecord = record_on_device ? nullptr : scratch_as<int32_t>(S_LWE_RECORD, HEAD + (size_t)count);
+    int32_t *dindex = scratch_as<int32_t>(S_LWE_INDEX, (size_t)count);
+    int32_t *dslots = slots ? scratch_as<int32_t>(S_LWE_SLOTS, (size_t)count) : nullptr;
+    int32_t *drows = slots ? pool->data() : scratch_as<int32_t>(S_LWE_ROWS, (size_t)widest * stride);
+    h2d_staged(dindex, index, (size_t)count, "upload expand index");
+    if (slots) h2d_staged(dslots, slots, (size_t)count, "upload slot list");
+    if (!record_on_device) {
+        std::vector<int32_t> up(HEAD + (size_t)count, 0);
+        std::copy(record, record + LWE_SEED_WORDS, up.begin());
+        for (int j = 0; j < count; ++j) up[HEAD + (size_t)j] = record[LWE_SEED_WORDS + (size_t)index[j]];
+        h2d_staged(drecord, up.data(), up.size(), "upload seed and bodies");
+    }
+    const int32_t *seed = record_on_device ? record : drecord;
+    std::vector<int32_t> rows(rows_out ? (size_t)widest * stride : 0);
+    for (int done = 0; done < count; done += LWE_EXPAND_CHUNK) {
+        const int cnt = std::min(LWE_EXPAND_CHUNK, count - done);
+        LweExpandArgs a{};
+        a.n = n; a.count = cnt; a.stride = stride; a.gathered = record_on_device ? 0 : 1;
+        a.seed = reinterpret_cast<const uint32_t *>(seed);
+        a.body = record_on_device ? record + LWE_SEED_WORDS : drecord + HEAD + done;
+        a.index = dindex + done;
+        a.slots = slots ? dslots + done : nullptr;
+        a.rows = drows;
+        if (!launch_lwe_expand(stream_, a)) api_fail("seeded import: arguments outside what the expand kernel was built for");
+        hip_check(hipGetLastError(), "lwe expand launch");
+        ++seeded_lwe_stats.seeded_import_launches;
+        if (rows_out) {
+            last_expand_words_ = (size_t)cnt * stride;
+            d2h(rows.data(), drows, (size_t)cnt * stride, "download expanded rows");
+            sync_stream("lwe expand");
+            unpad_rows(rows_out + (size_t)done * (n + 1), rows.data(), (size_t)cnt, (size_t)n + 1, (size_t)stride);
+        }
+    }
+    if (rows_out) return;
+    seeded_lwe_stats.seeded_imported_samples += (uint64_t)count;
+    finish(wait, "seeded import");
+}
+
+size_t Engine::read_expand_slots(Torus32 *out, size_t capacity) {
+    ENGINE_DEVICE_SCOPE();
+    const size_t words = last_expand_words_;
+    if (!out || capacity < words || !words) return words;
+    wait_flight();
+    d2h(out, scratch_as<int32_t>(S_LWE_ROWS, words), words, "download expand slots");      // (sized by that launch: no growth)
+    sync_stream("expand slots");
+    return words;
+}
+
 }  // namespace tfhe_hip

@@ -212,6 +212,20 @@ public:
     // word count, copies only if it fits `capacity`
     size_t read_extract_rows(Torus32 *out, size_t capacity);
 
+    // Seed-compressed LWE sample arrays (expand.hpp LweExpandArgs): row j becomes sample index[j] of the record whose
+    // LWE_SEED_WORDS + record_count words lie at `record` (host, or device memory the caller keeps until the stream has
+    // passed), in chunks of at most LWE_EXPAND_CHUNK, written by lwe_expand_kernel alone.  From a host record the seed, the
+    // bodies the index names and the lists go up through the pinned staging area: count words, not count (n + 1).
+    // The slot form (rows_out null): row j goes straight into pool slot slots[j]; wait = false returns with the work
+    // enqueued on the engine's stream.  The raw test form (pool null, rows_out [count][n + 1]): into scratch rows, read back.
+    // The caller has checked every index.  Every buffer is sized before anything is enqueued: an ApiError (device memory
+    // exhausted) leaves nothing written.
+    void run_lwe_expand(int n, int stride, const Torus32 *record, bool record_on_device, const int32_t *index, int count,
+                        SlotPool *pool, const int32_t *slots, Torus32 *rows_out, bool wait);
+    // test path: the scratch rows of the last raw expand launch, [rows][stride] as the kernel stored them -- returns the
+    // word count, copies only if it fits `capacity`
+    size_t read_expand_slots(Torus32 *out, size_t capacity);
+
     TfheHipStats stats{};
     TfheHipExpandStats expand_stats{};  // the device expansions of seed-compressed cloud keys (tfhe_hip_get_expand_stats)
     TfheHipSeededStats seeded_stats{};  // device-expanded packing keys and seeded unpacks (tfhe_hip_get_seeded_stats)
@@ -281,6 +295,10 @@ private:
         S_UNPACK_KS,      // run_unpack: the key-switch descriptors (row j -> slot j)
         S_UNPACK_EXTRACT, // run_unpack: the extracted samples of one chunk
         S_EXPAND_WORDS,   // raw, run_expand_masks: the stream words
+        S_LWE_RECORD,     // run_lwe_expand: the seed and the gathered bodies of a host record
+        S_LWE_INDEX,      // run_lwe_expand: the index list
+        S_LWE_SLOTS,      // run_lwe_expand: the slot list
+        S_LWE_ROWS,       // raw, run_lwe_expand: the rows of one chunk in place of pool slots
     };
     void *scratch(Scratch idx, size_t bytes);
     // the same by element count (and `margin` bytes), and `count` elements between host and device on the engine's stream
@@ -334,6 +352,10 @@ private:
     std::vector<SlotPool *> pools_;
     std::vector<void *> scratch_ptr_;
     std::vector<size_t> scratch_size_;
+    // behind everything else, so that the members the flush path reads keep their places
+    size_t last_expand_words_ = 0;                      // rows * stride of the last raw LWE expand launch (read_expand_slots)
+public:
+    TfheHipSeededLweStats seeded_lwe_stats{};           // seeded imports and their expand launches (tfhe_hip_get_seeded_lwe_stats)
 };
 
 }  // namespace tfhe_hip

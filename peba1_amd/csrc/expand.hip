@@ -13,6 +13,25 @@
 // Compute-bound on integer VALU (about 350 add / xor / rotate triples a block) with 32 bytes out per lane.  Every word of both
 // images is written here exactly once, with plain vector stores; the KSK's zero row is cleared by the caller.
 //
+//   lwe_expand_kernel   seed-compressed LWE sample arrays (expand.hpp LweExpandArgs): one workgroup of four wave64 per result
+//                       row, which is sample s = index[j] of the record.  The row's stream words [s n, s n + n) lie in blocks
+//                       floor(s n / 8) .. floor((s n + n - 1) / 8): at most ceil(n / 8) + 1 = 129 of them at n = 1,024.  Lane b
+//                       below that count computes block b and puts the words that fall inside the row into LDS; lanes 192 ..
+//                       195 put the body at word n and the zeros up to the slot stride behind it.  After ONE barrier the row
+//                       -- stride words, 4,112 bytes at most -- leaves LDS for its pool slot in 16-byte groups, one store a
+//                       lane (two for lane 0 when stride / 4 = 257).  The staging is what the layout asks for: s n mod 8 is
+//                       arbitrary (630 mod 8 = 6), so a block's eight words never line up with the slot's 16-byte groups,
+//                       and a lane that stored its own words would store single words at odd offsets.  No expanded array
+//                       exists in global memory: the slot is the only destination.
+//                       Counted per row at n = 630: 79 or 80 blocks of about 1,050 VALU operations = 8.4e4 lane-operations
+//                       in two of the four waves, against 2,528 bytes stored (158 16-byte groups); 1,024 rows are 8.6e7
+//                       lane-operations and 2.6 MB of stores.  A sample named twice is computed twice: finding repeats
+//                       costs more than the blocks they would save.
+//                       Bounds: s < 2^20 and n <= 1,024, so s n + n <= 2^30 and 32-bit index arithmetic is exact (the
+//                       launcher refuses other n; the caller has checked every index and slot); LDS words touched are
+//                       i < n by the test in front of each write, and n .. stride - 1 <= n + 3 by lanes 192 .. 195; the
+//                       global stores cover words 0 .. stride - 1 of the row's own slot and nothing else.
+//
 // kernels.hip is not touched by this file.
 #include "chacha_device.hpp"
 #include "expand.hpp"
@@ -69,6 +88,35 @@ __global__ __launch_bounds__(256) void expand_ksk_kernel(ExpandKskArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void lwe_expand_kernel(LweExpandArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lwe_row[];   // the row as its slot will hold it: stride words
+    const uint32_t n = (uint32_t)a.n, stride = (uint32_t)a.stride, j = blockIdx.x;     // the grid is `count` workgroups
+    const uint32_t s = (uint32_t)a.index[j];
+    const uint32_t first = s * n;                                        // the row's first stream word, below 2^30
+    const uint32_t b0 = first / 8, nblocks = (first + n - 1) / 8 - b0 + 1;             // at most ceil(n / 8) + 1 <= 129
+    if (threadIdx.x < nblocks) {
+        ExpandSeed seed;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) seed.key[i] = a.seed[i];
+        seed.nonce[0] = a.seed[8];
+        seed.nonce[1] = a.seed[9];
+        uint32_t w[8];
+        chacha_mask_words(seed, (uint64_t)(b0 + threadIdx.x), w);
+        const uint32_t i0 = (b0 + threadIdx.x) * 8 - first;              // wraps below zero in front of the row: fails i < n
+#pragma unroll
+        for (uint32_t c = 0; c < 8; ++c)
+            if (i0 + c < n) lwe_row[i0 + c] = w[c];
+    } else if (threadIdx.x >= 192) {
+        const uint32_t q = n + (threadIdx.x - 192);                      // the body, then the padding an import leaves zero
+        if (q < stride) lwe_row[q] = q == n ? (uint32_t)a.body[a.gathered ? j : s] : 0u;
+    }
+    __syncthreads();
+    const size_t at = a.slots ? (size_t)a.slots[j] : (size_t)j;
+    uint4 *dst = reinterpret_cast<uint4 *>(a.rows + at * stride);
+    const uint4 *src = reinterpret_cast<const uint4 *>(lwe_row);
+    for (uint32_t g = threadIdx.x; g < stride / 4; g += 256) dst[g] = src[g];
+}
+
 __global__ __launch_bounds__(256) void expand_masks_kernel(ExpandSeed seed, uint64_t first_word, uint32_t count, uint32_t *out) {
     const uint64_t counter = first_word / 8 + ((uint64_t)blockIdx.x * 256 + threadIdx.x);     // base + block index, 64-bit
     if (counter > (first_word + count - 1) / 8) return;
@@ -84,6 +132,15 @@ __global__ __launch_bounds__(256) void expand_masks_kernel(ExpandSeed seed, uint
 bool aligned16(const void *p) { return p && !(reinterpret_cast<uintptr_t>(p) & 15u); }
 
 }  // namespace
+
+bool launch_lwe_expand(hipStream_t s, const LweExpandArgs &a) {
+    // a row is n mask words, the body and the padding up to the slot stride; ceil(n / 8) + 1 blocks stay below lane 192
+    if (a.n < 1 || a.n > LWE_EXPAND_MAX_N || a.stride != ((a.n + 4) & ~3) || a.count < 1 || a.count > LWE_EXPAND_CHUNK || !a.seed ||
+        !a.body || !a.index || !aligned16(a.rows))
+        return false;
+    hipLaunchKernelGGL(lwe_expand_kernel, dim3(a.count), dim3(256), (size_t)a.stride * 4, s, a);
+    return true;
+}
 
 bool launch_expand_bk(hipStream_t s, const ExpandBkArgs &a) {
     if (a.rows < 1 || a.k < 1 || a.N < 8 || (a.N & 7) || !aligned16(a.body) || !aligned16(a.raw)) return false;

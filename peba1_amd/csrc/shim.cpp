@@ -1008,6 +1008,7 @@ void tfhe_hip_reset_stats(void) {
     Engine::get().stats = TfheHipStats{};
     Engine::get().expand_stats = TfheHipExpandStats{};
     Engine::get().seeded_stats = TfheHipSeededStats{};
+    Engine::get().seeded_lwe_stats = TfheHipSeededLweStats{};
 }
 void tfhe_hip_get_seeded_stats(TfheHipSeededStats *out) {
     auto g = recorder_lock();
@@ -1397,6 +1398,8 @@ int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const 
 #include "compressed_host.cpp"
 // and that of the seed-compressed packing keys and ring samples (it uses the packing key and the unpack defined above)
 #include "seeded_host.cpp"
+// and that of the seed-compressed LWE sample arrays
+#include "seeded_lwe_host.cpp"
 
 // The recorder is compiled as part of this object.  build.sh is one of the files kernels_sha16 hashes (kernel_id.py): a new
 // host source named there would mark every committed counter summary stale although no kernel changed.

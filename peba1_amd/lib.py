@@ -90,10 +90,16 @@ class SeededStats(C.Structure):
                 ("seeded_unpacked_samples", C.c_uint64), ("seeded_unpack_launches", C.c_uint64)]
 
 
+class SeededLweStats(C.Structure):
+    """TfheHipSeededLweStats: seeded imports of LWE sample arrays (tfhe_hip_get_seeded_lwe_stats)."""
+    _fields_ = [("seeded_imported_samples", C.c_uint64), ("seeded_import_launches", C.c_uint64)]
+
+
 STATS_FIELDS = [f for f, _ in Stats._fields_] + [f for f, _ in StatsAll._fields_]
 UNPACK_STATS_FIELDS = [f for f, _ in StatsWhole._fields_]
 EXPAND_STATS_FIELDS = [f for f, _ in ExpandStats._fields_]
 SEEDED_STATS_FIELDS = [f for f, _ in SeededStats._fields_]
+SEEDED_LWE_STATS_FIELDS = [f for f, _ in SeededLweStats._fields_]
 
 
 PS = C.POINTER(ParameterSet)
@@ -277,6 +283,17 @@ SIGNATURES = {
     "tfhe_hip_kernel_ring_extract_seeded": (C.c_int, [CK, I32P, C.c_int32, I32P, C.c_int32, I32P]),
     "tfhe_hip_test_pack_image": (C.c_int64, [C.c_void_p, CK, I32P, C.c_int64]),
     "tfhe_hip_test_extract_rows": (C.c_int64, [I32P, C.c_int64]),
+    "tfhe_hip_sym_encrypt_bits_compressed": (C.c_int, [SK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_sym_encrypt_bits_compressed_seeded": (C.c_int, [SK, I32P, C.c_int32, I32P, U32P, C.c_uint64]),
+    "tfhe_hip_sym_encrypt_torus_compressed": (C.c_int, [SK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_sym_encrypt_torus_compressed_seeded": (C.c_int, [SK, I32P, C.c_int32, I32P, U32P, C.c_uint64]),
+    "tfhe_hip_lwe_expand_host": (C.c_int, [I32P, C.c_int32, C.c_int32, I32P, C.c_int32, I32P]),
+    "tfhe_hip_import_samples_seeded": (C.c_int, [PS, I32P, C.c_int32, I32P, C.c_int32, LS]),
+    "tfhe_hip_import_samples_seeded_scattered": (C.c_int, [PS, I32P, C.c_int32, I32P, C.c_int32, C.POINTER(LS)]),
+    "tfhe_hip_import_samples_seeded_device": (C.c_int, [PS, C.c_void_p, C.c_int32, I32P, C.c_int32, LS]),
+    "tfhe_hip_kernel_lwe_expand": (C.c_int, [PS, I32P, C.c_int32, I32P, C.c_int32, I32P]),
+    "tfhe_hip_test_expand_slots": (C.c_int64, [I32P, C.c_int64]),
+    "tfhe_hip_get_seeded_lwe_stats": (None, [C.POINTER(SeededLweStats)]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])

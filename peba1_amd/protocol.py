@@ -17,6 +17,7 @@ that follows it.
     python -m peba1_amd.protocol --clients 4             # four clients, each with a key pair of its own, batched
     python -m peba1_amd.protocol --compressed-keys       # the cloud key travels as a seed and the bodies (10x fewer bytes)
     python -m peba1_amd.protocol --seeded-inputs         # template and sample travel as seed-compressed ring samples
+    python -m peba1_amd.protocol --seeded-lwe            # template and sample travel as seed-compressed LWE sample arrays
 
 With --clients K the server side runs as a multi-user server does: Function_f of all K clients in ONE flush and
 Function_g of all K in a second one (multi-key flushes, tuning "batch_keys"), one JSON line per client.
@@ -37,14 +38,27 @@ def shipped_vector(params, values, bitsize, key, ev):
     return circuits.EncryptedVector.from_ring(params, words, len(values), bitsize, ev)
 
 
-def run_p1(params, key, sample, template, bound_match, r0, r1, bitsize=8, cloud=None, function_f=None, seeded_inputs=False):
+def shipped_lwe_vector(params, values, bitsize, key):
+    """What --seeded-lwe puts between client and server: the client encrypts the features as ONE seed-compressed record of
+    fresh LWE samples (10 + nslots * bitsize words: a fresh mask seed and one body per bit), the server opens it on the
+    device -- no cloud key is involved and no key switch is paid."""
+    words = circuits.seeded_lwe_encrypt_vector(values, bitsize, key)
+    return circuits.EncryptedVector.from_seeded_lwe(params, words, len(values), bitsize)
+
+
+def run_p1(params, key, sample, template, bound_match, r0, r1, bitsize=8, cloud=None, function_f=None, seeded_inputs=False,
+           seeded_lwe=False):
     """One protocol run.  `key` is the client's secret keyset (encrypts, decrypts); `cloud`
     (default: its embedded cloud keyset) is all the evaluating side uses.  Returns a dict with
     the decrypted y, whether the client was authenticated (y == r1, main.cpp:578) and timings.
-    seeded_inputs: template and sample travel as seed-compressed ring samples (shipped_vector)."""
+    seeded_inputs: template and sample travel as seed-compressed ring samples (shipped_vector); seeded_lwe: as one
+    seed-compressed LWE record per vector (shipped_lwe_vector)."""
     ev = key if cloud is None else cloud
     t0 = time.perf_counter()
-    if seeded_inputs:
+    if seeded_lwe:
+        enc_template = shipped_lwe_vector(params, template, bitsize, key)
+        enc_sample = shipped_lwe_vector(params, sample, bitsize, key)
+    elif seeded_inputs:
         enc_template = shipped_vector(params, template, bitsize, key, ev)
         enc_sample = shipped_vector(params, sample, bitsize, key, ev)
     else:
@@ -133,7 +147,11 @@ def parse_args(argv=None):
                     help="each client ships a seed-compressed cloud key; the server expands it on the device at first use")
     ap.add_argument("--seeded-inputs", action="store_true",
                     help="template and sample travel as seed-compressed ring samples and are opened on the device")
+    ap.add_argument("--seeded-lwe", action="store_true",
+                    help="template and sample travel as one seed-compressed LWE record each and are opened on the device")
     a = ap.parse_args(argv)
+    if a.seeded_lwe and (a.clients or a.seeded_inputs):
+        ap.error("--seeded-lwe runs the single-client form, without --seeded-inputs")
     if a.clients < 0:
         ap.error("--clients must be >= 0")
     if a.seeded_inputs and a.clients:
@@ -181,7 +199,8 @@ def main():
     runs = {"genuine": [t + 1 for t in template], "impostor": [(91 * i + 5) % 256 for i in range(a.nslots)]}
     for name, sample in runs.items():
         out = run_p1(params, key, sample, template, a.bound, r0=17, r1=99, cloud=cloud,
-                     function_f=circuits.function_f_fast if a.fast else None, seeded_inputs=a.seeded_inputs)
+                     function_f=circuits.function_f_fast if a.fast else None, seeded_inputs=a.seeded_inputs,
+                     seeded_lwe=a.seeded_lwe)
         out["distance"] = sum((x - y) ** 2 for x, y in zip(sample, template))
         print(json.dumps({"run": name, **out}))
     if cloud is not None:
