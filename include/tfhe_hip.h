@@ -80,7 +80,14 @@ const Torus32 *tfhe_hip_key_ksk(const TFheGateBootstrappingCloudKeySet *cloud, i
 int32_t tfhe_hip_sample_words(const TFheGateBootstrappingParameterSet *params);
 /* samples[0..count) are consecutive elements of one array; words are packed
  * [count][n+1].  One call moves at most 65,536 samples through the device: more are refused ("too many samples in one
- * packed transfer") with nothing changed. */
+ * packed transfer") with nothing changed.
+ * An import beside a recording: every imported sample is renamed into a fresh slot, so recorded operations that have not
+ * run stay recorded and keep the samples they named -- one that reads the handle still reads the sample it held when the
+ * operation was recorded, and one whose result the handle held still runs (unless "eliminate_dead" finds its result
+ * unread) and writes the slot it was given, never the imported one.  A flush in flight is not waited for: the import is
+ * enqueued behind it on tfhe_hip_stream().  An export is an observation point: the recorded operations run first.
+ * Host mirrors: the host-form import sets sample->a / sample->b to the imported words in either mode; the device forms
+ * leave them stale, in immediate mode too, until the sample is passed to tfhe_hip_sync_samples(). */
 int tfhe_hip_export_samples(const LweSample *samples, int32_t count,
                             const TFheGateBootstrappingParameterSet *params, Torus32 *out_words);
 int tfhe_hip_import_samples(LweSample *samples, int32_t count,
