@@ -906,6 +906,76 @@ int tfhe_hip_kernel_lwe_expand(const TFheGateBootstrappingParameterSet *params, 
                                const int32_t *index, int32_t count, Torus32 *out_words);
 int64_t tfhe_hip_test_expand_slots(Torus32 *out, int64_t capacity);
 
+/* ---- private selection: a CMUX tree under TGSW-encrypted index bits picks ONE of M resident ring samples ----
+ * The leveled half of TFHE (upstream: tGswExternProduct, CMUX) outside a blind rotation.  A client sends d encrypted index
+ * bits; the server selects one of up to 2^d ring samples it holds (a gallery of templates, one ring sample each) without
+ * learning which, with M - 1 external products.  tfhe_hip_unpack_samples_device then opens the selected sample.  k = 1.
+ *
+ * TGSW sample of a bit: (k+1) l rows, each a TLWE sample of (k+1) N words under the ring key -- uniform masks, noise of the
+ * set's bk_stdev.  Row (u, p), u <= k, p < l, encrypts zero, and bit << (32 - (p+1) Bgbit) is added to coefficient 0 of its
+ * polynomial u.  Word order [u l + p][polynomial][N]: exactly one entry i of tfhe_hip_key_bk.  A selector of d bits has the
+ * words of a bootstrapping key with n = d, bit 0 first; its device image is the bootstrapping-key image with n = d.
+ * External product G (.) c of a TGSW sample G with a ring sample c, Bg = 2^Bgbit, offset = sum_{p < l} (Bg/2) << (32 - (p+1) Bgbit):
+ *     dig[u][p][j] = (((c[u][j] + offset) >> (32 - (p+1) Bgbit)) & (Bg - 1)) - Bg/2        signed digits in [-Bg/2, Bg/2)
+ *     (G (.) c)[w] = sum_{u, p} dig[u][p](X) * G.row(u, p)[w](X)        in Z[X]/(X^N + 1), wrapping mod 2^32, exact
+ * -- the offset decomposition of the blind rotation.  CMUX(G, d1, d0) = d0 + G (.) (d1 - d0), the word-wise wrapping
+ * difference taken first: it encrypts the phase of d1 where G encrypts 1 and that of d0 where it encrypts 0.
+ * Tree over entries e[0 .. M), 1 <= M <= 2^d, an entry at or past M being the all-zero ring sample: level j = 0 .. d - 1
+ * replaces the entries (2i, 2i+1) by CMUX(G_j, e[2i+1], e[2i]).  Bit 0 is the least significant index bit; after d
+ * levels the one entry left encrypts the phase polynomial of entry index = sum_j bit_j 2^j, and noise only for an index at or
+ * past M.  M = 1 with d = 0 is a copy.
+ * Variance added per CMUX to every coefficient, to first order -- COMPUTED from the definition, not measured (torus units):
+ *     key term       (k+1) l N E[dig^2] bk_stdev^2 <= (k+1) l N (Bg/2)^2 bk_stdev^2
+ *     rounding term  at most (1 + k N) eps^2 / 3,   eps = 2^-(l Bgbit + 1) the precision of the decomposition
+ * P128 (l = 3, Bgbit = 7, bk_stdev = 2^-25): 2.2e-8 + 1.9e-11, sigma <= 1.5e-4 per level, 4.7e-4 after ten levels -- beside
+ * the 2.8e-3 the unpack's key switch adds and an operand margin of 1/16.  The l = 2, Bgbit = 10 set (bk_stdev = 7.18e-9):
+ * 5.5e-8 + 7.8e-11, sigma <= 2.4e-4.  P2048 (l = 3, Bgbit = 6): 1.1e-8 + 2.5e-9, sigma <= 1.2e-4.
+ *
+ * Client side (host only, no GPU is needed).  tfhe_hip_tgsw_words: (k+1) l (k+1) N, the words of one bit (-1: null set).
+ * tfhe_hip_tgsw_encrypt_bits writes count TGSW samples, 1 <= count <= 20, bits[b] != 0 taken as 1, out_words[count][(k+1) l]
+ * [k+1][N].  The default form draws from two fresh ChaCha20 streams keyed by the OS, as a ring sample does; the seeded
+ * form from ONE seeded generator (xoshiro256** through splitmix64) started from `seed` for this call alone.  Draw order,
+ * both forms: for every bit, for every row (u, p) in word order: the k N mask words (one `torus` draw each), then the N
+ * noise samples (one `gauss` draw each) -- the order of a bootstrapping key's rows.  0, or -1 with the error set and
+ * out_words untouched.  Compressed selectors (a mask seed and the bodies) are OUT OF SCOPE: a selector travels as its words.
+ *
+ * Server side.  tfhe_hip_new_selector copies nbits TGSW samples (0 <= nbits <= 20; nbits = 0 takes no words) of parameter
+ * set `params`.  Every argument is checked before the device is looked at; NULL with the error set for a null pointer,
+ * nbits out of range, a parameter set a cloud key would be refused for (k != 1, the CRT range, the gadget range of the
+ * blind-rotate forms) or a gadget outside the CMUX kernel's own two bounds (peba1_amd/csrc/cmux.hpp: (k+1) l <= 18 at
+ * N = 1024, <= 16 at N = 2048, and (k+1) l N (Bg/2) 2^31 below the exact range of the two-prime CRT).  The words and their
+ * NTT image reach the device at the first select.
+ * tfhe_hip_ring_select: ring_words holds M ring samples of (k+1) N words, 1 <= M <= 2^nbits; out_ring_words receives the
+ * (k+1) N words of the tree's result.  The device form reads a gallery resident on the card and leaves the result there
+ * (both 16-byte aligned), ready for tfhe_hip_unpack_samples_device.  Both are enqueued on tfhe_hip_stream(): the host form
+ * returns with the words in place, the device form with the work enqueued, like tfhe_hip_unpack_samples_device (the
+ * caller keeps both buffers until the stream has passed).  A select names no ciphertext slot: recorded operations stay
+ * recorded, nothing is flushed, and a flush in flight is not waited for.  One kernel launch per tree level.
+ * Return 0, or -1 with tfhe_hip_last_error() set and the call without effect: a null pointer, a deleted selector, M < 1 or
+ * M > 2^nbits, misaligned device words, device memory exhausted.
+ * tfhe_hip_last_select_ms: the launches of the last select between two stream events (waits for the second); -1 unless
+ * kernel timing (tfhe_hip_set_kernel_timing) was on. */
+typedef struct TfheHipSelector TfheHipSelector;
+int64_t tfhe_hip_tgsw_words(const TFheGateBootstrappingParameterSet *params);
+int tfhe_hip_tgsw_encrypt_bits(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                               Torus32 *out_words);
+int tfhe_hip_tgsw_encrypt_bits_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                                      Torus32 *out_words, uint64_t seed);
+TfheHipSelector *tfhe_hip_new_selector(const TFheGateBootstrappingParameterSet *params, const Torus32 *words, int32_t nbits);
+void tfhe_hip_delete_selector(TfheHipSelector *selector);
+int32_t tfhe_hip_selector_bits(const TfheHipSelector *selector);
+int tfhe_hip_ring_select(const TfheHipSelector *selector, const Torus32 *ring_words, int32_t M, Torus32 *out_ring_words);
+int tfhe_hip_ring_select_device(const TfheHipSelector *selector, const void *device_ring_words, int32_t M, void *device_out);
+double tfhe_hip_last_select_ms(void);
+/* raw test entry: `count` independent CMUXes (1 <= count <= 65,536) under bit bit_index of the selector in ONE launch,
+ * out_words[c] = CMUX(G_bit, d1_words[c], d0_words[c]), (k+1) N host words each */
+int tfhe_hip_kernel_ring_cmux(const TfheHipSelector *selector, int32_t bit_index, const Torus32 *d1_words, const Torus32 *d0_words,
+                              int32_t count, Torus32 *out_words);
+/* host-logic test entry: the two magnitude bounds of the CMUX kernel (peba1_amd/csrc/cmux.hpp) for gadget (l, Bgbit) of ring
+ * size N (1024 or 2048), k = 1: bit 0 set = the MAC bound refuses it, bit 1 set = the CRT bound refuses it; -1 on bad
+ * arguments (Bgbit outside 1..12, l Bgbit > 32). */
+int tfhe_hip_test_select_bounds(int32_t N, int32_t l, int32_t Bgbit);
+
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through
  * the device NTT (two 27-bit primes + CRT); |ip| must be < 2^12 */

@@ -914,6 +914,94 @@ def kernel_ring_extract(key, words, index=None, count=None):
     return u
 
 
+def tgsw_words(params):
+    """The words of one TGSW-encrypted bit: (k+1) l (k+1) N (tfhe_hip_tgsw_words)."""
+    return int(_l.load().tfhe_hip_tgsw_words(params.ptr))
+
+
+def tgsw_encrypt_bits(bits, key, seed=None):
+    """TGSW samples of 1..20 index bits under the ring key of the secret keyset `key` (tfhe_hip_tgsw_encrypt_bits; host
+    only) -> int32 [len(bits)][(k+1) l][k+1][N], the words of a bootstrapping key with n = len(bits).  bits[0] is the least
+    significant index bit.  seed: the reproducible form (tests); None draws from OS-keyed streams."""
+    p = key.params
+    b = np.ascontiguousarray(bits, dtype=np.int32).reshape(-1)
+    out = np.zeros((max(len(b), 1), (p.k + 1) * p.l, p.k + 1, p.N), dtype=np.int32)
+    L = _l.load()
+    rc = (L.tfhe_hip_tgsw_encrypt_bits(key.ptr, _i32p(b), len(b), _i32p(out)) if seed is None
+          else L.tfhe_hip_tgsw_encrypt_bits_seeded(key.ptr, _i32p(b), len(b), _i32p(out), int(seed)))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+class Selector:
+    """The server's copy of d TGSW-encrypted index bits (tfhe_hip_new_selector): `words` is what tgsw_encrypt_bits made,
+    [d][(k+1) l][k+1][N]; d = 0 (no words) selects from a gallery of one.  The integers are in include/tfhe_hip.h."""
+
+    def __init__(self, params, words=None):
+        w = np.zeros(0, dtype=np.int32) if words is None else np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+        per_bit = tgsw_words(params)
+        if per_bit <= 0 or w.size % per_bit:
+            raise ValueError("a selector of this parameter set holds %d words per bit" % per_bit)
+        self.params, self.nbits = params, w.size // per_bit
+        self.ptr = _l.load().tfhe_hip_new_selector(params.ptr, _i32p(w) if w.size else None, self.nbits)
+        if not self.ptr:
+            raise ValueError("selector rejected: " + last_error())
+
+    def close(self):
+        if self.ptr:
+            _l.load().tfhe_hip_delete_selector(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ring_select(selector, gallery, device=False):
+    """The CMUX tree of `selector` over a gallery of M ring samples, 1 <= M <= 2^nbits: the (k+1) N words that encrypt the
+    phase polynomial of entry index = sum_j bit_j 2^j (tfhe_hip_ring_select).  Recorded operations stay recorded.
+    device=False: gallery is [M][(k+1) N] host words and the result a numpy array.  device=True: gallery is an int32 torch
+    tensor resident on the engine's device (written before the call: synchronise torch's stream first) and the result a
+    new tensor there, stream-ordered on tfhe_hip_stream() -- ready for unpack_device; wait (tfhe_hip_stream_sync) before
+    reading it through torch, and keep both tensors until then."""
+    p = selector.params
+    sw = (p.k + 1) * p.N
+    L = _l.load()
+    if device:
+        import torch
+        if gallery.dtype != torch.int32 or not gallery.is_contiguous() or gallery.numel() == 0 or gallery.numel() % sw:
+            raise ValueError("a device gallery is a contiguous int32 tensor of M (k+1) N words")
+        out = torch.empty(sw, dtype=torch.int32, device=gallery.device)
+        rc = L.tfhe_hip_ring_select_device(selector.ptr, C.c_void_p(gallery.data_ptr()), gallery.numel() // sw, C.c_void_p(out.data_ptr()))
+    else:
+        g = _ring_words(gallery, p)
+        out = np.zeros(sw, dtype=np.int32)
+        rc = L.tfhe_hip_ring_select(selector.ptr, _i32p(g), g.shape[0], _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def kernel_ring_cmux(selector, bit, d1, d0):
+    """CMUX(G_bit, d1[c], d0[c]) of caller-supplied ring samples [count][(k+1) N] in one launch (tfhe_hip_kernel_ring_cmux)."""
+    p = selector.params
+    a, b = _ring_words(d1, p), _ring_words(d0, p)
+    if a.shape != b.shape:
+        raise ValueError("d1 and d0 hold the same number of ring samples")
+    out = np.zeros_like(a)
+    if _l.load().tfhe_hip_kernel_ring_cmux(selector.ptr, int(bit), _i32p(a), _i32p(b), a.shape[0], _i32p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def last_select_ms():
+    """The launches of the last ring_select between two stream events, in ms; -1 unless kernel timing was on."""
+    return _l.load().tfhe_hip_last_select_ms()
+
+
 def _lwe_record(words):
     """a record as int32 [10 + record_count] and its record_count"""
     w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)

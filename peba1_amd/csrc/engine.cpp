@@ -1317,6 +1317,115 @@ void Engine::run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int
     finish(wait || !out_on_device || !slots, "pack");
 }
 
+// ---- private selection (cmux.hpp, cmux.hip) --------------------------------------------------
+static CmuxArgs cmux_args(const Engine::SelectorImage *sel, const Params &p) {
+    CmuxArgs a{};
+    a.N = p.N; a.l = p.l; a.Bgbit = p.Bgbit; a.offset = p.decomp_offset();
+    a.img = sel->img; a.tw = sel->tw;
+    return a;
+}
+
+Engine::SelectorImage *Engine::upload_selector(const Params &p, const Torus32 *words, int nbits) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    uint32_t scale[2];
+    const std::vector<uint32_t> tw = make_twiddles(p.N, scale);
+    const size_t raw_words = (size_t)nbits * p.kpl() * (p.k + 1) * p.N;
+    auto *sel = new SelectorImage();
+    int32_t *raw = nullptr;
+    try {
+        sel->tw_bytes = tw.size() * 4;
+        sel->tw = static_cast<uint32_t *>(recoverable_alloc(sel->tw_bytes, "the twiddle tables of a selector"));
+        sel->img_bytes = raw_words * 2 * 4;
+        sel->img = static_cast<uint32_t *>(recoverable_alloc(sel->img_bytes, "the NTT image of a selector"));
+        raw = static_cast<int32_t *>(recoverable_alloc(raw_words * 4, "the staging copy of a selector"));
+    } catch (const ApiError &) {
+        recoverable_free(sel->img, sel->img_bytes);
+        recoverable_free(sel->tw, sel->tw_bytes);
+        delete sel;
+        throw;
+    }
+    hip_check(hipMemcpy(sel->tw, tw.data(), sel->tw_bytes, hipMemcpyHostToDevice), "upload twiddles");
+    hip_check(hipMemcpy(raw, words, raw_words * 4, hipMemcpyHostToDevice), "upload selector");
+    DevParams dp{};
+    dp.N = p.N;
+    launch_bk_transform(stream_, dp, raw, sel->img, sel->tw, nbits * p.kpl(), p.k + 1, scale);
+    hip_check(hipGetLastError(), "selector transform launch");
+    sync_stream("selector transform");
+    recoverable_free(raw, raw_words * 4);
+    return sel;
+}
+
+void Engine::free_selector(SelectorImage *sel) {
+    ENGINE_DEVICE_SCOPE();
+    if (!sel) return;
+    if (inited_) sync_stream("sync before selector free");
+    recoverable_free(sel->img, sel->img_bytes);
+    recoverable_free(sel->tw, sel->tw_bytes);
+    delete sel;
+}
+
+void Engine::run_select(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, bool ring_on_device,
+                        Torus32 *out, bool out_on_device) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t sw = (size_t)(p.k + 1) * p.N;
+    // every buffer first (scratch() may throw: nothing has been enqueued then).  Level j holds ceil(M / 2^(j+1)) entries:
+    // the ping buffer is sized for level 0, the pong buffer for level 1
+    int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_SELECT_RING, (size_t)M * sw);
+    int32_t *lvl[2] = {nbits > 0 ? scratch_as<int32_t>(S_SELECT_A, (size_t)((M + 1) / 2) * sw) : nullptr,
+                       nbits > 1 ? scratch_as<int32_t>(S_SELECT_B, (size_t)((M + 3) / 4) * sw) : nullptr};
+    if (kernel_timing && !select_e0_) {
+        hip_check(hipEventCreate(&select_e0_), "select event");
+        hip_check(hipEventCreate(&select_e1_), "select event");
+    }
+    if (!ring_on_device) h2d_staged(dring, ring, (size_t)M * sw, "upload ring words");
+    const int32_t *src = ring_on_device ? ring : dring;
+    if (kernel_timing) hip_check(hipEventRecord(select_e0_, stream_), "select event");
+    int cnt = M;
+    for (int j = 0; j < nbits; ++j) {
+        CmuxArgs a = cmux_args(sel, p);
+        a.bit = j; a.count = (cnt + 1) / 2; a.n_d1 = cnt / 2;
+        a.stride = (int64_t)2 * sw; a.d0 = src; a.d1 = src + sw;
+        a.out = j == nbits - 1 && out_on_device ? out : lvl[j & 1];
+        if (!launch_cmux(stream_, a)) api_fail("select: arguments outside what the CMUX kernel was built for");
+        hip_check(hipGetLastError(), "cmux launch");
+        src = a.out;
+        cnt = a.count;
+    }
+    if (kernel_timing) hip_check(hipEventRecord(select_e1_, stream_), "select event");
+    select_timed_ = kernel_timing;
+    if (!out_on_device) d2h(out, src, sw, "download selected words");
+    else if (nbits == 0) hip_check(hipMemcpyAsync(out, src, sw * 4, hipMemcpyDeviceToDevice, stream_), "copy selected words");
+    finish(!ring_on_device || !out_on_device, "select");
+}
+
+void Engine::run_cmux(const SelectorImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t words = (size_t)count * (p.k + 1) * p.N;
+    int32_t *dd0 = scratch_as<int32_t>(S_SELECT_RING, words), *dd1 = scratch_as<int32_t>(S_CMUX_D1, words);
+    int32_t *dout = scratch_as<int32_t>(S_SELECT_A, words);
+    h2d(dd0, d0, words, "upload d0 words");
+    h2d(dd1, d1, words, "upload d1 words");
+    CmuxArgs a = cmux_args(sel, p);
+    a.bit = bit; a.count = count; a.n_d1 = count;
+    a.stride = (int64_t)(p.k + 1) * p.N; a.d0 = dd0; a.d1 = dd1; a.out = dout;
+    if (!launch_cmux(stream_, a)) api_fail("cmux: arguments outside what the kernel was built for");
+    hip_check(hipGetLastError(), "cmux launch");
+    d2h(out, dout, words, "download cmux words");
+    finish(true, "cmux");
+}
+
+double Engine::last_select_ms() {
+    ENGINE_DEVICE_SCOPE();
+    if (!select_timed_) return -1.0;
+    wait_event(select_e1_, "select event", sync_deadline_ms, diag_label);
+    float ms = 0.f;
+    hip_check(hipEventElapsedTime(&ms, select_e0_, select_e1_), "select event");
+    return ms;
+}
+
 // ---- ring-encrypted inputs (unpack.hpp, unpack.hip) -----------------------------------------
 void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, int nring, bool ring_on_device, const int32_t *index,
                         int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait, bool seeded) {

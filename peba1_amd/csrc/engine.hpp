@@ -16,6 +16,7 @@
 #include "kernels.hpp"
 #include "pack.hpp"
 #include "unpack.hpp"
+#include "cmux.hpp"
 #include "expand.hpp"
 #include "../../include/tfhe_hip.h"
 
@@ -299,6 +300,10 @@ private:
         S_LWE_INDEX,      // run_lwe_expand: the index list
         S_LWE_SLOTS,      // run_lwe_expand: the slot list
         S_LWE_ROWS,       // raw, run_lwe_expand: the rows of one chunk in place of pool slots
+        S_SELECT_RING,    // run_select: the ring words on their way from a host source; run_cmux: the d0 operands
+        S_SELECT_A,       // run_select: the tree levels 0, 2, ... (ping); run_cmux: the results
+        S_SELECT_B,       // run_select: the tree levels 1, 3, ... (pong)
+        S_CMUX_D1,        // raw, run_cmux: the d1 operands
     };
     void *scratch(Scratch idx, size_t bytes);
     // the same by element count (and `margin` bytes), and `count` elements between host and device on the engine's stream
@@ -356,6 +361,29 @@ private:
     size_t last_expand_words_ = 0;                      // rows * stride of the last raw LWE expand launch (read_expand_slots)
 public:
     TfheHipSeededLweStats seeded_lwe_stats{};           // seeded imports and their expand launches (tfhe_hip_get_seeded_lwe_stats)
+
+    // Private selection (cmux.hpp).  The device side of a selector: the NTT image of its rows [nbits][(k+1) l][2][N] (the
+    // bootstrapping-key image with n = nbits) and the ring's twiddle tables -- a selector belongs to a parameter set, not
+    // to a cloud key, so it carries its own.  Both buffers are allocated before anything is enqueued: device memory
+    // exhausted = ApiError with nothing held.  free_selector waits for the stream first (a select in flight reads both).
+    struct SelectorImage { uint32_t *img = nullptr, *tw = nullptr; size_t img_bytes = 0, tw_bytes = 0; };
+    SelectorImage *upload_selector(const Params &p, const Torus32 *words, int nbits);
+    void free_selector(SelectorImage *sel);
+    // The CMUX tree over the M ring samples `ring` (host, or device memory the caller keeps until the stream has passed)
+    // under the nbits selector bits of `sel` (null when nbits = 0: a copy), enqueued on the engine's stream behind
+    // whatever is there: one launch per level, level j from entries of level j - 1 in one of two ping-pong buffers into
+    // the other, the last one straight into a device destination.  Names no pool slot and waits for no flight.  Every
+    // buffer is sized before anything is enqueued: an ApiError (device memory exhausted) leaves nothing written.  A host
+    // source or destination makes the call return with the words in place; the device form returns with the work enqueued.
+    void run_select(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, bool ring_on_device,
+                    Torus32 *out, bool out_on_device);
+    // raw test path: `count` independent CMUXes under bit `bit` in ONE launch, host words in and out
+    void run_cmux(const SelectorImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out);
+    // the levels of the last run_select between two stream events (kernel timing on; waits for the second), else -1
+    double last_select_ms();
+private:
+    hipEvent_t select_e0_ = nullptr, select_e1_ = nullptr;
+    bool select_timed_ = false;
 };
 
 }  // namespace tfhe_hip

@@ -1,0 +1,171 @@
+// select_host.cpp -- host side of the private selection: the TGSW encryption of index bits, the selector object and the
+// C ABI of the CMUX tree (include/tfhe_hip.h "private selection").  Compiled as part of shim.cpp's object behind
+// unpack_host.cpp: it uses the guarded entry wrappers defined there and pack_host.cpp's negacyclic product.  No arithmetic
+// of the CMUX itself happens here (cmux.hip); encryption runs on the CPU like that of the ring samples.
+
+// the rows [nbits][(k+1) l][k+1][N] of a selector; the device image is made at the first select (a selector can be built
+// and deleted on a machine without a GPU)
+struct TfheHipSelector {
+    uint32_t magic;
+    Params p;
+    int32_t nbits;
+    std::vector<Torus32> words;
+    Engine::SelectorImage *img;
+};
+
+namespace {
+constexpr uint32_t SELECT_MAGIC = 0x53454C54u;
+// the most CMUXes one raw launch takes (tfhe_hip_kernel_ring_cmux)
+constexpr int32_t CMUX_MAX_COUNT = 1 << 16;
+
+// The draw order (include/tfhe_hip.h): for every bit, for u <= k, for p < l: the kN mask words, then the N noise samples
+// -- the order of the bootstrapping key's rows (host_keys.cpp generate_keys), of which a selector bit is one entry.
+void tgsw_encrypt_into(const TfheHipSecretKey &sk, const int32_t *bits, int32_t count, Rng &secret, Rng &mask, Torus32 *out) {
+    const Params &p = sk.p;
+    const int N = p.N, k = p.k, l = p.l, kpl = p.kpl();
+    for (int32_t b = 0; b < count; ++b)
+        for (int row = 0; row < kpl; ++row) {
+            uint32_t *smp = reinterpret_cast<uint32_t *>(out) + ((size_t)b * kpl + row) * (size_t)(k + 1) * N;
+            uint32_t *body = smp + (size_t)k * N;
+            for (int u = 0; u < k; ++u)
+                for (int j = 0; j < N; ++j) smp[(size_t)u * N + j] = (uint32_t)mask.torus();
+            for (int j = 0; j < N; ++j) body[j] = (uint32_t)dtot32(secret.gauss(p.bk_stdev));
+            for (int u = 0; u < k; ++u) pack_add_mul_by_bits(body, smp + (size_t)u * N, sk.tlwe_key.data() + (size_t)u * N, N, 1u);
+            const int u = row / l, pp = row % l;
+            smp[(size_t)u * N] += (uint32_t)(bits[b] ? 1 : 0) << (32 - (pp + 1) * p.Bgbit);
+        }
+}
+
+int tgsw_encrypt_impl(const char *who, const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                      Torus32 *out, const uint64_t *seed) {
+    if (!secret || !secret->lwe_key || !bits || !out) { set_error(std::string(who) + ": null argument"); return -1; }
+    if (count < 1 || count > SELECT_MAX_BITS) {
+        set_error(std::string(who) + ": count must be in 1.." + std::to_string(SELECT_MAX_BITS));
+        return -1;
+    }
+    const TfheHipSecretKey &sk = *secret->lwe_key;
+    if (seed) {
+        Rng both(*seed);                                  // a stream of its own, for this selector alone
+        tgsw_encrypt_into(sk, bits, count, both, both, out);
+    } else {
+        Rng noise = Rng::secure(), mask = Rng::secure();  // two fresh ChaCha20 streams, as for a ring sample
+        tgsw_encrypt_into(sk, bits, count, noise, mask, out);
+    }
+    return 0;
+}
+
+const TfheHipSelector *selector_checked(const std::string &w, const TfheHipSelector *sel) {
+    if (!sel || sel->magic != SELECT_MAGIC) api_fail(w + "null or deleted selector");
+    return sel;
+}
+
+// the selector's image, made at first use (under the recorder lock); null for a selector of no bits
+const Engine::SelectorImage *select_image(const TfheHipSelector *csel) {
+    auto *sel = const_cast<TfheHipSelector *>(csel);
+    if (!sel->img && sel->nbits > 0) sel->img = Engine::get().upload_selector(sel->p, sel->words.data(), sel->nbits);
+    return sel->img;
+}
+
+int select_impl(const char *who, const TfheHipSelector *sel, const Torus32 *ring, int32_t M, Torus32 *out, bool on_device) {
+    const std::string w = std::string(who) + ": ";
+    selector_checked(w, sel);
+    if (!ring || !out) api_fail(w + "null ring words or destination");
+    if (M < 1 || (int64_t)M > ((int64_t)1 << sel->nbits))
+        api_fail(w + "M must be in 1..2^" + std::to_string(sel->nbits) + " for a selector of " + std::to_string(sel->nbits) + " bits");
+    // (the kernel loads and stores 16 bytes at a time)
+    if (on_device && ((reinterpret_cast<uintptr_t>(ring) | reinterpret_cast<uintptr_t>(out)) & 15))
+        api_fail(w + "device words must be 16-byte aligned");
+    auto g = recorder_lock();
+    // names no pool slot: what is recorded stays recorded, a flush in flight goes on (the select is ordered behind it on
+    // the stream and works in scratch entries of its own)
+    const Engine::SelectorImage *img = select_image(sel);     // out of device memory: ApiError, nothing has changed
+    Engine::get().run_select(img, sel->p, sel->nbits, ring, M, on_device, out, on_device);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t tfhe_hip_tgsw_words(const TFheGateBootstrappingParameterSet *params) {
+    if (!params || !params->in_out_params) { set_error("tfhe_hip_tgsw_words: null parameter set"); return -1; }
+    const Params &p = params_of(params);
+    return (int64_t)p.kpl() * (p.k + 1) * p.N;
+}
+
+int tfhe_hip_tgsw_encrypt_bits(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                               Torus32 *out_words) {
+    return tgsw_encrypt_impl("tfhe_hip_tgsw_encrypt_bits", secret, bits, count, out_words, nullptr);
+}
+int tfhe_hip_tgsw_encrypt_bits_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                                      Torus32 *out_words, uint64_t seed) {
+    return tgsw_encrypt_impl("tfhe_hip_tgsw_encrypt_bits_seeded", secret, bits, count, out_words, &seed);
+}
+
+TfheHipSelector *tfhe_hip_new_selector(const TFheGateBootstrappingParameterSet *params, const Torus32 *words, int32_t nbits) {
+    const std::string w = "tfhe_hip_new_selector: ";
+    // every argument before the device is looked at: a refusal has no effect
+    if (!params || !params->in_out_params) { set_error(w + "null parameter set"); return nullptr; }
+    if (nbits < 0 || nbits > SELECT_MAX_BITS) { set_error(w + "nbits must be in 0.." + std::to_string(SELECT_MAX_BITS)); return nullptr; }
+    if (nbits > 0 && !words) { set_error(w + "null words"); return nullptr; }
+    const Params &p = params_of(params);
+    // what a cloud key of this set would be refused for (the CRT range, the kernel forms' gadget range), then the CMUX
+    // kernel's own two bounds
+    if (const char *why = unsupported_reason(p)) { set_error(w + why); return nullptr; }
+    if (const char *why = cmux_gadget_error(p.N, p.k, p.l, p.Bgbit)) { set_error(w + why); return nullptr; }
+    auto *sel = new TfheHipSelector{SELECT_MAGIC, p, nbits, std::vector<Torus32>(), nullptr};
+    if (nbits > 0) sel->words.assign(words, words + (size_t)nbits * p.kpl() * (p.k + 1) * p.N);
+    return sel;
+}
+void tfhe_hip_delete_selector(TfheHipSelector *sel) {
+    if (!sel) return;
+    if (sel->magic != SELECT_MAGIC) { set_error("tfhe_hip_delete_selector: not a selector (or already deleted)"); return; }
+    auto g = recorder_lock();
+    Engine::get().free_selector(sel->img);                // (waits for the stream: a select in flight reads the image)
+    sel->magic = 0;
+    delete sel;
+}
+int32_t tfhe_hip_selector_bits(const TfheHipSelector *sel) {
+    if (!sel || sel->magic != SELECT_MAGIC) { set_error("tfhe_hip_selector_bits: null or deleted selector"); return -1; }
+    return sel->nbits;
+}
+
+int tfhe_hip_ring_select(const TfheHipSelector *sel, const Torus32 *ring_words, int32_t M, Torus32 *out_ring_words) {
+    return guarded_rc([&] { return select_impl("tfhe_hip_ring_select", sel, ring_words, M, out_ring_words, false); });
+}
+int tfhe_hip_ring_select_device(const TfheHipSelector *sel, const void *device_ring_words, int32_t M, void *device_out) {
+    return guarded_rc([&] {
+        return select_impl("tfhe_hip_ring_select_device", sel, static_cast<const Torus32 *>(device_ring_words), M,
+                           static_cast<Torus32 *>(device_out), true);
+    });
+}
+
+int tfhe_hip_kernel_ring_cmux(const TfheHipSelector *sel, int32_t bit_index, const Torus32 *d1_words, const Torus32 *d0_words,
+                              int32_t count, Torus32 *out_words) {
+    return guarded_rc([&] {
+        const std::string w = "tfhe_hip_kernel_ring_cmux: ";
+        selector_checked(w, sel);
+        if (!d1_words || !d0_words || !out_words) api_fail(w + "null argument");
+        if (bit_index < 0 || bit_index >= sel->nbits) api_fail(w + "bit_index must be in 0.." + std::to_string(sel->nbits - 1));
+        if (count < 1 || count > CMUX_MAX_COUNT) api_fail(w + "count must be in 1.." + std::to_string(CMUX_MAX_COUNT));
+        auto g = recorder_lock();
+        const Engine::SelectorImage *img = select_image(sel);
+        Engine::get().run_cmux(img, sel->p, bit_index, d1_words, d0_words, count, out_words);
+        return 0;
+    });
+}
+
+double tfhe_hip_last_select_ms(void) {
+    auto g = recorder_lock();
+    return Engine::get().last_select_ms();
+}
+
+int tfhe_hip_test_select_bounds(int32_t N, int32_t l, int32_t Bgbit) {
+    if ((N != 1024 && N != 2048) || l < 1 || Bgbit < 1 || Bgbit > CMUX_MAX_BGBIT || l * Bgbit > 32) {
+        set_error("test_select_bounds: bad arguments");
+        return -1;
+    }
+    return (cmux_mac_ok(N, 2 * l) ? 0 : 1) | (cmux_crt_ok(N, 2 * l, Bgbit) ? 0 : 2);
+}
+
+}  // extern "C"

@@ -1393,6 +1393,8 @@ int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const 
 #include "pack_host.cpp"
 // and that of the ring-encrypted inputs, behind it (it uses the negacyclic product defined there)
 #include "unpack_host.cpp"
+// and that of the private selection, behind both (the TGSW encryptor uses the same product)
+#include "select_host.cpp"
 
 // and that of the seed-compressed cloud keys
 #include "compressed_host.cpp"

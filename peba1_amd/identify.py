@@ -72,3 +72,18 @@ def unpack_templates(ring_words_list, params, nslots, bitsize, key):
     told apart by their count -- in which a gallery rests in half the bytes), ready for identify().  One unpack per
     template; LWE samples exist only on the device."""
     return [circuits.EncryptedVector.from_ring(params, w, nslots, bitsize, key) for w in ring_words_list]
+
+
+def select_template(selector, ring_gallery, params, nslots, bitsize, key):
+    """Verification against a claimed identity the server must not learn: the CMUX tree of `selector` (api.Selector over
+    the client's TGSW-encrypted index bits) picks one template of a gallery that rests as ring samples, and the selected
+    sample is opened like any template that arrived as one (EncryptedVector.from_ring), ready for function_f.  ring_gallery:
+    [M][(k+1) N] host words, or an int32 torch tensor resident on the device -- then only the (k+1) N selected words pass
+    through the host on their way into the unpack, the gallery stays where it is."""
+    device = hasattr(ring_gallery, "data_ptr")               # a torch tensor; anything else is host words
+    words = api.ring_select(selector, ring_gallery, device=device)
+    if device:
+        if _l.load().tfhe_hip_stream_sync() != 0:
+            raise RuntimeError(api.last_error())
+        words = words.cpu().numpy()
+    return circuits.EncryptedVector.from_ring(params, words, nslots, bitsize, key)

@@ -294,6 +294,17 @@ SIGNATURES = {
     "tfhe_hip_kernel_lwe_expand": (C.c_int, [PS, I32P, C.c_int32, I32P, C.c_int32, I32P]),
     "tfhe_hip_test_expand_slots": (C.c_int64, [I32P, C.c_int64]),
     "tfhe_hip_get_seeded_lwe_stats": (None, [C.POINTER(SeededLweStats)]),
+    "tfhe_hip_tgsw_words": (C.c_int64, [PS]),
+    "tfhe_hip_tgsw_encrypt_bits": (C.c_int, [SK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_tgsw_encrypt_bits_seeded": (C.c_int, [SK, I32P, C.c_int32, I32P, C.c_uint64]),
+    "tfhe_hip_new_selector": (C.c_void_p, [PS, I32P, C.c_int32]),
+    "tfhe_hip_delete_selector": (None, [C.c_void_p]),
+    "tfhe_hip_selector_bits": (C.c_int32, [C.c_void_p]),
+    "tfhe_hip_ring_select": (C.c_int, [C.c_void_p, I32P, C.c_int32, I32P]),
+    "tfhe_hip_ring_select_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "tfhe_hip_last_select_ms": (C.c_double, []),
+    "tfhe_hip_kernel_ring_cmux": (C.c_int, [C.c_void_p, C.c_int32, I32P, I32P, C.c_int32, I32P]),
+    "tfhe_hip_test_select_bounds": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])
