@@ -304,7 +304,7 @@ int tfhe_hip_linear_batch(LweSample *result, int32_t nin, const LweSample *const
 void tfhe_hip_sym_encrypt_torus(LweSample *result, Torus32 mu, const TFheGateBootstrappingSecretKeySet *key);
 Torus32 tfhe_hip_sym_phase(const LweSample *sample, const TFheGateBootstrappingSecretKeySet *key);
 
-/* ---- tuning (eleven names that results never depend on, and the opt-in "fold_constants") ----
+/* ---- tuning (twelve names that results never depend on, and the opt-in "fold_constants") ----
  * "br_variant": which form of the blind-rotate kernel runs wide launches (env TFHE_HIP_BR_VARIANT): -1 (default) =
  * the fastest measured for the ring size (N = 1024: 4 waves per rotation; N = 2048: split), 0 = 4 waves (N = 1024),
  * 2 = split (8 waves, every transform as two half-size ones), 4 = 2 waves (N = 1024; the form with the widest admissible
@@ -329,6 +329,9 @@ Torus32 tfhe_hip_sym_phase(const LweSample *sample, const TFheGateBootstrappingS
  * observable changes; 0 = evaluate every recorded gate.
  * "balance_levels": 1 (default) = slack-aware level filling at flush, 0 = plain ASAP
  * levels.
+ * "level_slack" (env TFHE_HIP_LEVEL_SLACK): 1 (default) = behind that filling, gates with slack move off the cost steps
+ * of a MEASURED table of level costs, where the library holds one for the parameter set, the CU count and the launch
+ * tunings (profiles/level_cost_*.json); 0 = never.
  * "fold_constants": 0 (default) / 1 (env TFHE_HIP_FOLD_CONSTANTS) = OPT-IN constant folding at record time: a gate one of
  * whose operands is a trivial sample (bootsCONSTANT, a fresh sample, a copy of either: a PUBLIC constant) is not
  * bootstrapped -- its result is the constant, the other operand or its negation; a MUX with a constant data operand becomes
@@ -550,6 +553,25 @@ int tfhe_hip_test_level_plan_full(const int32_t *ops16, const int32_t *op_keys, 
  * tfhe_hip_test_ks_plan_form: the same six words and, seventh, the kernel form: 0 = per gate, 1 = LDS strips, 2 = index
  * (out7).  What Engine::launch_ks runs and counts (ks_*_launches) is this plan.
  * All return 0, -1 on bad arguments. ---- */
+/* ---- the cost-driven levelling (tuning "level_slack", peba1_amd/csrc/scheduler.cpp relevel_by_cost), without touching
+ * the device.  tfhe_hip_test_level_slack: levelise the DAG ops5 (records as tfhe_hip_test_schedule's, balance = 1) and,
+ * with level_slack != 0, run the pass under the cost table (cost_widths ascending from >= 1, cost_us; linear between
+ * entries; beyond the last one the last slope goes on (period = 0) or the table's last `period` rotations repeat, as
+ * for a compiled-in table with period = 2 CUs; ncost = 0: no table).  levels_out[count]: the level of every op; widths_out[depth + 1]:
+ * rotations per level; cost_out2 = {sum of the table's cost over the levels, the same sum without the pass}.  Returns the
+ * depth.  level_slack = 0 gives tfhe_hip_test_schedule's levels.
+ * tfhe_hip_test_level_cost: launch_plan.hpp level_cost_us under the default tunings: the compiled-in measured table's
+ * microseconds for a level of `width` rotations of this parameter set on a card of cu_count CUs, -1 = no table.
+ * tfhe_hip_test_set_level_cost: flushes use this table for every parameter set in place of the compiled-in ones
+ * (ncost = 0: those again).  tfhe_hip_last_level_slack: out4 = {sum before the pass, after it, gates moved, pool slots in use
+ * when the flush began -- its peak: slots are taken at record time} of the last flush (the first three 0: the pass did not run).  Return 0 (the first: the depth), -1 on bad arguments. ---- */
+int tfhe_hip_test_level_slack(const int32_t *ops5, int32_t count, int32_t unit, int32_t level_slack, const int32_t *cost_widths,
+                              const double *cost_us, int32_t ncost, int32_t period, int32_t *levels_out, int32_t *widths_out,
+                              double *cost_out2);
+int tfhe_hip_test_level_cost(int32_t n, int32_t N, int32_t k, int32_t l, int32_t Bgbit, int32_t ks_t, int32_t ks_basebit,
+                             int32_t cu_count, int32_t width, double *us_out);
+int tfhe_hip_test_set_level_cost(const int32_t *cost_widths, const double *cost_us, int32_t ncost);
+int tfhe_hip_last_level_slack(double *out4);
 int tfhe_hip_test_br_plan(int32_t N, int32_t l, int32_t Bgbit, const int32_t *tunings4, int32_t cu_count, int32_t count,
                           int32_t flags, int32_t *out3);
 int tfhe_hip_test_ks_plan(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,

@@ -6,7 +6,9 @@
 // (peba1_amd/kernel_id.py).
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cstddef>
+#include <cstdint>
 
 #include "br_forms.hpp"
 
@@ -168,6 +170,98 @@ inline int ks_splits(const LaunchTunings &t, int cu_count, int cnt, const KsShap
         while (splits < t.ks_max_splits && cnt * splits * 2 <= t.ks_target_blocks) splits *= 2;
     }
     return splits;
+}
+
+// What a level of a flush costs, by its width in rotations: MEASURED microseconds of the blind-rotate launches plan_br
+// forms for that width plus the key switch (tools/level_cost.py -> profiles/level_cost_<set>.json).  The leveller
+// (scheduler.cpp relevel_by_cost) minimises the sum over a flush's levels; it asks for nothing but this function.
+// n == 0: unknown -- the leveller then leaves its levels as they are.
+struct LevelCost {
+    const int32_t *width = nullptr;     // ascending
+    const double *us = nullptr;
+    int n = 0;
+    // beyond the table a launch repeats its last `period` rotations (a full round of the wide form: 2 workgroups per CU);
+    // 0 = the last segment's slope goes on
+    int period = 0;
+};
+
+// how many periods to take off a width beyond the table so that it falls into the table's last period
+inline long long level_cost_fold(const LevelCost &c, long long width) {
+    const long long top = c.width[c.n - 1];
+    if (width <= top || c.period <= 0 || c.period > top - c.width[0]) return 0;
+    return (width - top + c.period - 1) / c.period;
+}
+
+// 0 for an empty level, the first entry below it, linear between entries; beyond the table see `period`
+inline double level_cost_at(const LevelCost &c, long long width) {
+    if (width <= 0 || c.n <= 0) return 0.0;
+    if (width <= c.width[0] || c.n == 1) return c.us[0];
+    const long long top = c.width[c.n - 1], fold = level_cost_fold(c, width);
+    if (fold > 0) return level_cost_at(c, width - fold * c.period) + (double)fold * (c.us[c.n - 1] - level_cost_at(c, top - c.period));
+    const int32_t *hi = std::lower_bound(c.width, c.width + c.n, (int32_t)std::min<long long>(width, top));
+    const int j = (int)(hi - c.width);
+    return c.us[j - 1] + (c.us[j] - c.us[j - 1]) * (double)(width - c.width[j - 1]) / (double)(c.width[j] - c.width[j - 1]);
+}
+
+// The table's own widths next to `width`, nearest first -- where its cost steps are: up to `most` below it (dir < 0) or above
+// it (dir > 0), beyond the table those of the last period shifted.  Returns how many.
+inline int level_cost_steps(const LevelCost &c, long long width, int dir, long long *out, int most) {
+    if (c.n <= 0) return 0;
+    const long long shift = level_cost_fold(c, width) * c.period, at = width - shift;
+    int count = 0;
+    if (dir < 0) {
+        for (int j = (int)(std::lower_bound(c.width, c.width + c.n, (int32_t)std::min<long long>(at, INT32_MAX)) - c.width) - 1;
+             j >= 0 && count < most; --j)
+            out[count++] = c.width[j] + shift;
+    } else {
+        for (int j = (int)(std::upper_bound(c.width, c.width + c.n, (int32_t)std::min<long long>(at, INT32_MAX)) - c.width);
+             j < c.n && count < most; ++j)
+            out[count++] = c.width[j] + shift;
+    }
+    return count;
+}
+
+// The compiled-in copies of the measured tables: level_cost_tables.inc, written by tools/level_cost_inc.py from
+// profiles/level_cost_*.json when the library is built (absent: no table, every set unknown).
+struct LevelCostEntry {
+    int n, N, k, l, Bgbit, ks_t, ks_basebit;      // the parameter set ...
+    int cus;                                      // ... the card ...
+    int br_variant, br8_max_rotations, br_tail8, br_digit_table, ks_tile, ks_index, ks_max_splits, ks_target_blocks,
+        ks_split_ties;                            // ... and the tunings it was measured under
+    int count;
+    const int32_t *width;
+    const double *us;
+};
+#if __has_include("level_cost_tables.inc")
+#include "level_cost_tables.inc"
+#else
+#warning "level_cost_tables.inc is missing (run tools/level_cost_inc.py before peba1_amd/csrc/build.sh): this library knows no level-cost table and the tuning level_slack does nothing"
+static constexpr LevelCostEntry LEVEL_COST_TABLES[1] = {};
+static constexpr int LEVEL_COST_TABLE_COUNT = 0;
+#endif
+
+// what a parameter set is to the tables: the sizes the launches depend on
+struct LevelCostSet { int n, N, k, l, Bgbit, ks_t, ks_basebit; };
+
+// the table of this set on a card of `cus` CUs under these tunings; unknown (n == 0) unless all three are what a table was
+// measured with -- a launch rule switched by a tuning has other cost steps
+inline LevelCost level_cost_table(const LevelCostSet &p, int cus, const LaunchTunings &t) {
+    for (int i = 0; i < LEVEL_COST_TABLE_COUNT; ++i) {
+        const LevelCostEntry &e = LEVEL_COST_TABLES[i];
+        if (e.n == p.n && e.N == p.N && e.k == p.k && e.l == p.l && e.Bgbit == p.Bgbit && e.ks_t == p.ks_t &&
+            e.ks_basebit == p.ks_basebit && e.cus == cus && e.br_variant == t.br_variant &&
+            e.br8_max_rotations == t.br8_max_rotations && e.br_tail8 == t.br_tail8 && e.br_digit_table == t.br_digit_table &&
+            e.ks_tile == t.ks_tile && e.ks_index == t.ks_index && e.ks_max_splits == t.ks_max_splits &&
+            e.ks_target_blocks == t.ks_target_blocks && e.ks_split_ties == t.ks_split_ties)
+            return LevelCost{e.width, e.us, e.count, 2 * e.cus};
+    }
+    return LevelCost{};
+}
+
+// microseconds of a level of `width` rotations, -1 = unknown
+inline double level_cost_us(int width, const LevelCostSet &p, int cus, const LaunchTunings &t) {
+    const LevelCost c = level_cost_table(p, cus, t);
+    return c.n ? level_cost_at(c, width) : -1.0;
 }
 
 // the largest key-switch partial-sum buffer a launch of `count` gates uses

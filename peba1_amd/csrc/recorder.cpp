@@ -41,6 +41,14 @@ struct Recorder {
     // the pending ops, their one index (tuning "reuse_gates": OpGraph::reuse) and the NOT-origin table (op_graph.hpp)
     OpGraph<SlotPool> graph;
     bool balance_levels = true;   // slack-aware level filling (scheduler.hpp)
+    // the cost-driven pass behind it (scheduler.cpp relevel_by_cost; tuning "level_slack", env TFHE_HIP_LEVEL_SLACK): on,
+    // a flush whose parameter set, card and tunings have a measured cost table (launch_plan.hpp level_cost_table) moves
+    // gates with slack off the table's cost steps; off, or no table: the list scheduling's levels
+    bool level_slack = true;
+    // a table set by hand (tfhe_hip_test_set_level_cost) stands in for the compiled-in ones, whatever the parameter set
+    std::vector<int32_t> cost_width;
+    std::vector<double> cost_us;
+    LevelSlackReport last_slack;
     // operations of a flush launched without waiting (tfhe_hip_flush_async): released when it is complete
     std::vector<PendingOp> flight_ops;
     std::vector<LinTerm> flight_terms;      // the term table its linear combinations name
@@ -63,6 +71,7 @@ Recorder &rec() {
         if (const char *e = std::getenv("TFHE_HIP_DEFERRED")) r.deferred = std::atoi(e) != 0;
         if (const char *e = std::getenv("TFHE_HIP_FOLD_CONSTANTS")) r.fold_constants = std::atoi(e) != 0;   // opt-in (Recorder)
         if (const char *e = std::getenv("TFHE_HIP_BATCH_KEYS")) r.batch_keys = std::atoi(e) != 0;           // opt-in (Recorder)
+        if (const char *e = std::getenv("TFHE_HIP_LEVEL_SLACK")) r.level_slack = std::atoi(e) != 0;
         return true;
     }();
     (void)init;
@@ -425,7 +434,17 @@ int flush_locked(bool wait) {
     const std::vector<PendingOp> &ops = r.graph.ops();
     // level of every op: ASAP, or slack-aware balanced (same depth, fuller narrow levels)
     std::vector<int32_t> lvl, alap;
-    const int levels = schedule_levels(ops, r.graph.max_level(), r.balance_levels, Engine::get().cu_count(), lvl, &alap, r.graph.terms());
+    LevelCost cost;                                                 // unknown unless ...
+    if (r.level_slack && !r.cost_width.empty()) {
+        cost = LevelCost{r.cost_width.data(), r.cost_us.data(), (int)r.cost_width.size(), 0};
+    } else if (r.level_slack) {                                     // ... measured for this set, card and tunings
+        const DevParams &dp = r.keys[ops[0].key]->bk->dev->dp;      // (the keys of a flush share one parameter set)
+        cost = level_cost_table(LevelCostSet{dp.n, dp.N, dp.k, dp.l, dp.Bgbit, dp.ks_t, dp.ks_basebit}, Engine::get().cu_count(),
+                                Engine::get().tunings);
+    }
+    const int levels = schedule_levels(ops, r.graph.max_level(), r.balance_levels, Engine::get().cu_count(), lvl, &alap, r.graph.terms(),
+                                       &cost, &r.last_slack);
+    r.last_slack.pool_slots = (long long)pool->in_use();           // slots are taken at record time: the flush's peak
     if (const char *trace = std::getenv("TFHE_HIP_TRACE_DAG")) {      // diagnostic: per op "kind asap alap level dst a b c" (slots)
         if (FILE *f = std::fopen(trace, "w")) {
             for (size_t i = 0; i < ops.size(); ++i)
@@ -481,9 +500,21 @@ bool set_deferred_locked(bool on) { return std::exchange(rec().deferred, on); }
 
 bool set_batch_keys_locked(bool on) { return std::exchange(rec().batch_keys, on); }
 
+void set_level_cost_locked(const int32_t *widths, const double *us, int count) {
+    Recorder &r = rec();
+    r.cost_width.assign(widths, widths + count);
+    r.cost_us.assign(us, us + count);
+}
+
+void last_level_slack_locked(double *out4) {
+    const LevelSlackReport &s = rec().last_slack;
+    out4[0] = s.us_before; out4[1] = s.us_after; out4[2] = (double)s.moved; out4[3] = (double)s.pool_slots;
+}
+
 bool set_recorder_tuning_locked(const char *name, bool on) {
     Recorder &r = rec();
     bool *knob = std::strcmp(name, "reuse_gates") == 0      ? &r.graph.reuse
+                 : std::strcmp(name, "level_slack") == 0    ? &r.level_slack
                  : std::strcmp(name, "eliminate_dead") == 0 ? &r.eliminate_dead
                  : std::strcmp(name, "fold_constants") == 0 ? &r.fold_constants
                  : std::strcmp(name, "balance_levels") == 0 ? &r.balance_levels

@@ -72,8 +72,12 @@ void forget_key_locked(const TFheGateBootstrappingCloudKeySet *bk);   // a key a
 bool deferred_mode();
 bool set_deferred_locked(bool on);                          // returns the previous mode
 bool set_batch_keys_locked(bool on);                        // tuning "batch_keys"; returns the previous setting
+// a cost table for the leveller's cost-driven pass in place of the compiled-in ones (count 0: those again), and what the
+// pass did at the last flush: {sum of the levels' costs before, after, gates moved, pool slots in use at the flush}
+void set_level_cost_locked(const int32_t *widths, const double *us, int count);
+void last_level_slack_locked(double *out4);
 bool set_recorder_tuning_locked(const char *name, bool on); // reuse_gates, eliminate_dead, fold_constants, balance_levels,
-                                                            // batch_keys
+                                                            // batch_keys, level_slack
 #pragma GCC visibility pop
 
 }  // namespace tfhe_hip

@@ -2,6 +2,7 @@
 #include "scheduler.hpp"
 
 #include "engine.hpp"
+#include "launch_plan.hpp"
 
 #include <algorithm>
 #include <queue>
@@ -14,11 +15,112 @@ struct HeapItem {
     int32_t alap, idx;
     bool operator>(const HeapItem &o) const { return alap != o.alap ? alap > o.alap : idx > o.idx; }
 };
+
+// The cost-driven pass behind the list scheduling (tuning "level_slack").  The list scheduling fills levels by a width
+// policy; what a level really costs is a staircase in its width (launch_plan.hpp LevelCost: measured), and a level a few
+// rotations past a step pays the whole step.  One forward sweep: at level L, the gates whose successors all run later than
+// L + j may run j levels later (j up to 4: the look-ahead); among the amounts the table's own steps suggest -- down to a step
+// below L's width, up to a step above the other level's, or all of them -- the one that lowers cost(L) + cost(L + j) most, by
+// at least half a percent (the table is a measurement), is moved, gates with the latest bound first.  What was moved is
+// looked at again where it landed, so a surplus travels until it finds room.  Depth, dependencies and the set of gates stay;
+// linear ops follow their operands.  Sort aside, the work is one visit per gate and level it passes.  Nothing changes unless the sum over all levels fell.
+struct SuccLists { const std::vector<int32_t> &off, &to; };
+struct PredLists { const std::vector<size_t> &at; const std::vector<int32_t> &of, &count; };
+void relevel_by_cost(const std::vector<PendingOp> &ops, int depth, const LevelCost &cost, const SuccLists &succ,
+                     const PredLists &pred, std::vector<int32_t> &lvl, LevelSlackReport *report) {
+    const int n = (int)ops.size();
+    std::vector<long long> width((size_t)depth + 2, 0);
+    std::vector<std::vector<int32_t>> at((size_t)depth + 2);
+    for (int i = 0; i < n; ++i) {
+        if (op_is_linear(ops[i].kind)) continue;
+        width[(size_t)lvl[i]] += op_rotations(ops[i]);
+        at[(size_t)lvl[i]].push_back(i);
+    }
+    auto total = [&] { double t = 0; for (int L = 1; L <= depth; ++L) t += level_cost_at(cost, width[(size_t)L]); return t; };
+    const double before = total();
+    if (report) { report->us_before = report->us_after = before; report->moved = 0; }
+    const std::vector<int32_t> kept = lvl;
+    // the latest level of op i its successors allow: a gate behind it runs a level later, a linear op rides along
+    auto latest = [&](int32_t i, auto &&self) -> int32_t {
+        int32_t ub = depth;
+        for (int32_t e = succ.off[i]; e < succ.off[i + 1] && ub > lvl[i]; ++e) {
+            const int32_t s = succ.to[e];
+            ub = std::min(ub, op_is_linear(ops[s].kind) ? self(s, self) : lvl[s] - 1);
+        }
+        return ub;
+    };
+    std::vector<HeapItem> movable;          // (-latest level, op): sorts latest bound first, then recording order
+    long long moved_gates = 0;
+    constexpr int STEPS = 16, AHEAD = 4;
+    for (int L = 1; L < depth; ++L) {
+        movable.clear();
+        long long free_rot = 0;
+        for (int32_t i : at[(size_t)L]) {
+            const int32_t ub = latest(i, latest);
+            if (ub > L) { movable.push_back(HeapItem{-ub, i}); free_rot += op_rotations(ops[i]); }
+        }
+        if (!free_rot) continue;
+        std::sort(movable.begin(), movable.end(), [](const HeapItem &x, const HeapItem &y) { return y > x; });
+        // where to: one of the next AHEAD levels (a surplus that gains nothing next door may do so two levels on)
+        const long long w = width[(size_t)L];
+        double best_gain = 0;
+        long long best_m = 0;
+        int best_j = 0;
+        size_t reach = movable.size();                              // gates that may run at L + j: a prefix
+        for (int j = 1; j <= AHEAD && L + j <= depth; ++j) {
+            while (reach > 0 && -movable[reach - 1].alap < L + j) free_rot -= op_rotations(ops[movable[--reach].idx]);
+            if (!free_rot) break;
+            const long long nx = width[(size_t)(L + j)];
+            const double now = level_cost_at(cost, w) + level_cost_at(cost, nx);
+            auto consider = [&](long long m) {
+                if (m <= 0 || m > free_rot) return;
+                const double gain = now - level_cost_at(cost, w - m) - level_cost_at(cost, nx + m);
+                if (gain <= 0.005 * now) return;
+                // (equal gains: the nearer level, then the fewer gates -- what stays behind can still go elsewhere)
+                if (gain > best_gain + 1e-9 || (gain > best_gain - 1e-9 && j == best_j && m < best_m)) { best_gain = gain; best_m = m; best_j = j; }
+            };
+            long long steps[STEPS];
+            consider(free_rot);
+            for (int k = level_cost_steps(cost, w, -1, steps, STEPS); k-- > 0;) consider(w - steps[k]);
+            for (int k = level_cost_steps(cost, nx, +1, steps, STEPS); k-- > 0;) consider(steps[k] - nx);
+        }
+        if (!best_m) continue;
+        const int to = L + best_j;
+        long long m = 0;
+        size_t take = 0;
+        for (; take < movable.size() && -movable[take].alap >= to; ++take) {
+            const int r = op_rotations(ops[movable[take].idx]);
+            if (m + r > best_m) break;                          // (a MUX is two rotations: never past the amount)
+            m += r;
+        }
+        const double now = level_cost_at(cost, w) + level_cost_at(cost, width[(size_t)to]);
+        if (now - level_cost_at(cost, w - m) - level_cost_at(cost, width[(size_t)to] + m) <= 0.005 * now) continue;
+        for (size_t t = 0; t < take; ++t) {
+            lvl[movable[t].idx] = to;
+            at[(size_t)to].push_back(movable[t].idx);
+        }
+        width[(size_t)L] -= m;
+        width[(size_t)to] += m;
+        moved_gates += (long long)take;
+    }
+    const double after = total();
+    if (!moved_gates || !(after < before)) { lvl = kept; return; }
+    // linear ops: the highest level of what they read (recording order is topological)
+    for (int i = 0; i < n; ++i) {
+        if (!op_is_linear(ops[i].kind)) continue;
+        int32_t l = 0;
+        for (int t = 0; t < pred.count[i]; ++t) l = std::max(l, lvl[pred.of[pred.at[i] + t]]);
+        lvl[i] = l;
+    }
+    if (report) { report->us_after = after; report->moved = moved_gates; }
+}
 }  // namespace
 
 
 int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool balance, int unit,
-                    std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out, const LinTerm *terms) {
+                    std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out, const LinTerm *terms,
+                    const LevelCost *cost, LevelSlackReport *report) {
+    if (report) *report = LevelSlackReport{};
     const int n = (int)ops.size();
     lvl.resize(n);
     for (int i = 0; i < n; ++i) lvl[i] = ops[i].level;
@@ -146,6 +248,7 @@ int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool bala
         remaining -= width;
         for (int32_t i : batch) release_successors(i, L, release_successors);
     }
+    if (cost && cost->n > 0) relevel_by_cost(ops, asap_depth, *cost, SuccLists{succ_off, succ}, PredLists{pred_at, pred, npred}, lvl, report);
     return asap_depth;
 }
 

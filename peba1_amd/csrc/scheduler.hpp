@@ -142,8 +142,14 @@ inline OpKey op_key(const PendingOp &op) {
 // or 4 units depending on how much work is left per remaining level.  With
 // balance == false, or for trivial DAGs, lvl = ASAP.  Returns the depth.
 // If alap_out is given it receives each op's ALAP level (== lvl when not balancing).
+// cost (tuning "level_slack"; launch_plan.hpp): what a level costs by its width.  Given one, balanced levels go through the
+// cost-driven pass (scheduler.cpp relevel_by_cost), which keeps them unless the sum of the levels' costs falls; null or an
+// empty table: the levels are the list scheduling's.  report: that sum before and after, and the gates moved.
+struct LevelCost;
+struct LevelSlackReport { double us_before = 0, us_after = 0; long long moved = 0, pool_slots = 0; };
 int schedule_levels(const std::vector<PendingOp> &ops, int asap_depth, bool balance, int unit,
-                    std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out = nullptr, const LinTerm *terms = nullptr);
+                    std::vector<int32_t> &lvl, std::vector<int32_t> *alap_out = nullptr, const LinTerm *terms = nullptr,
+                    const LevelCost *cost = nullptr, LevelSlackReport *report = nullptr);
 
 // The descriptors of a flush (engine.hpp): ops[i] runs at level lvl[i] (schedule_levels), levels in all.  nkeys > 1 (a
 // flush of gates under several cloud keys): within a level, descriptors are grouped by ops[i].key.  Linear combinations

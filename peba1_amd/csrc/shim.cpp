@@ -991,7 +991,7 @@ int tfhe_hip_set_tuning(const char *name, int64_t value) {
     if (name && std::strcmp(name, "br8_max_rotations") == 0) { Engine::get().tunings.br8_max_rotations = (int)value; return 0; }
     if (name && std::strcmp(name, "br_tail8") == 0) { Engine::get().tunings.br_tail8 = (int)value; return 0; }
     if (name && std::strcmp(name, "br_variant") == 0) { Engine::get().tunings.br_variant = (int)value; return 0; }
-    if (name && set_recorder_tuning_locked(name, value != 0)) return 0;   // reuse_gates, eliminate_dead, fold_constants, balance_levels, batch_keys
+    if (name && set_recorder_tuning_locked(name, value != 0)) return 0;   // reuse_gates, eliminate_dead, fold_constants, balance_levels, batch_keys, level_slack
     if (name && std::strcmp(name, "sync_deadline_ms") == 0) { Engine::get().sync_deadline_ms = value > 0 ? (long long)value : 0; return 0; }
     set_error(std::string("tfhe_hip_set_tuning: unknown name ") + (name ? name : "(null)"));
     return -1;
@@ -1057,6 +1057,64 @@ int tfhe_hip_test_schedule(const int32_t *ops5, int32_t count, int32_t unit, int
     const int d = schedule_levels(ops, depth, balance != 0, unit, lvl);
     for (int32_t i = 0; i < count; ++i) levels_out[i] = lvl[i];
     return d;
+}
+
+int tfhe_hip_test_level_slack(const int32_t *ops5, int32_t count, int32_t unit, int32_t level_slack, const int32_t *cost_widths,
+                              const double *cost_us, int32_t ncost, int32_t period, int32_t *levels_out, int32_t *widths_out,
+                              double *cost_out2) {
+    if (!ops5 || count < 0 || unit < 1 || ncost < 0 || period < 0 || (ncost > 0 && (!cost_widths || !cost_us)) || !levels_out || !widths_out ||
+        !cost_out2) {
+        set_error("test_level_slack: bad arguments");
+        return -1;
+    }
+    for (int32_t j = 0; j < ncost; ++j)
+        if (cost_widths[j] < 1 || (j > 0 && cost_widths[j] <= cost_widths[j - 1]) || !(cost_us[j] >= 0)) {
+            set_error("test_level_slack: the table's widths must ascend from 1 on, its costs must not be negative");
+            return -1;
+        }
+    std::vector<PendingOp> ops;
+    const int depth = test_build_ops(ops5, count, ops);
+    if (depth < 0) return -1;
+    std::vector<int32_t> lvl;
+    const LevelCost table{cost_widths, cost_us, ncost, period}, none;
+    LevelSlackReport report;
+    schedule_levels(ops, depth, true, unit, lvl, nullptr, nullptr, level_slack ? &table : &none, &report);
+    std::fill(widths_out, widths_out + depth + 1, 0);
+    for (int32_t i = 0; i < count; ++i) {
+        levels_out[i] = lvl[i];
+        widths_out[lvl[i]] += op_rotations(ops[i]);
+    }
+    cost_out2[0] = cost_out2[1] = 0;
+    for (int L = 1; L <= depth; ++L) cost_out2[0] += level_cost_at(table, widths_out[L]);
+    // the sum without the pass: the pass reports it when it ran, else the levels are those
+    cost_out2[1] = report.moved ? report.us_before : cost_out2[0];
+    return depth;
+}
+
+int tfhe_hip_test_level_cost(int32_t n, int32_t N, int32_t k, int32_t l, int32_t Bgbit, int32_t ks_t, int32_t ks_basebit,
+                             int32_t cu_count, int32_t width, double *us_out) {
+    if (!us_out) { set_error("test_level_cost: null output"); return -1; }
+    *us_out = level_cost_us(width, LevelCostSet{n, N, k, l, Bgbit, ks_t, ks_basebit}, cu_count, LaunchTunings{});
+    return 0;
+}
+
+int tfhe_hip_test_set_level_cost(const int32_t *cost_widths, const double *cost_us, int32_t ncost) {
+    if (ncost < 0 || (ncost > 0 && (!cost_widths || !cost_us))) { set_error("test_set_level_cost: bad arguments"); return -1; }
+    for (int32_t j = 0; j < ncost; ++j)
+        if (cost_widths[j] < 1 || (j > 0 && cost_widths[j] <= cost_widths[j - 1]) || !(cost_us[j] >= 0)) {
+            set_error("test_set_level_cost: the table's widths must ascend from 1 on, its costs must not be negative");
+            return -1;
+        }
+    auto g = recorder_lock();
+    set_level_cost_locked(cost_widths, cost_us, ncost);
+    return 0;
+}
+
+int tfhe_hip_last_level_slack(double *out4) {
+    if (!out4) { set_error("last_level_slack: null output"); return -1; }
+    auto g = recorder_lock();
+    last_level_slack_locked(out4);
+    return 0;
 }
 
 // rot_words = 6: the two-operand words of every rotation (the form older callers know); 8: slot_c and sc as well; 9: and

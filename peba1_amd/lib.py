@@ -214,6 +214,11 @@ SIGNATURES = {
                                                C.c_int32, I32P, C.c_int32] + [I32P] * 16),
     "tfhe_hip_test_level_plan_full": (C.c_int, [I32P, I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, I32P,
                                                 C.c_int32, I32P, C.c_int32] + [I32P] * 18),
+    "tfhe_hip_test_level_slack": (C.c_int, [I32P, C.c_int32, C.c_int32, C.c_int32, I32P, C.POINTER(C.c_double), C.c_int32, C.c_int32, I32P,
+                                            I32P, C.POINTER(C.c_double)]),
+    "tfhe_hip_test_level_cost": (C.c_int, [C.c_int32] * 9 + [C.POINTER(C.c_double)]),
+    "tfhe_hip_test_set_level_cost": (C.c_int, [I32P, C.POINTER(C.c_double), C.c_int32]),
+    "tfhe_hip_last_level_slack": (C.c_int, [C.POINTER(C.c_double)]),     # out4
     "tfhe_hip_test_br_plan": (C.c_int, [C.c_int32] * 3 + [I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_ks_plan": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "tfhe_hip_test_ks_plan_form": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
