@@ -1,7 +1,13 @@
 // compressed_host.cpp -- host side of the seed-compressed cloud keys: the key object, its generators, the two expansions
-// and the C ABI (include/tfhe_hip.h "seed-compressed cloud keys").  Compiled as part of shim.cpp's object, like
-// pack_host.cpp.  The arithmetic of key generation and of the host expansion is in host_keys.cpp, the device expansion in
-// expand.hip behind Engine::upload_compressed_key; the file form is in io.cpp.
+// and the C ABI (include/tfhe_hip.h "seed-compressed cloud keys").  The arithmetic of key generation and of the host
+// expansion is in host_keys.cpp, the device expansion in expand.hip behind Engine::upload_compressed_key; the file form is
+// in io.cpp.
+#include <cstring>
+#include <string>
+
+#include "shim_internal.hpp"
+
+using namespace tfhe_hip;
 
 namespace {
 
@@ -26,7 +32,7 @@ TfheHipCompressedCloudKey *make_compressed_key(const char *who, const TFheGateBo
         generate_compressed_key(sk, noise, *key);
     } else {
         // two fresh ChaCha20 streams, as for a keyset: the noise stream's key stays here, the mask stream's key is the seed
-        if (!os_random(key->seed, sizeof key->seed)) fatal("the operating system offers no entropy (getrandom, /dev/urandom)");
+        os_seed(key->seed);
         Rng noise = Rng::secure();
         generate_compressed_key(sk, noise, *key);
     }

@@ -1,5 +1,5 @@
 // op_graph.hpp -- the pending operations of a recording as a graph over slots.  Pure host logic: no HIP, no engine, no
-// samples.  The recorder (recorder.cpp) runs it over the device slot pool; the plan test entries (shim.cpp) run the same
+// samples.  The recorder (recorder.cpp) runs it over the device slot pool; the plan test entries (test_entries.cpp) run the same
 // code over a plain table of vectors.
 //
 // Slots is any table with retain(s), release(s), refs(s) and per-slot vectors `level` and `pending` (SlotPool has them).

@@ -1,28 +1,20 @@
 // pack_host.cpp -- host side of the packing key switch: the key object, key generation, decryption of a packed
-// sample and the C ABI (include/tfhe_hip.h "packing key switch").  Compiled as part of shim.cpp's object, like
-// recorder.cpp: it uses the array headers and the guarded entry wrappers defined there.  No arithmetic of the pack
-// itself happens here (pack.hip); key generation and decryption run on the CPU like those of the LWE samples.
+// sample and the C ABI (include/tfhe_hip.h "packing key switch").  No arithmetic of the pack itself happens here
+// (pack.hip); key generation and decryption run on the CPU like those of the LWE samples.
+#include <cstring>
+#include <string>
+#include <vector>
 
-// rows [n][t][k+1][N] under a ring key; the device image is made at the first pack (a key can be built, read and
-// deleted on a machine without a GPU)
-struct TfheHipPackingKey {
-    uint32_t magic;
-    Params p;
-    int32_t t, basebit;
-    std::vector<Torus32> rows;
-    uint32_t *img;
-    size_t img_bytes;
-    // a device-expanded key (tfhe_hip_expand_packing_key, seeded_host.cpp) holds the mask seed and the bodies alone: rows
-    // stays empty until tfhe_hip_packing_key_words asks for the words
-    std::vector<uint32_t> mask_seed; // [10] or empty (a plain key)
-    std::vector<Torus32> body;       // [n][t][N]
-};
+#include "shim_internal.hpp"
+
+using namespace tfhe_hip;
 
 namespace {
 constexpr uint32_t PACK_MAGIC = 0x5041434Bu;
+}  // namespace
 
-// body += mask * key in Z[X]/(X^N + 1), key binary; sign = -1 subtracts
-void pack_add_mul_by_bits(uint32_t *body, const uint32_t *mask, const int32_t *bits, int N, uint32_t sign) {
+// ---- what the other host files use (shim_internal.hpp) ----
+void tfhe_hip::pack_add_mul_by_bits(uint32_t *body, const uint32_t *mask, const int32_t *bits, int N, uint32_t sign) {
     for (int i = 0; i < N; ++i) {
         if (!bits[i]) continue;
         for (int j = 0; j < N - i; ++j) body[i + j] += sign * mask[j];
@@ -30,9 +22,7 @@ void pack_add_mul_by_bits(uint32_t *body, const uint32_t *mask, const int32_t *b
     }
 }
 
-// 0, 0 = the set's own key-switch decomposition; null if the pair is refused (the error is set)
-// with_rows false: the rows stay empty (a device-expanded key, seeded_host.cpp)
-TfheHipPackingKey *new_packing_key_object(const char *who, const Params &p, int32_t pk_t, int32_t pk_basebit, bool with_rows = true) {
+TfheHipPackingKey *tfhe_hip::new_packing_key_object(const char *who, const Params &p, int32_t pk_t, int32_t pk_basebit, bool with_rows) {
     if (pk_t == 0 && pk_basebit == 0) { pk_t = p.ks_t; pk_basebit = p.ks_basebit; }
     if (const char *why = pack_decomp_error(p.N, p.k, pk_t, pk_basebit)) { set_error(std::string(who) + ": " + why); return nullptr; }
     if (p.n < 1 || p.n > 1024) { set_error(std::string(who) + ": LWE dimension n must be in [1, 1024]"); return nullptr; }
@@ -40,6 +30,38 @@ TfheHipPackingKey *new_packing_key_object(const char *who, const Params &p, int3
     if (with_rows) key->rows.assign((size_t)p.n * pk_t * (p.k + 1) * p.N, 0);
     return key;
 }
+
+bool tfhe_hip::pack_same_set(const Params &a, const Params &b) {
+    return a.n == b.n && a.N == b.N && a.k == b.k && a.l == b.l && a.Bgbit == b.Bgbit && a.ks_t == b.ks_t &&
+           a.ks_basebit == b.ks_basebit;
+}
+
+const TfheHipPackingKey *tfhe_hip::pack_key_checked(const char *who, const TfheHipPackingKey *key) {
+    if (!key || key->magic != PACK_MAGIC) api_fail(std::string(who) + ": null or deleted packing key");
+    return key;
+}
+
+const uint32_t *tfhe_hip::pack_image(const TfheHipPackingKey *ckey, const TFheGateBootstrappingCloudKeySet *bk) {
+    auto *key = const_cast<TfheHipPackingKey *>(ckey);
+    if (!key->img)
+        key->img = key->mask_seed.empty()
+                       ? Engine::get().upload_pack_image(bk->bk->dev, key->rows.data(), key->t, &key->img_bytes)
+                       : Engine::get().expand_pack_image(bk->bk->dev, key->mask_seed.data(), key->body.data(), key->t, &key->img_bytes);
+    return key->img;
+}
+
+void tfhe_hip::expand_packing_rows_host(const Params &p, int t, const uint32_t seed10[10], const Torus32 *body, std::vector<Torus32> &rows) {
+    const size_t N = (size_t)p.N, nrows = (size_t)p.n * t;
+    Rng mask = Rng::keyed(seed10);
+    rows.assign(nrows * 2 * N, 0);
+    for (size_t r = 0; r < nrows; ++r) {
+        Torus32 *smp = rows.data() + r * 2 * N;
+        for (size_t j = 0; j < N; ++j) smp[j] = mask.torus();
+        std::memcpy(smp + N, body + r * N, N * sizeof(Torus32));
+    }
+}
+
+namespace {
 
 // The draw order (include/tfhe_hip.h): for i < n, for p < t: the kN mask words, then the N noise samples.
 void fill_packing_key(TfheHipPackingKey &key, const TfheHipSecretKey &sk, Rng &secret, Rng &mask) {
@@ -73,26 +95,6 @@ TfheHipPackingKey *make_packing_key(const char *who, const TFheGateBootstrapping
     return key;
 }
 
-bool pack_same_set(const Params &a, const Params &b) {
-    return a.n == b.n && a.N == b.N && a.k == b.k && a.l == b.l && a.Bgbit == b.Bgbit && a.ks_t == b.ks_t &&
-           a.ks_basebit == b.ks_basebit;
-}
-
-const TfheHipPackingKey *pack_key_checked(const char *who, const TfheHipPackingKey *key) {
-    if (!key || key->magic != PACK_MAGIC) api_fail(std::string(who) + ": null or deleted packing key");
-    return key;
-}
-
-// the key's image, made at first use (under the recorder lock, the cloud key's image in place)
-const uint32_t *pack_image(const TfheHipPackingKey *ckey, const TFheGateBootstrappingCloudKeySet *bk) {
-    auto *key = const_cast<TfheHipPackingKey *>(ckey);
-    if (!key->img)
-        key->img = key->mask_seed.empty()
-                       ? Engine::get().upload_pack_image(bk->bk->dev, key->rows.data(), key->t, &key->img_bytes)
-                       : Engine::get().expand_pack_image(bk->bk->dev, key->mask_seed.data(), key->body.data(), key->t, &key->img_bytes);
-    return key->img;
-}
-
 int pack_impl(const TfheHipPackingKey *key, const LweSample *samples, int32_t count, const TFheGateBootstrappingCloudKeySet *bk,
               Torus32 *out, bool device_dst) {
     const char *who = "tfhe_hip_pack_samples";
@@ -122,17 +124,6 @@ void packed_phases(const TfheHipSecretKey &sk, const Torus32 *words, uint32_t *p
     for (int u = 0; u < k; ++u) pack_add_mul_by_bits(ph, w + (size_t)u * N, sk.tlwe_key.data() + (size_t)u * N, N, 0u - 1u);
 }
 
-// [n][t][2][N] from seed and bodies [n][t][N]: the mask polynomials are consecutive stretches of one sequential stream
-void expand_packing_rows_host(const Params &p, int t, const uint32_t seed10[10], const Torus32 *body, std::vector<Torus32> &rows) {
-    const size_t N = (size_t)p.N, nrows = (size_t)p.n * t;
-    Rng mask = Rng::keyed(seed10);
-    rows.assign(nrows * 2 * N, 0);
-    for (size_t r = 0; r < nrows; ++r) {
-        Torus32 *smp = rows.data() + r * 2 * N;
-        for (size_t j = 0; j < N; ++j) smp[j] = mask.torus();
-        std::memcpy(smp + N, body + r * N, N * sizeof(Torus32));
-    }
-}
 }  // namespace
 
 extern "C" {

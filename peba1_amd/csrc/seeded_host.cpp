@@ -1,8 +1,15 @@
 // seeded_host.cpp -- host side of the seed-compressed packing keys and ring samples: the compressed key object, its
 // generators, the two expansions, compressed ring encryption and the C ABI of the seeded unpack (include/tfhe_hip.h
-// "seed-compressed packing keys and ring samples").  Compiled as part of shim.cpp's object behind pack_host.cpp,
-// unpack_host.cpp and compressed_host.cpp, whose packing key, negacyclic product and unpack it uses.  The device side is
-// Engine::expand_pack_image (expand.hip) and the seeded extract kernel (unpack.hip); the file form is in io.cpp.
+// "seed-compressed packing keys and ring samples").  The packing key, the negacyclic product and the unpack are those of
+// pack_host.cpp and unpack_host.cpp.  The device side is Engine::expand_pack_image (expand.hip) and the seeded extract
+// kernel (unpack.hip); the file form is in io.cpp.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "shim_internal.hpp"
+
+using namespace tfhe_hip;
 
 namespace {
 
@@ -52,7 +59,7 @@ TfheHipCompressedPackingKey *make_compressed_packing_key(const char *who, const 
         Rng noise(*noise_seed);
         fill_compressed_packing_key(*key, sk, noise);
     } else {
-        if (!os_random(key->seed, sizeof key->seed)) fatal("the operating system offers no entropy (getrandom, /dev/urandom)");
+        os_seed(key->seed);
         Rng noise = Rng::secure();
         fill_compressed_packing_key(*key, sk, noise);
     }
@@ -75,15 +82,13 @@ int ring_encrypt_compressed_impl(const char *who, const TFheGateBootstrappingSec
     if (sk.p.k != 1) { set_error(std::string(who) + ": compressed ring samples are defined for k = 1"); return -1; }
     std::vector<Torus32> msg;
     if (bits) {
-        if (count < 1 || count > N) { set_error(std::string(who) + ": count must be in 1.." + std::to_string(N)); return -1; }
-        msg.assign((size_t)N, 0);
-        for (int32_t j = 0; j < count; ++j) msg[(size_t)j] = bits[j] ? (1 << 29) : -(1 << 29);
+        if (!ring_message_of_bits(who, bits, count, N, msg)) return -1;
         mu = msg.data();
     }
     uint32_t *w = reinterpret_cast<uint32_t *>(out);
     uint32_t seed[10];
     if (fixture) std::memcpy(seed, mask_seed10, sizeof seed);
-    else if (!os_random(seed, sizeof seed)) fatal("the operating system offers no entropy (getrandom, /dev/urandom)");
+    else os_seed(seed);
     Rng mask = Rng::keyed(seed);
     Rng noise = fixture ? Rng(noise_seed) : Rng::secure();
     std::vector<uint32_t> body((size_t)N);                 // (mu may alias out)
@@ -197,40 +202,20 @@ int tfhe_hip_ring_expand_host(const Torus32 *compressed_words, int32_t N, Torus3
 
 int tfhe_hip_unpack_samples_seeded(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *compressed_words, int32_t nring,
                                    const int32_t *index, int32_t count, LweSample *result) {
-    return guarded_rc([&] {
-        return unpack_impl("tfhe_hip_unpack_samples_seeded", bk, compressed_words, nring, index, count, result != nullptr, true,
-                           [&](int32_t j) { return result + j; }, false, true);
-    });
+    return guarded_rc([&] { return unpack_impl("tfhe_hip_unpack_samples_seeded", bk, compressed_words, nring, index, count, result, false, true); });
 }
 int tfhe_hip_unpack_samples_seeded_scattered(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *compressed_words,
                                              int32_t nring, const int32_t *index, int32_t count, LweSample *const *result) {
-    return guarded_rc([&] {
-        return unpack_impl("tfhe_hip_unpack_samples_seeded_scattered", bk, compressed_words, nring, index, count, result != nullptr,
-                           false, [&](int32_t j) { return result[j]; }, false, true);
-    });
+    return guarded_rc([&] { return unpack_impl("tfhe_hip_unpack_samples_seeded_scattered", bk, compressed_words, nring, index, count, result, false, true); });
 }
 int tfhe_hip_unpack_samples_seeded_device(const TFheGateBootstrappingCloudKeySet *bk, const void *device_compressed_words,
                                           int32_t nring, const int32_t *index, int32_t count, LweSample *result) {
-    return guarded_rc([&] {
-        return unpack_impl("tfhe_hip_unpack_samples_seeded_device", bk, static_cast<const Torus32 *>(device_compressed_words), nring,
-                           index, count, result != nullptr, true, [&](int32_t j) { return result + j; }, true, true);
-    });
+    return guarded_rc([&] { return unpack_impl("tfhe_hip_unpack_samples_seeded_device", bk, static_cast<const Torus32 *>(device_compressed_words), nring, index, count, result, true, true); });
 }
 
 int tfhe_hip_kernel_ring_extract_seeded(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *compressed_words, int32_t nring,
                                         const int32_t *index, int32_t count, Torus32 *u_out) {
-    return guarded_rc([&] {
-        const std::string w = "tfhe_hip_kernel_ring_extract_seeded: ";
-        if (!compressed_words || !u_out) api_fail(w + "null argument");
-        if (!bk || !bk->bk) api_fail(w + "null cloud key");
-        std::vector<int32_t> iota;
-        index = ring_index_checked(w, index, count, nring, bk->bk->p.N, false, iota);
-        auto g = recorder_lock();
-        pool_of_key(bk);
-        finish_flight_locked();
-        Engine::get().run_unpack(bk->bk->dev, compressed_words, nring, false, index, count, nullptr, nullptr, u_out, true, true);
-        return 0;
-    });
+    return guarded_rc([&] { return ring_extract_impl("tfhe_hip_kernel_ring_extract_seeded", bk, compressed_words, nring, index, count, u_out, true); });
 }
 
 int64_t tfhe_hip_test_pack_image(const TfheHipPackingKey *key, const TFheGateBootstrappingCloudKeySet *bk, Torus32 *out,

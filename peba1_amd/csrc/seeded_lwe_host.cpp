@@ -1,8 +1,14 @@
 // seeded_lwe_host.cpp -- host side of the seed-compressed LWE sample arrays (include/tfhe_hip.h "seed-compressed LWE sample
-// arrays"): the array encryptors, the host expansion and the C ABI of the seeded import.  Compiled as part of shim.cpp's
-// object behind seeded_host.cpp: it uses the array headers, the run checks and the guarded entry wrappers defined there.
-// The device side is Engine::run_lwe_expand and lwe_expand_kernel (expand.hip).  The encryptors and the host expansion
-// touch neither the device nor the recorder.
+// arrays"): the array encryptors, the host expansion and the C ABI of the seeded import.  The device side is
+// Engine::run_lwe_expand and lwe_expand_kernel (expand.hip).  The encryptors and the host expansion touch neither the
+// device nor the recorder.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "shim_internal.hpp"
+
+using namespace tfhe_hip;
 
 namespace {
 
@@ -43,7 +49,7 @@ int sym_encrypt_compressed_impl(const char *who, const TFheGateBootstrappingSecr
     if (!lwe_record_dimension_ok(w, sk.p.n) || !lwe_record_count_ok(w, count)) return -1;
     uint32_t seed[LWE_SEED_WORDS];
     if (fixture) std::memcpy(seed, mask_seed10, sizeof seed);
-    else if (!os_random(seed, sizeof seed)) fatal("the operating system offers no entropy (getrandom, /dev/urandom)");
+    else os_seed(seed);
     Rng mask = Rng::keyed(seed);
     Rng noise = fixture ? Rng(noise_seed) : Rng::secure();
     std::vector<uint32_t> body((size_t)count);             // (mu may alias out)
@@ -58,41 +64,26 @@ int sym_encrypt_compressed_impl(const char *who, const TFheGateBootstrappingSecr
     return 0;
 }
 
-// result_at(j): sample j of the results, consecutive or scattered
-template <typename At>
 int import_seeded_impl(const char *who, const TFheGateBootstrappingParameterSet *params, const Torus32 *record, int32_t record_count,
-                       const int32_t *index, int32_t count, bool have_result, bool consecutive, At result_at, bool device_src) {
+                       const int32_t *index, int32_t count, ResultsView result, bool device_src) {
     const std::string w = std::string(who) + ": ";
-    if (!record || !have_result) api_fail(w + "null record words or result");
+    if (!record || !result) api_fail(w + "null record words or result");
     if (!params || !params->in_out_params) api_fail(w + "null parameter set");
     const Params &p = params_of(params);
     if (!lwe_record_dimension_ok(w, p.n) || !lwe_record_count_ok(w, record_count) || !lwe_record_index_ok(w, index, count, record_count))
         api_fail(last_error_ref());
     std::vector<int32_t> iota;
-    if (!index) {
-        iota.resize((size_t)count);
-        std::iota(iota.begin(), iota.end(), 0);
-        index = iota.data();
-    }
+    index = index_or_iota(index, count, iota);
     auto g = recorder_lock();
     // every result is ours, of the set's LWE dimension and not bound to the pool of another shape -- before the device is
     // looked at and before anything changes
-    check_runs(w, SEEDED_IMPORT_RESULT, result_at, consecutive ? 1 : count, consecutive ? count : 1, p);
+    check_runs(w, SEEDED_IMPORT_RESULT, result, count, p);
     SlotPool *pool = Engine::get().pool_for(p);
     // what is recorded and has not run stays recorded: it cannot name the new slots
     finish_flight_locked();
-    std::vector<int32_t> slots;
-    slots.reserve((size_t)count);
-    try {
-        for (int32_t j = 0; j < count; ++j) slots.push_back(alloc_slot(pool));
-        Engine::get().run_lwe_expand(p.n, p.ct_stride(), record, device_src, index, count, pool, slots.data(), nullptr, !device_src);
-    } catch (const ApiError &) {
-        for (int32_t s : slots) pool->release(s);         // the pool or the device is full: nothing was enqueued
-        throw;
-    }
-    for (int32_t j = 0; j < count; ++j) repoint(result_at(j), pool, slots[(size_t)j]);
-    if (!deferred_mode())
-        for (int32_t j = 0; j < count; ++j) sync_sample_locked(result_at(j));
+    import_into_fresh_slots(pool, result, count, [&](const int32_t *slots) {
+        Engine::get().run_lwe_expand(p.n, p.ct_stride(), record, device_src, index, count, pool, slots, nullptr, !device_src);
+    });
     return 0;
 }
 
@@ -149,24 +140,15 @@ int tfhe_hip_lwe_expand_host(const Torus32 *compressed_words, int32_t n, int32_t
 
 int tfhe_hip_import_samples_seeded(const TFheGateBootstrappingParameterSet *params, const Torus32 *compressed_words,
                                    int32_t record_count, const int32_t *index, int32_t count, LweSample *result) {
-    return guarded_rc([&] {
-        return import_seeded_impl("tfhe_hip_import_samples_seeded", params, compressed_words, record_count, index, count,
-                                  result != nullptr, true, [&](int32_t j) { return result + j; }, false);
-    });
+    return guarded_rc([&] { return import_seeded_impl("tfhe_hip_import_samples_seeded", params, compressed_words, record_count, index, count, result, false); });
 }
 int tfhe_hip_import_samples_seeded_scattered(const TFheGateBootstrappingParameterSet *params, const Torus32 *compressed_words,
                                              int32_t record_count, const int32_t *index, int32_t count, LweSample *const *result) {
-    return guarded_rc([&] {
-        return import_seeded_impl("tfhe_hip_import_samples_seeded_scattered", params, compressed_words, record_count, index, count,
-                                  result != nullptr, false, [&](int32_t j) { return result[j]; }, false);
-    });
+    return guarded_rc([&] { return import_seeded_impl("tfhe_hip_import_samples_seeded_scattered", params, compressed_words, record_count, index, count, result, false); });
 }
 int tfhe_hip_import_samples_seeded_device(const TFheGateBootstrappingParameterSet *params, const void *device_compressed_words,
                                           int32_t record_count, const int32_t *index, int32_t count, LweSample *result) {
-    return guarded_rc([&] {
-        return import_seeded_impl("tfhe_hip_import_samples_seeded_device", params, static_cast<const Torus32 *>(device_compressed_words),
-                                  record_count, index, count, result != nullptr, true, [&](int32_t j) { return result + j; }, true);
-    });
+    return guarded_rc([&] { return import_seeded_impl("tfhe_hip_import_samples_seeded_device", params, static_cast<const Torus32 *>(device_compressed_words), record_count, index, count, result, true); });
 }
 
 int tfhe_hip_kernel_lwe_expand(const TFheGateBootstrappingParameterSet *params, const Torus32 *compressed_words, int32_t record_count,
@@ -179,11 +161,7 @@ int tfhe_hip_kernel_lwe_expand(const TFheGateBootstrappingParameterSet *params, 
         if (!lwe_record_dimension_ok(w, p.n) || !lwe_record_count_ok(w, record_count) || !lwe_record_index_ok(w, index, count, record_count))
             api_fail(last_error_ref());
         std::vector<int32_t> iota;
-        if (!index) {
-            iota.resize((size_t)count);
-            std::iota(iota.begin(), iota.end(), 0);
-            index = iota.data();
-        }
+        index = index_or_iota(index, count, iota);
         auto g = recorder_lock();
         finish_flight_locked();
         Engine::get().run_lwe_expand(p.n, p.ct_stride(), compressed_words, false, index, count, nullptr, nullptr, out_words, true);

@@ -1,7 +1,12 @@
 // select_host.cpp -- host side of the private selection: the TGSW encryption of index bits, the selector object and the
-// C ABI of the CMUX tree (include/tfhe_hip.h "private selection").  Compiled as part of shim.cpp's object behind
-// unpack_host.cpp: it uses the guarded entry wrappers defined there and pack_host.cpp's negacyclic product.  No arithmetic
+// C ABI of the CMUX tree (include/tfhe_hip.h "private selection").  The negacyclic product is pack_host.cpp's.  No arithmetic
 // of the CMUX itself happens here (cmux.hip); encryption runs on the CPU like that of the ring samples.
+#include <string>
+#include <vector>
+
+#include "shim_internal.hpp"
+
+using namespace tfhe_hip;
 
 // the rows [nbits][(k+1) l][k+1][N] of a selector; the device image is made at the first select (a selector can be built
 // and deleted on a machine without a GPU)

@@ -1,8 +1,55 @@
 // unpack_host.cpp -- host side of the ring-encrypted inputs: the ring encryption and the C ABI of the unpack
-// (include/tfhe_hip.h "ring-encrypted inputs").  Compiled as part of shim.cpp's object behind pack_host.cpp: it uses the
-// array headers and the guarded entry wrappers defined there and pack_host.cpp's negacyclic product.  No arithmetic of
-// the unpack itself happens here (unpack.hip, then the key-switch kernels); encryption runs on the CPU like that of the
-// LWE samples.
+// (include/tfhe_hip.h "ring-encrypted inputs").  No arithmetic of the unpack itself happens here (unpack.hip, then the
+// key-switch kernels); encryption runs on the CPU like that of the LWE samples.
+#include <string>
+#include <vector>
+
+#include "shim_internal.hpp"
+
+using namespace tfhe_hip;
+
+// ---- what the other host files use (shim_internal.hpp) ----
+bool tfhe_hip::ring_message_of_bits(const char *who, const int32_t *bits, int32_t count, int N, std::vector<Torus32> &msg) {
+    if (count < 1 || count > N) { set_error(std::string(who) + ": count must be in 1.." + std::to_string(N)); return false; }
+    msg.assign((size_t)N, 0);
+    for (int32_t j = 0; j < count; ++j) msg[(size_t)j] = bits[j] ? (1 << 29) : -(1 << 29);
+    return true;
+}
+
+int tfhe_hip::unpack_impl(const char *who, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring, int32_t nring,
+                          const int32_t *index, int32_t count, ResultsView result, bool device_src, bool seeded) {
+    const std::string w = std::string(who) + ": ";
+    if (!ring || !result) api_fail(w + "null ring words or result");
+    if (!bk || !bk->bk) api_fail(w + "null cloud key");
+    const Params &p = bk->bk->p;
+    std::vector<int32_t> iota;
+    index = ring_index_checked(w, index, count, nring, p.N, true, iota);
+    auto g = recorder_lock();
+    // every result is ours, of the key's LWE dimension and not bound to the pool of another shape -- before the device is
+    // looked at and before anything changes
+    check_runs(w, UNPACK_RESULT, result, count, p);
+    SlotPool *pool = pool_of_key(bk);
+    // a flush in flight owns the key switch's partial sums; what is recorded and has not run stays recorded
+    finish_flight_locked();
+    import_into_fresh_slots(pool, result, count, [&](const int32_t *slots) {
+        Engine::get().run_unpack(bk->bk->dev, ring, nring, device_src, index, count, pool, slots, nullptr, !device_src, seeded);
+    });
+    return 0;
+}
+
+int tfhe_hip::ring_extract_impl(const char *who, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring, int32_t nring,
+                                const int32_t *index, int32_t count, Torus32 *u_out, bool seeded) {
+    const std::string w = std::string(who) + ": ";
+    if (!ring || !u_out) api_fail(w + "null argument");
+    if (!bk || !bk->bk) api_fail(w + "null cloud key");
+    std::vector<int32_t> iota;
+    index = ring_index_checked(w, index, count, nring, bk->bk->p.N, false, iota);
+    auto g = recorder_lock();
+    pool_of_key(bk);
+    finish_flight_locked();
+    Engine::get().run_unpack(bk->bk->dev, ring, nring, false, index, count, nullptr, nullptr, u_out, true, seeded);
+    return 0;
+}
 
 namespace {
 
@@ -20,12 +67,9 @@ int ring_encrypt_impl(const char *who, const TFheGateBootstrappingSecretKeySet *
                       int32_t count, Torus32 *out, const uint64_t *seed) {
     if (!secret || !secret->lwe_key || (!mu && !bits) || !out) { set_error(std::string(who) + ": null argument"); return -1; }
     const TfheHipSecretKey &sk = *secret->lwe_key;
-    const int N = sk.p.N;
     std::vector<Torus32> msg;
     if (bits) {
-        if (count < 1 || count > N) { set_error(std::string(who) + ": count must be in 1.." + std::to_string(N)); return -1; }
-        msg.assign((size_t)N, 0);
-        for (int32_t j = 0; j < count; ++j) msg[(size_t)j] = bits[j] ? (1 << 29) : -(1 << 29);
+        if (!ring_message_of_bits(who, bits, count, sk.p.N, msg)) return -1;
         mu = msg.data();
     }
     if (seed) {
@@ -35,40 +79,6 @@ int ring_encrypt_impl(const char *who, const TFheGateBootstrappingSecretKeySet *
         Rng noise = Rng::secure(), mask = Rng::secure();  // two fresh ChaCha20 streams, as for a packing key
         ring_encrypt_into(sk, mu, noise, mask, out);
     }
-    return 0;
-}
-
-// result_at(j): sample j of the results, consecutive or scattered; seeded: `ring` holds seed-compressed records
-// (seeded_host.cpp)
-template <typename At>
-int unpack_impl(const char *who, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring, int32_t nring,
-                const int32_t *index, int32_t count, bool have_result, bool consecutive, At result_at, bool device_src,
-                bool seeded = false) {
-    const std::string w = std::string(who) + ": ";
-    if (!ring || !have_result) api_fail(w + "null ring words or result");
-    if (!bk || !bk->bk) api_fail(w + "null cloud key");
-    const Params &p = bk->bk->p;
-    std::vector<int32_t> iota;
-    index = ring_index_checked(w, index, count, nring, p.N, true, iota);
-    auto g = recorder_lock();
-    // every result is ours, of the key's LWE dimension and not bound to the pool of another shape -- before the device is
-    // looked at and before anything changes
-    check_runs(w, UNPACK_RESULT, result_at, consecutive ? 1 : count, consecutive ? count : 1, p);
-    SlotPool *pool = pool_of_key(bk);
-    // a flush in flight owns the key switch's partial sums; what is recorded and has not run stays recorded
-    finish_flight_locked();
-    std::vector<int32_t> slots;
-    slots.reserve((size_t)count);
-    try {
-        for (int32_t j = 0; j < count; ++j) slots.push_back(alloc_slot(pool));
-        Engine::get().run_unpack(bk->bk->dev, ring, nring, device_src, index, count, pool, slots.data(), nullptr, !device_src, seeded);
-    } catch (const ApiError &) {
-        for (int32_t s : slots) pool->release(s);         // the pool or the device is full: nothing was enqueued
-        throw;
-    }
-    for (int32_t j = 0; j < count; ++j) repoint(result_at(j), pool, slots[(size_t)j]);
-    if (!deferred_mode())
-        for (int32_t j = 0; j < count; ++j) sync_sample_locked(result_at(j));
     return 0;
 }
 
@@ -98,40 +108,20 @@ int tfhe_hip_ring_encrypt_bits_seeded(const TFheGateBootstrappingSecretKeySet *s
 
 int tfhe_hip_unpack_samples(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
                             const int32_t *index, int32_t count, LweSample *result) {
-    return guarded_rc([&] {
-        return unpack_impl("tfhe_hip_unpack_samples", bk, ring_words, nring, index, count, result != nullptr, true,
-                           [&](int32_t j) { return result + j; }, false);
-    });
+    return guarded_rc([&] { return unpack_impl("tfhe_hip_unpack_samples", bk, ring_words, nring, index, count, result, false); });
 }
 int tfhe_hip_unpack_samples_scattered(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
                                       const int32_t *index, int32_t count, LweSample *const *result) {
-    return guarded_rc([&] {
-        return unpack_impl("tfhe_hip_unpack_samples_scattered", bk, ring_words, nring, index, count, result != nullptr, false,
-                           [&](int32_t j) { return result[j]; }, false);
-    });
+    return guarded_rc([&] { return unpack_impl("tfhe_hip_unpack_samples_scattered", bk, ring_words, nring, index, count, result, false); });
 }
 int tfhe_hip_unpack_samples_device(const TFheGateBootstrappingCloudKeySet *bk, const void *device_ring_words, int32_t nring,
                                    const int32_t *index, int32_t count, LweSample *result) {
-    return guarded_rc([&] {
-        return unpack_impl("tfhe_hip_unpack_samples_device", bk, static_cast<const Torus32 *>(device_ring_words), nring, index,
-                           count, result != nullptr, true, [&](int32_t j) { return result + j; }, true);
-    });
+    return guarded_rc([&] { return unpack_impl("tfhe_hip_unpack_samples_device", bk, static_cast<const Torus32 *>(device_ring_words), nring, index, count, result, true); });
 }
 
 int tfhe_hip_kernel_ring_extract(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
                                  const int32_t *index, int32_t count, Torus32 *u_out) {
-    return guarded_rc([&] {
-        const std::string w = "tfhe_hip_kernel_ring_extract: ";
-        if (!ring_words || !u_out) api_fail(w + "null argument");
-        if (!bk || !bk->bk) api_fail(w + "null cloud key");
-        std::vector<int32_t> iota;
-        index = ring_index_checked(w, index, count, nring, bk->bk->p.N, false, iota);
-        auto g = recorder_lock();
-        pool_of_key(bk);
-        finish_flight_locked();
-        Engine::get().run_unpack(bk->bk->dev, ring_words, nring, false, index, count, nullptr, nullptr, u_out, true);
-        return 0;
-    });
+    return guarded_rc([&] { return ring_extract_impl("tfhe_hip_kernel_ring_extract", bk, ring_words, nring, index, count, u_out, false); });
 }
 
 }  // extern "C"
