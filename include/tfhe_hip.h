@@ -430,6 +430,14 @@ typedef struct TfheHipExpandStats {
     uint64_t expand_launches;
 } TfheHipExpandStats;
 void tfhe_hip_get_expand_stats(TfheHipExpandStats *out);
+/* the matrix key switch (tunings "ks_matrix", "ks_matrix_min"): the launches of a flush's wide levels that ran as an int8
+ * matrix product on the matrix cores, one per (level, key) (the raw entry tfhe_hip_kernel_keyswitch_matrix counts its one
+ * launch too).  Such a launch counts in none of ks_pergate / ks_strip / ks_index_launches.  A struct and an entry of their
+ * own, for the same reason as above; tfhe_hip_reset_stats() clears these too. */
+typedef struct TfheHipKsMatrixStats {
+    uint64_t ks_matrix_launches;
+} TfheHipKsMatrixStats;
+void tfhe_hip_get_ks_matrix_stats(TfheHipKsMatrixStats *out);
 /* seed-compressed packing keys and ring samples, a struct of their own for the same reason: the packing keys whose masks
  * were made on the device (tfhe_hip_expand_packing_key, at the first pack) and the expand kernel launches that took, one per
  * key -- a host-expanded or plain key counts nothing; the samples opened by the seeded unpack entries and their extract
@@ -578,6 +586,15 @@ int tfhe_hip_test_ks_plan(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t
                           int32_t cu_count, int32_t count, int64_t *out6);
 int tfhe_hip_test_ks_plan_form(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
                                int32_t cu_count, int32_t count, int64_t *out7);
+/* tfhe_hip_test_ks_plan_form2: the plan of a FLUSH's key-switch launch.  tunings7: the five words above, then the tunings
+ * ks_matrix and ks_matrix_min; has_image: the key holds the byte-plane image of the matrix form.  Form 3 = the matrix form
+ * (tile 64, one launch of `count` gates, one range, no partial sums) at and above ks_matrix_min where the tiled forms would
+ * have run; otherwise what tfhe_hip_test_ks_plan_form returns.  The two entries above have no word for these tunings and
+ * return the plan with the matrix form off: that of every caller but a flush. */
+int tfhe_hip_test_ks_plan_form2(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings7,
+                                int32_t has_image, int32_t cu_count, int32_t count, int64_t *out7);
+/* the four signed bytes s_0 .. s_3 in [-128, 127] of each word w, sum_p s_p 2^(8p) = w (mod 2^32): planes4[count][4] */
+int tfhe_hip_test_ks_byte_planes(const uint32_t *words, int32_t count, int8_t *planes4);
 /* Diagnostic (tools/wg_times.py): a 4-wave blind-rotate launch of `width` random gates (the second of two back to back);
  * times4[4i .. 4i+3] = s_memtime (shader cycles; the start stamp carries the XCC / CU id in its top 16
  * bits) at the start and end of workgroup i, then s_memrealtime (constant 100 MHz) at its start and
@@ -1025,6 +1042,10 @@ int tfhe_hip_kernel_lut_bootstrap_multi_woks(const TFheGateBootstrappingCloudKey
 /* key switch of `count` extracted samples u[c] (kN+1 words) -> out[c] (n+1 words) */
 int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *u,
                               int32_t count, Torus32 *out);
+/* the same rows through the matrix key switch alone, whatever their count (keys with ks_t = 8, ks_basebit = 2 and k N a
+ * multiple of 256; -1 otherwise, or where the device has no room for the key's byte-plane image) */
+int tfhe_hip_kernel_keyswitch_matrix(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *u,
+                                     int32_t count, Torus32 *out);
 /* the pack of `count` caller-supplied samples sample_words[count][n+1] (crafted operands; no slots involved) under
  * `key`, the twiddles of `bk`; idx_per_wg = mask indices per workgroup, 0 = what tfhe_hip_pack_samples uses */
 int tfhe_hip_kernel_pack(const TfheHipPackingKey *key, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *sample_words,

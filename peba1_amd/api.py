@@ -284,6 +284,13 @@ def key_image(key, which):
     return out
 
 
+def ks_matrix_stats():
+    """ks_matrix_launches (tfhe_hip_get_ks_matrix_stats)"""
+    s = _l.KsMatrixStats()
+    _l.load().tfhe_hip_get_ks_matrix_stats(C.byref(s))
+    return {"ks_matrix_launches": s.ks_matrix_launches}
+
+
 def expand_stats():
     """expanded_keys, expand_launches (tfhe_hip_get_expand_stats)"""
     s = _l.ExpandStats()
@@ -1273,6 +1280,17 @@ def kernel_keyswitch(key, u):
     u = np.ascontiguousarray(u, dtype=np.int32).reshape(-1, p.k * p.N + 1)
     out = np.zeros((u.shape[0], p.words), dtype=np.int32)
     rc = _l.load().tfhe_hip_kernel_keyswitch(key.cloud, _i32p(u), u.shape[0], _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def kernel_keyswitch_matrix(key, u):
+    """the rows u through the matrix key switch alone (tfhe_hip_kernel_keyswitch_matrix)"""
+    p = key.params
+    u = np.ascontiguousarray(u, dtype=np.int32).reshape(-1, p.k * p.N + 1)
+    out = np.zeros((u.shape[0], p.words), dtype=np.int32)
+    rc = _l.load().tfhe_hip_kernel_keyswitch_matrix(key.cloud, _i32p(u), u.shape[0], _i32p(out))
     if rc != 0:
         raise RuntimeError(last_error())
     return out

@@ -567,7 +567,30 @@ void Engine::free_key(DeviceKeyImage *img) {
     recoverable_free(img->bk_img, img->bk_img_bytes);
     recoverable_free(img->ksk, img->ksk_bytes);
     recoverable_free(img->tw, img->tw_bytes);
+    recoverable_free(img->ks_planes, img->ks_planes_bytes);
     delete img;
+}
+
+// ---- the byte-plane image of the matrix key switch (ks_matrix.hpp) --------------------------
+static_assert(KS_MATRIX_SPAN == KSM_WAVES * KSM_CHUNK && KS_MATRIX_TILE == KSM_GATES, "launch_plan.hpp plans what ks_matrix.hip runs");
+bool Engine::ensure_ks_planes(const DeviceKeyImage *key) {
+    ENGINE_DEVICE_SCOPE();
+    if (key->ks_planes) return true;
+    const DevParams &dp = key->dp;
+    if (!ks_matrix_shape_ok(dp.k * dp.N, dp.ks_t, dp.ks_basebit)) return false;
+    const size_t bytes = ks_matrix_image_bytes(dp.k * dp.N, dp.ct_stride);
+    uint8_t *img = nullptr;
+    try {
+        img = static_cast<uint8_t *>(recoverable_alloc(bytes, "the byte-plane image of a key-switching key"));
+    } catch (const ApiError &) {
+        return false;                                    // the key works without the matrix form
+    }
+    if (!launch_ksk_planes(stream_, dp, key->key, img)) { recoverable_free(img, bytes); return false; }
+    hip_check(hipGetLastError(), "ksk_planes launch");
+    sync_stream("ksk_planes");
+    key->ks_planes = img;
+    key->ks_planes_bytes = bytes;
+    return true;
 }
 
 // ---- growable device tables -------------------------------------------------------
@@ -787,12 +810,20 @@ void Engine::launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const Ks
     if (!stream) stream = stream_;
     const DevParams &dp = key->dp;
     const KsShape shape = ks_shape(dp);
-    const size_t bytes = ks_partial_bytes(tunings, cu_count_, count, shape);
+    const bool matrix = presized && key->ks_planes != nullptr;       // flushes only (run_level)
+    const size_t bytes = ks_partial_bytes(tunings, cu_count_, count, shape, matrix);
     if (presized && bytes > (scratch_size_.size() > S_KS_PARTIAL ? scratch_size_[S_KS_PARTIAL] : 0))
         fatal("launch_ks: the key-switch partial sums were not sized by execute()");
     int32_t *partial = bytes ? static_cast<int32_t *>(scratch(S_KS_PARTIAL, bytes)) : nullptr;
     // the form is the plan's (launch_plan.hpp plan_ks), decided once for the whole launch; the counters say what ran
-    const KsPlan plan = plan_ks(tunings, count, shape);
+    const KsPlan plan = plan_ks(tunings, count, shape, matrix);
+    if (plan.form == KS_FORM_MATRIX) {
+        // one launch whatever the width: nothing to chunk without partial sums
+        ++ks_matrix_stats.ks_matrix_launches;
+        if (!launch_keyswitch_matrix(stream, dp, key->ks_planes, u_buf, descs, count, pool))
+            fatal("launch_ks: the planned matrix key switch has no kernel for this shape");
+        return;
+    }
     const int chunk = plan.form != KS_FORM_PERGATE ? KS_CHUNK : count;
     for (int done = 0; done < count; done += chunk) {
         const int cnt = std::min(chunk, count - done), splits = ks_splits(tunings, cu_count_, cnt, shape);
@@ -845,8 +876,14 @@ Engine::FlushBuffers Engine::prepare_flush(const std::vector<const DeviceKeyImag
     fb.u_buf = scratch_as<int32_t>(S_EXTRACT, (size_t)(std::max(plan.max_rots, plan.max_extracts) + 1) * key->dp.u_stride);
     size_t partial = 0;
     const std::vector<int32_t> &ks_shares = nkeys == 1 ? plan.ks_off : plan.ks_koff;   // one key-switch launch per (level, key)
-    for (size_t sg = 0; sg + 1 < ks_shares.size(); ++sg)
-        partial = std::max(partial, ks_partial_bytes(tunings, cu_count_, ks_shares[sg + 1] - ks_shares[sg], ks_shape(key->dp)));
+    for (size_t sg = 0; sg + 1 < ks_shares.size(); ++sg) {
+        // a launch wide enough for the matrix form: its key gets the byte-plane image now, before anything is enqueued (a
+        // card without room for it: the launch runs the tiled form and is sized as such)
+        const DeviceKeyImage *share_key = keys[nkeys == 1 ? 0 : sg % (size_t)nkeys];
+        const int width = ks_shares[sg + 1] - ks_shares[sg];
+        const bool matrix = plan_ks(tunings, width, ks_shape(key->dp), true).form == KS_FORM_MATRIX && ensure_ks_planes(share_key);
+        partial = std::max(partial, ks_partial_bytes(tunings, cu_count_, width, ks_shape(key->dp), matrix));
+    }
     if (partial) (void)scratch(S_KS_PARTIAL, partial);
     // the key table and the key index of every rotation
     if (nkeys > 1) {
@@ -1139,6 +1176,29 @@ void Engine::run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int coun
     std::vector<int32_t> res((size_t)count * dp.ct_stride);
     d2h(res.data(), dpool, res.size(), "download ks");
     sync_stream("keyswitch");
+    unpad_rows(out, res.data(), (size_t)count, (size_t)dp.n + 1, (size_t)dp.ct_stride);
+    stats.keyswitches += (uint64_t)count;
+}
+
+void Engine::run_keyswitch_matrix(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out) {
+    ENGINE_DEVICE_SCOPE();
+    wait_flight();
+    const DevParams &dp = key->dp;
+    if (count <= 0) api_fail("keyswitch_matrix: no rows");
+    if (!ks_matrix_shape_ok(dp.k * dp.N, dp.ks_t, dp.ks_basebit)) api_fail("keyswitch_matrix: the key's shape has no matrix form");
+    const std::vector<int32_t> padded = pad_rows(u, (size_t)count, (size_t)dp.k * dp.N + 1, (size_t)dp.u_stride);
+    const int32_t *u_buf = scratch_upload(S_EXTRACT, padded.data(), padded.size(), "upload u");
+    std::vector<KsDesc> ks(count);
+    for (int c = 0; c < count; ++c) ks[c] = KsDesc{c, -1, 0, c};
+    const KsDesc *dks = scratch_upload(S_KS, ks.data(), ks.size(), "upload ks");
+    int32_t *dpool = scratch_as<int32_t>(S_RAW_POOL, (size_t)count * dp.ct_stride);
+    if (!ensure_ks_planes(key)) api_fail("keyswitch_matrix: out of device memory for the byte-plane image of the key");
+    ++ks_matrix_stats.ks_matrix_launches;
+    if (!launch_keyswitch_matrix(stream_, dp, key->ks_planes, u_buf, dks, count, dpool)) fatal("keyswitch_matrix: no kernel for this shape");
+    hip_check(hipGetLastError(), "keyswitch_matrix launch");
+    std::vector<int32_t> res((size_t)count * dp.ct_stride);
+    d2h(res.data(), dpool, res.size(), "download ks");
+    sync_stream("keyswitch_matrix");
     unpad_rows(out, res.data(), (size_t)count, (size_t)dp.n + 1, (size_t)dp.ct_stride);
     stats.keyswitches += (uint64_t)count;
 }

@@ -18,6 +18,7 @@
 #include "unpack.hpp"
 #include "cmux.hpp"
 #include "expand.hpp"
+#include "ks_matrix.hpp"
 #include "../../include/tfhe_hip.h"
 
 // Device image of one cloud key: NTT image of BK, compact KSK, twiddles.
@@ -30,6 +31,10 @@ struct DeviceKeyImage {
     int32_t *ksk = nullptr;
     uint32_t *tw = nullptr;
     size_t bk_img_bytes = 0, ksk_bytes = 0, tw_bytes = 0;        // what the three hold (recoverable_alloc's accounting)
+    // the byte-plane image of the KSK for the matrix key switch (ks_matrix.hip), made before the first flush with a launch
+    // wide enough to use it (Engine::ensure_ks_planes); null until then, and for good on a card without room for it
+    mutable uint8_t *ks_planes = nullptr;
+    mutable size_t ks_planes_bytes = 0;
 };
 
 namespace tfhe_hip {
@@ -179,6 +184,12 @@ public:
                            const Torus32 *polys, int npolys, const int32_t *spec_index, const ExtractSpec *specs, int nspecs,
                            int out_rows, Torus32 *u_out, Torus32 *acc_out, const char *name);
     void run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out);
+    // raw test path of the matrix key switch alone (ks_matrix.hip), whatever the width; ApiError where the key's shape has no
+    // matrix form or the card no room for its image
+    void run_keyswitch_matrix(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out);
+    // the key's byte-plane image, made on first need; false (and nothing held, nothing reported) if the shape has no matrix
+    // form or the device has no room: the key then goes on with the other forms
+    bool ensure_ks_planes(const DeviceKeyImage *key);
     void run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const Torus32 *tp, Torus32 *res, int count);
     // Packing key switch (pack.hpp).  upload_pack_image: the NTT image of a packing key's raw rows [n][t][2][N] under the
     // twiddles of `key` (a cloud key of the same ring); device memory exhausted: ApiError, nothing held.  *bytes: what the
@@ -229,12 +240,13 @@ public:
 
     TfheHipStats stats{};
     TfheHipExpandStats expand_stats{};  // the device expansions of seed-compressed cloud keys (tfhe_hip_get_expand_stats)
+    TfheHipKsMatrixStats ks_matrix_stats{};  // launches of the matrix key switch (tfhe_hip_get_ks_matrix_stats)
     TfheHipSeededStats seeded_stats{};  // device-expanded packing keys and seeded unpacks (tfhe_hip_get_seeded_stats)
     bool kernel_timing = false;
     // the launch rules' tunings (launch_plan.hpp; written by ensure_init()'s environment reads and tfhe_hip_set_tuning)
     LaunchTunings tunings;
     // stream == nullptr: the engine's stream; presized (a flush's levels): the partial sums were sized by the caller
-    // and must not grow (checked)
+    // and must not grow (checked), and the plan may be the matrix form where the key holds its image
     void launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
                    hipStream_t stream = nullptr, bool presized = false);
     // the launch plan (launch_plan.hpp plan_br) of `count` rotations under this key's parameter set on this card;

@@ -51,6 +51,12 @@ struct LaunchTunings {
     // VGPR index mode (kernels.hip keyswitch_index_kernel): 56 ms per match; 0 = the LDS-strip form (keyswitch_strip_kernel,
     // tiles of 16): 105 ms -- plain HIP source, the form to fall back on.  Tuning "ks_index", env TFHE_HIP_KS_INDEX
     int ks_index = 1;
+    // 1 (default) = a flush's key-switch launches of at least ks_matrix_min gates run as an int8 matrix product on the matrix
+    // cores (ks_matrix.hip keyswitch_matrix_kernel) where the tiled kernels would have run and the key holds its byte-plane
+    // image: one pass over the image serves 64 gates, no partial sums.  Unpack, pack and the raw entries keep the forms
+    // above.  Tunings "ks_matrix" and "ks_matrix_min"
+    int ks_matrix = 1;
+    int ks_matrix_min = 512;
 };
 
 // form_ok[form][tables]: the kernel form's magnitude bounds hold for the gadget (l, Bgbit) at ring size N (br_forms.hpp)
@@ -117,7 +123,11 @@ inline int ks_threads(const KsShape &p) { return ((p.ct_stride / 4 + 63) / 64) *
 // The kernel a launch of `count` gates runs (kernels.hip): one workgroup per (gate, range) [keyswitch_kernel], or a tile of
 // gates per workgroup with the staged rows in LDS strips [keyswitch_strip_kernel, tile 16] or in pinned registers
 // [keyswitch_index_kernel, tile 16 / 24 / 32].  tile = gates per workgroup, 0 for the per-gate kernel.
-enum KsForm { KS_FORM_PERGATE = 0, KS_FORM_STRIP = 1, KS_FORM_INDEX = 2 };
+// KS_FORM_MATRIX [ks_matrix.hip keyswitch_matrix_kernel]: the whole launch in one grid, tile = its 64 gates a workgroup.
+enum KsForm { KS_FORM_PERGATE = 0, KS_FORM_STRIP = 1, KS_FORM_INDEX = 2, KS_FORM_MATRIX = 3 };
+constexpr int KS_MATRIX_TILE = 64;
+// the matrix form's waves take whole blocks of 32 coefficients each: 8 waves a workgroup (ks_matrix.hpp)
+constexpr int KS_MATRIX_SPAN = 256;
 struct KsPlan { int form; int tile; };
 
 inline int ks_tile_size(const LaunchTunings &t) { return (t.ks_tile > 16 && !t.ks_index) ? 16 : t.ks_tile; }
@@ -127,12 +137,15 @@ inline int ks_tile_size(const LaunchTunings &t) { return (t.ks_tile > 16 && !t.k
 // (n in 256 .. 511, in 512 .. 767, and n = 1024); they take wide launches, from two tiles on.
 // Everything else -- every other accepted (ks_t, ks_basebit), row widths of 64 and 256 threads -- is the per-gate kernel,
 // planned as such: the narrow-launch split rule, one chunk.
-inline KsPlan plan_ks(const LaunchTunings &t, int count, const KsShape &p) {
+// matrix: the caller is a flush (engine.cpp run_level) and the key holds its byte-plane image -- only then may the plan be
+// the matrix form; every other caller plans what it always did.
+inline KsPlan plan_ks(const LaunchTunings &t, int count, const KsShape &p, bool matrix = false) {
     const int tile = ks_tile_size(t), threads = ks_threads(p);
     const bool tiled = (tile == 16 || tile == 24 || tile == 32) && count >= 2 * tile && p.ks_t == 8 && p.ks_basebit == 2 &&
                        t.ks_max_splits > 1 && (p.nin + t.ks_max_splits - 1) / t.ks_max_splits <= 64 &&
                        (threads == 128 || threads == 192 || threads == 320);
     if (!tiled) return KsPlan{KS_FORM_PERGATE, 0};
+    if (matrix && t.ks_matrix && count >= t.ks_matrix_min && p.nin % KS_MATRIX_SPAN == 0) return KsPlan{KS_FORM_MATRIX, KS_MATRIX_TILE};
     return KsPlan{t.ks_index ? KS_FORM_INDEX : KS_FORM_STRIP, tile};
 }
 
@@ -227,7 +240,7 @@ struct LevelCostEntry {
     int n, N, k, l, Bgbit, ks_t, ks_basebit;      // the parameter set ...
     int cus;                                      // ... the card ...
     int br_variant, br8_max_rotations, br_tail8, br_digit_table, ks_tile, ks_index, ks_max_splits, ks_target_blocks,
-        ks_split_ties;                            // ... and the tunings it was measured under
+        ks_split_ties, ks_matrix, ks_matrix_min;  // ... and the tunings it was measured under
     int count;
     const int32_t *width;
     const double *us;
@@ -252,7 +265,8 @@ inline LevelCost level_cost_table(const LevelCostSet &p, int cus, const LaunchTu
             e.ks_basebit == p.ks_basebit && e.cus == cus && e.br_variant == t.br_variant &&
             e.br8_max_rotations == t.br8_max_rotations && e.br_tail8 == t.br_tail8 && e.br_digit_table == t.br_digit_table &&
             e.ks_tile == t.ks_tile && e.ks_index == t.ks_index && e.ks_max_splits == t.ks_max_splits &&
-            e.ks_target_blocks == t.ks_target_blocks && e.ks_split_ties == t.ks_split_ties)
+            e.ks_target_blocks == t.ks_target_blocks && e.ks_split_ties == t.ks_split_ties && e.ks_matrix == t.ks_matrix &&
+            e.ks_matrix_min == t.ks_matrix_min)
             return LevelCost{e.width, e.us, e.count, 2 * e.cus};
     }
     return LevelCost{};
@@ -265,8 +279,9 @@ inline double level_cost_us(int width, const LevelCostSet &p, int cus, const Lau
 }
 
 // the largest key-switch partial-sum buffer a launch of `count` gates uses
-inline size_t ks_partial_bytes(const LaunchTunings &t, int cu_count, int count, const KsShape &p) {
+inline size_t ks_partial_bytes(const LaunchTunings &t, int cu_count, int count, const KsShape &p, bool matrix = false) {
     size_t most = 0;
+    if (plan_ks(t, count, p, matrix).form == KS_FORM_MATRIX) return 0;      // straight to the pool slots
     const int chunk = ks_tiled(t, count, p) ? KS_CHUNK : count;
     for (int done = 0; done < count; done += chunk) {
         const int cnt = std::min(chunk, count - done), splits = ks_splits(t, cu_count, cnt, p);

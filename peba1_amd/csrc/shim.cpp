@@ -882,6 +882,12 @@ int tfhe_hip_set_tuning(const char *name, int64_t value) {
         Engine::get().tunings.ks_max_splits = (int)value;
         return 0;
     }
+    if (name && std::strcmp(name, "ks_matrix") == 0) { Engine::get().tunings.ks_matrix = value != 0; return 0; }
+    if (name && std::strcmp(name, "ks_matrix_min") == 0) {
+        if (value < 1 || value > (1 << 30)) { set_error("ks_matrix_min must be in [1, 2^30]"); return -1; }
+        Engine::get().tunings.ks_matrix_min = (int)value;
+        return 0;
+    }
     if (name && std::strcmp(name, "br_digit_table") == 0) { Engine::get().tunings.br_digit_table = (int)value; return 0; }
     if (name && std::strcmp(name, "br8_max_rotations") == 0) { Engine::get().tunings.br8_max_rotations = (int)value; return 0; }
     if (name && std::strcmp(name, "br_tail8") == 0) { Engine::get().tunings.br_tail8 = (int)value; return 0; }
@@ -902,12 +908,17 @@ void tfhe_hip_reset_stats(void) {
     auto g = recorder_lock();
     Engine::get().stats = TfheHipStats{};
     Engine::get().expand_stats = TfheHipExpandStats{};
+    Engine::get().ks_matrix_stats = TfheHipKsMatrixStats{};
     Engine::get().seeded_stats = TfheHipSeededStats{};
     Engine::get().seeded_lwe_stats = TfheHipSeededLweStats{};
 }
 void tfhe_hip_get_seeded_stats(TfheHipSeededStats *out) {
     auto g = recorder_lock();
     if (out) *out = Engine::get().seeded_stats;
+}
+void tfhe_hip_get_ks_matrix_stats(TfheHipKsMatrixStats *out) {
+    auto g = recorder_lock();
+    if (out) *out = Engine::get().ks_matrix_stats;
 }
 void tfhe_hip_get_expand_stats(TfheHipExpandStats *out) {
     auto g = recorder_lock();

@@ -381,6 +381,33 @@ int tfhe_hip_test_ks_plan_form(int32_t n, int32_t N, int32_t k, int32_t ks_t, in
     return 0;
 }
 
+// the entry above with the two tunings of the matrix form (tunings7: the five above, then ks_matrix and ks_matrix_min) and
+// has_image: the key holds its byte-plane image, as a flush finds it -- the plan Engine::run_level runs
+int tfhe_hip_test_ks_plan_form2(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings7,
+                                int32_t has_image, int32_t cu_count, int32_t count, int64_t *out7) {
+    if (!tunings7 || !out7 || cu_count < 1 || count < 1) { set_error("test_ks_plan: bad arguments"); return -1; }
+    LaunchTunings t;
+    t.ks_target_blocks = tunings7[0]; t.ks_max_splits = tunings7[1]; t.ks_split_ties = tunings7[2];
+    t.ks_tile = tunings7[3]; t.ks_index = tunings7[4]; t.ks_matrix = tunings7[5]; t.ks_matrix_min = tunings7[6];
+    Params p{};
+    p.n = n;
+    const KsShape shape{k * N, ks_t, ks_basebit, p.ct_stride()};
+    const KsPlan plan = plan_ks(t, count, shape, has_image != 0);
+    if (plan.form != KS_FORM_MATRIX) return tfhe_hip_test_ks_plan_form(n, N, k, ks_t, ks_basebit, tunings7, cu_count, count, out7);
+    out7[0] = 1; out7[1] = plan.tile; out7[2] = count;   // one launch, one range, no partial sums
+    out7[3] = 1; out7[4] = 1;
+    out7[5] = (int64_t)ks_partial_bytes(t, cu_count, count, shape, true);
+    out7[6] = plan.form;
+    return 0;
+}
+
+// the byte planes of `count` words (ks_matrix.hpp ks_byte_planes): planes4[w][p]
+int tfhe_hip_test_ks_byte_planes(const uint32_t *words, int32_t count, int8_t *planes4) {
+    if (!words || !planes4 || count < 0) { set_error("test_ks_byte_planes: bad arguments"); return -1; }
+    for (int32_t i = 0; i < count; ++i) ks_byte_planes(words[i], planes4 + 4 * (size_t)i);
+    return 0;
+}
+
 // the first six words of the entry above: callers of this one provide room for six
 int tfhe_hip_test_ks_plan(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
                           int32_t cu_count, int32_t count, int64_t *out6) {
@@ -451,6 +478,16 @@ int tfhe_hip_kernel_keyswitch(const TFheGateBootstrappingCloudKeySet *bk, const 
     pool_of_key(bk);
     Engine::get().run_keyswitch(bk->bk->dev, u, count, out);
     return 0;
+}
+
+int tfhe_hip_kernel_keyswitch_matrix(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *u, int32_t count, Torus32 *out) {
+    if (!bk || !bk->bk || !u || !out) { set_error("keyswitch_matrix: null argument"); return -1; }
+    auto g = recorder_lock();
+    return guarded_rc([&] {
+        pool_of_key(bk);
+        Engine::get().run_keyswitch_matrix(bk->bk->dev, u, count, out);
+        return 0;
+    });
 }
 
 }  // extern "C"

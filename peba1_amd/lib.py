@@ -84,6 +84,11 @@ class ExpandStats(C.Structure):
     _fields_ = [("expanded_keys", C.c_uint64), ("expand_launches", C.c_uint64)]
 
 
+class KsMatrixStats(C.Structure):
+    """TfheHipKsMatrixStats: launches of the matrix key switch (tfhe_hip_get_ks_matrix_stats)."""
+    _fields_ = [("ks_matrix_launches", C.c_uint64)]
+
+
 class SeededStats(C.Structure):
     """TfheHipSeededStats: device-expanded packing keys and seeded unpacks (tfhe_hip_get_seeded_stats)."""
     _fields_ = [("expanded_packing_keys", C.c_uint64), ("packing_expand_launches", C.c_uint64),
@@ -228,6 +233,9 @@ SIGNATURES = {
     "tfhe_hip_kernel_lut_bootstrap_multi_woks": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P, C.c_int32, I32P, I32P, C.c_int32,
                                                            I32P, I32P]),
     "tfhe_hip_kernel_keyswitch": (C.c_int, [CK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_kernel_keyswitch_matrix": (C.c_int, [CK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_test_ks_plan_form2": (C.c_int, [C.c_int32] * 5 + [I32P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "tfhe_hip_test_ks_byte_planes": (C.c_int, [U32P, C.c_int32, C.POINTER(C.c_int8)]),
     "tfhe_hip_new_packing_key": (C.c_void_p, [SK, C.c_int32, C.c_int32]),
     "tfhe_hip_new_packing_key_seeded": (C.c_void_p, [SK, C.c_int32, C.c_int32, C.c_uint64]),
     "tfhe_hip_new_packing_key_from_words": (C.c_void_p, [PS, C.c_int32, C.c_int32, I32P]),
@@ -264,6 +272,7 @@ SIGNATURES = {
     "tfhe_hip_test_key_image": (C.c_int64, [CK, C.c_int, I32P, C.c_int64]),
     "tfhe_hip_last_expand_ms": (C.c_double, []),
     "tfhe_hip_get_expand_stats": (None, [C.POINTER(ExpandStats)]),
+    "tfhe_hip_get_ks_matrix_stats": (None, [C.POINTER(KsMatrixStats)]),
     "tfhe_hip_get_seeded_stats": (None, [C.POINTER(SeededStats)]),
     "tfhe_hip_new_compressed_packing_key": (C.c_void_p, [SK, C.c_int32, C.c_int32]),
     "tfhe_hip_new_compressed_packing_key_seeded": (C.c_void_p, [SK, C.c_int32, C.c_int32, C.c_uint64, U32P]),

@@ -32,6 +32,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "level_cost_P128.json"))
     ap.add_argument("--repeats", type=int, default=5)
+    # the library's defaults; other values measure a table for those tunings (the threshold sweep of the matrix key switch)
+    ap.add_argument("--ks-matrix", type=int, default=1)
+    ap.add_argument("--ks-matrix-min", type=int, default=512)
+    ap.add_argument("--widths", type=int, nargs="*", help="these widths only (a sweep; not a table for the build)")
     args = ap.parse_args()
 
     import numpy as np
@@ -42,12 +46,14 @@ def main():
     L = lib.load()
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     L.tfhe_hip_set_kernel_timing(1)
+    api.set_tuning("ks_matrix", args.ks_matrix)
+    api.set_tuning("ks_matrix_min", args.ks_matrix_min)
     was = api.get_deferred()
     api.set_deferred(False)
     pq = api.ParameterSet(128)
     kq = api.SecretKeySet(pq, 0x5EBA2)
     rng = np.random.default_rng(13)
-    widths = width_grid(cus)
+    widths = sorted(args.widths) if args.widths else width_grid(cus)
     G = max(widths)
     xa, xb = rng.integers(0, 2, G), rng.integers(0, 2, G)
     wa = api.CiphertextArray(pq, G).encrypt(xa, kq).words()
@@ -83,7 +89,8 @@ def main():
                    "ks_basebit": pq.ks_basebit},
         "cus": cus,
         "tunings": {"br_variant": -1, "br8_max_rotations": 1 << 30, "br_tail8": 1, "br_digit_table": 1, "ks_tile": 16,
-                    "ks_index": 1, "ks_max_splits": 48, "ks_target_blocks": 32768, "ks_split_ties": 0},
+                    "ks_index": 1, "ks_max_splits": 48, "ks_target_blocks": 32768, "ks_split_ties": 0,
+                    "ks_matrix": args.ks_matrix, "ks_matrix_min": args.ks_matrix_min},
         "kernels_sha16": kernels_sha16(),
         "shader_clock_ghz": round(0.1 * cycles / ticks, 3) if ticks else None,
         "repeats": args.repeats,
