@@ -799,40 +799,31 @@ void Engine::launch_br(const DeviceKeyImage *key, const BrPlan &plan, const BrLa
     else launch_blind_rotate8(stream, dp, key->key, a.pool, a.rots + head, plan.tail, a.u_buf, nullptr);
 }
 
-static KsShape ks_shape(const DevParams &dp) { return KsShape{dp.k * dp.N, dp.ks_t, dp.ks_basebit, dp.ct_stride}; }
+KsLaunchPlan Engine::plan_ks_launch(const DeviceKeyImage *key, int count, bool has_image) const {
+    const DevParams &dp = key->dp;
+    return tfhe_hip::plan_ks_launch(tunings, cu_count_, count, KsShape{dp.k * dp.N, dp.ks_t, dp.ks_basebit, dp.ct_stride}, has_image);
+}
 
-// the key switches of `count` gates by the rule of launch_plan.hpp: the form plan_ks names, in chunks of at most KS_CHUNK
-// gates when tiled, each in ks_splits coefficient ranges
-void Engine::launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
-                       hipStream_t stream, bool presized) {
+void Engine::launch_ks(const DeviceKeyImage *key, const KsLaunchPlan &plan, const int32_t *u_buf, const KsDesc *descs,
+                       int32_t *pool, hipStream_t stream) {
     ENGINE_DEVICE_SCOPE();
-    if (count <= 0) return;
     if (!stream) stream = stream_;
     const DevParams &dp = key->dp;
-    const KsShape shape = ks_shape(dp);
-    const bool matrix = presized && key->ks_planes != nullptr;       // flushes only (run_level)
-    const size_t bytes = ks_partial_bytes(tunings, cu_count_, count, shape, matrix);
-    if (presized && bytes > (scratch_size_.size() > S_KS_PARTIAL ? scratch_size_[S_KS_PARTIAL] : 0))
-        fatal("launch_ks: the key-switch partial sums were not sized by execute()");
-    int32_t *partial = bytes ? static_cast<int32_t *>(scratch(S_KS_PARTIAL, bytes)) : nullptr;
-    // the form is the plan's (launch_plan.hpp plan_ks), decided once for the whole launch; the counters say what ran
-    const KsPlan plan = plan_ks(tunings, count, shape, matrix);
-    if (plan.form == KS_FORM_MATRIX) {
-        // one launch whatever the width: nothing to chunk without partial sums
-        ++ks_matrix_stats.ks_matrix_launches;
-        if (!launch_keyswitch_matrix(stream, dp, key->ks_planes, u_buf, descs, count, pool))
-            fatal("launch_ks: the planned matrix key switch has no kernel for this shape");
-        return;
-    }
-    const int chunk = plan.form != KS_FORM_PERGATE ? KS_CHUNK : count;
-    for (int done = 0; done < count; done += chunk) {
-        const int cnt = std::min(chunk, count - done), splits = ks_splits(tunings, cu_count_, cnt, shape);
-        // (the last chunk of a tiled launch may be narrower than two tiles: it runs what the rule gives its own width)
-        const KsPlan part = done ? plan_ks(tunings, cnt, shape) : plan;
+    // the buffer as whoever built the plan sized it from partial_bytes, before anything was enqueued: it never grows here
+    int32_t *partial = static_cast<int32_t *>(scratch(S_KS_PARTIAL, 0));
+    if (plan.partial_bytes > scratch_size_[S_KS_PARTIAL]) fatal("launch_ks: the plan's partial sums do not fit their buffer");
+    for (int i = 0, done = 0; i < plan.parts; done += plan.gates(i++)) {
+        const KsPlan &part = plan.part(i);                   // (the counters say what ran, part by part)
+        if (part.form == KS_FORM_MATRIX) {
+            ++ks_matrix_stats.ks_matrix_launches;
+            if (!key->ks_planes || !launch_keyswitch_matrix(stream, dp, key->ks_planes, u_buf, descs + done, plan.gates(i), pool))
+                fatal("launch_ks: the planned matrix key switch has no kernel for this shape");
+            continue;
+        }
         ++(part.form == KS_FORM_INDEX ? stats.ks_index_launches : part.form == KS_FORM_STRIP ? stats.ks_strip_launches
                                                                                              : stats.ks_pergate_launches);
-        if (!launch_keyswitch(stream, dp, key->key, u_buf, descs + done, cnt, pool, splits, splits > 1 ? partial : nullptr,
-                              part.tile, part.form != KS_FORM_STRIP))
+        if (!launch_keyswitch(stream, dp, key->key, u_buf, descs + done, plan.gates(i), pool, part.splits,
+                              part.splits > 1 ? partial : nullptr, part.tile, part.form != KS_FORM_STRIP))
             fatal("launch_ks: the planned key-switch form has no kernel instantiation");
     }
 }
@@ -872,19 +863,22 @@ Engine::FlushBuffers Engine::prepare_flush(const std::vector<const DeviceKeyImag
         }
         fb.lins = scratch_as<LinDesc>(S_LINS, plan.lins.size());
     }
-    // extract buffer, sized for the widest level, and key-switch partial sums, sized by the split rule launch_ks applies
+    // extract buffer, sized for the widest level, and the key-switch plans that run_level runs, with their partial sums
     fb.u_buf = scratch_as<int32_t>(S_EXTRACT, (size_t)(std::max(plan.max_rots, plan.max_extracts) + 1) * key->dp.u_stride);
     size_t partial = 0;
     const std::vector<int32_t> &ks_shares = nkeys == 1 ? plan.ks_off : plan.ks_koff;   // one key-switch launch per (level, key)
+    flight_ks_plans_.clear();
     for (size_t sg = 0; sg + 1 < ks_shares.size(); ++sg) {
         // a launch wide enough for the matrix form: its key gets the byte-plane image now, before anything is enqueued (a
-        // card without room for it: the launch runs the tiled form and is sized as such)
+        // card without room for it: the launch is planned again without, and runs and is sized as that plan says)
         const DeviceKeyImage *share_key = keys[nkeys == 1 ? 0 : sg % (size_t)nkeys];
         const int width = ks_shares[sg + 1] - ks_shares[sg];
-        const bool matrix = plan_ks(tunings, width, ks_shape(key->dp), true).form == KS_FORM_MATRIX && ensure_ks_planes(share_key);
-        partial = std::max(partial, ks_partial_bytes(tunings, cu_count_, width, ks_shape(key->dp), matrix));
+        KsLaunchPlan kp = plan_ks_launch(share_key, width, true);
+        if (kp.full.form == KS_FORM_MATRIX && !ensure_ks_planes(share_key)) kp = plan_ks_launch(share_key, width, false);
+        partial = std::max(partial, kp.partial_bytes);
+        flight_ks_plans_.push_back(kp);
     }
-    if (partial) (void)scratch(S_KS_PARTIAL, partial);
+    (void)scratch(S_KS_PARTIAL, partial);
     // the key table and the key index of every rotation
     if (nkeys > 1) {
         fb.keys = scratch_as<DevKey>(S_KEYS, (size_t)nkeys);
@@ -980,12 +974,12 @@ void Engine::run_level(const std::vector<const DeviceKeyImage *> &keys, SlotPool
         if (t.wide8 || t.tail) { ++stats.br8_launches; stats.br8_rotations += (uint64_t)(t.wide8 ? nrot : t.tail); }
     }
     if (kernel_timing) { t.e1 = next_timing_event(); hip_check(hipEventRecord(t.e1, stream_), "event"); }
-    // the key-switch kernels are single-key: one launch per key with a share of the level
+    // the key-switch kernels are single-key: one launch per key with a share of the level, by the plan prepare_flush made of
+    // it (an empty share: a plan of no parts)
     for (int k = 0; k < nkeys && nks; ++k) {
         const size_t sg = gg * (size_t)nkeys + (size_t)k;
         const int32_t first = nkeys == 1 ? plan.ks_off[gg] : plan.ks_koff[sg];
-        const int n = nkeys == 1 ? nks : plan.ks_koff[sg + 1] - first;
-        if (n) launch_ks(keys[(size_t)k], fb.u_buf, fb.ks + first, n, pool->data(), stream_, true);
+        launch_ks(keys[(size_t)k], flight_ks_plans_[sg], fb.u_buf, fb.ks + first, pool->data(), stream_);
     }
     if (kernel_timing) {
         t.e2 = next_timing_event(); hip_check(hipEventRecord(t.e2, stream_), "event"); flight_timed_.push_back(t);
@@ -1161,23 +1155,31 @@ void Engine::run_raw_rotations(const DeviceKeyImage *key, const Torus32 *lin, in
     stats.blind_rotates += (uint64_t)count;
 }
 
-void Engine::run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out) {
-    ENGINE_DEVICE_SCOPE();
-    wait_flight();
+// the raw key-switch entries: plan.count rows up, row c into row c of a private pool by `plan`, the rows down.  name: the
+// entry, for error messages
+void Engine::run_keyswitch_rows(const DeviceKeyImage *key, const KsLaunchPlan &plan, const Torus32 *u, Torus32 *out, const char *name) {
     const DevParams &dp = key->dp;
+    const int count = plan.count;
     const std::vector<int32_t> padded = pad_rows(u, (size_t)count, (size_t)dp.k * dp.N + 1, (size_t)dp.u_stride);
     const int32_t *u_buf = scratch_upload(S_EXTRACT, padded.data(), padded.size(), "upload u");
     std::vector<KsDesc> ks(count);
     for (int c = 0; c < count; ++c) ks[c] = KsDesc{c, -1, 0, c};
     const KsDesc *dks = scratch_upload(S_KS, ks.data(), ks.size(), "upload ks");
     int32_t *dpool = scratch_as<int32_t>(S_RAW_POOL, (size_t)count * dp.ct_stride);
-    launch_ks(key, u_buf, dks, count, dpool);
-    hip_check(hipGetLastError(), "keyswitch launch");
+    (void)scratch(S_KS_PARTIAL, plan.partial_bytes);
+    launch_ks(key, plan, u_buf, dks, dpool);
+    hip_check(hipGetLastError(), (std::string(name) + " launch").c_str());
     std::vector<int32_t> res((size_t)count * dp.ct_stride);
     d2h(res.data(), dpool, res.size(), "download ks");
-    sync_stream("keyswitch");
+    sync_stream(name);
     unpad_rows(out, res.data(), (size_t)count, (size_t)dp.n + 1, (size_t)dp.ct_stride);
     stats.keyswitches += (uint64_t)count;
+}
+
+void Engine::run_keyswitch(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out) {
+    ENGINE_DEVICE_SCOPE();
+    wait_flight();
+    run_keyswitch_rows(key, plan_ks_launch(key, count, false), u, out, "keyswitch");
 }
 
 void Engine::run_keyswitch_matrix(const DeviceKeyImage *key, const Torus32 *u, int count, Torus32 *out) {
@@ -1186,21 +1188,8 @@ void Engine::run_keyswitch_matrix(const DeviceKeyImage *key, const Torus32 *u, i
     const DevParams &dp = key->dp;
     if (count <= 0) api_fail("keyswitch_matrix: no rows");
     if (!ks_matrix_shape_ok(dp.k * dp.N, dp.ks_t, dp.ks_basebit)) api_fail("keyswitch_matrix: the key's shape has no matrix form");
-    const std::vector<int32_t> padded = pad_rows(u, (size_t)count, (size_t)dp.k * dp.N + 1, (size_t)dp.u_stride);
-    const int32_t *u_buf = scratch_upload(S_EXTRACT, padded.data(), padded.size(), "upload u");
-    std::vector<KsDesc> ks(count);
-    for (int c = 0; c < count; ++c) ks[c] = KsDesc{c, -1, 0, c};
-    const KsDesc *dks = scratch_upload(S_KS, ks.data(), ks.size(), "upload ks");
-    int32_t *dpool = scratch_as<int32_t>(S_RAW_POOL, (size_t)count * dp.ct_stride);
     if (!ensure_ks_planes(key)) api_fail("keyswitch_matrix: out of device memory for the byte-plane image of the key");
-    ++ks_matrix_stats.ks_matrix_launches;
-    if (!launch_keyswitch_matrix(stream_, dp, key->ks_planes, u_buf, dks, count, dpool)) fatal("keyswitch_matrix: no kernel for this shape");
-    hip_check(hipGetLastError(), "keyswitch_matrix launch");
-    std::vector<int32_t> res((size_t)count * dp.ct_stride);
-    d2h(res.data(), dpool, res.size(), "download ks");
-    sync_stream("keyswitch_matrix");
-    unpad_rows(out, res.data(), (size_t)count, (size_t)dp.n + 1, (size_t)dp.ct_stride);
-    stats.keyswitches += (uint64_t)count;
+    run_keyswitch_rows(key, ks_matrix_plan(count), u, out, "keyswitch_matrix");
 }
 
 double Engine::run_wg_times(const DeviceKeyImage *key, int width, unsigned long long *wg_times) {
@@ -1493,18 +1482,15 @@ void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, in
     const DevParams &dp = key->dp;
     const size_t ring_count = (size_t)nring * (seeded ? RING_SEED_WORDS + dp.N : 2 * dp.N), uw = (size_t)dp.k * dp.N + 1;
     const int widest = std::min(count, UNPACK_CHUNK);
-    // every buffer first (scratch() may throw: nothing has been enqueued then).  The partial sums of the key switches are
-    // sized for the widest chunk and for the last one, which may be cut into more ranges
+    // every buffer first (scratch() may throw: nothing has been enqueued then).  The key switches run by two plans, the
+    // widest chunk's and the last one's (which may be cut into more ranges); the partial sums are sized for both
     int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_UNPACK_RING, ring_count);
     int32_t *dindex = scratch_as<int32_t>(S_UNPACK_INDEX, (size_t)count);
     KsDesc *dks = u_out ? nullptr : scratch_as<KsDesc>(S_UNPACK_KS, (size_t)count);
     int32_t *u_buf = scratch_as<int32_t>(S_UNPACK_EXTRACT, (size_t)widest * dp.u_stride);
-    if (!u_out) {
-        const int last = count - (count - 1) / UNPACK_CHUNK * UNPACK_CHUNK;
-        const size_t partial = std::max(ks_partial_bytes(tunings, cu_count_, widest, ks_shape(dp)),
-                                        ks_partial_bytes(tunings, cu_count_, last, ks_shape(dp)));
-        if (partial) (void)scratch(S_KS_PARTIAL, partial);
-    }
+    const KsLaunchPlan ks_wide = plan_ks_launch(key, widest, false);
+    const KsLaunchPlan ks_last = plan_ks_launch(key, count - (count - 1) / UNPACK_CHUNK * UNPACK_CHUNK, false);
+    if (!u_out) (void)scratch(S_KS_PARTIAL, std::max(ks_wide.partial_bytes, ks_last.partial_bytes));
     h2d_staged(dindex, index, (size_t)count, "upload unpack index");
     if (!u_out) {
         std::vector<KsDesc> hks((size_t)count);
@@ -1529,7 +1515,7 @@ void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, in
             unpad_rows(u_out + (size_t)done * uw, rows.data(), (size_t)cnt, uw, (size_t)dp.u_stride);
         } else {
             // (the next chunk's extract is ordered behind this key switch: one stream, one buffer)
-            launch_ks(key, u_buf, dks + done, cnt, pool->data());
+            launch_ks(key, cnt == widest ? ks_wide : ks_last, u_buf, dks + done, pool->data());
             hip_check(hipGetLastError(), "unpack keyswitch launch");
         }
     }

@@ -245,10 +245,13 @@ public:
     bool kernel_timing = false;
     // the launch rules' tunings (launch_plan.hpp; written by ensure_init()'s environment reads and tfhe_hip_set_tuning)
     LaunchTunings tunings;
-    // stream == nullptr: the engine's stream; presized (a flush's levels): the partial sums were sized by the caller
-    // and must not grow (checked), and the plan may be the matrix form where the key holds its image
-    void launch_ks(const DeviceKeyImage *key, const int32_t *u_buf, const KsDesc *descs, int count, int32_t *pool,
-                   hipStream_t stream = nullptr, bool presized = false);
+    // the launch plan (launch_plan.hpp plan_ks_launch) of the key switches of `count` gates under this key's parameter set
+    // on this card; has_image: the key holds its byte-plane image and the caller is a flush
+    KsLaunchPlan plan_ks_launch(const DeviceKeyImage *key, int count, bool has_image) const;
+    // runs a plan of plan_ks_launch on its plan.count descriptors: one kernel launch per part; decides nothing.  The caller
+    // sized S_KS_PARTIAL from plan.partial_bytes before it enqueued anything (checked); stream == nullptr: the engine's
+    void launch_ks(const DeviceKeyImage *key, const KsLaunchPlan &plan, const int32_t *u_buf, const KsDesc *descs, int32_t *pool,
+                   hipStream_t stream = nullptr);
     // the launch plan (launch_plan.hpp plan_br) of `count` rotations under this key's parameter set on this card;
     // acc_dump: the raw accumulators are read back
     BrPlan plan_br_launch(const DeviceKeyImage *key, int count, bool acc_dump) const;
@@ -293,7 +296,7 @@ private:
         S_NEGA_TP = S_RAW_POOL, S_NEGA_IP = S_RAW_ACC,     // run_negacyclic's two operands share those buffers
         S_NEGA_IMG,       // raw, run_negacyclic: the transform of tp
         S_NEGA_RES,       // raw, run_negacyclic: the products
-        S_KS_PARTIAL,     // flush (launch_ks checks that it never grows under one), run_keyswitch, run_unpack: partial sums of split key switches
+        S_KS_PARTIAL,     // flush, run_keyswitch, run_unpack: partial sums of split key switches, sized from the plans launch_ks runs
         S_KEYS,           // flush of several keys: the key table
         S_ROT_KEYS,       // flush of several keys: the key index of every rotation
         S_RAW_LUTS,       // raw rotations: the call's own test polynomials
@@ -371,6 +374,7 @@ private:
     std::vector<size_t> scratch_size_;
     // behind everything else, so that the members the flush path reads keep their places
     size_t last_expand_words_ = 0;                      // rows * stride of the last raw LWE expand launch (read_expand_slots)
+    void run_keyswitch_rows(const DeviceKeyImage *key, const KsLaunchPlan &plan, const Torus32 *u, Torus32 *out, const char *name);
 public:
     TfheHipSeededLweStats seeded_lwe_stats{};           // seeded imports and their expand launches (tfhe_hip_get_seeded_lwe_stats)
 
@@ -396,6 +400,8 @@ public:
 private:
     hipEvent_t select_e0_ = nullptr, select_e1_ = nullptr;
     bool select_timed_ = false;
+    // (behind everything else, as above) prepare_flush's key-switch plan of every (level, key) share of flight_plan_
+    std::vector<KsLaunchPlan> flight_ks_plans_;
 };
 
 }  // namespace tfhe_hip

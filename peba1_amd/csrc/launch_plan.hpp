@@ -1,9 +1,9 @@
 // launch_plan.hpp -- which kernel launches a level of a flush turns into (host side, no device code, no runtime calls).
 //
-// Pure functions of the tunings, the CU count, the parameter set and the level's width: the engine (engine.cpp
-// execute / launch_br / launch_ks) runs what they return, and tests/test_launch_plan_cpu.py drives them through
-// tfhe_hip_test_br_plan / tfhe_hip_test_ks_plan on a machine without a GPU.  Not a file the kernels are built from
-// (peba1_amd/kernel_id.py).
+// Pure functions of the tunings, the CU count, the parameter set and the level's width (plan_br -> BrPlan, plan_ks_launch ->
+// KsLaunchPlan): the engine (engine.cpp prepare_flush / launch_br / launch_ks) builds a plan once per launch and runs it, and
+// tests/test_launch_plan_cpu.py reads the same plans through tfhe_hip_test_br_plan / tfhe_hip_test_ks_plan* on a machine
+// without a GPU.  Not a file the kernels are built from (peba1_amd/kernel_id.py).
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -15,8 +15,9 @@
 namespace tfhe_hip {
 
 // Tunings of the launch rules (tfhe_hip_set_tuning: br_variant, br8_max_rotations, br_tail8, br_digit_table, ks_tile,
-// ks_index and ks_max_splits; beside them the recorder's reuse_gates / eliminate_dead / balance_levels / fold_constants / batch_keys, and
-// the engine's sync_deadline_ms).  HISTORY.md lists the forms and knobs removed in round 6.
+// ks_index, ks_max_splits, ks_matrix and ks_matrix_min; beside them the recorder's reuse_gates / eliminate_dead /
+// balance_levels / fold_constants / batch_keys, and the engine's sync_deadline_ms).  The ks_* ones are read by plan_ks and
+// ks_splits alone, both called by plan_ks_launch alone.  HISTORY.md lists the forms and knobs removed in round 6.
 struct LaunchTunings {
     // which form of the blind-rotate kernel runs wide launches (kernels.hip): -1 = the fastest measured for the ring size
     // (N = 1024: 4-wave; N = 2048: split), 0 = 4-wave (N = 1024), 2 = split (8 waves, half transforms), 4 = 2-wave
@@ -109,10 +110,10 @@ inline BrPlan plan_br(const bool form_ok[BR_FORM_COUNT][3], int N, int l, const 
     return BrPlan{form, tables, split ? tail : 0};
 }
 
-// The key-switch launch rule, one place for launch_ks, for execute()'s sizing of the partial sums and for the test entry: a
-// launch of `count` gates runs in chunks of at most KS_CHUNK gates when tiled (bounds the partial-sum buffer: 0.66 GB at
-// P128), each chunk of cnt gates in ks_splits(cnt) coefficient ranges.  Tiles of 24 or 32 gates exist in the index form only
-// (kernels.hip keyswitch_index_kernel); tile 0 = per-gate kernel only.
+// The key-switch launch rule (plan_ks_launch below: what the engine sizes the partial sums from, what launch_ks runs and what
+// the test entries return): a launch of `count` gates runs in chunks of at most KS_CHUNK gates when tiled (bounds the
+// partial-sum buffer: 0.66 GB at P128), each chunk of cnt gates in ks_splits(cnt) coefficient ranges.  Tiles of 24 or 32
+// gates exist in the index form only (kernels.hip keyswitch_index_kernel); tile 0 = per-gate kernel only.
 constexpr int KS_CHUNK = 8192;
 // what the rule reads of a parameter set: nin = k N input coefficients, the key-switch digits, words per ciphertext slot
 struct KsShape { int nin, ks_t, ks_basebit, ct_stride; };
@@ -128,18 +129,19 @@ enum KsForm { KS_FORM_PERGATE = 0, KS_FORM_STRIP = 1, KS_FORM_INDEX = 2, KS_FORM
 constexpr int KS_MATRIX_TILE = 64;
 // the matrix form's waves take whole blocks of 32 coefficients each: 8 waves a workgroup (ks_matrix.hpp)
 constexpr int KS_MATRIX_SPAN = 256;
-struct KsPlan { int form; int tile; };
+// splits: the coefficient ranges (partial sums per range where more than one); filled in by plan_ks_launch
+struct KsPlan { int form; int tile; int splits = 1; };
 
 inline int ks_tile_size(const LaunchTunings &t) { return (t.ks_tile > 16 && !t.ks_index) ? 16 : t.ks_tile; }
 
-// The whole decision (launch_keyswitch decides nothing).  The tiled kernels are built for the key switch of the built-in
-// sets only -- t = 8, base 4 -- for ranges of at most 64 input coefficients and for workgroups of 128, 192 or 320 threads
+// The form of a launch or chunk of `count` gates, decided here alone (launch_keyswitch decides nothing).  The tiled kernels
+// are built for the key switch of the built-in sets only -- t = 8, base 4 -- for ranges of at most 64 input coefficients and for workgroups of 128, 192 or 320 threads
 // (n in 256 .. 511, in 512 .. 767, and n = 1024); they take wide launches, from two tiles on.
 // Everything else -- every other accepted (ks_t, ks_basebit), row widths of 64 and 256 threads -- is the per-gate kernel,
 // planned as such: the narrow-launch split rule, one chunk.
-// matrix: the caller is a flush (engine.cpp run_level) and the key holds its byte-plane image -- only then may the plan be
-// the matrix form; every other caller plans what it always did.
-inline KsPlan plan_ks(const LaunchTunings &t, int count, const KsShape &p, bool matrix = false) {
+// matrix: the caller is a flush (engine.cpp prepare_flush) and the key holds its byte-plane image -- only then may the plan
+// be the matrix form; unpack and the raw entries pass false, and so does every chunk of a launch that is not the matrix form.
+inline KsPlan plan_ks(const LaunchTunings &t, int count, const KsShape &p, bool matrix) {
     const int tile = ks_tile_size(t), threads = ks_threads(p);
     const bool tiled = (tile == 16 || tile == 24 || tile == 32) && count >= 2 * tile && p.ks_t == 8 && p.ks_basebit == 2 &&
                        t.ks_max_splits > 1 && (p.nin + t.ks_max_splits - 1) / t.ks_max_splits <= 64 &&
@@ -149,12 +151,9 @@ inline KsPlan plan_ks(const LaunchTunings &t, int count, const KsShape &p, bool 
     return KsPlan{t.ks_index ? KS_FORM_INDEX : KS_FORM_STRIP, tile};
 }
 
-// the tiled kernels: wide launches, ranges of at most 64 input coefficients
-inline bool ks_tiled(const LaunchTunings &t, int count, const KsShape &p) { return plan_ks(t, count, p).form != KS_FORM_PERGATE; }
-
-inline int ks_splits(const LaunchTunings &t, int cu_count, int cnt, const KsShape &p) {
+// the coefficient ranges of `cnt` gates in the form `plan` (a tiled form or the per-gate kernel; the matrix form has none)
+inline int ks_splits(const LaunchTunings &t, int cu_count, int cnt, const KsShape &p, const KsPlan &plan) {
     int splits = 1;
-    const KsPlan plan = plan_ks(t, cnt, p);
     if (plan.form != KS_FORM_PERGATE) {
         // the number of coefficient ranges is free between nin/64 and ks_max_splits: take the
         // one whose grid (tiles x ranges) fills whole rounds of the workgroups the chip holds,
@@ -183,6 +182,43 @@ inline int ks_splits(const LaunchTunings &t, int cu_count, int cnt, const KsShap
         while (splits < t.ks_max_splits && cnt * splits * 2 <= t.ks_target_blocks) splits *= 2;
     }
     return splits;
+}
+
+// Everything a key-switch launch of `count` gates turns into: `parts` kernel launches, each but the last of `chunk` gates as
+// `full` says, the last of the remaining gates as `last` says (one part: the same), and the partial sums the widest of them
+// needs.  The matrix form is one part whatever the width, with no partial sums.
+struct KsLaunchPlan {
+    int count = 0, chunk = 0, parts = 0;
+    KsPlan full{}, last{};
+    size_t partial_bytes = 0;
+    const KsPlan &part(int i) const { return i + 1 < parts ? full : last; }
+    int gates(int i) const { return i + 1 < parts ? chunk : count - (parts - 1) * chunk; }
+};
+
+// the matrix form of `count` gates (planned below; forced by the raw entry tfhe_hip_kernel_keyswitch_matrix)
+inline KsLaunchPlan ks_matrix_plan(int count) {
+    const KsPlan part{KS_FORM_MATRIX, KS_MATRIX_TILE, 1};
+    return KsLaunchPlan{count, count, 1, part, part, 0};
+}
+
+// has_image: plan_ks's `matrix`.  A tiled launch runs in chunks of KS_CHUNK gates; its last chunk is planned by its own width
+// and may be narrower than two tiles -- the per-gate kernel.
+inline KsLaunchPlan plan_ks_launch(const LaunchTunings &t, int cu_count, int count, const KsShape &p, bool has_image) {
+    if (count <= 0) return KsLaunchPlan{};
+    auto part_of = [&](int cnt, bool image) {
+        KsPlan k = plan_ks(t, cnt, p, image);
+        if (k.form != KS_FORM_MATRIX) k.splits = ks_splits(t, cu_count, cnt, p, k);
+        return k;
+    };
+    const KsPlan whole = part_of(count, has_image);
+    if (whole.form == KS_FORM_MATRIX) return ks_matrix_plan(count);
+    KsLaunchPlan plan{count, whole.form != KS_FORM_PERGATE ? KS_CHUNK : count};
+    plan.parts = (count + plan.chunk - 1) / plan.chunk;
+    plan.full = plan.parts > 1 ? part_of(plan.chunk, false) : whole;
+    plan.last = plan.parts > 1 ? part_of(plan.gates(plan.parts - 1), false) : whole;
+    auto bytes = [&](int i) { return plan.part(i).splits > 1 ? (size_t)plan.gates(i) * plan.part(i).splits * p.ct_stride * 4 : 0; };
+    plan.partial_bytes = std::max(bytes(0), bytes(plan.parts - 1));
+    return plan;
 }
 
 // What a level of a flush costs, by its width in rotations: MEASURED microseconds of the blind-rotate launches plan_br
@@ -276,18 +312,6 @@ inline LevelCost level_cost_table(const LevelCostSet &p, int cus, const LaunchTu
 inline double level_cost_us(int width, const LevelCostSet &p, int cus, const LaunchTunings &t) {
     const LevelCost c = level_cost_table(p, cus, t);
     return c.n ? level_cost_at(c, width) : -1.0;
-}
-
-// the largest key-switch partial-sum buffer a launch of `count` gates uses
-inline size_t ks_partial_bytes(const LaunchTunings &t, int cu_count, int count, const KsShape &p, bool matrix = false) {
-    size_t most = 0;
-    if (plan_ks(t, count, p, matrix).form == KS_FORM_MATRIX) return 0;      // straight to the pool slots
-    const int chunk = ks_tiled(t, count, p) ? KS_CHUNK : count;
-    for (int done = 0; done < count; done += chunk) {
-        const int cnt = std::min(chunk, count - done), splits = ks_splits(t, cu_count, cnt, p);
-        if (splits > 1) most = std::max(most, (size_t)cnt * splits * p.ct_stride * 4);
-    }
-    return most;
 }
 
 }  // namespace tfhe_hip

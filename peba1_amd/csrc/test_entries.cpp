@@ -359,46 +359,34 @@ int tfhe_hip_test_br_plan(int32_t N, int32_t l, int32_t Bgbit, const int32_t *tu
     return 0;
 }
 
-int tfhe_hip_test_ks_plan_form(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
-                               int32_t cu_count, int32_t count, int64_t *out7) {
-    if (!tunings5 || !out7 || cu_count < 1 || count < 1) { set_error("test_ks_plan: bad arguments"); return -1; }
+// The first `nout` of the seven words of the key-switch launch plan (launch_plan.hpp plan_ks_launch, what Engine::launch_ks
+// runs): tiled, tile, chunk, ranges of a full chunk, ranges of the last chunk, partial-sum bytes, form.  tunings: the first
+// `ntunings` of ks_target_blocks, ks_max_splits, ks_split_ties, ks_tile, ks_index, ks_matrix, ks_matrix_min
+static int test_ks_plan_words(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings, int ntunings,
+                              bool has_image, int32_t cu_count, int32_t count, int64_t *out, int nout) {
+    if (!tunings || !out || cu_count < 1 || count < 1) { set_error("test_ks_plan: bad arguments"); return -1; }
     LaunchTunings t;
-    t.ks_target_blocks = tunings5[0]; t.ks_max_splits = tunings5[1]; t.ks_split_ties = tunings5[2];
-    t.ks_tile = tunings5[3]; t.ks_index = tunings5[4];
+    int *const fields[7] = {&t.ks_target_blocks, &t.ks_max_splits, &t.ks_split_ties, &t.ks_tile, &t.ks_index, &t.ks_matrix, &t.ks_matrix_min};
+    for (int i = 0; i < ntunings; ++i) *fields[i] = tunings[i];
     Params p{};
     p.n = n;
-    const KsShape shape{k * N, ks_t, ks_basebit, p.ct_stride()};
-    const KsPlan plan = plan_ks(t, count, shape);             // what Engine::launch_ks runs
-    const bool tiled = plan.form != KS_FORM_PERGATE;
-    const int chunk = tiled ? KS_CHUNK : count;               // launch_ks's chunks: all of `chunk` gates but the last
-    out7[0] = tiled ? 1 : 0;
-    out7[1] = plan.tile;
-    out7[2] = chunk;
-    out7[3] = ks_splits(t, cu_count, std::min(chunk, count), shape);
-    out7[4] = ks_splits(t, cu_count, count - (count - 1) / chunk * chunk, shape);
-    out7[5] = (int64_t)ks_partial_bytes(t, cu_count, count, shape);
-    out7[6] = plan.form;
+    const KsLaunchPlan plan = plan_ks_launch(t, cu_count, count, KsShape{k * N, ks_t, ks_basebit, p.ct_stride()}, has_image);
+    const int64_t words[7] = {plan.full.form != KS_FORM_PERGATE, plan.full.tile, plan.chunk, plan.full.splits, plan.last.splits,
+                              (int64_t)plan.partial_bytes, plan.full.form};
+    std::copy(words, words + nout, out);
     return 0;
 }
 
-// the entry above with the two tunings of the matrix form (tunings7: the five above, then ks_matrix and ks_matrix_min) and
-// has_image: the key holds its byte-plane image, as a flush finds it -- the plan Engine::run_level runs
+int tfhe_hip_test_ks_plan_form(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
+                               int32_t cu_count, int32_t count, int64_t *out7) {
+    return test_ks_plan_words(n, N, k, ks_t, ks_basebit, tunings5, 5, false, cu_count, count, out7, 7);
+}
+
+// the entry above with the two tunings of the matrix form and has_image: the key holds its byte-plane image, as a flush finds
+// it -- the plan Engine::prepare_flush makes and run_level runs
 int tfhe_hip_test_ks_plan_form2(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings7,
                                 int32_t has_image, int32_t cu_count, int32_t count, int64_t *out7) {
-    if (!tunings7 || !out7 || cu_count < 1 || count < 1) { set_error("test_ks_plan: bad arguments"); return -1; }
-    LaunchTunings t;
-    t.ks_target_blocks = tunings7[0]; t.ks_max_splits = tunings7[1]; t.ks_split_ties = tunings7[2];
-    t.ks_tile = tunings7[3]; t.ks_index = tunings7[4]; t.ks_matrix = tunings7[5]; t.ks_matrix_min = tunings7[6];
-    Params p{};
-    p.n = n;
-    const KsShape shape{k * N, ks_t, ks_basebit, p.ct_stride()};
-    const KsPlan plan = plan_ks(t, count, shape, has_image != 0);
-    if (plan.form != KS_FORM_MATRIX) return tfhe_hip_test_ks_plan_form(n, N, k, ks_t, ks_basebit, tunings7, cu_count, count, out7);
-    out7[0] = 1; out7[1] = plan.tile; out7[2] = count;   // one launch, one range, no partial sums
-    out7[3] = 1; out7[4] = 1;
-    out7[5] = (int64_t)ks_partial_bytes(t, cu_count, count, shape, true);
-    out7[6] = plan.form;
-    return 0;
+    return test_ks_plan_words(n, N, k, ks_t, ks_basebit, tunings7, 7, has_image != 0, cu_count, count, out7, 7);
 }
 
 // the byte planes of `count` words (ks_matrix.hpp ks_byte_planes): planes4[w][p]
@@ -411,11 +399,7 @@ int tfhe_hip_test_ks_byte_planes(const uint32_t *words, int32_t count, int8_t *p
 // the first six words of the entry above: callers of this one provide room for six
 int tfhe_hip_test_ks_plan(int32_t n, int32_t N, int32_t k, int32_t ks_t, int32_t ks_basebit, const int32_t *tunings5,
                           int32_t cu_count, int32_t count, int64_t *out6) {
-    int64_t out7[7];
-    if (!out6) { set_error("test_ks_plan: bad arguments"); return -1; }
-    const int rc = tfhe_hip_test_ks_plan_form(n, N, k, ks_t, ks_basebit, tunings5, cu_count, count, out7);
-    if (rc == 0) std::copy(out7, out7 + 6, out6);
-    return rc;
+    return test_ks_plan_words(n, N, k, ks_t, ks_basebit, tunings5, 5, false, cu_count, count, out6, 6);
 }
 
 int tfhe_hip_test_wg_times(const TFheGateBootstrappingCloudKeySet *bk, int32_t width, uint64_t *times4, double *launch_ms) {

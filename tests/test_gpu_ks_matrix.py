@@ -130,3 +130,48 @@ def test_a_recorded_level_takes_the_form_and_gives_the_oracles_words(oracle):
         api.set_tuning("ks_matrix_min", 512)
         ks.close()
         oks.close()
+
+
+def test_a_level_is_sized_and_run_by_one_plan_when_the_image_cannot_be_made(oracle):
+    """Engine::prepare_flush plans a wide share for the matrix form, finds no room for the key's byte-plane image (an allocation
+    cap of one byte: ensure_ks_planes' handled refusal), plans it again without the image, sizes the partial sums from THAT
+    plan and hands it to run_level: the flush succeeds in the index form with the oracle's words.  With the cap lifted the
+    same level makes the image and runs the matrix form, same words.  A fresh P80 key (no image yet), 72 gates: a matrix tile
+    of 64 and one of 8; the first flush, matrix form off, makes every scratch buffer so that the capped one needs none."""
+    from peba1_amd import api, lib
+    L = lib.load()
+    seed, G = 0x4D5A, 72
+    pp = api.ParameterSet(80)
+    ks = api.SecretKeySet(pp, seed, device=True)
+    oks = oracle.KeySet(oracle.params("P80"), seed)
+    deferred = api.get_deferred()
+    try:
+        rng = oracle.Rng(seed + 1)
+        ca, cb = oks.encrypt(rng, np.arange(G) % 2), oks.encrypt(rng, (np.arange(G) // 2) % 2)
+        want = oks.gate_batch("NAND", ca, cb, nthreads=16)
+        a, b = api.CiphertextArray(pp, G).set_words(ca), api.CiphertextArray(pp, G).set_words(cb)
+        results = [api.CiphertextArray(pp, G) for _ in range(3)]                   # (before the cap: their slots exist)
+        counters = lambda: np.array([api.stats()[f] for f in K.KS_COUNTERS] + [api.ks_matrix_stats()["ks_matrix_launches"]])
+        api.set_deferred(True)
+        api.flush()
+        words = []
+        # (ks_matrix, allocation cap) -> launches per gate / strip / index / matrix
+        for r, (on, cap, delta) in zip(results, ((0, 0, (0, 0, 1, 0)), (1, 1, (0, 0, 1, 0)), (1, 0, (0, 0, 0, 1)))):
+            api.set_tuning("ks_matrix", on)
+            api.set_tuning("ks_matrix_min", 64)
+            L.tfhe_hip_test_set_alloc_cap(cap)
+            before = counters()
+            api.gate_batch("NAND", r, a, b, ks)
+            assert api.flush() >= 0, api.last_error()
+            L.tfhe_hip_test_set_alloc_cap(0)
+            assert tuple(counters() - before) == delta, ("ks_matrix", on, "cap", cap, counters() - before)
+            words.append(r.words())
+        for w in words:
+            assert (w == want).all(), np.flatnonzero((w != want).any(axis=1))[:8]
+    finally:
+        L.tfhe_hip_test_set_alloc_cap(0)
+        api.set_deferred(deferred)
+        api.set_tuning("ks_matrix", 1)
+        api.set_tuning("ks_matrix_min", 512)
+        ks.close()
+        oks.close()

@@ -271,3 +271,54 @@ def test_ks_partial_bytes_cover_every_chunk(pname):
                 if tiled:
                     assert tile in (16, 24, 32) and count >= 2 * tile, where
                     assert max(2, -(-k * N // 64)) <= first <= dict(KS_DEFAULTS, **tunings)["ks_max_splits"], where
+
+
+# ---- one planner: the words before and after, and what unpack sizes from ---------------------------------------------------
+def ks_plan_form2(shape, t7, has_image, cu_count, count):
+    out = (C.c_int64 * 7)()
+    assert lib().tfhe_hip_test_ks_plan_form2(*shape, (C.c_int32 * 7)(*t7), has_image, cu_count, count, out) == 0
+    return list(out)
+
+
+def test_ks_launch_plan_returns_the_recorded_words_of_the_commit_before():
+    """tests/golden/ks_plan_parent.json: the seven words of tfhe_hip_test_ks_plan_form2 over the grid the file states (5 shapes
+    x 10 tunings x has_image 0 / 1 x 3 CU counts x 19 widths: 1, the two-tile thresholds 32 / 48 / 64, the matrix thresholds
+    64 / 512 and the chunk boundaries 8192 / 16384 with their neighbours, 20000), recorded from the library of the commit
+    before plan_ks_launch replaced plan_ks / ks_tiled / ks_splits / ks_partial_bytes and their callers' chunk loops.  Word
+    for word.  (The file holds each distinct row of seven words once and, per grid point, its index.)"""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(__file__), "golden", "ks_plan_parent.json")) as f:
+        doc = json.load(f)
+    g = doc["grid"]
+    assert len(g["shapes"]) == 5 and len(g["tunings"]) == 10 and len(g["widths"]) == 19
+    lines = iter(doc["rows"])
+    checked = 0
+    for sname, shape in g["shapes"].items():
+        for tn in g["tunings"]:
+            t7 = [tn.get(name, default) for name, default in zip(g["tuning_names"], g["tuning_defaults"])]
+            for img in g["has_image"]:
+                for cu in g["cu_counts"]:
+                    line = next(lines)
+                    assert len(line) == len(g["widths"])
+                    for width, index in zip(g["widths"], line):
+                        want, got = doc["distinct"][index], ks_plan_form2(shape, t7, img, cu, width)
+                        assert got == want, ("first differing row", sname, tn, "has_image", img, "CUs", cu, "width", width,
+                                             "recorded", want, "now", got)
+                        checked += 1
+    assert next(lines, None) is None and checked == 5700
+
+
+@pytest.mark.parametrize("pname", sorted(KS_SETS))
+def test_unpack_partial_sums_hold_the_full_chunk_and_the_last_one(pname):
+    """Engine::run_unpack runs the key switches of UNPACK_CHUNK + 33 samples by two plans, one of a full chunk (8,192 gates)
+    and one of 33 (which may be cut into more ranges), and sizes the partial sums once from the larger of the two: each
+    plan's bytes hold gates x ranges x ct_stride words of its own width."""
+    UNPACK_CHUNK = 8192                                          # unpack.hpp
+    shape = KS_SETS[pname]
+    stride = (shape[0] + 1 + 3) & ~3
+    for tunings in ({}, {"ks_tile": 0}, {"ks_index": 0}, {"ks_max_splits": 32}):
+        for gates in (UNPACK_CHUNK, 33):
+            tiled, tile, chunk, first, last, nbytes = ks_plan(shape, tunings, 256, gates)
+            assert chunk >= gates and first == last > 1, (pname, tunings, gates)      # one part each
+            assert nbytes >= gates * first * stride * 4, (pname, tunings, gates, nbytes)
