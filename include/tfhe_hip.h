@@ -1015,6 +1015,49 @@ int tfhe_hip_kernel_ring_cmux(const TfheHipSelector *selector, int32_t bit_index
  * arguments (Bgbit outside 1..12, l Bgbit > 32). */
 int tfhe_hip_test_select_bounds(int32_t N, int32_t l, int32_t Bgbit);
 
+/* ---- private lookup in packed galleries: the tree picks a ring sample, the low index bits rotate it ----
+ * The second half of a LUT evaluation with TGSW inputs.  The select's unit is a whole ring sample; an entry here is `width`
+ * coefficients of one, so a gallery of 128-bit templates rests at 1 KB per template at N = 1024 instead of 8 KB, and a table
+ * of single coefficients can be looked up at all: a public function of d encrypted bits, evaluated without a bootstrap.
+ * No new key material: the selector is the select's.  k = 1.
+ *
+ * Monomial multiple of a ring sample c, 0 <= r < N, on both polynomials u:
+ *     (X^(-r) c)[u][j] =  c[u][j + r]          for j + r < N
+ *                        -c[u][j + r - N]      otherwise, wrapping mod 2^32
+ * -- the convention of a test polynomial's rotation in the blind rotation.
+ * Rotation step.  ROT(G, r, c) = CMUX(G, X^(-r) c, c) = c + G (.) (X^(-r) c - c): the CMUX, the external product and the offset
+ * decomposition are exactly those of the private selection above, the word-wise wrapping difference taken first.
+ * Lookup.  Entries of width w = 2^e coefficients, 1 <= w <= N.  S = N / w entries rest in one ring sample, s = log2 S; entry
+ * i sits on coefficients (i mod S) w .. + w - 1 of sample i / S; a gallery of M entries holds R = ceil(M / S) ring samples.
+ * The selector has d bits, bit 0 least significant, d >= s and 1 <= M <= 2^d.
+ *   1. The tree of the private selection over the R samples under bits s .. d - 1: level j uses G_(s+j), a sample at or
+ *      past R is the all-zero sample.
+ *   2. For t = 0 .. s - 1 in ascending order: c <- ROT(G_t, w 2^t, c).
+ *   3. The result is one ring sample; its coefficients 0 .. w - 1 carry the phase of entry i = sum_t bit_t 2^t.  The other
+ *      coefficients carry other entries of the same sample, rotated: they are not part of the result's meaning.
+ * w = N is word for word tfhe_hip_ring_select.  An index at or past M inside the last sample gives whatever the gallery
+ * holds there; an index in a sample at or past R gives noise near zero.
+ * Noise: at most (d - s) + s = d CMUX terms of the per-CMUX variance stated above (sigma <= 1.5e-4 each at P128) --
+ * COMPUTED, not measured: a rotation step is a CMUX whose d1 is a monomial multiple of its d0.
+ *
+ * tfhe_hip_ring_lookup: ring_words holds the R ring samples of (k+1) N words; out_ring_words receives the (k+1) N words of
+ * step 3 -- tfhe_hip_unpack_samples[_device] with indices 0 .. width - 1 opens the entry.  The device form reads a gallery
+ * resident on the card and leaves the result there (both 16-byte aligned; the result must not overlap the gallery).  Both
+ * are enqueued on tfhe_hip_stream() like the select's two forms: one kernel launch per tree level, then one per rotation
+ * bit, d in all; the rotation steps go between two scratch samples sized before anything is enqueued, the last launch
+ * writes a device destination directly.  The call names no ciphertext slot: recorded operations stay recorded, nothing is
+ * flushed, and a flush in flight is not waited for.  tfhe_hip_last_select_ms covers a lookup too.
+ * Every argument is checked before the device is looked at.  Return 0, or -1 with tfhe_hip_last_error() set and the call
+ * without effect: a null pointer, a deleted selector, width not a power of two in 1 .. N, d < s, M < 1 or M > 2^d,
+ * misaligned device words, device memory exhausted. */
+int tfhe_hip_ring_lookup(const TfheHipSelector *selector, const Torus32 *ring_words, int32_t M, int32_t width, Torus32 *out_ring_words);
+int tfhe_hip_ring_lookup_device(const TfheHipSelector *selector, const void *device_ring_words, int32_t M, int32_t width,
+                                void *device_out);
+/* raw test entry: `count` independent rotation steps (1 <= count <= 65,536) under bit bit_index of the selector in ONE
+ * launch, out_words[c] = ROT(G_bit, rot, d0_words[c]), 1 <= rot < N, (k+1) N host words each */
+int tfhe_hip_kernel_ring_cmux_rotate(const TfheHipSelector *selector, int32_t bit_index, int32_t rot, const Torus32 *d0_words,
+                                     int32_t count, Torus32 *out_words);
+
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through
  * the device NTT (two 27-bit primes + CRT); |ip| must be < 2^12 */

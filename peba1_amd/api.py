@@ -1005,8 +1005,64 @@ def kernel_ring_cmux(selector, bit, d1, d0):
 
 
 def last_select_ms():
-    """The launches of the last ring_select between two stream events, in ms; -1 unless kernel timing was on."""
+    """The launches of the last ring_select or ring_lookup between two stream events, in ms; -1 unless kernel timing was on."""
     return _l.load().tfhe_hip_last_select_ms()
+
+
+def lookup_samples(params, M, width):
+    """R = ceil(M / S): the ring samples a packed gallery of M entries of `width` coefficients holds, S = N / width each."""
+    N = params.N
+    if width < 1 or width > N or width & (width - 1):
+        raise ValueError("width must be a power of two in 1..%d" % N)
+    return -(-int(M) // (N // width))
+
+
+def ring_lookup(selector, gallery, M, width, device=False):
+    """The packed lookup (tfhe_hip_ring_lookup): `gallery` holds M entries of `width` = 2^e coefficients, S = N / width per
+    ring sample, entry i on coefficients (i mod S) width .. of sample i / S.  The tree of `selector` over the samples under
+    its high bits, then one rotation step per low bit: coefficients 0 .. width - 1 of the (k+1) N result words carry the
+    phase of entry index = sum_j bit_j 2^j.  width = N is ring_select.  Host and device forms as for ring_select."""
+    p = selector.params
+    sw = (p.k + 1) * p.N
+    R = lookup_samples(p, M, width)
+    L = _l.load()
+    if device:
+        import torch
+        if gallery.dtype != torch.int32 or not gallery.is_contiguous() or gallery.numel() != R * sw:
+            raise ValueError("a device gallery of %d entries is a contiguous int32 tensor of %d (k+1) N words" % (M, R))
+        out = torch.empty(sw, dtype=torch.int32, device=gallery.device)
+        rc = L.tfhe_hip_ring_lookup_device(selector.ptr, C.c_void_p(gallery.data_ptr()), int(M), int(width), C.c_void_p(out.data_ptr()))
+    else:
+        g = _ring_words(gallery, p)
+        if g.shape[0] != R:
+            raise ValueError("a gallery of %d entries of width %d holds %d ring samples" % (M, width, R))
+        out = np.zeros(sw, dtype=np.int32)
+        rc = L.tfhe_hip_ring_lookup(selector.ptr, _i32p(g), int(M), int(width), _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def kernel_ring_cmux_rotate(selector, bit, rot, d0):
+    """ROT(G_bit, rot, d0[c]) = CMUX(G_bit, X^(-rot) d0[c], d0[c]) of caller-supplied ring samples [count][(k+1) N] in one
+    launch (tfhe_hip_kernel_ring_cmux_rotate)."""
+    a = _ring_words(d0, selector.params)
+    out = np.zeros_like(a)
+    if _l.load().tfhe_hip_kernel_ring_cmux_rotate(selector.ptr, int(bit), int(rot), _i32p(a), a.shape[0], _i32p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def ring_trivial(params, values):
+    """The noiseless ring sample (0, values): a zero mask and the 1..N torus words `values` as the body (zero behind them).
+    It decrypts to `values` under every key, so a gallery of such samples is a PUBLIC table, and ring_lookup over it
+    evaluates a public function of the selector's encrypted bits."""
+    v = np.ascontiguousarray([_wrap32(x) for x in np.asarray(values).reshape(-1)], dtype=np.int32)
+    if not 1 <= v.size <= params.N:
+        raise ValueError("a ring sample of this parameter set carries 1..%d words" % params.N)
+    out = np.zeros((params.k + 1) * params.N, dtype=np.int32)
+    out[params.k * params.N:params.k * params.N + v.size] = v
+    return out
 
 
 def _lwe_record(words):

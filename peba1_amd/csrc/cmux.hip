@@ -8,6 +8,10 @@
 //                        reduction and inverse NTT per output polynomial; the residues go to LDS in natural order, wave q
 //                        then owns output polynomial q: it reads four consecutive coefficients of both primes, applies the
 //                        signed CRT, adds d0 and writes 16 bytes per lane and store.
+//   cmux_kernel<., true> the rotation step ROT(G, rot, d0) = CMUX(G, X^(-rot) d0, d0) of the packed lookup: the same kernel with
+//                        another operand load -- coefficient j of X^(-rot) d0 is d0[j + rot], negated past the wrap -- and
+//                        nothing else; d1 and n_d1 are not read.  Lanes read words of d0 other lanes' stores would hit:
+//                        launch_cmux refuses an output that overlaps d0.
 // No atomics, no global scratch; a CMUX reads nothing another CMUX of the launch writes.
 //
 // kernels.hip is not touched by this file; the few lines it keeps private (the per-prime context) are restated here.
@@ -38,7 +42,7 @@ __device__ __forceinline__ PrimeCtx cmux_ctx(int q, const uint32_t *tw, int n_ri
 // the most rows any accepted gadget has: the accumulators below take that many products (cmux.hpp MAC bound)
 static_assert(cmux_mac_ok(1024, 18) && cmux_mac_ok(2048, 16), "rows one accumulator takes");
 
-template <int LOGN>
+template <int LOGN, bool ROT>
 __global__ __launch_bounds__(128) void cmux_kernel(CmuxArgs a) {
     using NTT = WaveNtt<LOGN>;
     constexpr int N = NTT::N, REGS = NTT::REGS;
@@ -71,7 +75,14 @@ __global__ __launch_bounds__(128) void cmux_kernel(CmuxArgs a) {
 #pragma unroll
         for (int r = 0; r < REGS; ++r) {
             const int j = u * N + r * 64 + lane;
-            v[r] = (has_d1 ? (uint32_t)d1[j] : 0u) - (uint32_t)d0[j] + a.offset;
+            if constexpr (ROT) {
+                // (X^(-rot) d0)[j] = d0[j + rot], and -d0[j + rot - N] past the wrap (lut_coef's convention); 0 < rot < N
+                const int jr = r * 64 + lane + a.rot;
+                const uint32_t w = (uint32_t)d0[u * N + (jr & (N - 1))];
+                v[r] = (jr >= N ? 0u - w : w) - (uint32_t)d0[j] + a.offset;
+            } else {
+                v[r] = (has_d1 ? (uint32_t)d1[j] : 0u) - (uint32_t)d0[j] + a.offset;
+            }
         }
         for (int p = 0; p < a.l; ++p) {
             const int shift = 32 - (p + 1) * a.Bgbit;
@@ -130,10 +141,21 @@ __global__ __launch_bounds__(128) void cmux_kernel(CmuxArgs a) {
 bool launch_cmux(hipStream_t s, const CmuxArgs &a) {
     // the kernel is instantiated for k = 1; everything else it was bounded for is checked here once more
     if (cmux_gadget_error(a.N, 1, a.l, a.Bgbit) || a.bit < 0 || a.bit >= SELECT_MAX_BITS || a.count < 1 || a.n_d1 < 0 ||
-        a.n_d1 > a.count || a.stride < 2 * (int64_t)a.N || (a.stride & 3) || !a.d0 || (a.n_d1 && !a.d1) || !a.img || !a.tw || !a.out)
+        a.n_d1 > a.count || a.stride < 2 * (int64_t)a.N || (a.stride & 3) || !a.d0 || (a.n_d1 && !a.d1) || !a.img || !a.tw || !a.out ||
+        a.rot < 0 || a.rot >= a.N)
         return false;
-    if (a.N == 2048) hipLaunchKernelGGL(cmux_kernel<11>, dim3(a.count), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(cmux_kernel<10>, dim3(a.count), dim3(128), 0, s, a);
+    if (a.rot) {
+        // a rotation reads d0 across lanes: the words [d0, d0 + (count - 1) stride + 2N) and [out, out + count 2N) stay apart
+        const uintptr_t d0b = reinterpret_cast<uintptr_t>(a.d0), outb = reinterpret_cast<uintptr_t>(a.out);
+        const uintptr_t d0e = d0b + ((uintptr_t)(a.count - 1) * (uintptr_t)a.stride + 2 * (uintptr_t)a.N) * 4;
+        const uintptr_t oute = outb + (uintptr_t)a.count * 2 * (uintptr_t)a.N * 4;
+        if (d0b < oute && outb < d0e) return false;
+        if (a.N == 2048) hipLaunchKernelGGL((cmux_kernel<11, true>), dim3(a.count), dim3(128), 0, s, a);
+        else hipLaunchKernelGGL((cmux_kernel<10, true>), dim3(a.count), dim3(128), 0, s, a);
+        return true;
+    }
+    if (a.N == 2048) hipLaunchKernelGGL((cmux_kernel<11, false>), dim3(a.count), dim3(128), 0, s, a);
+    else hipLaunchKernelGGL((cmux_kernel<10, false>), dim3(a.count), dim3(128), 0, s, a);
     return true;
 }
 

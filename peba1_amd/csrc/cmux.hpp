@@ -78,10 +78,14 @@ inline const char *cmux_gadget_error(int N, int k, int l, int Bgbit) {
 // all-zero sample and is not read (a tree level whose last pair has no right entry).  A tree level over entries e[0..cnt)
 // is d0 = e, d1 = e + 2N, stride = 4N, count = ceil(cnt / 2), n_d1 = cnt / 2.  out overlaps neither input.
 // img: the rows' NTT image (launch_bk_transform of the selector's words [nbits][(k+1) l][2][N] with nw = 2).
+// rot != 0 (0 < rot < N): a launch of rotation steps of the packed lookup (include/tfhe_hip.h), CMUX c being
+// ROT(G, rot, d0[c]) = CMUX(G, X^(-rot) d0[c], d0[c]) with (X^(-rot) c)[u][j] = c[u][j + rot] for j + rot < N and
+// -c[u][j + rot - N] otherwise; d1 and n_d1 are not read, and out must not overlap d0 (the launcher refuses it).
 struct CmuxArgs {
     int32_t N, l, Bgbit, bit, count, n_d1;
     int64_t stride;
     uint32_t offset;                // sum_p (Bg/2) 2^(32 - p Bgbit): the decomposition's offset
+    int32_t rot;                    // 0: a CMUX of (d1, d0); else the rotation step's monomial power (in what was padding)
     const int32_t *d0, *d1;
     const uint32_t *img;
     const uint32_t *tw;             // the twiddle tables of the ring (engine.cpp make_twiddles)

@@ -1414,28 +1414,38 @@ void Engine::free_selector(SelectorImage *sel) {
     delete sel;
 }
 
-void Engine::run_select(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, bool ring_on_device,
+void Engine::run_lookup(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, int width, bool ring_on_device,
                         Torus32 *out, bool out_on_device) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
     const size_t sw = (size_t)(p.k + 1) * p.N;
-    // every buffer first (scratch() may throw: nothing has been enqueued then).  Level j holds ceil(M / 2^(j+1)) entries:
-    // the ping buffer is sized for level 0, the pong buffer for level 1
-    int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_SELECT_RING, (size_t)M * sw);
-    int32_t *lvl[2] = {nbits > 0 ? scratch_as<int32_t>(S_SELECT_A, (size_t)((M + 1) / 2) * sw) : nullptr,
-                       nbits > 1 ? scratch_as<int32_t>(S_SELECT_B, (size_t)((M + 3) / 4) * sw) : nullptr};
+    // S = N / width entries rest in one sample: R samples, nbits - s tree levels over them, then s rotations
+    int s = 0;
+    while ((width << s) < p.N) ++s;
+    const int R = (int)(((int64_t)M + (p.N / width) - 1) / (p.N / width)), levels = nbits - s;
+    // every buffer first (scratch() may throw: nothing has been enqueued then).  Level j holds ceil(R / 2^(j+1)) entries:
+    // the ping buffer is sized for level 0, the pong buffer for level 1; a rotation's one sample fits either
+    int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_SELECT_RING, (size_t)R * sw);
+    int32_t *lvl[2] = {nbits > 0 ? scratch_as<int32_t>(S_SELECT_A, (size_t)((R + 1) / 2) * sw) : nullptr,
+                       nbits > 1 ? scratch_as<int32_t>(S_SELECT_B, (size_t)((R + 3) / 4) * sw) : nullptr};
     if (kernel_timing && !select_e0_) {
         hip_check(hipEventCreate(&select_e0_), "select event");
         hip_check(hipEventCreate(&select_e1_), "select event");
     }
-    if (!ring_on_device) h2d_staged(dring, ring, (size_t)M * sw, "upload ring words");
+    if (!ring_on_device) h2d_staged(dring, ring, (size_t)R * sw, "upload ring words");
     const int32_t *src = ring_on_device ? ring : dring;
     if (kernel_timing) hip_check(hipEventRecord(select_e0_, stream_), "select event");
-    int cnt = M;
+    int cnt = R;
     for (int j = 0; j < nbits; ++j) {
         CmuxArgs a = cmux_args(sel, p);
-        a.bit = j; a.count = (cnt + 1) / 2; a.n_d1 = cnt / 2;
-        a.stride = (int64_t)2 * sw; a.d0 = src; a.d1 = src + sw;
+        if (j < levels) {
+            a.bit = s + j; a.count = (cnt + 1) / 2; a.n_d1 = cnt / 2;
+            a.stride = (int64_t)2 * sw; a.d0 = src; a.d1 = src + sw;
+        } else {
+            // c <- ROT(G_t, width 2^t, c), t = j - levels: the one sample the tree left (cnt = 1)
+            a.bit = j - levels; a.rot = width << (j - levels); a.count = 1; a.n_d1 = 0;
+            a.stride = (int64_t)sw; a.d0 = src;
+        }
         a.out = j == nbits - 1 && out_on_device ? out : lvl[j & 1];
         if (!launch_cmux(stream_, a)) api_fail("select: arguments outside what the CMUX kernel was built for");
         hip_check(hipGetLastError(), "cmux launch");
@@ -1449,16 +1459,17 @@ void Engine::run_select(const SelectorImage *sel, const Params &p, int nbits, co
     finish(!ring_on_device || !out_on_device, "select");
 }
 
-void Engine::run_cmux(const SelectorImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out) {
+void Engine::run_cmux(const SelectorImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out,
+                      int rot) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
     const size_t words = (size_t)count * (p.k + 1) * p.N;
-    int32_t *dd0 = scratch_as<int32_t>(S_SELECT_RING, words), *dd1 = scratch_as<int32_t>(S_CMUX_D1, words);
+    int32_t *dd0 = scratch_as<int32_t>(S_SELECT_RING, words), *dd1 = rot ? nullptr : scratch_as<int32_t>(S_CMUX_D1, words);
     int32_t *dout = scratch_as<int32_t>(S_SELECT_A, words);
     h2d(dd0, d0, words, "upload d0 words");
-    h2d(dd1, d1, words, "upload d1 words");
+    if (!rot) h2d(dd1, d1, words, "upload d1 words");
     CmuxArgs a = cmux_args(sel, p);
-    a.bit = bit; a.count = count; a.n_d1 = count;
+    a.bit = bit; a.count = count; a.n_d1 = rot ? 0 : count; a.rot = rot;
     a.stride = (int64_t)(p.k + 1) * p.N; a.d0 = dd0; a.d1 = dd1; a.out = dout;
     if (!launch_cmux(stream_, a)) api_fail("cmux: arguments outside what the kernel was built for");
     hip_check(hipGetLastError(), "cmux launch");

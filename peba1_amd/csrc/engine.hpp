@@ -316,8 +316,8 @@ private:
         S_LWE_SLOTS,      // run_lwe_expand: the slot list
         S_LWE_ROWS,       // raw, run_lwe_expand: the rows of one chunk in place of pool slots
         S_SELECT_RING,    // run_select: the ring words on their way from a host source; run_cmux: the d0 operands
-        S_SELECT_A,       // run_select: the tree levels 0, 2, ... (ping); run_cmux: the results
-        S_SELECT_B,       // run_select: the tree levels 1, 3, ... (pong)
+        S_SELECT_A,       // run_select / run_lookup: the launches 0, 2, ... (ping), tree levels then rotations; run_cmux: the results
+        S_SELECT_B,       // run_select / run_lookup: the launches 1, 3, ... (pong)
         S_CMUX_D1,        // raw, run_cmux: the d1 operands
     };
     void *scratch(Scratch idx, size_t bytes);
@@ -392,10 +392,21 @@ public:
     // buffer is sized before anything is enqueued: an ApiError (device memory exhausted) leaves nothing written.  A host
     // source or destination makes the call return with the words in place; the device form returns with the work enqueued.
     void run_select(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, bool ring_on_device,
+                    Torus32 *out, bool out_on_device) {
+        run_lookup(sel, p, nbits, ring, M, p.N, ring_on_device, out, out_on_device);
+    }
+    // The packed lookup (include/tfhe_hip.h): `ring` holds R = ceil(M / S) samples of S = N / width entries each.  The tree
+    // above over the R samples under bits s .. nbits - 1 (s = log2 S), then one rotation launch per bit t < s, rot =
+    // width 2^t, in the same two ping-pong buffers (each at least one sample), the last launch of all straight into a
+    // device destination.  width = N is run_select: no rotation, every launch and every buffer as before.  The caller has
+    // checked width, nbits >= s and M; everything else as for run_select.
+    void run_lookup(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, int width, bool ring_on_device,
                     Torus32 *out, bool out_on_device);
-    // raw test path: `count` independent CMUXes under bit `bit` in ONE launch, host words in and out
-    void run_cmux(const SelectorImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out);
-    // the levels of the last run_select between two stream events (kernel timing on; waits for the second), else -1
+    // raw test path: `count` independent CMUXes under bit `bit` in ONE launch, host words in and out; rot != 0: `count`
+    // rotation steps ROT(G_bit, rot, d0[c]) instead (d1 is not looked at)
+    void run_cmux(const SelectorImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out,
+                  int rot = 0);
+    // the launches of the last run_select / run_lookup between two stream events (kernel timing on; waits for the second), else -1
     double last_select_ms();
 private:
     hipEvent_t select_e0_ = nullptr, select_e1_ = nullptr;

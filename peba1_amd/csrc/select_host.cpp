@@ -1,5 +1,5 @@
 // select_host.cpp -- host side of the private selection: the TGSW encryption of index bits, the selector object and the
-// C ABI of the CMUX tree (include/tfhe_hip.h "private selection").  The negacyclic product is pack_host.cpp's.  No arithmetic
+// C ABI of the CMUX tree and of the packed lookup (include/tfhe_hip.h "private selection", "private lookup").  The negacyclic product is pack_host.cpp's.  No arithmetic
 // of the CMUX itself happens here (cmux.hip); encryption runs on the CPU like that of the ring samples.
 #include <string>
 #include <vector>
@@ -88,6 +88,30 @@ int select_impl(const char *who, const TfheHipSelector *sel, const Torus32 *ring
     return 0;
 }
 
+// the packed lookup: every argument before the device is looked at, in the order the header lists the refusals
+int lookup_impl(const char *who, const TfheHipSelector *sel, const Torus32 *ring, int32_t M, int32_t width, Torus32 *out, bool on_device) {
+    const std::string w = std::string(who) + ": ";
+    selector_checked(w, sel);
+    if (!ring || !out) api_fail(w + "null ring words or destination");
+    const int N = sel->p.N;
+    if (width < 1 || width > N || (width & (width - 1)))
+        api_fail(w + "width must be a power of two in 1.." + std::to_string(N));
+    int s = 0;
+    while ((width << s) < N) ++s;
+    if (sel->nbits < s)
+        api_fail(w + "entries of width " + std::to_string(width) + " need the " + std::to_string(s) + " rotation bits of a sample; the selector has " +
+                 std::to_string(sel->nbits) + " bits");
+    if (M < 1 || (int64_t)M > ((int64_t)1 << sel->nbits))
+        api_fail(w + "M must be in 1..2^" + std::to_string(sel->nbits) + " for a selector of " + std::to_string(sel->nbits) + " bits");
+    if (on_device && ((reinterpret_cast<uintptr_t>(ring) | reinterpret_cast<uintptr_t>(out)) & 15))
+        api_fail(w + "device words must be 16-byte aligned");
+    auto g = recorder_lock();
+    // like a select: names no pool slot, flushes nothing, waits for no flight
+    const Engine::SelectorImage *img = select_image(sel);
+    Engine::get().run_lookup(img, sel->p, sel->nbits, ring, M, width, on_device, out, on_device);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -142,6 +166,32 @@ int tfhe_hip_ring_select_device(const TfheHipSelector *sel, const void *device_r
     return guarded_rc([&] {
         return select_impl("tfhe_hip_ring_select_device", sel, static_cast<const Torus32 *>(device_ring_words), M,
                            static_cast<Torus32 *>(device_out), true);
+    });
+}
+
+int tfhe_hip_ring_lookup(const TfheHipSelector *sel, const Torus32 *ring_words, int32_t M, int32_t width, Torus32 *out_ring_words) {
+    return guarded_rc([&] { return lookup_impl("tfhe_hip_ring_lookup", sel, ring_words, M, width, out_ring_words, false); });
+}
+int tfhe_hip_ring_lookup_device(const TfheHipSelector *sel, const void *device_ring_words, int32_t M, int32_t width, void *device_out) {
+    return guarded_rc([&] {
+        return lookup_impl("tfhe_hip_ring_lookup_device", sel, static_cast<const Torus32 *>(device_ring_words), M, width,
+                           static_cast<Torus32 *>(device_out), true);
+    });
+}
+
+int tfhe_hip_kernel_ring_cmux_rotate(const TfheHipSelector *sel, int32_t bit_index, int32_t rot, const Torus32 *d0_words, int32_t count,
+                                     Torus32 *out_words) {
+    return guarded_rc([&] {
+        const std::string w = "tfhe_hip_kernel_ring_cmux_rotate: ";
+        selector_checked(w, sel);
+        if (!d0_words || !out_words) api_fail(w + "null argument");
+        if (bit_index < 0 || bit_index >= sel->nbits) api_fail(w + "bit_index must be in 0.." + std::to_string(sel->nbits - 1));
+        if (rot < 1 || rot >= sel->p.N) api_fail(w + "rot must be in 1.." + std::to_string(sel->p.N - 1));
+        if (count < 1 || count > CMUX_MAX_COUNT) api_fail(w + "count must be in 1.." + std::to_string(CMUX_MAX_COUNT));
+        auto g = recorder_lock();
+        const Engine::SelectorImage *img = select_image(sel);
+        Engine::get().run_cmux(img, sel->p, bit_index, nullptr, d0_words, count, out_words, rot);
+        return 0;
     });
 }
 

@@ -12,6 +12,8 @@ pins ~0.22 M ciphertext slots of a pool that may grow to 4 M slots).
 Only the match-bit ciphertext of each match is kept: M x (n+1) words, the one thing that leaves
 the GPU.  Plumbing only: every gate runs in libtfhe-hip.
 """
+import numpy as np
+
 from . import api, circuits
 from . import lib as _l
 
@@ -87,3 +89,44 @@ def select_template(selector, ring_gallery, params, nslots, bitsize, key):
             raise RuntimeError(api.last_error())
         words = words.cpu().numpy()
     return circuits.EncryptedVector.from_ring(params, words, nslots, bitsize, key)
+
+
+def pack_gallery(entries, width, secret, compressed=False, seed=None, mask_seed=None):
+    """The client side of lookup_template: M entries of `width` bits each (width a power of two up to N), S = N / width of
+    them per ring sample under the secret keyset `secret` -- bit j of entry i at coefficient (i mod S) width + j of sample
+    i / S (api.ring_encrypt_bits; a last sample that is not full carries 0 behind its entries).  A gallery of 128-bit
+    templates rests at 1 KB per template at N = 1,024 where select_template's rests at 8 KB.  Returns int32 [R][(k+1) N],
+    R = ceil(M / S); compressed: [R][10 + N], which api.ring_expand turns into the former on the server.  seed (and
+    mask_seed, compressed): the reproducible form, sample r drawn from seed + r."""
+    N = secret.params.N
+    R = api.lookup_samples(secret.params, len(entries), width)
+    S = N // width
+    out = []
+    for r in range(R):
+        bits = []
+        for e in entries[r * S:(r + 1) * S]:
+            e = [int(b) & 1 for b in e]
+            if len(e) != width:
+                raise ValueError("every entry carries %d bits" % width)
+            bits += e
+        out.append(api.ring_encrypt_bits(bits, secret, seed=None if seed is None else seed + r, compressed=compressed,
+                                         mask_seed=mask_seed))
+    return np.stack(out)
+
+
+def lookup_template(selector, ring_gallery, M, width, key):
+    """select_template's packed twin: api.ring_lookup of `selector` over a gallery pack_gallery made (host words
+    [R][(k+1) N], or an int32 torch tensor resident on the device), then the unpack of coefficients 0 .. width - 1 of the
+    result: a CiphertextArray of the `width` bits of the entry the client's index names, ready for circuits.hamming_match.
+    key: the keyset whose cloud key evaluates.  From a resident gallery nothing passes through the host."""
+    params = selector.params
+    device = hasattr(ring_gallery, "data_ptr")
+    words = api.ring_lookup(selector, ring_gallery, M, width, device=device)
+    bits = api.CiphertextArray(params, width)
+    if device:
+        api.unpack_device(words.data_ptr(), 1, key, bits, count=width)
+        if _l.load().tfhe_hip_stream_sync() != 0:            # `words` is released on return
+            raise RuntimeError(api.last_error())
+    else:
+        api.unpack(words, key, bits, count=width)
+    return bits

@@ -319,6 +319,9 @@ SIGNATURES = {
     "tfhe_hip_last_select_ms": (C.c_double, []),
     "tfhe_hip_kernel_ring_cmux": (C.c_int, [C.c_void_p, C.c_int32, I32P, I32P, C.c_int32, I32P]),
     "tfhe_hip_test_select_bounds": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "tfhe_hip_ring_lookup": (C.c_int, [C.c_void_p, I32P, C.c_int32, C.c_int32, I32P]),
+    "tfhe_hip_ring_lookup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "tfhe_hip_kernel_ring_cmux_rotate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, I32P, C.c_int32, I32P]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])

@@ -18,6 +18,7 @@ that follows it.
     python -m peba1_amd.protocol --compressed-keys       # the cloud key travels as a seed and the bodies (10x fewer bytes)
     python -m peba1_amd.protocol --seeded-inputs         # template and sample travel as seed-compressed ring samples
     python -m peba1_amd.protocol --seeded-lwe            # template and sample travel as seed-compressed LWE sample arrays
+    python -m peba1_amd.protocol --packed-gallery        # Hamming match of one claimed identity against a packed gallery
 
 With --clients K the server side runs as a multi-user server does: Function_f of all K clients in ONE flush and
 Function_g of all K in a second one (multi-key flushes, tuning "batch_keys"), one JSON line per client.
@@ -135,6 +136,48 @@ def client_inputs(c, nslots, seed):
     return {"key_seed": seed + 1 + c, "template": template, "sample": sample, "r0": (17 + c) % 256, "r1": (99 + 7 * c) % 256}
 
 
+def run_packed_gallery(params, key, templates, claimed, probes, bound, width=128, cloud=None):
+    """Verification of a claimed identity the server must not learn, against a gallery of `width`-bit templates that rests
+    packed (identify.pack_gallery: N / width templates per ring sample).  The client sends the TGSW-encrypted bits of
+    `claimed` and, per run, an encrypted probe; the server looks the template up (identify.lookup_template: the CMUX tree
+    over the samples, one rotation step per low index bit, the unpack of `width` coefficients) and runs
+    peba1_hamming_match on it.  probes: {name: bits}.  Returns one dict per probe: the decrypted bit (1 = the distance
+    exceeds `bound`, the polarity of Function_f), the plaintext distance and the timings."""
+    from . import identify
+    ev = key if cloud is None else cloud
+    M = len(templates)
+    d = max((params.N // width).bit_length() - 1 + max(api.lookup_samples(params, M, width) - 1, 0).bit_length(), 1)
+    t0 = time.perf_counter()
+    gallery = identify.pack_gallery(templates, width, key)                               # enrolment, on the client
+    selector = api.Selector(params, api.tgsw_encrypt_bits([(claimed >> j) & 1 for j in range(d)], key))
+    cw = circuits.hamming_count_bits(width)
+    enc_bound = circuits.encrypt_number(params, bound, cw, key)
+    t_enc = time.perf_counter()
+    out = []
+    was_deferred = api.get_deferred()
+    api.set_deferred(True)
+    try:
+        for name, bits in probes.items():
+            t1 = time.perf_counter()
+            probe = api.CiphertextArray(params, width).encrypt(bits, key)
+            template = identify.lookup_template(selector, gallery, M, width, ev)
+            t_lookup = time.perf_counter()
+            enc_b = api.CiphertextArray(params, cw)
+            circuits.hamming_match(enc_b, probe, template, width, enc_bound, ev)
+            levels = api.flush()
+            t_match = time.perf_counter()
+            distance = sum(int(a) ^ int(b) for a, b in zip(bits, templates[claimed]))
+            out.append({"run": name, "match_bit": int(enc_b.decrypt(key)[0]), "distance": distance, "bound": bound,
+                        "expected_bit": int(distance > bound), "entries": M, "width": width, "selector_bits": d,
+                        "gallery_bytes": int(gallery.nbytes),
+                        "seconds": {"enrol": t_enc - t0, "lookup": t_lookup - t1, "hamming_match": t_match - t_lookup},
+                        "levels": {"hamming_match": levels}})
+    finally:
+        api.set_deferred(was_deferred)
+        selector.close()
+    return out
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--nslots", type=int, default=128)
@@ -149,7 +192,15 @@ def parse_args(argv=None):
                     help="template and sample travel as seed-compressed ring samples and are opened on the device")
     ap.add_argument("--seeded-lwe", action="store_true",
                     help="template and sample travel as one seed-compressed LWE record each and are opened on the device")
+    ap.add_argument("--packed-gallery", action="store_true",
+                    help="Hamming match of one claimed identity against a gallery of 128-bit templates packed eight to a ring "
+                         "sample: looked up under TGSW-encrypted index bits, the server does not learn which")
+    ap.add_argument("--entries", type=int, default=20, help="--packed-gallery: templates in the gallery")
     a = ap.parse_args(argv)
+    if a.packed_gallery and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast):
+        ap.error("--packed-gallery runs the single-client Hamming match alone")
+    if a.packed_gallery and not 1 <= a.entries <= 1 << 20:
+        ap.error("--entries must be in 1..2^20")
     if a.seeded_lwe and (a.clients or a.seeded_inputs):
         ap.error("--seeded-lwe runs the single-client form, without --seeded-inputs")
     if a.clients < 0:
@@ -195,6 +246,21 @@ def main():
     params = api.ParameterSet(128)
     key = api.SecretKeySet(params, a.seed + 1, device=not a.compressed_keys)
     cloud = shipped_cloud(key) if a.compressed_keys else None
+    if a.packed_gallery:
+        import random
+        rnd = random.Random(a.seed)
+        templates = [[rnd.getrandbits(1) for _ in range(128)] for _ in range(a.entries)]
+        claimed = a.entries * 2 // 3
+        genuine = list(templates[claimed])
+        for j in rnd.sample(range(128), 5):
+            genuine[j] ^= 1
+        probes = {"genuine": genuine, "impostor": [rnd.getrandbits(1) for _ in range(128)]}
+        for out in run_packed_gallery(params, key, templates, claimed, probes, bound=20, cloud=cloud):
+            print(json.dumps(out))
+        if cloud is not None:
+            cloud.close()
+        key.close()
+        return
     template = [(37 * i + 11) % 255 for i in range(a.nslots)]             # SURVEY 8c inputs
     runs = {"genuine": [t + 1 for t in template], "impostor": [(91 * i + 5) % 256 for i in range(a.nslots)]}
     for name, sample in runs.items():
