@@ -1058,6 +1058,88 @@ int tfhe_hip_ring_lookup_device(const TfheHipSelector *selector, const void *dev
 int tfhe_hip_kernel_ring_cmux_rotate(const TfheHipSelector *selector, int32_t bit_index, int32_t rot, const Torus32 *d0_words,
                                      int32_t count, Torus32 *out_words);
 
+/* ---- encrypted inner products on packed galleries: Hamming 1-to-N by ONE external product per ring sample ----
+ * The leveled half computing on templates instead of moving them.  A TGSW sample may encrypt a small-integer POLYNOMIAL
+ * instead of a bit; G (.) c is then the negacyclic product of that polynomial with the ring sample's message.  No new key
+ * material on the server: the cloud key and the selector object do everything.  k = 1.
+ *
+ * TGSW sample of a polynomial p in Z[X]/(X^N + 1), given as N int32 coefficients: row (u, r), u <= k, r < l, is a TLWE
+ * encryption of zero under the ring key, and p[j] << (32 - (r+1) Bgbit), wrapping, is added to coefficient j of its
+ * polynomial u.  Word order and draw order (masks, then noise, row by row) are those of tfhe_hip_tgsw_encrypt_bits[_seeded]:
+ * for p = bit (a constant polynomial) under the same seed the words are IDENTICAL to the bit encryptor's.
+ * tfhe_hip_tgsw_encrypt_polys[_seeded]: polys[count][N], 1 <= count <= 20, out_words[count][(k+1) l][k+1][N]; host only;
+ * 0, or -1 with the error set and out_words untouched.  tfhe_hip_new_selector takes such words unchanged: a selector's
+ * samples may be polynomial samples (the tree and the lookup are meaningful for bit samples alone).
+ * Product.  G (.) c exactly as defined for the private selection: the offset decomposition of c, signed digits, exact in
+ * Z[X]/(X^N + 1) mod 2^32.  The row words of a polynomial sample are arbitrary 32-bit words like any other, so the two
+ * bounds of peba1_amd/csrc/cmux.hpp hold unchanged; there is no new bound.
+ * Probe layout.  For s_0 .. s_(w-1):  p[0] = s_0,  p[N - i] = -s_i for 1 <= i < w,  0 elsewhere: p = sum_i s_i X^(-i).
+ * Why.  Let t be the message of a ring sample in the lookup's layout (S = N / w entries of w coefficients, entry e on
+ * coefficients e w .. e w + w - 1).  A term t[j] p[m] of p t lands on coefficient e w iff j + m = e w or j + m = N + e w.
+ * With m in {0} u (N - w, N) the first case forces m = 0, j = e w; the second m = N - i, j = e w + i with 1 <= i < w,
+ * where the wrap's sign cancels the minus of p[N - i].  So coefficient e w of p t is sum_i s_i t[e w + i], the inner
+ * product of the probe with entry e, and nothing of any other entry enters it.
+ * Inner.  The gallery is R ring samples holding M <= R S entries in the lookup's layout, R = ceil(M / S):
+ *     result[i] = KeySwitch(Extract_((i mod S) w)(G_b (.) c_(i / S)))        for i < M, b = sample_index,
+ * Extract and KeySwitch being those of tfhe_hip_unpack_samples.  The product and the S extractions of a ring sample are
+ * ONE kernel launch of R workgroups; the key switch is the unpack's.
+ * Variance of result[i], to first order -- COMPUTED from the definition, not measured (torus units):
+ *     key term       (k+1) l N E[dig^2] bk_stdev^2,  E[dig^2] = Bg^2 / 12 for uniform digits
+ *     rounding term  (1 + k N) |p|_2^2 eps^2 / 3,  eps = 2^-(l Bgbit + 1)
+ *     input term     |p|_2^2 times the ring sample's variance (bk_stdev^2 for a fresh one)
+ *     the unpack's key-switch term, N t ks_stdev^2 + (N / 2) prec^2 / 3
+ * P128, w = 128, s_i = +-1 (|p|_2^2 = 128): before the key switch 2.2e-8 (with (Bg/2)^2 in place of E[dig^2], the bound
+ * the select states) + 2.5e-9 + 1e-13, sigma ~ 1.6e-4; after it sigma ~ 2.8e-3.
+ * The rounding term takes the decomposition's error as zero-mean, AND ON A GALLERY MADE BY PLAIN tfhe_hip_ring_encrypt IT IS
+ * NOT.  The offset decomposition KEEPS the top l Bgbit bits of a word, so the error of a word as it arrives lies in
+ * [0, 2 eps) with mean eps, and a probe of coefficient sum s = sum_i s_i shifts coefficient e w of the result's phase by
+ *     bias[e w] = -(p * eps (1 - ones * S))[e w],    |bias| <= |s| (1 + N / 2) eps to first order,
+ * S the ring key, `ones` the all-one polynomial: 1.3e-3 for s = 11 (a random 128-bit probe), 1.6e-2 for 128 equal bits at
+ * P128 -- above Delta / 2 = 9.8e-4, so distances from such a gallery are NOT exact to round.
+ * tfhe_hip_ring_center_words adds 2^(31 - l Bgbit), wrapping, to `count` words in place (nothing where l Bgbit = 32): applied
+ * ONCE to every word of a gallery -- a public operation on ciphertext words, client or server, at enrolment -- it makes the
+ * kept bits those of the rounded word and the error the zero-mean [-eps, eps) the term assumes.  Everything stated below for
+ * distances assumes a centred gallery.  0, or -1 with the error set and the words untouched: a null pointer, count < 0.
+ * tfhe_hip_ring_inner itself computes the product as defined, on the words it is given.
+ *
+ * Hamming distance on top of this.  The enrolled entry carries a_i Delta, Delta = 2^-(log2 w + 2), so distances stay
+ * inside [0, 1/4]; the probe is s_i = 1 - 2 b_i, and inner = (sum_i a_i - 2 sum_i a_i b_i) Delta.  The client also sends
+ * ONE LWE sample of (sum_i b_i) Delta (tfhe_hip_sym_encrypt_torus): inner + addend = d Delta, d the Hamming distance.  The
+ * server forms (tau + 1/2) Delta - (inner + addend) with tfhe_hip_linear (recorded like any other op) and applies
+ * tfhe_hip_lut_bootstrap with tfhe_hip_new_lut_constant(1/8): the output is TRUE iff d <= tau.
+ * THIS DECISION IS NOT EXACT NEAR THE THRESHOLD.  The bootstrap's modulus switch adds about (1 + n/2) / (12 (2N)^2)
+ * (sigma ~ 2.5e-3 at P128) to the key switch's 2.8e-3: sigma_dec ~ 3.7e-3 in all, 1.9 Delta at w = 128.  The decision is
+ * guaranteed only for |d - tau - 1/2| Delta >= 6 sigma_dec (peba1_amd.identify.inner_decision_band computes the band).
+ * The distance BEFORE the key switch is exact to round: Delta / 2 = 9.8e-4 is 6 sigma at w = 128.
+ * Euclidean distance on 8-bit features does NOT fit the torus (23 bits of range against sigma 1.6e-4): OUT OF SCOPE.
+ *
+ * tfhe_hip_ring_inner follows tfhe_hip_unpack_samples throughout: every result is renamed into a fresh slot; all arguments
+ * are checked before anything changes; a flush in flight is completed first; recorded operations stay recorded; work runs
+ * in chunks of at most 8,192 rows; the host form returns with the slots written, the device form (ring words resident on
+ * the card, 16-byte aligned) with the work enqueued on tfhe_hip_stream().  tfhe_hip_last_select_ms covers the product
+ * launch.  Return 0, or -1 with tfhe_hip_last_error() set and the call without effect (results keep values and slots): a
+ * null pointer, a deleted selector, sample_index outside the selector, a selector of another ring (N, k) than the key's --
+ * the gadget (l, Bgbit) MAY differ: the product runs under the selector's, the key serves the key switch alone --, width
+ * not a power of two in 1 .. N, M < 1, misaligned device words, a result sample this library did not allocate or of another
+ * LWE dimension than the key's, M past the end of the result array, the slot pool exhausted, device memory exhausted. */
+int tfhe_hip_tgsw_encrypt_polys(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *polys, int32_t count,
+                                Torus32 *out_words);
+int tfhe_hip_tgsw_encrypt_polys_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *polys, int32_t count,
+                                       Torus32 *out_words, uint64_t seed);
+int tfhe_hip_ring_center_words(const TFheGateBootstrappingParameterSet *params, Torus32 *words, int64_t count);
+int tfhe_hip_ring_inner(const TfheHipSelector *selector, int32_t sample_index, const TFheGateBootstrappingCloudKeySet *bk,
+                        const Torus32 *ring_words, int32_t M, int32_t width, LweSample *result);
+int tfhe_hip_ring_inner_device(const TfheHipSelector *selector, int32_t sample_index, const TFheGateBootstrappingCloudKeySet *bk,
+                               const void *device_ring_words, int32_t M, int32_t width, LweSample *result);
+/* raw test entry: out_words[c] = G_bit (.) ring_words[c], the full product, 1 <= count <= 65,536 in ONE launch, (k+1) N
+ * host words each */
+int tfhe_hip_kernel_ring_product(const TfheHipSelector *selector, int32_t bit_index, const Torus32 *ring_words, int32_t count,
+                                 Torus32 *out_words);
+/* raw test entry: the extracted rows before the key switch, out_rows[i] (kN+1 words) = Extract_((i mod S) width)(G_bit (.)
+ * ring sample i / S) for i < M, (R - 1) S < M <= R S; no slots involved */
+int tfhe_hip_kernel_ring_inner_rows(const TfheHipSelector *selector, int32_t bit_index, const Torus32 *ring_words, int32_t R,
+                                    int32_t M, int32_t width, Torus32 *out_rows);
+
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through
  * the device NTT (two 27-bit primes + CRT); |ip| must be < 2^12 */

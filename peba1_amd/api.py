@@ -1053,6 +1053,67 @@ def kernel_ring_cmux_rotate(selector, bit, rot, d0):
     return out
 
 
+def tgsw_encrypt_polys(polys, key, seed=None):
+    """TGSW samples of 1..20 small-integer polynomials [count][N] under the ring key of the secret keyset `key`
+    (tfhe_hip_tgsw_encrypt_polys; host only) -> int32 [count][(k+1) l][k+1][N], words a Selector takes like those of bits.
+    A constant polynomial 0 / 1 under a seed gives the words of tgsw_encrypt_bits under that seed."""
+    p = key.params
+    q = np.ascontiguousarray(polys, dtype=np.int32).reshape(-1, p.N)
+    out = np.zeros((max(len(q), 1), (p.k + 1) * p.l, p.k + 1, p.N), dtype=np.int32)
+    L = _l.load()
+    rc = (L.tfhe_hip_tgsw_encrypt_polys(key.ptr, _i32p(q), len(q), _i32p(out)) if seed is None
+          else L.tfhe_hip_tgsw_encrypt_polys_seeded(key.ptr, _i32p(q), len(q), _i32p(out), int(seed)))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def ring_inner(selector, sample, gallery, M, width, key, result, first=0, device=False):
+    """The encrypted inner products (tfhe_hip_ring_inner): `gallery` holds M entries of `width` coefficients in ring_lookup's
+    layout, sample `sample` of `selector` is the TGSW sample of a probe polynomial (sum_i s_i X^(-i)), and result[first + i]
+    receives, in a fresh slot, the key switch of coefficient (i mod S) width of G (.) c_(i / S): the inner product of the
+    probe with entry i.  key: the keyset whose cloud key evaluates.  Host and device forms of the gallery as for
+    ring_lookup; the device form returns with the work enqueued.  Recorded operations stay recorded."""
+    p = selector.params
+    sw = (p.k + 1) * p.N
+    R = lookup_samples(p, M, width)
+    L = _l.load()
+    if device:
+        import torch
+        if gallery.dtype != torch.int32 or not gallery.is_contiguous() or gallery.numel() != R * sw:
+            raise ValueError("a device gallery of %d entries is a contiguous int32 tensor of %d (k+1) N words" % (M, R))
+        rc = L.tfhe_hip_ring_inner_device(selector.ptr, int(sample), key.cloud, C.c_void_p(gallery.data_ptr()), int(M), int(width),
+                                          result.at(first))
+    else:
+        g = _ring_words(gallery, p)
+        if g.shape[0] != R:
+            raise ValueError("a gallery of %d entries of width %d holds %d ring samples" % (M, width, R))
+        rc = L.tfhe_hip_ring_inner(selector.ptr, int(sample), key.cloud, _i32p(g), int(M), int(width), result.at(first))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def kernel_ring_product(selector, bit, ring):
+    """G_bit (.) ring[c], the full products of caller-supplied ring samples [count][(k+1) N] in one launch of the
+    product-and-extract kernel (tfhe_hip_kernel_ring_product)."""
+    a = _ring_words(ring, selector.params)
+    out = np.zeros_like(a)
+    if _l.load().tfhe_hip_kernel_ring_product(selector.ptr, int(bit), _i32p(a), a.shape[0], _i32p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def kernel_ring_inner_rows(selector, bit, ring, M, width):
+    """The rows ring_inner key-switches, before the key switch (tfhe_hip_kernel_ring_inner_rows): int32 [M][kN+1]."""
+    p = selector.params
+    a = _ring_words(ring, p)
+    u = np.zeros((int(M), p.k * p.N + 1), dtype=np.int32)
+    if _l.load().tfhe_hip_kernel_ring_inner_rows(selector.ptr, int(bit), _i32p(a), a.shape[0], int(M), int(width), _i32p(u)) != 0:
+        raise RuntimeError(last_error())
+    return u
+
+
 def ring_trivial(params, values):
     """The noiseless ring sample (0, values): a zero mask and the 1..N torus words `values` as the body (zero behind them).
     It decrypts to `values` under every key, so a gallery of such samples is a PUBLIC table, and ring_lookup over it

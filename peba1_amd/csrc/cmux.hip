@@ -12,7 +12,16 @@
 //                        another operand load -- coefficient j of X^(-rot) d0 is d0[j + rot], negated past the wrap -- and
 //                        nothing else; d1 and n_d1 are not read.  Lanes read words of d0 other lanes' stores would hit:
 //                        launch_cmux refuses an output that overlaps d0.
-// No atomics, no global scratch; a CMUX reads nothing another CMUX of the launch writes.
+//   inner_kernel        the product alone, G (.) c, of the encrypted inner products (include/tfhe_hip.h "encrypted inner
+//                        products"): the same body with the operand c itself -- no d1 - d0, no + d0 -- and a fused sample
+//                        extraction.  After the CRT the torus words go back into LDS over prime 0's residues (every lane
+//                        overwrites the 16 bytes it alone has just read), one more barrier, and the two waves write the
+//                        rows Extract_(e w), e < S = N / w, of their ring sample in ring_extract_kernel's layout
+//                        (unpack.hip): a lane owns 16-byte groups of a row, reads the mask polynomial descending from
+//                        A[e w - 4g] in LDS and stores 16 bytes; the last group is (B[e w], 0, 0, 0).  Only rows below M
+//                        are written.  The raw test form stores the full product as well (out != null) or alone.
+//                        The epilogue starts after the accumulators have died: it adds no register to the body's peak.
+// No atomics, no global scratch beyond the row buffer; a CMUX reads nothing another CMUX of the launch writes.
 //
 // kernels.hip is not touched by this file; the few lines it keeps private (the per-prime context) are restated here.
 #include "cmux.hpp"
@@ -42,101 +51,43 @@ __device__ __forceinline__ PrimeCtx cmux_ctx(int q, const uint32_t *tw, int n_ri
 // the most rows any accepted gadget has: the accumulators below take that many products (cmux.hpp MAC bound)
 static_assert(cmux_mac_ok(1024, 18) && cmux_mac_ok(2048, 16), "rows one accumulator takes");
 
-template <int LOGN, bool ROT>
+enum { MODE_CMUX = 0, MODE_ROT = 1, MODE_PRODUCT = 2 };
+
+template <int LOGN, bool ROT_KERNEL>
 __global__ __launch_bounds__(128) void cmux_kernel(CmuxArgs a) {
-    using NTT = WaveNtt<LOGN>;
-    constexpr int N = NTT::N, REGS = NTT::REGS;
-    __shared__ __align__(16) uint32_t lds_scr[2][NTT::SCRATCH_WORDS];
-    // residues in natural order, [prime = the wave that wrote them][output polynomial][N]
-    __shared__ __align__(16) uint32_t lds_x[2][2][N];
-    const int tid = threadIdx.x;
-    const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    const PrimeCtx c = cmux_ctx(q, a.tw, N);
-    uint32_t *scr = lds_scr[q];
+    constexpr int MODE = ROT_KERNEL ? MODE_ROT : MODE_CMUX;
+    const InnerRows t{};
+#include "cmux_body.inc"
+}
 
-    const int cm = blockIdx.x;                                   // < a.count: the grid is a.count workgroups
-    const int32_t *d0 = a.d0 + (size_t)cm * a.stride;
-    const bool has_d1 = cm < a.n_d1;                             // workgroup-uniform
-    const int32_t *d1 = a.d1 + (size_t)cm * a.stride;            // read only if has_d1
-    const uint32_t mask = (1u << a.Bgbit) - 1u;
-    const int32_t half = 1 << (a.Bgbit - 1);
-    typename NTT::FwdTw0 t0;                 // lane-uniform and the same for every transform
-    t0.load(c, lane);
-
-    int64_t acc0[REGS], acc1[REGS];
-#pragma unroll
-    for (int r = 0; r < REGS; ++r) { acc0[r] = 0; acc1[r] = 0; }
-    // image of row (bit, u, p): [X = bit (k+1) l + u l + p][prime][polynomial 2][N] (kernels.hip bk_transform_kernel, nw = 2)
-    const uint4 *rowimg = reinterpret_cast<const uint4 *>(a.img + ((size_t)a.bit * 2 * a.l * 2 + q) * 2 * N) + lane;
-    for (int u = 0; u < 2; ++u) {
-        // coefficient j = 64 r + lane of polynomial u (layout L0 of ntt_wave.hpp)
-        uint32_t v[REGS];
-#pragma unroll
-        for (int r = 0; r < REGS; ++r) {
-            const int j = u * N + r * 64 + lane;
-            if constexpr (ROT) {
-                // (X^(-rot) d0)[j] = d0[j + rot], and -d0[j + rot - N] past the wrap (lut_coef's convention); 0 < rot < N
-                const int jr = r * 64 + lane + a.rot;
-                const uint32_t w = (uint32_t)d0[u * N + (jr & (N - 1))];
-                v[r] = (jr >= N ? 0u - w : w) - (uint32_t)d0[j] + a.offset;
-            } else {
-                v[r] = (has_d1 ? (uint32_t)d1[j] : 0u) - (uint32_t)d0[j] + a.offset;
-            }
-        }
-        for (int p = 0; p < a.l; ++p) {
-            const int shift = 32 - (p + 1) * a.Bgbit;
-            int32_t x[REGS];
-#pragma unroll
-            for (int r = 0; r < REGS; ++r) x[r] = (int32_t)((v[r] >> shift) & mask) - half;    // |x| <= Bg/2 <= 2^11
-            NTT::template forward<false>(x, c, scr, lane, t0);            // |x| < 6.1 P / 6.7 P (cmux.hpp)
-            const uint4 *bp = rowimg + (size_t)(u * a.l + p) * N;       // 4N words per row = N uint4
-#pragma unroll
-            for (int g = 0; g < REGS / 4; ++g) {
-                const uint4 b0 = bp[g * 64], b1 = bp[N / 4 + g * 64];
-                acc0[4 * g + 0] += (int64_t)x[4 * g + 0] * (int32_t)b0.x;
-                acc0[4 * g + 1] += (int64_t)x[4 * g + 1] * (int32_t)b0.y;
-                acc0[4 * g + 2] += (int64_t)x[4 * g + 2] * (int32_t)b0.z;
-                acc0[4 * g + 3] += (int64_t)x[4 * g + 3] * (int32_t)b0.w;
-                acc1[4 * g + 0] += (int64_t)x[4 * g + 0] * (int32_t)b1.x;
-                acc1[4 * g + 1] += (int64_t)x[4 * g + 1] * (int32_t)b1.y;
-                acc1[4 * g + 2] += (int64_t)x[4 * g + 2] * (int32_t)b1.z;
-                acc1[4 * g + 3] += (int64_t)x[4 * g + 3] * (int32_t)b1.w;
-            }
-        }
-    }
-    // |acc| < (k+1) l f P^2 -> reduction below 4 P (MAC bound) -> inverse NTT: signed residues below P, natural order
-    int32_t y[REGS];
-#pragma unroll
-    for (int r = 0; r < REGS; ++r) y[r] = mont_redc(acc0[r], c.P, c.pinv);
-    NTT::inverse(y, c, scr, lane);
-#pragma unroll
-    for (int r = 0; r < REGS; ++r) lds_x[q][0][r * 64 + lane] = (uint32_t)y[r];
-#pragma unroll
-    for (int r = 0; r < REGS; ++r) y[r] = mont_redc(acc1[r], c.P, c.pinv);
-    NTT::inverse(y, c, scr, lane);
-#pragma unroll
-    for (int r = 0; r < REGS; ++r) lds_x[q][1][r * 64 + lane] = (uint32_t)y[r];
-    // the waves took different primes and now exchange through LDS alone: the barrier form ntt_wave.hpp documents for
-    // that (both waves reach it on the same path; nothing was stored to global memory yet)
-    lds_barrier();
-    // wave q owns output polynomial q: coefficients 4 (64 g + lane) .. + 3, both primes' residues, the signed CRT
-    // (the true integer is below CRT_EXACT_LIMIT: CRT bound), + d0, one 16-byte store
-    const uint4 *r0 = reinterpret_cast<const uint4 *>(lds_x[0][q]) + lane;
-    const uint4 *r1 = reinterpret_cast<const uint4 *>(lds_x[1][q]) + lane;
-    const uint4 *src = reinterpret_cast<const uint4 *>(d0 + (size_t)q * N) + lane;
-    uint4 *dst = reinterpret_cast<uint4 *>(a.out + ((size_t)cm * 2 + q) * N) + lane;
-#pragma unroll
-    for (int g = 0; g < REGS / 4; ++g) {
-        const uint4 x0 = r0[g * 64], x1 = r1[g * 64], base = src[g * 64];
-        dst[g * 64] = make_uint4(base.x + crt_signed_to_torus((int32_t)x0.x, (int32_t)x1.x),
-                                 base.y + crt_signed_to_torus((int32_t)x0.y, (int32_t)x1.y),
-                                 base.z + crt_signed_to_torus((int32_t)x0.z, (int32_t)x1.z),
-                                 base.w + crt_signed_to_torus((int32_t)x0.w, (int32_t)x1.w));
-    }
+template <int LOGN>
+__global__ __launch_bounds__(128) void inner_kernel(InnerArgs x) {
+    constexpr int MODE = MODE_PRODUCT;
+    const CmuxArgs &a = x.c;
+    const InnerRows &t = x.rows;
+#include "cmux_body.inc"
 }
 
 }  // namespace
+
+bool launch_inner(hipStream_t s, const InnerArgs &x) {
+    const CmuxArgs &a = x.c;
+    const InnerRows &t = x.rows;
+    // the gadget as launch_cmux; the operands are the `count` ring samples at d0, 16-byte aligned like every destination
+    if (cmux_gadget_error(a.N, 1, a.l, a.Bgbit) || a.bit < 0 || a.bit >= SELECT_MAX_BITS || a.count < 1 || a.stride < 2 * (int64_t)a.N ||
+        (a.stride & 3) || !a.d0 || !a.img || !a.tw || a.rot || a.n_d1 || (!a.out && !t.u_buf) || (reinterpret_cast<uintptr_t>(a.out) & 15u))
+        return false;
+    if (t.u_buf) {
+        // rows: w a power of two in 1 .. N, every workgroup has an entry ((count - 1) S < M <= count S), one chunk at most
+        if (t.width < 1 || t.width > a.N || (t.width & (t.width - 1)) || t.u_stride != a.N + 4 || (reinterpret_cast<uintptr_t>(t.u_buf) & 15u))
+            return false;
+        const int64_t S = a.N / t.width;
+        if (t.M < 1 || t.M > UNPACK_CHUNK || t.M > a.count * S || t.M <= (a.count - 1) * S) return false;
+    }
+    if (a.N == 2048) hipLaunchKernelGGL((inner_kernel<11>), dim3(a.count), dim3(128), 0, s, x);
+    else hipLaunchKernelGGL((inner_kernel<10>), dim3(a.count), dim3(128), 0, s, x);
+    return true;
+}
 
 bool launch_cmux(hipStream_t s, const CmuxArgs &a) {
     // the kernel is instantiated for k = 1; everything else it was bounded for is checked here once more

@@ -1487,55 +1487,121 @@ double Engine::last_select_ms() {
 }
 
 // ---- ring-encrypted inputs (unpack.hpp, unpack.hip) -----------------------------------------
+// The tail run_unpack and run_inner share: `count` rows of u_stride words, made chunk by chunk, and their key switch.
+// size_rows sizes every buffer of it (scratch() may throw: nothing has been enqueued then).  The key switches run by two
+// plans, the widest chunk's and the last one's (which may be cut into more ranges); the partial sums are sized for both
+Engine::RowsPlan Engine::size_rows(const DeviceKeyImage *key, int u_stride, int count, bool to_slots) {
+    RowsPlan r;
+    r.widest = std::min(count, UNPACK_CHUNK);
+    r.u_stride = u_stride;
+    r.dks = to_slots ? scratch_as<KsDesc>(S_UNPACK_KS, (size_t)count) : nullptr;
+    r.u_buf = scratch_as<int32_t>(S_UNPACK_EXTRACT, (size_t)r.widest * u_stride);
+    if (to_slots) {
+        r.ks_wide = plan_ks_launch(key, r.widest, false);
+        r.ks_last = plan_ks_launch(key, count - (count - 1) / UNPACK_CHUNK * UNPACK_CHUNK, false);
+        (void)scratch(S_KS_PARTIAL, std::max(r.ks_wide.partial_bytes, r.ks_last.partial_bytes));
+    }
+    return r;
+}
+
+// make_rows(done, cnt): the launch that writes rows done .. done + cnt - 1 of the call into r.u_buf[0 .. cnt).  The slot
+// form (u_out null): the key switch of row j goes into pool slot slots[j]; the raw form: the rows alone, [count][uw]
+template <class MakeRows>
+void Engine::run_rows(const DeviceKeyImage *key, const RowsPlan &r, int count, size_t uw, SlotPool *pool, const int32_t *slots,
+                      Torus32 *u_out, const char *what, MakeRows &&make_rows) {
+    if (!u_out) {
+        std::vector<KsDesc> hks((size_t)count);
+        for (int j = 0; j < count; ++j) hks[j] = KsDesc{j % UNPACK_CHUNK, -1, 0, slots[j]};
+        h2d_staged(r.dks, hks.data(), hks.size(), "upload unpack ks");
+    }
+    std::vector<int32_t> rows(u_out ? (size_t)r.widest * r.u_stride : 0);
+    for (int done = 0; done < count; done += UNPACK_CHUNK) {
+        const int cnt = std::min(UNPACK_CHUNK, count - done);
+        make_rows(done, cnt);
+        last_extract_words_ = (size_t)cnt * r.u_stride;
+        if (u_out) {
+            d2h(rows.data(), r.u_buf, (size_t)cnt * r.u_stride, "download extracted rows");
+            sync_stream(what);
+            unpad_rows(u_out + (size_t)done * uw, rows.data(), (size_t)cnt, uw, (size_t)r.u_stride);
+        } else {
+            // (the next chunk's rows are ordered behind this key switch: one stream, one buffer)
+            launch_ks(key, cnt == r.widest ? r.ks_wide : r.ks_last, r.u_buf, r.dks + done, pool->data());
+            hip_check(hipGetLastError(), "unpack keyswitch launch");
+        }
+    }
+    if (!u_out) stats.keyswitches += (uint64_t)count;
+}
+
 void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, int nring, bool ring_on_device, const int32_t *index,
                         int count, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait, bool seeded) {
     ENGINE_DEVICE_SCOPE();
     const DevParams &dp = key->dp;
     const size_t ring_count = (size_t)nring * (seeded ? RING_SEED_WORDS + dp.N : 2 * dp.N), uw = (size_t)dp.k * dp.N + 1;
-    const int widest = std::min(count, UNPACK_CHUNK);
-    // every buffer first (scratch() may throw: nothing has been enqueued then).  The key switches run by two plans, the
-    // widest chunk's and the last one's (which may be cut into more ranges); the partial sums are sized for both
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
     int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_UNPACK_RING, ring_count);
     int32_t *dindex = scratch_as<int32_t>(S_UNPACK_INDEX, (size_t)count);
-    KsDesc *dks = u_out ? nullptr : scratch_as<KsDesc>(S_UNPACK_KS, (size_t)count);
-    int32_t *u_buf = scratch_as<int32_t>(S_UNPACK_EXTRACT, (size_t)widest * dp.u_stride);
-    const KsLaunchPlan ks_wide = plan_ks_launch(key, widest, false);
-    const KsLaunchPlan ks_last = plan_ks_launch(key, count - (count - 1) / UNPACK_CHUNK * UNPACK_CHUNK, false);
-    if (!u_out) (void)scratch(S_KS_PARTIAL, std::max(ks_wide.partial_bytes, ks_last.partial_bytes));
+    const RowsPlan r = size_rows(key, dp.u_stride, count, !u_out);
     h2d_staged(dindex, index, (size_t)count, "upload unpack index");
-    if (!u_out) {
-        std::vector<KsDesc> hks((size_t)count);
-        for (int j = 0; j < count; ++j) hks[j] = KsDesc{j % UNPACK_CHUNK, -1, 0, slots[j]};
-        h2d_staged(dks, hks.data(), hks.size(), "upload unpack ks");
-    }
     if (!ring_on_device) h2d(dring, ring_words, ring_count, "upload ring words");
-    std::vector<int32_t> rows(u_out ? (size_t)widest * dp.u_stride : 0);
-    for (int done = 0; done < count; done += UNPACK_CHUNK) {
-        const int cnt = std::min(UNPACK_CHUNK, count - done);
-        const int32_t *src = ring_on_device ? ring_words : dring;
-        if (seeded ? !launch_ring_extract_seeded(stream_, UnpackSeededArgs{dp.N, cnt, dp.u_stride, src, dindex + done, u_buf})
-                   : !launch_ring_extract(stream_, UnpackArgs{dp.N, cnt, dp.u_stride, src, dindex + done, u_buf}))
+    const int32_t *src = ring_on_device ? ring_words : dring;
+    run_rows(key, r, count, uw, pool, slots, u_out, "ring extract", [&](int done, int cnt) {
+        if (seeded ? !launch_ring_extract_seeded(stream_, UnpackSeededArgs{dp.N, cnt, dp.u_stride, src, dindex + done, r.u_buf})
+                   : !launch_ring_extract(stream_, UnpackArgs{dp.N, cnt, dp.u_stride, src, dindex + done, r.u_buf}))
             api_fail("unpack: arguments outside what the extract kernel was built for");
         hip_check(hipGetLastError(), "ring extract launch");
         ++stats.unpack_launches;
         if (seeded) ++seeded_stats.seeded_unpack_launches;
-        last_extract_words_ = (size_t)cnt * dp.u_stride;
-        if (u_out) {
-            d2h(rows.data(), u_buf, (size_t)cnt * dp.u_stride, "download extracted rows");
-            sync_stream("ring extract");
-            unpad_rows(u_out + (size_t)done * uw, rows.data(), (size_t)cnt, uw, (size_t)dp.u_stride);
-        } else {
-            // (the next chunk's extract is ordered behind this key switch: one stream, one buffer)
-            launch_ks(key, cnt == widest ? ks_wide : ks_last, u_buf, dks + done, pool->data());
-            hip_check(hipGetLastError(), "unpack keyswitch launch");
-        }
-    }
+    });
     if (u_out) return;
     stats.unpacked_samples += (uint64_t)count;
-    stats.keyswitches += (uint64_t)count;
     if (seeded) seeded_stats.seeded_unpacked_samples += (uint64_t)count;
     // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
     finish(wait || !ring_on_device, "unpack");
+}
+
+// ---- encrypted inner products (cmux.hpp InnerArgs, cmux.hip inner_kernel) ---------------------
+void Engine::run_inner(const SelectorImage *sel, const Params &p, int bit, const DeviceKeyImage *key, const Torus32 *ring, int R,
+                       bool ring_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, Torus32 *prod_out,
+                       bool wait) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t sw = (size_t)(p.k + 1) * p.N;
+    const int S = p.N / width;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_SELECT_RING, (size_t)R * sw);
+    InnerArgs x{cmux_args(sel, p), InnerRows{}};
+    x.c.bit = bit; x.c.stride = (int64_t)sw;
+    if (prod_out) {
+        // the raw product form: one launch over all R samples, no rows
+        x.c.out = scratch_as<int32_t>(S_SELECT_A, (size_t)R * sw);
+        h2d(dring, ring, (size_t)R * sw, "upload ring words");
+        x.c.d0 = dring; x.c.count = R;
+        if (!launch_inner(stream_, x)) api_fail("ring product: arguments outside what the kernel was built for");
+        hip_check(hipGetLastError(), "ring product launch");
+        d2h(prod_out, x.c.out, (size_t)R * sw, "download product words");
+        finish(true, "ring product");
+        return;
+    }
+    const RowsPlan r = size_rows(key, p.u_stride(), M, !u_out);
+    if (kernel_timing && !select_e0_) {
+        hip_check(hipEventCreate(&select_e0_), "select event");
+        hip_check(hipEventCreate(&select_e1_), "select event");
+    }
+    if (!ring_on_device) h2d(dring, ring, (size_t)R * sw, "upload ring words");
+    const int32_t *src = ring_on_device ? ring : dring;
+    x.rows.width = width; x.rows.u_stride = r.u_stride; x.rows.u_buf = r.u_buf;
+    run_rows(key, r, M, (size_t)p.k * p.N + 1, pool, slots, u_out, "ring inner", [&](int done, int cnt) {
+        // a chunk starts on a sample: S divides UNPACK_CHUNK (both powers of two, S <= N <= UNPACK_CHUNK)
+        x.c.d0 = src + (size_t)(done / S) * sw; x.c.count = (cnt + S - 1) / S; x.rows.M = cnt;
+        if (kernel_timing && done == 0) hip_check(hipEventRecord(select_e0_, stream_), "select event");
+        if (!launch_inner(stream_, x)) api_fail("ring inner: arguments outside what the kernel was built for");
+        hip_check(hipGetLastError(), "ring inner launch");
+        if (kernel_timing && done + cnt == M) hip_check(hipEventRecord(select_e1_, stream_), "select event");
+    });
+    select_timed_ = kernel_timing;
+    if (u_out) return;
+    // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
+    finish(wait || !ring_on_device, "ring inner");
 }
 
 size_t Engine::read_extract_rows(Torus32 *out, size_t capacity) {

@@ -308,14 +308,14 @@ private:
         S_PACK_OUT,       // run_pack: the result on its way to a host destination
         S_UNPACK_RING,    // run_unpack: the ring words on their way from a host source
         S_UNPACK_INDEX,   // run_unpack: the index list
-        S_UNPACK_KS,      // run_unpack: the key-switch descriptors (row j -> slot j)
-        S_UNPACK_EXTRACT, // run_unpack: the extracted samples of one chunk
+        S_UNPACK_KS,      // run_unpack, run_inner: the key-switch descriptors (row j -> slot j)
+        S_UNPACK_EXTRACT, // run_unpack, run_inner: the extracted samples of one chunk
         S_EXPAND_WORDS,   // raw, run_expand_masks: the stream words
         S_LWE_RECORD,     // run_lwe_expand: the seed and the gathered bodies of a host record
         S_LWE_INDEX,      // run_lwe_expand: the index list
         S_LWE_SLOTS,      // run_lwe_expand: the slot list
         S_LWE_ROWS,       // raw, run_lwe_expand: the rows of one chunk in place of pool slots
-        S_SELECT_RING,    // run_select: the ring words on their way from a host source; run_cmux: the d0 operands
+        S_SELECT_RING,    // run_select, run_inner: the ring words on their way from a host source; run_cmux: the d0 operands
         S_SELECT_A,       // run_select / run_lookup: the launches 0, 2, ... (ping), tree levels then rotations; run_cmux: the results
         S_SELECT_B,       // run_select / run_lookup: the launches 1, 3, ... (pong)
         S_CMUX_D1,        // raw, run_cmux: the d1 operands
@@ -406,9 +406,27 @@ public:
     // rotation steps ROT(G_bit, rot, d0[c]) instead (d1 is not looked at)
     void run_cmux(const SelectorImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out,
                   int rot = 0);
-    // the launches of the last run_select / run_lookup between two stream events (kernel timing on; waits for the second), else -1
+    // Encrypted inner products (include/tfhe_hip.h; cmux.hpp InnerArgs): `ring` holds R samples (host, or device memory the
+    // caller keeps until the stream has passed) of S = N / width entries each, M of them real, (R - 1) S < M <= R S.  Entry
+    // i becomes the row Extract_((i mod S) width)(G_bit (.) c_(i / S)) -- product and extraction in ONE launch per chunk of
+    // at most UNPACK_CHUNK rows -- and then goes the way of run_unpack's rows, through the same code: the slot form (u_out
+    // and prod_out null) key-switches row i into pool slot slots[i] under `key`; the raw form u_out [M][kN+1] returns the
+    // rows alone (key may be null); the raw form prod_out [R][(k+1) N] the full products of one launch and no rows.
+    // The caller has checked every argument and, for the slot form, waited for the flight.  Every buffer is sized before
+    // anything is enqueued: an ApiError (device memory exhausted) leaves nothing written.
+    void run_inner(const SelectorImage *sel, const Params &p, int bit, const DeviceKeyImage *key, const Torus32 *ring, int R,
+                   bool ring_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, Torus32 *prod_out,
+                   bool wait);
+    // the launches of the last run_select / run_lookup between two stream events (kernel timing on; waits for the second), else -1;
+    // after a run_inner: from its first product launch to its last (ONE launch up to UNPACK_CHUNK rows)
     double last_select_ms();
 private:
+    // what run_unpack and run_inner share (engine.cpp): the buffers and key-switch plans of `count` rows, then the chunks
+    struct RowsPlan { int widest = 0, u_stride = 0; KsDesc *dks = nullptr; int32_t *u_buf = nullptr; KsLaunchPlan ks_wide, ks_last; };
+    RowsPlan size_rows(const DeviceKeyImage *key, int u_stride, int count, bool to_slots);
+    template <class MakeRows>
+    void run_rows(const DeviceKeyImage *key, const RowsPlan &r, int count, size_t uw, SlotPool *pool, const int32_t *slots,
+                  Torus32 *u_out, const char *what, MakeRows &&make_rows);
     hipEvent_t select_e0_ = nullptr, select_e1_ = nullptr;
     bool select_timed_ = false;
     // (behind everything else, as above) prepare_flush's key-switch plan of every (level, key) share of flight_plan_

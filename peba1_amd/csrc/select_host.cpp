@@ -25,7 +25,8 @@ constexpr int32_t CMUX_MAX_COUNT = 1 << 16;
 
 // The draw order (include/tfhe_hip.h): for every bit, for u <= k, for p < l: the kN mask words, then the N noise samples
 // -- the order of the bootstrapping key's rows (host_keys.cpp generate_keys), of which a selector bit is one entry.
-void tgsw_encrypt_into(const TfheHipSecretKey &sk, const int32_t *bits, int32_t count, Rng &secret, Rng &mask, Torus32 *out) {
+// polys false: sample b encrypts the bit bits[b] (a constant polynomial); true: the polynomial at bits[b N .. + N)
+void tgsw_encrypt_into(const TfheHipSecretKey &sk, const int32_t *bits, bool polys, int32_t count, Rng &secret, Rng &mask, Torus32 *out) {
     const Params &p = sk.p;
     const int N = p.N, k = p.k, l = p.l, kpl = p.kpl();
     for (int32_t b = 0; b < count; ++b)
@@ -37,12 +38,15 @@ void tgsw_encrypt_into(const TfheHipSecretKey &sk, const int32_t *bits, int32_t 
             for (int j = 0; j < N; ++j) body[j] = (uint32_t)dtot32(secret.gauss(p.bk_stdev));
             for (int u = 0; u < k; ++u) pack_add_mul_by_bits(body, smp + (size_t)u * N, sk.tlwe_key.data() + (size_t)u * N, N, 1u);
             const int u = row / l, pp = row % l;
-            smp[(size_t)u * N] += (uint32_t)(bits[b] ? 1 : 0) << (32 - (pp + 1) * p.Bgbit);
+            const int shift = 32 - (pp + 1) * p.Bgbit;
+            if (!polys) smp[(size_t)u * N] += (uint32_t)(bits[b] ? 1 : 0) << shift;
+            else
+                for (int j = 0; j < N; ++j) smp[(size_t)u * N + j] += (uint32_t)bits[(size_t)b * N + j] << shift;
         }
 }
 
 int tgsw_encrypt_impl(const char *who, const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
-                      Torus32 *out, const uint64_t *seed) {
+                      Torus32 *out, const uint64_t *seed, bool polys = false) {
     if (!secret || !secret->lwe_key || !bits || !out) { set_error(std::string(who) + ": null argument"); return -1; }
     if (count < 1 || count > SELECT_MAX_BITS) {
         set_error(std::string(who) + ": count must be in 1.." + std::to_string(SELECT_MAX_BITS));
@@ -51,10 +55,10 @@ int tgsw_encrypt_impl(const char *who, const TFheGateBootstrappingSecretKeySet *
     const TfheHipSecretKey &sk = *secret->lwe_key;
     if (seed) {
         Rng both(*seed);                                  // a stream of its own, for this selector alone
-        tgsw_encrypt_into(sk, bits, count, both, both, out);
+        tgsw_encrypt_into(sk, bits, polys, count, both, both, out);
     } else {
         Rng noise = Rng::secure(), mask = Rng::secure();  // two fresh ChaCha20 streams, as for a ring sample
-        tgsw_encrypt_into(sk, bits, count, noise, mask, out);
+        tgsw_encrypt_into(sk, bits, polys, count, noise, mask, out);
     }
     return 0;
 }
@@ -112,6 +116,56 @@ int lookup_impl(const char *who, const TfheHipSelector *sel, const Torus32 *ring
     return 0;
 }
 
+// the encrypted inner products: every argument before the device is looked at, in the order the header lists the refusals
+int inner_impl(const char *who, const TfheHipSelector *sel, int32_t sample, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring,
+               int32_t M, int32_t width, LweSample *result, bool on_device) {
+    const std::string w = std::string(who) + ": ";
+    if (!ring || !result) api_fail(w + "null ring words or result");
+    if (!bk || !bk->bk) api_fail(w + "null cloud key");
+    selector_checked(w, sel);
+    if (sample < 0 || sample >= sel->nbits) api_fail(w + "sample_index must be in 0.." + std::to_string(sel->nbits - 1));
+    const Params &p = bk->bk->p;
+    const int N = sel->p.N;
+    if (p.N != N || p.k != sel->p.k) api_fail(w + "the selector and the cloud key belong to different rings");
+    if (width < 1 || width > N || (width & (width - 1)))
+        api_fail(w + "width must be a power of two in 1.." + std::to_string(N));
+    if (M < 1) api_fail(w + "M must be at least 1");
+    if (on_device && (reinterpret_cast<uintptr_t>(ring) & 15)) api_fail(w + "device words must be 16-byte aligned");
+    const int S = N / width, R = (int)(((int64_t)M + S - 1) / S);
+    auto g = recorder_lock();
+    // as the unpack: every result ours, of the key's LWE dimension, not bound to the pool of another shape
+    check_runs(w, UNPACK_RESULT, ResultsView(result), M, p);
+    SlotPool *pool = pool_of_key(bk);
+    // a flush in flight owns the key switch's partial sums; what is recorded and has not run stays recorded
+    finish_flight_locked();
+    const Engine::SelectorImage *img = select_image(sel);     // out of device memory: ApiError, nothing has changed
+    import_into_fresh_slots(pool, ResultsView(result), M, [&](const int32_t *slots) {
+        Engine::get().run_inner(img, sel->p, sample, bk->bk->dev, ring, R, on_device, M, width, pool, slots, nullptr, nullptr, !on_device);
+    });
+    return 0;
+}
+
+// the two raw forms: the full products of R samples (u_out null), or the M extracted rows
+int inner_raw_impl(const char *who, const TfheHipSelector *sel, int32_t sample, const Torus32 *ring, int32_t R, int32_t M, int32_t width,
+                   Torus32 *u_out, Torus32 *prod_out) {
+    const std::string w = std::string(who) + ": ";
+    selector_checked(w, sel);
+    if (!ring || (!u_out && !prod_out)) api_fail(w + "null argument");
+    if (sample < 0 || sample >= sel->nbits) api_fail(w + "bit_index must be in 0.." + std::to_string(sel->nbits - 1));
+    if (R < 1 || R > CMUX_MAX_COUNT) api_fail(w + "count must be in 1.." + std::to_string(CMUX_MAX_COUNT));
+    const int N = sel->p.N;
+    if (u_out) {
+        if (width < 1 || width > N || (width & (width - 1))) api_fail(w + "width must be a power of two in 1.." + std::to_string(N));
+        const int64_t S = N / width;
+        if (M <= (R - 1) * S || M > R * S) api_fail(w + "M must name an entry of the last of the R samples");
+    }
+    auto g = recorder_lock();
+    finish_flight_locked();                                   // (the row buffer is the unpack's)
+    const Engine::SelectorImage *img = select_image(sel);
+    Engine::get().run_inner(img, sel->p, sample, nullptr, ring, R, false, M, u_out ? width : N, nullptr, nullptr, u_out, prod_out, true);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -129,6 +183,27 @@ int tfhe_hip_tgsw_encrypt_bits(const TFheGateBootstrappingSecretKeySet *secret, 
 int tfhe_hip_tgsw_encrypt_bits_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
                                       Torus32 *out_words, uint64_t seed) {
     return tgsw_encrypt_impl("tfhe_hip_tgsw_encrypt_bits_seeded", secret, bits, count, out_words, &seed);
+}
+
+int tfhe_hip_tgsw_encrypt_polys(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *polys, int32_t count,
+                                Torus32 *out_words) {
+    return tgsw_encrypt_impl("tfhe_hip_tgsw_encrypt_polys", secret, polys, count, out_words, nullptr, true);
+}
+int tfhe_hip_tgsw_encrypt_polys_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *polys, int32_t count,
+                                       Torus32 *out_words, uint64_t seed) {
+    return tgsw_encrypt_impl("tfhe_hip_tgsw_encrypt_polys_seeded", secret, polys, count, out_words, &seed, true);
+}
+
+int tfhe_hip_ring_center_words(const TFheGateBootstrappingParameterSet *params, Torus32 *words, int64_t count) {
+    const std::string w = "tfhe_hip_ring_center_words: ";
+    if (!params || !params->in_out_params || !words) { set_error(w + "null argument"); return -1; }
+    if (count < 0) { set_error(w + "count must not be negative"); return -1; }
+    const Params &p = params_of(params);
+    const int low = 32 - p.l * p.Bgbit;                    // the bits the decomposition drops
+    if (low <= 0) return 0;
+    const uint32_t half = 1u << (low - 1);
+    for (int64_t j = 0; j < count; ++j) words[j] = (Torus32)((uint32_t)words[j] + half);
+    return 0;
 }
 
 TfheHipSelector *tfhe_hip_new_selector(const TFheGateBootstrappingParameterSet *params, const Torus32 *words, int32_t nbits) {
@@ -208,6 +283,27 @@ int tfhe_hip_kernel_ring_cmux(const TfheHipSelector *sel, int32_t bit_index, con
         Engine::get().run_cmux(img, sel->p, bit_index, d1_words, d0_words, count, out_words);
         return 0;
     });
+}
+
+int tfhe_hip_ring_inner(const TfheHipSelector *sel, int32_t sample_index, const TFheGateBootstrappingCloudKeySet *bk,
+                        const Torus32 *ring_words, int32_t M, int32_t width, LweSample *result) {
+    return guarded_rc([&] { return inner_impl("tfhe_hip_ring_inner", sel, sample_index, bk, ring_words, M, width, result, false); });
+}
+int tfhe_hip_ring_inner_device(const TfheHipSelector *sel, int32_t sample_index, const TFheGateBootstrappingCloudKeySet *bk,
+                               const void *device_ring_words, int32_t M, int32_t width, LweSample *result) {
+    return guarded_rc([&] {
+        return inner_impl("tfhe_hip_ring_inner_device", sel, sample_index, bk, static_cast<const Torus32 *>(device_ring_words), M, width,
+                          result, true);
+    });
+}
+
+int tfhe_hip_kernel_ring_product(const TfheHipSelector *sel, int32_t bit_index, const Torus32 *ring_words, int32_t count,
+                                 Torus32 *out_words) {
+    return guarded_rc([&] { return inner_raw_impl("tfhe_hip_kernel_ring_product", sel, bit_index, ring_words, count, 0, 0, nullptr, out_words); });
+}
+int tfhe_hip_kernel_ring_inner_rows(const TfheHipSelector *sel, int32_t bit_index, const Torus32 *ring_words, int32_t R, int32_t M,
+                                    int32_t width, Torus32 *out_rows) {
+    return guarded_rc([&] { return inner_raw_impl("tfhe_hip_kernel_ring_inner_rows", sel, bit_index, ring_words, R, M, width, out_rows, nullptr); });
 }
 
 double tfhe_hip_last_select_ms(void) {

@@ -130,3 +130,115 @@ def lookup_template(selector, ring_gallery, M, width, key):
     else:
         api.unpack(words, key, bits, count=width)
     return bits
+
+
+# ---- Hamming 1-to-N by encrypted inner products (include/tfhe_hip.h "encrypted inner products") ----
+def inner_delta(width):
+    """Delta = 2^-(log2 width + 2) as a torus word: `width` disagreeing bits reach 1/4"""
+    if width < 1 or width & (width - 1):
+        raise ValueError("width must be a power of two")
+    return (1 << 30) // width
+
+
+def inner_round_gallery(words, params):
+    """Every word of ring samples + 2^(31 - l Bgbit), wrapping (tfhe_hip_ring_center_words): half a step of the offset
+    decomposition, which keeps the top l Bgbit bits of a word and so errs by [0, 2 eps) -- a MEAN of eps per coefficient that
+    a probe of coefficient sum s multiplies by up to s (1 + N / 2) (1.6e-2 at P128 for 128 equal bits).  With the half step
+    in place the kept digits are those of the rounded word and the error is the zero-mean [-eps, eps) the header's rounding
+    term assumes.  A public operation on ciphertext words: client or server may apply it, once.  Returns a copy."""
+    w = np.ascontiguousarray(words, dtype=np.int32).copy()
+    flat = w.reshape(-1)
+    if _l.load().tfhe_hip_ring_center_words(params.ptr, api._i32p(flat), flat.size) != 0:
+        raise RuntimeError(api.last_error())
+    return w
+
+
+def pack_gallery_inner(entries, width, secret, seed=None):
+    """Enrolment for match_by_inner: M entries of `width` bits each in pack_gallery's layout (S = N / width per ring sample,
+    bit j of entry i at coefficient (i mod S) width + j of sample i / S), a bit of 1 carried at amplitude Delta =
+    2^-(log2 width + 2) and a bit of 0 as 0 (api.ring_encrypt), the words then centred for the decomposition
+    (inner_round_gallery).  Returns int32 [R][(k+1) N]; seed: the reproducible form, sample r drawn from seed + r."""
+    N = secret.params.N
+    R = api.lookup_samples(secret.params, len(entries), width)
+    S, delta = N // width, inner_delta(width)
+    out = []
+    for r in range(R):
+        mu = np.zeros(N, dtype=np.int64)
+        for e, entry in enumerate(entries[r * S:(r + 1) * S]):
+            bits = [int(b) & 1 for b in entry]
+            if len(bits) != width:
+                raise ValueError("every entry carries %d bits" % width)
+            mu[e * width:(e + 1) * width] = np.asarray(bits, dtype=np.int64) * delta
+        out.append(api.ring_encrypt(mu.astype(np.int32), secret, seed=None if seed is None else seed + r))
+    return inner_round_gallery(np.stack(out), secret.params)
+
+
+def hamming_probe_poly(bits, N):
+    """sum_i s_i X^(-i) with s_i = 1 - 2 b_i: p[0] = s_0, p[N - i] = -s_i -> int32 [N]"""
+    s = 1 - 2 * (np.asarray(bits, dtype=np.int64).reshape(-1) & 1)
+    if not 1 <= len(s) <= N:
+        raise ValueError("a probe carries 1..%d bits" % N)
+    p = np.zeros(N, dtype=np.int32)
+    p[0] = s[0]
+    for i in range(1, len(s)):
+        p[N - i] = -s[i]
+    return p
+
+
+def hamming_probe(bits, width, secret, seed=None):
+    """The client's probe for match_by_inner over a gallery of `width`-bit entries: (the TGSW words of sum_i (1 - 2 b_i)
+    X^(-i), ready for api.Selector, and a CiphertextArray of ONE sample that encrypts (sum_i b_i) Delta, the addend that turns
+    the inner product into the Hamming distance; Delta is the gallery's, 2^-(log2 width + 2)).  len(bits) must be `width`.
+    seed: the reproducible TGSW form."""
+    params = secret.params
+    b = np.asarray(bits, dtype=np.int64).reshape(-1) & 1
+    if len(b) != width:
+        raise ValueError("the probe carries %d bits, the gallery's entries %d" % (len(b), width))
+    words = api.tgsw_encrypt_polys(hamming_probe_poly(b, params.N)[None, :], secret, seed=seed)
+    addend = api.CiphertextArray(params, 1)
+    api.encrypt_torus(addend.at(0), int(b.sum()) * inner_delta(width), secret)
+    return words, addend
+
+
+def inner_decision_sigma(params):
+    """sigma_dec of the header, COMPUTED (torus units): the unpack's key switch, N t ks_stdev^2 + (N / 2) prec^2 / 3, plus
+    the bootstrap's modulus switch, (1 + n / 2) / (12 (2N)^2)"""
+    ks_stdev = params.ptr.contents.in_out_params.contents.alpha_min
+    N, n = params.N, params.n
+    prec = 2.0 ** -(1 + params.ks_basebit * params.ks_t)
+    return (N * params.ks_t * ks_stdev ** 2 + (N / 2.0) * prec ** 2 / 3.0 + (1.0 + n / 2.0) / (12.0 * (2.0 * N) ** 2)) ** 0.5
+
+
+def inner_decision_band(params, width):
+    """The smallest integer g with (g - 1/2) Delta >= 6 sigma_dec: match_by_inner's answer for an entry at distance d is
+    guaranteed only where |d - tau| >= g.  12 at P128 and width 128, 2 at width 16."""
+    delta = inner_delta(width) / 2.0 ** 32
+    g = 1
+    while (g - 0.5) * delta < 6.0 * inner_decision_sigma(params):
+        g += 1
+    return g
+
+
+def match_by_inner(selector, gallery, M, width, addend, tau, key, sample=0):
+    """Hamming 1-to-N in one product launch, one key switch and one level of M bootstraps: api.ring_inner of sample
+    `sample` of `selector` (hamming_probe's words) over a gallery pack_gallery_inner made (host words, or an int32 torch
+    tensor resident on the device), then per entry (tau + 1/2) Delta - (inner + addend) (api.linear, recorded) and the LUT
+    bootstrap with the constant 1/8, and one flush.  Returns a CiphertextArray of M match bits, TRUE iff distance <= tau --
+    NOT exact within inner_decision_band of the threshold -- ready for pack_match_bits."""
+    params = selector.params
+    device = hasattr(gallery, "data_ptr")
+    delta = inner_delta(width)
+    inner = api.CiphertextArray(params, M)
+    api.ring_inner(selector, sample, gallery, M, width, key, inner, device=device)
+    lin = api.CiphertextArray(params, M)
+    c0 = (2 * int(tau) + 1) * delta // 2
+    for i in range(M):
+        api.linear(lin.at(i), [inner.at(i), addend.at(0)], [-1, -1], c0, key)
+    lut = api.Lut.constant(params, 1 << 29)
+    bits = api.CiphertextArray(params, M)
+    api.lut_bootstrap_batch(lut, bits, [lin], [1], 0, key)
+    api.flush()                                               # (the device form's gallery has been read by now)
+    lut.close()
+    for o in (inner, lin):
+        o.close()
+    return bits

@@ -322,6 +322,13 @@ SIGNATURES = {
     "tfhe_hip_ring_lookup": (C.c_int, [C.c_void_p, I32P, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_ring_lookup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "tfhe_hip_kernel_ring_cmux_rotate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, I32P, C.c_int32, I32P]),
+    "tfhe_hip_tgsw_encrypt_polys": (C.c_int, [SK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_tgsw_encrypt_polys_seeded": (C.c_int, [SK, I32P, C.c_int32, I32P, C.c_uint64]),
+    "tfhe_hip_ring_center_words": (C.c_int, [PS, I32P, C.c_int64]),
+    "tfhe_hip_ring_inner": (C.c_int, [C.c_void_p, C.c_int32, CK, I32P, C.c_int32, C.c_int32, LS]),
+    "tfhe_hip_ring_inner_device": (C.c_int, [C.c_void_p, C.c_int32, CK, C.c_void_p, C.c_int32, C.c_int32, LS]),
+    "tfhe_hip_kernel_ring_product": (C.c_int, [C.c_void_p, C.c_int32, I32P, C.c_int32, I32P]),
+    "tfhe_hip_kernel_ring_inner_rows": (C.c_int, [C.c_void_p, C.c_int32, I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])

@@ -178,6 +178,26 @@ def run_packed_gallery(params, key, templates, claimed, probes, bound, width=128
     return out
 
 
+def run_inner_product(params, key, templates, probe, tau, width=128):
+    """Client and server of identify.match_by_inner once: the client enrols the gallery (pack_gallery_inner) and sends the
+    probe (hamming_probe); the server answers one match bit per template; the client decrypts.  Yields one record per
+    template: its distance, the plaintext decision, the decrypted one and whether the distance lies inside the computed
+    band around tau where the decision is not guaranteed."""
+    from . import identify
+    gallery = identify.pack_gallery_inner(templates, width, key)          # client, at enrolment
+    tgsw, addend = identify.hamming_probe(probe, width, key)                     # client, per query
+    selector = api.Selector(params, tgsw)                                 # server
+    bits = identify.match_by_inner(selector, gallery, len(templates), width, addend, tau, key)
+    got = [int(b) for b in bits.decrypt(key)]                             # client
+    g = identify.inner_decision_band(params, width)
+    for i, t in enumerate(templates):
+        d = sum(int(x) ^ int(y) for x, y in zip(t, probe))
+        yield {"entry": i, "distance": d, "plain": int(d <= tau), "decrypted": got[i], "inside_band": abs(d - tau) < g}
+    selector.close()
+    for o in (bits, addend):
+        o.close()
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--nslots", type=int, default=128)
@@ -195,8 +215,15 @@ def parse_args(argv=None):
     ap.add_argument("--packed-gallery", action="store_true",
                     help="Hamming match of one claimed identity against a gallery of 128-bit templates packed eight to a ring "
                          "sample: looked up under TGSW-encrypted index bits, the server does not learn which")
-    ap.add_argument("--entries", type=int, default=20, help="--packed-gallery: templates in the gallery")
+    ap.add_argument("--entries", type=int, default=20, help="--packed-gallery, --inner-product: templates in the gallery")
+    ap.add_argument("--inner-product", action="store_true",
+                    help="Hamming 1-to-N of one probe against the whole packed gallery by encrypted inner products: one external "
+                         "product per ring sample, one key switch, one level of bootstraps (not exact near the threshold)")
     a = ap.parse_args(argv)
+    if a.inner_product and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.packed_gallery or a.compressed_keys):
+        ap.error("--inner-product runs alone")
+    if a.inner_product and not 1 <= a.entries <= 1 << 20:
+        ap.error("--entries must be in 1..2^20")
     if a.packed_gallery and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast):
         ap.error("--packed-gallery runs the single-client Hamming match alone")
     if a.packed_gallery and not 1 <= a.entries <= 1 << 20:
@@ -246,6 +273,20 @@ def main():
     params = api.ParameterSet(128)
     key = api.SecretKeySet(params, a.seed + 1, device=not a.compressed_keys)
     cloud = shipped_cloud(key) if a.compressed_keys else None
+    if a.inner_product:
+        import random
+        rnd = random.Random(a.seed)
+        probe = [rnd.getrandbits(1) for _ in range(128)]
+        templates = []
+        for i in range(a.entries):                                        # every third template near the probe
+            t = list(probe) if i % 3 == 0 else [rnd.getrandbits(1) for _ in range(128)]
+            for j in rnd.sample(range(128), (5 * i) % 29):
+                t[j] ^= 1
+            templates.append(t)
+        for out in run_inner_product(params, key, templates, probe, tau=40):
+            print(json.dumps(out))
+        key.close()
+        return
     if a.packed_gallery:
         import random
         rnd = random.Random(a.seed)
