@@ -279,14 +279,32 @@ struct AccLds {
 // 1 for the second, 2 from the third (blind_rotate4_body raises it to 3 for the step's tail).
 // V: instantiation tag -- the multi-key kernels pass 1, so that the row lambda below is a function of their own and the
 // single-key kernels compile exactly as they would alone
-template <int LOGN, bool FRESH, bool TABLE, bool LDSTW = false, bool PROGRESS = false, int V = 0>
+// HELD (forms with LDSTW): the second- and third-pass twiddles are read from the workgroup's LDS image ONCE per call --
+// once per step and input polynomial, in front of the gadget rows -- and every row's transform uses those registers,
+// instead of every row reading them again (12 ds_read_b128 per row at N = 1024).  held: the caller's own copy, loaded
+// once per rotation (BR_HELD_TW = 2); then nothing is read here at all.
+struct NoHeldTw {};
+template <int LOGN>
+struct HeldTw {
+    typename WaveNtt<LOGN>::FwdTw1 t1;
+    typename WaveNtt<LOGN>::FwdTw2 t2;
+    __device__ __forceinline__ void from_images(const PrimeCtx &c) {
+        t1.from_image(static_cast<const uint4 *>(c.fw1));
+        t2.from_image(static_cast<const uint4 *>(c.fw2));
+    }
+};
+template <int LOGN, bool FRESH, bool TABLE, bool LDSTW = false, bool PROGRESS = false, int V = 0, int HELD = 0>
 __device__ __forceinline__ void forward_poly(const DevParams &p, const DevKey &key, const PrimeCtx &c,
                                              const AccLds<LOGN> &lds_acc, uint32_t *scr,
                                              int lane, int q, int i, int u, int abar, bool swap_outputs,
                                              int64_t (&acc0)[WaveNtt<LOGN>::REGS], int64_t (&acc1)[WaveNtt<LOGN>::REGS],
-                                             const typename WaveNtt<LOGN>::FwdTw0 &t0, int jbegin = 0, int jend = -1) {
+                                             const typename WaveNtt<LOGN>::FwdTw0 &t0, int jbegin = 0, int jend = -1,
+                                             const HeldTw<LOGN> *held = nullptr) {
     using NTT = WaveNtt<LOGN>;
     constexpr int N = NTT::N, REGS = NTT::REGS, G4 = REGS / 4;
+    static_assert(HELD == 0 || LDSTW, "held twiddles come from the LDS image");
+    std::conditional_t<HELD == 1, HeldTw<LOGN>, NoHeldTw> own;      // HELD: 0 no, 1 loaded here, 2 the caller's (*held)
+    if constexpr (HELD == 1) own.from_images(c);
     uint32_t Dk[REGS];
     lds_acc.template rotated_difference<REGS>(Dk, u, lane, abar, p.decomp_offset);
     const int o0 = swap_outputs ? N / 4 : 0, o1 = N / 4 - o0;          // uint4 offset of output poly 0 / 1
@@ -303,7 +321,9 @@ __device__ __forceinline__ void forward_poly(const DevParams &p, const DevKey &k
         for (int g = 0; g < G4; ++g) b1[g] = bp[o1 + g * 64];
         const int shift = 32 - (jj + 1) * width;
         int32_t x[REGS];
-        NTT::template forward_digits<TABLE, LDSTW>(x, Dk, shift, width, c, scr, lane, t0);
+        if constexpr (HELD == 1) NTT::template forward_digits<TABLE>(x, Dk, shift, width, c, scr, lane, t0, own.t1, own.t2);
+        else if constexpr (HELD == 2) NTT::template forward_digits<TABLE>(x, Dk, shift, width, c, scr, lane, t0, held->t1, held->t2);
+        else NTT::template forward_digits<TABLE, LDSTW>(x, Dk, shift, width, c, scr, lane, t0);
 #pragma unroll
         for (int g = 0; g < G4; ++g) {
             const int32_t bb0[4] = {(int32_t)b0[g].x, (int32_t)b0[g].y, (int32_t)b0[g].z, (int32_t)b0[g].w};
@@ -497,14 +517,27 @@ __device__ unsigned long long g_stamps[8][8];      // [wave][phase]; the 4-wave 
 // wave (q,u) works modulo prime q on input polynomial u (l forward NTTs), hands
 // the partial sum of the other output polynomial to wave (q,1-u), runs ONE
 // inverse NTT for output polynomial u, and shares the CRT with wave (1-q,u).
-// Three workgroup barriers per step.  N = 1024 only (241 VGPRs, two workgroups per CU): D and both 64-bit row sums in
-// registers, a pass's twiddles loaded one transpose ahead, three exchange buffers per wave.  (N = 2048 runs the split form:
+// Three workgroup barriers per step.  N = 1024 only (242 VGPRs, two workgroups per CU): D, both 64-bit row sums and the
+// forward transforms' twiddles in registers (BR_HELD_TW), the inverse transform's twiddles read from LDS one transpose
+// ahead, three exchange buffers per wave.  (N = 2048 runs the split form:
 // 32 coefficients per lane do not fit the register file without reducing both sums per row, 196 against 142 ms per 4,096.)
 // ---------------------------------------------------------------------------
-// LDS of one 4-wave workgroup (81,428 B: two per CU).  Each wave has two exchange areas: the scratch of its NTT
+// LDS of one 4-wave workgroup (81,648 B: two per CU).  Each wave has two exchange areas: the scratch of its NTT
 // transposes (private while a transform runs; from the end of its inverse transform to the step's last barrier it carries
 // the residues of the half its CRT partner recombines -- nobody else touches it in between) and the partial sums it sends
 // to the wave of the other input polynomial.
+// How long a wave of the 4-wave form holds the second- and third-pass twiddles of its forward transforms in registers
+// (they are the same for every row, step and rotation; a measurement switch like BR_TAB_GROUPS):
+//   0: not at all -- every row's transform reads them from the workgroup's LDS image (rounds 3-6);
+//   1: for the gadget rows of a step -- read from the image once per step (forward_poly HELD);
+//   2: for the whole rotation -- loaded from global memory once, next to the first pass's; the image's place in LDS then
+//      holds images of the INVERSE transform's twiddles instead, and a step's only vector-memory loads are its key rows.
+// Measured, variants interleaved on one box: profiles/held_twiddles_ab.txt.
+// 4,096 P128 rotations 36.31 (0) -> 36.08 (1) -> 34.98 ms (2), parent against parent 0.00; 512: 5.08 -> 5.08 -> 4.98.
+// At 2 every instantiation has fewer registers than at 0 and none spills; at 1 the multi-key table form spills 12 bytes.
+#ifndef BR_HELD_TW
+#define BR_HELD_TW 2
+#endif
 template <int LOGN>
 struct Br4Lds {
     using NTT = WaveNtt<LOGN>;
@@ -513,10 +546,18 @@ struct Br4Lds {
     uint32_t buf1[4][NTT::ROW_WORDS];              // per wave: the partial sums sent (rows only: layout R)
     uint16_t bar[1024 + 8];                        // modulus-switched mask and body
     alignas(8) uint32_t dtab[2][5 * DIGIT_TAB];    // per prime: first-step products of the gadget digits (ntt_wave.hpp)
+#if BR_HELD_TW == 2
+    // per prime: the inverse transform's twiddles -- first pass (one image per lane), second pass (one per group of 2^LC
+    // lanes) and last pass (lane-uniform)
+    uint4 it2[2][64][NTT::InvTw2::IMAGE16];
+    uint4 it1[2][64 >> NTT::LC][NTT::InvTw1::IMAGE16];
+    uint4 it0[2][NTT::InvTw0::IMAGE16];
+#else
     // per prime: the forward transforms' second-pass twiddles (one image per group of 2^LC lanes) and third-pass
     // twiddles (one per lane)
     uint4 ft1[2][64 >> NTT::LC][NTT::FwdTw1::IMAGE16];
     uint4 ft2[2][64][NTT::FwdTw2::IMAGE16];
+#endif
     __device__ __forceinline__ uint32_t *scr(int wv) { return buf0[wv]; }
     __device__ __forceinline__ uint32_t *x1(int wv) { return buf1[wv]; }
     __device__ __forceinline__ uint32_t *x2(int wv) { return buf0[wv]; }
@@ -546,6 +587,21 @@ __device__ __forceinline__ void blind_rotate4_body(const DevParams &p, const Dev
         NTT::build_digit_table(sh.dtab[q], c, p.Bgbit, (u << 6) | lane, 128);
         c.dtab = sh.dtab[q];
     }
+#if BR_HELD_TW == 2
+    // wave (q, 0) copies prime q's INVERSE twiddles into LDS, once (the forward ones are held in registers: below)
+    if (u == 0) {
+        typename NTT::InvTw2 a;
+        a.load(c, lane);
+        a.to_image(sh.it2[q][lane]);
+        typename NTT::InvTw1 b;
+        b.load(c, lane);
+        if ((lane & ((1 << NTT::LC) - 1)) == 0) b.to_image(sh.it1[q][lane >> NTT::LC]);
+        typename NTT::InvTw0 d;
+        d.load(c, lane);
+        if (lane == 0) d.to_image(sh.it0[q]);
+    }
+    const uint4 *const iw2 = sh.it2[q][lane], *const iw1 = sh.it1[q][lane >> NTT::LC], *const iw0 = sh.it0[q];
+#else
     // wave (q, 0) copies prime q's pass-2 / pass-3 twiddles of the forward transforms into LDS, once
     if (u == 0) {
         typename NTT::FwdTw1 a;
@@ -557,6 +613,7 @@ __device__ __forceinline__ void blind_rotate4_body(const DevParams &p, const Dev
     }
     c.fw1 = sh.ft1[q][lane >> NTT::LC];
     c.fw2 = sh.ft2[q][lane];
+#endif
     __syncthreads();
     if (q == 0) {
         const int barb = sh.bar[n];
@@ -572,6 +629,11 @@ __device__ __forceinline__ void blind_rotate4_body(const DevParams &p, const Dev
     STAMP_DECL;
     typename NTT::FwdTw0 t0;                 // first-pass twiddles of every forward transform: loaded once (forward_poly)
     t0.load(c, lane);
+#if BR_HELD_TW == 2
+    HeldTw<LOGN> held;                       // and the second and third pass's, per lane: held for the whole rotation
+    held.t1.load(c, lane);
+    held.t2.load(c, lane);
+#endif
 
     // Issue priority by PROGRESS (round 5).  The workgroups that share a CU put one wave each on every SIMD, and the SIMD
     // arbitrates their issue by priority, then age: left alone, the older workgroup runs at the pace of a lone wave and the
@@ -589,7 +651,13 @@ __device__ __forceinline__ void blind_rotate4_body(const DevParams &p, const Dev
 
         // acc0 accumulates output poly u (kept), acc1 output poly 1-u (sent to wave (q,1-u)); both in 64 bits, reduced once
         int64_t acc0[REGS], acc1[REGS];
-        forward_poly<LOGN, true, TAB, true, true, V>(p, key, c, sh.acc, scr, lane, q, i, u, abar, u != 0, acc0, acc1, t0);
+#if BR_HELD_TW == 2
+        forward_poly<LOGN, true, TAB, true, true, V, 2>(p, key, c, sh.acc, scr, lane, q, i, u, abar, u != 0, acc0, acc1, t0,
+                                                        0, -1, &held);
+#else
+        forward_poly<LOGN, true, TAB, true, true, V, BR_HELD_TW>(p, key, c, sh.acc, scr, lane, q, i, u, abar, u != 0, acc0,
+                                                                 acc1, t0);
+#endif
         STAMP(1);
 
         int32_t t[REGS];
@@ -604,7 +672,11 @@ __device__ __forceinline__ void blind_rotate4_body(const DevParams &p, const Dev
         }
         // the first twiddles of the inverse transform are requested before the barrier and arrive while the wave waits
         typename NTT::InvTw2 t2;
+#if BR_HELD_TW == 2
+        t2.from_image(iw2);
+#else
         t2.load(c, lane);
+#endif
         STAMP(2);
         lds_barrier();
         __builtin_amdgcn_s_setprio(3);                    // the step's tail (above: progress priority)
@@ -617,7 +689,11 @@ __device__ __forceinline__ void blind_rotate4_body(const DevParams &p, const Dev
         }
         // the inverse transform up to its last radix-4 step (signed residues, |t| < P: recombined as they are)
         typename NTT::InvTw0 ti0;
+#if BR_HELD_TW == 2
+        NTT::inverse_head(t, c, scr, lane, t2, ti0, iw1, iw0);
+#else
         NTT::inverse_head(t, c, scr, lane, t2, ti0);
+#endif
         STAMP(4);
 
         // CRT of output poly u is split with wave (1-q,u): wave q recombines registers [q*HALF, (q+1)*HALF)

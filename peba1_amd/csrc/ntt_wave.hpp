@@ -430,11 +430,27 @@ struct WaveNtt {
     template <bool TABLE, bool LDSTW = false>
     static __device__ __forceinline__ void forward_digits(int32_t (&x)[REGS], const uint32_t (&D)[REGS], int shift, int width,
                                                           const PrimeCtx &c, uint32_t *scr, int lane, const FwdTw0 &t0) {
+        forward_digits_then<TABLE>(x, D, shift, width, c, lane, t0, [&] { forward_tail<LDSTW>(x, c, scr, lane); });
+    }
+    // HELD form: the second- and third-pass twiddles are the caller's registers (t1, t2: loaded once for many transforms,
+    // from the LDS image or from global memory) -- the transform itself reads no twiddle at all.  Same operations on the
+    // same operands as the LDSTW form.
+    template <bool TABLE>
+    static __device__ __forceinline__ void forward_digits(int32_t (&x)[REGS], const uint32_t (&D)[REGS], int shift, int width,
+                                                          const PrimeCtx &c, uint32_t *scr, int lane, const FwdTw0 &t0,
+                                                          const FwdTw1 &t1, const FwdTw2 &t2) {
+        forward_digits_then<TABLE>(x, D, shift, width, c, lane, t0, [&] { forward_tail(x, c, scr, lane, t1, t2); });
+    }
+    // the digits and the first pass (or, TABLE, its first step from the table and the rest of it), then tail(): the
+    // second and third pass in the caller's form
+    template <bool TABLE, typename TAIL>
+    static __device__ __forceinline__ void forward_digits_then(int32_t (&x)[REGS], const uint32_t (&D)[REGS], int shift, int width,
+                                                               const PrimeCtx &c, int lane, const FwdTw0 &t0, TAIL tail) {
         if constexpr (!TABLE) {
 #pragma unroll
             for (int r = 0; r < REGS; ++r) x[r] = __builtin_amdgcn_sbfe((int32_t)D[r], shift, width);
             fwd_pass(x, c, t0);
-            forward_tail<LDSTW>(x, c, scr, lane);
+            tail();
         } else {
             static_assert(FwdTw0::PAIR && FwdTw0::CNT == 1, "the first step is a radix-4 step with one block");
             constexpr int RBIT = rbit_of(0), h = 1 << RBIT, l = h >> 1;
@@ -466,7 +482,9 @@ struct WaveNtt {
                     const int32_t u = x0 + A, v = x0 - A;
                     x[r] = u + S; x[r | l] = u - S; x[r | h] = v + T; x[r | h | l] = v - T;
                 }
-            forward_rest<LDSTW>(x, c, scr, lane, t0);
+            static_assert(FwdTw0::PAIR, "the first step is a radix-4 step");
+            if constexpr (RB > 2) fwd_pass(x, c, t0.rest);               // the other steps of the first pass
+            tail();
         }
     }
     // everything after the first radix-4 step of a forward transform (for callers that produce that
@@ -492,6 +510,22 @@ struct WaveNtt {
         fwd_pass(x, c, t1);
         FwdTw2 t2;
         if constexpr (LDSTW) t2.from_image(static_cast<const uint4 *>(c.fw2)); else t2.load(c, lane);
+#pragma unroll
+        for (int r = 0; r < REGS; ++r) scr[t2_l1_addr(lane, r)] = (uint32_t)x[r];
+        wave_lds_fence();
+        read_row(x, scr, lane);
+        wave_lds_fence();
+        fwd_pass(x, c, t2);
+    }
+    // the same with both passes' twiddles held by the caller
+    static __device__ __forceinline__ void forward_tail(int32_t (&x)[REGS], const PrimeCtx &c, uint32_t *scr, int lane,
+                                                        const FwdTw1 &t1, const FwdTw2 &t2) {
+#pragma unroll
+        for (int r = 0; r < REGS; ++r) scr[t1_l0_addr(lane, r)] = (uint32_t)x[r];
+        wave_lds_fence();
+        read_row(x, scr, lane);
+        wave_lds_fence();
+        fwd_pass(x, c, t1);
 #pragma unroll
         for (int r = 0; r < REGS; ++r) scr[t2_l1_addr(lane, r)] = (uint32_t)x[r];
         wave_lds_fence();
@@ -546,18 +580,20 @@ struct WaveNtt {
     // the half named by UPPER_FIRST final first, calls emit() (the caller's stores of that half), then finishes the
     // other half: the stores and whoever waits for them run under the rest of the step.  Same operations on the same
     // operands as inverse(): every output word is what it was.
+    // img1, img0: LDS images of this lane's second- and last-pass twiddles (PassTw::to_image) to read instead of global memory
     static __device__ __forceinline__ void inverse_head(int32_t (&x)[REGS], const PrimeCtx &c, uint32_t *scr, int lane,
-                                                        const InvTw2 &t2, InvTw0 &t0) {
+                                                        const InvTw2 &t2, InvTw0 &t0, const uint4 *img1 = nullptr,
+                                                        const uint4 *img0 = nullptr) {
         inv_pass<0>(x, c, t2);
         InvTw1 t1;
-        t1.load(c, lane);
+        if (img1) t1.from_image(img1); else t1.load(c, lane);
         write_row_h(x, scr, lane);
         wave_lds_fence();
 #pragma unroll
         for (int r = 0; r < REGS; ++r) x[r] = (int32_t)scr[h_t2_addr(lane, r)];
         wave_lds_fence();
         inv_pass<steps_in(LC)>(x, c, t1);
-        t0.load(c, lane);
+        if (img0) t0.from_image(img0); else t0.load(c, lane);
         write_row_h(x, scr, lane);
         wave_lds_fence();
 #pragma unroll

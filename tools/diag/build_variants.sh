@@ -17,6 +17,6 @@ done
 wait
 for spec in "$@"; do
   name=${spec%%=*}
-  $ROCM/bin/hipcc -shared -Wl,-Bsymbolic-functions -o $O/libtfhe-hip-$name.so $O/kernels-$name.o $S/host_keys.o $S/engine.o $S/shim.o $S/scheduler.o $S/io.o
+  $ROCM/bin/hipcc -shared -Wl,-Bsymbolic-functions -o $O/libtfhe-hip-$name.so $O/kernels-$name.o $S/pack.o $S/unpack.o $S/expand.o $S/cmux.o $S/ks_matrix.o $S/host_keys.o $S/engine.o $S/shim.o $S/scheduler.o $S/io.o
   echo "built $O/libtfhe-hip-$name.so"
 done
