@@ -1140,6 +1140,90 @@ int tfhe_hip_kernel_ring_product(const TfheHipSelector *selector, int32_t bit_in
 int tfhe_hip_kernel_ring_inner_rows(const TfheHipSelector *selector, int32_t bit_index, const Torus32 *ring_words, int32_t R,
                                     int32_t M, int32_t width, Torus32 *out_rows);
 
+/* ---- ring sample times public polynomials: one probe against a CLEAR gallery, or a clear probe against an encrypted one ----
+ * The product of a ring sample with a polynomial the server knows needs no gadget, no decomposition and no TGSW sample:
+ * q (a, b) = (q a, q b).  No key material at all for the product; the cloud key serves the key switch alone.  k = 1, N = 1024
+ * or 2048.
+ *
+ * Public polynomial.  q is N int32 coefficients with |q[j]| <= T, T = TFHE_HIP_PUBLIC_MAX_COEF(N) the largest power of two
+ * with N T 2^31 < CRT_EXACT_LIMIT (peba1_amd/csrc/ntt_field.hpp, 0.36 P0 P1 = 2^52.5): 2^11 at N = 1024, 2^10 at N = 2048
+ * (peba1_amd/csrc/ring_public.hpp derives it; a static_assert ties the macro to it).  Worst case, which reaches N T 2^31
+ * exactly at coefficient N - 1: all q[j] = -T against words 0x80000000.
+ * Product.  (q * c)[u] = q(X) c[u](X) for u = 0 and 1, in Z[X]/(X^N + 1), the words of c taken as signed 32-bit integers,
+ * the result wrapping mod 2^32: coefficient m is sum_(i+j=m) q[i] c[u][j] - sum_(i+j=m+N) q[i] c[u][j].  q = 1 is the
+ * identity; q = X^r gives (X^r c)[u][j] = c[u][j - r] for j >= r and -c[u][j - r + N] below it -- the private lookup's
+ * monomial convention with the sign of the exponent flipped: X^r (X^(-r) c) = c.
+ * Inner products.  The layouts are those of the encrypted inner products above: one factor in the lookup's gallery layout
+ * (entry e on coefficients e w .. e w + w - 1, S = N / w entries to a polynomial), the other in the probe layout
+ * p = sum_i s_i X^(-i).  Coefficient e w of the product is the inner product with entry e alone -- the argument stated
+ * there ("Why.") is symmetric in the two factors and holds whichever of them is the ciphertext.
+ * In the headline use the PROBE is the ring sample -- the client encrypts the torus polynomial s_i Delta in probe layout,
+ * mu[0] = s_0 Delta, mu[N - i] = -s_i Delta, with tfhe_hip_ring_encrypt[_seeded] or its seed-compressed forms (8 KB, or
+ * 4,136 bytes, against the 48 KB of a TGSW probe at P128) -- and the GALLERY is R public polynomials of 0/1 coefficients:
+ *     result[i] = KeySwitch(Extract_((i mod S) w)(q_(i / S) * c))        for i < M <= R S,
+ * Extract and KeySwitch being those of tfhe_hip_unpack_samples, exactly as in tfhe_hip_ring_inner.  The product and the S
+ * extractions of a polynomial are ONE kernel launch of ceil(M / S) workgroups; the key switch is the unpack's.
+ * Variance before the key switch -- COMPUTED from the definition, not measured (torus units): |q|_2^2 times the ring
+ * sample's variance (bk_stdev^2 for a fresh one).  There is no other term, and no bias: nothing is decomposed, nothing is
+ * rounded, and there is nothing to centre.  For a 0/1 polynomial |q|_2^2 <= N:
+ *     P128 (N = 1024, bk_stdev 2^-25)            at most 2^-40 = 9.1e-13,  sigma <= 9.5e-7
+ *     the l = 2 set (N = 1024, bk_stdev 7.18e-9)   at most 5.3e-14,          sigma <= 2.3e-7
+ *     P2048 (N = 2048, bk_stdev 2^-25)           at most 2^-39 = 1.8e-12,  sigma <= 1.3e-6
+ * (the gadget does not enter; the TGSW route's sigma ~ 1.6e-4 at P128 is about 170 times the first).
+ * Hamming decision on top: UNCHANGED.  The same addend sample, tfhe_hip_linear, the constant-1/8 LUT bootstrap and the same
+ * peba1_amd.identify.inner_decision_band: the band is set by the key switch and the bootstrap's modulus switch, which this
+ * section does not touch.  THIS DOES NOT MAKE THE DECISION EXACT NEAR THE THRESHOLD; only the distance before the key switch
+ * gains (Delta / 2 = 9.8e-4 is a thousand sigma here).
+ * OUT OF SCOPE: Euclidean distance on 8-bit features (the range argument of the section above stands), an exact decision
+ * inside the band, multi-key batching, libpeba1-dist, k > 1, recording these calls in the op graph.
+ *
+ * tfhe_hip_new_public_gallery copies polys[R][N], 1 <= R <= 2^20; host only -- the device image (the canonical NTT residues
+ * under both primes, 8 KB a polynomial) is made once, at the first product, and kept on the card until the gallery is
+ * deleted.  Every argument is checked before the device is looked at; NULL with the error set for: a null pointer, k != 1
+ * or N outside {1024, 2048}, R out of range, a coefficient past T (the message names the first offending index).
+ * tfhe_hip_public_gallery_polys: R, or -1 with the error set for a null or deleted gallery.
+ * tfhe_hip_ring_mul_public: out[g] = q_(poly_index + (npolys == 1 ? 0 : g)) * c_(count == 1 ? 0 : g), (k+1) N words each.  npolys == 1 broadcasts one
+ * polynomial over `count` samples (the clear probe against an encrypted gallery); count == 1 broadcasts one sample over
+ * npolys polynomials; otherwise npolys == count and the product is pairwise: max(npolys, count) products in ONE launch,
+ * both at most 65,536.  Enqueued on tfhe_hip_stream() like the select: the call names no ciphertext slot, recorded
+ * operations stay recorded, nothing is flushed, a flush in flight is not waited for.  The host form returns with the words
+ * in place; the device form (both 16-byte aligned, the destination overlapping no ring word) with the work enqueued.
+ * Return 0, or -1 with the error set and the call without effect: a null pointer, a deleted gallery, npolys or count out
+ * of range, polynomials outside the gallery, npolys != count with neither 1, misaligned or overlapping device words, device
+ * memory exhausted.
+ * tfhe_hip_ring_inner_public follows tfhe_hip_ring_inner in every contract: every result is renamed into a fresh slot; all
+ * arguments are checked before anything changes; a flush in flight is completed first; recorded operations stay recorded;
+ * work runs in chunks of at most 8,192 rows; the host form returns with the slots written, the device form (the probe's
+ * (k+1) N words resident on the card, 16-byte aligned) with the work enqueued on tfhe_hip_stream().
+ * tfhe_hip_last_select_ms covers the product launch (and that of tfhe_hip_ring_mul_public).  Return 0, or -1 with the error
+ * set and the call without effect (results keep values and slots): a null pointer, a deleted gallery, a gallery of another
+ * ring (N, k) than the key's, width not a power of two in 1 .. N, M < 1, M past the R S entries of the gallery, misaligned
+ * device words, a result sample this library did not allocate or of another LWE dimension than the key's, M past the end of
+ * the result array, the slot pool exhausted, device memory exhausted. */
+#define TFHE_HIP_PUBLIC_MAX_COEF(N) ((N) == 2048 ? 1024 : (N) == 1024 ? 2048 : 0)
+typedef struct TfheHipPublicGallery TfheHipPublicGallery;
+TfheHipPublicGallery *tfhe_hip_new_public_gallery(const TFheGateBootstrappingParameterSet *params, const int32_t *polys, int32_t R);
+void tfhe_hip_delete_public_gallery(TfheHipPublicGallery *gallery);
+int32_t tfhe_hip_public_gallery_polys(const TfheHipPublicGallery *gallery);
+int tfhe_hip_ring_mul_public(const TfheHipPublicGallery *gallery, int32_t poly_index, int32_t npolys, const Torus32 *ring_words,
+                             int32_t count, Torus32 *out_ring_words);
+int tfhe_hip_ring_mul_public_device(const TfheHipPublicGallery *gallery, int32_t poly_index, int32_t npolys,
+                                    const void *device_ring_words, int32_t count, void *device_out);
+int tfhe_hip_ring_inner_public(const TfheHipPublicGallery *gallery, const TFheGateBootstrappingCloudKeySet *bk,
+                               const Torus32 *probe_ring_words, int32_t M, int32_t width, LweSample *result);
+int tfhe_hip_ring_inner_public_device(const TfheHipPublicGallery *gallery, const TFheGateBootstrappingCloudKeySet *bk,
+                                      const void *device_probe_ring_words, int32_t M, int32_t width, LweSample *result);
+/* raw test entry: the products of tfhe_hip_ring_mul_public's host form, after a flush in flight has completed */
+int tfhe_hip_kernel_ring_public_product(const TfheHipPublicGallery *gallery, int32_t poly_index, int32_t npolys,
+                                        const Torus32 *ring_words, int32_t count, Torus32 *out_words);
+/* raw test entry: the extracted rows before the key switch, out_rows[i] (kN+1 words) = Extract_((i mod S) width)(q_(i / S) *
+ * probe) for i < M <= R S; no slots involved */
+int tfhe_hip_kernel_ring_public_rows(const TfheHipPublicGallery *gallery, const Torus32 *probe_ring_words, int32_t M, int32_t width,
+                                     Torus32 *out_rows);
+/* host-logic test entry: 0 if coefficients up to T pass the CRT bound N T 2^31 < CRT_EXACT_LIMIT at ring size N, 1 if not;
+ * -1 with the error set for N outside {1024, 2048} or T < 1 */
+int tfhe_hip_test_public_bounds(int32_t N, int32_t T);
+
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through
  * the device NTT (two 27-bit primes + CRT); |ip| must be < 2^12 */

@@ -1114,6 +1114,115 @@ def kernel_ring_inner_rows(selector, bit, ring, M, width):
     return u
 
 
+def public_max_coef(N):
+    """T = TFHE_HIP_PUBLIC_MAX_COEF(N): the largest coefficient magnitude of a public polynomial (2^11 at N = 1024, 2^10
+    at N = 2048; include/tfhe_hip.h)"""
+    return {1024: 2048, 2048: 1024}.get(int(N), 0)
+
+
+class PublicGallery:
+    """R public small-integer polynomials [R][N], |coefficient| <= public_max_coef(N), that ring samples are multiplied by
+    (tfhe_hip_new_public_gallery): a clear gallery in ring_lookup's layout for ring_inner_public, or clear probes, weights
+    or projections for ring_mul_public.  The device image is made at the first product and kept until close()."""
+
+    def __init__(self, params, polys):
+        q = np.ascontiguousarray(polys, dtype=np.int32).reshape(-1, params.N)
+        self.params, self.count = params, q.shape[0]
+        self.ptr = _l.load().tfhe_hip_new_public_gallery(params.ptr, _i32p(q) if q.size else None, self.count)
+        if not self.ptr:
+            raise ValueError("public gallery rejected: " + last_error())
+
+    def close(self):
+        if self.ptr:
+            _l.load().tfhe_hip_delete_public_gallery(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _public_counts(gallery, first, npolys, count):
+    npolys = gallery.count - int(first) if npolys is None else int(npolys)
+    if npolys != 1 and count != 1 and npolys != count:
+        raise ValueError("npolys and the number of ring samples must be equal unless one of them is 1")
+    return npolys, max(npolys, count)
+
+
+def ring_mul_public(gallery, ring, first=0, npolys=None, device=False):
+    """q * c for public polynomials of `gallery` and ring samples `ring` (tfhe_hip_ring_mul_public): polynomials first ..
+    first + npolys - 1 (default: to the gallery's end).  One polynomial is broadcast over all samples, one sample over all
+    polynomials, otherwise the product is pairwise -> [max(npolys, count)][(k+1) N].  Recorded operations stay recorded.
+    device=False: host words in, a numpy array out.  device=True: `ring` is an int32 torch tensor resident on the engine's
+    device and the result a new tensor there, stream-ordered on tfhe_hip_stream()."""
+    p = gallery.params
+    sw = (p.k + 1) * p.N
+    L = _l.load()
+    if device:
+        import torch
+        if ring.dtype != torch.int32 or not ring.is_contiguous() or ring.numel() == 0 or ring.numel() % sw:
+            raise ValueError("device ring words are a contiguous int32 tensor of count (k+1) N words")
+        count = ring.numel() // sw
+        npolys, total = _public_counts(gallery, first, npolys, count)
+        out = torch.empty(total * sw, dtype=torch.int32, device=ring.device)
+        rc = L.tfhe_hip_ring_mul_public_device(gallery.ptr, int(first), npolys, C.c_void_p(ring.data_ptr()), count, C.c_void_p(out.data_ptr()))
+    else:
+        c = _ring_words(ring, p)
+        npolys, total = _public_counts(gallery, first, npolys, c.shape[0])
+        out = np.zeros((total, sw), dtype=np.int32)
+        rc = L.tfhe_hip_ring_mul_public(gallery.ptr, int(first), npolys, _i32p(c), c.shape[0], _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def ring_inner_public(gallery, probe_ring, M, width, key, result, first=0, device=False):
+    """The inner products of ONE encrypted probe with a clear gallery (tfhe_hip_ring_inner_public): `gallery` holds M
+    entries of `width` coefficients in ring_lookup's layout as public polynomials, `probe_ring` is the ring sample of the
+    probe polynomial sum_i s_i Delta X^(-i), and result[first + i] receives, in a fresh slot, the key switch of coefficient
+    (i mod S) width of q_(i / S) * probe.  key: the keyset whose cloud key evaluates.  device=True: the probe's (k+1) N words
+    are an int32 torch tensor on the engine's device; the call returns with the work enqueued."""
+    p = gallery.params
+    sw = (p.k + 1) * p.N
+    L = _l.load()
+    if device:
+        import torch
+        if probe_ring.dtype != torch.int32 or not probe_ring.is_contiguous() or probe_ring.numel() != sw:
+            raise ValueError("a device probe is a contiguous int32 tensor of (k+1) N words")
+        rc = L.tfhe_hip_ring_inner_public_device(gallery.ptr, key.cloud, C.c_void_p(probe_ring.data_ptr()), int(M), int(width), result.at(first))
+    else:
+        c = _ring_words(probe_ring, p)
+        if c.shape[0] != 1:
+            raise ValueError("the probe is ONE ring sample of (k+1) N words")
+        rc = L.tfhe_hip_ring_inner_public(gallery.ptr, key.cloud, _i32p(c), int(M), int(width), result.at(first))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def kernel_ring_public_product(gallery, ring, first=0, npolys=None):
+    """ring_mul_public's host form through the raw test entry (tfhe_hip_kernel_ring_public_product)."""
+    p = gallery.params
+    c = _ring_words(ring, p)
+    npolys, total = _public_counts(gallery, first, npolys, c.shape[0])
+    out = np.zeros((total, (p.k + 1) * p.N), dtype=np.int32)
+    if _l.load().tfhe_hip_kernel_ring_public_product(gallery.ptr, int(first), npolys, _i32p(c), c.shape[0], _i32p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def kernel_ring_public_rows(gallery, probe_ring, M, width):
+    """The rows ring_inner_public key-switches, before the key switch (tfhe_hip_kernel_ring_public_rows): int32 [M][kN+1]."""
+    p = gallery.params
+    c = _ring_words(probe_ring, p)
+    u = np.zeros((int(M), p.k * p.N + 1), dtype=np.int32)
+    if _l.load().tfhe_hip_kernel_ring_public_rows(gallery.ptr, _i32p(c), int(M), int(width), _i32p(u)) != 0:
+        raise RuntimeError(last_error())
+    return u
+
+
 def ring_trivial(params, values):
     """The noiseless ring sample (0, values): a zero mask and the 1..N torus words `values` as the body (zero behind them).
     It decrypts to `values` under every key, so a gallery of such samples is a PUBLIC table, and ring_lookup over it

@@ -24,6 +24,8 @@ $HIPCC $KFLAGS -c expand.hip -o expand.o &
 $HIPCC $KFLAGS -c cmux.hip -o cmux.o &
 # the matrix key switch of wide levels (int8 MFMA), likewise
 $HIPCC $KFLAGS -c ks_matrix.hip -o ks_matrix.o &
+# a ring sample times public polynomials, likewise
+$HIPCC $KFLAGS -c ring_public.hip -o ring_public.o &
 # EMIT_KERNEL_ASM=<file>: also the assembly listing of exactly this compile (tools/isa_mix.py counts the instructions of a
 # blind-rotate step from it; __graft_entry__.build() asks for it when profiles/isa_mix.json is stale)
 if [ -n "${EMIT_KERNEL_ASM-}" ]; then
@@ -35,12 +37,14 @@ $CXX $HOSTFLAGS -c engine.cpp -o engine.o &
 $CXX $HOSTFLAGS -c shim.cpp -o shim.o &
 $CXX $HOSTFLAGS -c scheduler.cpp -o scheduler.o &
 $CXX $HOSTFLAGS -c io.cpp -o io.o &
-wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n
+# the host side of ring_public.hip: an object of its own (the list of files shim.cpp includes is closed)
+$CXX $HOSTFLAGS -c public_host.cpp -o public_host.o &
+wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n
 if [ -n "${EXTRA_WAIT-}" ]; then wait -n; fi
 # -Bsymbolic-functions: calls between the library's own exported functions bind inside the library, so
 # another provider of the tfhe API loaded RTLD_GLOBAL in the same process (a CPU tfhe, the tests'
 # plaintext mock) cannot interpose on them
-$HIPCC -shared -Wl,-Bsymbolic-functions -o $OUT kernels.o pack.o unpack.o expand.o cmux.o ks_matrix.o host_keys.o engine.o shim.o scheduler.o io.o
+$HIPCC -shared -Wl,-Bsymbolic-functions -o $OUT kernels.o pack.o unpack.o expand.o cmux.o ks_matrix.o ring_public.o host_keys.o engine.o shim.o scheduler.o io.o public_host.o
 echo "built $(realpath $OUT)"
 # circuits: calls only the public tfhe API; symbols resolve at load time against
 # whichever provider is loaded first (libtfhe-hip.so, or the tests' plain mock)

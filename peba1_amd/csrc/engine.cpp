@@ -1604,6 +1604,102 @@ void Engine::run_inner(const SelectorImage *sel, const Params &p, int bit, const
     finish(wait || !ring_on_device, "ring inner");
 }
 
+// ---- ring sample times public polynomials (ring_public.hpp, ring_public.hip) -----------------
+Engine::PublicImage *Engine::upload_public(int N, const int32_t *polys, int R) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    PublicImageArgs a{};
+    const std::vector<uint32_t> tw = make_twiddles(N, a.scale);
+    const size_t raw_words = (size_t)R * N;
+    auto *g = new PublicImage();
+    int32_t *raw = nullptr;
+    try {
+        g->tw_bytes = tw.size() * 4;
+        g->tw = static_cast<uint32_t *>(recoverable_alloc(g->tw_bytes, "the twiddle tables of a public gallery"));
+        g->img_bytes = raw_words * 2 * 4;
+        g->img = static_cast<uint32_t *>(recoverable_alloc(g->img_bytes, "the NTT image of a public gallery"));
+        raw = static_cast<int32_t *>(recoverable_alloc(raw_words * 4, "the staging copy of a public gallery"));
+    } catch (const ApiError &) {
+        recoverable_free(g->img, g->img_bytes);
+        recoverable_free(g->tw, g->tw_bytes);
+        delete g;
+        throw;
+    }
+    hip_check(hipMemcpy(g->tw, tw.data(), g->tw_bytes, hipMemcpyHostToDevice), "upload twiddles");
+    hip_check(hipMemcpy(raw, polys, raw_words * 4, hipMemcpyHostToDevice), "upload public gallery");
+    a.N = N; a.count = R; a.polys = raw; a.img = g->img; a.tw = g->tw;
+    if (!launch_public_image(stream_, a)) fatal("public gallery transform: arguments outside what the kernel was built for");
+    hip_check(hipGetLastError(), "public gallery transform launch");
+    sync_stream("public gallery transform");
+    recoverable_free(raw, raw_words * 4);
+    return g;
+}
+
+void Engine::free_public(PublicImage *g) {
+    ENGINE_DEVICE_SCOPE();
+    if (!g) return;
+    if (inited_) sync_stream("sync before public gallery free");
+    recoverable_free(g->img, g->img_bytes);
+    recoverable_free(g->tw, g->tw_bytes);
+    delete g;
+}
+
+void Engine::run_public_mul(const PublicImage *g, int N, int first, int img_step, const Torus32 *ring, int nsamples, int total,
+                            bool on_device, Torus32 *out) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t sw = (size_t)2 * N;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    int32_t *dring = on_device ? nullptr : scratch_as<int32_t>(S_PUBLIC_RING, (size_t)nsamples * sw);
+    int32_t *dout = on_device ? out : scratch_as<int32_t>(S_PUBLIC_OUT, (size_t)total * sw);
+    if (kernel_timing && !select_e0_) {
+        hip_check(hipEventCreate(&select_e0_), "select event");
+        hip_check(hipEventCreate(&select_e1_), "select event");
+    }
+    if (!on_device) h2d(dring, ring, (size_t)nsamples * sw, "upload ring words");
+    PublicArgs a{};
+    a.N = N; a.count = total; a.img_step = img_step; a.ring_stride = nsamples == 1 ? 0 : (int64_t)sw;
+    a.ring = on_device ? ring : dring; a.img = g->img + (size_t)first * sw; a.tw = g->tw; a.out = dout;
+    if (kernel_timing) hip_check(hipEventRecord(select_e0_, stream_), "select event");
+    if (!launch_public(stream_, a)) api_fail("ring mul public: arguments outside what the kernel was built for");
+    hip_check(hipGetLastError(), "ring mul public launch");
+    if (kernel_timing) hip_check(hipEventRecord(select_e1_, stream_), "select event");
+    select_timed_ = kernel_timing;
+    if (!on_device) d2h(out, dout, (size_t)total * sw, "download product words");
+    finish(!on_device, "ring mul public");
+}
+
+void Engine::run_public_inner(const PublicImage *g, const Params &p, const DeviceKeyImage *key, const Torus32 *probe, bool probe_on_device,
+                              int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t sw = (size_t)2 * p.N;
+    const int S = p.N / width;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    int32_t *dprobe = probe_on_device ? nullptr : scratch_as<int32_t>(S_PUBLIC_RING, sw);
+    const RowsPlan r = size_rows(key, p.u_stride(), M, !u_out);
+    if (kernel_timing && !select_e0_) {
+        hip_check(hipEventCreate(&select_e0_), "select event");
+        hip_check(hipEventCreate(&select_e1_), "select event");
+    }
+    if (!probe_on_device) h2d(dprobe, probe, sw, "upload probe words");
+    PublicArgs a{};
+    a.N = p.N; a.img_step = 1; a.ring_stride = 0; a.ring = probe_on_device ? probe : dprobe; a.tw = g->tw;
+    a.rows.width = width; a.rows.u_stride = r.u_stride; a.rows.u_buf = r.u_buf;
+    run_rows(key, r, M, (size_t)p.k * p.N + 1, pool, slots, u_out, "ring inner public", [&](int done, int cnt) {
+        // a chunk starts on a polynomial: S divides UNPACK_CHUNK (both powers of two, S <= N <= UNPACK_CHUNK)
+        a.img = g->img + (size_t)(done / S) * sw; a.count = (cnt + S - 1) / S; a.rows.M = cnt;
+        if (kernel_timing && done == 0) hip_check(hipEventRecord(select_e0_, stream_), "select event");
+        if (!launch_public(stream_, a)) api_fail("ring inner public: arguments outside what the kernel was built for");
+        hip_check(hipGetLastError(), "ring inner public launch");
+        if (kernel_timing && done + cnt == M) hip_check(hipEventRecord(select_e1_, stream_), "select event");
+    });
+    select_timed_ = kernel_timing;
+    if (u_out) return;
+    // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
+    finish(wait || !probe_on_device, "ring inner public");
+}
+
 size_t Engine::read_extract_rows(Torus32 *out, size_t capacity) {
     ENGINE_DEVICE_SCOPE();
     const size_t words = last_extract_words_;

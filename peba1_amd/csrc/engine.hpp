@@ -19,6 +19,7 @@
 #include "cmux.hpp"
 #include "expand.hpp"
 #include "ks_matrix.hpp"
+#include "ring_public.hpp"
 #include "../../include/tfhe_hip.h"
 
 // Device image of one cloud key: NTT image of BK, compact KSK, twiddles.
@@ -319,6 +320,8 @@ private:
         S_SELECT_A,       // run_select / run_lookup: the launches 0, 2, ... (ping), tree levels then rotations; run_cmux: the results
         S_SELECT_B,       // run_select / run_lookup: the launches 1, 3, ... (pong)
         S_CMUX_D1,        // raw, run_cmux: the d1 operands
+        S_PUBLIC_RING,    // run_public_mul, run_public_inner: the ring words on their way from a host source
+        S_PUBLIC_OUT,     // run_public_mul: the products on their way to a host destination
     };
     void *scratch(Scratch idx, size_t bytes);
     // the same by element count (and `margin` bytes), and `count` elements between host and device on the engine's stream
@@ -420,8 +423,30 @@ public:
     // the launches of the last run_select / run_lookup between two stream events (kernel timing on; waits for the second), else -1;
     // after a run_inner: from its first product launch to its last (ONE launch up to UNPACK_CHUNK rows)
     double last_select_ms();
+
+    // Ring sample times public polynomials (ring_public.hpp).  The device side of a public gallery: the canonical NTT
+    // residues of its R polynomials under both primes, [R][2][N] (8 KB each), made by ONE launch of public_image_kernel at
+    // upload, and the ring's twiddle tables -- a gallery belongs to a parameter set, not to a cloud key, so it carries its
+    // own.  Every buffer is allocated before anything is enqueued: device memory exhausted = ApiError with nothing held.
+    // free_public waits for the stream first (a product in flight reads both).
+    struct PublicImage { uint32_t *img = nullptr, *tw = nullptr; size_t img_bytes = 0, tw_bytes = 0; };
+    PublicImage *upload_public(int N, const int32_t *polys, int R);
+    void free_public(PublicImage *g);
+    // The products q_(first + g * img_step) * c_(g * (broadcast ? 0 : 1)), g < total, of ring samples `ring` (host, or
+    // device memory the caller keeps until the stream has passed), enqueued on the engine's stream behind whatever is
+    // there in ONE launch.  nsamples: the samples `ring` holds (1: one sample under every polynomial).  Names no pool slot
+    // and waits for no flight.  A host source or destination makes the call return with the words in place.
+    void run_public_mul(const PublicImage *g, int N, int first, int img_step, const Torus32 *ring, int nsamples, int total,
+                        bool on_device, Torus32 *out);
+    // The inner products of ONE probe sample with the gallery's polynomials 0 .. R - 1 (include/tfhe_hip.h): entry i < M is
+    // the row Extract_((i mod S) width)(q_(i / S) * probe), product and extraction in ONE launch per chunk of at most
+    // UNPACK_CHUNK rows, the rows then going the way of run_unpack's and run_inner's through the same code: the slot form
+    // (u_out null) key-switches row i into pool slot slots[i] under `key`; the raw form u_out [M][kN+1] returns the rows
+    // alone (key may be null).  The caller has checked every argument and, for the slot form, waited for the flight.
+    void run_public_inner(const PublicImage *g, const Params &p, const DeviceKeyImage *key, const Torus32 *probe, bool probe_on_device,
+                          int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait);
 private:
-    // what run_unpack and run_inner share (engine.cpp): the buffers and key-switch plans of `count` rows, then the chunks
+    // what run_unpack, run_inner and run_public_inner share (engine.cpp): the buffers and key-switch plans of `count` rows, then the chunks
     struct RowsPlan { int widest = 0, u_stride = 0; KsDesc *dks = nullptr; int32_t *u_buf = nullptr; KsLaunchPlan ks_wide, ks_last; };
     RowsPlan size_rows(const DeviceKeyImage *key, int u_stride, int count, bool to_slots);
     template <class MakeRows>

@@ -227,9 +227,15 @@ def match_by_inner(selector, gallery, M, width, addend, tau, key, sample=0):
     NOT exact within inner_decision_band of the threshold -- ready for pack_match_bits."""
     params = selector.params
     device = hasattr(gallery, "data_ptr")
-    delta = inner_delta(width)
     inner = api.CiphertextArray(params, M)
     api.ring_inner(selector, sample, gallery, M, width, key, inner, device=device)
+    return _hamming_decision(params, inner, M, width, addend, tau, key)
+
+
+def _hamming_decision(params, inner, M, width, addend, tau, key):
+    """The decision tail match_by_inner and match_clear_gallery share: per entry (tau + 1/2) Delta - (inner + addend)
+    (api.linear, recorded), the LUT bootstrap with the constant 1/8, one flush.  Closes `inner`."""
+    delta = inner_delta(width)
     lin = api.CiphertextArray(params, M)
     c0 = (2 * int(tau) + 1) * delta // 2
     for i in range(M):
@@ -242,3 +248,55 @@ def match_by_inner(selector, gallery, M, width, addend, tau, key, sample=0):
     for o in (inner, lin):
         o.close()
     return bits
+
+
+# ---- Hamming 1-to-N against a CLEAR gallery (include/tfhe_hip.h "ring sample times public polynomials") ----
+def clear_gallery_polys(entries, width, N):
+    """A gallery the server owns in the clear, as public polynomials for api.PublicGallery: M entries of `width` bits in
+    pack_gallery's layout (S = N / width per polynomial, bit j of entry i at coefficient (i mod S) width + j of polynomial
+    i / S, 0 behind the last entry) -> int32 [R][N], R = ceil(M / S)."""
+    if width < 1 or width > N or width & (width - 1):
+        raise ValueError("width must be a power of two in 1..%d" % N)
+    S = N // width
+    R = -(-len(entries) // S)
+    q = np.zeros((max(R, 1), N), dtype=np.int32)
+    for i, entry in enumerate(entries):
+        bits = [int(b) & 1 for b in entry]
+        if len(bits) != width:
+            raise ValueError("every entry carries %d bits" % width)
+        q[i // S, (i % S) * width:(i % S + 1) * width] = bits
+    return q
+
+
+def hamming_probe_ring(bits, width, secret, compressed=False, seed=None):
+    """The client's probe for match_clear_gallery: (ONE ring sample that encrypts the torus polynomial sum_i s_i Delta
+    X^(-i), s_i = 1 - 2 b_i, Delta = 2^-(log2 width + 2) -- (k+1) N words, or the 10 + N words of the seed-compressed form --
+    and a CiphertextArray of ONE sample that encrypts (sum_i b_i) Delta, hamming_probe's addend).  len(bits) must be
+    `width`.  seed: the reproducible form (the compressed form's mask seed is derived from it)."""
+    params = secret.params
+    b = np.asarray(bits, dtype=np.int64).reshape(-1) & 1
+    if len(b) != width:
+        raise ValueError("the probe carries %d bits, the gallery's entries %d" % (len(b), width))
+    mu = hamming_probe_poly(b, params.N).astype(np.int64) * inner_delta(width)
+    mask_seed = None if seed is None or not compressed else [(int(seed) * 0x9E3779B1 + j) & 0xFFFFFFFF for j in range(10)]
+    words = api.ring_encrypt(mu, secret, seed=seed, compressed=compressed, mask_seed=mask_seed)
+    addend = api.CiphertextArray(params, 1)
+    api.encrypt_torus(addend.at(0), int(b.sum()) * inner_delta(width), secret)
+    return words, addend
+
+
+def match_clear_gallery(gallery, probe_ring, M, width, addend, tau, key):
+    """match_by_inner with the roles exchanged: `gallery` is an api.PublicGallery over clear_gallery_polys, `probe_ring`
+    hamming_probe_ring's sample (host words, plain or seed-compressed -- told apart by their count --, or an int32 torch
+    tensor of the plain words resident on the device).  api.ring_inner_public, then match_by_inner's decision tail, word
+    for word.  Returns a CiphertextArray of M match bits, TRUE iff distance <= tau -- NOT exact within inner_decision_band
+    of the threshold, exactly as match_by_inner: the band is the key switch's and the modulus switch's."""
+    params = gallery.params
+    device = hasattr(probe_ring, "data_ptr")
+    if not device:
+        probe_ring = np.ascontiguousarray(probe_ring, dtype=np.int32).reshape(-1)
+        if probe_ring.size == 10 + params.N:
+            probe_ring = api.ring_expand(probe_ring, params.N)
+    inner = api.CiphertextArray(params, M)
+    api.ring_inner_public(gallery, probe_ring, M, width, key, inner, device=device)
+    return _hamming_decision(params, inner, M, width, addend, tau, key)    # (its flush: the device form's probe has been read)

@@ -329,6 +329,16 @@ SIGNATURES = {
     "tfhe_hip_ring_inner_device": (C.c_int, [C.c_void_p, C.c_int32, CK, C.c_void_p, C.c_int32, C.c_int32, LS]),
     "tfhe_hip_kernel_ring_product": (C.c_int, [C.c_void_p, C.c_int32, I32P, C.c_int32, I32P]),
     "tfhe_hip_kernel_ring_inner_rows": (C.c_int, [C.c_void_p, C.c_int32, I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
+    "tfhe_hip_new_public_gallery": (C.c_void_p, [PS, I32P, C.c_int32]),
+    "tfhe_hip_delete_public_gallery": (None, [C.c_void_p]),
+    "tfhe_hip_public_gallery_polys": (C.c_int32, [C.c_void_p]),
+    "tfhe_hip_ring_mul_public": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, I32P, C.c_int32, I32P]),
+    "tfhe_hip_ring_mul_public_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "tfhe_hip_ring_inner_public": (C.c_int, [C.c_void_p, CK, I32P, C.c_int32, C.c_int32, LS]),
+    "tfhe_hip_ring_inner_public_device": (C.c_int, [C.c_void_p, CK, C.c_void_p, C.c_int32, C.c_int32, LS]),
+    "tfhe_hip_kernel_ring_public_product": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, I32P, C.c_int32, I32P]),
+    "tfhe_hip_kernel_ring_public_rows": (C.c_int, [C.c_void_p, I32P, C.c_int32, C.c_int32, I32P]),
+    "tfhe_hip_test_public_bounds": (C.c_int, [C.c_int32, C.c_int32]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])

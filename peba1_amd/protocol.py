@@ -198,6 +198,26 @@ def run_inner_product(params, key, templates, probe, tau, width=128):
         o.close()
 
 
+def run_clear_gallery(params, key, templates, probe, tau, width=128):
+    """Client and server of identify.match_clear_gallery once: the server owns the gallery in the clear
+    (clear_gallery_polys, api.PublicGallery -- nothing is enrolled under a key); the client sends ONE seed-compressed ring
+    sample and the addend (hamming_probe_ring); the server answers one match bit per template; the client decrypts.
+    Yields run_inner_product's records, plus the probe's bytes on the wire."""
+    from . import identify
+    gallery = api.PublicGallery(params, identify.clear_gallery_polys(templates, width, params.N))    # server
+    ring, addend = identify.hamming_probe_ring(probe, width, key, compressed=True)                   # client, per query
+    bits = identify.match_clear_gallery(gallery, ring, len(templates), width, addend, tau, key)
+    got = [int(b) for b in bits.decrypt(key)]                             # client
+    g = identify.inner_decision_band(params, width)
+    for i, t in enumerate(templates):
+        d = sum(int(x) ^ int(y) for x, y in zip(t, probe))
+        yield {"entry": i, "distance": d, "plain": int(d <= tau), "decrypted": got[i], "inside_band": abs(d - tau) < g,
+               "probe_bytes": int(ring.nbytes)}
+    gallery.close()
+    for o in (bits, addend):
+        o.close()
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--nslots", type=int, default=128)
@@ -215,11 +235,18 @@ def parse_args(argv=None):
     ap.add_argument("--packed-gallery", action="store_true",
                     help="Hamming match of one claimed identity against a gallery of 128-bit templates packed eight to a ring "
                          "sample: looked up under TGSW-encrypted index bits, the server does not learn which")
-    ap.add_argument("--entries", type=int, default=20, help="--packed-gallery, --inner-product: templates in the gallery")
+    ap.add_argument("--entries", type=int, default=20, help="--packed-gallery, --inner-product, --clear-gallery: templates in the gallery")
     ap.add_argument("--inner-product", action="store_true",
                     help="Hamming 1-to-N of one probe against the whole packed gallery by encrypted inner products: one external "
                          "product per ring sample, one key switch, one level of bootstraps (not exact near the threshold)")
+    ap.add_argument("--clear-gallery", action="store_true",
+                    help="--inner-product with the roles exchanged: the server owns the gallery in the clear, the probe travels "
+                         "as one seed-compressed ring sample; a ring sample times public polynomials, no TGSW sample")
     a = ap.parse_args(argv)
+    if a.clear_gallery and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.packed_gallery or a.compressed_keys or a.inner_product):
+        ap.error("--clear-gallery runs alone")
+    if a.clear_gallery and not 1 <= a.entries <= 1 << 20:
+        ap.error("--entries must be in 1..2^20")
     if a.inner_product and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.packed_gallery or a.compressed_keys):
         ap.error("--inner-product runs alone")
     if a.inner_product and not 1 <= a.entries <= 1 << 20:
@@ -273,7 +300,7 @@ def main():
     params = api.ParameterSet(128)
     key = api.SecretKeySet(params, a.seed + 1, device=not a.compressed_keys)
     cloud = shipped_cloud(key) if a.compressed_keys else None
-    if a.inner_product:
+    if a.inner_product or a.clear_gallery:
         import random
         rnd = random.Random(a.seed)
         probe = [rnd.getrandbits(1) for _ in range(128)]
@@ -283,7 +310,7 @@ def main():
             for j in rnd.sample(range(128), (5 * i) % 29):
                 t[j] ^= 1
             templates.append(t)
-        for out in run_inner_product(params, key, templates, probe, tau=40):
+        for out in (run_clear_gallery if a.clear_gallery else run_inner_product)(params, key, templates, probe, tau=40):
             print(json.dumps(out))
         key.close()
         return
