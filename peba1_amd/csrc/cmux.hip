@@ -23,30 +23,13 @@
 //                        The epilogue starts after the accumulators have died: it adds no register to the body's peak.
 // No atomics, no global scratch beyond the row buffer; a CMUX reads nothing another CMUX of the launch writes.
 //
-// kernels.hip is not touched by this file; the few lines it keeps private (the per-prime context) are restated here.
+// kernels.hip is not touched by this file; the few lines it keeps private (the per-prime context) are restated once, in
+// ring_wave.hpp (through cmux.hpp), with inner_kernel's tail, which ring_public.hip shares.
 #include "cmux.hpp"
-#include "ntt_wave.hpp"
 
 namespace tfhe_hip {
 
 namespace {
-
-// the twiddle tables of prime q (engine.cpp make_twiddles; the same lines as kernels.hip make_ctx)
-__device__ __forceinline__ PrimeCtx cmux_ctx(int q, const uint32_t *tw, int n_ring) {
-    PrimeCtx c;
-    c.P = q ? NTT_P1 : NTT_P0;
-    c.pinv = q ? NTT_PINV1 : NTT_PINV0;
-    c.rmod = q ? NTT_R[1] : NTT_R[0];
-    c.wf = tw + (size_t)(q * 2 + 0) * n_ring;
-    c.wi = tw + (size_t)(q * 2 + 1) * n_ring;
-    const uint4 *quads = reinterpret_cast<const uint4 *>(tw + (size_t)4 * n_ring);
-    c.qf = quads + (size_t)(q * 2 + 0) * (n_ring / 2);
-    c.qi = quads + (size_t)(q * 2 + 1) * (n_ring / 2);
-    c.dtab = nullptr;
-    c.fw1 = nullptr;
-    c.fw2 = nullptr;
-    return c;
-}
 
 // the most rows any accepted gadget has: the accumulators below take that many products (cmux.hpp MAC bound)
 static_assert(cmux_mac_ok(1024, 18) && cmux_mac_ok(2048, 16), "rows one accumulator takes");
@@ -56,7 +39,7 @@ enum { MODE_CMUX = 0, MODE_ROT = 1, MODE_PRODUCT = 2 };
 template <int LOGN, bool ROT_KERNEL>
 __global__ __launch_bounds__(128) void cmux_kernel(CmuxArgs a) {
     constexpr int MODE = ROT_KERNEL ? MODE_ROT : MODE_CMUX;
-    const InnerRows t{};
+    const RingRows t{};
 #include "cmux_body.inc"
 }
 
@@ -64,7 +47,7 @@ template <int LOGN>
 __global__ __launch_bounds__(128) void inner_kernel(InnerArgs x) {
     constexpr int MODE = MODE_PRODUCT;
     const CmuxArgs &a = x.c;
-    const InnerRows &t = x.rows;
+    const RingRows &t = x.rows;
 #include "cmux_body.inc"
 }
 
@@ -72,18 +55,12 @@ __global__ __launch_bounds__(128) void inner_kernel(InnerArgs x) {
 
 bool launch_inner(hipStream_t s, const InnerArgs &x) {
     const CmuxArgs &a = x.c;
-    const InnerRows &t = x.rows;
+    const RingRows &t = x.rows;
     // the gadget as launch_cmux; the operands are the `count` ring samples at d0, 16-byte aligned like every destination
     if (cmux_gadget_error(a.N, 1, a.l, a.Bgbit) || a.bit < 0 || a.bit >= SELECT_MAX_BITS || a.count < 1 || a.stride < 2 * (int64_t)a.N ||
         (a.stride & 3) || !a.d0 || !a.img || !a.tw || a.rot || a.n_d1 || (!a.out && !t.u_buf) || (reinterpret_cast<uintptr_t>(a.out) & 15u))
         return false;
-    if (t.u_buf) {
-        // rows: w a power of two in 1 .. N, every workgroup has an entry ((count - 1) S < M <= count S), one chunk at most
-        if (t.width < 1 || t.width > a.N || (t.width & (t.width - 1)) || t.u_stride != a.N + 4 || (reinterpret_cast<uintptr_t>(t.u_buf) & 15u))
-            return false;
-        const int64_t S = a.N / t.width;
-        if (t.M < 1 || t.M > UNPACK_CHUNK || t.M > a.count * S || t.M <= (a.count - 1) * S) return false;
-    }
+    if (t.u_buf && (ring_rows_error(a.N, a.count, t.M, t.width, t.u_stride) || (reinterpret_cast<uintptr_t>(t.u_buf) & 15u))) return false;
     if (a.N == 2048) hipLaunchKernelGGL((inner_kernel<11>), dim3(a.count), dim3(128), 0, s, x);
     else hipLaunchKernelGGL((inner_kernel<10>), dim3(a.count), dim3(128), 0, s, x);
     return true;

@@ -37,7 +37,7 @@
 
 #include "ntt_field.hpp"
 #include "pack.hpp"
-#include "unpack.hpp"
+#include "ring_wave.hpp"
 
 namespace tfhe_hip {
 
@@ -101,18 +101,12 @@ bool launch_cmux(hipStream_t s, const CmuxArgs &a);
 // |word| <= 2^31 -- so they hold unchanged and there is no third bound.  The operand is c itself (the digits of c + offset),
 // nothing is added to the sum.
 // One launch: c.count workgroups, workgroup r on the ring sample at c.d0[r * c.stride] under selector sample c.bit.
-// rows.u_buf != null: the sample holds S = N / width entries and entry e < S is written as row r S + e of u_buf,
-//     Extract_(e width)(G (.) c_r):  a_i = A[e w - i] for i <= e w,  a_i = -A[N + e w - i] past it,  b = B[e w],
-// in the layout of ring_extract_kernel (unpack.hpp: u_stride = N + 4 words a row, the body and three zeros last), for the
-// rows below rows.M alone, (count - 1) S < M <= count S and M <= UNPACK_CHUNK.  c.out != null: the full products
-// out[r * 2N] as well (the raw test form; alone when u_buf is null).  c.d1, c.n_d1 and c.rot are not used and must be zero.
-struct InnerRows {
-    int32_t M = 0, width = 1, u_stride = 0;
-    int32_t *u_buf = nullptr;
-};
+// rows.u_buf != null: the rows Extract_(e width)(G (.) c_r) of ring_wave.hpp RingRows, passing ring_rows_error.  c.out !=
+// null: the full products out[r * 2N] as well (the raw test form; alone when u_buf is null).  c.d1, c.n_d1 and c.rot are
+// not used and must be zero.
 struct InnerArgs {
     CmuxArgs c;
-    InnerRows rows;
+    RingRows rows;
 };
 // false, and nothing launched, for arguments outside what the kernel was built and bounded for
 bool launch_inner(hipStream_t s, const InnerArgs &a);

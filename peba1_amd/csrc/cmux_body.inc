@@ -4,7 +4,7 @@
 //   LOGN                  the template parameter
 //   MODE                  constexpr int: MODE_CMUX (d1 - d0), MODE_ROT (X^(-rot) d0 - d0), MODE_PRODUCT (d0 itself, nothing added)
 //   a                     the CmuxArgs
-//   t                     the InnerRows (looked at under MODE_PRODUCT alone)
+//   t                     the RingRows (looked at under MODE_PRODUCT alone)
     constexpr bool ROT = MODE == MODE_ROT;
     using NTT = WaveNtt<LOGN>;
     constexpr int N = NTT::N, REGS = NTT::REGS;
@@ -14,7 +14,7 @@
     const int tid = threadIdx.x;
     const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    const PrimeCtx c = cmux_ctx(q, a.tw, N);
+    const PrimeCtx c = ring_prime_ctx(q, a.tw, N);
     uint32_t *scr = lds_scr[q];
 
     const int cm = blockIdx.x;                                   // < a.count: the grid is a.count workgroups
@@ -84,50 +84,14 @@
     // the waves took different primes and now exchange through LDS alone: the barrier form ntt_wave.hpp documents for
     // that (both waves reach it on the same path; nothing was stored to global memory yet)
     lds_barrier();
+    if constexpr (MODE == MODE_PRODUCT) {
+        ring_crt_rows<LOGN>(lds_x, q, lane, tid, cm, a.out, t);    // the CRT, the full product, the rows (ring_wave.hpp)
+        return;
+    }
     // wave q owns output polynomial q: coefficients 4 (64 g + lane) .. + 3, both primes' residues, the signed CRT
     // (the true integer is below CRT_EXACT_LIMIT: CRT bound), + d0, one 16-byte store
     const uint4 *r0 = reinterpret_cast<const uint4 *>(lds_x[0][q]) + lane;
     const uint4 *r1 = reinterpret_cast<const uint4 *>(lds_x[1][q]) + lane;
-    if constexpr (MODE == MODE_PRODUCT) {
-        // the torus words of polynomial q take the place of prime 0's residues: a lane writes the 16 bytes it alone read
-        uint4 *tor = reinterpret_cast<uint4 *>(lds_x[0][q]) + lane;
-        uint4 *full = a.out ? reinterpret_cast<uint4 *>(a.out + ((size_t)cm * 2 + q) * N) + lane : nullptr;    // uniform
-#pragma unroll
-        for (int g = 0; g < REGS / 4; ++g) {
-            const uint4 x0 = r0[g * 64], x1 = r1[g * 64];
-            const uint4 w = make_uint4(crt_signed_to_torus((int32_t)x0.x, (int32_t)x1.x), crt_signed_to_torus((int32_t)x0.y, (int32_t)x1.y),
-                                       crt_signed_to_torus((int32_t)x0.z, (int32_t)x1.z), crt_signed_to_torus((int32_t)x0.w, (int32_t)x1.w));
-            tor[g * 64] = w;
-            if (full) full[g * 64] = w;
-        }
-        if (!t.u_buf) return;                                    // workgroup-uniform: the raw product form
-        lds_barrier();
-        // entry e of this sample is row cm S + e of the launch: Extract_(e w) as ring_extract_kernel writes it, A and B in LDS
-        const uint32_t *A = lds_x[0][0], *B = lds_x[0][1];
-        const int S = N / t.width;
-        const int rows = min(S, t.M - cm * S);                   // >= 1: the launcher checks (count - 1) S < M <= count S
-        constexpr int groups = N / 4;                            // mask groups; group `groups` is (b, 0, 0, 0)
-        for (int e = 0; e < rows; ++e) {
-            const int ew = e * t.width;
-            uint4 *row = reinterpret_cast<uint4 *>(t.u_buf + ((size_t)cm * S + e) * t.u_stride);
-            for (int g = tid; g <= groups; g += 128) {
-                uint4 w;
-                if (g < groups) {
-                    uint32_t m[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int d = ew - (4 * g + i);
-                        m[i] = d >= 0 ? A[d] : 0u - A[d + N];
-                    }
-                    w = make_uint4(m[0], m[1], m[2], m[3]);
-                } else {
-                    w = make_uint4(B[ew], 0u, 0u, 0u);
-                }
-                row[g] = w;
-            }
-        }
-        return;
-    }
     const uint4 *src = reinterpret_cast<const uint4 *>(d0 + (size_t)q * N) + lane;
     uint4 *dst = reinterpret_cast<uint4 *>(a.out + ((size_t)cm * 2 + q) * N) + lane;
 #pragma unroll

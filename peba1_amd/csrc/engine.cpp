@@ -1414,6 +1414,13 @@ void Engine::free_selector(SelectorImage *sel) {
     delete sel;
 }
 
+// the event pair last_select_ms reads, made by the first timed launch
+void Engine::ensure_select_events() {
+    if (!kernel_timing || select_e0_) return;
+    hip_check(hipEventCreate(&select_e0_), "select event");
+    hip_check(hipEventCreate(&select_e1_), "select event");
+}
+
 void Engine::run_lookup(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, int width, bool ring_on_device,
                         Torus32 *out, bool out_on_device) {
     ENGINE_DEVICE_SCOPE();
@@ -1428,10 +1435,7 @@ void Engine::run_lookup(const SelectorImage *sel, const Params &p, int nbits, co
     int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_SELECT_RING, (size_t)R * sw);
     int32_t *lvl[2] = {nbits > 0 ? scratch_as<int32_t>(S_SELECT_A, (size_t)((R + 1) / 2) * sw) : nullptr,
                        nbits > 1 ? scratch_as<int32_t>(S_SELECT_B, (size_t)((R + 3) / 4) * sw) : nullptr};
-    if (kernel_timing && !select_e0_) {
-        hip_check(hipEventCreate(&select_e0_), "select event");
-        hip_check(hipEventCreate(&select_e1_), "select event");
-    }
+    ensure_select_events();
     if (!ring_on_device) h2d_staged(dring, ring, (size_t)R * sw, "upload ring words");
     const int32_t *src = ring_on_device ? ring : dring;
     if (kernel_timing) hip_check(hipEventRecord(select_e0_, stream_), "select event");
@@ -1569,7 +1573,7 @@ void Engine::run_inner(const SelectorImage *sel, const Params &p, int bit, const
     const int S = p.N / width;
     // every buffer first (scratch() may throw: nothing has been enqueued then)
     int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_SELECT_RING, (size_t)R * sw);
-    InnerArgs x{cmux_args(sel, p), InnerRows{}};
+    InnerArgs x{cmux_args(sel, p), RingRows{}};
     x.c.bit = bit; x.c.stride = (int64_t)sw;
     if (prod_out) {
         // the raw product form: one launch over all R samples, no rows
@@ -1583,10 +1587,7 @@ void Engine::run_inner(const SelectorImage *sel, const Params &p, int bit, const
         return;
     }
     const RowsPlan r = size_rows(key, p.u_stride(), M, !u_out);
-    if (kernel_timing && !select_e0_) {
-        hip_check(hipEventCreate(&select_e0_), "select event");
-        hip_check(hipEventCreate(&select_e1_), "select event");
-    }
+    ensure_select_events();
     if (!ring_on_device) h2d(dring, ring, (size_t)R * sw, "upload ring words");
     const int32_t *src = ring_on_device ? ring : dring;
     x.rows.width = width; x.rows.u_stride = r.u_stride; x.rows.u_buf = r.u_buf;
@@ -1652,10 +1653,7 @@ void Engine::run_public_mul(const PublicImage *g, int N, int first, int img_step
     // every buffer first (scratch() may throw: nothing has been enqueued then)
     int32_t *dring = on_device ? nullptr : scratch_as<int32_t>(S_PUBLIC_RING, (size_t)nsamples * sw);
     int32_t *dout = on_device ? out : scratch_as<int32_t>(S_PUBLIC_OUT, (size_t)total * sw);
-    if (kernel_timing && !select_e0_) {
-        hip_check(hipEventCreate(&select_e0_), "select event");
-        hip_check(hipEventCreate(&select_e1_), "select event");
-    }
+    ensure_select_events();
     if (!on_device) h2d(dring, ring, (size_t)nsamples * sw, "upload ring words");
     PublicArgs a{};
     a.N = N; a.count = total; a.img_step = img_step; a.ring_stride = nsamples == 1 ? 0 : (int64_t)sw;
@@ -1678,10 +1676,7 @@ void Engine::run_public_inner(const PublicImage *g, const Params &p, const Devic
     // every buffer first (scratch() may throw: nothing has been enqueued then)
     int32_t *dprobe = probe_on_device ? nullptr : scratch_as<int32_t>(S_PUBLIC_RING, sw);
     const RowsPlan r = size_rows(key, p.u_stride(), M, !u_out);
-    if (kernel_timing && !select_e0_) {
-        hip_check(hipEventCreate(&select_e0_), "select event");
-        hip_check(hipEventCreate(&select_e1_), "select event");
-    }
+    ensure_select_events();
     if (!probe_on_device) h2d(dprobe, probe, sw, "upload probe words");
     PublicArgs a{};
     a.N = p.N; a.img_step = 1; a.ring_stride = 0; a.ring = probe_on_device ? probe : dprobe; a.tw = g->tw;

@@ -452,6 +452,7 @@ private:
     template <class MakeRows>
     void run_rows(const DeviceKeyImage *key, const RowsPlan &r, int count, size_t uw, SlotPool *pool, const int32_t *slots,
                   Torus32 *u_out, const char *what, MakeRows &&make_rows);
+    void ensure_select_events();                        // kernel timing on: select_e0_ / select_e1_ exist from here on
     hipEvent_t select_e0_ = nullptr, select_e1_ = nullptr;
     bool select_timed_ = false;
     // (behind everything else, as above) prepare_flush's key-switch plan of every (level, key) share of flight_plan_

@@ -11,30 +11,14 @@
 //   pack_reduce_kernel   sums the partials, negates, adds sum_j b_j X^j to the body: the 2N words of the result.
 // No atomics; the result does not depend on the order anything ran in.
 //
-// kernels.hip is not touched by this file; the few lines it keeps private (the per-prime context) are restated here.
+// kernels.hip is not touched by this file; the few lines it keeps private (the per-prime context) are restated once, in
+// ring_wave.hpp.
 #include "pack.hpp"
-#include "ntt_wave.hpp"
+#include "ring_wave.hpp"
 
 namespace tfhe_hip {
 
 namespace {
-
-// the twiddle tables of prime q (engine.cpp make_twiddles; the same lines as kernels.hip make_ctx)
-__device__ __forceinline__ PrimeCtx pack_ctx(int q, const uint32_t *tw, int n_ring) {
-    PrimeCtx c;
-    c.P = q ? NTT_P1 : NTT_P0;
-    c.pinv = q ? NTT_PINV1 : NTT_PINV0;
-    c.rmod = q ? NTT_R[1] : NTT_R[0];
-    c.wf = tw + (size_t)(q * 2 + 0) * n_ring;
-    c.wi = tw + (size_t)(q * 2 + 1) * n_ring;
-    const uint4 *quads = reinterpret_cast<const uint4 *>(tw + (size_t)4 * n_ring);
-    c.qf = quads + (size_t)(q * 2 + 0) * (n_ring / 2);
-    c.qi = quads + (size_t)(q * 2 + 1) * (n_ring / 2);
-    c.dtab = nullptr;
-    c.fw1 = nullptr;
-    c.fw2 = nullptr;
-    return c;
-}
 
 // the largest t any accepted decomposition has: the accumulators below take that many products (pack.hpp MAC bound)
 static_assert(pack_mac_ok(1024, 18) && pack_mac_ok(2048, 16), "rows one accumulator takes");
@@ -50,7 +34,7 @@ __global__ __launch_bounds__(128) void pack_kernel(PackArgs a) {
     const int tid = threadIdx.x;
     const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    const PrimeCtx c = pack_ctx(q, a.tw, N);
+    const PrimeCtx c = ring_prime_ctx(q, a.tw, N);
     uint32_t *scr = lds_scr[q];
 
     // coefficient j = 64 r + lane of every digit polynomial comes from sample j (layout L0 of ntt_wave.hpp)

@@ -19,31 +19,13 @@
 //                        4 l forward and 4 inverse; no 64-bit accumulator lives across a transform.
 // No atomics, no global scratch beyond the row buffer; a workgroup reads nothing another workgroup of the launch writes.
 //
-// kernels.hip and cmux.hip are not touched by this file; the few lines they keep private (the per-prime context) are
-// restated here.
+// kernels.hip is not touched by this file; the few lines it keeps private (the per-prime context) are restated once, in
+// ring_wave.hpp (through ring_public.hpp), with the tail public_kernel shares with cmux.hip's inner_kernel.
 #include "ring_public.hpp"
-#include "ntt_wave.hpp"
 
 namespace tfhe_hip {
 
 namespace {
-
-// the twiddle tables of prime p (engine.cpp make_twiddles; the same lines as kernels.hip make_ctx)
-__device__ __forceinline__ PrimeCtx public_ctx(int p, const uint32_t *tw, int n_ring) {
-    PrimeCtx c;
-    c.P = p ? NTT_P1 : NTT_P0;
-    c.pinv = p ? NTT_PINV1 : NTT_PINV0;
-    c.rmod = p ? NTT_R[1] : NTT_R[0];
-    c.wf = tw + (size_t)(p * 2 + 0) * n_ring;
-    c.wi = tw + (size_t)(p * 2 + 1) * n_ring;
-    const uint4 *quads = reinterpret_cast<const uint4 *>(tw + (size_t)4 * n_ring);
-    c.qf = quads + (size_t)(p * 2 + 0) * (n_ring / 2);
-    c.qi = quads + (size_t)(p * 2 + 1) * (n_ring / 2);
-    c.dtab = nullptr;
-    c.fw1 = nullptr;
-    c.fw2 = nullptr;
-    return c;
-}
 
 // grid (count, 2 primes), one wave each
 template <int LOGN>
@@ -54,7 +36,7 @@ __global__ __launch_bounds__(64) void public_image_kernel(PublicImageArgs a) {
     const int lane = threadIdx.x;
     const int p = blockIdx.y;
     const int poly = blockIdx.x;                                 // < a.count: the grid is a.count polynomials wide
-    const PrimeCtx c = public_ctx(p, a.tw, N);
+    const PrimeCtx c = ring_prime_ctx(p, a.tw, N);
     const uint32_t scale = p ? a.scale[1] : a.scale[0];
     const int32_t *src = a.polys + (size_t)poly * N;
     int32_t x[REGS];
@@ -87,9 +69,8 @@ __global__ __launch_bounds__(128) void public_kernel(PublicArgs a) {
     const int tid = threadIdx.x;
     const int p = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    const PrimeCtx c = public_ctx(p, a.tw, N);
+    const PrimeCtx c = ring_prime_ctx(p, a.tw, N);
     uint32_t *scr = lds_scr[p];
-    const PublicRows &t = a.rows;
 
     const int wg = blockIdx.x;                                   // < a.count: the grid is a.count workgroups
     const int32_t *ring = a.ring + (size_t)wg * a.ring_stride;
@@ -122,47 +103,7 @@ __global__ __launch_bounds__(128) void public_kernel(PublicArgs a) {
     // the waves took different primes and now exchange through LDS alone: the barrier form ntt_wave.hpp documents for
     // that (both waves reach it on the same path; nothing was stored to global memory yet)
     lds_barrier();
-    // wave p owns output polynomial p: coefficients 4 (64 g + lane) .. + 3, both primes' residues, the signed CRT (the
-    // true integer is below CRT_EXACT_LIMIT: CRT bound)
-    const uint4 *r0 = reinterpret_cast<const uint4 *>(lds_x[0][p]) + lane;
-    const uint4 *r1 = reinterpret_cast<const uint4 *>(lds_x[1][p]) + lane;
-    // the torus words of polynomial p take the place of prime 0's residues: a lane writes the 16 bytes it alone read
-    uint4 *tor = reinterpret_cast<uint4 *>(lds_x[0][p]) + lane;
-    uint4 *full = a.out ? reinterpret_cast<uint4 *>(a.out + ((size_t)wg * 2 + p) * N) + lane : nullptr;    // uniform
-#pragma unroll
-    for (int g = 0; g < REGS / 4; ++g) {
-        const uint4 x0 = r0[g * 64], x1 = r1[g * 64];
-        const uint4 w = make_uint4(crt_signed_to_torus((int32_t)x0.x, (int32_t)x1.x), crt_signed_to_torus((int32_t)x0.y, (int32_t)x1.y),
-                                   crt_signed_to_torus((int32_t)x0.z, (int32_t)x1.z), crt_signed_to_torus((int32_t)x0.w, (int32_t)x1.w));
-        tor[g * 64] = w;
-        if (full) full[g * 64] = w;
-    }
-    if (!t.u_buf) return;                                        // workgroup-uniform: the raw product form
-    lds_barrier();
-    // entry e of this product is row wg S + e of the launch: Extract_(e w) as ring_extract_kernel writes it, A and B in LDS
-    const uint32_t *A = lds_x[0][0], *B = lds_x[0][1];
-    const int S = N / t.width;
-    const int rows = min(S, t.M - wg * S);                       // >= 1: the launcher checks (count - 1) S < M <= count S
-    constexpr int groups = N / 4;                                // mask groups; group `groups` is (b, 0, 0, 0)
-    for (int e = 0; e < rows; ++e) {
-        const int ew = e * t.width;
-        uint4 *row = reinterpret_cast<uint4 *>(t.u_buf + ((size_t)wg * S + e) * t.u_stride);
-        for (int g = tid; g <= groups; g += 128) {
-            uint4 w;
-            if (g < groups) {
-                uint32_t m[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int d = ew - (4 * g + i);
-                    m[i] = d >= 0 ? A[d] : 0u - A[d + N];
-                }
-                w = make_uint4(m[0], m[1], m[2], m[3]);
-            } else {
-                w = make_uint4(B[ew], 0u, 0u, 0u);
-            }
-            row[g] = w;
-        }
-    }
+    ring_crt_rows<LOGN>(lds_x, p, lane, tid, wg, a.out, a.rows);    // the CRT, the full product, the rows (ring_wave.hpp)
 }
 
 }  // namespace
@@ -177,18 +118,12 @@ bool launch_public_image(hipStream_t s, const PublicImageArgs &a) {
 }
 
 bool launch_public(hipStream_t s, const PublicArgs &a) {
-    const PublicRows &t = a.rows;
+    const RingRows &t = a.rows;
     if ((a.N != 1024 && a.N != 2048) || a.count < 1 || a.count > PUBLIC_MAX_COUNT || (a.img_step != 0 && a.img_step != 1) ||
         (a.ring_stride != 0 && (a.ring_stride < 2 * (int64_t)a.N || (a.ring_stride & 3))) || !a.ring || !a.img || !a.tw ||
         (!a.out && !t.u_buf) || ((reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.img)) & 15u))
         return false;
-    if (t.u_buf) {
-        // rows: w a power of two in 1 .. N, every workgroup has an entry ((count - 1) S < M <= count S), one chunk at most
-        if (t.width < 1 || t.width > a.N || (t.width & (t.width - 1)) || t.u_stride != a.N + 4 || (reinterpret_cast<uintptr_t>(t.u_buf) & 15u))
-            return false;
-        const int64_t S = a.N / t.width;
-        if (t.M < 1 || t.M > UNPACK_CHUNK || t.M > a.count * S || t.M <= (a.count - 1) * S) return false;
-    }
+    if (t.u_buf && (ring_rows_error(a.N, a.count, t.M, t.width, t.u_stride) || (reinterpret_cast<uintptr_t>(t.u_buf) & 15u))) return false;
     if (a.N == 2048) hipLaunchKernelGGL((public_kernel<11>), dim3(a.count), dim3(128), 0, s, a);
     else hipLaunchKernelGGL((public_kernel<10>), dim3(a.count), dim3(128), 0, s, a);
     return true;

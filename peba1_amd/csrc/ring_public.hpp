@@ -33,7 +33,7 @@
 
 #include "ntt_field.hpp"
 #include "pack.hpp"
-#include "unpack.hpp"
+#include "ring_wave.hpp"
 
 namespace tfhe_hip {
 
@@ -90,15 +90,8 @@ bool launch_public_image(hipStream_t s, const PublicImageArgs &a);
 // One launch of `count` workgroups: workgroup g multiplies the ring sample at ring[g * ring_stride] (2N words; stride 0:
 // every workgroup reads the same sample) by the polynomial whose image is img[(g * img_step) * 2N] (img_step 0: every
 // workgroup the same polynomial, 1: consecutive ones).
-// rows.u_buf != null: the sample's product holds S = N / width entries and entry e < S is written as row g S + e of u_buf,
-//     Extract_(e width)(q_g * c_g):  a_i = A[e w - i] for i <= e w,  a_i = -A[N + e w - i] past it,  b = B[e w],
-// in the layout of ring_extract_kernel (unpack.hpp: u_stride = N + 4 words a row, the body and three zeros last), for the
-// rows below rows.M alone, (count - 1) S < M <= count S and M <= UNPACK_CHUNK.  out != null: the full products out[g * 2N]
-// as well (alone when u_buf is null).  out overlaps no input.
-struct PublicRows {
-    int32_t M = 0, width = 1, u_stride = 0;
-    int32_t *u_buf = nullptr;
-};
+// rows.u_buf != null: the rows Extract_(e width)(q_g * c_g) of ring_wave.hpp RingRows, passing ring_rows_error.  out !=
+// null: the full products out[g * 2N] as well (alone when u_buf is null).  out overlaps no input.
 struct PublicArgs {
     int32_t N, count;
     int32_t img_step;               // 0 or 1
@@ -107,7 +100,7 @@ struct PublicArgs {
     const uint32_t *img;            // the image of workgroup 0's polynomial
     const uint32_t *tw;
     int32_t *out;
-    PublicRows rows;
+    RingRows rows;
 };
 // false, and nothing launched, for arguments outside what the kernel was built and bounded for
 bool launch_public(hipStream_t s, const PublicArgs &a);

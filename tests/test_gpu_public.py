@@ -167,7 +167,8 @@ def small_keys():
     ks.close()
 
 
-@pytest.mark.parametrize("w,M", [(128, 11), (1024, 2), (16, 70)])
+# (1, 8192 + 5): nine polynomials and the one shape with a second chunk -- done / S != 0, a cut last workgroup, two key-switch plans
+@pytest.mark.parametrize("w,M", [(128, 11), (1024, 2), (16, 70), (1, 8192 + 5)])
 def test_ring_inner_public_equals_the_restatement_with_its_key_switch(L, small_keys, w, M):
     import torch
     from peba1_amd import api
