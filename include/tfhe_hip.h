@@ -1223,6 +1223,11 @@ int tfhe_hip_kernel_ring_public_rows(const TfheHipPublicGallery *gallery, const 
 /* host-logic test entry: 0 if coefficients up to T pass the CRT bound N T 2^31 < CRT_EXACT_LIMIT at ring size N, 1 if not;
  * -1 with the error set for N outside {1024, 2048} or T < 1 */
 int tfhe_hip_test_public_bounds(int32_t N, int32_t T);
+/* host-logic test entry: the magnitude recurrences of the wave NTT as the library states them, for a transform of 2^logn
+ * points (logn = 9, 10, 11) on inputs |x| <= x0.  fwd2 = {pack_forward_bound(logn, x0), br_forms forward_bound(logn, x0 / P,
+ * no table)}: |outputs| / P of the forward transform.  plan25 = make_inv_plan(logn): {nsteps, fan[12], renorm[12]}, and
+ * *inv_out its out_bound.  -1 with the error set for other arguments. */
+int tfhe_hip_test_ntt_bounds(int32_t logn, double x0, double *fwd2, int32_t *plan25, double *inv_out);
 
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through

@@ -108,6 +108,15 @@ __global__ __launch_bounds__(128) void public_kernel(PublicArgs a) {
 
 }  // namespace
 
+InvPlanWords inv_plan_words(int logn) {
+    const InvPlan pl = make_inv_plan(logn);
+    InvPlanWords w{};
+    w.nsteps = pl.nsteps;
+    for (int k = 0; k < 12; ++k) { w.fan[k] = pl.fan[k]; w.renorm[k] = pl.renorm[k] ? 1 : 0; }
+    w.out_bound = pl.out_bound;
+    return w;
+}
+
 bool launch_public_image(hipStream_t s, const PublicImageArgs &a) {
     if ((a.N != 1024 && a.N != 2048) || a.count < 1 || a.count > PUBLIC_MAX_POLYS || !a.polys || !a.img || !a.tw ||
         (reinterpret_cast<uintptr_t>(a.img) & 15u))

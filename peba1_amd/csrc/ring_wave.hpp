@@ -39,6 +39,16 @@ constexpr bool ring_rows_edges_ok(int N) {
 static_assert(ring_rows_edges_ok(1024) && ring_rows_edges_ok(2048),
               "M = count S, (count - 1) S + 1, S = 1, S = N hold; (count - 1) S, width 3, 2 N, a second chunk, u_stride N do not");
 
+// ntt_wave.hpp make_inv_plan(logn) in plain words, for the host's compiler, which cannot read that file: the inverse
+// transform's steps, their fan (4 or 2), which of them renormalise, the bound of its outputs in units of the larger prime
+// (include/tfhe_hip.h tfhe_hip_test_ntt_bounds; defined in ring_public.hip, beside the kernels that run the plan).
+struct InvPlanWords {
+    int32_t nsteps;
+    int32_t fan[12], renorm[12];
+    double out_bound;
+};
+InvPlanWords inv_plan_words(int logn);
+
 }  // namespace tfhe_hip
 
 // the device half: ntt_wave.hpp is device code, and the host's compiler reads this file through cmux.hpp and ring_public.hpp

@@ -36,6 +36,17 @@ int tfhe_hip_test_form_admissible(int form, int32_t N, int32_t l, int32_t Bgbit,
     return br_form_admissible(form, N, l, Bgbit, tables) ? 1 : 0;
 }
 
+int tfhe_hip_test_ntt_bounds(int32_t logn, double x0, double *fwd2, int32_t *plan25, double *inv_out) {
+    if (logn < 9 || logn > 11 || !(x0 >= 0) || !fwd2 || !plan25 || !inv_out) { set_error("test_ntt_bounds: bad arguments"); return -1; }
+    fwd2[0] = pack_forward_bound(logn, x0);
+    fwd2[1] = br_forms_detail::forward_bound(logn, x0 / (double)NTT_P[1], false);
+    const InvPlanWords pl = inv_plan_words(logn);
+    plan25[0] = pl.nsteps;
+    for (int k = 0; k < 12; ++k) { plan25[1 + k] = pl.fan[k]; plan25[13 + k] = pl.renorm[k]; }
+    *inv_out = pl.out_bound;
+    return 0;
+}
+
 static int test_build_ops(const int32_t *ops5, int32_t count, std::vector<PendingOp> &ops) {
     // ops5[i] = {kind, dst, a, b, c}; ASAP levels are derived here exactly as the recorder derives them
     for (int32_t i = 0; i < count; ++i)

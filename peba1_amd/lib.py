@@ -339,6 +339,7 @@ SIGNATURES = {
     "tfhe_hip_kernel_ring_public_product": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, I32P, C.c_int32, I32P]),
     "tfhe_hip_kernel_ring_public_rows": (C.c_int, [C.c_void_p, I32P, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_public_bounds": (C.c_int, [C.c_int32, C.c_int32]),
+    "tfhe_hip_test_ntt_bounds": (C.c_int, [C.c_int32, C.c_double, C.POINTER(C.c_double), I32P, C.POINTER(C.c_double)]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])
