@@ -483,6 +483,8 @@ int tfhe_hip_test_stage_place(int64_t pos, int64_t capacity, int32_t outstanding
  * that needed the memory has no effect (recorded gates stay recorded, tfhe_hip_flush returns -1), tfhe_hip_last_error()
  * says what could not be allocated, and the caller may free ciphertext arrays and carry on. ---- */
 void tfhe_hip_test_set_alloc_cap(int64_t bytes);
+/* ---- test entry (read-only): the bytes those allocations hold now, the figure the cap is compared with ---- */
+int64_t tfhe_hip_test_alloc_held(void);
 
 /* ---- host-logic test entry: levelise a DAG given as count x {kind, dst, a, b, c} slot
  * records (kind: gate code 0..9, 16 = MUX, 17 = NOT, 32 + 8 * TfheHipGate3 + negate_mask = a three-input gate; absent

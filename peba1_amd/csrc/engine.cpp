@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 
 #include "br_forms.hpp"
@@ -48,7 +49,8 @@ void hip_check(hipError_t e, const char *what) {
 // tfhe_hip_test_set_alloc_cap) makes allocations above a total fail the same way, so that the path has a test.
 static long long g_alloc_cap = 0, g_alloc_total = 0;
 void set_alloc_cap(long long bytes) { g_alloc_cap = bytes > 0 ? bytes : 0; }
-static void *recoverable_alloc(size_t bytes, const char *what) {
+long long alloc_held() { return g_alloc_total; }
+void *recoverable_alloc(size_t bytes, const char *what) {
     void *p = nullptr;
     hipError_t e = hipErrorOutOfMemory;
     if (!(g_alloc_cap > 0 && g_alloc_total + (long long)bytes > g_alloc_cap)) e = hipMalloc(&p, bytes);
@@ -62,7 +64,7 @@ static void *recoverable_alloc(size_t bytes, const char *what) {
     g_alloc_total += (long long)bytes;
     return p;
 }
-static void recoverable_free(void *p, size_t bytes) {
+void recoverable_free(void *p, size_t bytes) {
     if (!p) return;
     (void)hipFree(p);
     g_alloc_total -= (long long)bytes;
@@ -303,7 +305,7 @@ static uint32_t bitrev32(uint32_t x, int bits) {
 // twiddles [prime][fwd,inv][N]: psi^{+-brv(i)} * R mod P, followed by the radix-4 quads
 // [prime][fwd,inv][N/2][4]: entry e = 2^s + t (stage pair (s, s+1), block t) holds, with
 // w1 = W[e], w2 = W[2e], w3 = W[2e+1]: {w2, w3, w1 w2, P - w1 w3}, all times R mod P
-static std::vector<uint32_t> make_twiddles(int N, uint32_t scale_out[2]) {
+static std::vector<uint32_t> make_twiddles(int N) {
     int logn = 0;
     while ((1 << logn) < N) ++logn;
     std::vector<uint32_t> tw((size_t)24 * N);
@@ -362,11 +364,19 @@ static std::vector<uint32_t> make_twiddles(int N, uint32_t scale_out[2]) {
                 }
             }
         }
-        // image scale: N^-1 (the inverse NTT is unscaled) times R (so that the
-        // Montgomery reduction of sum x*img leaves sum x*bk / N)
-        scale_out[q] = (uint32_t)(powmod_c((uint64_t)N, P - 2, P) * R % P);
     }
     return tw;
+}
+// image scale: N^-1 (the inverse NTT is unscaled) times R (so that the
+// Montgomery reduction of sum x*img leaves sum x*bk / N)
+static void image_scale(int N, uint32_t scale_out[2]) {
+    for (int q = 0; q < 2; ++q) scale_out[q] = (uint32_t)(powmod_c((uint64_t)N, NTT_P[q] - 2, NTT_P[q]) * NTT_R[q] % NTT_P[q]);
+}
+static ExpandSeed expand_seed(const uint32_t seed10[10]) {
+    ExpandSeed seed;
+    std::memcpy(seed.key, seed10, sizeof seed.key);
+    seed.nonce[0] = seed10[8]; seed.nonce[1] = seed10[9];
+    return seed;
 }
 
 static DevParams make_dev_params(const Params &p) {
@@ -400,47 +410,89 @@ const char *unsupported_reason(const Params &p) {
     return "gadget (l, Bgbit) outside the exact range of every blind-rotate kernel form (br_forms.hpp)";
 }
 
+// ---- the upload path of the resident images ------------------------------------------------------------
+// Every buffer of an image is a DeviceBuf: an ApiError out of any allocation (a card without room fails there, recoverably)
+// gives back what the path holds so far as it unwinds -- the object is not made, tfhe_hip_last_error() says what was needed.
+DeviceBuf<uint32_t> Engine::upload_twiddles(int N, const char *what) {
+    const std::vector<uint32_t> host = make_twiddles(N);
+    DeviceBuf<uint32_t> tw(host.size(), what);
+    hip_check(hipMemcpy(tw.get(), host.data(), tw.bytes(), hipMemcpyHostToDevice), "upload twiddles");
+    return tw;
+}
+
+// The NTT image of r.rows rows of r.polys polynomials under the tables `tw`: the image, the raw staging rows and, where
+// seeded, the bodies are allocated before anything is enqueued; the staging rows are filled from the host or by
+// launch_expand_bk (masks from the stream, bodies from the upload); launch_bk_transform follows, the stream is waited for
+// and the staging goes with this scope.  at(step): where a cloud key allocates and enqueues what it has besides.
+template <class Hook>
+DeviceBuf<uint32_t> Engine::upload_image(const DevParams &dp, const uint32_t *tw, const ImageRows &r, Hook &&at) {
+    const size_t body_words = (size_t)r.rows * dp.N, words = body_words * r.polys;
+    uint32_t scale[2];
+    image_scale(dp.N, scale);
+    DeviceBuf<uint32_t> img(words * 2, r.say.img);
+    at(ImageStep::IMAGE_HELD);
+    DeviceBuf<int32_t> raw(words, r.say.raw), body;
+    if (r.seed10) body = DeviceBuf<int32_t>(body_words, r.say.body);
+    at(ImageStep::STAGING_HELD);
+    if (!r.seed10) {
+        hip_check(hipMemcpy(raw.get(), r.host, words * 4, hipMemcpyHostToDevice), r.say.upload);
+    } else {
+        if (r.staged) h2d_staged(body.get(), r.host, body_words, r.say.upload);
+        else hip_check(hipMemcpy(body.get(), r.host, body_words * 4, hipMemcpyHostToDevice), r.say.upload);
+        at(ImageStep::BODIES_UP);
+        const ExpandBkArgs ea{expand_seed(r.seed10), r.rows, r.polys - 1, dp.N, body.get(), raw.get()};
+        if (!launch_expand_bk(stream_, ea)) fatal(r.say.refused);
+        hip_check(hipGetLastError(), (std::string(r.say.expand) + " launch").c_str());
+    }
+    at(ImageStep::FILLED);
+    launch_bk_transform(stream_, dp, raw.get(), img.get(), tw, r.rows, r.polys, scale);
+    hip_check(hipGetLastError(), (std::string(r.say.transform) + " launch").c_str());
+    sync_stream(r.say.sync);
+    return img;
+}
+
+// a resident image goes (drop()), if it was made: behind whatever on the stream still reads it
+template <class Drop>
+void Engine::free_image(bool made, const char *what, Drop &&drop) {
+    ENGINE_DEVICE_SCOPE();
+    if (!made) return;
+    if (inited_) sync_stream(what);
+    drop();
+}
+
+// what the two cloud-key forms share: the empty image of an accepted parameter set, and the kernels' view of the full one
+static std::unique_ptr<DeviceKeyImage> new_key_image(const Params &p) {
+    // a parameter set the kernels cannot run exactly is refused (the call that needed the key has no effect and
+    // tfhe_hip_last_error() says why): a custom tuple or a loaded file may carry anything
+    if (const char *why = unsupported_reason(p)) api_fail(why);
+    auto img = std::make_unique<DeviceKeyImage>();
+    img->dp = make_dev_params(p);
+    fill_form_ok(img->form_ok, p.N, p.l, p.Bgbit);
+    return img;
+}
+static DeviceKeyImage *finish_key_image(std::unique_ptr<DeviceKeyImage> img, size_t compact_rows) {
+    img->key.bk_img = img->bk_img.get();
+    img->key.ksk = img->ksk.get();
+    img->key.ksk_zero = img->ksk.get() + compact_rows * img->dp.ct_stride;
+    img->key.tw = img->tw.get();
+    return img.release();
+}
+
 DeviceKeyImage *Engine::upload_key(const TfheHipCloudKey &ck) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
     const Params &p = ck.p;
-    // a parameter set the kernels cannot run exactly is refused (the call that needed the key has no effect and
-    // tfhe_hip_last_error() says why): a custom tuple or a loaded file may carry anything
-    if (const char *why = unsupported_reason(p)) api_fail(why);
-    auto *img = new DeviceKeyImage();
-    img->dp = make_dev_params(p);
-    fill_form_ok(img->form_ok, p.N, p.l, p.Bgbit);
-    uint32_t scale[2];
-    const std::vector<uint32_t> tw = make_twiddles(p.N, scale);
-    const size_t bk_words = p.bk_words();
+    auto img = new_key_image(p);
     const int base = 1 << p.ks_basebit, stride = p.ct_stride();
     const size_t rows = (size_t)p.k * p.N * p.ks_t;
-    int32_t *raw = nullptr;
-    try {
-        // every buffer first (a card without room for them fails here, recoverably: the keyset is not made and
-        // tfhe_hip_last_error() says what was needed), then the uploads and the transform
-        img->tw_bytes = tw.size() * 4;
-        img->tw = static_cast<uint32_t *>(recoverable_alloc(img->tw_bytes, "the twiddle tables of a key"));
-        img->bk_img_bytes = bk_words * 2 * 4;
-        img->bk_img = static_cast<uint32_t *>(recoverable_alloc(img->bk_img_bytes, "the bootstrapping-key image"));
-        img->ksk_bytes = (rows * (base - 1) + 1) * (size_t)stride * 4;
-        img->ksk = static_cast<int32_t *>(recoverable_alloc(img->ksk_bytes, "the key-switching key"));
-        raw = static_cast<int32_t *>(recoverable_alloc(bk_words * 4, "the staging copy of the bootstrapping key"));
-    } catch (const ApiError &) {
-        recoverable_free(img->tw, img->tw_bytes);
-        recoverable_free(img->bk_img, img->bk_img_bytes);
-        recoverable_free(img->ksk, img->ksk_bytes);
-        delete img;
-        throw;
-    }
-    hip_check(hipMemcpy(img->tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice), "upload twiddles");
-
-    // BK: upload raw, transform on device
-    hip_check(hipMemcpy(raw, ck.bk.data(), bk_words * 4, hipMemcpyHostToDevice), "upload bk");
-    launch_bk_transform(stream_, img->dp, raw, img->bk_img, img->tw, p.n * p.kpl(), p.k + 1, scale);
-    hip_check(hipGetLastError(), "bk_transform launch");
-    sync_stream("bk_transform");
-    recoverable_free(raw, bk_words * 4);
+    // BK: upload raw, transform on device; the staging copy has gone when the compact KSK goes up
+    img->tw = upload_twiddles(p.N, "the twiddle tables of a key");
+    const ImageRows bk{p.n * p.kpl(), p.k + 1, ck.bk.data(), nullptr, false,
+                       {"the bootstrapping-key image", "the staging copy of the bootstrapping key", nullptr, "upload bk", nullptr,
+                        nullptr, "bk_transform", "bk_transform"}};
+    img->bk_img = upload_image(img->dp, img->tw.get(), bk, [&](ImageStep s) {
+        if (s == ImageStep::IMAGE_HELD) img->ksk = DeviceBuf<int32_t>((rows * (base - 1) + 1) * (size_t)stride, "the key-switching key");
+    });
 
     // KSK: drop the all-zero digit-0 rows, pad rows to ct_stride
     std::vector<int32_t> compact((rows * (base - 1) + 1) * stride, 0);   // + one row of zeros (digit 0)
@@ -448,13 +500,8 @@ DeviceKeyImage *Engine::upload_key(const TfheHipCloudKey &ck) {
         for (int v = 1; v < base; ++v)
             std::memcpy(&compact[(r * (base - 1) + (v - 1)) * stride], &ck.ksk[(r * base + v) * (size_t)(p.n + 1)],
                         (size_t)(p.n + 1) * 4);
-    hip_check(hipMemcpy(img->ksk, compact.data(), compact.size() * 4, hipMemcpyHostToDevice), "upload ksk");
-
-    img->key.bk_img = img->bk_img;
-    img->key.ksk = img->ksk;
-    img->key.ksk_zero = img->ksk + rows * (base - 1) * stride;
-    img->key.tw = img->tw;
-    return img;
+    hip_check(hipMemcpy(img->ksk.get(), compact.data(), compact.size() * 4, hipMemcpyHostToDevice), "upload ksk");
+    return finish_key_image(std::move(img), rows * (base - 1));
 }
 
 // ---- seed-compressed cloud keys (expand.hpp, expand.hip) ------------------------------------
@@ -462,58 +509,43 @@ DeviceKeyImage *Engine::upload_compressed_key(const TfheHipCloudKey &ck) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
     const Params &p = ck.p;
-    if (const char *why = unsupported_reason(p)) api_fail(why);
-    auto *img = new DeviceKeyImage();
-    img->dp = make_dev_params(p);
-    fill_form_ok(img->form_ok, p.N, p.l, p.Bgbit);
-    uint32_t scale[2];
-    const std::vector<uint32_t> tw = make_twiddles(p.N, scale);
-    const size_t bk_words = p.bk_words(), bk_body = p.bk_body_words() * 4, ksk_body = p.ksk_body_words() * 4;
+    auto img = new_key_image(p);
     const int stride = p.ct_stride();
     const size_t rows = p.ksk_body_words();                   // kN t (base-1) compact rows, and the zero row behind them
-    int32_t *raw = nullptr, *dbk = nullptr, *dksk = nullptr;
-    try {
-        img->tw_bytes = tw.size() * 4;
-        img->tw = static_cast<uint32_t *>(recoverable_alloc(img->tw_bytes, "the twiddle tables of a key"));
-        img->bk_img_bytes = bk_words * 2 * 4;
-        img->bk_img = static_cast<uint32_t *>(recoverable_alloc(img->bk_img_bytes, "the bootstrapping-key image"));
-        img->ksk_bytes = (rows + 1) * (size_t)stride * 4;
-        img->ksk = static_cast<int32_t *>(recoverable_alloc(img->ksk_bytes, "the key-switching key"));
-        raw = static_cast<int32_t *>(recoverable_alloc(bk_words * 4, "the staging copy of the bootstrapping key"));
-        dbk = static_cast<int32_t *>(recoverable_alloc(bk_body, "the bodies of a compressed bootstrapping key"));
-        dksk = static_cast<int32_t *>(recoverable_alloc(ksk_body, "the bodies of a compressed key-switching key"));
-    } catch (const ApiError &) {
-        recoverable_free(dbk, bk_body);
-        recoverable_free(raw, bk_words * 4);
-        recoverable_free(img->tw, img->tw_bytes);
-        recoverable_free(img->bk_img, img->bk_img_bytes);
-        recoverable_free(img->ksk, img->ksk_bytes);
-        delete img;
-        throw;
-    }
-    hip_check(hipMemcpy(img->tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice), "upload twiddles");
-    hip_check(hipMemcpy(dbk, ck.bk_body.data(), bk_body, hipMemcpyHostToDevice), "upload bk bodies");
-    hip_check(hipMemcpy(dksk, ck.ksk_body.data(), ksk_body, hipMemcpyHostToDevice), "upload ksk bodies");
-
-    ExpandSeed seed;
-    std::memcpy(seed.key, ck.mask_seed.data(), sizeof seed.key);
-    seed.nonce[0] = ck.mask_seed[8]; seed.nonce[1] = ck.mask_seed[9];
+    DeviceBuf<int32_t> dksk;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (kernel_timing) {
-        hip_check(hipEventCreate(&e0), "expand event");
-        hip_check(hipEventCreate(&e1), "expand event");
-        hip_check(hipEventRecord(e0, stream_), "expand event");
-    }
-    const ExpandBkArgs ba{seed, p.n * p.kpl(), p.k, p.N, dbk, raw};
-    const ExpandKskArgs ka{seed, (uint64_t)(p.bk_mask_words() / 8), (int64_t)rows, p.n, stride, dksk, img->ksk};
-    if (!launch_expand_bk(stream_, ba) || !launch_expand_ksk(stream_, ka)) fatal("expand: arguments outside what the kernels were built for");
-    hip_check(hipGetLastError(), "expand launch");
-    if (kernel_timing) hip_check(hipEventRecord(e1, stream_), "expand event");
-    // the all-zero digit-0 row
-    hip_check(hipMemsetAsync(img->ksk + rows * stride, 0, (size_t)stride * 4, stream_), "clear the zero row");
-    launch_bk_transform(stream_, img->dp, raw, img->bk_img, img->tw, p.n * p.kpl(), p.k + 1, scale);
-    hip_check(hipGetLastError(), "bk_transform launch");
-    sync_stream("key expansion");
+    img->tw = upload_twiddles(p.N, "the twiddle tables of a key");
+    const ImageRows bk{p.n * p.kpl(), p.k + 1, ck.bk_body.data(), ck.mask_seed.data(), false,
+                       {"the bootstrapping-key image", "the staging copy of the bootstrapping key",
+                        "the bodies of a compressed bootstrapping key", "upload bk bodies", "expand",
+                        "expand: arguments outside what the kernels were built for", "bk_transform", "key expansion"}};
+    // The compact KSK beside the image: its bodies go up, launch_expand_ksk writes it from the seed behind the BK's masks.
+    // With upload_image's own steps the sequence is: allocate twiddles (above), BK image, [compact KSK], staging copy, BK
+    // bodies, [KSK bodies]; upload BK bodies and [KSK bodies] (blocking); [event e0]; launch_expand_bk; [launch_expand_ksk;
+    // event e1; clear the zero row]; launch_bk_transform; wait for the stream -- the bracketed steps are the hook's.  Only the
+    // two expand launches lie between e0 and e1 (last_expand_ms).
+    img->bk_img = upload_image(img->dp, img->tw.get(), bk, [&](ImageStep s) {
+        if (s == ImageStep::IMAGE_HELD) {
+            img->ksk = DeviceBuf<int32_t>((rows + 1) * (size_t)stride, "the key-switching key");
+        } else if (s == ImageStep::STAGING_HELD) {
+            dksk = DeviceBuf<int32_t>(rows, "the bodies of a compressed key-switching key");
+        } else if (s == ImageStep::BODIES_UP) {
+            hip_check(hipMemcpy(dksk.get(), ck.ksk_body.data(), dksk.bytes(), hipMemcpyHostToDevice), "upload ksk bodies");
+            if (kernel_timing) {
+                hip_check(hipEventCreate(&e0), "expand event");
+                hip_check(hipEventCreate(&e1), "expand event");
+                hip_check(hipEventRecord(e0, stream_), "expand event");
+            }
+        } else {
+            const ExpandKskArgs ka{expand_seed(ck.mask_seed.data()), (uint64_t)(p.bk_mask_words() / 8), (int64_t)rows, p.n, stride,
+                                   dksk.get(), img->ksk.get()};
+            if (!launch_expand_ksk(stream_, ka)) fatal("expand: arguments outside what the kernels were built for");
+            hip_check(hipGetLastError(), "expand launch");
+            if (kernel_timing) hip_check(hipEventRecord(e1, stream_), "expand event");
+            // the all-zero digit-0 row
+            hip_check(hipMemsetAsync(img->ksk.get() + rows * stride, 0, (size_t)stride * 4, stream_), "clear the zero row");
+        }
+    });
     if (kernel_timing) {
         float ms = 0.f;
         hip_check(hipEventElapsedTime(&ms, e0, e1), "expand event");
@@ -521,76 +553,58 @@ DeviceKeyImage *Engine::upload_compressed_key(const TfheHipCloudKey &ck) {
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
     }
-    recoverable_free(raw, bk_words * 4);
-    recoverable_free(dbk, bk_body);
-    recoverable_free(dksk, ksk_body);
     ++expand_stats.expanded_keys;
     expand_stats.expand_launches += 2;
-
-    img->key.bk_img = img->bk_img;
-    img->key.ksk = img->ksk;
-    img->key.ksk_zero = img->ksk + rows * stride;
-    img->key.tw = img->tw;
-    return img;
+    return finish_key_image(std::move(img), rows);
 }
 
 void Engine::run_expand_masks(const uint32_t seed10[10], int64_t first_word, int count, uint32_t *out) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
     wait_flight();
-    ExpandSeed seed;
-    std::memcpy(seed.key, seed10, sizeof seed.key);
-    seed.nonce[0] = seed10[8]; seed.nonce[1] = seed10[9];
     uint32_t *d = scratch_as<uint32_t>(S_EXPAND_WORDS, (size_t)count);
-    if (!launch_expand_masks(stream_, seed, first_word, count, d)) api_fail("expand_masks: arguments outside what the kernel was built for");
+    if (!launch_expand_masks(stream_, expand_seed(seed10), first_word, count, d)) api_fail("expand_masks: arguments outside what the kernel was built for");
     hip_check(hipGetLastError(), "expand_masks launch");
     ++expand_stats.expand_launches;
     d2h(out, d, (size_t)count, "download stream words");
     sync_stream("expand_masks");
 }
 
-size_t Engine::read_key_image(const DeviceKeyImage *img, int which, Torus32 *out, size_t capacity) {
+// test paths: `words` device words copied back -- returns the word count, copies only if it fits `capacity`
+// (src(): where they lie, asked for only once they are to be copied)
+template <class Src>
+size_t Engine::read_back(size_t words, Torus32 *out, size_t capacity, const char *what, Src &&src) {
     ENGINE_DEVICE_SCOPE();
-    const size_t words = (which == 0 ? img->bk_img_bytes : img->ksk_bytes) / 4;
-    if (!out || capacity < words) return words;
+    if (!out || capacity < words || !words) return words;
     wait_flight();
-    const void *src = which == 0 ? static_cast<const void *>(img->bk_img) : static_cast<const void *>(img->ksk);
-    hip_check(hipMemcpyAsync(out, src, words * 4, hipMemcpyDeviceToHost, stream_), "download key image");
-    sync_stream("key image");
+    hip_check(hipMemcpyAsync(out, src(), words * 4, hipMemcpyDeviceToHost, stream_), (std::string("download ") + what).c_str());
+    sync_stream(what);
     return words;
 }
-
-void Engine::free_key(DeviceKeyImage *img) {
-    ENGINE_DEVICE_SCOPE();
-    if (!img) return;
-    if (inited_) sync_stream("sync before key free");
-    recoverable_free(img->bk_img, img->bk_img_bytes);
-    recoverable_free(img->ksk, img->ksk_bytes);
-    recoverable_free(img->tw, img->tw_bytes);
-    recoverable_free(img->ks_planes, img->ks_planes_bytes);
-    delete img;
+size_t Engine::read_key_image(const DeviceKeyImage *img, int which, Torus32 *out, size_t capacity) {
+    return which == 0 ? read_back(img->bk_img.bytes() / 4, out, capacity, "key image", [&] { return img->bk_img.get(); })
+                      : read_back(img->ksk.bytes() / 4, out, capacity, "key image", [&] { return img->ksk.get(); });
 }
+
+void Engine::free_key(DeviceKeyImage *img) { free_image(img, "sync before key free", [&] { delete img; }); }
 
 // ---- the byte-plane image of the matrix key switch (ks_matrix.hpp) --------------------------
 static_assert(KS_MATRIX_SPAN == KSM_WAVES * KSM_CHUNK && KS_MATRIX_TILE == KSM_GATES, "launch_plan.hpp plans what ks_matrix.hip runs");
 bool Engine::ensure_ks_planes(const DeviceKeyImage *key) {
     ENGINE_DEVICE_SCOPE();
-    if (key->ks_planes) return true;
+    if (!key->ks_planes.empty()) return true;
     const DevParams &dp = key->dp;
     if (!ks_matrix_shape_ok(dp.k * dp.N, dp.ks_t, dp.ks_basebit)) return false;
-    const size_t bytes = ks_matrix_image_bytes(dp.k * dp.N, dp.ct_stride);
-    uint8_t *img = nullptr;
     try {
-        img = static_cast<uint8_t *>(recoverable_alloc(bytes, "the byte-plane image of a key-switching key"));
+        DeviceBuf<uint8_t> img(ks_matrix_image_bytes(dp.k * dp.N, dp.ct_stride), "the byte-plane image of a key-switching key");
+        if (!launch_ksk_planes(stream_, dp, key->key, img.get())) return false;
+        hip_check(hipGetLastError(), "ksk_planes launch");
+        sync_stream("ksk_planes");
+        key->ks_planes = std::move(img);
+        return true;
     } catch (const ApiError &) {
         return false;                                    // the key works without the matrix form
     }
-    if (!launch_ksk_planes(stream_, dp, key->key, img)) { recoverable_free(img, bytes); return false; }
-    hip_check(hipGetLastError(), "ksk_planes launch");
-    sync_stream("ksk_planes");
-    key->ks_planes = img;
-    key->ks_planes_bytes = bytes;
-    return true;
 }
 
 // ---- growable device tables -------------------------------------------------------
@@ -816,7 +830,7 @@ void Engine::launch_ks(const DeviceKeyImage *key, const KsLaunchPlan &plan, cons
         const KsPlan &part = plan.part(i);                   // (the counters say what ran, part by part)
         if (part.form == KS_FORM_MATRIX) {
             ++ks_matrix_stats.ks_matrix_launches;
-            if (!key->ks_planes || !launch_keyswitch_matrix(stream, dp, key->ks_planes, u_buf, descs + done, plan.gates(i), pool))
+            if (key->ks_planes.empty() || !launch_keyswitch_matrix(stream, dp, key->ks_planes.get(), u_buf, descs + done, plan.gates(i), pool))
                 fatal("launch_ks: the planned matrix key switch has no kernel for this shape");
             continue;
         }
@@ -1247,96 +1261,48 @@ void Engine::run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const 
     dp.br_variant = tunings.br_variant == 2 ? 2 : 0;            // 2: through the split transforms
     const size_t words = (size_t)count * dp.N;
     uint32_t scale[2];
-    (void)make_twiddles(dp.N, scale);
+    image_scale(dp.N, scale);
     const int32_t *dtp = scratch_upload(S_NEGA_TP, tp, words, "upload tp");
     const int32_t *dip = scratch_upload(S_NEGA_IP, ip, words, "upload ip");
     uint32_t *dimg = scratch_as<uint32_t>(S_NEGA_IMG, words * 2);
     int32_t *dres = scratch_as<int32_t>(S_NEGA_RES, words);
-    launch_bk_transform(stream_, dp, dtp, dimg, key->tw, count, 1, scale);
-    launch_negacyclic(stream_, dp, key->tw, dip, dimg, dres, count);
+    launch_bk_transform(stream_, dp, dtp, dimg, key->tw.get(), count, 1, scale);
+    launch_negacyclic(stream_, dp, key->tw.get(), dip, dimg, dres, count);
     hip_check(hipGetLastError(), "negacyclic launch");
     d2h(res, dres, words, "download res");
     sync_stream("negacyclic");
 }
 
 // ---- packing key switch (pack.hpp, pack.hip) ------------------------------------------------
-uint32_t *Engine::upload_pack_image(const DeviceKeyImage *key, const Torus32 *rows, int t, size_t *bytes) {
+DeviceBuf<uint32_t> Engine::upload_pack_image(const DeviceKeyImage *key, const Torus32 *rows, int t) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
-    const DevParams &dp = key->dp;
-    const size_t words = (size_t)dp.n * t * 2 * dp.N;
-    uint32_t scale[2];
-    (void)make_twiddles(dp.N, scale);
-    // both buffers first: a card without room for them fails here, recoverably, with nothing held
-    uint32_t *img = static_cast<uint32_t *>(recoverable_alloc(words * 2 * 4, "the NTT image of a packing key"));
-    int32_t *raw = nullptr;
-    try {
-        raw = static_cast<int32_t *>(recoverable_alloc(words * 4, "the staging copy of a packing key"));
-    } catch (const ApiError &) {
-        recoverable_free(img, words * 2 * 4);
-        throw;
-    }
-    hip_check(hipMemcpy(raw, rows, words * 4, hipMemcpyHostToDevice), "upload packing key");
-    launch_bk_transform(stream_, dp, raw, img, key->tw, dp.n * t, 2, scale);
-    hip_check(hipGetLastError(), "packing key transform launch");
-    sync_stream("packing key transform");
-    recoverable_free(raw, words * 4);
-    *bytes = words * 2 * 4;
-    return img;
+    const ImageRows r{key->dp.n * t, 2, rows, nullptr, false,
+                      {"the NTT image of a packing key", "the staging copy of a packing key", nullptr, "upload packing key", nullptr,
+                       nullptr, "packing key transform", "packing key transform"}};
+    return upload_image(key->dp, key->tw.get(), r, [](ImageStep) {});
 }
 
-uint32_t *Engine::expand_pack_image(const DeviceKeyImage *key, const uint32_t seed10[10], const Torus32 *body, int t, size_t *bytes) {
+DeviceBuf<uint32_t> Engine::expand_pack_image(const DeviceKeyImage *key, const uint32_t seed10[10], const Torus32 *body, int t) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
-    const DevParams &dp = key->dp;
-    const size_t body_words = (size_t)dp.n * t * dp.N, words = body_words * 2;
-    uint32_t scale[2];
-    (void)make_twiddles(dp.N, scale);
-    // all three buffers first: a card without room for them fails here, recoverably, with nothing held
-    uint32_t *img = nullptr;
-    int32_t *raw = nullptr, *dbody = nullptr;
-    try {
-        img = static_cast<uint32_t *>(recoverable_alloc(words * 2 * 4, "the NTT image of a packing key"));
-        raw = static_cast<int32_t *>(recoverable_alloc(words * 4, "the staging copy of a packing key"));
-        dbody = static_cast<int32_t *>(recoverable_alloc(body_words * 4, "the bodies of a compressed packing key"));
-    } catch (const ApiError &) {
-        recoverable_free(raw, words * 4);
-        recoverable_free(img, words * 2 * 4);
-        throw;
-    }
-    h2d_staged(dbody, body, body_words, "upload packing key bodies");
-    ExpandBkArgs ea{};
-    std::memcpy(ea.seed.key, seed10, sizeof ea.seed.key);
-    ea.seed.nonce[0] = seed10[8]; ea.seed.nonce[1] = seed10[9];
-    ea.rows = dp.n * t; ea.k = 1; ea.N = dp.N; ea.body = dbody; ea.raw = raw;
-    if (!launch_expand_bk(stream_, ea)) fatal("packing key expand: arguments outside what the kernel was built for");
-    hip_check(hipGetLastError(), "packing key expand launch");
-    launch_bk_transform(stream_, dp, raw, img, key->tw, dp.n * t, 2, scale);
-    hip_check(hipGetLastError(), "packing key transform launch");
-    sync_stream("packing key expansion");
-    recoverable_free(raw, words * 4);
-    recoverable_free(dbody, body_words * 4);
+    const ImageRows r{key->dp.n * t, 2, body, seed10, true,
+                      {"the NTT image of a packing key", "the staging copy of a packing key", "the bodies of a compressed packing key",
+                       "upload packing key bodies", "packing key expand",
+                       "packing key expand: arguments outside what the kernel was built for", "packing key transform",
+                       "packing key expansion"}};
+    DeviceBuf<uint32_t> img = upload_image(key->dp, key->tw.get(), r, [](ImageStep) {});
     ++seeded_stats.expanded_packing_keys;
     ++seeded_stats.packing_expand_launches;
-    *bytes = words * 2 * 4;
     return img;
 }
 
-size_t Engine::read_pack_image(const uint32_t *img, size_t bytes, Torus32 *out, size_t capacity) {
-    ENGINE_DEVICE_SCOPE();
-    const size_t words = bytes / 4;
-    if (!out || capacity < words) return words;
-    wait_flight();
-    hip_check(hipMemcpyAsync(out, img, bytes, hipMemcpyDeviceToHost, stream_), "download packing key image");
-    sync_stream("packing key image");
-    return words;
+size_t Engine::read_pack_image(const DeviceBuf<uint32_t> &img, Torus32 *out, size_t capacity) {
+    return read_back(img.bytes() / 4, out, capacity, "packing key image", [&] { return img.get(); });
 }
 
-void Engine::free_pack_image(uint32_t *img, size_t bytes) {
-    ENGINE_DEVICE_SCOPE();
-    if (!img) return;
-    if (inited_) sync_stream("sync before packing key free");
-    recoverable_free(img, bytes);
+void Engine::free_pack_image(DeviceBuf<uint32_t> &img) {
+    free_image(!img.empty(), "sync before packing key free", [&] { img.reset(); });
 }
 
 void Engine::run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int basebit, SlotPool *pool, const int32_t *slots,
@@ -1347,7 +1313,7 @@ void Engine::run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int
     a.N = dp.N; a.n = dp.n; a.t = t; a.basebit = basebit; a.count = count;
     // one mask index per workgroup: n workgroups of two waves (630 at P128) over the chip's 1,024 SIMDs
     a.idx_per_wg = idx_per_wg > 0 ? idx_per_wg : 1;
-    a.img = img; a.tw = key->tw;
+    a.img = img; a.tw = key->tw.get();
     // every buffer first (scratch() may throw: nothing has been enqueued then)
     const size_t out_words = (size_t)2 * dp.N, raw_words_n = (size_t)count * (dp.n + 1);
     a.partial = scratch_as<int32_t>(S_PACK_PARTIAL, (size_t)pack_groups(a.n, a.idx_per_wg) * out_words);
@@ -1367,52 +1333,28 @@ void Engine::run_pack(const DeviceKeyImage *key, const uint32_t *img, int t, int
 }
 
 // ---- private selection (cmux.hpp, cmux.hip) --------------------------------------------------
-static CmuxArgs cmux_args(const Engine::SelectorImage *sel, const Params &p) {
+static CmuxArgs cmux_args(const RingImage *sel, const Params &p) {
     CmuxArgs a{};
     a.N = p.N; a.l = p.l; a.Bgbit = p.Bgbit; a.offset = p.decomp_offset();
-    a.img = sel->img; a.tw = sel->tw;
+    a.img = sel->img.get(); a.tw = sel->tw.get();
     return a;
 }
 
-Engine::SelectorImage *Engine::upload_selector(const Params &p, const Torus32 *words, int nbits) {
+RingImage *Engine::upload_selector(const Params &p, const Torus32 *words, int nbits) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
-    uint32_t scale[2];
-    const std::vector<uint32_t> tw = make_twiddles(p.N, scale);
-    const size_t raw_words = (size_t)nbits * p.kpl() * (p.k + 1) * p.N;
-    auto *sel = new SelectorImage();
-    int32_t *raw = nullptr;
-    try {
-        sel->tw_bytes = tw.size() * 4;
-        sel->tw = static_cast<uint32_t *>(recoverable_alloc(sel->tw_bytes, "the twiddle tables of a selector"));
-        sel->img_bytes = raw_words * 2 * 4;
-        sel->img = static_cast<uint32_t *>(recoverable_alloc(sel->img_bytes, "the NTT image of a selector"));
-        raw = static_cast<int32_t *>(recoverable_alloc(raw_words * 4, "the staging copy of a selector"));
-    } catch (const ApiError &) {
-        recoverable_free(sel->img, sel->img_bytes);
-        recoverable_free(sel->tw, sel->tw_bytes);
-        delete sel;
-        throw;
-    }
-    hip_check(hipMemcpy(sel->tw, tw.data(), sel->tw_bytes, hipMemcpyHostToDevice), "upload twiddles");
-    hip_check(hipMemcpy(raw, words, raw_words * 4, hipMemcpyHostToDevice), "upload selector");
+    auto sel = std::make_unique<RingImage>();
+    sel->tw = upload_twiddles(p.N, "the twiddle tables of a selector");
     DevParams dp{};
     dp.N = p.N;
-    launch_bk_transform(stream_, dp, raw, sel->img, sel->tw, nbits * p.kpl(), p.k + 1, scale);
-    hip_check(hipGetLastError(), "selector transform launch");
-    sync_stream("selector transform");
-    recoverable_free(raw, raw_words * 4);
-    return sel;
+    const ImageRows r{nbits * p.kpl(), p.k + 1, words, nullptr, false,
+                      {"the NTT image of a selector", "the staging copy of a selector", nullptr, "upload selector", nullptr,
+                       nullptr, "selector transform", "selector transform"}};
+    sel->img = upload_image(dp, sel->tw.get(), r, [](ImageStep) {});
+    return sel.release();
 }
 
-void Engine::free_selector(SelectorImage *sel) {
-    ENGINE_DEVICE_SCOPE();
-    if (!sel) return;
-    if (inited_) sync_stream("sync before selector free");
-    recoverable_free(sel->img, sel->img_bytes);
-    recoverable_free(sel->tw, sel->tw_bytes);
-    delete sel;
-}
+void Engine::free_selector(RingImage *sel) { free_image(sel, "sync before selector free", [&] { delete sel; }); }
 
 // the event pair last_select_ms reads, made by the first timed launch
 void Engine::ensure_select_events() {
@@ -1421,7 +1363,7 @@ void Engine::ensure_select_events() {
     hip_check(hipEventCreate(&select_e1_), "select event");
 }
 
-void Engine::run_lookup(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, int width, bool ring_on_device,
+void Engine::run_lookup(const RingImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, int width, bool ring_on_device,
                         Torus32 *out, bool out_on_device) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
@@ -1463,7 +1405,7 @@ void Engine::run_lookup(const SelectorImage *sel, const Params &p, int nbits, co
     finish(!ring_on_device || !out_on_device, "select");
 }
 
-void Engine::run_cmux(const SelectorImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out,
+void Engine::run_cmux(const RingImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out,
                       int rot) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
@@ -1564,7 +1506,7 @@ void Engine::run_unpack(const DeviceKeyImage *key, const Torus32 *ring_words, in
 }
 
 // ---- encrypted inner products (cmux.hpp InnerArgs, cmux.hip inner_kernel) ---------------------
-void Engine::run_inner(const SelectorImage *sel, const Params &p, int bit, const DeviceKeyImage *key, const Torus32 *ring, int R,
+void Engine::run_inner(const RingImage *sel, const Params &p, int bit, const DeviceKeyImage *key, const Torus32 *ring, int R,
                        bool ring_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, Torus32 *prod_out,
                        bool wait) {
     ENGINE_DEVICE_SCOPE();
@@ -1606,46 +1548,27 @@ void Engine::run_inner(const SelectorImage *sel, const Params &p, int bit, const
 }
 
 // ---- ring sample times public polynomials (ring_public.hpp, ring_public.hip) -----------------
-Engine::PublicImage *Engine::upload_public(int N, const int32_t *polys, int R) {
+RingImage *Engine::upload_public(int N, const int32_t *polys, int R) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
-    PublicImageArgs a{};
-    const std::vector<uint32_t> tw = make_twiddles(N, a.scale);
     const size_t raw_words = (size_t)R * N;
-    auto *g = new PublicImage();
-    int32_t *raw = nullptr;
-    try {
-        g->tw_bytes = tw.size() * 4;
-        g->tw = static_cast<uint32_t *>(recoverable_alloc(g->tw_bytes, "the twiddle tables of a public gallery"));
-        g->img_bytes = raw_words * 2 * 4;
-        g->img = static_cast<uint32_t *>(recoverable_alloc(g->img_bytes, "the NTT image of a public gallery"));
-        raw = static_cast<int32_t *>(recoverable_alloc(raw_words * 4, "the staging copy of a public gallery"));
-    } catch (const ApiError &) {
-        recoverable_free(g->img, g->img_bytes);
-        recoverable_free(g->tw, g->tw_bytes);
-        delete g;
-        throw;
-    }
-    hip_check(hipMemcpy(g->tw, tw.data(), g->tw_bytes, hipMemcpyHostToDevice), "upload twiddles");
-    hip_check(hipMemcpy(raw, polys, raw_words * 4, hipMemcpyHostToDevice), "upload public gallery");
-    a.N = N; a.count = R; a.polys = raw; a.img = g->img; a.tw = g->tw;
+    auto g = std::make_unique<RingImage>();
+    g->tw = upload_twiddles(N, "the twiddle tables of a public gallery");
+    g->img = DeviceBuf<uint32_t>(raw_words * 2, "the NTT image of a public gallery");
+    DeviceBuf<int32_t> raw(raw_words, "the staging copy of a public gallery");
+    hip_check(hipMemcpy(raw.get(), polys, raw_words * 4, hipMemcpyHostToDevice), "upload public gallery");
+    PublicImageArgs a{};
+    image_scale(N, a.scale);
+    a.N = N; a.count = R; a.polys = raw.get(); a.img = g->img.get(); a.tw = g->tw.get();
     if (!launch_public_image(stream_, a)) fatal("public gallery transform: arguments outside what the kernel was built for");
     hip_check(hipGetLastError(), "public gallery transform launch");
     sync_stream("public gallery transform");
-    recoverable_free(raw, raw_words * 4);
-    return g;
+    return g.release();
 }
 
-void Engine::free_public(PublicImage *g) {
-    ENGINE_DEVICE_SCOPE();
-    if (!g) return;
-    if (inited_) sync_stream("sync before public gallery free");
-    recoverable_free(g->img, g->img_bytes);
-    recoverable_free(g->tw, g->tw_bytes);
-    delete g;
-}
+void Engine::free_public(RingImage *g) { free_image(g, "sync before public gallery free", [&] { delete g; }); }
 
-void Engine::run_public_mul(const PublicImage *g, int N, int first, int img_step, const Torus32 *ring, int nsamples, int total,
+void Engine::run_public_mul(const RingImage *g, int N, int first, int img_step, const Torus32 *ring, int nsamples, int total,
                             bool on_device, Torus32 *out) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
@@ -1657,7 +1580,7 @@ void Engine::run_public_mul(const PublicImage *g, int N, int first, int img_step
     if (!on_device) h2d(dring, ring, (size_t)nsamples * sw, "upload ring words");
     PublicArgs a{};
     a.N = N; a.count = total; a.img_step = img_step; a.ring_stride = nsamples == 1 ? 0 : (int64_t)sw;
-    a.ring = on_device ? ring : dring; a.img = g->img + (size_t)first * sw; a.tw = g->tw; a.out = dout;
+    a.ring = on_device ? ring : dring; a.img = g->img.get() + (size_t)first * sw; a.tw = g->tw.get(); a.out = dout;
     if (kernel_timing) hip_check(hipEventRecord(select_e0_, stream_), "select event");
     if (!launch_public(stream_, a)) api_fail("ring mul public: arguments outside what the kernel was built for");
     hip_check(hipGetLastError(), "ring mul public launch");
@@ -1667,7 +1590,7 @@ void Engine::run_public_mul(const PublicImage *g, int N, int first, int img_step
     finish(!on_device, "ring mul public");
 }
 
-void Engine::run_public_inner(const PublicImage *g, const Params &p, const DeviceKeyImage *key, const Torus32 *probe, bool probe_on_device,
+void Engine::run_public_inner(const RingImage *g, const Params &p, const DeviceKeyImage *key, const Torus32 *probe, bool probe_on_device,
                               int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait) {
     ENGINE_DEVICE_SCOPE();
     ensure_init();
@@ -1679,11 +1602,11 @@ void Engine::run_public_inner(const PublicImage *g, const Params &p, const Devic
     ensure_select_events();
     if (!probe_on_device) h2d(dprobe, probe, sw, "upload probe words");
     PublicArgs a{};
-    a.N = p.N; a.img_step = 1; a.ring_stride = 0; a.ring = probe_on_device ? probe : dprobe; a.tw = g->tw;
+    a.N = p.N; a.img_step = 1; a.ring_stride = 0; a.ring = probe_on_device ? probe : dprobe; a.tw = g->tw.get();
     a.rows.width = width; a.rows.u_stride = r.u_stride; a.rows.u_buf = r.u_buf;
     run_rows(key, r, M, (size_t)p.k * p.N + 1, pool, slots, u_out, "ring inner public", [&](int done, int cnt) {
         // a chunk starts on a polynomial: S divides UNPACK_CHUNK (both powers of two, S <= N <= UNPACK_CHUNK)
-        a.img = g->img + (size_t)(done / S) * sw; a.count = (cnt + S - 1) / S; a.rows.M = cnt;
+        a.img = g->img.get() + (size_t)(done / S) * sw; a.count = (cnt + S - 1) / S; a.rows.M = cnt;
         if (kernel_timing && done == 0) hip_check(hipEventRecord(select_e0_, stream_), "select event");
         if (!launch_public(stream_, a)) api_fail("ring inner public: arguments outside what the kernel was built for");
         hip_check(hipGetLastError(), "ring inner public launch");
@@ -1696,13 +1619,8 @@ void Engine::run_public_inner(const PublicImage *g, const Params &p, const Devic
 }
 
 size_t Engine::read_extract_rows(Torus32 *out, size_t capacity) {
-    ENGINE_DEVICE_SCOPE();
-    const size_t words = last_extract_words_;
-    if (!out || capacity < words || !words) return words;
-    wait_flight();
-    d2h(out, scratch_as<int32_t>(S_UNPACK_EXTRACT, words), words, "download extract rows");     // (sized by that launch: no growth)
-    sync_stream("extract rows");
-    return words;
+    const size_t words = last_extract_words_;                     // (the buffer was sized by that launch: no growth)
+    return read_back(words, out, capacity, "extract rows", [&] { return scratch_as<int32_t>(S_UNPACK_EXTRACT, words); });
 }
 
 // ---- seed-compressed LWE sample arrays (expand.hpp, expand.hip) ------------------------------
@@ -1753,13 +1671,8 @@ void Engine::run_lwe_expand(int n, int stride, const Torus32 *record, bool recor
 }
 
 size_t Engine::read_expand_slots(Torus32 *out, size_t capacity) {
-    ENGINE_DEVICE_SCOPE();
-    const size_t words = last_expand_words_;
-    if (!out || capacity < words || !words) return words;
-    wait_flight();
-    d2h(out, scratch_as<int32_t>(S_LWE_ROWS, words), words, "download expand slots");      // (sized by that launch: no growth)
-    sync_stream("expand slots");
-    return words;
+    const size_t words = last_expand_words_;                      // (the buffer was sized by that launch: no growth)
+    return read_back(words, out, capacity, "expand slots", [&] { return scratch_as<int32_t>(S_LWE_ROWS, words); });
 }
 
 }  // namespace tfhe_hip

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "device_buf.hpp"
 #include "host_keys.hpp"
 #include "host_stage.hpp"
 #include "br_forms.hpp"
@@ -28,15 +29,16 @@ struct DeviceKeyImage {
     tfhe_hip::DevKey key;
     // form_ok[form][tables]: the kernel form's magnitude bounds hold for this key's (l, Bgbit) (br_forms.hpp)
     bool form_ok[tfhe_hip::BR_FORM_COUNT][3] = {};
-    uint32_t *bk_img = nullptr;
-    int32_t *ksk = nullptr;
-    uint32_t *tw = nullptr;
-    size_t bk_img_bytes = 0, ksk_bytes = 0, tw_bytes = 0;        // what the three hold (recoverable_alloc's accounting)
+    tfhe_hip::DeviceBuf<uint32_t> bk_img;
+    tfhe_hip::DeviceBuf<int32_t> ksk;
+    tfhe_hip::DeviceBuf<uint32_t> tw;
     // the byte-plane image of the KSK for the matrix key switch (ks_matrix.hip), made before the first flush with a launch
-    // wide enough to use it (Engine::ensure_ks_planes); null until then, and for good on a card without room for it
-    mutable uint8_t *ks_planes = nullptr;
-    mutable size_t ks_planes_bytes = 0;
+    // wide enough to use it (Engine::ensure_ks_planes); empty until then, and for good on a card without room for it
+    mutable tfhe_hip::DeviceBuf<uint8_t> ks_planes;
 };
+// Device image of an object that belongs to a parameter set, not to a cloud key, and so carries the ring's twiddle tables
+// itself: the NTT image of a selector's rows (Engine::upload_selector) or of a public gallery's polynomials (upload_public)
+struct RingImage { tfhe_hip::DeviceBuf<uint32_t> img, tw; };
 
 namespace tfhe_hip {
 
@@ -55,6 +57,7 @@ struct ApiError { std::string msg; };
 // test hook: device allocations of the slot pool and the flush scratch beyond `bytes` in total fail like hipErrorOutOfMemory
 // (recoverably: engine.cpp recoverable_alloc); 0 = no cap
 void set_alloc_cap(long long bytes);
+long long alloc_held();                         // test hook: the bytes those allocations hold now
 [[noreturn]] void api_fail(const std::string &msg);
 
 // Pool of device-resident ciphertext slots (ct_stride words each).  Slots are
@@ -193,17 +196,16 @@ public:
     bool ensure_ks_planes(const DeviceKeyImage *key);
     void run_negacyclic(const DeviceKeyImage *key, const int32_t *ip, const Torus32 *tp, Torus32 *res, int count);
     // Packing key switch (pack.hpp).  upload_pack_image: the NTT image of a packing key's raw rows [n][t][2][N] under the
-    // twiddles of `key` (a cloud key of the same ring); device memory exhausted: ApiError, nothing held.  *bytes: what the
-    // image holds, for free_pack_image.
-    uint32_t *upload_pack_image(const DeviceKeyImage *key, const Torus32 *rows, int t, size_t *bytes);
+    // twiddles of `key` (a cloud key of the same ring); device memory exhausted: ApiError, nothing held.
+    DeviceBuf<uint32_t> upload_pack_image(const DeviceKeyImage *key, const Torus32 *rows, int t);
     // The same image for a key that holds a mask seed and bodies [n][t][N] alone (tfhe_hip_expand_packing_key): the bodies go
     // up through the pinned staging area (half the bytes of the raw rows), launch_expand_bk (rows = n t, k = 1) writes the raw
     // staging buffer -- masks from the stream, bodies from the upload -- and launch_bk_transform follows.  All three buffers
     // are allocated before anything is enqueued: device memory exhausted = ApiError with nothing held.
-    uint32_t *expand_pack_image(const DeviceKeyImage *key, const uint32_t seed10[10], const Torus32 *body, int t, size_t *bytes);
-    void free_pack_image(uint32_t *img, size_t bytes);
+    DeviceBuf<uint32_t> expand_pack_image(const DeviceKeyImage *key, const uint32_t seed10[10], const Torus32 *body, int t);
+    void free_pack_image(DeviceBuf<uint32_t> &img);
     // test path: a packing key's image copied back -- returns the word count, copies only if it fits `capacity`
-    size_t read_pack_image(const uint32_t *img, size_t bytes, Torus32 *out, size_t capacity);
+    size_t read_pack_image(const DeviceBuf<uint32_t> &img, Torus32 *out, size_t capacity);
     // One pack of `count` samples, enqueued on the engine's stream behind whatever is there.  slots (the slot form): sample
     // j is pool slot slots[j]; raw_words (the test form, slots null): sample j is raw_words[j][n + 1], uploaded for this
     // call.  idx_per_wg: mask indices per workgroup, 0 = the engine's choice.  out: 2N words, host or device; a host
@@ -385,16 +387,15 @@ public:
     // bootstrapping-key image with n = nbits) and the ring's twiddle tables -- a selector belongs to a parameter set, not
     // to a cloud key, so it carries its own.  Both buffers are allocated before anything is enqueued: device memory
     // exhausted = ApiError with nothing held.  free_selector waits for the stream first (a select in flight reads both).
-    struct SelectorImage { uint32_t *img = nullptr, *tw = nullptr; size_t img_bytes = 0, tw_bytes = 0; };
-    SelectorImage *upload_selector(const Params &p, const Torus32 *words, int nbits);
-    void free_selector(SelectorImage *sel);
+    RingImage *upload_selector(const Params &p, const Torus32 *words, int nbits);
+    void free_selector(RingImage *sel);
     // The CMUX tree over the M ring samples `ring` (host, or device memory the caller keeps until the stream has passed)
     // under the nbits selector bits of `sel` (null when nbits = 0: a copy), enqueued on the engine's stream behind
     // whatever is there: one launch per level, level j from entries of level j - 1 in one of two ping-pong buffers into
     // the other, the last one straight into a device destination.  Names no pool slot and waits for no flight.  Every
     // buffer is sized before anything is enqueued: an ApiError (device memory exhausted) leaves nothing written.  A host
     // source or destination makes the call return with the words in place; the device form returns with the work enqueued.
-    void run_select(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, bool ring_on_device,
+    void run_select(const RingImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, bool ring_on_device,
                     Torus32 *out, bool out_on_device) {
         run_lookup(sel, p, nbits, ring, M, p.N, ring_on_device, out, out_on_device);
     }
@@ -403,11 +404,11 @@ public:
     // width 2^t, in the same two ping-pong buffers (each at least one sample), the last launch of all straight into a
     // device destination.  width = N is run_select: no rotation, every launch and every buffer as before.  The caller has
     // checked width, nbits >= s and M; everything else as for run_select.
-    void run_lookup(const SelectorImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, int width, bool ring_on_device,
+    void run_lookup(const RingImage *sel, const Params &p, int nbits, const Torus32 *ring, int M, int width, bool ring_on_device,
                     Torus32 *out, bool out_on_device);
     // raw test path: `count` independent CMUXes under bit `bit` in ONE launch, host words in and out; rot != 0: `count`
     // rotation steps ROT(G_bit, rot, d0[c]) instead (d1 is not looked at)
-    void run_cmux(const SelectorImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out,
+    void run_cmux(const RingImage *sel, const Params &p, int bit, const Torus32 *d1, const Torus32 *d0, int count, Torus32 *out,
                   int rot = 0);
     // Encrypted inner products (include/tfhe_hip.h; cmux.hpp InnerArgs): `ring` holds R samples (host, or device memory the
     // caller keeps until the stream has passed) of S = N / width entries each, M of them real, (R - 1) S < M <= R S.  Entry
@@ -417,7 +418,7 @@ public:
     // rows alone (key may be null); the raw form prod_out [R][(k+1) N] the full products of one launch and no rows.
     // The caller has checked every argument and, for the slot form, waited for the flight.  Every buffer is sized before
     // anything is enqueued: an ApiError (device memory exhausted) leaves nothing written.
-    void run_inner(const SelectorImage *sel, const Params &p, int bit, const DeviceKeyImage *key, const Torus32 *ring, int R,
+    void run_inner(const RingImage *sel, const Params &p, int bit, const DeviceKeyImage *key, const Torus32 *ring, int R,
                    bool ring_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, Torus32 *prod_out,
                    bool wait);
     // the launches of the last run_select / run_lookup between two stream events (kernel timing on; waits for the second), else -1;
@@ -429,23 +430,36 @@ public:
     // upload, and the ring's twiddle tables -- a gallery belongs to a parameter set, not to a cloud key, so it carries its
     // own.  Every buffer is allocated before anything is enqueued: device memory exhausted = ApiError with nothing held.
     // free_public waits for the stream first (a product in flight reads both).
-    struct PublicImage { uint32_t *img = nullptr, *tw = nullptr; size_t img_bytes = 0, tw_bytes = 0; };
-    PublicImage *upload_public(int N, const int32_t *polys, int R);
-    void free_public(PublicImage *g);
+    RingImage *upload_public(int N, const int32_t *polys, int R);
+    void free_public(RingImage *g);
     // The products q_(first + g * img_step) * c_(g * (broadcast ? 0 : 1)), g < total, of ring samples `ring` (host, or
     // device memory the caller keeps until the stream has passed), enqueued on the engine's stream behind whatever is
     // there in ONE launch.  nsamples: the samples `ring` holds (1: one sample under every polynomial).  Names no pool slot
     // and waits for no flight.  A host source or destination makes the call return with the words in place.
-    void run_public_mul(const PublicImage *g, int N, int first, int img_step, const Torus32 *ring, int nsamples, int total,
+    void run_public_mul(const RingImage *g, int N, int first, int img_step, const Torus32 *ring, int nsamples, int total,
                         bool on_device, Torus32 *out);
     // The inner products of ONE probe sample with the gallery's polynomials 0 .. R - 1 (include/tfhe_hip.h): entry i < M is
     // the row Extract_((i mod S) width)(q_(i / S) * probe), product and extraction in ONE launch per chunk of at most
     // UNPACK_CHUNK rows, the rows then going the way of run_unpack's and run_inner's through the same code: the slot form
     // (u_out null) key-switches row i into pool slot slots[i] under `key`; the raw form u_out [M][kN+1] returns the rows
     // alone (key may be null).  The caller has checked every argument and, for the slot form, waited for the flight.
-    void run_public_inner(const PublicImage *g, const Params &p, const DeviceKeyImage *key, const Torus32 *probe, bool probe_on_device,
+    void run_public_inner(const RingImage *g, const Params &p, const DeviceKeyImage *key, const Torus32 *probe, bool probe_on_device,
                           int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait);
 private:
+    // The one upload path of the transformed images (engine.cpp upload_image).  ImageRows: what an image is made from --
+    // `rows` rows of `polys` polynomials, raw at `host`, or with seed10 their bodies alone at `host` (staged: through the
+    // pinned staging area, else a blocking copy).  ImageTexts: what the path's allocations are called in an out-of-memory
+    // message, and its steps in a fatal one (refused: the whole text when launch_expand_bk takes no such arguments).  ImageStep:
+    // the points at which a cloud key adds buffers and launches of its own -- the image allocated; the staging allocated too
+    // (nothing enqueued yet); seeded only, the bodies up and launch_expand_bk next; the staging rows filled, the transform next
+    struct ImageTexts { const char *img, *raw, *body, *upload, *expand, *refused, *transform, *sync; };
+    struct ImageRows { int rows, polys; const Torus32 *host; const uint32_t *seed10; bool staged; ImageTexts say; };
+    enum class ImageStep { IMAGE_HELD, STAGING_HELD, BODIES_UP, FILLED };
+    template <class Hook>
+    DeviceBuf<uint32_t> upload_image(const DevParams &dp, const uint32_t *tw, const ImageRows &r, Hook &&at);
+    DeviceBuf<uint32_t> upload_twiddles(int N, const char *what);
+    template <class Drop> void free_image(bool made, const char *what, Drop &&drop);
+    template <class Src> size_t read_back(size_t words, Torus32 *out, size_t capacity, const char *what, Src &&src);
     // what run_unpack, run_inner and run_public_inner share (engine.cpp): the buffers and key-switch plans of `count` rows, then the chunks
     struct RowsPlan { int widest = 0, u_stride = 0; KsDesc *dks = nullptr; int32_t *u_buf = nullptr; KsLaunchPlan ks_wide, ks_last; };
     RowsPlan size_rows(const DeviceKeyImage *key, int u_stride, int count, bool to_slots);

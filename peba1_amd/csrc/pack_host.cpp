@@ -26,7 +26,7 @@ TfheHipPackingKey *tfhe_hip::new_packing_key_object(const char *who, const Param
     if (pk_t == 0 && pk_basebit == 0) { pk_t = p.ks_t; pk_basebit = p.ks_basebit; }
     if (const char *why = pack_decomp_error(p.N, p.k, pk_t, pk_basebit)) { set_error(std::string(who) + ": " + why); return nullptr; }
     if (p.n < 1 || p.n > 1024) { set_error(std::string(who) + ": LWE dimension n must be in [1, 1024]"); return nullptr; }
-    auto *key = new TfheHipPackingKey{PACK_MAGIC, p, pk_t, pk_basebit, std::vector<Torus32>(), nullptr, 0};
+    auto *key = new TfheHipPackingKey{PACK_MAGIC, p, pk_t, pk_basebit, std::vector<Torus32>(), {}};
     if (with_rows) key->rows.assign((size_t)p.n * pk_t * (p.k + 1) * p.N, 0);
     return key;
 }
@@ -43,11 +43,11 @@ const TfheHipPackingKey *tfhe_hip::pack_key_checked(const char *who, const TfheH
 
 const uint32_t *tfhe_hip::pack_image(const TfheHipPackingKey *ckey, const TFheGateBootstrappingCloudKeySet *bk) {
     auto *key = const_cast<TfheHipPackingKey *>(ckey);
-    if (!key->img)
+    if (key->img.empty())
         key->img = key->mask_seed.empty()
-                       ? Engine::get().upload_pack_image(bk->bk->dev, key->rows.data(), key->t, &key->img_bytes)
-                       : Engine::get().expand_pack_image(bk->bk->dev, key->mask_seed.data(), key->body.data(), key->t, &key->img_bytes);
-    return key->img;
+                       ? Engine::get().upload_pack_image(bk->bk->dev, key->rows.data(), key->t)
+                       : Engine::get().expand_pack_image(bk->bk->dev, key->mask_seed.data(), key->body.data(), key->t);
+    return key->img.get();
 }
 
 void tfhe_hip::expand_packing_rows_host(const Params &p, int t, const uint32_t seed10[10], const Torus32 *body, std::vector<Torus32> &rows) {
@@ -147,7 +147,7 @@ void tfhe_hip_delete_packing_key(TfheHipPackingKey *key) {
     if (!key) return;
     if (key->magic != PACK_MAGIC) { set_error("tfhe_hip_delete_packing_key: not a packing key (or already deleted)"); return; }
     auto g = recorder_lock();
-    Engine::get().free_pack_image(key->img, key->img_bytes);      // (waits for the stream: a pack in flight reads the image)
+    Engine::get().free_pack_image(key->img);      // (waits for the stream: a pack in flight reads the image)
     key->magic = 0;
     delete key;
 }

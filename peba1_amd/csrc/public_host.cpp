@@ -19,7 +19,7 @@ struct TfheHipPublicGallery {
     Params p;
     int32_t R;
     std::vector<int32_t> polys;
-    Engine::PublicImage *img;
+    RingImage *img;
 };
 
 namespace {
@@ -31,7 +31,7 @@ const TfheHipPublicGallery *gallery_checked(const std::string &w, const TfheHipP
 }
 
 // the gallery's image, made at first use (under the recorder lock)
-const Engine::PublicImage *gallery_image(const TfheHipPublicGallery *cg) {
+const RingImage *gallery_image(const TfheHipPublicGallery *cg) {
     auto *g = const_cast<TfheHipPublicGallery *>(cg);
     if (!g->img) g->img = Engine::get().upload_public(g->p.N, g->polys.data(), g->R);
     return g->img;
@@ -65,7 +65,7 @@ int mul_impl(const char *who, const TfheHipPublicGallery *g, int32_t first, int3
     if (raw) finish_flight_locked();
     // names no pool slot: what is recorded stays recorded, a flush in flight goes on (the product is ordered behind it on
     // the stream and works in scratch entries of its own)
-    const Engine::PublicImage *img = gallery_image(g);           // out of device memory: ApiError, nothing has changed
+    const RingImage *img = gallery_image(g);           // out of device memory: ApiError, nothing has changed
     Engine::get().run_public_mul(img, g->p.N, first, npolys == 1 ? 0 : 1, ring, count, total, on_device, out);
     return 0;
 }
@@ -98,7 +98,7 @@ int inner_impl(const char *who, const TfheHipPublicGallery *g, const TFheGateBoo
     SlotPool *pool = pool_of_key(bk);
     // a flush in flight owns the key switch's partial sums; what is recorded and has not run stays recorded
     finish_flight_locked();
-    const Engine::PublicImage *img = gallery_image(g);           // out of device memory: ApiError, nothing has changed
+    const RingImage *img = gallery_image(g);           // out of device memory: ApiError, nothing has changed
     import_into_fresh_slots(pool, ResultsView(result), M, [&](const int32_t *slots) {
         Engine::get().run_public_inner(img, g->p, bk->bk->dev, probe, on_device, M, width, pool, slots, nullptr, !on_device);
     });
@@ -177,7 +177,7 @@ int tfhe_hip_kernel_ring_public_rows(const TfheHipPublicGallery *g, const Torus3
         inner_shape(w, g, M, width);
         auto lk = recorder_lock();
         finish_flight_locked();                                  // (the row buffer is the unpack's)
-        const Engine::PublicImage *img = gallery_image(g);
+        const RingImage *img = gallery_image(g);
         Engine::get().run_public_inner(img, g->p, nullptr, probe_ring_words, false, M, width, nullptr, nullptr, out_rows, true);
         return 0;
     });

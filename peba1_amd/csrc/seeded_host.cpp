@@ -228,8 +228,8 @@ int64_t tfhe_hip_test_pack_image(const TfheHipPackingKey *key, const TFheGateBoo
         if (!pack_same_set(key->p, bk->bk->p)) api_fail(std::string(who) + ": the cloud key belongs to another parameter set than the packing key");
         auto g = recorder_lock();
         pool_of_key(bk);
-        const uint32_t *img = pack_image(key, bk);
-        words = (int64_t)Engine::get().read_pack_image(img, key->img_bytes, out, (size_t)capacity);
+        pack_image(key, bk);
+        words = (int64_t)Engine::get().read_pack_image(key->img, out, (size_t)capacity);
     });
     return words;
 }

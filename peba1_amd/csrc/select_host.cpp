@@ -15,7 +15,7 @@ struct TfheHipSelector {
     Params p;
     int32_t nbits;
     std::vector<Torus32> words;
-    Engine::SelectorImage *img;
+    RingImage *img;
 };
 
 namespace {
@@ -69,7 +69,7 @@ const TfheHipSelector *selector_checked(const std::string &w, const TfheHipSelec
 }
 
 // the selector's image, made at first use (under the recorder lock); null for a selector of no bits
-const Engine::SelectorImage *select_image(const TfheHipSelector *csel) {
+const RingImage *select_image(const TfheHipSelector *csel) {
     auto *sel = const_cast<TfheHipSelector *>(csel);
     if (!sel->img && sel->nbits > 0) sel->img = Engine::get().upload_selector(sel->p, sel->words.data(), sel->nbits);
     return sel->img;
@@ -87,7 +87,7 @@ int select_impl(const char *who, const TfheHipSelector *sel, const Torus32 *ring
     auto g = recorder_lock();
     // names no pool slot: what is recorded stays recorded, a flush in flight goes on (the select is ordered behind it on
     // the stream and works in scratch entries of its own)
-    const Engine::SelectorImage *img = select_image(sel);     // out of device memory: ApiError, nothing has changed
+    const RingImage *img = select_image(sel);     // out of device memory: ApiError, nothing has changed
     Engine::get().run_select(img, sel->p, sel->nbits, ring, M, on_device, out, on_device);
     return 0;
 }
@@ -111,7 +111,7 @@ int lookup_impl(const char *who, const TfheHipSelector *sel, const Torus32 *ring
         api_fail(w + "device words must be 16-byte aligned");
     auto g = recorder_lock();
     // like a select: names no pool slot, flushes nothing, waits for no flight
-    const Engine::SelectorImage *img = select_image(sel);
+    const RingImage *img = select_image(sel);
     Engine::get().run_lookup(img, sel->p, sel->nbits, ring, M, width, on_device, out, on_device);
     return 0;
 }
@@ -138,7 +138,7 @@ int inner_impl(const char *who, const TfheHipSelector *sel, int32_t sample, cons
     SlotPool *pool = pool_of_key(bk);
     // a flush in flight owns the key switch's partial sums; what is recorded and has not run stays recorded
     finish_flight_locked();
-    const Engine::SelectorImage *img = select_image(sel);     // out of device memory: ApiError, nothing has changed
+    const RingImage *img = select_image(sel);     // out of device memory: ApiError, nothing has changed
     import_into_fresh_slots(pool, ResultsView(result), M, [&](const int32_t *slots) {
         Engine::get().run_inner(img, sel->p, sample, bk->bk->dev, ring, R, on_device, M, width, pool, slots, nullptr, nullptr, !on_device);
     });
@@ -161,7 +161,7 @@ int inner_raw_impl(const char *who, const TfheHipSelector *sel, int32_t sample, 
     }
     auto g = recorder_lock();
     finish_flight_locked();                                   // (the row buffer is the unpack's)
-    const Engine::SelectorImage *img = select_image(sel);
+    const RingImage *img = select_image(sel);
     Engine::get().run_inner(img, sel->p, sample, nullptr, ring, R, false, M, u_out ? width : N, nullptr, nullptr, u_out, prod_out, true);
     return 0;
 }
@@ -264,7 +264,7 @@ int tfhe_hip_kernel_ring_cmux_rotate(const TfheHipSelector *sel, int32_t bit_ind
         if (rot < 1 || rot >= sel->p.N) api_fail(w + "rot must be in 1.." + std::to_string(sel->p.N - 1));
         if (count < 1 || count > CMUX_MAX_COUNT) api_fail(w + "count must be in 1.." + std::to_string(CMUX_MAX_COUNT));
         auto g = recorder_lock();
-        const Engine::SelectorImage *img = select_image(sel);
+        const RingImage *img = select_image(sel);
         Engine::get().run_cmux(img, sel->p, bit_index, nullptr, d0_words, count, out_words, rot);
         return 0;
     });
@@ -279,7 +279,7 @@ int tfhe_hip_kernel_ring_cmux(const TfheHipSelector *sel, int32_t bit_index, con
         if (bit_index < 0 || bit_index >= sel->nbits) api_fail(w + "bit_index must be in 0.." + std::to_string(sel->nbits - 1));
         if (count < 1 || count > CMUX_MAX_COUNT) api_fail(w + "count must be in 1.." + std::to_string(CMUX_MAX_COUNT));
         auto g = recorder_lock();
-        const Engine::SelectorImage *img = select_image(sel);
+        const RingImage *img = select_image(sel);
         Engine::get().run_cmux(img, sel->p, bit_index, d1_words, d0_words, count, out_words);
         return 0;
     });

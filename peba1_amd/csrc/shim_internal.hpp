@@ -21,8 +21,7 @@ struct TfheHipPackingKey {
     tfhe_hip::Params p;
     int32_t t, basebit;
     std::vector<Torus32> rows;
-    uint32_t *img;
-    size_t img_bytes;
+    tfhe_hip::DeviceBuf<uint32_t> img;       // empty until the first pack
     // a device-expanded key (tfhe_hip_expand_packing_key, seeded_host.cpp) holds the mask seed and the bodies alone: rows
     // stays empty until tfhe_hip_packing_key_words asks for the words
     std::vector<uint32_t> mask_seed; // [10] or empty (a plain key)

@@ -25,6 +25,11 @@ void tfhe_hip_test_set_alloc_cap(int64_t bytes) {
     set_alloc_cap((long long)bytes);
 }
 
+int64_t tfhe_hip_test_alloc_held(void) {
+    auto g = recorder_lock();
+    return (int64_t)alloc_held();
+}
+
 int tfhe_hip_test_stage_place(int64_t pos, int64_t capacity, int32_t outstanding, int64_t bytes, int64_t *out4) {
     if (pos < 0 || capacity < 0 || bytes < 0 || !out4) { set_error("test_stage_place: bad arguments"); return -1; }
     const StagePlace p = stage_place((size_t)pos, (size_t)capacity, outstanding != 0, (size_t)bytes);

@@ -203,6 +203,7 @@ SIGNATURES = {
     "tfhe_hip_set_tuning": (C.c_int, [C.c_char_p, C.c_int64]),
     "tfhe_hip_test_form_admissible": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int]),
     "tfhe_hip_test_set_alloc_cap": (None, [C.c_int64]),
+    "tfhe_hip_test_alloc_held": (C.c_int64, []),
     "tfhe_hip_test_stage_place": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "tfhe_hip_get_stats": (None, [C.POINTER(StatsWhole)]),
     "tfhe_hip_reset_stats": (None, []),
