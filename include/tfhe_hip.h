@@ -978,7 +978,8 @@ int64_t tfhe_hip_test_expand_slots(Torus32 *out, int64_t capacity);
  * form from ONE seeded generator (xoshiro256** through splitmix64) started from `seed` for this call alone.  Draw order,
  * both forms: for every bit, for every row (u, p) in word order: the k N mask words (one `torus` draw each), then the N
  * noise samples (one `gauss` draw each) -- the order of a bootstrapping key's rows.  0, or -1 with the error set and
- * out_words untouched.  Compressed selectors (a mask seed and the bodies) are OUT OF SCOPE: a selector travels as its words.
+ * out_words untouched.  A selector may also travel as a mask seed and its bodies, half the words: "seed-compressed selectors"
+ * below.
  *
  * Server side.  tfhe_hip_new_selector copies nbits TGSW samples (0 <= nbits <= 20; nbits = 0 takes no words) of parameter
  * set `params`.  Every argument is checked before the device is looked at; NULL with the error set for a null pointer,
@@ -1230,6 +1231,68 @@ int tfhe_hip_test_public_bounds(int32_t N, int32_t T);
  * no table)}: |outputs| / P of the forward transform.  plan25 = make_inv_plan(logn): {nsteps, fan[12], renorm[12]}, and
  * *inv_out its out_bound.  -1 with the error set for other arguments. */
 int tfhe_hip_test_ntt_bounds(int32_t logn, double x0, double *fwd2, int32_t *plan25, double *inv_out);
+
+/* ---- seed-compressed selectors: index bits and TGSW probes travel as bodies plus one seed ----
+ * Half the words of every TGSW row are a uniform public mask.  A record of `count` TGSW samples, 1 <= count <= 20, is
+ * TFHE_HIP_TGSW_COMPRESSED_WORDS(k, l, N, count) = 10 + count (k+1) l N words: the mask seed (ChaCha20 key[8], nonce[2]), then
+ * the bodies body[count][(k+1) l][N].  P128: one bit is 6,154 words against the 12,288 of tfhe_hip_tgsw_words; ten index bits
+ * are 245,800 bytes against 491,520.  tfhe_hip_tgsw_compressed_words gives the same count from a parameter set (-1 with the
+ * error set: a null set, a negative count).  The stream is the compressed cloud key's.
+ * Masks.  Mask word m of the record is stream word m of the seed: word 2 (m mod 8) + 1 of ChaCha20 block floor(m / 8) under
+ * (key, nonce), 64-bit block counter from 0 (tfhe_hip_test_chacha20_block).  Masks are numbered in [sample][row][u < k][j]
+ * order, the bootstrapping key's: polynomial u of row r of sample b is stream words ((b (k+1) l + r) k + u) N .. + N - 1.
+ * Rows.  A seeded mask cannot carry a gadget term, so every row's term is on its body, as in a compressed bootstrapping key.
+ * Row (u, p), u <= k, p < l, of a sample with message polynomial m (the constant bit for a bit sample), g_p = 2^(32 - (p+1)
+ * Bgbit), a_u' the row's masks, s_u' the ring key's polynomials, e gaussian of the set's bk_stdev, everything in
+ * Z[X]/(X^N + 1) wrapping mod 2^32:
+ *     body = sum_u' a_u' s_u' + e + g_p m            for u = k
+ *     body = sum_u' a_u' s_u' + e - g_p (m s_u)      for u < k
+ * The phase body - sum a s of the row is e + g_p m resp. e - g_p m s_u: that of the plain row, whose term sits on mask
+ * polynomial u.  The expanded sample -- masks = the stream words verbatim, bodies = the transmitted ones, in the layout
+ * [count][(k+1) l][k+1][N] -- is therefore a VALID TGSW sample of the same message and the same noise, and everything stated
+ * for the private selection, the lookup and the inner products holds for it unchanged.  IT IS NOT the words
+ * tfhe_hip_tgsw_encrypt_bits[_seeded] or _polys would give: there the term is on a mask polynomial, here no mask word
+ * depends on the message.
+ * ONE SEED PER RECORD: two records under one key must never share mask words -- the difference of two rows with equal masks
+ * is the difference of their gadget terms plus noise.  Within a record distinct rows own disjoint stream words by
+ * construction.  The default encryptors therefore draw ten fresh words of OS entropy for every call (and the noise from a
+ * fresh OS-keyed stream), and no entry takes an offset into a stream shared between records.
+ * tfhe_hip_tgsw_encrypt_bits_compressed / _polys_compressed: arguments, count limit and -- for polynomials -- the
+ * coefficient contract of tfhe_hip_tgsw_encrypt_bits / _polys; out_words receives the record.  Noise draws: N gaussians per
+ * row, rows in word order.  The _seeded forms (fixtures only; NOT for samples that protect data) start ONE seeded generator
+ * (xoshiro256** through splitmix64) from `seed` for this record alone: its first ten `torus` draws are the seed words, the
+ * noise follows from the same generator.  Host only.  0, or -1 with the error set and out_words untouched: a null argument,
+ * count outside 1..20.
+ * tfhe_hip_tgsw_expand_host: out_words[count][(k+1) l][k+1][N], the plain words of the record's `count` samples -- what
+ * tfhe_hip_new_selector takes -- the masks drawn from one sequential stream.  Needs no key.  The reference, and the way in
+ * for a caller without a GPU.  0, or -1 with the error set and out_words untouched: a null argument, count outside 1..20.
+ * tfhe_hip_new_selector_compressed: a selector of the first nbits samples, 0 <= nbits <= count, of a record of `count`
+ * samples; it copies the seed and nbits (k+1) l N body words and can be made and deleted on a machine without a GPU.  At its
+ * first use the bodies alone are copied to the card (through the pinned staging area) and the masks are written there into
+ * the staging rows the NTT transform reads: the image is word for word that of tfhe_hip_new_selector over
+ * tfhe_hip_tgsw_expand_host of the same record.  Every entry that takes a selector takes it unchanged (tfhe_hip_ring_select,
+ * tfhe_hip_ring_lookup, tfhe_hip_ring_inner, their device forms, the raw tfhe_hip_kernel_ring_* entries,
+ * tfhe_hip_selector_bits, tfhe_hip_delete_selector).  NULL with the error set for what tfhe_hip_new_selector refuses, in its
+ * words (a null set, nbits outside 0..20, a parameter set or gadget it refuses), for null words, count outside 1..20 and
+ * nbits above count.
+ * tfhe_hip_selector_upload_bytes: the bytes the selector's image copied to the card when it was made -- nbits (k+1) l N * 4
+ * for a compressed selector, twice that (k = 1) for a plain one -- or 0 before the first use; -1 with the error set for a null
+ * or deleted selector. */
+#define TFHE_HIP_TGSW_COMPRESSED_WORDS(k, l, N, count) (10 + (int64_t)(count) * ((k) + 1) * (l) * (N))
+int64_t tfhe_hip_tgsw_compressed_words(const TFheGateBootstrappingParameterSet *params, int32_t count);
+int tfhe_hip_tgsw_encrypt_bits_compressed(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                                          Torus32 *out_words);
+int tfhe_hip_tgsw_encrypt_bits_compressed_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *bits, int32_t count,
+                                                 Torus32 *out_words, uint64_t seed);
+int tfhe_hip_tgsw_encrypt_polys_compressed(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *polys, int32_t count,
+                                           Torus32 *out_words);
+int tfhe_hip_tgsw_encrypt_polys_compressed_seeded(const TFheGateBootstrappingSecretKeySet *secret, const int32_t *polys, int32_t count,
+                                                  Torus32 *out_words, uint64_t seed);
+int tfhe_hip_tgsw_expand_host(const TFheGateBootstrappingParameterSet *params, const Torus32 *compressed_words, int32_t count,
+                              Torus32 *out_words);
+TfheHipSelector *tfhe_hip_new_selector_compressed(const TFheGateBootstrappingParameterSet *params, const Torus32 *compressed_words,
+                                                  int32_t count, int32_t nbits);
+int64_t tfhe_hip_selector_upload_bytes(const TfheHipSelector *selector);
 
 /* ---- kernel-level entry points (K2/K3 parity tests against the oracle) ---- */
 /* exact negacyclic products res[c] = ip[c] * tp[c] mod (X^N+1) mod 2^32 through

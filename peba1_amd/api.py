@@ -955,6 +955,27 @@ class Selector:
         if not self.ptr:
             raise ValueError("selector rejected: " + last_error())
 
+    @classmethod
+    def from_compressed(cls, params, words, nbits=None):
+        """The server's copy of a seed-compressed record (tgsw_encrypt_bits_compressed / _polys_compressed): seed and bodies
+        are kept, only the bodies are copied to the card at first use and the masks are written there
+        (tfhe_hip_new_selector_compressed).  nbits: the first nbits samples of the record (default: all)."""
+        w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+        per_bit = tgsw_compressed_words(params, 1) - 10
+        if w.size <= 10 or (w.size - 10) % per_bit:
+            raise ValueError("a compressed record of this parameter set holds 10 + %d words per sample" % per_bit)
+        count = (w.size - 10) // per_bit
+        self = cls.__new__(cls)
+        self.params, self.nbits = params, count if nbits is None else int(nbits)
+        self.ptr = _l.load().tfhe_hip_new_selector_compressed(params.ptr, _i32p(w), count, self.nbits)
+        if not self.ptr:
+            raise ValueError("selector rejected: " + last_error())
+        return self
+
+    def upload_bytes(self):
+        """The bytes the image's upload copied to the card; 0 before the first use (tfhe_hip_selector_upload_bytes)."""
+        return int(_l.load().tfhe_hip_selector_upload_bytes(self.ptr))
+
     def close(self):
         if self.ptr:
             _l.load().tfhe_hip_delete_selector(self.ptr)
@@ -1064,6 +1085,53 @@ def tgsw_encrypt_polys(polys, key, seed=None):
     rc = (L.tfhe_hip_tgsw_encrypt_polys(key.ptr, _i32p(q), len(q), _i32p(out)) if seed is None
           else L.tfhe_hip_tgsw_encrypt_polys_seeded(key.ptr, _i32p(q), len(q), _i32p(out), int(seed)))
     if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def tgsw_compressed_words(params, count):
+    """The words of a seed-compressed record of `count` TGSW samples: 10 + count (k+1) l N (tfhe_hip_tgsw_compressed_words)."""
+    n = int(_l.load().tfhe_hip_tgsw_compressed_words(params.ptr, int(count)))
+    if n < 0:
+        raise ValueError(last_error())
+    return n
+
+
+def _tgsw_compressed(plain, seeded, values, count, key, seed):
+    out = np.zeros(tgsw_compressed_words(key.params, max(count, 1)), dtype=np.int32)
+    rc = plain(key.ptr, _i32p(values), count, _i32p(out)) if seed is None else seeded(key.ptr, _i32p(values), count, _i32p(out), int(seed))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def tgsw_encrypt_bits_compressed(bits, key, seed=None):
+    """tgsw_encrypt_bits as ONE seed-compressed record (tfhe_hip_tgsw_encrypt_bits_compressed; host only) -> int32
+    [10 + len(bits) (k+1) l N]: a fresh mask seed, then the bodies; half the words.  Selector.from_compressed takes it,
+    tgsw_expand gives the plain words -- which are a valid TGSW sample, NOT those of tgsw_encrypt_bits.  seed: the
+    reproducible form (tests): seed words and noise from one seeded generator."""
+    L = _l.load()
+    b = np.ascontiguousarray(bits, dtype=np.int32).reshape(-1)
+    return _tgsw_compressed(L.tfhe_hip_tgsw_encrypt_bits_compressed, L.tfhe_hip_tgsw_encrypt_bits_compressed_seeded, b, len(b), key, seed)
+
+
+def tgsw_encrypt_polys_compressed(polys, key, seed=None):
+    """tgsw_encrypt_polys as ONE seed-compressed record (tfhe_hip_tgsw_encrypt_polys_compressed), as above."""
+    L = _l.load()
+    q = np.ascontiguousarray(polys, dtype=np.int32).reshape(-1, key.params.N)
+    return _tgsw_compressed(L.tfhe_hip_tgsw_encrypt_polys_compressed, L.tfhe_hip_tgsw_encrypt_polys_compressed_seeded, q, len(q), key, seed)
+
+
+def tgsw_expand(words, params):
+    """The plain words [count][(k+1) l][k+1][N] of a seed-compressed record: the stream words of its seed as masks, its
+    bodies (tfhe_hip_tgsw_expand_host; host only, no key)."""
+    w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+    per_bit = tgsw_compressed_words(params, 1) - 10
+    if w.size <= 10 or (w.size - 10) % per_bit:
+        raise ValueError("a compressed record of this parameter set holds 10 + %d words per sample" % per_bit)
+    count = (w.size - 10) // per_bit
+    out = np.zeros((count, (params.k + 1) * params.l, params.k + 1, params.N), dtype=np.int32)
+    if _l.load().tfhe_hip_tgsw_expand_host(params.ptr, _i32p(w), count, _i32p(out)) != 0:
         raise RuntimeError(last_error())
     return out
 

@@ -39,12 +39,14 @@ $CXX $HOSTFLAGS -c scheduler.cpp -o scheduler.o &
 $CXX $HOSTFLAGS -c io.cpp -o io.o &
 # the host side of ring_public.hip: an object of its own (the list of files shim.cpp includes is closed)
 $CXX $HOSTFLAGS -c public_host.cpp -o public_host.o &
-wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n
+# the seed-compressed selectors (client encryptors, host expansion, the compressed selector), likewise
+$CXX $HOSTFLAGS -c seeded_select_host.cpp -o seeded_select_host.o &
+wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n
 if [ -n "${EXTRA_WAIT-}" ]; then wait -n; fi
 # -Bsymbolic-functions: calls between the library's own exported functions bind inside the library, so
 # another provider of the tfhe API loaded RTLD_GLOBAL in the same process (a CPU tfhe, the tests'
 # plaintext mock) cannot interpose on them
-$HIPCC -shared -Wl,-Bsymbolic-functions -o $OUT kernels.o pack.o unpack.o expand.o cmux.o ks_matrix.o ring_public.o host_keys.o engine.o shim.o scheduler.o io.o public_host.o
+$HIPCC -shared -Wl,-Bsymbolic-functions -o $OUT kernels.o pack.o unpack.o expand.o cmux.o ks_matrix.o ring_public.o host_keys.o engine.o shim.o scheduler.o io.o public_host.o seeded_select_host.o
 echo "built $(realpath $OUT)"
 # circuits: calls only the public tfhe API; symbols resolve at load time against
 # whichever provider is loaded first (libtfhe-hip.so, or the tests' plain mock)

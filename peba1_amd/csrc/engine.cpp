@@ -1354,6 +1354,21 @@ RingImage *Engine::upload_selector(const Params &p, const Torus32 *words, int nb
     return sel.release();
 }
 
+RingImage *Engine::upload_selector_seeded(const Params &p, const uint32_t seed10[10], const Torus32 *bodies, int nbits) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    auto sel = std::make_unique<RingImage>();
+    sel->tw = upload_twiddles(p.N, "the twiddle tables of a selector");
+    DevParams dp{};
+    dp.N = p.N;
+    const ImageRows r{nbits * p.kpl(), p.k + 1, bodies, seed10, true,
+                      {"the NTT image of a selector", "the staging copy of a selector", "the bodies of a compressed selector",
+                       "upload selector bodies", "selector expand", "selector expand: arguments outside what the kernel was built for",
+                       "selector transform", "selector expansion"}};
+    sel->img = upload_image(dp, sel->tw.get(), r, [](ImageStep) {});
+    return sel.release();
+}
+
 void Engine::free_selector(RingImage *sel) { free_image(sel, "sync before selector free", [&] { delete sel; }); }
 
 // the event pair last_select_ms reads, made by the first timed launch

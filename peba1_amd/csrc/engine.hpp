@@ -388,6 +388,10 @@ public:
     // to a cloud key, so it carries its own.  Both buffers are allocated before anything is enqueued: device memory
     // exhausted = ApiError with nothing held.  free_selector waits for the stream first (a select in flight reads both).
     RingImage *upload_selector(const Params &p, const Torus32 *words, int nbits);
+    // The same image from a seed-compressed selector (include/tfhe_hip.h "seed-compressed selectors"): bodies
+    // [nbits][(k+1) l][N] go up through the pinned staging area, launch_expand_bk writes the masks of the staging rows from
+    // the stream of seed10 (rows = nbits (k+1) l, from 2 l for one bit), the transform is upload_selector's.
+    RingImage *upload_selector_seeded(const Params &p, const uint32_t seed10[10], const Torus32 *bodies, int nbits);
     void free_selector(RingImage *sel);
     // The CMUX tree over the M ring samples `ring` (host, or device memory the caller keeps until the stream has passed)
     // under the nbits selector bits of `sel` (null when nbits = 0: a copy), enqueued on the engine's stream behind

@@ -8,15 +8,7 @@
 
 using namespace tfhe_hip;
 
-// the rows [nbits][(k+1) l][k+1][N] of a selector; the device image is made at the first select (a selector can be built
-// and deleted on a machine without a GPU)
-struct TfheHipSelector {
-    uint32_t magic;
-    Params p;
-    int32_t nbits;
-    std::vector<Torus32> words;
-    RingImage *img;
-};
+// (struct TfheHipSelector: shim_internal.hpp -- seeded_select_host.cpp makes the compressed kind)
 
 namespace {
 constexpr uint32_t SELECT_MAGIC = 0x53454C54u;
@@ -71,7 +63,16 @@ const TfheHipSelector *selector_checked(const std::string &w, const TfheHipSelec
 // the selector's image, made at first use (under the recorder lock); null for a selector of no bits
 const RingImage *select_image(const TfheHipSelector *csel) {
     auto *sel = const_cast<TfheHipSelector *>(csel);
-    if (!sel->img && sel->nbits > 0) sel->img = Engine::get().upload_selector(sel->p, sel->words.data(), sel->nbits);
+    if (sel->img || sel->nbits < 1) return sel->img;
+    const int64_t body_bytes = (int64_t)sel->nbits * sel->p.kpl() * sel->p.N * 4;
+    if (sel->mask_seed.empty()) {
+        sel->img = Engine::get().upload_selector(sel->p, sel->words.data(), sel->nbits);
+        sel->upload_bytes = body_bytes * (sel->p.k + 1);
+    } else {
+        // a compressed selector: the bodies go up, the masks are written on the card (expand.hip)
+        sel->img = Engine::get().upload_selector_seeded(sel->p, sel->mask_seed.data(), sel->body.data(), sel->nbits);
+        sel->upload_bytes = body_bytes;
+    }
     return sel->img;
 }
 
@@ -168,6 +169,18 @@ int inner_raw_impl(const char *who, const TfheHipSelector *sel, int32_t sample, 
 
 }  // namespace
 
+TfheHipSelector *tfhe_hip::new_selector_object(const std::string &w, const TFheGateBootstrappingParameterSet *params, int32_t nbits) {
+    if (!params || !params->in_out_params) { set_error(w + "null parameter set"); return nullptr; }
+    if (nbits < 0 || nbits > SELECT_MAX_BITS) { set_error(w + "nbits must be in 0.." + std::to_string(SELECT_MAX_BITS)); return nullptr; }
+    const Params &p = params_of(params);
+    // what a cloud key of this set would be refused for (the CRT range, the kernel forms' gadget range), then the CMUX
+    // kernel's own two bounds
+    if (const char *why = unsupported_reason(p)) { set_error(w + why); return nullptr; }
+    if (const char *why = cmux_gadget_error(p.N, p.k, p.l, p.Bgbit)) { set_error(w + why); return nullptr; }
+    return new TfheHipSelector{SELECT_MAGIC, p, nbits, std::vector<Torus32>(), nullptr, std::vector<uint32_t>(), std::vector<Torus32>(), 0};
+}
+bool tfhe_hip::selector_ok(const TfheHipSelector *sel) { return sel && sel->magic == SELECT_MAGIC; }
+
 extern "C" {
 
 int64_t tfhe_hip_tgsw_words(const TFheGateBootstrappingParameterSet *params) {
@@ -212,13 +225,8 @@ TfheHipSelector *tfhe_hip_new_selector(const TFheGateBootstrappingParameterSet *
     if (!params || !params->in_out_params) { set_error(w + "null parameter set"); return nullptr; }
     if (nbits < 0 || nbits > SELECT_MAX_BITS) { set_error(w + "nbits must be in 0.." + std::to_string(SELECT_MAX_BITS)); return nullptr; }
     if (nbits > 0 && !words) { set_error(w + "null words"); return nullptr; }
-    const Params &p = params_of(params);
-    // what a cloud key of this set would be refused for (the CRT range, the kernel forms' gadget range), then the CMUX
-    // kernel's own two bounds
-    if (const char *why = unsupported_reason(p)) { set_error(w + why); return nullptr; }
-    if (const char *why = cmux_gadget_error(p.N, p.k, p.l, p.Bgbit)) { set_error(w + why); return nullptr; }
-    auto *sel = new TfheHipSelector{SELECT_MAGIC, p, nbits, std::vector<Torus32>(), nullptr};
-    if (nbits > 0) sel->words.assign(words, words + (size_t)nbits * p.kpl() * (p.k + 1) * p.N);
+    TfheHipSelector *sel = new_selector_object(w, params, nbits);
+    if (sel && nbits > 0) sel->words.assign(words, words + (size_t)nbits * sel->p.kpl() * (sel->p.k + 1) * sel->p.N);
     return sel;
 }
 void tfhe_hip_delete_selector(TfheHipSelector *sel) {

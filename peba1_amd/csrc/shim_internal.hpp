@@ -1,6 +1,6 @@
 // shim_internal.hpp -- what the host entry files share: shim.cpp (the public C ABI) and the files it includes into its
 // object (pack_host.cpp, unpack_host.cpp, select_host.cpp, compressed_host.cpp, seeded_host.cpp, seeded_lwe_host.cpp,
-// test_entries.cpp, recorder.cpp).  The object stays one because build.sh is one of the files kernels_sha16 hashes
+// test_entries.cpp, recorder.cpp), and the host files that are objects of their own (public_host.cpp, seeded_select_host.cpp).  The object stays one because build.sh is one of the files kernels_sha16 hashes
 // (kernel_id.py); every one of those files includes this header and whatever else it uses, and parses on its own
 // (tests/test_host_sources_cpu.py), so the order of the include lines at the end of shim.cpp means nothing.
 // Each cross-file function is defined in the file named above its declaration.
@@ -26,6 +26,21 @@ struct TfheHipPackingKey {
     // stays empty until tfhe_hip_packing_key_words asks for the words
     std::vector<uint32_t> mask_seed; // [10] or empty (a plain key)
     std::vector<Torus32> body;       // [n][t][N]
+};
+
+// the rows [nbits][(k+1) l][k+1][N] of a selector; the device image is made at the first select (a selector can be built
+// and deleted on a machine without a GPU)
+struct TfheHipSelector {
+    uint32_t magic;
+    tfhe_hip::Params p;
+    int32_t nbits;
+    std::vector<Torus32> words;
+    RingImage *img;
+    // a compressed selector (tfhe_hip_new_selector_compressed, seeded_select_host.cpp) holds the mask seed and the bodies
+    // alone: words stays empty, and only the bodies reach the card
+    std::vector<uint32_t> mask_seed; // [10] or empty (a plain selector)
+    std::vector<Torus32> body;       // [nbits][(k+1) l][N]
+    int64_t upload_bytes;            // what the image's upload copied to the card; 0 until it is made
 };
 
 namespace tfhe_hip {
@@ -180,6 +195,13 @@ const TfheHipPackingKey *pack_key_checked(const char *who, const TfheHipPackingK
 const uint32_t *pack_image(const TfheHipPackingKey *ckey, const TFheGateBootstrappingCloudKeySet *bk);
 // [n][t][2][N] from seed and bodies [n][t][N]: the mask polynomials are consecutive stretches of one sequential stream
 void expand_packing_rows_host(const Params &p, int t, const uint32_t seed10[10], const Torus32 *body, std::vector<Torus32> &rows);
+
+// ---- select_host.cpp ----
+// An empty selector of nbits bits for an accepted parameter set; null, the error set under the prefix w, for what
+// tfhe_hip_new_selector refuses: a null set, nbits outside 0..SELECT_MAX_BITS, a set no cloud key is accepted with, a
+// gadget outside the CMUX kernel's two bounds.
+TfheHipSelector *new_selector_object(const std::string &w, const TFheGateBootstrappingParameterSet *params, int32_t nbits);
+bool selector_ok(const TfheHipSelector *sel);       // not null, not deleted
 
 // ---- unpack_host.cpp ----
 // msg = the N coefficients that encode `count` bits (+-1/8, then zeros); false, the error set, unless count is in 1..N

@@ -185,16 +185,18 @@ def hamming_probe_poly(bits, N):
     return p
 
 
-def hamming_probe(bits, width, secret, seed=None):
+def hamming_probe(bits, width, secret, seed=None, compressed=False):
     """The client's probe for match_by_inner over a gallery of `width`-bit entries: (the TGSW words of sum_i (1 - 2 b_i)
     X^(-i), ready for api.Selector, and a CiphertextArray of ONE sample that encrypts (sum_i b_i) Delta, the addend that turns
     the inner product into the Hamming distance; Delta is the gallery's, 2^-(log2 width + 2)).  len(bits) must be `width`.
-    seed: the reproducible TGSW form."""
+    seed: the reproducible TGSW form.  compressed: the probe as a seed-compressed record instead (10 + (k+1) l N words, half
+    the bytes), ready for api.Selector.from_compressed."""
     params = secret.params
     b = np.asarray(bits, dtype=np.int64).reshape(-1) & 1
     if len(b) != width:
         raise ValueError("the probe carries %d bits, the gallery's entries %d" % (len(b), width))
-    words = api.tgsw_encrypt_polys(hamming_probe_poly(b, params.N)[None, :], secret, seed=seed)
+    encrypt = api.tgsw_encrypt_polys_compressed if compressed else api.tgsw_encrypt_polys
+    words = encrypt(hamming_probe_poly(b, params.N)[None, :], secret, seed=seed)
     addend = api.CiphertextArray(params, 1)
     api.encrypt_torus(addend.at(0), int(b.sum()) * inner_delta(width), secret)
     return words, addend

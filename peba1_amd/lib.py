@@ -341,6 +341,14 @@ SIGNATURES = {
     "tfhe_hip_kernel_ring_public_rows": (C.c_int, [C.c_void_p, I32P, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_public_bounds": (C.c_int, [C.c_int32, C.c_int32]),
     "tfhe_hip_test_ntt_bounds": (C.c_int, [C.c_int32, C.c_double, C.POINTER(C.c_double), I32P, C.POINTER(C.c_double)]),
+    "tfhe_hip_tgsw_compressed_words": (C.c_int64, [PS, C.c_int32]),
+    "tfhe_hip_tgsw_encrypt_bits_compressed": (C.c_int, [SK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_tgsw_encrypt_bits_compressed_seeded": (C.c_int, [SK, I32P, C.c_int32, I32P, C.c_uint64]),
+    "tfhe_hip_tgsw_encrypt_polys_compressed": (C.c_int, [SK, I32P, C.c_int32, I32P]),
+    "tfhe_hip_tgsw_encrypt_polys_compressed_seeded": (C.c_int, [SK, I32P, C.c_int32, I32P, C.c_uint64]),
+    "tfhe_hip_tgsw_expand_host": (C.c_int, [PS, I32P, C.c_int32, I32P]),
+    "tfhe_hip_new_selector_compressed": (C.c_void_p, [PS, I32P, C.c_int32, C.c_int32]),
+    "tfhe_hip_selector_upload_bytes": (C.c_int64, [C.c_void_p]),
 }
 for _g in _GATE2:
     SIGNATURES[_g] = (None, [LS, LS, LS, CK])

@@ -19,6 +19,7 @@ that follows it.
     python -m peba1_amd.protocol --seeded-inputs         # template and sample travel as seed-compressed ring samples
     python -m peba1_amd.protocol --seeded-lwe            # template and sample travel as seed-compressed LWE sample arrays
     python -m peba1_amd.protocol --packed-gallery        # Hamming match of one claimed identity against a packed gallery
+    python -m peba1_amd.protocol --seeded-selectors      # select, packed lookup and inner products, the TGSW material seed-compressed
 
 With --clients K the server side runs as a multi-user server does: Function_f of all K clients in ONE flush and
 Function_g of all K in a second one (multi-key flushes, tuning "batch_keys"), one JSON line per client.
@@ -26,6 +27,8 @@ Function_g of all K in a second one (multi-key flushes, tuning "batch_keys"), on
 import argparse
 import json
 import time
+
+import numpy as np
 
 from . import api, circuits
 
@@ -136,7 +139,40 @@ def client_inputs(c, nslots, seed):
     return {"key_seed": seed + 1 + c, "template": template, "sample": sample, "r0": (17 + c) % 256, "r1": (99 + 7 * c) % 256}
 
 
-def run_packed_gallery(params, key, templates, claimed, probes, bound, width=128, cloud=None):
+def shipped_selector(params, key, bits=None, polys=None, seeded=False):
+    """What travels for a selector or a TGSW probe, and the server's object made from it: the plain words, or with `seeded`
+    ONE seed-compressed record (ten seed words and the bodies, half the bytes; the masks are written on the card at first
+    use).  Returns (selector, bytes sent, bytes the plain words would have been)."""
+    count = len(bits) if polys is None else len(polys)
+    plain_bytes = 4 * count * api.tgsw_words(params)
+    if seeded:
+        record = (api.tgsw_encrypt_bits_compressed(bits, key) if polys is None else api.tgsw_encrypt_polys_compressed(polys, key))
+        return api.Selector.from_compressed(params, record), int(record.nbytes), plain_bytes
+    words = api.tgsw_encrypt_bits(bits, key) if polys is None else api.tgsw_encrypt_polys(polys, key)
+    return api.Selector(params, words), int(words.nbytes), plain_bytes
+
+
+def run_private_select(params, key, templates, claimed, bitsize=8, seeded_selectors=False):
+    """Verification against a claimed identity by the CMUX tree alone: the gallery rests as one ring sample per template
+    (circuits.ring_encrypt_vector), the client sends the TGSW-encrypted bits of `claimed`, the server selects
+    (identify.select_template) and the client decrypts the selected template.  Returns one dict."""
+    from . import identify
+    M = len(templates)
+    d = max((M - 1).bit_length(), 1)
+    gallery = np.stack([circuits.ring_encrypt_vector(t, bitsize, key) for t in templates])  # enrolment, on the client
+    selector, sent, plain = shipped_selector(params, key, bits=[(claimed >> j) & 1 for j in range(d)], seeded=seeded_selectors)
+    t0 = time.perf_counter()
+    got = identify.select_template(selector, gallery, params, len(templates[claimed]), bitsize, key)
+    t_select = time.perf_counter()
+    values = [circuits.decrypt_number(s, key) for s in got.slots]
+    out = {"run": "select", "entries": M, "selector_bits": d, "selected_is_claimed": values == list(templates[claimed]),
+           "selector_bytes": sent, "selector_bytes_plain": plain, "selector_upload_bytes": selector.upload_bytes(),
+           "seconds": {"select_and_unpack": t_select - t0}}
+    selector.close()
+    return out
+
+
+def run_packed_gallery(params, key, templates, claimed, probes, bound, width=128, cloud=None, seeded_selectors=False):
     """Verification of a claimed identity the server must not learn, against a gallery of `width`-bit templates that rests
     packed (identify.pack_gallery: N / width templates per ring sample).  The client sends the TGSW-encrypted bits of
     `claimed` and, per run, an encrypted probe; the server looks the template up (identify.lookup_template: the CMUX tree
@@ -149,7 +185,7 @@ def run_packed_gallery(params, key, templates, claimed, probes, bound, width=128
     d = max((params.N // width).bit_length() - 1 + max(api.lookup_samples(params, M, width) - 1, 0).bit_length(), 1)
     t0 = time.perf_counter()
     gallery = identify.pack_gallery(templates, width, key)                               # enrolment, on the client
-    selector = api.Selector(params, api.tgsw_encrypt_bits([(claimed >> j) & 1 for j in range(d)], key))
+    selector, sent, plain = shipped_selector(params, key, bits=[(claimed >> j) & 1 for j in range(d)], seeded=seeded_selectors)
     cw = circuits.hamming_count_bits(width)
     enc_bound = circuits.encrypt_number(params, bound, cw, key)
     t_enc = time.perf_counter()
@@ -169,7 +205,7 @@ def run_packed_gallery(params, key, templates, claimed, probes, bound, width=128
             distance = sum(int(a) ^ int(b) for a, b in zip(bits, templates[claimed]))
             out.append({"run": name, "match_bit": int(enc_b.decrypt(key)[0]), "distance": distance, "bound": bound,
                         "expected_bit": int(distance > bound), "entries": M, "width": width, "selector_bits": d,
-                        "gallery_bytes": int(gallery.nbytes),
+                        "gallery_bytes": int(gallery.nbytes), "selector_bytes": sent, "selector_bytes_plain": plain,
                         "seconds": {"enrol": t_enc - t0, "lookup": t_lookup - t1, "hamming_match": t_match - t_lookup},
                         "levels": {"hamming_match": levels}})
     finally:
@@ -178,21 +214,23 @@ def run_packed_gallery(params, key, templates, claimed, probes, bound, width=128
     return out
 
 
-def run_inner_product(params, key, templates, probe, tau, width=128):
+def run_inner_product(params, key, templates, probe, tau, width=128, seeded_selectors=False):
     """Client and server of identify.match_by_inner once: the client enrols the gallery (pack_gallery_inner) and sends the
     probe (hamming_probe); the server answers one match bit per template; the client decrypts.  Yields one record per
     template: its distance, the plaintext decision, the decrypted one and whether the distance lies inside the computed
-    band around tau where the decision is not guaranteed."""
+    band around tau where the decision is not guaranteed, and the probe's bytes on the wire beside the plain figure.
+    seeded_selectors: the probe travels as a seed-compressed record."""
     from . import identify
     gallery = identify.pack_gallery_inner(templates, width, key)          # client, at enrolment
-    tgsw, addend = identify.hamming_probe(probe, width, key)                     # client, per query
-    selector = api.Selector(params, tgsw)                                 # server
+    tgsw, addend = identify.hamming_probe(probe, width, key, compressed=seeded_selectors)      # client, per query
+    selector = api.Selector.from_compressed(params, tgsw) if seeded_selectors else api.Selector(params, tgsw)    # server
     bits = identify.match_by_inner(selector, gallery, len(templates), width, addend, tau, key)
     got = [int(b) for b in bits.decrypt(key)]                             # client
     g = identify.inner_decision_band(params, width)
     for i, t in enumerate(templates):
         d = sum(int(x) ^ int(y) for x, y in zip(t, probe))
-        yield {"entry": i, "distance": d, "plain": int(d <= tau), "decrypted": got[i], "inside_band": abs(d - tau) < g}
+        yield {"entry": i, "distance": d, "plain": int(d <= tau), "decrypted": got[i], "inside_band": abs(d - tau) < g,
+               "probe_bytes": int(tgsw.nbytes), "probe_bytes_plain": 4 * api.tgsw_words(params)}
     selector.close()
     for o in (bits, addend):
         o.close()
@@ -242,7 +280,17 @@ def parse_args(argv=None):
     ap.add_argument("--clear-gallery", action="store_true",
                     help="--inner-product with the roles exchanged: the server owns the gallery in the clear, the probe travels "
                          "as one seed-compressed ring sample; a ring sample times public polynomials, no TGSW sample")
+    ap.add_argument("--seeded-selectors", action="store_true",
+                    help="index bits and TGSW probes travel as seed-compressed records (a seed and the bodies, half the bytes), "
+                         "the masks written on the card; alone: the select, the packed lookup and the inner products in turn; "
+                         "with --packed-gallery or --inner-product: that route")
     a = ap.parse_args(argv)
+    if a.seeded_selectors and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.clear_gallery):
+        ap.error("--seeded-selectors goes with the select, --packed-gallery and --inner-product only")
+    if a.seeded_selectors and a.compressed_keys and not a.packed_gallery:
+        ap.error("--seeded-selectors takes --compressed-keys with --packed-gallery only")
+    if a.seeded_selectors and not 1 <= a.entries <= 1 << 20:
+        ap.error("--entries must be in 1..2^20")
     if a.clear_gallery and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.packed_gallery or a.compressed_keys or a.inner_product):
         ap.error("--clear-gallery runs alone")
     if a.clear_gallery and not 1 <= a.entries <= 1 << 20:
@@ -300,7 +348,14 @@ def main():
     params = api.ParameterSet(128)
     key = api.SecretKeySet(params, a.seed + 1, device=not a.compressed_keys)
     cloud = shipped_cloud(key) if a.compressed_keys else None
-    if a.inner_product or a.clear_gallery:
+    routes = a.seeded_selectors and not (a.packed_gallery or a.inner_product)      # alone: the three routes in turn
+    if routes:
+        import random
+        rnd = random.Random(a.seed)
+        entries = min(a.entries, 64)                                      # (one ring sample per template here)
+        templates = [[rnd.getrandbits(8) for _ in range(4)] for _ in range(entries)]
+        print(json.dumps(run_private_select(params, key, templates, entries * 2 // 3, seeded_selectors=True)))
+    if a.inner_product or a.clear_gallery or routes:
         import random
         rnd = random.Random(a.seed)
         probe = [rnd.getrandbits(1) for _ in range(128)]
@@ -310,11 +365,16 @@ def main():
             for j in rnd.sample(range(128), (5 * i) % 29):
                 t[j] ^= 1
             templates.append(t)
-        for out in (run_clear_gallery if a.clear_gallery else run_inner_product)(params, key, templates, probe, tau=40):
+        if a.clear_gallery:
+            outs = run_clear_gallery(params, key, templates, probe, tau=40)
+        else:
+            outs = run_inner_product(params, key, templates, probe, tau=40, seeded_selectors=a.seeded_selectors)
+        for out in outs:
             print(json.dumps(out))
-        key.close()
-        return
-    if a.packed_gallery:
+        if not routes:
+            key.close()
+            return
+    if a.packed_gallery or routes:
         import random
         rnd = random.Random(a.seed)
         templates = [[rnd.getrandbits(1) for _ in range(128)] for _ in range(a.entries)]
@@ -323,7 +383,8 @@ def main():
         for j in rnd.sample(range(128), 5):
             genuine[j] ^= 1
         probes = {"genuine": genuine, "impostor": [rnd.getrandbits(1) for _ in range(128)]}
-        for out in run_packed_gallery(params, key, templates, claimed, probes, bound=20, cloud=cloud):
+        for out in run_packed_gallery(params, key, templates, claimed, probes, bound=20, cloud=cloud,
+                                      seeded_selectors=a.seeded_selectors):
             print(json.dumps(out))
         if cloud is not None:
             cloud.close()
