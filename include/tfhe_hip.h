@@ -1226,6 +1226,85 @@ int tfhe_hip_kernel_ring_public_rows(const TfheHipPublicGallery *gallery, const 
 /* host-logic test entry: 0 if coefficients up to T pass the CRT bound N T 2^31 < CRT_EXACT_LIMIT at ring size N, 1 if not;
  * -1 with the error set for N outside {1024, 2048} or T < 1 */
 int tfhe_hip_test_public_bounds(int32_t N, int32_t T);
+
+/* ---- public products over several ring samples: long and masked templates ----
+ * sum_t q_t * c_t over K = `terms` ring samples c_0 .. c_(K-1): the public product above as a matrix-vector product instead
+ * of a diagonal one.  The sum is taken in the NTT domain -- per prime and output polynomial K forward transforms, K
+ * products into one 64-bit accumulator, ONE reduction and ONE inverse transform -- followed by one CRT, one extraction and
+ * one key switch.  1 <= terms <= TFHE_HIP_PUBLIC_MAX_TERMS = 8: one accumulator takes 14 products at N = 1024 and 13 at
+ * N = 2048 before its reduction leaves the inverse transform's 4 P (peba1_amd/csrc/ring_public.hpp MAC bound); 8 is the
+ * largest power of two under both, and a static_assert ties the macro to the derivation.  terms = 1 computes the words of
+ * the single-term calls.
+ *
+ * Groups.  The gallery is read as groups of K consecutive polynomials: R = polys / K groups, group g being polynomials
+ * g K .. g K + K - 1; the polynomial count must be a multiple of K.  The probe is K ring samples, [K][(k+1) N] words.
+ * CRT bound of a group.  N (sum_t max|q_t|) 2^31 < CRT_EXACT_LIMIT: the largest magnitudes of a group's K polynomials sum
+ * to at most T = TFHE_HIP_PUBLIC_MAX_COEF(N), what ONE polynomial is held to.  The gallery keeps max|q| of every polynomial
+ * from its construction; every group a call uses is checked before the device is touched, and the refusal names the first
+ * offending group.  Worst case, which reaches N T 2^31 exactly at coefficient N - 1: all coefficients -T / K against words
+ * 0x80000000.
+ * Product.  tfhe_hip_ring_mul_public_sum: out[g] = sum_(t < K) q_(poly_index + g K + t) * c_t for g < ngroups, (k+1) N words
+ * each, 1 <= ngroups <= 65,536, ONE launch; every other contract is tfhe_hip_ring_mul_public's.
+ * Inner products.  tfhe_hip_ring_inner_public_sum:
+ *     result[i] = KeySwitch(Extract_((i mod S) w)(sum_(t < K) q_((i / S) K + t) * c_t))        for i < M <= R S,
+ * S = N / w: ONE launch of ceil(M / S) workgroups per chunk of 8,192 rows, and the unpack's key switch under the same plans.
+ * Every contract is tfhe_hip_ring_inner_public's: all arguments are checked before anything changes; every result is renamed
+ * into a fresh slot; a flush in flight is completed first; recorded operations stay recorded; the device form (the probe's
+ * K (k+1) N words resident on the card, 16-byte aligned) returns with the work enqueued on tfhe_hip_stream();
+ * tfhe_hip_last_select_ms covers the launch.  TfheHipStats has no new field: the key switches count as `keyswitches`.
+ * Variance before the key switch -- COMPUTED from the definition, not measured: sum_t |q_t|_2^2 times the ring samples'
+ * variance (bk_stdev^2 for fresh ones).  There is no other term.
+ *
+ * What it is for (peba1_amd.identify).
+ * Long templates: an entry of K w bits, term t holding bits t w .. t w + w - 1 in the lookup's layout against K probe samples
+ * in probe layout -- an iris code of 2,048 bits at P128 is K = 2, w = 1,024.  The Hamming decision's tail is unchanged, with
+ * Delta = 2^-(log2(K w) + 2) and the addend sample.
+ * Masked templates: code bits b (probe), g (gallery) and validity masks m, n (1 = valid); s = 1 - 2 b, sigma = 1 - 2 g.  The
+ * probe encrypts, per chunk of w bits, the TWO polynomials s_i m_i Delta and m_i Delta in probe layout; the gallery holds,
+ * per chunk, -den sigma_i n_i and (den - 2 num) n_i.  The one summed product is D Delta with
+ *     D = (den - 2 num) valid - den (agree - disagree) = 2 (den disagree - num valid),
+ * valid = sum m n, and disagree / valid <= num / den iff D <= 0.  The server forms Delta / 2 - D Delta with tfhe_hip_linear
+ * (a constant alone; there is NO addend sample) and applies the constant-1/8 LUT bootstrap: TRUE iff D <= 0.
+ * Delta = 2^-(2 + ceil(log2(den L))), L the entry length, keeps |D| Delta below 1/2.  A masked match is one row, one key
+ * switch and one bootstrap per entry: what an unmasked one is.
+ * The weights den and den - 2 num live in the gallery polynomials and so are applied BEFORE the key switch, where the noise
+ * is the ring sample's: sigma^2 = (den^2 + (den - 2 num)^2) (valid gallery bits) bk_stdev^2 in torus units, 3.6e-5 at P128
+ * for 2,048 bits at 8/25 -- against the key switch's 2.8e-3, which enters ONCE.  The two-product route (valid and
+ * agree - disagree as two inner products, weighted by tfhe_hip_linear afterwards) multiplies the key switch's sigma by
+ * sqrt(den^2 + (den - 2 num)^2) = 26.6 at 8/25, 7.4e-2, at twice the product launches and key switches and with a recorded
+ * linear op per entry.  COMPUTED, not measured.
+ * THE DECISION IS NOT EXACT INSIDE THE BAND: it is guaranteed only for |D| >= g, g the smallest integer with
+ * (g - 1/2) Delta >= 6 sigma_dec (peba1_amd.identify.clear_decision_band; sigma_dec ~ 3.7e-3 at P128 as above).  Computed at
+ * P128: long 2,048-bit codes, Delta = 2^-13: g = 184 bits of distance; masked 2,048-bit codes at 8/25, Delta = 2^-18:
+ * g = 5,869 in units of D, which is 118 disagreeing bits at full validity (D moves by 2 den = 50 a bit).
+ * OUT OF SCOPE: an exact decision inside the band, Euclidean distance, probe hoisting (the K forward transforms of the
+ * probe are repeated by every workgroup), the TGSW counterpart (tfhe_hip_ring_inner), multi-key batching, recording these
+ * calls in the op graph, libpeba1-dist, k > 1.
+ *
+ * Return 0, or -1 with tfhe_hip_last_error() set and the call without effect (outputs untouched, results keep values and
+ * slots): terms outside 1 .. TFHE_HIP_PUBLIC_MAX_TERMS, a polynomial count that is not a multiple of terms, a group past the
+ * CRT bound, ngroups outside 1 .. 65,536 or groups outside the gallery, and every refusal of the single-term calls. */
+#define TFHE_HIP_PUBLIC_MAX_TERMS 8
+int tfhe_hip_ring_mul_public_sum(const TfheHipPublicGallery *gallery, int32_t poly_index, int32_t terms, int32_t ngroups,
+                                 const Torus32 *ring_words, Torus32 *out_ring_words);
+int tfhe_hip_ring_mul_public_sum_device(const TfheHipPublicGallery *gallery, int32_t poly_index, int32_t terms, int32_t ngroups,
+                                        const void *device_ring_words, void *device_out);
+int tfhe_hip_ring_inner_public_sum(const TfheHipPublicGallery *gallery, const TFheGateBootstrappingCloudKeySet *bk,
+                                   const Torus32 *probe_ring_words, int32_t terms, int32_t M, int32_t width, LweSample *result);
+int tfhe_hip_ring_inner_public_sum_device(const TfheHipPublicGallery *gallery, const TFheGateBootstrappingCloudKeySet *bk,
+                                          const void *device_probe_ring_words, int32_t terms, int32_t M, int32_t width,
+                                          LweSample *result);
+/* raw test entry: the sums of tfhe_hip_ring_mul_public_sum's host form, after a flush in flight has completed */
+int tfhe_hip_kernel_ring_public_sum_product(const TfheHipPublicGallery *gallery, int32_t poly_index, int32_t terms, int32_t ngroups,
+                                            const Torus32 *ring_words, Torus32 *out_words);
+/* raw test entry: the extracted rows before the key switch, out_rows[i] (kN+1 words) = Extract_((i mod S) width)(sum_t
+ * q_((i / S) terms + t) * probe_t) for i < M <= R S; no slots involved */
+int tfhe_hip_kernel_ring_public_sum_rows(const TfheHipPublicGallery *gallery, const Torus32 *probe_ring_words, int32_t terms,
+                                         int32_t M, int32_t width, Torus32 *out_rows);
+/* host-logic test entry: 0 if a group of `terms` polynomials whose largest magnitudes sum to coef_sum passes the CRT bound
+ * at ring size N (coef_sum <= TFHE_HIP_PUBLIC_MAX_COEF(N)), 1 if not; -1 with the error set for N outside {1024, 2048},
+ * terms outside 1 .. TFHE_HIP_PUBLIC_MAX_TERMS or coef_sum < 0 */
+int tfhe_hip_test_public_sum_bounds(int32_t N, int32_t terms, int64_t coef_sum);
 /* host-logic test entry: the magnitude recurrences of the wave NTT as the library states them, for a transform of 2^logn
  * points (logn = 9, 10, 11) on inputs |x| <= x0.  fwd2 = {pack_forward_bound(logn, x0), br_forms forward_bound(logn, x0 / P,
  * no table)}: |outputs| / P of the forward transform.  plan25 = make_inv_plan(logn): {nsteps, fan[12], renorm[12]}, and

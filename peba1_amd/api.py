@@ -1291,6 +1291,94 @@ def kernel_ring_public_rows(gallery, probe_ring, M, width):
     return u
 
 
+PUBLIC_MAX_TERMS = 8     # TFHE_HIP_PUBLIC_MAX_TERMS (include/tfhe_hip.h)
+
+
+def _sum_groups(gallery, first, terms, ngroups):
+    terms = int(terms)
+    if terms < 1:
+        raise ValueError("terms must be at least 1")
+    return terms, (gallery.count - int(first)) // terms if ngroups is None else int(ngroups)
+
+
+def ring_mul_public_sum(gallery, ring, terms, first=0, ngroups=None, device=False):
+    """sum_t q_(first + g terms + t) * c_t for g < ngroups (tfhe_hip_ring_mul_public_sum): `ring` holds the `terms` ring
+    samples c_t, the gallery is read as groups of `terms` consecutive polynomials (default: every group from `first` to
+    its end) -> [ngroups][(k+1) N], ONE launch.  Recorded operations stay recorded.  device=False: host words in, a numpy
+    array out.  device=True: `ring` is an int32 torch tensor resident on the engine's device and the result a new tensor
+    there, stream-ordered on tfhe_hip_stream()."""
+    p = gallery.params
+    sw = (p.k + 1) * p.N
+    L = _l.load()
+    terms, ngroups = _sum_groups(gallery, first, terms, ngroups)
+    if device:
+        import torch
+        if ring.dtype != torch.int32 or not ring.is_contiguous() or ring.numel() != terms * sw:
+            raise ValueError("device ring words are a contiguous int32 tensor of terms (k+1) N words")
+        out = torch.empty(max(ngroups, 1) * sw, dtype=torch.int32, device=ring.device)
+        rc = L.tfhe_hip_ring_mul_public_sum_device(gallery.ptr, int(first), terms, ngroups, C.c_void_p(ring.data_ptr()), C.c_void_p(out.data_ptr()))
+    else:
+        c = _ring_words(ring, p)
+        if c.shape[0] != terms:
+            raise ValueError("the ring words are `terms` samples of (k+1) N words")
+        out = np.zeros((max(ngroups, 1), sw), dtype=np.int32)
+        rc = L.tfhe_hip_ring_mul_public_sum(gallery.ptr, int(first), terms, ngroups, _i32p(c), _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def ring_inner_public_sum(gallery, probe_ring, terms, M, width, key, result, first=0, device=False):
+    """The inner products of ONE encrypted probe of `terms` ring samples with a clear gallery of groups of `terms`
+    polynomials (tfhe_hip_ring_inner_public_sum): result[first + i] receives, in a fresh slot, the key switch of coefficient
+    (i mod S) width of sum_t q_((i / S) terms + t) * probe_t.  key: the keyset whose cloud key evaluates.  device=True: the
+    probe's terms (k+1) N words are an int32 torch tensor on the engine's device; the call returns with the work enqueued."""
+    p = gallery.params
+    sw = (p.k + 1) * p.N
+    L = _l.load()
+    terms = int(terms)
+    if device:
+        import torch
+        if probe_ring.dtype != torch.int32 or not probe_ring.is_contiguous() or probe_ring.numel() != terms * sw:
+            raise ValueError("a device probe is a contiguous int32 tensor of terms (k+1) N words")
+        rc = L.tfhe_hip_ring_inner_public_sum_device(gallery.ptr, key.cloud, C.c_void_p(probe_ring.data_ptr()), terms, int(M), int(width),
+                                                     result.at(first))
+    else:
+        c = _ring_words(probe_ring, p)
+        if c.shape[0] != terms:
+            raise ValueError("the probe is `terms` ring samples of (k+1) N words")
+        rc = L.tfhe_hip_ring_inner_public_sum(gallery.ptr, key.cloud, _i32p(c), terms, int(M), int(width), result.at(first))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def kernel_ring_public_sum_product(gallery, ring, terms, first=0, ngroups=None):
+    """ring_mul_public_sum's host form through the raw test entry (tfhe_hip_kernel_ring_public_sum_product)."""
+    p = gallery.params
+    c = _ring_words(ring, p)
+    terms, ngroups = _sum_groups(gallery, first, terms, ngroups)
+    if c.shape[0] != terms:
+        raise ValueError("the ring words are `terms` samples of (k+1) N words")
+    out = np.zeros((max(ngroups, 1), (p.k + 1) * p.N), dtype=np.int32)
+    if _l.load().tfhe_hip_kernel_ring_public_sum_product(gallery.ptr, int(first), terms, ngroups, _i32p(c), _i32p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def kernel_ring_public_sum_rows(gallery, probe_ring, terms, M, width):
+    """The rows ring_inner_public_sum key-switches, before the key switch (tfhe_hip_kernel_ring_public_sum_rows): int32
+    [M][kN+1]."""
+    p = gallery.params
+    c = _ring_words(probe_ring, p)
+    if c.shape[0] != int(terms):
+        raise ValueError("the probe is `terms` ring samples of (k+1) N words")
+    u = np.zeros((int(M), p.k * p.N + 1), dtype=np.int32)
+    if _l.load().tfhe_hip_kernel_ring_public_sum_rows(gallery.ptr, _i32p(c), int(terms), int(M), int(width), _i32p(u)) != 0:
+        raise RuntimeError(last_error())
+    return u
+
+
 def ring_trivial(params, values):
     """The noiseless ring sample (0, values): a zero mask and the 1..N torus words `values` as the body (zero behind them).
     It decrypts to `values` under every key, so a gallery of such samples is a PUBLIC table, and ring_lookup over it

@@ -1633,6 +1633,57 @@ void Engine::run_public_inner(const RingImage *g, const Params &p, const DeviceK
     finish(wait || !probe_on_device, "ring inner public");
 }
 
+void Engine::run_public_sum_mul(const RingImage *g, int N, int first, int terms, int ngroups, const Torus32 *ring, bool on_device,
+                                Torus32 *out) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t sw = (size_t)2 * N;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    int32_t *dring = on_device ? nullptr : scratch_as<int32_t>(S_PUBLIC_RING, (size_t)terms * sw);
+    int32_t *dout = on_device ? out : scratch_as<int32_t>(S_PUBLIC_OUT, (size_t)ngroups * sw);
+    ensure_select_events();
+    if (!on_device) h2d(dring, ring, (size_t)terms * sw, "upload ring words");
+    PublicSumArgs a{};
+    a.N = N; a.count = ngroups; a.terms = terms;
+    a.ring = on_device ? ring : dring; a.img = g->img.get() + (size_t)first * sw; a.tw = g->tw.get(); a.out = dout;
+    if (kernel_timing) hip_check(hipEventRecord(select_e0_, stream_), "select event");
+    if (!launch_public_sum(stream_, a)) api_fail("ring mul public sum: arguments outside what the kernel was built for");
+    hip_check(hipGetLastError(), "ring mul public sum launch");
+    if (kernel_timing) hip_check(hipEventRecord(select_e1_, stream_), "select event");
+    select_timed_ = kernel_timing;
+    if (!on_device) d2h(out, dout, (size_t)ngroups * sw, "download product words");
+    finish(!on_device, "ring mul public sum");
+}
+
+void Engine::run_public_sum_inner(const RingImage *g, const Params &p, const DeviceKeyImage *key, int terms, const Torus32 *probe,
+                                  bool probe_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out,
+                                  bool wait) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t sw = (size_t)2 * p.N;
+    const int S = p.N / width;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    int32_t *dprobe = probe_on_device ? nullptr : scratch_as<int32_t>(S_PUBLIC_RING, (size_t)terms * sw);
+    const RowsPlan r = size_rows(key, p.u_stride(), M, !u_out);
+    ensure_select_events();
+    if (!probe_on_device) h2d(dprobe, probe, (size_t)terms * sw, "upload probe words");
+    PublicSumArgs a{};
+    a.N = p.N; a.terms = terms; a.ring = probe_on_device ? probe : dprobe; a.tw = g->tw.get();
+    a.rows.width = width; a.rows.u_stride = r.u_stride; a.rows.u_buf = r.u_buf;
+    run_rows(key, r, M, (size_t)p.k * p.N + 1, pool, slots, u_out, "ring inner public sum", [&](int done, int cnt) {
+        // a chunk starts on a group: S divides UNPACK_CHUNK (both powers of two, S <= N <= UNPACK_CHUNK)
+        a.img = g->img.get() + (size_t)(done / S) * terms * sw; a.count = (cnt + S - 1) / S; a.rows.M = cnt;
+        if (kernel_timing && done == 0) hip_check(hipEventRecord(select_e0_, stream_), "select event");
+        if (!launch_public_sum(stream_, a)) api_fail("ring inner public sum: arguments outside what the kernel was built for");
+        hip_check(hipGetLastError(), "ring inner public sum launch");
+        if (kernel_timing && done + cnt == M) hip_check(hipEventRecord(select_e1_, stream_), "select event");
+    });
+    select_timed_ = kernel_timing;
+    if (u_out) return;
+    // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
+    finish(wait || !probe_on_device, "ring inner public sum");
+}
+
 size_t Engine::read_extract_rows(Torus32 *out, size_t capacity) {
     const size_t words = last_extract_words_;                     // (the buffer was sized by that launch: no growth)
     return read_back(words, out, capacity, "extract rows", [&] { return scratch_as<int32_t>(S_UNPACK_EXTRACT, words); });

@@ -322,8 +322,8 @@ private:
         S_SELECT_A,       // run_select / run_lookup: the launches 0, 2, ... (ping), tree levels then rotations; run_cmux: the results
         S_SELECT_B,       // run_select / run_lookup: the launches 1, 3, ... (pong)
         S_CMUX_D1,        // raw, run_cmux: the d1 operands
-        S_PUBLIC_RING,    // run_public_mul, run_public_inner: the ring words on their way from a host source
-        S_PUBLIC_OUT,     // run_public_mul: the products on their way to a host destination
+        S_PUBLIC_RING,    // run_public[_sum]_mul, run_public[_sum]_inner: the ring words on their way from a host source
+        S_PUBLIC_OUT,     // run_public[_sum]_mul: the products on their way to a host destination
     };
     void *scratch(Scratch idx, size_t bytes);
     // the same by element count (and `margin` bytes), and `count` elements between host and device on the engine's stream
@@ -449,6 +449,16 @@ public:
     // alone (key may be null).  The caller has checked every argument and, for the slot form, waited for the flight.
     void run_public_inner(const RingImage *g, const Params &p, const DeviceKeyImage *key, const Torus32 *probe, bool probe_on_device,
                           int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait);
+    // Sums of products over `terms` ring samples (ring_public.hpp PublicSumArgs; include/tfhe_hip.h "public products over
+    // several ring samples"): out[g] = sum_t q_(first + g terms + t) * c_t for g < ngroups in ONE launch, `ring` the
+    // [terms][(k+1) N] words of the samples.  Everything else as run_public_mul.  The caller has checked the groups'
+    // CRT bound.
+    void run_public_sum_mul(const RingImage *g, int N, int first, int terms, int ngroups, const Torus32 *ring, bool on_device,
+                            Torus32 *out);
+    // run_public_inner over groups: entry i < M is the row Extract_((i mod S) width)(sum_t q_((i / S) terms + t) * probe_t),
+    // a further row maker for run_rows -- the same chunks, the same key-switch plans.
+    void run_public_sum_inner(const RingImage *g, const Params &p, const DeviceKeyImage *key, int terms, const Torus32 *probe,
+                              bool probe_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait);
 private:
     // The one upload path of the transformed images (engine.cpp upload_image).  ImageRows: what an image is made from --
     // `rows` rows of `polys` polynomials, raw at `host`, or with seed10 their bodies alone at `host` (staged: through the
@@ -464,7 +474,7 @@ private:
     DeviceBuf<uint32_t> upload_twiddles(int N, const char *what);
     template <class Drop> void free_image(bool made, const char *what, Drop &&drop);
     template <class Src> size_t read_back(size_t words, Torus32 *out, size_t capacity, const char *what, Src &&src);
-    // what run_unpack, run_inner and run_public_inner share (engine.cpp): the buffers and key-switch plans of `count` rows, then the chunks
+    // what run_unpack, run_inner, run_public_inner and run_public_sum_inner share (engine.cpp): the buffers and key-switch plans of `count` rows, then the chunks
     struct RowsPlan { int widest = 0, u_stride = 0; KsDesc *dks = nullptr; int32_t *u_buf = nullptr; KsLaunchPlan ks_wide, ks_last; };
     RowsPlan size_rows(const DeviceKeyImage *key, int u_stride, int count, bool to_slots);
     template <class MakeRows>

@@ -2,6 +2,7 @@
 // public polynomials"): the gallery object and the C ABI of the product and of the inner products against a clear gallery.
 // No arithmetic happens here (ring_public.hip); the bounds a gallery is checked against are ring_public.hpp's.  An object
 // of its own in build.sh: shim.cpp's list of included files is closed (tests/test_host_sources_cpu.py).
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -11,6 +12,9 @@ using namespace tfhe_hip;
 
 static_assert(TFHE_HIP_PUBLIC_MAX_COEF(1024) == public_max_coef(1024) && TFHE_HIP_PUBLIC_MAX_COEF(2048) == public_max_coef(2048),
               "the header's T is the one ring_public.hpp derives");
+static_assert(TFHE_HIP_PUBLIC_MAX_TERMS == PUBLIC_MAX_TERMS && TFHE_HIP_PUBLIC_MAX_TERMS <= public_sum_mac_terms(1024) &&
+                  TFHE_HIP_PUBLIC_MAX_TERMS <= public_sum_mac_terms(2048) && 2 * TFHE_HIP_PUBLIC_MAX_TERMS > public_sum_mac_terms(2048),
+              "the header's term count is the largest power of two under the MAC bound ring_public.hpp derives (13 at N = 2048)");
 
 // R polynomials [R][N] of a ring (N, k = 1); the device image is made at the first product (a gallery can be built and
 // deleted on a machine without a GPU)
@@ -20,6 +24,7 @@ struct TfheHipPublicGallery {
     int32_t R;
     std::vector<int32_t> polys;
     RingImage *img;
+    std::vector<int32_t> maxabs;     // max|q| of every polynomial, from construction (the CRT bound of a group of terms)
 };
 
 namespace {
@@ -105,6 +110,84 @@ int inner_impl(const char *who, const TfheHipPublicGallery *g, const TFheGateBoo
     return 0;
 }
 
+// ---- sums over several ring samples (ring_public.hpp "sums of products over several ring samples") ----
+// terms and the gallery read as groups of them
+void sum_terms_checked(const std::string &w, const TfheHipPublicGallery *g, int32_t terms) {
+    if (terms < 1 || terms > PUBLIC_MAX_TERMS) api_fail(w + "terms must be in 1.." + std::to_string(PUBLIC_MAX_TERMS));
+    if (g->R % terms) api_fail(w + "the gallery's " + std::to_string(g->R) + " polynomials are not a multiple of terms = " + std::to_string(terms));
+}
+// the CRT bound of the `ngroups` groups from polynomial first_poly on, before the device is looked at; the first offending
+// group is named
+void sum_crt_checked(const std::string &w, const TfheHipPublicGallery *g, int32_t terms, int64_t first_poly, int64_t ngroups) {
+    for (int64_t grp = 0; grp < ngroups; ++grp) {
+        int64_t sum = 0;
+        for (int t = 0; t < terms; ++t) sum += g->maxabs[(size_t)(first_poly + grp * terms + t)];
+        if (!public_sum_crt_ok(g->p.N, terms, sum))
+            api_fail(w + "group " + std::to_string(grp) + " (polynomials " + std::to_string(first_poly + grp * terms) + ".." +
+                     std::to_string(first_poly + grp * terms + terms - 1) + "): its terms' largest coefficients sum to " + std::to_string(sum) +
+                     ", past " + std::to_string(public_max_coef(g->p.N)) + ", the exact range of the two-prime CRT (ring_public.hpp CRT bound)");
+    }
+}
+
+int sum_mul_impl(const char *who, const TfheHipPublicGallery *g, int32_t first, int32_t terms, int32_t ngroups, const Torus32 *ring,
+                 Torus32 *out, bool on_device, bool raw) {
+    const std::string w = std::string(who) + ": ";
+    gallery_checked(w, g);
+    if (!ring || !out) api_fail(w + "null ring words or destination");
+    sum_terms_checked(w, g, terms);
+    if (ngroups < 1 || ngroups > PUBLIC_MAX_COUNT) api_fail(w + "ngroups must be in 1.." + std::to_string(PUBLIC_MAX_COUNT));
+    if (first < 0 || (int64_t)first + (int64_t)ngroups * terms > g->R)
+        api_fail(w + "poly_index .. poly_index + ngroups terms - 1 must lie in 0.." + std::to_string(g->R - 1));
+    sum_crt_checked(w, g, terms, first, ngroups);
+    if (on_device) {
+        const uintptr_t rb = reinterpret_cast<uintptr_t>(ring), ob = reinterpret_cast<uintptr_t>(out);
+        if ((rb | ob) & 15) api_fail(w + "device words must be 16-byte aligned");
+        const uintptr_t sb = (uintptr_t)2 * g->p.N * 4;
+        if (rb < ob + (uintptr_t)ngroups * sb && ob < rb + (uintptr_t)terms * sb) api_fail(w + "the destination overlaps the ring words");
+    }
+    auto lk = recorder_lock();
+    if (raw) finish_flight_locked();
+    // as tfhe_hip_ring_mul_public: names no pool slot, what is recorded stays recorded, a flush in flight goes on
+    const RingImage *img = gallery_image(g);           // out of device memory: ApiError, nothing has changed
+    Engine::get().run_public_sum_mul(img, g->p.N, first, terms, ngroups, ring, on_device, out);
+    return 0;
+}
+
+// what the summed inner products and their raw rows check alike
+void sum_inner_shape(const std::string &w, const TfheHipPublicGallery *g, int32_t terms, int32_t M, int32_t width) {
+    const int N = g->p.N;
+    sum_terms_checked(w, g, terms);
+    if (width < 1 || width > N || (width & (width - 1))) api_fail(w + "width must be a power of two in 1.." + std::to_string(N));
+    if (M < 1) api_fail(w + "M must be at least 1");
+    const int64_t S = N / width, groups = g->R / terms;
+    if ((int64_t)M > groups * S)
+        api_fail(w + "M = " + std::to_string(M) + " entries of width " + std::to_string(width) + " need more than the " + std::to_string(groups) +
+                 " groups of the gallery");
+    sum_crt_checked(w, g, terms, 0, (M + S - 1) / S);
+}
+
+int sum_inner_impl(const char *who, const TfheHipPublicGallery *g, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *probe,
+                   int32_t terms, int32_t M, int32_t width, LweSample *result, bool on_device) {
+    const std::string w = std::string(who) + ": ";
+    if (!probe || !result) api_fail(w + "null ring words or result");
+    if (!bk || !bk->bk) api_fail(w + "null cloud key");
+    gallery_checked(w, g);
+    const Params &p = bk->bk->p;
+    if (p.N != g->p.N || p.k != g->p.k) api_fail(w + "the gallery and the cloud key belong to different rings");
+    sum_inner_shape(w, g, terms, M, width);
+    if (on_device && (reinterpret_cast<uintptr_t>(probe) & 15)) api_fail(w + "device words must be 16-byte aligned");
+    auto lk = recorder_lock();
+    check_runs(w, UNPACK_RESULT, ResultsView(result), M, p);
+    SlotPool *pool = pool_of_key(bk);
+    // a flush in flight owns the key switch's partial sums; what is recorded and has not run stays recorded
+    finish_flight_locked();
+    const RingImage *img = gallery_image(g);           // out of device memory: ApiError, nothing has changed
+    import_into_fresh_slots(pool, ResultsView(result), M, [&](const int32_t *slots) {
+        Engine::get().run_public_sum_inner(img, g->p, bk->bk->dev, terms, probe, on_device, M, width, pool, slots, nullptr, !on_device);
+    });
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -125,7 +208,9 @@ TfheHipPublicGallery *tfhe_hip_new_public_gallery(const TFheGateBootstrappingPar
                       ", the exact range of the two-prime CRT (ring_public.hpp CRT bound)");
             return nullptr;
         }
-    return new TfheHipPublicGallery{PUBLIC_MAGIC, p, R, std::vector<int32_t>(polys, polys + words), nullptr};
+    std::vector<int32_t> maxabs((size_t)R, 0);
+    for (int64_t j = 0; j < words; ++j) maxabs[j / p.N] = std::max(maxabs[j / p.N], polys[j] < 0 ? -polys[j] : polys[j]);
+    return new TfheHipPublicGallery{PUBLIC_MAGIC, p, R, std::vector<int32_t>(polys, polys + words), nullptr, std::move(maxabs)};
 }
 void tfhe_hip_delete_public_gallery(TfheHipPublicGallery *g) {
     if (!g) return;
@@ -189,6 +274,56 @@ int tfhe_hip_test_public_bounds(int32_t N, int32_t T) {
         return -1;
     }
     return public_crt_ok(N, T) ? 0 : 1;
+}
+
+int tfhe_hip_ring_mul_public_sum(const TfheHipPublicGallery *g, int32_t poly_index, int32_t terms, int32_t ngroups, const Torus32 *ring_words,
+                                 Torus32 *out_ring_words) {
+    return guarded_rc([&] { return sum_mul_impl("tfhe_hip_ring_mul_public_sum", g, poly_index, terms, ngroups, ring_words, out_ring_words, false, false); });
+}
+int tfhe_hip_ring_mul_public_sum_device(const TfheHipPublicGallery *g, int32_t poly_index, int32_t terms, int32_t ngroups,
+                                        const void *device_ring_words, void *device_out) {
+    return guarded_rc([&] {
+        return sum_mul_impl("tfhe_hip_ring_mul_public_sum_device", g, poly_index, terms, ngroups, static_cast<const Torus32 *>(device_ring_words),
+                            static_cast<Torus32 *>(device_out), true, false);
+    });
+}
+int tfhe_hip_ring_inner_public_sum(const TfheHipPublicGallery *g, const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *probe_ring_words,
+                                   int32_t terms, int32_t M, int32_t width, LweSample *result) {
+    return guarded_rc([&] { return sum_inner_impl("tfhe_hip_ring_inner_public_sum", g, bk, probe_ring_words, terms, M, width, result, false); });
+}
+int tfhe_hip_ring_inner_public_sum_device(const TfheHipPublicGallery *g, const TFheGateBootstrappingCloudKeySet *bk,
+                                          const void *device_probe_ring_words, int32_t terms, int32_t M, int32_t width, LweSample *result) {
+    return guarded_rc([&] {
+        return sum_inner_impl("tfhe_hip_ring_inner_public_sum_device", g, bk, static_cast<const Torus32 *>(device_probe_ring_words), terms, M,
+                              width, result, true);
+    });
+}
+int tfhe_hip_kernel_ring_public_sum_product(const TfheHipPublicGallery *g, int32_t poly_index, int32_t terms, int32_t ngroups,
+                                            const Torus32 *ring_words, Torus32 *out_words) {
+    return guarded_rc(
+        [&] { return sum_mul_impl("tfhe_hip_kernel_ring_public_sum_product", g, poly_index, terms, ngroups, ring_words, out_words, false, true); });
+}
+int tfhe_hip_kernel_ring_public_sum_rows(const TfheHipPublicGallery *g, const Torus32 *probe_ring_words, int32_t terms, int32_t M,
+                                         int32_t width, Torus32 *out_rows) {
+    return guarded_rc([&] {
+        const std::string w = "tfhe_hip_kernel_ring_public_sum_rows: ";
+        gallery_checked(w, g);
+        if (!probe_ring_words || !out_rows) api_fail(w + "null argument");
+        sum_inner_shape(w, g, terms, M, width);
+        auto lk = recorder_lock();
+        finish_flight_locked();                                  // (the row buffer is the unpack's)
+        const RingImage *img = gallery_image(g);
+        Engine::get().run_public_sum_inner(img, g->p, nullptr, terms, probe_ring_words, false, M, width, nullptr, nullptr, out_rows, true);
+        return 0;
+    });
+}
+
+int tfhe_hip_test_public_sum_bounds(int32_t N, int32_t terms, int64_t coef_sum) {
+    if ((N != 1024 && N != 2048) || terms < 1 || terms > PUBLIC_MAX_TERMS || coef_sum < 0) {
+        set_error("test_public_sum_bounds: bad arguments");
+        return -1;
+    }
+    return public_sum_crt_ok(N, terms, coef_sum) ? 0 : 1;
 }
 
 }  // extern "C"

@@ -105,4 +105,64 @@ struct PublicArgs {
 // false, and nothing launched, for arguments outside what the kernel was built and bounded for
 bool launch_public(hipStream_t s, const PublicArgs &a);
 
+// ---- sums of products over several ring samples (include/tfhe_hip.h "public products over several ring samples") ----
+// out[u] = sum_(t < K) q_t(X) * c_t[u](X): K ring samples c_t against the K polynomials of one GROUP of the gallery, the
+// sum taken in the NTT domain -- per prime and output polynomial u, K forward transforms, K products with an image word
+// into one 64-bit accumulator, ONE Montgomery reduction, ONE inverse transform -- then the signed CRT once.  A public
+// matrix-vector product where public_kernel is a diagonal one.  The forward input bound and the gallery transform are
+// those above, per term; the other two bounds change.
+// MAC bound (how many products one int64 accumulator takes before its reduction), cmux.hpp's with this file's f.
+//   K products of a transform output |x| < f P (f = public_forward_bound: 7.6 / 8.2) and a canonical image word
+//   0 <= w < P: |acc| < K f P^2; its Montgomery reduction is below K f P^2 / 2^32 + P/2, and the inverse transform takes
+//   inputs below 4 P (make_inv_plan), hence
+//       K * f * P / 2^32 < 3.5               K <= 14 (N = 1024),  K <= 13 (N = 2048)
+//   (|acc| < 3.5 P 2^32 < 2^61 then holds with it: no int64 overflow).  PUBLIC_MAX_TERMS is the largest power of two both
+//   rings take: 8.  K = 1 is public_product_ok, and the kernel then computes public_kernel's words (one product, the same
+//   reduction).
+// CRT bound.  A coefficient of sum_t q_t c_t[u] is a sum of K N products of a coefficient and a word:
+//       |S| <= N * (sum_t max|q_t|) * 2^31 < CRT_EXACT_LIMIT
+//   so the per-term maxima of a group may sum to T = public_max_coef(N), the power of two a single polynomial is held to:
+//   a group is held to what ONE polynomial is, and K = 1 changes nothing.  The gallery keeps max|q| of every polynomial
+//   from its construction and the host caller adds them up per group before the device is touched (public_host.cpp).
+//   All q_t[j] = -T / K against words 0x80000000 reach N T 2^31 exactly, at coefficient N - 1.
+constexpr int PUBLIC_MAX_TERMS = 8;
+constexpr bool public_sum_mac_ok(int N, int terms) {
+    const double P = (double)NTT_P[1];
+    return terms >= 1 && (double)terms * public_forward_bound(pack_logn(N)) * P / 4294967296.0 < 3.5;
+}
+// the most terms the MAC bound takes
+constexpr int public_sum_mac_terms(int N) {
+    int K = 0;
+    while (K < 64 && public_sum_mac_ok(N, K + 1)) ++K;
+    return K;
+}
+constexpr bool public_sum_crt_ok(int N, int terms, int64_t coef_sum) {
+    return terms >= 1 && terms <= PUBLIC_MAX_TERMS && coef_sum >= 0 && coef_sum <= public_max_coef(N) &&
+           (coef_sum == 0 || public_crt_ok(N, coef_sum));
+}
+static_assert(public_sum_mac_terms(1024) == 14 && public_sum_mac_terms(2048) == 13, "MAC bound: the exact figures");
+static_assert(public_sum_mac_ok(1024, PUBLIC_MAX_TERMS) && public_sum_mac_ok(2048, PUBLIC_MAX_TERMS) &&
+                  (!public_sum_mac_ok(1024, 2 * PUBLIC_MAX_TERMS) || !public_sum_mac_ok(2048, 2 * PUBLIC_MAX_TERMS)) &&
+                  (PUBLIC_MAX_TERMS & (PUBLIC_MAX_TERMS - 1)) == 0,
+              "PUBLIC_MAX_TERMS is the largest power of two the MAC bound takes at both ring sizes");
+static_assert((double)PUBLIC_MAX_TERMS * public_forward_bound(11) * (double)NTT_P[1] * (double)NTT_P[1] < 2305843009213693952.0,
+              "the accumulator stays below 2^61");
+static_assert(public_sum_crt_ok(1024, 8, 2048) && !public_sum_crt_ok(1024, 8, 2049) && public_sum_crt_ok(2048, 8, 1024) &&
+                  !public_sum_crt_ok(2048, 8, 1025) && !public_sum_crt_ok(1024, 9, 1) && !public_sum_crt_ok(1024, 0, 1),
+              "CRT bound of a group: the sum of the maxima is held to one polynomial's T");
+
+// One launch of `count` workgroups: workgroup g forms sum_(t < terms) q_(g terms + t) * c_t from the `terms` ring samples at
+// ring[t * 2N] (every workgroup reads the same ones) and the polynomials whose images start at img[(g terms) * 2N].
+// rows / out: as PublicArgs, entry e of workgroup g being row g S + e.  out overlaps no input.
+struct PublicSumArgs {
+    int32_t N, count, terms;        // terms in 1 .. PUBLIC_MAX_TERMS
+    const int32_t *ring;            // [terms][2N]
+    const uint32_t *img;            // the image of workgroup 0's first polynomial
+    const uint32_t *tw;
+    int32_t *out;
+    RingRows rows;
+};
+// false, and nothing launched, for arguments outside what the kernel was built and bounded for
+bool launch_public_sum(hipStream_t s, const PublicSumArgs &a);
+
 }  // namespace tfhe_hip

@@ -302,3 +302,188 @@ def match_clear_gallery(gallery, probe_ring, M, width, addend, tau, key):
     inner = api.CiphertextArray(params, M)
     api.ring_inner_public(gallery, probe_ring, M, width, key, inner, device=device)
     return _hamming_decision(params, inner, M, width, addend, tau, key)    # (its flush: the device form's probe has been read)
+
+
+# ---- long and masked templates against a CLEAR gallery (include/tfhe_hip.h "public products over several ring samples") ----
+def clear_decision_band(params, delta):
+    """inner_decision_band for any amplitude: the smallest integer g with (g - 1/2) Delta >= 6 sigma_dec, `delta` the torus
+    word of Delta.  The decision of a match whose phase is (1/2 - D) Delta (D an integer: d - tau for a Hamming distance,
+    the masked route's D) is guaranteed only where |D| >= g, and is NOT exact inside the band.  At inner_delta(128) this
+    is inner_decision_band(params, 128) = 12 at P128.  Computed at P128: 184 for long 2,048-bit codes (Delta = 2^-13);
+    5,869 in units of D for masked 2,048-bit codes at 8/25 (Delta = 2^-18), 118 disagreeing bits at full validity."""
+    d = int(delta) / 2.0 ** 32
+    if d <= 0:
+        raise ValueError("Delta must be positive")
+    six = 6.0 * inner_decision_sigma(params)
+    g = max(int(six / d + 0.5) - 1, 1)
+    while (g - 0.5) * d < six:
+        g += 1
+    return g
+
+
+def probe_layout(values, N):
+    """sum_i v_i X^(-i) for integers v_i: p[0] = v_0, p[N - i] = -v_i (hamming_probe_poly for any coefficients) -> int64 [N]"""
+    v = np.asarray(values, dtype=np.int64).reshape(-1)
+    if not 1 <= len(v) <= N:
+        raise ValueError("a probe carries 1..%d coefficients" % N)
+    p = np.zeros(N, dtype=np.int64)
+    p[0] = v[0]
+    p[N - np.arange(1, len(v))] = -v[1:]
+    return p
+
+
+def _long_shape(width, N, terms):
+    if width < 1 or width > N or width & (width - 1):
+        raise ValueError("width must be a power of two in 1..%d" % N)
+    if not 1 <= terms <= api.PUBLIC_MAX_TERMS or terms & (terms - 1):
+        raise ValueError("terms must be a power of two in 1..%d" % api.PUBLIC_MAX_TERMS)
+    return N // width
+
+
+def clear_gallery_polys_long(entries, width, N, terms):
+    """clear_gallery_polys for entries of terms * width bits: S = N / width entries to a GROUP of `terms` polynomials, term t
+    of group i / S holding bits t width .. t width + width - 1 of entry i at coefficients (i mod S) width .. of polynomial
+    (i / S) terms + t -> int32 [R terms][N], R = ceil(M / S) groups."""
+    S = _long_shape(width, N, terms)
+    R = max(-(-len(entries) // S), 1)
+    q = np.zeros((R * terms, N), dtype=np.int32)
+    for i, entry in enumerate(entries):
+        bits = np.asarray([int(b) & 1 for b in entry], dtype=np.int32)
+        if len(bits) != terms * width:
+            raise ValueError("every entry carries %d bits" % (terms * width))
+        for t in range(terms):
+            q[(i // S) * terms + t, (i % S) * width:(i % S + 1) * width] = bits[t * width:(t + 1) * width]
+    return q
+
+
+def hamming_probe_ring_long(bits, width, terms, secret, seed=None):
+    """The client's probe for match_clear_gallery_long: (`terms` ring samples, sample t encrypting sum_i s_i Delta X^(-i) over
+    bits t width .., s_i = 1 - 2 b_i, Delta = 2^-(log2(terms width) + 2) -> int32 [terms][(k+1) N], and a CiphertextArray of
+    ONE sample that encrypts (sum_i b_i) Delta over all terms * width bits).  seed: the reproducible form, sample t from
+    seed + t."""
+    params = secret.params
+    _long_shape(width, params.N, terms)
+    b = np.asarray(bits, dtype=np.int64).reshape(-1) & 1
+    if len(b) != terms * width:
+        raise ValueError("the probe carries %d bits, the gallery's entries %d" % (len(b), terms * width))
+    delta = inner_delta(terms * width)
+    words = np.stack([api.ring_encrypt(probe_layout(1 - 2 * b[t * width:(t + 1) * width], params.N) * delta, secret,
+                                       seed=None if seed is None else seed + t) for t in range(terms)])
+    addend = api.CiphertextArray(params, 1)
+    api.encrypt_torus(addend.at(0), int(b.sum()) * delta, secret)
+    return words, addend
+
+
+def match_clear_gallery_long(gallery, probe_ring, terms, M, width, addend, tau, key):
+    """match_clear_gallery for entries of terms * width bits: `gallery` an api.PublicGallery over clear_gallery_polys_long,
+    `probe_ring` hamming_probe_ring_long's samples (host words, or an int32 torch tensor resident on the device).
+    api.ring_inner_public_sum -- ONE product launch, one key switch per entry --, then the unchanged decision tail with Delta =
+    2^-(log2(terms width) + 2) and the addend sample.  TRUE iff distance <= tau; NOT exact within
+    clear_decision_band(params, inner_delta(terms * width)) of the threshold."""
+    params = gallery.params
+    inner = api.CiphertextArray(params, M)
+    api.ring_inner_public_sum(gallery, probe_ring, terms, M, width, key, inner, device=hasattr(probe_ring, "data_ptr"))
+    return _hamming_decision(params, inner, M, terms * width, addend, tau, key)
+
+
+def masked_delta(den, length):
+    """Delta = 2^-(2 + ceil(log2(den L))) as a torus word: |D| Delta stays below 1/2 for every D of an entry of L bits"""
+    if den < 1 or length < 1 or (den * length - 1).bit_length() > 29:
+        raise ValueError("den L must be in 1..2^29")
+    return 1 << (30 - (int(den) * int(length) - 1).bit_length())
+
+
+def masked_decision(b, g, m, n, num, den):
+    """D = (den - 2 num) valid - den (agree - disagree) over the bits both masks keep, in plain integers: disagree / valid <=
+    num / den iff D <= 0 (D = 2 (den disagree - num valid))"""
+    b, g, m, n = (np.asarray(x, dtype=np.int64).reshape(-1) & 1 for x in (b, g, m, n))
+    return int((den - 2 * num) * (m * n).sum() - den * ((1 - 2 * b) * (1 - 2 * g) * m * n).sum())
+
+
+def _masked_shape(length, width, N, num, den):
+    if width < 1 or width > N or width & (width - 1):
+        raise ValueError("width must be a power of two in 1..%d" % N)
+    if length < width or length % width or 2 * (length // width) > api.PUBLIC_MAX_TERMS:
+        raise ValueError("an entry carries 1..%d chunks of %d bits" % (api.PUBLIC_MAX_TERMS // 2, width))
+    if not 0 < num < den:
+        raise ValueError("the threshold num / den must lie inside (0, 1)")
+    return N // width, length // width
+
+
+def masked_gallery_polys(codes, masks, width, N, num, den):
+    """A masked gallery the server owns in the clear, with the threshold's weights in it: M entries of L = chunks * width
+    code bits g and mask bits n (1 = valid), sigma = 1 - 2 g.  Entry i of group i / S (S = N / width) takes, per chunk c, the
+    TWO polynomials (i / S) terms + 2 c and + 2 c + 1, terms = 2 chunks: -den sigma_j n_j and (den - 2 num) n_j at
+    coefficients (i mod S) width + j -> int32 [R terms][N].  A group's largest coefficients sum to chunks (den + |den - 2
+    num|), which the CRT bound holds to public_max_coef(N)."""
+    codes, masks = np.asarray(codes, dtype=np.int64) & 1, np.asarray(masks, dtype=np.int64) & 1
+    if codes.ndim != 2 or codes.shape != masks.shape:
+        raise ValueError("codes and masks are [M][L] bits of one shape")
+    S, chunks = _masked_shape(codes.shape[1], width, N, num, den)
+    terms = 2 * chunks
+    R = max(-(-len(codes) // S), 1)
+    q = np.zeros((R * terms, N), dtype=np.int32)
+    for i in range(len(codes)):
+        sig_n, n = (1 - 2 * codes[i]) * masks[i], masks[i]
+        for c in range(chunks):
+            at = slice((i % S) * width, (i % S + 1) * width)
+            q[(i // S) * terms + 2 * c, at] = -den * sig_n[c * width:(c + 1) * width]
+            q[(i // S) * terms + 2 * c + 1, at] = (den - 2 * num) * n[c * width:(c + 1) * width]
+    return q
+
+
+def masked_probe_ring(bits, mask, width, num, den, secret, seed=None):
+    """The client's probe for match_clear_gallery_masked: per chunk of `width` bits the TWO ring samples that encrypt s_i m_i
+    Delta and m_i Delta in probe layout (s = 1 - 2 b, m the mask, 1 = valid), Delta = masked_delta(den, L) -> int32
+    [2 chunks][(k+1) N].  There is no addend sample.  seed: the reproducible form, sample t from seed + t."""
+    params = secret.params
+    b, m = (np.asarray(x, dtype=np.int64).reshape(-1) & 1 for x in (bits, mask))
+    if len(b) != len(m):
+        raise ValueError("code and mask carry the same number of bits")
+    _, chunks = _masked_shape(len(b), width, params.N, num, den)
+    delta = masked_delta(den, len(b))
+    polys = []
+    for c in range(chunks):
+        at = slice(c * width, (c + 1) * width)
+        polys += [probe_layout((1 - 2 * b[at]) * m[at], params.N) * delta, probe_layout(m[at], params.N) * delta]
+    return np.stack([api.ring_encrypt(mu, secret, seed=None if seed is None else seed + t) for t, mu in enumerate(polys)])
+
+
+def masked_product_sigma(num, den, valid_bits, bk_stdev):
+    """COMPUTED sigma of D Delta before the key switch (torus units): sum_t |q_t|_2^2 = (den^2 + (den - 2 num)^2) per valid
+    gallery bit, times the probe samples' variance; nothing else"""
+    return ((den ** 2 + (den - 2 * num) ** 2) * valid_bits) ** 0.5 * bk_stdev
+
+
+def masked_weight_gain(num, den):
+    """What applying the weights BEFORE the key switch buys, COMPUTED: the two-product route (valid and agree - disagree as two
+    key-switched inner products, weighted by api.linear afterwards) multiplies the key switch's sigma by sqrt(den^2 +
+    (den - 2 num)^2) -- 26.6 at 8/25 --; here the key switch's sigma enters once."""
+    return float(den ** 2 + (den - 2 * num) ** 2) ** 0.5
+
+
+def match_clear_gallery_masked(gallery, probe_ring, M, width, length, num, den, key):
+    """Masked Hamming 1-to-N at the fractional threshold num / den: `gallery` an api.PublicGallery over masked_gallery_polys,
+    `probe_ring` masked_probe_ring's samples (host words, or an int32 torch tensor resident on the device), `length` the
+    entries' L.  api.ring_inner_public_sum with terms = 2 L / width gives D Delta per entry -- ONE row, one key switch --;
+    then Delta / 2 - D Delta (api.linear, a constant alone, recorded: no addend sample), the LUT bootstrap with the constant
+    1/8 and one flush: what match_clear_gallery costs per entry.  The weights den and den - 2 num are in the gallery
+    polynomials, so they are applied BEFORE the key switch, whose noise then enters once (masked_weight_gain).  Returns a
+    CiphertextArray of M match bits, TRUE iff disagree / valid <= num / den -- NOT exact where |D| <
+    clear_decision_band(params, masked_delta(den, length))."""
+    params = gallery.params
+    _, chunks = _masked_shape(length, width, params.N, num, den)
+    delta = masked_delta(den, length)
+    inner = api.CiphertextArray(params, M)
+    api.ring_inner_public_sum(gallery, probe_ring, 2 * chunks, M, width, key, inner, device=hasattr(probe_ring, "data_ptr"))
+    lin = api.CiphertextArray(params, M)
+    for i in range(M):
+        api.linear(lin.at(i), [inner.at(i)], [-1], delta // 2, key)
+    lut = api.Lut.constant(params, 1 << 29)
+    bits = api.CiphertextArray(params, M)
+    api.lut_bootstrap_batch(lut, bits, [lin], [1], 0, key)
+    api.flush()                                               # (the device form's probe has been read by now)
+    lut.close()
+    for o in (inner, lin):
+        o.close()
+    return bits

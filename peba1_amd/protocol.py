@@ -256,6 +256,48 @@ def run_clear_gallery(params, key, templates, probe, tau, width=128):
         o.close()
 
 
+def run_clear_gallery_long(params, key, templates, probe, tau, width=1024, terms=2):
+    """run_clear_gallery for templates of terms * width bits (identify.match_clear_gallery_long): the gallery is groups of
+    `terms` public polynomials, the client sends `terms` ring samples and the addend; ONE summed product launch, one key
+    switch and one bootstrap per template.  Yields run_inner_product's records, plus the probe's bytes on the wire."""
+    from . import identify
+    gallery = api.PublicGallery(params, identify.clear_gallery_polys_long(templates, width, params.N, terms))    # server
+    ring, addend = identify.hamming_probe_ring_long(probe, width, terms, key)                                    # client, per query
+    bits = identify.match_clear_gallery_long(gallery, ring, terms, len(templates), width, addend, tau, key)
+    got = [int(b) for b in bits.decrypt(key)]                             # client
+    g = identify.clear_decision_band(params, identify.inner_delta(terms * width))
+    for i, t in enumerate(templates):
+        d = sum(int(x) ^ int(y) for x, y in zip(t, probe))
+        yield {"entry": i, "distance": d, "plain": int(d <= tau), "decrypted": got[i], "inside_band": abs(d - tau) < g,
+               "probe_bytes": int(ring.nbytes)}
+    gallery.close()
+    for o in (bits, addend):
+        o.close()
+
+
+def run_masked_clear_gallery(params, key, codes, masks, probe, probe_mask, num, den, width=1024):
+    """Client and server of identify.match_clear_gallery_masked once: the server owns codes and validity masks in the clear,
+    with the threshold num / den folded into its polynomials (masked_gallery_polys); the client sends two ring samples per
+    chunk of `width` bits (masked_probe_ring) and NO addend; the server answers one match bit per template -- one row, one
+    key switch, one bootstrap each.  Yields one record per template: valid and disagreeing bits, D, the plaintext
+    decision, the decrypted one and whether D lies inside the computed band."""
+    from . import identify
+    length = len(probe)
+    gallery = api.PublicGallery(params, identify.masked_gallery_polys(codes, masks, width, params.N, num, den))  # server
+    ring = identify.masked_probe_ring(probe, probe_mask, width, num, den, key)                                   # client, per query
+    bits = identify.match_clear_gallery_masked(gallery, ring, len(codes), width, length, num, den, key)
+    got = [int(b) for b in bits.decrypt(key)]                             # client
+    g = identify.clear_decision_band(params, identify.masked_delta(den, length))
+    for i, (code, mask) in enumerate(zip(codes, masks)):
+        valid = sum(int(m) & int(n) for m, n in zip(probe_mask, mask))
+        disagree = sum((int(x) ^ int(y)) & int(m) & int(n) for x, y, m, n in zip(probe, code, probe_mask, mask))
+        D = identify.masked_decision(probe, code, probe_mask, mask, num, den)
+        yield {"entry": i, "valid": valid, "disagree": disagree, "D": D, "plain": int(den * disagree <= num * valid),
+               "decrypted": got[i], "inside_band": abs(D) < g, "probe_bytes": int(ring.nbytes)}
+    gallery.close()
+    bits.close()
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--nslots", type=int, default=128)
@@ -280,6 +322,12 @@ def parse_args(argv=None):
     ap.add_argument("--clear-gallery", action="store_true",
                     help="--inner-product with the roles exchanged: the server owns the gallery in the clear, the probe travels "
                          "as one seed-compressed ring sample; a ring sample times public polynomials, no TGSW sample")
+    ap.add_argument("--clear-gallery-long", action="store_true",
+                    help="--clear-gallery for 2,048-bit templates: two public polynomials a template, two ring samples a probe, "
+                         "one summed product launch (public products over several ring samples)")
+    ap.add_argument("--masked-clear-gallery", action="store_true",
+                    help="masked 2,048-bit templates at the fractional threshold 8/25 over the bits both masks keep: the weights "
+                         "live in the gallery polynomials, one key switch and one bootstrap a template, no addend sample")
     ap.add_argument("--seeded-selectors", action="store_true",
                     help="index bits and TGSW probes travel as seed-compressed records (a seed and the bodies, half the bytes), "
                          "the masks written on the card; alone: the select, the packed lookup and the inner products in turn; "
@@ -291,6 +339,12 @@ def parse_args(argv=None):
         ap.error("--seeded-selectors takes --compressed-keys with --packed-gallery only")
     if a.seeded_selectors and not 1 <= a.entries <= 1 << 20:
         ap.error("--entries must be in 1..2^20")
+    for flag, on in (("--clear-gallery-long", a.clear_gallery_long), ("--masked-clear-gallery", a.masked_clear_gallery)):
+        if on and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.packed_gallery or a.compressed_keys or a.inner_product or
+                   a.clear_gallery or a.seeded_selectors or (a.clear_gallery_long and a.masked_clear_gallery)):
+            ap.error(flag + " runs alone")
+        if on and not 1 <= a.entries <= 1 << 16:
+            ap.error("--entries must be in 1..2^16")
     if a.clear_gallery and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.packed_gallery or a.compressed_keys or a.inner_product):
         ap.error("--clear-gallery runs alone")
     if a.clear_gallery and not 1 <= a.entries <= 1 << 20:
@@ -349,6 +403,27 @@ def main():
     key = api.SecretKeySet(params, a.seed + 1, device=not a.compressed_keys)
     cloud = shipped_cloud(key) if a.compressed_keys else None
     routes = a.seeded_selectors and not (a.packed_gallery or a.inner_product)      # alone: the three routes in turn
+    if a.clear_gallery_long or a.masked_clear_gallery:
+        import random
+        rnd = random.Random(a.seed)
+        length = 2048
+        probe = [rnd.getrandbits(1) for _ in range(length)]
+        templates = []
+        for i in range(a.entries):                                        # every third template near the probe
+            t = list(probe) if i % 3 == 0 else [rnd.getrandbits(1) for _ in range(length)]
+            for j in rnd.sample(range(length), (97 * i) % 397):
+                t[j] ^= 1
+            templates.append(t)
+        if a.clear_gallery_long:
+            outs = run_clear_gallery_long(params, key, templates, probe, tau=655)
+        else:
+            masks = [[int(rnd.random() < 0.85) for _ in range(length)] for _ in range(a.entries)]
+            probe_mask = [int(rnd.random() < 0.9) for _ in range(length)]
+            outs = run_masked_clear_gallery(params, key, templates, masks, probe, probe_mask, num=8, den=25)
+        for out in outs:
+            print(json.dumps(out))
+        key.close()
+        return
     if routes:
         import random
         rnd = random.Random(a.seed)
