@@ -1088,7 +1088,10 @@ int tfhe_hip_kernel_ring_cmux_rotate(const TfheHipSelector *selector, int32_t bi
  * ONE kernel launch of R workgroups; the key switch is the unpack's.
  * Variance of result[i], to first order -- COMPUTED from the definition, not measured (torus units):
  *     key term       (k+1) l N E[dig^2] bk_stdev^2,  E[dig^2] = Bg^2 / 12 for uniform digits
- *     rounding term  (1 + k N) |p|_2^2 eps^2 / 3,  eps = 2^-(l Bgbit + 1)
+ *     rounding term  (1 + k N) |p|_2^2 eps^2 / 3,  eps = 2^-(l Bgbit + 1) -- FOR PROBE COEFFICIENTS OF RANDOM SIGNS: the exact
+ *                    weight is E_S[|p|_2^2 + |p S|_2^2], which coefficients of one sign (a code of all 0 or all 1, long runs)
+ *                    raise to as much as N^3 / 12, 87 times more at w = N ("TGSW products over several ring samples" below,
+ *                    peba1_amd.identify.probe_rounding_weight)
  *     input term     |p|_2^2 times the ring sample's variance (bk_stdev^2 for a fresh one)
  *     the unpack's key-switch term, N t ks_stdev^2 + (N / 2) prec^2 / 3
  * P128, w = 128, s_i = +-1 (|p|_2^2 = 128): before the key switch 2.2e-8 (with (Bg/2)^2 in place of E[dig^2], the bound
@@ -1278,8 +1281,8 @@ int tfhe_hip_test_public_bounds(int32_t N, int32_t T);
  * P128: long 2,048-bit codes, Delta = 2^-13: g = 184 bits of distance; masked 2,048-bit codes at 8/25, Delta = 2^-18:
  * g = 5,869 in units of D, which is 118 disagreeing bits at full validity (D moves by 2 den = 50 a bit).
  * OUT OF SCOPE: an exact decision inside the band, Euclidean distance, probe hoisting (the K forward transforms of the
- * probe are repeated by every workgroup), the TGSW counterpart (tfhe_hip_ring_inner), multi-key batching, recording these
- * calls in the op graph, libpeba1-dist, k > 1.
+ * probe are repeated by every workgroup), multi-key batching, recording these calls in the op graph, libpeba1-dist, k > 1.
+ * (The TGSW counterpart, for galleries that rest encrypted, is tfhe_hip_ring_inner_sum below.)
  *
  * Return 0, or -1 with tfhe_hip_last_error() set and the call without effect (outputs untouched, results keep values and
  * slots): terms outside 1 .. TFHE_HIP_PUBLIC_MAX_TERMS, a polynomial count that is not a multiple of terms, a group past the
@@ -1310,6 +1313,105 @@ int tfhe_hip_test_public_sum_bounds(int32_t N, int32_t terms, int64_t coef_sum);
  * no table)}: |outputs| / P of the forward transform.  plan25 = make_inv_plan(logn): {nsteps, fan[12], renorm[12]}, and
  * *inv_out its out_bound.  -1 with the error set for other arguments. */
 int tfhe_hip_test_ntt_bounds(int32_t logn, double x0, double *fwd2, int32_t *plan25, double *inv_out);
+
+/* ---- TGSW products over several ring samples: long and masked templates against an ENCRYPTED gallery ----
+ * sum_t G_(b+t) (.) c_(gK+t) over K = `terms` ring samples: tfhe_hip_ring_inner's external product as a matrix-vector
+ * product, for the gallery the server must not see.  The K probe polynomials are K samples of ONE selector (plain or
+ * seed-compressed: no new key material), the gallery is read as groups of K consecutive ring samples.  The sum is taken in
+ * the NTT domain -- per prime K (k+1) l forward transforms into the same two 64-bit accumulators, ONE inverse transform per
+ * output polynomial -- followed by one CRT, one extraction and one key switch, where K calls of tfhe_hip_ring_inner take K
+ * of each and a recorded linear op per entry.  Exactly, in Z[X]/(X^N + 1) mod 2^32:
+ *     out[g] = sum_(t < K) G_(b+t) (.) c_(gK+t),         b = sample_index,
+ * G (.) c as defined for the private selection (the offset decomposition of c, signed digits).  terms = 1 computes the
+ * words of tfhe_hip_ring_inner and tfhe_hip_kernel_ring_product.
+ *
+ * Admissible terms (peba1_amd/csrc/ring_inner_sum.hpp derives both bounds and static_asserts them).
+ * MAC bound.  One accumulator takes 18 rows (N = 1024) or 16 (N = 2048) before its reduction leaves the inverse transform's
+ * 4 P, and a term has (k+1) l rows, 6 at the built-in gadgets.  So the accumulator is FOLDED after every block of 18 (16)
+ * rows: y = acc 2^-32 mod P by one Montgomery reduction, then acc = y (2^32 mod P), the same residue again and below
+ * 0.102 P^2 -- a sixtieth of one row -- so the block lengths stay 18 and 16 and this side sets no limit on K.  A block
+ * boundary may fall inside a term.
+ * CRT bound.  K (k+1) l N (Bg/2) 2^31 < CRT_EXACT_LIMIT: K <= 7 at both built-in gadgets, (3, 7) at N = 1024 and (3, 6) at
+ * N = 2048.  All digits at -Bg/2 against row words 0x80000000 reach the left side exactly.
+ * tfhe_hip_ring_inner_sum_max_terms(params): the largest K both bounds take for that set's gadget, capped at
+ * TFHE_HIP_INNER_MAX_TERMS = 8 -- 7 at both built-in sets; -1 with the error set for a null set or a gadget outside the
+ * CMUX kernel's own two bounds (cmux_gadget_error of peba1_amd/csrc/cmux.hpp).  It does not look at what else
+ * tfhe_hip_new_selector refuses a set for (a set no cloud key is accepted with): no selector exists for such a set.
+ *
+ * Product.  tfhe_hip_ring_mul_tgsw_sum: ring_words [ngroups][terms][(k+1) N], out [ngroups][(k+1) N], 1 <= ngroups <=
+ * 65,536, ONE launch; names no pool slot, completes no flight; the device form (words resident, 16-byte aligned, the
+ * destination apart from the source) returns with the work enqueued on tfhe_hip_stream().
+ * Inner products.  tfhe_hip_ring_inner_sum: the gallery is R groups holding M <= R S entries, S = N / w, R = ceil(M / S);
+ * entry i spans the K samples of group i / S, term t holding its coefficients t w .. t w + w - 1 in the lookup's layout:
+ *     result[i] = KeySwitch(Extract_((i mod S) w)(sum_(t < K) G_(b+t) (.) c_((i / S) K + t)))        for i < M.
+ * Every contract is tfhe_hip_ring_inner's: all arguments are checked before anything changes; a flush in flight is completed
+ * first; every result is renamed into a fresh slot; recorded operations stay recorded; work runs in chunks of at most 8,192
+ * rows; tfhe_hip_last_select_ms covers the launch; TfheHipStats has no new field: the key switches count as `keyswitches`.
+ * Variance before the key switch -- COMPUTED from the definition, not measured -- is the sum over the K terms of
+ * tfhe_hip_ring_inner's three terms (torus units):
+ *     key term       K (k+1) l N E[dig^2] bk_stdev^2
+ *     rounding term  (sum_t W(p_t)) eps^2 / 3,  eps = 2^-(l Bgbit + 1), ON A CENTRED GALLERY,  W(p) = E_S[|p|_2^2 + |p S|_2^2]
+ *     input term     (sum_t |p_t|_2^2) times the ring samples' variance
+ * and the gallery must be centred with tfhe_hip_ring_center_words exactly as for tfhe_hip_ring_inner: without it every
+ * term carries that call's bias.  W(p) over a uniform binary key S is |p|_2^2 (1 + N / 4) + sum_j sigma_j^2 / 4, sigma_j the
+ * signed coefficient sum of p = sum_i v_i X^(-i) split at the wrap of coefficient j.  For coefficients of random signs that is
+ * (1 + N / 2) |p|_2^2, inside the (1 + k N) |p|_2^2 tfhe_hip_ring_inner states.  FOR COEFFICIENTS OF ONE SIGN IT IS NOT: the
+ * mask polynomial m of a masked probe has sigma_j up to its coefficient sum, W = N^3 / 12 = 9.0e7 at 1,024 valid bits against
+ * (1 + N) |p|_2^2 = 1.0e6, sigma 1.3e-3 a polynomial at P128 (peba1_amd.identify.probe_rounding_weight; the masked decrypt
+ * test prints the phase error it sees beside it).  The weights of a masked gallery are in the MESSAGES of the ring samples, so they enter
+ * none of the three terms: the product's noise grows with the probe's |p|_2^2 alone.
+ *
+ * What it is for (peba1_amd.identify).
+ * Long templates: an entry of K w bits against K probe polynomials in probe layout, Delta = 2^-(log2(K w) + 2), the
+ * addend sample and the Hamming decision's tail unchanged (pack_gallery_inner_long, hamming_probe_long,
+ * match_by_inner_long).  A 2,048-bit iris code at P128 is K = 2, w = 1,024: one launch, one key switch and one bootstrap an
+ * entry, where the single-term call needs two of the first two and a linear op.
+ * Masked templates at num / den: the probe is, per chunk, the TWO 0/+-1 polynomials s_i m_i and m_i; the encrypted gallery
+ * holds, per chunk, -den sigma_i n_i Delta and (den - 2 num) n_i Delta (notation of the public sum above).  ONE summed
+ * product is D Delta, D = 2 (den disagree - num valid); the server forms Delta / 2 - D Delta (a constant alone, no addend
+ * sample) and applies the constant-1/8 LUT bootstrap: TRUE iff D <= 0.  The weights are applied before the key switch,
+ * whose sigma enters once -- not times sqrt(den^2 + (den - 2 num)^2) = 26.6 at 8/25 as on the two-product route
+ * (masked_gallery_inner, masked_probe_tgsw, match_by_inner_masked).  2,048 bits at 8/25 are two chunks of 1,024: K = 4.
+ * THE DECISION IS NOT EXACT INSIDE THE BAND: it is guaranteed only for |D| >= g (D = d - tau for a long template), g the
+ * smallest integer with (g - 1/2) Delta >= 6 sigma, sigma^2 = sigma_dec^2 + the variance above at |p_t|_2^2 = N and
+ * (Bg/2)^2 for E[dig^2] (peba1_amd.identify.inner_sum_decision_band, masked_inner_band).  COMPUTED at P128, not measured:
+ * long 2,048-bit codes, Delta = 2^-13, K = 2: g = 185 bits of distance FOR PROBE CODES WHOSE BITS LOOK RANDOM -- the server
+ * cannot see the probe; a client whose code is all 0, all 1 or has long runs has s_i of one sign and takes its band from
+ * the rounding weight of its own probe (identify.hamming_probe_rounding_weight): 206 bits for an all-zero code; masked 2,048-bit codes at 8/25, Delta = 2^-18, K = 4,
+ * the two mask polynomials at W = N^3 / 12: sigma before the key switch 1.9e-3, g = 6,571 in units of D, 132 disagreeing bits
+ * at full validity (D moves by 2 den = 50 a bit) -- against 5,869 for the clear gallery, whose product has no rounding.
+ * OUT OF SCOPE: an exact decision inside the band, probe hoisting, multi-key batching, recording these calls in the op
+ * graph, libpeba1-dist, k > 1.
+ *
+ * Return 0, or -1 with tfhe_hip_last_error() set and the call without effect (outputs untouched, results keep values and
+ * slots): terms outside 1 .. tfhe_hip_ring_inner_sum_max_terms, sample_index + terms past the selector's samples, ngroups
+ * outside 1 .. 65,536, a device destination that overlaps the ring words, and every refusal of tfhe_hip_ring_inner. */
+#define TFHE_HIP_INNER_MAX_TERMS 8
+int32_t tfhe_hip_ring_inner_sum_max_terms(const TFheGateBootstrappingParameterSet *params);
+int tfhe_hip_ring_mul_tgsw_sum(const TfheHipSelector *selector, int32_t sample_index, int32_t terms, int32_t ngroups,
+                               const Torus32 *ring_words, Torus32 *out_ring_words);
+int tfhe_hip_ring_mul_tgsw_sum_device(const TfheHipSelector *selector, int32_t sample_index, int32_t terms, int32_t ngroups,
+                                      const void *device_ring_words, void *device_out);
+int tfhe_hip_ring_inner_sum(const TfheHipSelector *selector, int32_t sample_index, int32_t terms,
+                            const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t M, int32_t width,
+                            LweSample *result);
+int tfhe_hip_ring_inner_sum_device(const TfheHipSelector *selector, int32_t sample_index, int32_t terms,
+                                   const TFheGateBootstrappingCloudKeySet *bk, const void *device_ring_words, int32_t M,
+                                   int32_t width, LweSample *result);
+/* raw test entry: the sums of tfhe_hip_ring_mul_tgsw_sum's host form, after a flush in flight has completed */
+int tfhe_hip_kernel_ring_inner_sum_product(const TfheHipSelector *selector, int32_t sample_index, int32_t terms, int32_t ngroups,
+                                           const Torus32 *ring_words, Torus32 *out_words);
+/* raw test entry: the extracted rows before the key switch, out_rows[i] (kN+1 words) = Extract_((i mod S) width)(the sum of
+ * group i / S) for i < M, (G - 1) S < M <= G S, ring_words [G][terms][(k+1) N]; no slots involved */
+int tfhe_hip_kernel_ring_inner_sum_rows(const TfheHipSelector *selector, int32_t sample_index, int32_t terms,
+                                        const Torus32 *ring_words, int32_t G, int32_t M, int32_t width, Torus32 *out_rows);
+/* host-logic test entry: bit 0 set if `terms` terms of gadget (l, Bgbit) at ring size N fail the MAC bound (the block the
+ * kernel folds after, or the whole sum where it is shorter), bit 1 if they fail the CRT bound; -1 with the error set for N
+ * outside {1024, 2048}, a gadget whose digits do not fit (Bgbit outside 1 .. 12, l Bgbit > 32) or terms outside
+ * 1 .. TFHE_HIP_INNER_MAX_TERMS */
+int tfhe_hip_test_inner_sum_bounds(int32_t N, int32_t l, int32_t Bgbit, int32_t terms);
+/* host-logic test entry: the rows between two folds of the accumulator at ring size N (18, 16); -1 for another N */
+int32_t tfhe_hip_test_inner_sum_block_rows(int32_t N);
 
 /* ---- seed-compressed selectors: index bits and TGSW probes travel as bodies plus one seed ----
  * Half the words of every TGSW row are a uniform public mask.  A record of `count` TGSW samples, 1 <= count <= 20, is

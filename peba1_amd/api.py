@@ -1182,6 +1182,100 @@ def kernel_ring_inner_rows(selector, bit, ring, M, width):
     return u
 
 
+INNER_MAX_TERMS = 8      # TFHE_HIP_INNER_MAX_TERMS (include/tfhe_hip.h)
+
+
+def inner_sum_max_terms(params):
+    """The most terms ring_inner_sum takes under a selector of this parameter set's gadget
+    (tfhe_hip_ring_inner_sum_max_terms): 7 at both built-in sets, from the CRT bound."""
+    k = _l.load().tfhe_hip_ring_inner_sum_max_terms(params.ptr)
+    if k < 0:
+        raise ValueError(last_error())
+    return k
+
+
+def _sum_ring_words(ring, params, terms, groups=None):
+    """host words [groups][terms][(k+1) N] of a gallery read as groups of `terms` ring samples"""
+    a = _ring_words(ring, params)
+    terms = max(int(terms), 1)            # (a term count below 1 is the library's to refuse)
+    if a.shape[0] % terms or (groups is not None and a.shape[0] != groups * terms):
+        raise ValueError("the gallery holds %d ring samples, not %sgroups of %d" % (a.shape[0], "" if groups is None else "%d " % groups, terms))
+    return a
+
+
+def ring_mul_tgsw_sum(selector, sample, terms, ring, ngroups=None, device=False):
+    """sum_t G_(sample + t) (.) c_(g terms + t) for g < ngroups (tfhe_hip_ring_mul_tgsw_sum): `ring` holds ngroups groups of
+    `terms` ring samples (host words [ngroups terms][(k+1) N], or an int32 torch tensor resident on the device), the
+    selector's samples sample .. sample + terms - 1 are TGSW samples; ONE launch.  Returns the sums [ngroups][(k+1) N]: a
+    numpy array, or a device tensor for the device form (which returns with the work enqueued)."""
+    p = selector.params
+    sw = (p.k + 1) * p.N
+    terms = int(terms)
+    L = _l.load()
+    if device:
+        import torch
+        if ring.dtype != torch.int32 or not ring.is_contiguous() or terms < 1 or ring.numel() % (terms * sw):
+            raise ValueError("a device gallery is a contiguous int32 tensor of groups of %d (k+1) N words" % terms)
+        ngroups = ring.numel() // (terms * sw) if ngroups is None else int(ngroups)
+        if ngroups * terms * sw > ring.numel():
+            raise ValueError("ngroups runs past the gallery")
+        out = torch.empty((ngroups, sw), dtype=torch.int32, device=ring.device)
+        rc = L.tfhe_hip_ring_mul_tgsw_sum_device(selector.ptr, int(sample), terms, ngroups, C.c_void_p(ring.data_ptr()), C.c_void_p(out.data_ptr()))
+    else:
+        a = _sum_ring_words(ring, p, terms, ngroups)
+        ngroups = a.shape[0] // max(terms, 1)
+        out = np.zeros((ngroups, sw), dtype=np.int32)
+        rc = L.tfhe_hip_ring_mul_tgsw_sum(selector.ptr, int(sample), terms, ngroups, _i32p(a), _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def ring_inner_sum(selector, sample, terms, gallery, M, width, key, result, first=0, device=False):
+    """ring_inner over groups of `terms` ring samples (tfhe_hip_ring_inner_sum): entry i < M of the gallery spans the `terms`
+    samples of group i / S (S = N / width), and result[first + i] receives, in a fresh slot, the key switch of coefficient
+    (i mod S) width of sum_t G_(sample + t) (.) c_((i / S) terms + t) -- ONE product launch, one key switch per entry.
+    Host and device forms of the gallery as for ring_inner."""
+    p = selector.params
+    sw = (p.k + 1) * p.N
+    G = lookup_samples(p, M, width)
+    terms = int(terms)
+    L = _l.load()
+    if device:
+        import torch
+        if gallery.dtype != torch.int32 or not gallery.is_contiguous() or gallery.numel() != G * terms * sw:
+            raise ValueError("a device gallery of %d entries is a contiguous int32 tensor of %d groups of %d (k+1) N words" % (M, G, terms))
+        rc = L.tfhe_hip_ring_inner_sum_device(selector.ptr, int(sample), terms, key.cloud, C.c_void_p(gallery.data_ptr()), int(M), int(width),
+                                              result.at(first))
+    else:
+        g = _sum_ring_words(gallery, p, terms, G)
+        rc = L.tfhe_hip_ring_inner_sum(selector.ptr, int(sample), terms, key.cloud, _i32p(g), int(M), int(width), result.at(first))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def kernel_ring_inner_sum_product(selector, sample, terms, ring):
+    """ring_mul_tgsw_sum's host form through the raw test entry (tfhe_hip_kernel_ring_inner_sum_product)."""
+    a = _sum_ring_words(ring, selector.params, terms)
+    ngroups = a.shape[0] // max(int(terms), 1)
+    out = np.zeros((ngroups, a.shape[1]), dtype=np.int32)
+    if _l.load().tfhe_hip_kernel_ring_inner_sum_product(selector.ptr, int(sample), int(terms), ngroups, _i32p(a), _i32p(out)) != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def kernel_ring_inner_sum_rows(selector, sample, terms, ring, M, width):
+    """The rows ring_inner_sum key-switches, before the key switch (tfhe_hip_kernel_ring_inner_sum_rows): int32 [M][kN+1]."""
+    p = selector.params
+    a = _sum_ring_words(ring, p, terms)
+    u = np.zeros((int(M), p.k * p.N + 1), dtype=np.int32)
+    if _l.load().tfhe_hip_kernel_ring_inner_sum_rows(selector.ptr, int(sample), int(terms), _i32p(a), a.shape[0] // max(int(terms), 1), int(M), int(width),
+                                                     _i32p(u)) != 0:
+        raise RuntimeError(last_error())
+    return u
+
+
 def public_max_coef(N):
     """T = TFHE_HIP_PUBLIC_MAX_COEF(N): the largest coefficient magnitude of a public polynomial (2^11 at N = 1024, 2^10
     at N = 2048; include/tfhe_hip.h)"""

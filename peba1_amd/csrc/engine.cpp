@@ -1562,6 +1562,62 @@ void Engine::run_inner(const RingImage *sel, const Params &p, int bit, const Dev
     finish(wait || !ring_on_device, "ring inner");
 }
 
+// ---- sums of TGSW products over several ring samples (ring_inner_sum.hpp, ring_inner_sum.hip) ----
+static InnerSumArgs inner_sum_args(const RingImage *sel, const Params &p, int bit, int terms) {
+    InnerSumArgs x{cmux_args(sel, p), terms, inner_sum_block_rows(p.N), RingRows{}};
+    x.c.bit = bit; x.c.stride = (int64_t)terms * (p.k + 1) * p.N;
+    return x;
+}
+
+void Engine::run_inner_sum_mul(const RingImage *sel, const Params &p, int bit, int terms, const Torus32 *ring, int G, bool on_device,
+                               Torus32 *out) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t sw = (size_t)(p.k + 1) * p.N;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    int32_t *dring = on_device ? nullptr : scratch_as<int32_t>(S_SELECT_RING, (size_t)G * terms * sw);
+    int32_t *dout = on_device ? out : scratch_as<int32_t>(S_SELECT_A, (size_t)G * sw);
+    ensure_select_events();
+    if (!on_device) h2d(dring, ring, (size_t)G * terms * sw, "upload ring words");
+    InnerSumArgs x = inner_sum_args(sel, p, bit, terms);
+    x.c.d0 = on_device ? ring : dring; x.c.count = G; x.c.out = dout;
+    if (kernel_timing) hip_check(hipEventRecord(select_e0_, stream_), "select event");
+    if (!launch_inner_sum(stream_, x)) api_fail("ring mul tgsw sum: arguments outside what the kernel was built for");
+    hip_check(hipGetLastError(), "ring mul tgsw sum launch");
+    if (kernel_timing) hip_check(hipEventRecord(select_e1_, stream_), "select event");
+    select_timed_ = kernel_timing;
+    if (!on_device) d2h(out, dout, (size_t)G * sw, "download product words");
+    finish(!on_device, "ring mul tgsw sum");
+}
+
+void Engine::run_inner_sum(const RingImage *sel, const Params &p, int bit, int terms, const DeviceKeyImage *key, const Torus32 *ring, int G,
+                           bool ring_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t gw = (size_t)terms * (p.k + 1) * p.N;
+    const int S = p.N / width;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    int32_t *dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_SELECT_RING, (size_t)G * gw);
+    const RowsPlan r = size_rows(key, p.u_stride(), M, !u_out);
+    ensure_select_events();
+    if (!ring_on_device) h2d(dring, ring, (size_t)G * gw, "upload ring words");
+    const int32_t *src = ring_on_device ? ring : dring;
+    InnerSumArgs x = inner_sum_args(sel, p, bit, terms);
+    x.rows.width = width; x.rows.u_stride = r.u_stride; x.rows.u_buf = r.u_buf;
+    run_rows(key, r, M, (size_t)p.k * p.N + 1, pool, slots, u_out, "ring inner sum", [&](int done, int cnt) {
+        // a chunk starts on a group: S divides UNPACK_CHUNK (both powers of two, S <= N <= UNPACK_CHUNK)
+        x.c.d0 = src + (size_t)(done / S) * gw; x.c.count = (cnt + S - 1) / S; x.rows.M = cnt;
+        if (kernel_timing && done == 0) hip_check(hipEventRecord(select_e0_, stream_), "select event");
+        if (!launch_inner_sum(stream_, x)) api_fail("ring inner sum: arguments outside what the kernel was built for");
+        hip_check(hipGetLastError(), "ring inner sum launch");
+        if (kernel_timing && done + cnt == M) hip_check(hipEventRecord(select_e1_, stream_), "select event");
+    });
+    select_timed_ = kernel_timing;
+    if (u_out) return;
+    // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
+    finish(wait || !ring_on_device, "ring inner sum");
+}
+
 // ---- ring sample times public polynomials (ring_public.hpp, ring_public.hip) -----------------
 RingImage *Engine::upload_public(int N, const int32_t *polys, int R) {
     ENGINE_DEVICE_SCOPE();

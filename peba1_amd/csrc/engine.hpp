@@ -21,6 +21,7 @@
 #include "expand.hpp"
 #include "ks_matrix.hpp"
 #include "ring_public.hpp"
+#include "ring_inner_sum.hpp"
 #include "../../include/tfhe_hip.h"
 
 // Device image of one cloud key: NTT image of BK, compact KSK, twiddles.
@@ -318,8 +319,8 @@ private:
         S_LWE_INDEX,      // run_lwe_expand: the index list
         S_LWE_SLOTS,      // run_lwe_expand: the slot list
         S_LWE_ROWS,       // raw, run_lwe_expand: the rows of one chunk in place of pool slots
-        S_SELECT_RING,    // run_select, run_inner: the ring words on their way from a host source; run_cmux: the d0 operands
-        S_SELECT_A,       // run_select / run_lookup: the launches 0, 2, ... (ping), tree levels then rotations; run_cmux: the results
+        S_SELECT_RING,    // run_select, run_inner[_sum], run_inner_sum_mul: the ring words on their way from a host source; run_cmux: the d0 operands
+        S_SELECT_A,       // run_select / run_lookup: the launches 0, 2, ... (ping), tree levels then rotations; run_cmux: the results; run_inner_sum_mul: the sums on their way to a host destination
         S_SELECT_B,       // run_select / run_lookup: the launches 1, 3, ... (pong)
         S_CMUX_D1,        // raw, run_cmux: the d1 operands
         S_PUBLIC_RING,    // run_public[_sum]_mul, run_public[_sum]_inner: the ring words on their way from a host source
@@ -425,6 +426,17 @@ public:
     void run_inner(const RingImage *sel, const Params &p, int bit, const DeviceKeyImage *key, const Torus32 *ring, int R,
                    bool ring_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, Torus32 *prod_out,
                    bool wait);
+    // Sums of TGSW products over `terms` ring samples (ring_inner_sum.hpp InnerSumArgs; include/tfhe_hip.h "TGSW products
+    // over several ring samples"): `ring` holds G groups of `terms` samples, group g under the selector samples bit ..
+    // bit + terms - 1.  run_inner_sum_mul: out[g] = sum_t G_(bit + t) (.) c_(g terms + t) for g < G in ONE launch, enqueued
+    // behind whatever is on the stream; names no pool slot; a host source or destination makes the call return with the
+    // words in place.  run_inner_sum: run_inner over groups -- entry i < M is the row Extract_((i mod S) width)(sum of group
+    // i / S), (G - 1) S < M <= G S, a further row maker for run_rows: the same chunks, the same key-switch plans, the slot
+    // form and the raw form u_out.  The caller has checked every argument (terms against inner_sum_max_terms among them).
+    void run_inner_sum_mul(const RingImage *sel, const Params &p, int bit, int terms, const Torus32 *ring, int G, bool on_device,
+                           Torus32 *out);
+    void run_inner_sum(const RingImage *sel, const Params &p, int bit, int terms, const DeviceKeyImage *key, const Torus32 *ring, int G,
+                       bool ring_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait);
     // the launches of the last run_select / run_lookup between two stream events (kernel timing on; waits for the second), else -1;
     // after a run_inner: from its first product launch to its last (ONE launch up to UNPACK_CHUNK rows)
     double last_select_ms();
@@ -474,7 +486,7 @@ private:
     DeviceBuf<uint32_t> upload_twiddles(int N, const char *what);
     template <class Drop> void free_image(bool made, const char *what, Drop &&drop);
     template <class Src> size_t read_back(size_t words, Torus32 *out, size_t capacity, const char *what, Src &&src);
-    // what run_unpack, run_inner, run_public_inner and run_public_sum_inner share (engine.cpp): the buffers and key-switch plans of `count` rows, then the chunks
+    // what run_unpack, run_inner, run_inner_sum, run_public_inner and run_public_sum_inner share (engine.cpp): the buffers and key-switch plans of `count` rows, then the chunks
     struct RowsPlan { int widest = 0, u_stride = 0; KsDesc *dks = nullptr; int32_t *u_buf = nullptr; KsLaunchPlan ks_wide, ks_last; };
     RowsPlan size_rows(const DeviceKeyImage *key, int u_stride, int count, bool to_slots);
     template <class MakeRows>

@@ -55,27 +55,6 @@ int tgsw_encrypt_impl(const char *who, const TFheGateBootstrappingSecretKeySet *
     return 0;
 }
 
-const TfheHipSelector *selector_checked(const std::string &w, const TfheHipSelector *sel) {
-    if (!sel || sel->magic != SELECT_MAGIC) api_fail(w + "null or deleted selector");
-    return sel;
-}
-
-// the selector's image, made at first use (under the recorder lock); null for a selector of no bits
-const RingImage *select_image(const TfheHipSelector *csel) {
-    auto *sel = const_cast<TfheHipSelector *>(csel);
-    if (sel->img || sel->nbits < 1) return sel->img;
-    const int64_t body_bytes = (int64_t)sel->nbits * sel->p.kpl() * sel->p.N * 4;
-    if (sel->mask_seed.empty()) {
-        sel->img = Engine::get().upload_selector(sel->p, sel->words.data(), sel->nbits);
-        sel->upload_bytes = body_bytes * (sel->p.k + 1);
-    } else {
-        // a compressed selector: the bodies go up, the masks are written on the card (expand.hip)
-        sel->img = Engine::get().upload_selector_seeded(sel->p, sel->mask_seed.data(), sel->body.data(), sel->nbits);
-        sel->upload_bytes = body_bytes;
-    }
-    return sel->img;
-}
-
 int select_impl(const char *who, const TfheHipSelector *sel, const Torus32 *ring, int32_t M, Torus32 *out, bool on_device) {
     const std::string w = std::string(who) + ": ";
     selector_checked(w, sel);
@@ -180,6 +159,26 @@ TfheHipSelector *tfhe_hip::new_selector_object(const std::string &w, const TFheG
     return new TfheHipSelector{SELECT_MAGIC, p, nbits, std::vector<Torus32>(), nullptr, std::vector<uint32_t>(), std::vector<Torus32>(), 0};
 }
 bool tfhe_hip::selector_ok(const TfheHipSelector *sel) { return sel && sel->magic == SELECT_MAGIC; }
+const TfheHipSelector *tfhe_hip::selector_checked(const std::string &w, const TfheHipSelector *sel) {
+    if (!sel || sel->magic != SELECT_MAGIC) api_fail(w + "null or deleted selector");
+    return sel;
+}
+
+// the selector's image, made at first use (under the recorder lock); null for a selector of no bits
+const RingImage *tfhe_hip::select_image(const TfheHipSelector *csel) {
+    auto *sel = const_cast<TfheHipSelector *>(csel);
+    if (sel->img || sel->nbits < 1) return sel->img;
+    const int64_t body_bytes = (int64_t)sel->nbits * sel->p.kpl() * sel->p.N * 4;
+    if (sel->mask_seed.empty()) {
+        sel->img = Engine::get().upload_selector(sel->p, sel->words.data(), sel->nbits);
+        sel->upload_bytes = body_bytes * (sel->p.k + 1);
+    } else {
+        // a compressed selector: the bodies go up, the masks are written on the card (expand.hip)
+        sel->img = Engine::get().upload_selector_seeded(sel->p, sel->mask_seed.data(), sel->body.data(), sel->nbits);
+        sel->upload_bytes = body_bytes;
+    }
+    return sel->img;
+}
 
 extern "C" {
 

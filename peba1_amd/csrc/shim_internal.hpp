@@ -1,6 +1,6 @@
 // shim_internal.hpp -- what the host entry files share: shim.cpp (the public C ABI) and the files it includes into its
 // object (pack_host.cpp, unpack_host.cpp, select_host.cpp, compressed_host.cpp, seeded_host.cpp, seeded_lwe_host.cpp,
-// test_entries.cpp, recorder.cpp), and the host files that are objects of their own (public_host.cpp, seeded_select_host.cpp).  The object stays one because build.sh is one of the files kernels_sha16 hashes
+// test_entries.cpp, recorder.cpp), and the host files that are objects of their own (public_host.cpp, seeded_select_host.cpp, inner_sum_host.cpp).  The object stays one because build.sh is one of the files kernels_sha16 hashes
 // (kernel_id.py); every one of those files includes this header and whatever else it uses, and parses on its own
 // (tests/test_host_sources_cpu.py), so the order of the include lines at the end of shim.cpp means nothing.
 // Each cross-file function is defined in the file named above its declaration.
@@ -202,6 +202,9 @@ void expand_packing_rows_host(const Params &p, int t, const uint32_t seed10[10],
 // gadget outside the CMUX kernel's two bounds.
 TfheHipSelector *new_selector_object(const std::string &w, const TFheGateBootstrappingParameterSet *params, int32_t nbits);
 bool selector_ok(const TfheHipSelector *sel);       // not null, not deleted
+const TfheHipSelector *selector_checked(const std::string &w, const TfheHipSelector *sel);   // ApiError: null or deleted
+// the selector's image, made at first use (under the recorder lock); null for a selector of no bits
+const RingImage *select_image(const TfheHipSelector *sel);
 
 // ---- unpack_host.cpp ----
 // msg = the N coefficients that encode `count` bits (+-1/8, then zeros); false, the error set, unless count is in 1..N

@@ -400,11 +400,14 @@ def masked_decision(b, g, m, n, num, den):
     return int((den - 2 * num) * (m * n).sum() - den * ((1 - 2 * b) * (1 - 2 * g) * m * n).sum())
 
 
-def _masked_shape(length, width, N, num, den):
+def _masked_shape(length, width, N, num, den, max_terms=None):
+    """(S, chunks) of masked entries of `length` bits in chunks of `width`; max_terms: the most terms the summed product
+    takes, two a chunk (default: the public sum's)"""
+    most = api.PUBLIC_MAX_TERMS if max_terms is None else max_terms
     if width < 1 or width > N or width & (width - 1):
         raise ValueError("width must be a power of two in 1..%d" % N)
-    if length < width or length % width or 2 * (length // width) > api.PUBLIC_MAX_TERMS:
-        raise ValueError("an entry carries 1..%d chunks of %d bits" % (api.PUBLIC_MAX_TERMS // 2, width))
+    if length < width or length % width or 2 * (length // width) > most:
+        raise ValueError("an entry carries 1..%d chunks of %d bits" % (most // 2, width))
     if not 0 < num < den:
         raise ValueError("the threshold num / den must lie inside (0, 1)")
     return N // width, length // width
@@ -462,6 +465,22 @@ def masked_weight_gain(num, den):
     return float(den ** 2 + (den - 2 * num) ** 2) ** 0.5
 
 
+def _masked_decision_tail(params, inner, M, delta, key):
+    """The decision tail match_clear_gallery_masked and match_by_inner_masked share: per entry Delta / 2 - D Delta (api.linear,
+    a constant alone, recorded), the LUT bootstrap with the constant 1/8, one flush.  Closes `inner`."""
+    lin = api.CiphertextArray(params, M)
+    for i in range(M):
+        api.linear(lin.at(i), [inner.at(i)], [-1], delta // 2, key)
+    lut = api.Lut.constant(params, 1 << 29)
+    bits = api.CiphertextArray(params, M)
+    api.lut_bootstrap_batch(lut, bits, [lin], [1], 0, key)
+    api.flush()
+    lut.close()
+    for o in (inner, lin):
+        o.close()
+    return bits
+
+
 def match_clear_gallery_masked(gallery, probe_ring, M, width, length, num, den, key):
     """Masked Hamming 1-to-N at the fractional threshold num / den: `gallery` an api.PublicGallery over masked_gallery_polys,
     `probe_ring` masked_probe_ring's samples (host words, or an int32 torch tensor resident on the device), `length` the
@@ -476,14 +495,224 @@ def match_clear_gallery_masked(gallery, probe_ring, M, width, length, num, den, 
     delta = masked_delta(den, length)
     inner = api.CiphertextArray(params, M)
     api.ring_inner_public_sum(gallery, probe_ring, 2 * chunks, M, width, key, inner, device=hasattr(probe_ring, "data_ptr"))
-    lin = api.CiphertextArray(params, M)
-    for i in range(M):
-        api.linear(lin.at(i), [inner.at(i)], [-1], delta // 2, key)
-    lut = api.Lut.constant(params, 1 << 29)
-    bits = api.CiphertextArray(params, M)
-    api.lut_bootstrap_batch(lut, bits, [lin], [1], 0, key)
-    api.flush()                                               # (the device form's probe has been read by now)
-    lut.close()
-    for o in (inner, lin):
-        o.close()
-    return bits
+    return _masked_decision_tail(params, inner, M, delta, key)          # (its flush: the device form's probe has been read)
+
+
+# ---- long and masked templates against an ENCRYPTED gallery (include/tfhe_hip.h "TGSW products over several ring samples") ----
+def _inner_sum_terms(params, terms):
+    most = api.inner_sum_max_terms(params)
+    if not 1 <= terms <= most:
+        raise ValueError("terms must be in 1..%d for this parameter set" % most)
+
+
+def _long_inner_shape(params, width, terms):
+    N = params.N
+    if width < 1 or width > N or width & (width - 1):
+        raise ValueError("width must be a power of two in 1..%d" % N)
+    _inner_sum_terms(params, terms)
+    if terms & (terms - 1):
+        raise ValueError("terms must be a power of two (Delta = 2^-(log2(terms width) + 2))")
+    return N // width
+
+
+def _encrypt_groups(mu, secret, seed):
+    """ring samples of the torus polynomials mu [R][N], sample r from seed + r, centred for the decomposition"""
+    out = [api.ring_encrypt(m, secret, seed=None if seed is None else seed + r) for r, m in enumerate(mu)]
+    return inner_round_gallery(np.stack(out), secret.params)
+
+
+def pack_gallery_inner_long(entries, width, terms, secret, seed=None):
+    """Enrolment for match_by_inner_long: M entries of terms * width bits, S = N / width entries to a GROUP of `terms` ring
+    samples, term t of group i / S holding bits t width .. t width + width - 1 of entry i at coefficients (i mod S) width ..
+    (the lookup's layout), a bit of 1 at amplitude Delta = 2^-(log2(terms width) + 2); the words are centred for the
+    decomposition (inner_round_gallery).  Returns int32 [R terms][(k+1) N], R = ceil(M / S) groups; seed: the reproducible
+    form, sample r drawn from seed + r."""
+    params = secret.params
+    S = _long_inner_shape(params, width, terms)
+    delta = inner_delta(terms * width)
+    R = max(-(-len(entries) // S), 1)
+    mu = np.zeros((R * terms, params.N), dtype=np.int64)
+    for i, entry in enumerate(entries):
+        bits = np.asarray([int(b) & 1 for b in entry], dtype=np.int64)
+        if len(bits) != terms * width:
+            raise ValueError("every entry carries %d bits" % (terms * width))
+        for t in range(terms):
+            mu[(i // S) * terms + t, (i % S) * width:(i % S + 1) * width] = bits[t * width:(t + 1) * width] * delta
+    return _encrypt_groups(mu, secret, seed)
+
+
+def hamming_probe_long_polys(bits, width, terms, N):
+    """the `terms` probe polynomials of hamming_probe_long: polynomial t is sum_i s_i X^(-i) over bits t width .. -> int32 [terms][N]"""
+    b = np.asarray(bits, dtype=np.int64).reshape(-1) & 1
+    if len(b) != terms * width:
+        raise ValueError("the probe carries %d bits, the gallery's entries %d" % (len(b), terms * width))
+    return np.stack([probe_layout(1 - 2 * b[t * width:(t + 1) * width], N) for t in range(terms)]).astype(np.int32)
+
+
+def hamming_probe_rounding_weight(bits, width, terms, N):
+    """sum_t probe_rounding_weight of the `terms` probe polynomials of a code: what the client puts into
+    inner_sum_decision_band for the band of ITS probe (random-looking codes stay inside the default (1 + N) terms width)"""
+    b = np.asarray(bits, dtype=np.int64).reshape(-1) & 1
+    if len(b) != terms * width:
+        raise ValueError("the probe carries %d bits, the gallery's entries %d" % (len(b), terms * width))
+    return sum(probe_rounding_weight(1 - 2 * b[t * width:(t + 1) * width], N) for t in range(terms))
+
+
+def hamming_probe_long(bits, width, terms, secret, compressed=False, seed=None):
+    """The client's probe for match_by_inner_long: (the TGSW words of the `terms` polynomials sum_i (1 - 2 b_i) X^(-i), one per
+    chunk of `width` bits, as ONE selector record -- plain words for api.Selector, or with compressed=True one
+    seed-compressed record for api.Selector.from_compressed --, and a CiphertextArray of ONE sample that encrypts (sum_i b_i)
+    Delta over all terms * width bits, Delta = 2^-(log2(terms width) + 2)).  seed: the reproducible TGSW form."""
+    params = secret.params
+    _long_inner_shape(params, width, terms)
+    polys = hamming_probe_long_polys(bits, width, terms, params.N)
+    encrypt = api.tgsw_encrypt_polys_compressed if compressed else api.tgsw_encrypt_polys
+    words = encrypt(polys, secret, seed=seed)
+    addend = api.CiphertextArray(params, 1)
+    api.encrypt_torus(addend.at(0), int((np.asarray(bits, dtype=np.int64).reshape(-1) & 1).sum()) * inner_delta(terms * width), secret)
+    return words, addend
+
+
+def match_by_inner_long(selector, gallery, terms, M, width, addend, tau, key, sample=0):
+    """match_by_inner for entries of terms * width bits: `selector` holds hamming_probe_long's `terms` samples from `sample`
+    on, `gallery` is pack_gallery_inner_long's groups (host words, or an int32 torch tensor resident on the device).
+    api.ring_inner_sum -- ONE product launch, one key switch per entry --, then the unchanged decision tail with Delta =
+    2^-(log2(terms width) + 2) and the addend sample.  TRUE iff distance <= tau; NOT exact within
+    inner_sum_decision_band(params, inner_delta(terms * width), terms) of the threshold -- and that band (185 bits at P128 for
+    2,048-bit codes) holds for probe codes whose bits look random.  The server cannot see the probe; a CLIENT whose code is
+    all 0, all 1 or has long runs has s_i of one sign, a rounding weight up to N^3 / 12 a polynomial instead of (1 + N) w, and
+    must take the band from inner_sum_decision_band(..., rounding_weight=hamming_probe_rounding_weight(bits, width, terms, N)):
+    206 bits at P128 for an all-zero 2,048-bit code."""
+    params = selector.params
+    inner = api.CiphertextArray(params, M)
+    api.ring_inner_sum(selector, sample, terms, gallery, M, width, key, inner, device=hasattr(gallery, "data_ptr"))
+    return _hamming_decision(params, inner, M, terms * width, addend, tau, key)
+
+
+def _masked_inner_shape(params, length, width, num, den):
+    """_masked_shape under the term cap of this parameter set's gadget (api.inner_sum_max_terms)"""
+    return _masked_shape(length, width, params.N, num, den, max_terms=api.inner_sum_max_terms(params))
+
+
+def masked_gallery_inner(codes, masks, width, num, den, secret, seed=None):
+    """Enrolment for match_by_inner_masked, the threshold's weights in the gallery's MESSAGES: M entries of L = chunks * width
+    code bits g and mask bits n (1 = valid), sigma = 1 - 2 g.  Entry i of group i / S (S = N / width) takes, per chunk c, the
+    TWO ring samples (i / S) terms + 2 c and + 2 c + 1, terms = 2 chunks, encrypting -den sigma_j n_j Delta and
+    (den - 2 num) n_j Delta at coefficients (i mod S) width + j, Delta = masked_delta(den, L); centred for the decomposition.
+    Returns int32 [R terms][(k+1) N]."""
+    params = secret.params
+    codes, masks = np.asarray(codes, dtype=np.int64) & 1, np.asarray(masks, dtype=np.int64) & 1
+    if codes.ndim != 2 or codes.shape != masks.shape:
+        raise ValueError("codes and masks are [M][L] bits of one shape")
+    S, chunks = _masked_inner_shape(params, codes.shape[1], width, num, den)
+    terms, delta = 2 * chunks, masked_delta(den, codes.shape[1])
+    R = max(-(-len(codes) // S), 1)
+    mu = np.zeros((R * terms, params.N), dtype=np.int64)
+    for i in range(len(codes)):
+        sig_n, n = (1 - 2 * codes[i]) * masks[i], masks[i]
+        for c in range(chunks):
+            at = slice((i % S) * width, (i % S + 1) * width)
+            mu[(i // S) * terms + 2 * c, at] = -den * sig_n[c * width:(c + 1) * width] * delta
+            mu[(i // S) * terms + 2 * c + 1, at] = (den - 2 * num) * n[c * width:(c + 1) * width] * delta
+    return _encrypt_groups(mu, secret, seed)
+
+
+def masked_probe_polys(bits, mask, width, N):
+    """the 2 chunks probe polynomials of masked_probe_tgsw: per chunk s_i m_i and m_i in probe layout (0 / +-1) -> int32 [2 chunks][N]"""
+    b, m = (np.asarray(x, dtype=np.int64).reshape(-1) & 1 for x in (bits, mask))
+    if len(b) != len(m) or len(b) % width:
+        raise ValueError("code and mask carry the same number of bits, whole chunks of %d" % width)
+    polys = []
+    for c in range(len(b) // width):
+        at = slice(c * width, (c + 1) * width)
+        polys += [probe_layout((1 - 2 * b[at]) * m[at], N), probe_layout(m[at], N)]
+    return np.stack(polys).astype(np.int32)
+
+
+def masked_probe_tgsw(bits, mask, width, num, den, secret, compressed=False, seed=None):
+    """The client's probe for match_by_inner_masked: per chunk of `width` bits the TGSW samples of the TWO 0 / +-1
+    polynomials s_i m_i and m_i in probe layout (s = 1 - 2 b, m the mask, 1 = valid), as ONE selector record of 2 chunks
+    samples (plain, or seed-compressed).  The amplitude and the weights are the gallery's; there is no addend sample."""
+    params = secret.params
+    _masked_inner_shape(params, len(np.asarray(bits).reshape(-1)), width, num, den)
+    encrypt = api.tgsw_encrypt_polys_compressed if compressed else api.tgsw_encrypt_polys
+    return encrypt(masked_probe_polys(bits, mask, width, params.N), secret, seed=seed)
+
+
+def probe_rounding_weight(values, N):
+    """What the rounding errors of a centred ring sample are multiplied by in a coefficient of p c, p = sum_i v_i X^(-i) the
+    probe polynomial of `values`: E_S[|p|_2^2 + |p S|_2^2] over a uniform binary ring key S (k = 1).  Coefficient j of p S is
+    sum_i +-v_i S[j + i], the sign flipping past the wrap, so E (p S)[j]^2 = |v|^2 / 4 + sigma_j^2 / 4 with sigma_j = sum_(i <
+    N - j) v_i - sum_(i >= N - j) v_i:  weight = |v|^2 (1 + N / 4) + sum_j sigma_j^2 / 4.  For coefficients of random signs
+    sigma_j^2 ~ |v|^2 and the weight is (1 + N / 2) |v|^2, inside the header's (1 + N) |v|^2; for coefficients of ONE sign --
+    the mask polynomial m of a masked probe -- sigma_j grows to |v|_1 and the weight to N^3 / 12 at N valid bits: 87 N |v|^2."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    if not 1 <= len(v) <= N:
+        raise ValueError("a probe carries 1..%d coefficients" % N)
+    head = np.concatenate([[0.0], np.cumsum(v)])                  # head[c] = v_0 + .. + v_(c-1)
+    first = head[np.minimum(N - np.arange(N), len(v))]            # the coefficients that do not wrap at j
+    sigma = 2.0 * first - head[-1]
+    n2 = float((v * v).sum())
+    return n2 * (1.0 + N / 4.0) + float((sigma * sigma).sum()) / 4.0
+
+
+def masked_rounding_weight(width, chunks, N):
+    """the largest rounding weight of a masked probe of `chunks` chunks: per chunk a polynomial s m of random signs, held to
+    the header's (1 + N) width, and a mask polynomial m with every bit valid, probe_rounding_weight of `width` ones"""
+    return chunks * ((1.0 + N) * width + probe_rounding_weight(np.ones(width), N))
+
+
+def inner_sum_product_variance(params, terms, norm2=None, ring_variance=None, rounding_weight=None):
+    """COMPUTED variance of a coefficient of sum_t G_t (.) c_t before the key switch (torus units), the header's three terms
+    summed over `terms` terms with (Bg/2)^2 for E[dig^2]: terms (k+1) l N (Bg/2)^2 bk^2 + W eps^2 / 3 + P v, P the probe's
+    sum_t |p_t|_2^2 (default terms N, the most 0 / +-1 polynomials have), eps = 2^-(l Bgbit + 1) on a centred gallery, v the
+    ring samples' variance (default bk^2, fresh ones), W the rounding weight: (1 + k N) P for probe coefficients of random
+    signs (the default), sum_t probe_rounding_weight(p_t) in general -- far more for polynomials of one sign."""
+    tl = params.ptr.contents.tgsw_params.contents.tlwe_params.contents
+    bk = tl.alpha_min
+    N, k, l = params.N, params.k, params.l
+    P = terms * N if norm2 is None else norm2
+    v = bk ** 2 if ring_variance is None else ring_variance
+    W = (1 + k * N) * P if rounding_weight is None else rounding_weight
+    eps = 2.0 ** -(l * params.Bgbit + 1)
+    return terms * (k + 1) * l * N * (2.0 ** (params.Bgbit - 1)) ** 2 * bk ** 2 + W * eps ** 2 / 3.0 + P * v
+
+
+def inner_sum_decision_band(params, delta, terms, rounding_weight=None):
+    """clear_decision_band with the summed product's own noise in it: the smallest integer g with (g - 1/2) Delta >= 6 sigma,
+    sigma^2 = inner_decision_sigma^2 + inner_sum_product_variance(params, terms, rounding_weight=...) (probe polynomials of
+    norm^2 N, the largest), `delta` the torus word of Delta.  The decision of a match whose phase is (1/2 - D) Delta is
+    guaranteed only where |D| >= g, and is NOT exact inside the band.  rounding_weight: None for probe coefficients of random
+    signs (long templates), masked_rounding_weight for the masked route, whose mask polynomials have one sign.  COMPUTED at
+    P128: 185 for long 2,048-bit codes (Delta = 2^-13, terms = 2); 6,571 in units of D (132 disagreeing bits at full validity) for masked 2,048-bit codes
+    at 8/25 (Delta = 2^-18, terms = 4, masked_rounding_weight(1024, 2, 1024))."""
+    d = int(delta) / 2.0 ** 32
+    if d <= 0:
+        raise ValueError("Delta must be positive")
+    six = 6.0 * (inner_decision_sigma(params) ** 2 + inner_sum_product_variance(params, terms, rounding_weight=rounding_weight)) ** 0.5
+    g = max(int(six / d + 0.5) - 1, 1)
+    while (g - 0.5) * d < six:
+        g += 1
+    return g
+
+
+def masked_inner_band(params, length, width, den):
+    """inner_sum_decision_band of the masked route for entries of `length` bits in chunks of `width`"""
+    chunks = length // width
+    return inner_sum_decision_band(params, masked_delta(den, length), 2 * chunks, masked_rounding_weight(width, chunks, params.N))
+
+
+def match_by_inner_masked(selector, gallery, M, width, length, num, den, key, sample=0):
+    """Masked Hamming 1-to-N at the fractional threshold num / den against an ENCRYPTED gallery: `selector` holds
+    masked_probe_tgsw's 2 L / width samples from `sample` on, `gallery` is masked_gallery_inner's groups (host words, or an
+    int32 torch tensor resident on the device).  api.ring_inner_sum gives D Delta per entry -- ONE row, one key switch --;
+    then Delta / 2 - D Delta (api.linear, a constant alone, recorded: no addend sample), the LUT bootstrap with the constant
+    1/8 and one flush.  The weights are in the gallery's messages, so they are applied BEFORE the key switch, whose noise
+    enters once (masked_weight_gain), and they do not enter the product's noise.  TRUE iff disagree / valid <= num / den --
+    NOT exact where |D| < masked_inner_band(params, length, width, den)."""
+    params = selector.params
+    _, chunks = _masked_inner_shape(params, length, width, num, den)
+    delta = masked_delta(den, length)
+    inner = api.CiphertextArray(params, M)
+    api.ring_inner_sum(selector, sample, 2 * chunks, gallery, M, width, key, inner, device=hasattr(gallery, "data_ptr"))
+    return _masked_decision_tail(params, inner, M, delta, key)          # (its flush: the device form's gallery has been read)

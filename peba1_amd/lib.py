@@ -347,6 +347,15 @@ SIGNATURES = {
     "tfhe_hip_kernel_ring_public_sum_product": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, I32P, I32P]),
     "tfhe_hip_kernel_ring_public_sum_rows": (C.c_int, [C.c_void_p, I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_public_sum_bounds": (C.c_int, [C.c_int32, C.c_int32, C.c_int64]),
+    "tfhe_hip_ring_inner_sum_max_terms": (C.c_int32, [PS]),
+    "tfhe_hip_ring_mul_tgsw_sum": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, I32P, I32P]),
+    "tfhe_hip_ring_mul_tgsw_sum_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "tfhe_hip_ring_inner_sum": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, CK, I32P, C.c_int32, C.c_int32, LS]),
+    "tfhe_hip_ring_inner_sum_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, CK, C.c_void_p, C.c_int32, C.c_int32, LS]),
+    "tfhe_hip_kernel_ring_inner_sum_product": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, I32P, I32P]),
+    "tfhe_hip_kernel_ring_inner_sum_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
+    "tfhe_hip_test_inner_sum_bounds": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tfhe_hip_test_inner_sum_block_rows": (C.c_int32, [C.c_int32]),
     "tfhe_hip_test_ntt_bounds": (C.c_int, [C.c_int32, C.c_double, C.POINTER(C.c_double), I32P, C.POINTER(C.c_double)]),
     "tfhe_hip_tgsw_compressed_words": (C.c_int64, [PS, C.c_int32]),
     "tfhe_hip_tgsw_encrypt_bits_compressed": (C.c_int, [SK, I32P, C.c_int32, I32P]),

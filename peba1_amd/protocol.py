@@ -298,6 +298,50 @@ def run_masked_clear_gallery(params, key, codes, masks, probe, probe_mask, num, 
     bits.close()
 
 
+def run_inner_product_long(params, key, templates, probe, tau, width=1024, terms=2, seeded_selectors=False):
+    """run_inner_product for templates of terms * width bits against an ENCRYPTED gallery (identify.match_by_inner_long): the
+    gallery is enrolled as groups of `terms` ring samples, the client sends the `terms` TGSW probe polynomials as ONE selector
+    record (seed-compressed with seeded_selectors) and the addend; ONE summed product launch, one key switch and one
+    bootstrap per template.  Yields run_inner_product's records."""
+    from . import identify
+    gallery = identify.pack_gallery_inner_long(templates, width, terms, key)                                     # client, at enrolment
+    tgsw, addend = identify.hamming_probe_long(probe, width, terms, key, compressed=seeded_selectors)            # client, per query
+    selector = api.Selector.from_compressed(params, tgsw) if seeded_selectors else api.Selector(params, tgsw)   # server
+    bits = identify.match_by_inner_long(selector, gallery, terms, len(templates), width, addend, tau, key)
+    got = [int(b) for b in bits.decrypt(key)]                             # client
+    g = identify.inner_sum_decision_band(params, identify.inner_delta(terms * width), terms)
+    for i, t in enumerate(templates):
+        d = sum(int(x) ^ int(y) for x, y in zip(t, probe))
+        yield {"entry": i, "distance": d, "plain": int(d <= tau), "decrypted": got[i], "inside_band": abs(d - tau) < g,
+               "probe_bytes": int(tgsw.nbytes), "probe_bytes_plain": 4 * terms * api.tgsw_words(params)}
+    selector.close()
+    for o in (bits, addend):
+        o.close()
+
+
+def run_masked_inner_product(params, key, codes, masks, probe, probe_mask, num, den, width=1024, seeded_selectors=False):
+    """Client and server of identify.match_by_inner_masked once: codes and validity masks are enrolled ENCRYPTED, with the
+    threshold num / den folded into the messages (masked_gallery_inner); the client sends two 0 / +-1 TGSW probe polynomials
+    per chunk of `width` bits as ONE selector record (masked_probe_tgsw) and NO addend; the server answers one match bit per
+    template -- one row, one key switch, one bootstrap each.  Yields run_masked_clear_gallery's records."""
+    from . import identify
+    length = len(probe)
+    gallery = identify.masked_gallery_inner(codes, masks, width, num, den, key)                                  # client, at enrolment
+    tgsw = identify.masked_probe_tgsw(probe, probe_mask, width, num, den, key, compressed=seeded_selectors)      # client, per query
+    selector = api.Selector.from_compressed(params, tgsw) if seeded_selectors else api.Selector(params, tgsw)   # server
+    bits = identify.match_by_inner_masked(selector, gallery, len(codes), width, length, num, den, key)
+    got = [int(b) for b in bits.decrypt(key)]                             # client
+    g = identify.masked_inner_band(params, length, width, den)
+    for i, (code, mask) in enumerate(zip(codes, masks)):
+        valid = sum(int(m) & int(n) for m, n in zip(probe_mask, mask))
+        disagree = sum((int(x) ^ int(y)) & int(m) & int(n) for x, y, m, n in zip(probe, code, probe_mask, mask))
+        D = identify.masked_decision(probe, code, probe_mask, mask, num, den)
+        yield {"entry": i, "valid": valid, "disagree": disagree, "D": D, "plain": int(den * disagree <= num * valid),
+               "decrypted": got[i], "inside_band": abs(D) < g, "probe_bytes": int(tgsw.nbytes)}
+    selector.close()
+    bits.close()
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--nslots", type=int, default=128)
@@ -328,13 +372,28 @@ def parse_args(argv=None):
     ap.add_argument("--masked-clear-gallery", action="store_true",
                     help="masked 2,048-bit templates at the fractional threshold 8/25 over the bits both masks keep: the weights "
                          "live in the gallery polynomials, one key switch and one bootstrap a template, no addend sample")
+    ap.add_argument("--inner-product-long", action="store_true",
+                    help="--inner-product for 2,048-bit templates against an encrypted gallery: two ring samples a template, two "
+                         "TGSW probe polynomials in one selector record, one summed product launch (TGSW products over several "
+                         "ring samples); goes with --seeded-selectors")
+    ap.add_argument("--masked-inner-product", action="store_true",
+                    help="masked 2,048-bit templates at the fractional threshold 8/25 against an encrypted gallery: the weights live "
+                         "in the gallery's messages, four 0/+-1 TGSW probe polynomials, one key switch and one bootstrap a template, "
+                         "no addend sample; goes with --seeded-selectors")
     ap.add_argument("--seeded-selectors", action="store_true",
                     help="index bits and TGSW probes travel as seed-compressed records (a seed and the bodies, half the bytes), "
                          "the masks written on the card; alone: the select, the packed lookup and the inner products in turn; "
                          "with --packed-gallery or --inner-product: that route")
     a = ap.parse_args(argv)
     if a.seeded_selectors and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.clear_gallery):
-        ap.error("--seeded-selectors goes with the select, --packed-gallery and --inner-product only")
+        ap.error("--seeded-selectors goes with the select, --packed-gallery, --inner-product, --inner-product-long and "
+                 "--masked-inner-product only")
+    for flag, on in (("--inner-product-long", a.inner_product_long), ("--masked-inner-product", a.masked_inner_product)):
+        if on and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.packed_gallery or a.compressed_keys or a.inner_product or
+                   a.clear_gallery or a.clear_gallery_long or a.masked_clear_gallery or (a.inner_product_long and a.masked_inner_product)):
+            ap.error(flag + " runs alone or with --seeded-selectors")
+        if on and not 1 <= a.entries <= 1 << 16:
+            ap.error("--entries must be in 1..2^16")
     if a.seeded_selectors and a.compressed_keys and not a.packed_gallery:
         ap.error("--seeded-selectors takes --compressed-keys with --packed-gallery only")
     if a.seeded_selectors and not 1 <= a.entries <= 1 << 20:
@@ -402,8 +461,9 @@ def main():
     params = api.ParameterSet(128)
     key = api.SecretKeySet(params, a.seed + 1, device=not a.compressed_keys)
     cloud = shipped_cloud(key) if a.compressed_keys else None
-    routes = a.seeded_selectors and not (a.packed_gallery or a.inner_product)      # alone: the three routes in turn
-    if a.clear_gallery_long or a.masked_clear_gallery:
+    long_routes = a.inner_product_long or a.masked_inner_product
+    routes = a.seeded_selectors and not (a.packed_gallery or a.inner_product or long_routes)      # alone: the three routes in turn
+    if a.clear_gallery_long or a.masked_clear_gallery or long_routes:
         import random
         rnd = random.Random(a.seed)
         length = 2048
@@ -416,10 +476,15 @@ def main():
             templates.append(t)
         if a.clear_gallery_long:
             outs = run_clear_gallery_long(params, key, templates, probe, tau=655)
+        elif a.inner_product_long:
+            outs = run_inner_product_long(params, key, templates, probe, tau=655, seeded_selectors=a.seeded_selectors)
         else:
             masks = [[int(rnd.random() < 0.85) for _ in range(length)] for _ in range(a.entries)]
             probe_mask = [int(rnd.random() < 0.9) for _ in range(length)]
-            outs = run_masked_clear_gallery(params, key, templates, masks, probe, probe_mask, num=8, den=25)
+            run = run_masked_clear_gallery
+            if a.masked_inner_product:
+                run = lambda *args, **kw: run_masked_inner_product(*args, seeded_selectors=a.seeded_selectors, **kw)    # noqa: E731
+            outs = run(params, key, templates, masks, probe, probe_mask, num=8, den=25)
         for out in outs:
             print(json.dumps(out))
         key.close()
