@@ -1413,6 +1413,74 @@ int tfhe_hip_test_inner_sum_bounds(int32_t N, int32_t l, int32_t Bgbit, int32_t 
 /* host-logic test entry: the rows between two folds of the accumulator at ring size N (18, 16); -1 for another N */
 int32_t tfhe_hip_test_inner_sum_block_rows(int32_t N);
 
+/* ---- ring LUT bootstrap: blind-rotate an ENCRYPTED ring sample by an LWE sample under the cloud key ----
+ * The ring operations above take their control input from the client (TGSW samples, ring samples).  This one takes it from
+ * an LWE sample the SERVER computed -- a gate output, a tfhe_hip_linear combination, a tfhe_hip_lut_bootstrap digit -- and
+ * needs no key material beyond the cloud key: the TFHE paper's other LUT form, a blind rotation whose accumulator starts
+ * from an encrypted ring sample (a packed table, the result of tfhe_hip_pack_samples) in place of a public test polynomial.
+ * The rotation adds the same noise whatever the accumulator starts as, so the budget is the gate bootstrap's plus the
+ * table's own.  The programmable bootstrap with the noiseless table (0, v) is the special case c = (0, v).
+ * Exactly, with k = 1, N = 1,024 or 2,048, c = (a, b) a ring sample of (k+1) N words and (alpha_0 .. alpha_(n-1), beta) an
+ * LWE sample under the cloud key's LWE key:
+ *     abar_i = round(alpha_i 2N / 2^32) mod 2N, bbar = round(beta 2N / 2^32) mod 2N
+ *              -- the modulus switch of the gate path and of tfhe_hip_lut_bootstrap, ((x + 2^(31 - log2(2N))) >> (32 - log2(2N)))
+ *              on the unsigned word (the oracle's orc_modswitch)
+ *     ACC_0     = X^(-bbar) c                                   on both polynomials
+ *     ACC_(i+1) = CMUX(BK_i, X^(abar_i) ACC_i, ACC_i)          for i = 0 .. n - 1
+ *     out       = ACC_n
+ * (X^(-r) c)[u][j] = c[u][(j + r) mod 2N] where that index is below N and -c[u][index - N] from N on, for every r in
+ * [0, 2N): the rotation convention of the private lookup continued past N, where it negates the whole sample; X^(abar) is
+ * X^(-(2N - abar)).  CMUX(G, d1, d0) = d0 + G (.) (d1 - d0) is the external product of the private selection: the same
+ * offset decomposition into signed digits, the same exact negacyclic product mod 2^32, BK_i the rows of the cloud key's
+ * bootstrapping key for LWE index i.  A step with abar_i = 0 is SKIPPED; computed it would leave the same words (the
+ * difference is zero, the digits of the offset alone are zero).  The row of a result is Extract_0(ACC_n) in the layout of
+ * the unpack (a_0 = A[0], a_i = -A[N - i], b = B[0]).
+ *
+ * tfhe_hip_ring_blind_rotate: ring_in holds nring ring samples, rotation j < count turns sample ring_index[j] (NULL: j) by
+ * index_samples[j] -- many samples may rotate one table -- and writes ACC_n to ring_out[j (k+1) N].  ONE launch, one
+ * workgroup a rotation (peba1_amd/csrc/ring_rotate.hip), the cloud key's resident image read as it rests.  The index
+ * samples are LweSamples of this library; if one of them is the result of a recorded operation the recording is flushed
+ * first, otherwise what is recorded stays recorded.  The call names no pool slot of its own and completes no flight.  The
+ * device form (ring words resident, 16-byte aligned, the destination apart from the source) returns with the work enqueued
+ * on tfhe_hip_stream().
+ * tfhe_hip_ring_lut_bootstrap: out[j] = KeySwitch(Extract_0(ACC_n of rotation j)) -- rotation, extraction and the
+ * planner's key switch, in chunks of at most 8,192 rows.  Like the unpack it completes a flush in flight, renames every
+ * result into a fresh slot and, in immediate mode, refreshes the host mirrors; the recording is flushed only if an input
+ * depends on it.  out may be `in`.  TfheHipStats has no new field: the key switches count as `keyswitches`.
+ * tfhe_hip_last_ring_rotate_ms: the rotation launches of the last of these calls between two stream events (waits for the
+ * second); -1 unless kernel timing is on.
+ * Variance of a result's phase -- COMPUTED from the definition, not measured -- is the table sample's own plus the gate
+ * bootstrap's: n CMUX terms ((k+1) l N (Bg/2)^2 bk_stdev^2 + (1 + k N) eps^2 / 3 apiece, eps = 2^-(l Bgbit + 1)), the key
+ * switch's.  In front of them stands the rounding of the modulus switch, which moves the ROTATION, not the phase: each of
+ * the n / 2 + 1 rounded words that count errs uniformly within half a step of 1 / 2N, sigma = sqrt((1 + n / 2) / 12)
+ * coefficients (5.1 at n = 630) on top of the index sample's own noise times 2N -- a table entry must span enough
+ * coefficients for that, exactly as a public LUT's sector must.
+ * OUT OF SCOPE: recording these calls in the op graph, multi-key batching, libpeba1-dist, k > 1, circuit bootstrapping
+ * proper (server-made TGSW samples), any change to the tuned 4- and 8-wave rotation kernels.
+ *
+ * Return 0, or -1 with tfhe_hip_last_error() set and the call without effect, each decided on the host before the device is
+ * looked at: a null argument, count outside 1 .. 65,536, nring < 1, a ring_index outside 0 .. nring - 1 (or, ring_index
+ * NULL, count > nring), a cloud key with k != 1 or N outside {1024, 2048} or a gadget outside the CMUX kernel's two bounds,
+ * samples of another LWE dimension than the cloud key's or of the pool of another ciphertext shape, foreign samples,
+ * device words that are not 16-byte aligned, a device destination that overlaps the ring words. */
+int tfhe_hip_ring_blind_rotate(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_in, int32_t nring,
+                               const int32_t *ring_index, const LweSample *index_samples, int32_t count, Torus32 *ring_out);
+int tfhe_hip_ring_blind_rotate_device(const TFheGateBootstrappingCloudKeySet *bk, const void *device_ring_in, int32_t nring,
+                                      const int32_t *ring_index, const LweSample *index_samples, int32_t count,
+                                      void *device_ring_out);
+int tfhe_hip_ring_lut_bootstrap(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_tables, int32_t ntables,
+                                const int32_t *ring_index, const LweSample *in, int32_t count, LweSample *out);
+int tfhe_hip_ring_lut_bootstrap_device(const TFheGateBootstrappingCloudKeySet *bk, const void *device_ring_tables,
+                                       int32_t ntables, const int32_t *ring_index, const LweSample *in, int32_t count,
+                                       LweSample *out);
+double tfhe_hip_last_ring_rotate_ms(void);
+/* raw test entry: the launch on caller words, after a flush in flight has completed.  ring_words [nring][(k+1) N],
+ * lwe_words [count][n + 1] (rotation j by sample j), ring_index as above.  out_ring_words (or NULL) [count][(k+1) N]: ACC_n;
+ * out_rows (or NULL) [count][kN + 1]: Extract_0(ACC_n) before the key switch, from a launch of its own; no slots involved */
+int tfhe_hip_kernel_ring_rotate(const TFheGateBootstrappingCloudKeySet *bk, const Torus32 *ring_words, int32_t nring,
+                                const int32_t *ring_index, const Torus32 *lwe_words, int32_t count, Torus32 *out_ring_words,
+                                Torus32 *out_rows);
+
 /* ---- seed-compressed selectors: index bits and TGSW probes travel as bodies plus one seed ----
  * Half the words of every TGSW row are a uniform public mask.  A record of `count` TGSW samples, 1 <= count <= 20, is
  * TFHE_HIP_TGSW_COMPRESSED_WORDS(k, l, N, count) = 10 + count (k+1) l N words: the mask seed (ChaCha20 key[8], nonce[2]), then

@@ -1074,6 +1074,89 @@ def kernel_ring_cmux_rotate(selector, bit, rot, d0):
     return out
 
 
+def _ring_index(ring_index, count):
+    if ring_index is None:
+        return None, None
+    idx = np.ascontiguousarray(ring_index, dtype=np.int32).reshape(-1)
+    if len(idx) != count:
+        raise ValueError("ring_index names one ring sample per rotation")
+    return idx, _i32p(idx)
+
+
+def _rotation_tables(tables, p, device):
+    """(pointer argument, the number of ring samples, what keeps the words alive)"""
+    sw = (p.k + 1) * p.N
+    if device:
+        import torch
+        if tables.dtype != torch.int32 or not tables.is_contiguous() or tables.numel() == 0 or tables.numel() % sw:
+            raise ValueError("device ring samples are a contiguous int32 tensor of (k+1) N words each")
+        return C.c_void_p(tables.data_ptr()), tables.numel() // sw, tables
+    t = _ring_words(tables, p)
+    return _i32p(t), t.shape[0], t
+
+
+def ring_blind_rotate(tables, index, key, count=None, ring_index=None, first=0, device=False):
+    """The blind rotation of encrypted ring samples by LWE samples (tfhe_hip_ring_blind_rotate): rotation j < count turns
+    ring sample ring_index[j] (None: j) of `tables` [nring][(k+1) N] by index[first + j], a sample of a CiphertextArray the
+    server computed, under the cloud key of `key` -> ACC_n of every rotation, int32 [count][(k+1) N] (host), or with
+    device=True (`tables` an int32 torch tensor on the card) a tensor there, the work enqueued.  A recording the index
+    samples depend on is flushed first; otherwise it stays recorded."""
+    p = key.params
+    sw = (p.k + 1) * p.N
+    count = (len(ring_index) if ring_index is not None else index.count - first) if count is None else int(count)
+    keep, idxp = _ring_index(ring_index, count)
+    ptr, nring, alive = _rotation_tables(tables, p, device)
+    L = _l.load()
+    if device:
+        import torch
+        out = torch.empty(max(count, 1) * sw, dtype=torch.int32, device=alive.device)
+        rc = L.tfhe_hip_ring_blind_rotate_device(key.cloud, ptr, nring, idxp, index.at(first), count, C.c_void_p(out.data_ptr()))
+    else:
+        out = np.zeros((max(count, 1), sw), dtype=np.int32)
+        rc = L.tfhe_hip_ring_blind_rotate(key.cloud, ptr, nring, idxp, index.at(first), count, _i32p(out))
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def ring_lut_bootstrap(tables, index, key, result, count=None, ring_index=None, first=0, result_first=0, device=False):
+    """The ring LUT bootstrap (tfhe_hip_ring_lut_bootstrap): result[result_first + j] receives, in a fresh slot, the key
+    switch of Extract_0 of ring sample ring_index[j] (None: j) of `tables` blind-rotated by index[first + j] -- an ENCRYPTED
+    table looked up under an index the server computed.  Host and device forms of the tables as for ring_blind_rotate; the
+    device form returns with the work enqueued.  Operations recorded earlier and not involved stay recorded."""
+    p = key.params
+    count = (len(ring_index) if ring_index is not None else index.count - first) if count is None else int(count)
+    keep, idxp = _ring_index(ring_index, count)
+    ptr, nring, alive = _rotation_tables(tables, p, device)
+    L = _l.load()
+    fn = L.tfhe_hip_ring_lut_bootstrap_device if device else L.tfhe_hip_ring_lut_bootstrap
+    if fn(key.cloud, ptr, nring, idxp, index.at(first), count, result.at(result_first)) != 0:
+        raise RuntimeError(last_error())
+    return result
+
+
+def kernel_ring_rotate(key, tables, lwe, ring_index=None, rows=False):
+    """The raw launch (tfhe_hip_kernel_ring_rotate): ring samples `tables` [nring][(k+1) N] and LWE words `lwe` [count][n + 1],
+    caller words both, rotation j of sample ring_index[j] (None: j) by sample j under the cloud key of `key` -> ACC_n
+    [count][(k+1) N], or with rows=True the rows Extract_0(ACC_n) [count][kN + 1] before the key switch."""
+    p = key.params
+    t = _ring_words(tables, p)
+    w = np.ascontiguousarray(lwe, dtype=np.int32).reshape(-1, p.n + 1)
+    keep, idxp = _ring_index(ring_index, len(w))
+    out = np.zeros((len(w), p.k * p.N + 1 if rows else (p.k + 1) * p.N), dtype=np.int32)
+    rc = _l.load().tfhe_hip_kernel_ring_rotate(key.cloud, _i32p(t), t.shape[0], idxp, _i32p(w), len(w), None if rows else _i32p(out),
+                                               _i32p(out) if rows else None)
+    if rc != 0:
+        raise RuntimeError(last_error())
+    return out
+
+
+def last_ring_rotate_ms():
+    """The rotation launches of the last ring_blind_rotate / ring_lut_bootstrap between two stream events, in ms; -1 unless
+    kernel timing was on."""
+    return _l.load().tfhe_hip_last_ring_rotate_ms()
+
+
 def tgsw_encrypt_polys(polys, key, seed=None):
     """TGSW samples of 1..20 small-integer polynomials [count][N] under the ring key of the secret keyset `key`
     (tfhe_hip_tgsw_encrypt_polys; host only) -> int32 [count][(k+1) l][k+1][N], words a Selector takes like those of bits.

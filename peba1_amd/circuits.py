@@ -245,3 +245,74 @@ def hamming_match_batch(results_b, a, b, nbits, bounds, keys, csa=False):
     if rc < 0:
         raise RuntimeError(api.last_error())
     return rc
+
+
+# ---- tree LUT: a function of two small digits by S + 1 rotations and one pack (include/tfhe_hip.h "ring LUT bootstrap") ----
+def digit_phase(m, S):
+    """The torus word of digit m < S: phase (m + 1/2) / (2 S), the centre of block m on the negacyclic half torus."""
+    return ((2 * int(m) + 1) << 32) // (4 * S)
+
+
+def tree_lut_variance(params, pk_t=None, pk_basebit=None):
+    """COMPUTED variance (torus units) of a tree_lut result's phase: a block value carries one gate bootstrap's output
+    variance V (rotation and key switch, the typical-case formula of the noise tests: digits uniform, E[dig^2] = Bg^2 / 12)
+    and the packing key switch's first-order variance for the N samples of one pack (the header's: n t N E[d^2] bk_stdev^2 +
+    (n / 2) prec^2 / 3); the rotation by x_hi and its key switch add V again: 2 V + pack.  It does not depend on S: the N / S copies of an entry are the SAME sample, so a block is
+    constant, noise included."""
+    tg = params.ptr.contents.tgsw_params.contents
+    ks_stdev, bk = params.ptr.contents.in_out_params.contents.alpha_min, tg.tlwe_params.contents.alpha_min
+    n, N, k, l, Bg = params.n, params.N, params.k, params.l, float(1 << params.Bgbit)
+    eps, delta = 2.0 ** -(l * params.Bgbit + 1), 2.0 ** -(params.ks_t * params.ks_basebit + 1)
+    rot = n * (k + 1) * l * N * (Bg ** 2 / 12) * bk ** 2 + n * (1 + k * N / 2) * eps ** 2 / 3 + (n / 2) * (N * eps) ** 2 / 12
+    ks = k * N * params.ks_t * (1 - 2.0 ** -params.ks_basebit) * ks_stdev ** 2 + k * N / 2 * delta ** 2 / 3
+    t, bb = params.ks_t if pk_t is None else pk_t, params.ks_basebit if pk_basebit is None else pk_basebit
+    base = 2 ** bb
+    pack = n * t * N * ((base - 1) * (2 * base - 1) / 6.0) * bk ** 2 + (n / 2.0) * (2.0 ** -(1 + bb * t)) ** 2 / 3.0
+    return 2 * (rot + ks) + pack
+
+
+def tree_lut(tables, x_hi, x_lo, key, pkey, result=None):
+    """result[i] = tables[hi_i][lo_i] for digits hi_i, lo_i < S carried by the samples x_hi[i], x_lo[i] at digit_phase(m, S)
+    (CiphertextArrays of equal count); `tables` is an S x S integer table of 2-bit output digits v, returned at phase
+    (2 v + 1) / 16.  S a power of two, 2 <= S <= 8.
+      1. S LUT bootstraps of x_lo against the PUBLIC test polynomials of the rows: row h gives tables[h][lo]
+         (api.lut_bootstrap_batch, recorded into one level);
+      2. per i, api.pack of N samples -- N / S COPIES (bootsCOPY: handles, no arithmetic) of each of the S results, so that
+         entry h fills the block of N / S equal coefficients from h N / S -- into ONE ring sample under the packing key `pkey`;
+      3. api.ring_lut_bootstrap of the packed samples by x_hi: the block of hi, extracted and key-switched.
+    S + 1 rotations and one pack per pair of digits.  Noise: tree_lut_variance -- a block is constant (the copies are one
+    sample), each value carrying its bootstrap's variance and the pack's; sigma 4.9e-3 at P128, six of them 0.029 against the half sector 1/16.
+    The other way to fill a block -- packing each result once and multiplying by the public polynomial 1 + X + .. +
+    X^(N/S - 1) -- is NOT built: it needs the results N / S coefficients apart, which a pack of consecutive samples does not
+    give, and it multiplies the results' noise by sqrt(N / S) = 16 at S = 4 (sigma 0.056, six of them far past the half sector)."""
+    params = key.params
+    N, S = params.N, len(tables)
+    if S < 2 or S > 8 or S & (S - 1) or any(len(row) != S for row in tables):
+        raise ValueError("tables is an S x S table, S a power of two in 2..8")
+    if any(not 0 <= int(v) < 4 for row in tables for v in row):
+        raise ValueError("the output digits are 2-bit values")
+    count = x_lo.count
+    if x_hi.count != count:
+        raise ValueError("x_hi and x_lo hold one digit each per lookup")
+    result = api.CiphertextArray(params, count) if result is None else result
+    L = _l.load()
+    luts = [api.Lut(params, np.array([(2 * int(row[j * S // N]) + 1) << 28 for j in range(N)], dtype=np.int64).astype(np.int32))
+            for row in tables]
+    rows = [api.CiphertextArray(params, count) for _ in range(S)]
+    block = api.CiphertextArray(params, N)
+    was = api.get_deferred()
+    api.set_deferred(True)
+    try:
+        for lut, row in zip(luts, rows):
+            api.lut_bootstrap_batch(lut, row, [x_lo], [1], 0, key)
+        packed = np.zeros((count, (params.k + 1) * N), dtype=np.int32)
+        for i in range(count):
+            for j in range(N):
+                L.bootsCOPY(block.at(j), rows[j * S // N].at(i), key.cloud)
+            packed[i] = api.pack(pkey, block, N, key)                     # (its flush runs the S bootstraps at i = 0)
+        api.ring_lut_bootstrap(packed, x_hi, key, result, count=count)
+    finally:
+        api.set_deferred(was)
+        for o in luts + rows + [block]:
+            o.close()
+    return result

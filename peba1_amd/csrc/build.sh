@@ -30,6 +30,8 @@ $HIPCC $KFLAGS -c ring_public.hip -o ring_public.o &
 $HIPCC $KFLAGS -c ring_public_sum.hip -o ring_public_sum.o &
 # sums of TGSW products over several ring samples, likewise (cmux.hip's listings stay what they were)
 $HIPCC $KFLAGS -c ring_inner_sum.hip -o ring_inner_sum.o &
+# the blind rotation of an encrypted ring sample by an LWE sample, likewise (kernels.hip's and cmux.hip's listings stay what they were)
+$HIPCC $KFLAGS -c ring_rotate.hip -o ring_rotate.o &
 # EMIT_KERNEL_ASM=<file>: also the assembly listing of exactly this compile (tools/isa_mix.py counts the instructions of a
 # blind-rotate step from it; __graft_entry__.build() asks for it when profiles/isa_mix.json is stale)
 if [ -n "${EMIT_KERNEL_ASM-}" ]; then
@@ -47,12 +49,14 @@ $CXX $HOSTFLAGS -c public_host.cpp -o public_host.o &
 $CXX $HOSTFLAGS -c seeded_select_host.cpp -o seeded_select_host.o &
 # the host side of ring_inner_sum.hip, likewise
 $CXX $HOSTFLAGS -c inner_sum_host.cpp -o inner_sum_host.o &
-wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n
+# the host side of ring_rotate.hip, likewise
+$CXX $HOSTFLAGS -c ring_rotate_host.cpp -o ring_rotate_host.o &
+wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n; wait -n
 if [ -n "${EXTRA_WAIT-}" ]; then wait -n; fi
 # -Bsymbolic-functions: calls between the library's own exported functions bind inside the library, so
 # another provider of the tfhe API loaded RTLD_GLOBAL in the same process (a CPU tfhe, the tests'
 # plaintext mock) cannot interpose on them
-$HIPCC -shared -Wl,-Bsymbolic-functions -o $OUT kernels.o pack.o unpack.o expand.o cmux.o ks_matrix.o ring_public.o ring_public_sum.o ring_inner_sum.o host_keys.o engine.o shim.o scheduler.o io.o public_host.o seeded_select_host.o inner_sum_host.o
+$HIPCC -shared -Wl,-Bsymbolic-functions -o $OUT kernels.o pack.o unpack.o expand.o cmux.o ks_matrix.o ring_public.o ring_public_sum.o ring_inner_sum.o ring_rotate.o host_keys.o engine.o shim.o scheduler.o io.o public_host.o seeded_select_host.o inner_sum_host.o ring_rotate_host.o
 echo "built $(realpath $OUT)"
 # circuits: calls only the public tfhe API; symbols resolve at load time against
 # whichever provider is loaded first (libtfhe-hip.so, or the tests' plain mock)

@@ -1740,6 +1740,100 @@ void Engine::run_public_sum_inner(const RingImage *g, const Params &p, const Dev
     finish(wait || !probe_on_device, "ring inner public sum");
 }
 
+// ---- ring LUT bootstrap (ring_rotate.hpp, ring_rotate.hip) -------------------------------------
+// every operand buffer of `count` rotations (scratch() may throw: nothing has been enqueued then), and the launch
+// arguments that do not change from chunk to chunk
+Engine::RotateOperands Engine::size_ring_rotate(const DeviceKeyImage *key, int nring, bool ring_on_device, const int32_t *ring_index,
+                                                SlotPool *pool, int count) {
+    const DevParams &dp = key->dp;
+    RotateOperands o{};
+    o.dring = ring_on_device ? nullptr : scratch_as<int32_t>(S_ROTATE_RING, (size_t)nring * 2 * dp.N);
+    o.dindex = ring_index ? scratch_as<int32_t>(S_ROTATE_INDEX, (size_t)count) : nullptr;
+    o.dslots = pool ? scratch_as<int32_t>(S_ROTATE_SLOTS, (size_t)count) : nullptr;
+    o.dlwe = pool ? nullptr : scratch_as<int32_t>(S_ROTATE_LWE, (size_t)count * (dp.n + 1));
+    RingRotateArgs &a = o.a;
+    a.N = dp.N; a.l = dp.l; a.Bgbit = dp.Bgbit; a.n = dp.n; a.offset = dp.decomp_offset;
+    // the cloud key's bootstrapping image and twiddle tables as they rest: nothing is uploaded again
+    a.img = key->bk_img.get(); a.tw = key->tw.get();
+    a.lwe = pool ? pool->data() : o.dlwe;
+    a.lwe_stride = pool ? pool->ct_stride() : dp.n + 1;
+    if (kernel_timing && !rotate_e0_) {
+        hip_check(hipEventCreate(&rotate_e0_), "ring rotate event");
+        hip_check(hipEventCreate(&rotate_e1_), "ring rotate event");
+    }
+    return o;
+}
+
+void Engine::upload_ring_rotate(RotateOperands &o, const DeviceKeyImage *key, const Torus32 *ring, int nring, bool ring_on_device,
+                                const int32_t *ring_index, SlotPool *pool, const int32_t *in_slots, const Torus32 *lwe_words, int count) {
+    const DevParams &dp = key->dp;
+    if (ring_index) h2d_staged(o.dindex, ring_index, (size_t)count, "upload ring index");
+    if (pool) h2d_staged(o.dslots, in_slots, (size_t)count, "upload slot list");
+    else h2d(o.dlwe, lwe_words, (size_t)count * (dp.n + 1), "upload sample words");
+    if (!ring_on_device) h2d(o.dring, ring, (size_t)nring * 2 * dp.N, "upload ring words");
+    o.a.ring = ring_on_device ? ring : o.dring;
+}
+
+void Engine::run_ring_rotate(const DeviceKeyImage *key, const Torus32 *ring, int nring, bool ring_on_device, const int32_t *ring_index,
+                             SlotPool *pool, const int32_t *in_slots, const Torus32 *lwe_words, int count, Torus32 *out,
+                             bool out_on_device) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const size_t out_words = (size_t)count * 2 * key->dp.N;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    RotateOperands o = size_ring_rotate(key, nring, ring_on_device, ring_index, pool, count);
+    int32_t *dout = out_on_device ? out : scratch_as<int32_t>(S_ROTATE_OUT, out_words);
+    upload_ring_rotate(o, key, ring, nring, ring_on_device, ring_index, pool, in_slots, lwe_words, count);
+    o.a.ring_index = o.dindex; o.a.lwe_index = o.dslots; o.a.count = count; o.a.out = dout;
+    if (kernel_timing) hip_check(hipEventRecord(rotate_e0_, stream_), "ring rotate event");
+    if (!launch_ring_rotate(stream_, o.a)) api_fail(std::string("ring rotate: ") + ring_rotate_error(o.a));
+    hip_check(hipGetLastError(), "ring rotate launch");
+    if (kernel_timing) hip_check(hipEventRecord(rotate_e1_, stream_), "ring rotate event");
+    rotate_timed_ = kernel_timing;
+    if (!out_on_device) d2h(out, dout, out_words, "download rotated words");
+    // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
+    finish(!ring_on_device || !out_on_device || !pool, "ring rotate");
+}
+
+void Engine::run_ring_rotate_rows(const DeviceKeyImage *key, const Torus32 *ring, int nring, bool ring_on_device, const int32_t *ring_index,
+                                  SlotPool *pool, const int32_t *in_slots, const Torus32 *lwe_words, int count, const int32_t *out_slots,
+                                  Torus32 *u_out, bool wait) {
+    ENGINE_DEVICE_SCOPE();
+    ensure_init();
+    const DevParams &dp = key->dp;
+    // every buffer first (scratch() may throw: nothing has been enqueued then)
+    RotateOperands o = size_ring_rotate(key, nring, ring_on_device, ring_index, pool, count);
+    const RowsPlan r = size_rows(key, dp.u_stride, count, !u_out);
+    upload_ring_rotate(o, key, ring, nring, ring_on_device, ring_index, pool, in_slots, lwe_words, count);
+    o.a.rows.width = dp.N; o.a.rows.u_stride = r.u_stride; o.a.rows.u_buf = r.u_buf;
+    // (the slot form's results go to the caller's pool, which is the LWE samples' own when they rest in slots)
+    run_rows(key, r, count, (size_t)dp.k * dp.N + 1, pool, out_slots, u_out, "ring rotate rows", [&](int done, int cnt) {
+        o.a.ring_index = o.dindex ? o.dindex + done : nullptr;
+        o.a.lwe_index = o.dslots ? o.dslots + done : nullptr;
+        // without a list rotation j takes sample j: a chunk starts `done` samples on
+        if (!o.dindex) o.a.ring = (ring_on_device ? ring : o.dring) + (size_t)done * 2 * dp.N;
+        if (!o.dslots) o.a.lwe = o.dlwe + (size_t)done * (dp.n + 1);
+        o.a.count = cnt; o.a.rows.M = cnt;
+        if (kernel_timing && done == 0) hip_check(hipEventRecord(rotate_e0_, stream_), "ring rotate event");
+        if (!launch_ring_rotate(stream_, o.a)) api_fail(std::string("ring rotate rows: ") + ring_rotate_error(o.a));
+        hip_check(hipGetLastError(), "ring rotate launch");
+        if (kernel_timing && done + cnt == count) hip_check(hipEventRecord(rotate_e1_, stream_), "ring rotate event");
+    });
+    rotate_timed_ = kernel_timing;
+    if (u_out) return;
+    // (a host source is the caller's pageable memory: its upload is waited for like a host destination)
+    finish(wait || !ring_on_device, "ring rotate rows");
+}
+
+double Engine::last_ring_rotate_ms() {
+    ENGINE_DEVICE_SCOPE();
+    if (!rotate_timed_) return -1.0;
+    wait_event(rotate_e1_, "ring rotate event", sync_deadline_ms, diag_label);
+    float ms = 0.f;
+    hip_check(hipEventElapsedTime(&ms, rotate_e0_, rotate_e1_), "ring rotate event");
+    return ms;
+}
+
 size_t Engine::read_extract_rows(Torus32 *out, size_t capacity) {
     const size_t words = last_extract_words_;                     // (the buffer was sized by that launch: no growth)
     return read_back(words, out, capacity, "extract rows", [&] { return scratch_as<int32_t>(S_UNPACK_EXTRACT, words); });

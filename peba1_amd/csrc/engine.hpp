@@ -22,6 +22,7 @@
 #include "ks_matrix.hpp"
 #include "ring_public.hpp"
 #include "ring_inner_sum.hpp"
+#include "ring_rotate.hpp"
 #include "../../include/tfhe_hip.h"
 
 // Device image of one cloud key: NTT image of BK, compact KSK, twiddles.
@@ -325,6 +326,11 @@ private:
         S_CMUX_D1,        // raw, run_cmux: the d1 operands
         S_PUBLIC_RING,    // run_public[_sum]_mul, run_public[_sum]_inner: the ring words on their way from a host source
         S_PUBLIC_OUT,     // run_public[_sum]_mul: the products on their way to a host destination
+        S_ROTATE_RING,    // run_ring_rotate[_rows]: the ring words on their way from a host source
+        S_ROTATE_INDEX,   // run_ring_rotate[_rows]: the ring index list
+        S_ROTATE_SLOTS,   // run_ring_rotate[_rows]: the slot list of the LWE samples
+        S_ROTATE_LWE,     // raw, run_ring_rotate[_rows]: the caller's LWE words in place of pool slots
+        S_ROTATE_OUT,     // run_ring_rotate: the accumulators on their way to a host destination
     };
     void *scratch(Scratch idx, size_t bytes);
     // the same by element count (and `margin` bytes), and `count` elements between host and device on the engine's stream
@@ -471,6 +477,24 @@ public:
     // a further row maker for run_rows -- the same chunks, the same key-switch plans.
     void run_public_sum_inner(const RingImage *g, const Params &p, const DeviceKeyImage *key, int terms, const Torus32 *probe,
                               bool probe_on_device, int M, int width, SlotPool *pool, const int32_t *slots, Torus32 *u_out, bool wait);
+    // Ring LUT bootstrap (ring_rotate.hpp; include/tfhe_hip.h "ring LUT bootstrap"): rotation j < count blind-rotates ring
+    // sample ring_index[j] (a host list the caller has checked against nring; null: sample j) of `ring` (nring samples: host,
+    // or device memory the caller keeps until the stream has passed) by an LWE sample under `key`, whose bootstrapping image
+    // is read as it rests.  The LWE samples: pool slots in_slots[j] (a host list), or -- pool null -- the caller's host words
+    // lwe_words [count][n + 1].  run_ring_rotate: ONE launch, ACC_n of every rotation to `out` (host or device); names no
+    // pool slot of its own.  run_ring_rotate_rows: a further row maker for run_rows -- the row Extract_0(ACC_n) of every
+    // rotation, one launch per chunk of at most UNPACK_CHUNK rows, the same chunks and key-switch plans as run_unpack: the
+    // slot form (u_out null) key-switches row j into pool slot out_slots[j]; the raw form u_out [count][kN+1] returns the
+    // rows alone.  The caller has checked every argument and, for the slot form, waited for the flight.  Every buffer is
+    // sized before anything is enqueued: an ApiError (device memory exhausted) leaves nothing written.
+    void run_ring_rotate(const DeviceKeyImage *key, const Torus32 *ring, int nring, bool ring_on_device, const int32_t *ring_index,
+                         SlotPool *pool, const int32_t *in_slots, const Torus32 *lwe_words, int count, Torus32 *out, bool out_on_device);
+    void run_ring_rotate_rows(const DeviceKeyImage *key, const Torus32 *ring, int nring, bool ring_on_device, const int32_t *ring_index,
+                              SlotPool *pool, const int32_t *in_slots, const Torus32 *lwe_words, int count, const int32_t *out_slots,
+                              Torus32 *u_out, bool wait);
+    // the rotation launches of the last of those two calls between two stream events (kernel timing on; waits for the
+    // second), else -1
+    double last_ring_rotate_ms();
 private:
     // The one upload path of the transformed images (engine.cpp upload_image).  ImageRows: what an image is made from --
     // `rows` rows of `polys` polynomials, raw at `host`, or with seed10 their bodies alone at `host` (staged: through the
@@ -495,8 +519,17 @@ private:
     void ensure_select_events();                        // kernel timing on: select_e0_ / select_e1_ exist from here on
     hipEvent_t select_e0_ = nullptr, select_e1_ = nullptr;
     bool select_timed_ = false;
+    // what run_ring_rotate and run_ring_rotate_rows share (engine.cpp): the buffers of the operands, and their uploads
+    struct RotateOperands { RingRotateArgs a; int32_t *dring = nullptr, *dindex = nullptr, *dslots = nullptr, *dlwe = nullptr; };
+    RotateOperands size_ring_rotate(const DeviceKeyImage *key, int nring, bool ring_on_device, const int32_t *ring_index, SlotPool *pool,
+                                    int count);
+    void upload_ring_rotate(RotateOperands &o, const DeviceKeyImage *key, const Torus32 *ring, int nring, bool ring_on_device,
+                            const int32_t *ring_index, SlotPool *pool, const int32_t *in_slots, const Torus32 *lwe_words, int count);
     // (behind everything else, as above) prepare_flush's key-switch plan of every (level, key) share of flight_plan_
     std::vector<KsLaunchPlan> flight_ks_plans_;
+    // (likewise) the event pair last_ring_rotate_ms reads, made by the first timed rotation launch
+    hipEvent_t rotate_e0_ = nullptr, rotate_e1_ = nullptr;
+    bool rotate_timed_ = false;
 };
 
 }  // namespace tfhe_hip

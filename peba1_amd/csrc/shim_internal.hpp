@@ -1,6 +1,6 @@
 // shim_internal.hpp -- what the host entry files share: shim.cpp (the public C ABI) and the files it includes into its
 // object (pack_host.cpp, unpack_host.cpp, select_host.cpp, compressed_host.cpp, seeded_host.cpp, seeded_lwe_host.cpp,
-// test_entries.cpp, recorder.cpp), and the host files that are objects of their own (public_host.cpp, seeded_select_host.cpp, inner_sum_host.cpp).  The object stays one because build.sh is one of the files kernels_sha16 hashes
+// test_entries.cpp, recorder.cpp), and the host files that are objects of their own (public_host.cpp, seeded_select_host.cpp, inner_sum_host.cpp, ring_rotate_host.cpp).  The object stays one because build.sh is one of the files kernels_sha16 hashes
 // (kernel_id.py); every one of those files includes this header and whatever else it uses, and parses on its own
 // (tests/test_host_sources_cpu.py), so the order of the include lines at the end of shim.cpp means nothing.
 // Each cross-file function is defined in the file named above its declaration.

@@ -356,6 +356,12 @@ SIGNATURES = {
     "tfhe_hip_kernel_ring_inner_sum_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, I32P, C.c_int32, C.c_int32, C.c_int32, I32P]),
     "tfhe_hip_test_inner_sum_bounds": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "tfhe_hip_test_inner_sum_block_rows": (C.c_int32, [C.c_int32]),
+    "tfhe_hip_ring_blind_rotate": (C.c_int, [CK, I32P, C.c_int32, I32P, LS, C.c_int32, I32P]),
+    "tfhe_hip_ring_blind_rotate_device": (C.c_int, [CK, C.c_void_p, C.c_int32, I32P, LS, C.c_int32, C.c_void_p]),
+    "tfhe_hip_ring_lut_bootstrap": (C.c_int, [CK, I32P, C.c_int32, I32P, LS, C.c_int32, LS]),
+    "tfhe_hip_ring_lut_bootstrap_device": (C.c_int, [CK, C.c_void_p, C.c_int32, I32P, LS, C.c_int32, LS]),
+    "tfhe_hip_last_ring_rotate_ms": (C.c_double, []),
+    "tfhe_hip_kernel_ring_rotate": (C.c_int, [CK, I32P, C.c_int32, I32P, I32P, C.c_int32, I32P, I32P]),
     "tfhe_hip_test_ntt_bounds": (C.c_int, [C.c_int32, C.c_double, C.POINTER(C.c_double), I32P, C.POINTER(C.c_double)]),
     "tfhe_hip_tgsw_compressed_words": (C.c_int64, [PS, C.c_int32]),
     "tfhe_hip_tgsw_encrypt_bits_compressed": (C.c_int, [SK, I32P, C.c_int32, I32P]),

@@ -18,6 +18,7 @@ that follows it.
     python -m peba1_amd.protocol --compressed-keys       # the cloud key travels as a seed and the bodies (10x fewer bytes)
     python -m peba1_amd.protocol --seeded-inputs         # template and sample travel as seed-compressed ring samples
     python -m peba1_amd.protocol --seeded-lwe            # template and sample travel as seed-compressed LWE sample arrays
+    python -m peba1_amd.protocol --ring-lut              # an encrypted 8-entry table under an index the server computed
     python -m peba1_amd.protocol --packed-gallery        # Hamming match of one claimed identity against a packed gallery
     python -m peba1_amd.protocol --seeded-selectors      # select, packed lookup and inner products, the TGSW material seed-compressed
 
@@ -342,6 +343,39 @@ def run_masked_inner_product(params, key, codes, masks, probe, probe_mask, num, 
     bits.close()
 
 
+def run_ring_lut(params, key, table, perm):
+    """An ENCRYPTED 8-entry table of 2-bit values looked up under an index the SERVER computed (include/tfhe_hip.h "ring LUT
+    bootstrap").  Client: the table as ONE ring sample, entry m on the block of N / 8 coefficients from m N / 8 at phase
+    (2 v + 1) / 16, and a 3-bit digit x as a fresh sample at phase (x + 1/2) / 16.  Server: index = perm[x] by a LUT bootstrap
+    of the digit (the server's own public function; the result is an LWE sample it computed, recorded, not flushed), then
+    api.ring_lut_bootstrap of the table by that index -- the call flushes the recording its input depends on.  Client:
+    decrypts the 2-bit value.  Yields one record per digit x = 0 .. 7."""
+    import numpy as np
+    N = params.N
+    mu = np.repeat((2 * np.asarray(table, dtype=np.int64) + 1) << 28, N // 8)
+    mu = (mu - ((mu >> 31) << 32)).astype(np.int32)
+    ring = api.ring_encrypt(mu, key)                                       # client, once: 8 KB
+    xs = api.CiphertextArray(params, 8)
+    for x in range(8):
+        api.encrypt_torus(xs.at(x), (2 * x + 1) << 27, key)                # client, per query
+    lut = api.Lut(params, np.array([(2 * perm[j * 8 // N] + 1) << 27 for j in range(N)], dtype=np.int64).astype(np.int32))
+    index, out = api.CiphertextArray(params, 8), api.CiphertextArray(params, 8)
+    was = api.get_deferred()
+    api.set_deferred(True)
+    try:
+        api.lut_bootstrap_batch(lut, index, [xs], [1], 0, key)             # server: index = perm[x]
+        api.ring_lut_bootstrap(ring.reshape(1, -1), index, key, out, ring_index=[0] * 8)
+    finally:
+        api.set_deferred(was)
+    w = out.words().astype(np.int64)                                       # client
+    ph = (w[:, -1] - (w[:, :-1] % 2 ** 32) @ np.asarray(key.lwe_key(), dtype=np.int64)) % 2 ** 32
+    for x in range(8):
+        yield {"x": x, "index": int(perm[x]), "plain": int(table[perm[x]]), "decrypted": int(ph[x] >> 29), "table_bytes": int(ring.nbytes)}
+    lut.close()
+    for o in (xs, index, out):
+        o.close()
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--nslots", type=int, default=128)
@@ -384,7 +418,14 @@ def parse_args(argv=None):
                     help="index bits and TGSW probes travel as seed-compressed records (a seed and the bodies, half the bytes), "
                          "the masks written on the card; alone: the select, the packed lookup and the inner products in turn; "
                          "with --packed-gallery or --inner-product: that route")
+    ap.add_argument("--ring-lut", action="store_true",
+                    help="an encrypted 8-entry table of 2-bit values looked up under an index the server computed by a LUT "
+                         "bootstrap (ring LUT bootstrap: the blind rotation of an encrypted ring sample by an LWE sample); runs alone")
     a = ap.parse_args(argv)
+    if a.ring_lut and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.packed_gallery or a.compressed_keys or a.inner_product or
+                       a.clear_gallery or a.clear_gallery_long or a.masked_clear_gallery or a.inner_product_long or
+                       a.masked_inner_product or a.seeded_selectors):
+        ap.error("--ring-lut runs alone")
     if a.seeded_selectors and (a.clients or a.seeded_inputs or a.seeded_lwe or a.fast or a.clear_gallery):
         ap.error("--seeded-selectors goes with the select, --packed-gallery, --inner-product, --inner-product-long and "
                  "--masked-inner-product only")
@@ -461,6 +502,16 @@ def main():
     params = api.ParameterSet(128)
     key = api.SecretKeySet(params, a.seed + 1, device=not a.compressed_keys)
     cloud = shipped_cloud(key) if a.compressed_keys else None
+    if a.ring_lut:
+        import random
+        rnd = random.Random(a.seed)
+        table = [rnd.getrandbits(2) for _ in range(8)]
+        perm = list(range(8))
+        rnd.shuffle(perm)
+        for out in run_ring_lut(params, key, table, perm):
+            print(json.dumps(out))
+        key.close()
+        return
     long_routes = a.inner_product_long or a.masked_inner_product
     routes = a.seeded_selectors and not (a.packed_gallery or a.inner_product or long_routes)      # alone: the three routes in turn
     if a.clear_gallery_long or a.masked_clear_gallery or long_routes:
